@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: measures/sec of full MeasureVAE training steps on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload vae|latent]
+    python bench.py --gpus N --steps K --warmup W [--workload vae|latent] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic FolkDB-shaped tokens:
   vae    (headline, BASELINE.json configs[1]): zero_grad -> encoder fwd -> reparameterise -> hierarchical decoder
          fwd (teacher-forcing coin per step, dropout 0.5) -> CE + KL + accuracy -> backward -> [all-reduce of the flat
-         gradient arena over RCCL when N > 1] -> fused Adam.  256 measures PER GPU (weak scaling).
+         gradient arena over RCCL when N > 1] -> fused Adam.  256 measures PER GPU (weak scaling).  Every step of both
+         workloads starts from the seeded weights (one device copy in front of it): same inputs, same results in every run.
   latent (BASELINE.json configs[2] on one GPU, configs[3] on N): frozen MeasureVAE encode of 16 measures -> context
          bi-GRUs -> generator bi-GRU -> Linear -> frozen decode -> CE -> backward -> all-reduce of the 159.6 MB
          LatentRNN arena -> Adam.  128 sequences PER GPU (1024 global at N = 8).
@@ -16,7 +17,10 @@ Launching: with --gpus N > 1 and no WORLD_SIZE in the environment this process o
 code; under torch.distributed.run it is one rank.  --gpus must equal the world size RCCL reports, and N may not exceed
 the visible devices: a mismatch is an error, never a silent 1-GPU number.
 
-Prints ONE JSON line (< 4 KB) on rank 0 (contract in the task brief) carrying
+A plain run sets up, runs W un-timed and exactly K timed steps, checks the persistent kernels' health over them, writes the
+last timed step's outputs with --dump-outputs (dump_outputs) and prints ONE JSON line (< 4 KB) on rank 0: `value` (units per
+second over the K steps, all GPUs), `ms_per_step`, `chain_timeouts` and `slow_waits`.  Everything else is measured only with
+--full, and the line then also carries
   roofline       the kernel with the largest summed time in the step (per-launch HIP-event timing on the launch
                  stream during separate un-timed steps), its algorithmic FLOPs and bytes per launch against the MFMA roof of
                  the pipe it runs on (157.3 TFLOP/s f32-input; kernels on the bf16 pipe through exact three-piece splits:
@@ -24,11 +28,12 @@ Prints ONE JSON line (< 4 KB) on rank 0 (contract in the task brief) carrying
                  committed rocprofv3 PMC pass (profiles/), and the same table for the top kernels;
   cpu_baseline   the oracle's CPU port of the same step on the host cores (bounded sample, best thread count);
   parity_checked one un-timed step at the bench's own batch compared with the oracle (loss, logits, every gradient).
-plus `chain_timeouts`, `slow_waits` (the library's recorder of waits > ~50 us inside persistent kernels, timed region only), the
-timed steps one by one (`first_steps_ms`) and one scalar per secondary workload.  The line is HARD-LIMITED to 4 KB (compact_line;
-round 5's 20 KB line was dropped by the driver): kernel tables, per-step host times, parity detail and workload prose go to
-bench_detail.json beside this file and to stderr.  --warmup W means W: nothing runs in front of it (round 5 primed both branches of
-the teacher-forcing coin; the one-time host work of a kernel's first launch is now done by inet_preload() at trainer construction).
+plus the timed steps one by one (`first_steps_ms`), one scalar per secondary workload and, for N > 1, the cost of the gradient
+exchange (`allreduce_ms_per_step`, `dp`).  `slow_waits` is the library's recorder of waits > ~50 us inside persistent kernels
+(warm-up and timed steps).  The line is HARD-LIMITED to 4 KB (compact_line; round 5's 20 KB line was dropped by the driver): with
+--full, kernel tables, per-step host times, parity detail and workload prose go to bench_detail.json beside this file and to stderr.
+--warmup W means W: nothing runs in front of it (round 5 primed both branches of the teacher-forcing coin; the one-time host work
+of a kernel's first launch is now done by inet_preload() at trainer construction).
 """
 import argparse
 import collections
@@ -264,19 +269,25 @@ class VaeWorkload:
         self.model.train()
         self.tokens = torch.from_numpy(synthetic.det_tokens(f"bench/rank{rank}", (VAE_BATCH_PER_GPU, 24), NUM_NOTES)).to(dev)
         self.arena_mb = self.model.flat.numel() * 4 / 1e6
+        self.start = self.model.flat.detach().clone()
 
     def step(self):
+        # Every step trains the seeded weights (Adam's moments and step count go on): fp32 atomics make one step's results vary
+        # in the last bits from run to run, and training on its own results amplifies that to O(1) in the gradients within ~50
+        # steps -- with the weights restored the step's inputs, and so what it computes, are the same in every run.
+        self.model.flat.copy_(self.start)
         t = self.trainer
         t.zero_grad()
         loss, acc = t.loss_and_acc_for_batch(self.tokens, 0, train=True)
         loss.backward()
         t.step()
+        self.accuracy = acc                                    # (for --dump-outputs)
         return loss
 
     def describe(self, world):
         return {"workload": "MeasureVAE training, synthetic FolkDB-shaped tokens, 256 measures per GPU "
                             "(BASELINE.json configs[1]); V=48,E=10,H=512,Z=256, dropout 0.5, "
-                            "teacher-forcing coin per step, Adam lr=1e-4",
+                            "teacher-forcing coin per step, Adam lr=1e-4, every step from the seeded weights",
                 "batch_per_gpu": VAE_BATCH_PER_GPU, "global_batch": world * VAE_BATCH_PER_GPU,
                 "parallelism": f"dp{world}"}
 
@@ -314,13 +325,16 @@ class LatentWorkload:
         score = torch.from_numpy(synthetic.folk_score(LATENT_SEQ_PER_GPU, NUM_NOTES, seed=9 + rank))
         self.batch = LatentRNNTrainer.split_score(score, 6, 6, 4, 24)
         self.arena_mb = self.model.flat.numel() * 4 / 1e6
+        self.start = self.model.flat.detach().clone()
 
     def step(self):
+        self.model.flat.copy_(self.start)                     # (as VaeWorkload.step)
         t = self.trainer
         t.zero_grad()
         loss, acc = t.loss_and_acc_for_batch(self.batch, 0, train=True)
         loss.backward()
         t.step()
+        self.accuracy = acc
         return loss
 
     def describe(self, world):
@@ -374,6 +388,30 @@ def timed(step, steps, warmup, fence, trace=None):
         trace["gc_in_timed_region"] = {"collections": len(gcs), "generation2": sum(1 for g, _ in gcs if g == 2),
                                        "longest_ms": max([m for _, m in gcs], default=0.0)}
     return dt, loss
+
+
+DUMP_SAMPLE = 1 << 22       # floats per sampled array: two of them are 32 MB, under the dump's 64 MB
+
+
+def dump_outputs(wl, loss, out_dir):
+    """--dump-outputs: what the caller of the timed step holds after the LAST timed step, as DIR/<name>.npy -- the step's loss and
+    accuracy (float32, shape (1,)) and the trainable parameters after its optimizer update and the gradients it computed, both in
+    named_parameters() order and flattened.  Those two hold 17.7 M floats each at the bench's sizes, so the same fixed, seeded
+    sample of DUMP_SAMPLE positions is taken of both (sorted; the whole array when it is smaller).  The inputs (weights, tokens, the
+    seeded draws) depend only on the arguments and every step starts from the seeded weights (VaeWorkload.step), so two runs agree
+    to one step's rounding and two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = [k for k, _ in wl.model.named_parameters()]
+    params = torch.cat([wl.model.param(k).reshape(-1) for k in names])
+    grads = torch.cat([wl.model.param_grad(k).reshape(-1) for k in names])
+    n = params.numel()
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(20240).choice(n, DUMP_SAMPLE, replace=False))
+    idx = torch.from_numpy(idx).to(params.device)
+    arrays = {"loss": loss.detach().reshape(1), "accuracy": wl.accuracy.detach().reshape(1),
+              "params_sample": params[idx], "grads_sample": grads[idx]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def exchange_report(wl, dp, step_s, fence, dev, steps=40):
@@ -947,10 +985,10 @@ def _get(d, *path):
     return d
 
 
-def compact_line(out):
+def compact_line(out, detail=DETAIL_FILE):
     """The ONE stdout line: the contract's keys, the dominant kernel's roofline row, the CPU baseline and one scalar per secondary
     workload -- hard limit LINE_LIMIT bytes (tests/test_bench_keys.py).  Kernel tables, per-step host times, parity detail and
-    workload prose stay in `out`, which main() writes to DETAIL_FILE and stderr."""
+    workload prose stay in `out`, which a --full run writes to `detail` (named in the line) and stderr."""
     ex = out.get("extras") or {}
     cfg = out.get("config") or {}
     line = {k: out.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
@@ -1003,7 +1041,8 @@ def compact_line(out):
     scal = {k: v for k, v in scal.items() if v is not None}
     if scal:
         line["extras"] = scal
-    line["detail"] = os.path.basename(DETAIL_FILE)
+    if detail:
+        line["detail"] = os.path.basename(detail)
     # the limit is hard: optional keys go first, then the config's prose, before a line the driver cannot read is printed
     for drop in ("first_steps_ms", "extras", "dp", "per_rank_units_per_s"):
         if len(json.dumps(line)) < LINE_LIMIT:
@@ -1024,13 +1063,20 @@ def main():
     ap.add_argument("--steps", type=int, default=400)         # >= 2 s of timed GPU work at ~5 ms per step
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=("vae", "latent"), default="vae")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-step trace, roofline, parity check, CPU baseline, secondary workloads, data-parallel "
+                         "exchange figures and the detail file; without it only the timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true")     # --no-*: leave one part out of a --full run
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args, sys.argv[1:]))            # nothing above touched the GPU
@@ -1084,7 +1130,7 @@ def main():
         torch.cuda.synchronize()
 
     try:
-        trace = {}
+        trace = {} if args.full else None
         dt, loss = timed(wl.step, args.steps, args.warmup, fence, trace)
     except ops.ChainTimeoutError as e:
         # raised by Trainer.step() on EVERY rank at the same step (the decision travels with the gradients): all ranks leave
@@ -1119,6 +1165,8 @@ def main():
         if world > 1:
             torch.distributed.destroy_process_group()
         sys.exit(3)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(wl, loss, args.dump_outputs)                # before anything else runs a step on these weights
 
     per_rank = None
     ar_ms = None
@@ -1128,6 +1176,7 @@ def main():
         mine[rank] = wl.units_per_step * args.steps / dt_local
         torch.distributed.all_reduce(mine)
         per_rank = [round(v, 1) for v in mine.tolist()]
+    if world > 1 and args.full:
         ar_ms = allreduce_ms(wl.model.grad)
         dp_report = exchange_report(wl, dp, dt / args.steps, fence, dev)
         dp_report["chain_timeouts_per_rank"] = timeouts_per_rank
@@ -1139,12 +1188,12 @@ def main():
     roof = None
     if rank == 0 and os.environ.get("INET_BENCH_SEQ"):         # tools/profile_r02.sh: launch order of shape-sharing kernels
         dump_kernel_sequences(wl.step, os.environ["INET_BENCH_SEQ"])
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         roof = roofline(wl.step)
     if world > 1:
         torch.distributed.barrier()
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if world > 1 and args.workload == "vae":
             # BASELINE.json configs[3]: the LatentRNN step under the same data-parallel exchange (159.6 MB arena)
             lw = LatentWorkload(dev, rank, vae=wl.model, ds=wl.ds)
@@ -1235,7 +1284,7 @@ def main():
             "slow_wait_entries": slow["entries"][:16],
             # the timed steps one by one (the first 32): GPU time between events behind consecutive steps, host time to queue each,
             # Python garbage collections inside the region -- a cold-start transient shows up HERE (profiles/r05_cold_start.txt)
-            **trace,
+            **(trace or {}),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -1259,7 +1308,7 @@ def main():
             if share_gpu:
                 out["data"] = "synthetic; FUNCTIONAL CHECK ONLY: all ranks share one GPU and gloo carries the exchange"
         cpu = None
-        if world == 1 and args.workload == "vae":
+        if world == 1 and args.workload == "vae" and args.full:
             if not args.no_parity:
                 wl.model.trainable = True
                 out.update(parity_check(wl.model, wl.tokens))
@@ -1267,14 +1316,16 @@ def main():
                 cpu = cpu_baseline(VAE_BATCH_PER_GPU)
         out["cpu_baseline"] = cpu
         out["extras"] = extras or None
-        detail = json.dumps(out)
-        try:
-            with open(DETAIL_FILE, "w") as f:                  # tables, per-step traces, parity detail, workload prose
-                f.write(detail + "\n")
-        except OSError as e:
-            print(f"[bench] could not write {DETAIL_FILE}: {e}", file=sys.stderr)
-        print("[bench detail] " + detail, file=sys.stderr, flush=True)
-        print(compact_line(out), flush=True, file=_REAL_STDOUT)   # the ONE line of the contract (< LINE_LIMIT bytes)
+        if args.full:
+            detail = json.dumps(out)
+            try:
+                with open(DETAIL_FILE, "w") as f:              # tables, per-step traces, parity detail, workload prose
+                    f.write(detail + "\n")
+            except OSError as e:
+                print(f"[bench] could not write {DETAIL_FILE}: {e}", file=sys.stderr)
+            print("[bench detail] " + detail, file=sys.stderr, flush=True)
+        # the ONE line of the contract (< LINE_LIMIT bytes)
+        print(compact_line(out, DETAIL_FILE if args.full else None), flush=True, file=_REAL_STDOUT)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

@@ -159,3 +159,59 @@ def test_multi_gpu_line_and_launcher(bench):
     assert len(line["per_rank_units_per_s"]) == 8 and line["allreduce_ms_per_step"] == 0.4321 and line["allreduce_mbytes"] == 70.7
     assert line["dp"]["exposed_exchange_ms_per_step"] == 0.2 and line["extras"]["latent_dp_ms"] == 10.2
     assert line["cpu_baseline"] is None and line["vs_baseline"] is None
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+class _Model:
+    """The surface dump_outputs reads, on host tensors: named parameters and their gradients."""
+
+    def __init__(self, shapes):
+        import torch
+        n = 0
+        self.p, self.g = {}, {}
+        for k, s in shapes.items():
+            size = int(torch.Size(s).numel())
+            self.p[k] = torch.arange(n, n + size, dtype=torch.float32).view(s)          # value = position in the dump's order
+            self.g[k] = -self.p[k]
+            n += size
+
+    def named_parameters(self):
+        return iter(self.p.items())
+
+    def param(self, k):
+        return self.p[k]
+
+    def param_grad(self, k):
+        return self.g[k]
+
+
+def _dump(bench, shapes, path):
+    import types
+    import numpy as np
+    import torch
+    wl = types.SimpleNamespace(model=_Model(shapes), accuracy=torch.tensor(0.25))
+    bench.dump_outputs(wl, torch.tensor(2.5, requires_grad=True), str(path))
+    return {f[:-4]: np.load(path / f) for f in sorted(os.listdir(path))}
+
+
+def test_dump_outputs_small_model_whole(bench, tmp_path):
+    import numpy as np
+    d = _dump(bench, {"b.weight": (3, 4), "a.bias": (5,)}, tmp_path)
+    assert sorted(d) == ["accuracy", "grads_sample", "loss", "params_sample"]
+    assert all(v.dtype == np.float32 for v in d.values())
+    assert d["loss"].tolist() == [2.5] and d["accuracy"].tolist() == [0.25]
+    assert d["params_sample"].tolist() == list(range(17)) and d["grads_sample"].tolist() == [-float(i) for i in range(17)]
+
+
+def test_dump_outputs_samples_large_models_the_same_way(bench, tmp_path, monkeypatch):
+    """Beyond DUMP_SAMPLE floats: the same sorted, distinct positions in every run, for the weights and the gradients alike."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    shapes = {"w": (40, 10), "b": (100,)}
+    d1 = _dump(bench, shapes, tmp_path / "1")
+    d2 = _dump(bench, shapes, tmp_path / "2")
+    pos = d1["params_sample"]
+    assert pos.shape == (64,) and np.all(np.diff(pos) > 0) and 0 <= pos[0] and pos[-1] < 500
+    assert np.array_equal(d1["grads_sample"], -pos)
+    for k in d1:
+        assert np.array_equal(d1[k], d2[k]), k

@@ -71,7 +71,7 @@ def test_encoder_and_decoder_backward_chains_repeatedly():
     assert skipped <= 80, skipped                 # at least 120 of the 200 calls were compared element by element
 
 
-def test_chunked_chain_forward_for_large_batches():
+def test_chunked_chain_forward_for_large_batches(tmp_path):
     """More rows than one resident chain launch takes (the frozen encoder of LatentRNN: 2048 measures).  Three forms of the
     forward pass must agree: the default (B = 2048: one bf16-pipe product per time step with the GRU cell as its epilogue,
     csrc/gru_step_bf3.hip; smaller batches: the chain kernel over 256-row chunks), the chunked chain launches everywhere
@@ -91,9 +91,9 @@ def test_chunked_chain_forward_for_large_batches():
                 ops.prof_enable(True)
                 mu, ls, _ = ops.encoder_fwd(cfg, tok, params, mask=None, save=False)
                 torch.cuda.synchronize()
-                ops.prof_dump("/tmp/_inet_chunk.csv")
+                ops.prof_dump(str(tmp_path / "_inet_chunk.csv"))
                 ops.prof_enable(False)
-                labels = [l.split(",")[1] for l in open("/tmp/_inet_chunk.csv").read().strip().splitlines()[1:]]
+                labels = [l.split(",")[1] for l in open(str(tmp_path / "_inet_chunk.csv")).read().strip().splitlines()[1:]]
                 nstep = sum(l.startswith("gru_step_bf3") for l in labels)
                 assert nstep == (48 if (B in (2048, 1536) and step_tiles) else 0), (B, chain, step_tiles, labels[:6])
                 if chain and not nstep:

@@ -251,7 +251,7 @@ def test_chain_timeout_on_one_rank_is_handled_by_all_ranks_together(tmp_path):
 
 
 def test_bench_two_ranks_functional(tmp_path):
-    """`bench.py --gpus 2` end to end on ONE GPU (INET_BENCH_SHARE_GPU=1: both ranks on cuda:0, gloo carries the exchange): the
+    """`bench.py --gpus 2 --full` end to end on ONE GPU (INET_BENCH_SHARE_GPU=1: both ranks on cuda:0, gloo carries the exchange): the
     N > 1 code path the driver's scaling run takes -- rank spawn, world check, seeded shared draws, bucketed exchange with the
     step flag, collective health verdict, exchange report, the LatentRNN step under the same exchange (BASELINE.json
     configs[3]) -- prints one JSON line with the data-parallel fields.  A functional check, not a scaling number."""
@@ -263,7 +263,7 @@ def test_bench_two_ranks_functional(tmp_path):
     env = dict(os.environ, INET_BENCH_SHARE_GPU="1", INET_BENCH_DETAIL=detail)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "3", "--full",
                         "--no-cpu-baseline", "--no-roofline", "--no-parity"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -64,7 +64,7 @@ def test_gemm_layouts(akm, bkm, M, N, K):
 
 
 @pytest.mark.parametrize("M,N,K", [(1, 1024, 256), (4, 1536, 512), (4, 512, 512), (8, 130, 1030), (3, 48, 10), (2, 7, 5)])
-def test_gemv_rows(M, N, K):
+def test_gemv_rows(M, N, K, tmp_path):
     """Products of up to 8 rows (the small projections of a b = 1 decode call) on the wave-per-column kernel (csrc/gemm.hip
     gemv_rows_kernel): plain, bias + every epilogue, accumulation into a live strided destination; odd N and K."""
     g = torch.Generator().manual_seed(M * 100 + N + K)
@@ -78,10 +78,10 @@ def test_gemv_rows(M, N, K):
     try:
         C = ops.gemm(Ad, Bd, M, N, K)
         torch.cuda.synchronize()
-        ops.prof_dump("/tmp/_inet_gemv.csv")
+        ops.prof_dump(str(tmp_path / "_inet_gemv.csv"))
     finally:
         ops.prof_enable(False)
-    assert "gemv" in open("/tmp/_inet_gemv.csv").read().strip().splitlines()[-1].split(",")[1]
+    assert "gemv" in open(str(tmp_path / "_inet_gemv.csv")).read().strip().splitlines()[-1].split(",")[1]
     assert relmax(C, ref) < 2e-5
     assert relmax(ops.gemm(Ad, Bd, M, N, K, bias=bias.to(DEV), epi=1), O.selu(ref + bias.double())) < 2e-5
     assert relmax(ops.gemm(Ad, Bd, M, N, K, bias=bias.to(DEV), epi=2), torch.relu(ref + bias.double())) < 2e-5
@@ -167,7 +167,7 @@ def test_gemm_bf3_edge_operands():
 
 
 @pytest.mark.parametrize("save,B", [(False, 2048), (True, 2048), (False, 1536), (True, 1536)])
-def test_gru_step_bf3_matches_chain_path(save, B):
+def test_gru_step_bf3_matches_chain_path(save, B, tmp_path):
     """Big batches: a 2-layer bi-GRU whose single time step fills the chip (B = 2048, H = 512) runs one bf16-pipe product per
     step with the GRU cell as its epilogue (csrc/gru_step_bf3.hip; inet_set_option key 12) instead of chunked chain launches.
     Same arithmetic (nine exact piece products, f32 accumulation), different summation order: outputs and final states agree
@@ -186,9 +186,9 @@ def test_gru_step_bf3_matches_chain_path(save, B):
             ops.prof_enable(True)
             out, hn, ws = ops.bigru2_fwd(x, None, weights, H, B, T, K, mask=mask, save=save)
             torch.cuda.synchronize()
-            ops.prof_dump("/tmp/_inet_stepbf3.csv")
+            ops.prof_dump(str(tmp_path / "_inet_stepbf3.csv"))
             ops.prof_enable(False)
-            labels = open("/tmp/_inet_stepbf3.csv").read()
+            labels = open(str(tmp_path / "_inet_stepbf3.csv")).read()
             assert ("gru_step_bf3" in labels) == (key12 == 256), labels[-600:]
             assert ops.chain_status() <= 0
             outs[key12] = (out.clone(), hn.clone())
@@ -209,7 +209,7 @@ def test_gemm_bf3_rejects_shapes_it_does_not_tile():
 
 @pytest.mark.parametrize("M,N,K", [(1536, 512, 6144), (1536, 1024, 1000), (384, 256, 131), (128, 128, 64),
                                    (576, 576, 777), (1024, 2048, 256)])
-def test_gemm_direct_kmajor_products(M, N, K):
+def test_gemm_direct_kmajor_products(M, N, K, tmp_path):
     """The LDS-free weight-gradient kernel (csrc/gemm.hip gemm_tn_direct_kernel), forced wherever the shape qualifies:
     plain, accumulating, biased + non-linear epilogue, strided destination; odd K and K not a multiple of the prefetch
     block exercise the zero-returning out-of-range buffer loads."""
@@ -224,9 +224,9 @@ def test_gemm_direct_kmajor_products(M, N, K):
         ops.prof_enable(True)
         C = ops.gemm(Ad, Bd, M, N, K, a_kmajor=1, b_kmajor=1)
         torch.cuda.synchronize()
-        ops.prof_dump("/tmp/_inet_direct.csv")
+        ops.prof_dump(str(tmp_path / "_inet_direct.csv"))
         ops.prof_enable(False)
-        assert " d" in open("/tmp/_inet_direct.csv").read().strip().splitlines()[-1].split(",")[1]
+        assert " d" in open(str(tmp_path / "_inet_direct.csv")).read().strip().splitlines()[-1].split(",")[1]
         assert relmax(C, ref) < 2e-5
         C0 = torch.randn(M, N, generator=g)
         C1 = C0.to(DEV).clone()
@@ -245,7 +245,7 @@ def test_gemm_direct_kmajor_products(M, N, K):
 
 @pytest.mark.parametrize("M,N,K,nb,label", [(1536, 512, 6144, 2, "s4 e0 x2"), (1536, 1024, 6144, 2, "s2 e0 x2"),
                                             (1536, 512, 1536, 2, None), (1536, 512, 6144, 3, None), (96, 40, 300, 2, None)])
-def test_gemm_batched_weight_gradients(M, N, K, nb, label):
+def test_gemm_batched_weight_gradients(M, N, K, nb, label, tmp_path):
     """Several k-major x k-major products of one shape in one launch (the two directions of a bi-GRU layer's weight
     gradients share 256 workgroups at half the split-K factor), accumulating into live destinations; interleaved
     operands (direction d at column offset d*M of a [K, nb*M] buffer) and separately allocated ones; shapes the batched
@@ -260,12 +260,12 @@ def test_gemm_batched_weight_gradients(M, N, K, nb, label):
     try:
         ops.gemm_batched(Ad[:, :M], Bd[0], Cd[0], M, N, K, nb, M, K * N, M * N)
         torch.cuda.synchronize()
-        ops.prof_dump("/tmp/_inet_batched.csv")
+        ops.prof_dump(str(tmp_path / "_inet_batched.csv"))
     finally:
         ops.prof_enable(False)
     assert relmax(Cd, ref) < 2e-5
     if label:
-        assert open("/tmp/_inet_batched.csv").read().strip().splitlines()[-1].split(",")[1].endswith(label)
+        assert open(str(tmp_path / "_inet_batched.csv")).read().strip().splitlines()[-1].split(",")[1].endswith(label)
     # a negative stride: the same problems listed backwards
     Cd2 = C0.to(DEV).clone()
     ops.gemm_batched(Ad[:, (nb - 1) * M:], Bd[nb - 1], Cd2[nb - 1], M, N, K, nb, -M, -K * N, -M * N)
@@ -300,7 +300,7 @@ def test_repeated_weight_gradient_accumulation_across_side_streams():
 @pytest.mark.parametrize("bkm", [0, 1])
 @pytest.mark.parametrize("M,N,K", [(6144, 1536, 1024), (6144, 1024, 1536), (6144, 512, 1536), (384, 256, 64),
                                    (192, 64, 192), (1152, 768, 320)])
-def test_gemm_direct_kcontiguous_products(M, N, K, bkm):
+def test_gemm_direct_kcontiguous_products(M, N, K, bkm, tmp_path):
     """The LDS-free forward / data-gradient kernel (csrc/gemm.hip gemm_kc_direct_kernel), forced wherever the shape
     qualifies: plain, accumulating, bias + non-linear epilogue with an aux operand, strided destination."""
     g = torch.Generator().manual_seed(M + 3 * N + K + bkm)
@@ -315,9 +315,9 @@ def test_gemm_direct_kcontiguous_products(M, N, K, bkm):
         ops.prof_enable(True)
         C = ops.gemm(Ad, Bd, M, N, K, b_kmajor=bkm)
         torch.cuda.synchronize()
-        ops.prof_dump("/tmp/_inet_direct.csv")
+        ops.prof_dump(str(tmp_path / "_inet_direct.csv"))
         ops.prof_enable(False)
-        assert " d" in open("/tmp/_inet_direct.csv").read().strip().splitlines()[-1].split(",")[1]
+        assert " d" in open(str(tmp_path / "_inet_direct.csv")).read().strip().splitlines()[-1].split(",")[1]
         assert relmax(C, ref) < 2e-5
         C0 = torch.randn(M, N, generator=g)
         C1 = C0.to(DEV).clone()
@@ -340,7 +340,7 @@ def test_gemm_direct_kcontiguous_products(M, N, K, bkm):
 @pytest.mark.parametrize("M,N,K", [(256, 1024, 2048), (1536, 512, 1024), (1024, 2048, 256), (256, 256, 1024),
                                    (64, 32, 64), (32, 32, 1008), (128, 96, 336),
                                    (1536, 512, 6144), (1536, 1024, 6144), (192, 128, 2064)])   # TN: 96x64 tiles (+ grid split)
-def test_gemm_workgroup_split_k(akm, bkm, M, N, K):
+def test_gemm_workgroup_split_k(akm, bkm, M, N, K, tmp_path):
     """The in-workgroup split-K kernel (csrc/gemm.hip gemm_ks_kernel) on the medium / small shapes of the step, every
     operand layout it takes: plain, accumulating, bias + SELU, aux epilogues, strided destination; for k-major
     operands also a K that is not a multiple of the 16-deep group."""
@@ -359,10 +359,10 @@ def test_gemm_workgroup_split_k(akm, bkm, M, N, K):
         ops.prof_enable(True)
         C = ops.gemm(Ad, Bd, M, N, Kx, **kw)
         torch.cuda.synchronize()
-        ops.prof_dump("/tmp/_inet_ks.csv")
+        ops.prof_dump(str(tmp_path / "_inet_ks.csv"))
         ops.prof_enable(False)
         if Kx >= 64:                                          # shorter products stay on the LDS-tiled kernel
-            assert " k" in open("/tmp/_inet_ks.csv").read().strip().splitlines()[-1].split(",")[1]
+            assert " k" in open(str(tmp_path / "_inet_ks.csv")).read().strip().splitlines()[-1].split(",")[1]
         assert relmax(C, ref) < 2e-5
         C0 = torch.randn(M, N, generator=g)
         C1 = C0.to(DEV).clone()
@@ -714,7 +714,7 @@ def test_adam_kernel_matches_torch():
                                             # input) -- first-generation chain kernels with 192 registers of W_hh per lane -- and a
                                             # ragged batch in 16-row tiles
                                             (128, 4, 1, 1024, True), (40, 3, 8, 1024, False)])
-def test_bigru2_fwd_bwd_vs_oracle(B, T, K, H, scalar):
+def test_bigru2_fwd_bwd_vs_oracle(B, T, K, H, scalar, tmp_path):
     from inpaintnet_amd import layout
     g = torch.Generator().manual_seed(B * 100 + T * 10 + K)
     shapes = layout._gru("g", K, H, 2, True)
@@ -765,9 +765,9 @@ def test_bigru2_fwd_bwd_vs_oracle(B, T, K, H, scalar):
         ops.prof_enable(True)
         ops.bigru2_fwd(xd, xsd, flat, H, B, T, K, h0=h0.detach().to(DEV), mask=mask.to(DEV), save=True)
         torch.cuda.synchronize()
-        ops.prof_dump("/tmp/_inet_h1024.csv")
+        ops.prof_dump(str(tmp_path / "_inet_h1024.csv"))
         ops.prof_enable(False)
-        assert "gru_chain_fwd ms" in open("/tmp/_inet_h1024.csv").read() and ops.chain_status() <= 0
+        assert "gru_chain_fwd ms" in open(str(tmp_path / "_inet_h1024.csv")).read() and ops.chain_status() <= 0
 
 
 def test_backward_refuses_a_workspace_written_under_other_options():

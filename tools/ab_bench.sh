@@ -5,7 +5,7 @@
 for cfg in "$@"; do
   for sw in "20 5" "400 20"; do
     read -r K W <<< "$sw"
-    out=$(env $cfg timeout 300 python3 bench.py --gpus 1 --steps $K --warmup $W --no-cpu-baseline --no-extras --no-parity --no-roofline 2>/dev/null | tail -1)
+    out=$(env $cfg timeout 300 python3 bench.py --gpus 1 --steps $K --warmup $W --full --no-cpu-baseline --no-extras --no-parity --no-roofline 2>/dev/null | tail -1)
     python3 - "$cfg" "$out" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

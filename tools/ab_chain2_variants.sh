@@ -16,7 +16,7 @@ else
   for rep in 1 2; do
     for v in default "$@"; do
       if [ "$v" = default ]; then unset INET_LIB_PATH; else read -r R D <<< "$v"; export INET_LIB_PATH=$PWD/build/lib_r${R}d${D}.so; fi
-      out=$(timeout 300 python3 bench.py --gpus 1 --steps 300 --warmup 20 --no-cpu-baseline --no-extras --no-parity 2>/dev/null | tail -1)
+      out=$(timeout 300 python3 bench.py --gpus 1 --steps 300 --warmup 20 --full --no-cpu-baseline --no-extras --no-parity 2>/dev/null | tail -1)
       python3 -c "
 import json,sys
 d=json.loads(sys.argv[1]); r=d['roofline']

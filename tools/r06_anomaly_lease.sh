@@ -4,7 +4,7 @@
 mkdir -p gpurun_out
 tag=$(date +%s)
 for i in 1 2 3 4 5; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline --no-roofline --no-parity 2>/dev/null
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline --no-roofline --no-parity 2>/dev/null
 done | python -c "
 import json, sys
 rows = [json.loads(l) for l in sys.stdin if l.startswith('{')]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the per-kernel table of a bench.py JSON line read from stdin: `python bench.py ... | python tools/roofline_print.py [n]`."""
+"""Print the per-kernel table of a bench.py JSON line read from stdin: `python bench.py --full ... | python tools/roofline_print.py [n]`."""
 import json
 import sys
 
