@@ -269,6 +269,24 @@ int inet_arnn_generate(int L, int E, int Hc, int H, int U, int V, const float* e
                        const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
                        const float* W2, const float* b2, const float* hc_init, const int64_t* first_tok, int64_t* tokens, float* ws,
                        int64_t ws_floats, void* stream);
+/* AnticipationRNN's temperature-sampled generation (ConstraintModelGaussianReg.generate, AnticipationRNN/
+ * anticipation_rnn_gauss_reg_model.py:570-679) for R independent rows.  Row r runs L ticks of [embedding of the previous token
+ * (tick 0: token 0) | oc0 + r * oc_batch_stride + t * oc_row_stride (Hc floats)] -> LSTM 0 -> LSTM 1 -> ReLU(linear_1) -> note head,
+ * from the state hc_init[r] ([R][layer][h | c][H], nullable: zeros), and DRAWS token t from softmax(temperature * logits) with the
+ * uniform uniforms[r][t] in [0, 1) (host-side doubles) in np.random.choice's order: the first v with sum_{w <= v} p_w > u (prefix
+ * in f64).  A NaN logit, a non-finite total or a uniform outside [0, 1) take the argmax rule of inet_arnn_generate for that tick;
+ * tokens [R][L] int64 on the device are always inside [0, V).  H = U = 256, V <= 128 with inet_set_option key 14 != 0 and the chain
+ * kernels on: the persistent token pass of inet_arnn_generate with the sampling head, up to 8 rows per launch (each an independent
+ * team of 13 workgroups; more rows, or a chain capacity below 13 x rows: successive launches); otherwise four launches per tick,
+ * row after row.  Returns -1 on invalid arguments (R < 1, L < 1, a workspace smaller than inet_arnn_sample_ws_floats, a non-finite
+ * temperature, a null pointer where one is required), -2 on a launch failure; timeouts of the persistent launch are reported by
+ * inet_chain_status. */
+int64_t inet_arnn_sample_ws_floats(int R, int L, int E, int Hc, int H, int U, int V);
+int inet_arnn_sample(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
+                     int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,
+                     const float* W_ih1, const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
+                     const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
+                     int64_t* tokens, float* ws, int64_t ws_floats, void* stream);
 /* nn.Embedding forward / backward (rows of E floats gathered by int64 index; backward accumulates with atomics).
  * row_scale (nullable, [rows]) multiplies each gathered row: the Dropout2d on the shifted note embeddings
  * (drop_input, anticipation_rnn_gauss_reg_model.py:437-442) and the all-zero first time step (:373-376). */

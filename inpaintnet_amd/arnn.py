@@ -7,12 +7,14 @@ single-voice datasets (FolkDataset: num_voices = 1 -- everything the reference t
 in the fused step kernels of csrc/lstm.hip (same K-split geometry as the GRU steps); input projections,
 the Linear+ReLU head and the embedding gathers are the batched kernels of the C-ABI.
 
-Out of scope as in SURVEY.md section 2.1: generate()/generation() (music21 I/O), forward_inpaint, the unused
-gaussian_regularization.
+generate() is the reference's temperature-sampled generation (:570-679) on the sampling build of the token pass
+(ops.arnn_sample); the draws come from numpy's global stream as in the reference, so np.random.seed(s) reproduces its tokens.
+Out of scope as in SURVEY.md section 2.1: the model-level generation() (music21 I/O), the unused gaussian_regularization.
 """
 import os
 import random
 
+import numpy as np
 import torch
 
 from . import layout, ops
@@ -397,6 +399,64 @@ class ConstraintModelGaussianReg(Model):
             ws.append(w)
             gen[:, 0, tick + 1] = ops.argmax_rows(w.detach()[0:1]).view(1)     # batch element 0 decides (:340-343)
         return [torch.stack(ws, 1)], gen
+
+    @torch.no_grad()
+    def generate(self, tensor_score, tensor_metadata, constraints_location, temperature=1.):
+        """Temperature-sampled generation (anticipation_rnn_gauss_reg_model.py:570-679).  Shapes (1, L), (1, L, M), (1, L) as the
+        reference takes them, or a batch (B, 1, L), (B, 1, L, M), (B, 1, L) of independent rows.  Leaves the model in eval().
+
+        The constraint outputs oc come from the masked score (:585-589, `_constraints`).  Warm-up (:596-621): 23 ticks
+        (num_voices * 4 * subdivision - 1) feed the embedding of the dataset's start symbol (empty_score_tensor(L)[0, 0]) with oc[1..23];
+        their state carries over and no head is evaluated.  Generation (:623-671): L ticks, tick 0 feeds token 0 with oc[0], tick t
+        the token drawn at t - 1 with oc[t]; token t = np.random.choice(V, p=softmax(temperature * logits)) -- the temperature
+        MULTIPLIES the logits.  Every tick is drawn, constrained ones included.  The draws are one np.random.random_sample() double
+        per tick, all taken up front as np.random.random_sample((B, L)), row 0 first: with B = 1 the global stream is consumed
+        exactly as by the reference.  -> (score | None (dataset.tensor_to_score where the dataset has it; a list per row for a
+        batch), gen_chorale int64 (1, L) or (B, 1, L) on the model's device, tensor_metadata)."""
+        self.eval()
+        batched = tensor_score.dim() == 3
+        score = tensor_score if batched else tensor_score[None]
+        md = tensor_metadata if batched else tensor_metadata[None]
+        loc = constraints_location if batched else constraints_location[None]
+        B, nv, L = score.shape
+        if nv != 1 or md.dim() != 4 or tuple(md.shape[:3]) != (B, 1, L) or tuple(loc.shape) != (B, 1, L):
+            raise ValueError("generate: expects (1, L), (1, L, M), (1, L) or a batch (B, 1, L), (B, 1, L, M), (B, 1, L)")
+        warm = self.dataset.num_voices * 4 * self.dataset.subdivision - 1
+        if L < warm + 1:
+            raise ValueError(f"generate: the warm-up reads constraint outputs up to tick {warm}: need L >= {warm + 1}, got {L}")
+        if self.num_layers != 2:
+            raise NotImplementedError("generate runs the two-layer generation LSTMs of the sampling kernels (num_layers=2)")
+        empty = getattr(self.dataset, "empty_score_tensor", None)
+        if empty is None:
+            raise ValueError("generate: the dataset has no empty_score_tensor (the start symbol of the warm-up)")
+        start = int(empty(L)[0, 0])
+        dev = self.flat.device
+        score, md, loc = score.to(dev).long(), md.to(dev).long(), loc.to(dev).long()
+        oc = self._constraints(score, md, loc)                                 # [L,B,H]
+        H = self.num_lstm_generation_units
+        x = torch.cat((self._embed("note_embeddings.0.weight", torch.full((warm, B), start, dtype=torch.int64, device=dev)),
+                       oc[1:warm + 1]), 2)
+        hc = torch.empty(B, 2, 2, H, dtype=torch.float32, device=dev)          # [row][layer][h | c][H]
+        for l in range(2):
+            x, hT, cT = self._lstm(f"lstm_generation.{l}", x, False)
+            hc[:, l, 0], hc[:, l, 1] = hT.reshape(B, H), cT.reshape(B, H)
+        u = np.random.random_sample((B, L))
+        pr = self.param
+        toks = ops.arnn_sample(pr("note_embeddings.0.weight"), oc.permute(1, 0, 2),
+                               pr("lstm_generation.0.weight_ih_l0"), pr("lstm_generation.0.bias_ih_l0"),
+                               pr("lstm_generation.0.weight_hh_l0"), pr("lstm_generation.0.bias_hh_l0"),
+                               pr("lstm_generation.1.weight_ih_l0"), pr("lstm_generation.1.bias_ih_l0"),
+                               pr("lstm_generation.1.weight_hh_l0"), pr("lstm_generation.1.bias_hh_l0"),
+                               pr("linear_1.weight"), pr("linear_1.bias"),
+                               pr("linear_ouput_notes.0.weight"), pr("linear_ouput_notes.0.bias"), temperature, u, hc_init=hc)
+        torch.cuda.synchronize()
+        ops.check_chains("generate")                                           # never hand back tokens of a failed launch
+        gen = toks.view(B, 1, L)
+        to_score = getattr(self.dataset, "tensor_to_score", None)
+        if not batched:
+            gen = gen[0]
+            return (to_score(gen.cpu()) if to_score is not None else None), gen, tensor_metadata
+        return ([to_score(g.cpu()) for g in gen] if to_score is not None else None), gen, tensor_metadata
 
     def forward(self, score_tensor, metadata_tensor, constraints_loc, start_tick=None, end_tick=None, train=True,
                 teacher_forcing=None, trim=False):

@@ -1,0 +1,194 @@
+"""Test surface of the AnticipationRNN (AnticipationRNN/anticipation_rnn_tester.py of the reference): inpainting loss /
+accuracy over a loader, and generation of a window of measures with ConstraintModelGaussianReg.generate (temperature 1.5).
+
+The tensor -> music21 score conversions (dataset.tensor_to_score, dataset.transposed_score_and_metadata_tensors) are outside
+the hot path: they are used when the dataset offers them, otherwise the score slots of the return tuples are None and
+`generation` takes the metadata from its caller (tensor_metadata=) or raises ValueError naming what is missing.
+"""
+import os
+from random import randint
+
+import numpy as np
+import torch
+
+from . import ops
+from .arnn import AnticipationRNNGaussianRegTrainer
+from .helpers import to_cuda_variable_long
+
+
+class AnticipationRNNTester(object):
+    def __init__(self, dataset, model):
+        self.dataset = dataset
+        self.model = model
+        self.model.eval()
+        if self.model.flat.is_cuda:
+            ops.preload()                            # no generation call pays a kernel's first launch (csrc/preload.hip)
+        self.filepath = os.path.join('models/', self.model.__repr__())
+        self.batch_size = 1
+        self.measure_seq_len = 24                    # (:16-18: set from the dataset, then fixed to 24)
+
+    def _to_score(self, tensor):
+        fn = getattr(self.dataset, "tensor_to_score", None)
+        return fn(tensor.cpu()) if fn is not None else None
+
+    def test_model(self, batch_size=512):
+        """Loss / accuracy of inpainting on the test split (:20-42)."""
+        (_, gen_val, gen_test) = self.dataset.data_loaders(batch_size=batch_size, split=(0.01, 0.01))
+        print('Num Test Batches: ', len(gen_test))
+        mean_loss_test, mean_accuracy_test = self.loss_and_acc_test(gen_test)
+        print(f'Test Epoch: {1}/{1}')
+        print(f'\tTest Loss: {mean_loss_test}'
+              f'\tTest Accuracy: {mean_accuracy_test * 100} %')
+        return mean_loss_test, mean_accuracy_test
+
+    def loss_and_acc_test(self, data_loader):
+        """Mean loss / accuracy of forward_inpaint over the loader, targets = the unconstrained ticks (:44-86)."""
+        mean_loss = mean_accuracy = 0.0
+        for batch in data_loader:
+            score_tensor, metadata_tensor, constraints_loc, start_tick, end_tick = self.process_batch_data(batch)
+            with torch.no_grad():
+                weights, _ = self.model.forward_inpaint(score_tensor=score_tensor, metadata_tensor=metadata_tensor,
+                                                        constraints_loc=constraints_loc, start_tick=start_tick, end_tick=end_tick)
+                targets = score_tensor[:, :, (constraints_loc[0, 0, :] == 0).nonzero().squeeze(-1)].transpose(0, 1)
+                loss = self.mean_crossentropy_loss(weights=weights, targets=targets)
+                accuracy = self.mean_accuracy(weights=weights, targets=targets)
+            mean_loss += float(loss)
+            mean_accuracy += float(accuracy)
+            ops.check_chains("AnticipationRNNTester.loss_and_acc_test")
+        return mean_loss / len(data_loader), mean_accuracy / len(data_loader)
+
+    def loss_and_acc_test_alt(self, data_loader):
+        """Loss / accuracy of the training objective at one tick near the middle, t = seq_size_in_beats * subdivision / 2 +
+        np.random.randint(-5, 5) per batch (:88-130)."""
+        mean_loss = mean_accuracy = 0.0
+        for batch in data_loader:
+            score_tensor, metadata_tensor, _, _, _ = self.process_batch_data(batch)
+            with torch.no_grad():
+                # the reference's call passes no constraints_loc (:101-104): here the tensor's ticks are all unconstrained, so
+                # forward() returns every tick and `t` indexes ticks as in the reference's intent
+                loc = torch.zeros_like(score_tensor)
+                weights, _ = self.model(score_tensor=score_tensor, metadata_tensor=metadata_tensor, constraints_loc=loc, train=False)
+                t = int(self.dataset.seq_size_in_beats * self.dataset.subdivision / 2) + np.random.randint(-5, 5)
+                targets = score_tensor[:, :, t].transpose(0, 1)
+                w = [wv[:, t, :] for wv in weights]
+                loss = self.mean_crossentropy_loss(weights=[x[:, None] for x in w], targets=targets[:, :, None])
+                accuracy = self.mean_accuracy(weights=[x[:, None] for x in w], targets=targets[:, :, None])
+            mean_loss += float(loss)
+            mean_accuracy += float(accuracy)
+            ops.check_chains("AnticipationRNNTester.loss_and_acc_test_alt")
+        return mean_loss / len(data_loader), mean_accuracy / len(data_loader)
+
+    def generation_test(self):
+        """Inpainting of measures 8 and 9 on a random sample of the test split (:132-183) -> (gen_score | None, gen_score_tensor
+        (1, L): past | generated | future, original_score | None).  (The reference unpacks process_batch_data's five values into
+        two, :149; here the batch's score and metadata are taken directly.)"""
+        (_, gen_val, gen_test) = self.dataset.data_loaders(batch_size=1, split=(0.70, 0.20))
+        gen_it_test = iter(gen_test)
+        batch = next(gen_it_test)
+        for _ in range(randint(0, len(gen_test)) - 1):
+            batch = next(gen_it_test)
+        tensor_score, tensor_metadata = to_cuda_variable_long(batch[0]), to_cuda_variable_long(batch[1])
+        batch_size, num_voices, seq_len, num_metadata = tensor_metadata.size()
+        assert batch_size == 1
+        return self._generate_window(tensor_score.view(num_voices, seq_len),
+                                     tensor_metadata.view(num_voices, seq_len, num_metadata), start_measure=8, num_measures_gen=2)
+
+    def generation(self, tensor_score, start_measure, num_measures_gen, tensor_metadata=None):
+        """Generates measures start_measure .. start_measure + num_measures_gen - 1 (1-based) of a score with temperature 1.5
+        (:185-243) -> (gen_score | None, gen_score_tensor (1, L): past | generated | future, original_score | None).
+
+        tensor_score (1, L) tokens (None: a random score of dataset.iterator_gen()); its metadata come from
+        dataset.transposed_score_and_metadata_tensors where the dataset has it and a score can be built, else from
+        `tensor_metadata` (1, L, M).  Where the reference trims a score whose length is not a multiple of a measure it indexes
+        one tick (`tensor_score[:, n * len]`, :211-212) and compares a tick count with 16 measures (`min(16, size(1))`, :213):
+        here the score is cut to whole measures and to at most 16 of them."""
+        if tensor_score is None:
+            if not hasattr(self.dataset, "iterator_gen"):
+                raise ValueError("generation: tensor_score is None and the dataset has no iterator_gen()")
+            score_gen = iter(self.dataset.iterator_gen())
+            original_score = next(score_gen)
+            for _ in range(randint(0, 100) - 1):
+                original_score = next(score_gen)
+        else:
+            original_score = self._to_score(tensor_score) if tensor_metadata is None else None
+        if original_score is not None and hasattr(self.dataset, "transposed_score_and_metadata_tensors"):
+            trans_interval = self.dataset.get_transpostion_interval_from_semitone(0)
+            tensor_score, tensor_metadata = self.dataset.transposed_score_and_metadata_tensors(original_score, trans_interval)
+        elif tensor_metadata is None:
+            raise ValueError("generation: pass tensor_metadata= (the dataset cannot derive it: no tensor_to_score / "
+                             "transposed_score_and_metadata_tensors)")
+        tensor_score = to_cuda_variable_long(torch.as_tensor(tensor_score))
+        tensor_metadata = to_cuda_variable_long(torch.as_tensor(tensor_metadata))
+        num_measures = min(16, tensor_score.size(1) // self.measure_seq_len)
+        tensor_score = tensor_score[:, :num_measures * self.measure_seq_len]
+        tensor_metadata = tensor_metadata[:, :num_measures * self.measure_seq_len]
+        return self._generate_window(tensor_score, tensor_metadata, start_measure, num_measures_gen)
+
+    def _generate_window(self, tensor_score, tensor_metadata, start_measure, num_measures_gen):
+        constraints_location = torch.zeros_like(tensor_score)
+        measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
+        start_tick = (start_measure - 1) * measure_seq_len
+        end_tick = start_tick + num_measures_gen * measure_seq_len
+        if start_tick > 0:
+            constraints_location[:, :start_tick] = 1
+        if end_tick < constraints_location.size(1) - 1:
+            constraints_location[:, end_tick:] = 1
+        tensor_past = tensor_score[:, :start_tick]
+        tensor_future = tensor_score[:, end_tick:]
+        tensor_target = tensor_score[:, start_tick:end_tick]
+        _, gen_target, _ = self.model.generate(tensor_score=tensor_score, tensor_metadata=tensor_metadata,
+                                               constraints_location=constraints_location, temperature=1.5)
+        gen_target = gen_target[:, start_tick:end_tick]
+        gen_score_tensor = torch.cat((tensor_past, gen_target, tensor_future), 1)
+        original_tensor = torch.cat((tensor_past, tensor_target, tensor_future), 1)
+        return self._to_score(gen_score_tensor), gen_score_tensor, self._to_score(original_tensor)
+
+    def process_batch_data(self, batch):
+        """(score, metadata) -> device tensors, the default constraint window (measures 8 and 9), start / end tick (:245-260)."""
+        tensor_score, tensor_metadata = batch
+        tensor_score = to_cuda_variable_long(tensor_score)
+        tensor_metadata = to_cuda_variable_long(tensor_metadata)
+        constraints_location, start_tick, end_tick = self.get_constraints_location(tensor_score, is_stochastic=False)
+        return tensor_score, tensor_metadata, constraints_location, start_tick, end_tick
+
+    def get_constraints_location(self, tensor_score, is_stochastic, start_measure=None, num_measures=None):
+        """1 = constrained tick, 0 = to be generated (:262-316).  The stochastic branch draws the window from torch's global
+        generator (5+ measures of past and of future, 2+ to generate).  As in the reference, start_tick = start_measure * 24
+        here, while generation() puts its window at (start_measure - 1) * 24."""
+        constraints_location = torch.zeros_like(tensor_score)
+        measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
+        if is_stochastic:
+            min_num_measures_past = min_num_measures_future = 5
+            min_num_measures_target = 2
+            num_measures = int(tensor_score.size(2) / measure_seq_len)
+            assert num_measures == self.dataset.n_bars
+            num_target = int(torch.randint(low=min_num_measures_target,
+                                           high=num_measures - min_num_measures_past - min_num_measures_future, size=(1,)).item())
+            num_past = int(torch.randint(low=min_num_measures_past, high=num_measures - num_target - min_num_measures_future,
+                                         size=(1,)).item())
+            assert num_measures - num_past - num_target >= min_num_measures_future
+            start_measure = num_past + 1
+            num_measures = num_target
+        else:
+            if start_measure is None:
+                start_measure = 8
+            if num_measures is None:
+                num_measures = 2
+        start_tick = start_measure * measure_seq_len
+        end_tick = start_tick + num_measures * measure_seq_len
+        if start_tick > 0:
+            constraints_location[:, :, :start_tick] = 1
+        if end_tick < constraints_location.size(2) - 1:
+            constraints_location[:, :, end_tick:] = 1
+        return constraints_location, start_tick, end_tick
+
+    @staticmethod
+    def mean_crossentropy_loss(weights, targets):
+        """Mean over voices of nn.CrossEntropyLoss (mean) of weights[i] (B, T, V) against targets[i] (B, T) (:318-336)."""
+        return AnticipationRNNGaussianRegTrainer.mean_crossentropy_loss_and_accuracy_voices(weights, targets)[0]
+
+    @staticmethod
+    def mean_accuracy(weights, targets):
+        """Mean over voices of the fraction of ticks whose argmax is the target (:338-356)."""
+        return AnticipationRNNGaussianRegTrainer.mean_crossentropy_loss_and_accuracy_voices(weights, targets)[1]
+

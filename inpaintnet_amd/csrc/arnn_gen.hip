@@ -31,20 +31,26 @@
 // for the two hand-offs, 0.4 us per 256 x 256 product, 0.25 each for the head's product and the argmax, the rest barriers and the
 // cells: 384 ticks in 1.5 ms (round 4: 5.5).
 // Shapes: H = U = 256 (the reference's configuration), V <= 128; anything else keeps the per-tick launches.  Every spin is bounded.
+// The sampling build (SAMPLE = true: ConstraintModelGaussianReg.generate, anticipation_rnn_gauss_reg_model.py:570-679) draws each token
+// from softmax(T * logits) with a host-drawn uniform (sample.h) instead of the argmax, and runs up to 8 independent rows ("teams" of 13
+// workgroups, each with its own exchange) in the workgroups that the argmax build leaves idle.
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include "chain.h"
 #define INET_GRANULE_KID chain::K_ARNN_GEN
 #include "granule.h"
 #include "prof.h"
 #include "lstm.h"
 #include "pointwise.h"
+#include "sample.h"
 
 namespace {
 using namespace granule;
 
 constexpr int GH = 256, G4 = 4 * GH;
 constexpr int kExXcc = 4 * GH + 2 * G4;          // granules behind the exchange: the workgroups' XCC ids (granule::same_xcd)
+constexpr long kExGranules = kExXcc + 16;         // 8-byte granules of the exchange (of one team)
 
 struct GenArgs {
     int L, V, E, K0, stride, near;                   // K0 = E + Hc: row stride of W_ih0; stride: block b works iff b % stride == 0, role b / stride
@@ -56,6 +62,9 @@ struct GenArgs {
     unsigned long long* ex;                      // granules: h0 [2][256] | h1 [2][256] | hh0 [1024] | hh1 [1024]  (h: slot = tag & 1)
     unsigned long long* stamps;                  // diagnostics (INET_ARNN_GEN_STAMPS=1): [C, Bi_0][L][8] wall-clock ticks (10 ns), or null
     chain::Status status;
+    // sampling build: `rows` independent teams of 13 workgroups (pre, hc_init, uniforms, tokens and the exchange per team; T0
+    // shared), the head draws token t from softmax(temp * logits) with the uniform uniforms[team][t] (sample.h)
+    int rows; float temp; const double* uniforms;
 };
 #define GEN_STAMP(who, t, i) do { if (a.stamps && tid == 0) a.stamps[((long)(who) * a.L + (t)) * 8 + (i)] = wall_clock64(); } while (0)
 
@@ -131,29 +140,39 @@ __device__ __forceinline__ void recurrent_role(const GenArgs& a, int k, const fl
     }
 }
 
-template <int NV>
+// SAMPLE = false: the argmax head (the free-running forward's token pass); true: the sampling head and teams (generate)
+template <int NV, bool SAMPLE>
 __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
     __shared__ __attribute__((aligned(16))) float xs[2][XS];
     __shared__ __attribute__((aligned(16))) float us[GH];
     __shared__ float ps[8][64 * NV];
     __shared__ int bad_s, near_s;
-    if (blockIdx.x % a.stride) return;
-    const int role = blockIdx.x / a.stride;
+    // sampling build: team r = the blocks b = r (mod 8) with role b / 8 under stride 8 (one XCD per team under round-robin
+    // dispatch), the contiguous blocks [13 r, 13 r + 13) under stride 1.  (Written so that the argmax build compiles to the same
+    // code as before the teams: team 0, its pointers a's own.)
+    if (!SAMPLE && blockIdx.x % a.stride) return;
+    const int team = SAMPLE ? (a.stride == 1 ? (int)blockIdx.x / 13 : (int)blockIdx.x % a.stride) : 0;
+    const int role = SAMPLE ? (a.stride == 1 ? (int)blockIdx.x % 13 : (int)blockIdx.x / a.stride) : (int)(blockIdx.x / a.stride);
+    if (SAMPLE && team >= a.rows) return;
+    unsigned long long* const ex = a.ex + team * kExGranules;
+    const float* const pre = a.pre + (long)team * a.L * G4;
+    const float* const hc_init = SAMPLE && a.hc_init ? a.hc_init + team * 4 * GH : a.hc_init;
+    long long* const tokens = a.tokens + (long)team * a.L;
     const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
-    unsigned long long* const e_h0 = a.ex;
-    unsigned long long* const e_h1 = a.ex + 2 * GH;
-    unsigned long long* const e_hh0 = a.ex + 4 * GH;
-    unsigned long long* const e_hh1 = a.ex + 4 * GH + G4;
+    unsigned long long* const e_h0 = ex;
+    unsigned long long* const e_h1 = ex + 2 * GH;
+    unsigned long long* const e_hh0 = ex + 4 * GH;
+    unsigned long long* const e_hh1 = ex + 4 * GH + G4;
     volatile int* const bad = &bad_s;
     if (tid == 0) bad_s = 0;
     __syncthreads();
     // all 13 workgroups on one XCD (mode 3 asks; the answer is the hardware's): granules as plain stores (granule.h)
-    const bool near = a.near && same_xcd(a.ex + kExXcc, role, 13, a.status, &near_s);
+    const bool near = a.near && same_xcd(ex + kExXcc, role, 13, a.status, &near_s);
 
     if (role >= 1 && role <= 4) {
-        recurrent_role(a, role - 1, a.W_hh0, nullptr, a.hc_init, e_h0, e_hh0, xs, bad, near);  // (b_hh0 sits in pre)
+        recurrent_role(a, role - 1, a.W_hh0, nullptr, hc_init, e_h0, e_hh0, xs, bad, near);  // (b_hh0 sits in pre)
     } else if (role >= 9) {
-        recurrent_role(a, role - 9, a.W_hh1, a.b_hh1, a.hc_init ? a.hc_init + 2 * GH : nullptr, e_h1, e_hh1, xs, bad, near);
+        recurrent_role(a, role - 9, a.W_hh1, a.b_hh1, hc_init ? hc_init + 2 * GH : nullptr, e_h1, e_hh1, xs, bad, near);
     } else if (role >= 5) {
         // ---- Bi_k: layer 1's input-side product and its cell: thread (unit j, eighth e) holds the four gate rows of its unit, the
         // sums land in every lane of the 8-lane group, lane e = 0 computes the cell -- no LDS, no barrier behind the product ----
@@ -165,7 +184,7 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
         float bb[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) bb[i] = a.b_ih1[row[i]];
-        float c1 = (cell && a.hc_init) ? a.hc_init[3 * GH + 64 * k + j] : 0.f;
+        float c1 = (cell && hc_init) ? hc_init[3 * GH + 64 * k + j] : 0.f;
         for (int t = 0; t < a.L; ++t) {
             // the recurrent summands of this tick were started a tick ago: they are here before h0_t is
             float hh[4] = {0.f, 0.f, 0.f, 0.f};
@@ -213,17 +232,23 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
         }
         const float b1 = a.b1[4 * rq + (e & 3)];               // lanes 0 .. 3 of the group write one row of u each
         const bool unit = tid < GH;                            // threads 0 .. 255 also own one unit of layer 0
-        float c0 = (unit && a.hc_init) ? a.hc_init[GH + tid] : 0.f;
+        float c0 = (unit && hc_init) ? hc_init[GH + tid] : 0.f;
         long long tok = a.first_tok ? *a.first_tok : 0;
         float pr[4] = {0.f, 0.f, 0.f, 0.f}, hh[4] = {0.f, 0.f, 0.f, 0.f};
         unsigned long long hw[4];
+        const double* const urow = SAMPLE ? a.uniforms + (long)team * a.L : nullptr;
+        double u = 0.0, u_next = SAMPLE ? urow[0] : 0.0;       // (the next tick's uniform is requested a tick early)
         if (unit) {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) pr[g] = a.pre[g * GH + tid];
+            for (int g = 0; g < 4; ++g) pr[g] = pre[g * GH + tid];
             if (!get_n<4>(e_hh0 + tid, GH, 1u, a.status, hh, hw)) *bad = 1;
         }
         for (int t = 0; t < a.L; ++t) {
             const bool more = t + 1 < a.L;
+            if constexpr (SAMPLE) {
+                u = u_next;
+                if (more) u_next = urow[t + 1];
+            }
             GEN_STAMP(0, t, 0);
             if (unit) {
                 float gate[4];
@@ -244,7 +269,7 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                 GEN_STAMP(0, t, 1);
                 if (more) {
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) pr[g] = a.pre[(long)(t + 1) * G4 + g * GH + tid];
+                    for (int g = 0; g < 4; ++g) pr[g] = pre[(long)(t + 1) * G4 + g * GH + tid];
                 }
                 float x;
                 if (!get_1(e_h1 + ((t + 1) & 1) * GH + tid, (unsigned)t + 1u, a.status, x)) *bad = 1;
@@ -294,21 +319,35 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                 }
                 m = wave_max_dpp(m);
                 int bi = -1;
+                if constexpr (SAMPLE) {
+                    // the sampling head (sample.h): a NaN logit, a non-finite total or a uniform outside [0, 1) keep the argmax rule
+                    float sv[NV], ms = -INFINITY;
+                    bool nan = false;
 #pragma unroll
-                for (int j = NV - 1; j >= 0; --j) {
-                    const unsigned long long eq = __ballot(lg[j] == m);
-                    if (eq) bi = 64 * j + __builtin_ctzll(eq);
+                    for (int j = 0; j < NV; ++j) {
+                        sv[j] = lane + 64 * j < a.V ? lg[j] * a.temp : -INFINITY;
+                        nan |= sv[j] != sv[j];
+                        ms = fmaxf(ms, sv[j]);
+                    }
+                    if (!__ballot(nan)) bi = sample::pick<NV>(sv, wave_max_dpp(ms), u, a.V, lane);
                 }
+                if (bi < 0) {
 #pragma unroll
-                for (int j = NV - 1; j >= 0; --j)
-                    if (nanm[j]) bi = 64 * j + __builtin_ctzll(nanm[j]);
-                // (NaN in the lower half beats one in the upper: the loops run downwards and the lower overwrites)
-                bool anynan = false;
+                    for (int j = NV - 1; j >= 0; --j) {
+                        const unsigned long long eq = __ballot(lg[j] == m);
+                        if (eq) bi = 64 * j + __builtin_ctzll(eq);
+                    }
 #pragma unroll
-                for (int j = 0; j < NV; ++j) anynan |= nanm[j] != 0;
-                if (!anynan && bi < 0) bi = 0;
+                    for (int j = NV - 1; j >= 0; --j)
+                        if (nanm[j]) bi = 64 * j + __builtin_ctzll(nanm[j]);
+                    // (NaN in the lower half beats one in the upper: the loops run downwards and the lower overwrites)
+                    bool anynan = false;
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) anynan |= nanm[j] != 0;
+                    if (!anynan && bi < 0) bi = 0;
+                }
                 tok = (bi >= 0 && bi < a.V) ? bi : 0;
-                if (tid == 0) a.tokens[t] = tok;
+                if (tid == 0) tokens[t] = tok;
             }
             GEN_STAMP(0, t, 6);
             if (unit && more && !get_n<4>(e_hh0 + tid, GH, (unsigned)t + 2u, a.status, hh, hw, false)) *bad = 1;
@@ -320,10 +359,11 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
 }
 
 // pre[t][r] = sum_k oc[t][k] W_ih0[r][E + k] + b_ih0[r] + b_hh0[r]  (tiles of 16 ticks x 64 gate rows), and
-// T0[v][r] = sum_e emb[v][e] W_ih0[r][e]                              (the blocks behind them, 256 outputs each)
+// T0[v][r] = sum_e emb[v][e] W_ih0[r][e]                              (the blocks behind them, 256 outputs each);
+// `rows` rows of pre (the sampling build's teams): row i from oc0 + i * oc_bstride into pre + i * L * 4H
 struct PrepArgs {
-    int L, V, E, Hc, K0, nb_pre;
-    const float* oc0; long oc_stride;
+    int L, V, E, Hc, K0, nb_pre, rows;
+    const float* oc0; long oc_stride, oc_bstride;
     const float* emb; const float* W_ih0; const float* b_ih0; const float* b_hh0;
     float* pre; float* T0;
 };
@@ -331,8 +371,8 @@ __global__ __launch_bounds__(256) void arnn_gen_prep_kernel(PrepArgs a) {
     __shared__ float Ws[64 * 65];
     __shared__ float Os[16 * 64];
     const int tid = threadIdx.x, lane = tid & 63, tg = tid >> 6;
-    if ((int)blockIdx.x >= a.nb_pre) {
-        const long o = (long)(blockIdx.x - a.nb_pre) * 256 + tid;
+    if ((int)blockIdx.x >= a.nb_pre * a.rows) {
+        const long o = (long)(blockIdx.x - a.nb_pre * a.rows) * 256 + tid;
         if (o < (long)a.V * G4) {
             const int v = (int)(o / G4), r = (int)(o % G4);
             float s = 0.f;
@@ -341,7 +381,10 @@ __global__ __launch_bounds__(256) void arnn_gen_prep_kernel(PrepArgs a) {
         }
         return;
     }
-    const int rb = blockIdx.x % (G4 / 64), tb = blockIdx.x / (G4 / 64);
+    const int row = blockIdx.x / a.nb_pre, bb = blockIdx.x % a.nb_pre;
+    const int rb = bb % (G4 / 64), tb = bb / (G4 / 64);
+    const float* const oc0 = a.oc0 + row * a.oc_bstride;
+    float* const pre = a.pre + (long)row * a.L * G4;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < a.Hc; k0 += 64) {
         __syncthreads();
@@ -353,7 +396,7 @@ __global__ __launch_bounds__(256) void arnn_gen_prep_kernel(PrepArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int e = tid + 256 * i, kk = e & 63, tk = e >> 6, t = tb * 16 + tk;
-            Os[tk * 64 + kk] = (t < a.L && k0 + kk < a.Hc) ? a.oc0[(long)t * a.oc_stride + k0 + kk] : 0.f;
+            Os[tk * 64 + kk] = (t < a.L && k0 + kk < a.Hc) ? oc0[(long)t * a.oc_stride + k0 + kk] : 0.f;
         }
         __syncthreads();
 #pragma unroll 8
@@ -368,7 +411,7 @@ __global__ __launch_bounds__(256) void arnn_gen_prep_kernel(PrepArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int t = tb * 16 + 4 * tg + i;
-        if (t < a.L) a.pre[(long)t * G4 + r] = acc[i] + b;
+        if (t < a.L) pre[(long)t * G4 + r] = acc[i] + b;
     }
 }
 
@@ -386,7 +429,6 @@ int mode() {
     }
     return g_mode;
 }
-constexpr long kExGranules = kExXcc + 16;         // 8-byte granules of the exchange
 constexpr long kExFloats = 2 * kExGranules + 64; // ... as floats, + the launch's status word (64 floats behind them)
 }  // namespace
 
@@ -410,7 +452,7 @@ int arnn_token_pass(int L, int E, int Hc, int V, const float* emb, const float* 
     if (hipMemsetAsync(ex, 0, (size_t)kExFloats * sizeof(float), s) != hipSuccess) return -2;
     PrepArgs p{};
     p.L = L; p.V = V; p.E = E; p.Hc = Hc; p.K0 = E + Hc;
-    p.nb_pre = (G4 / 64) * ((L + 15) / 16);
+    p.nb_pre = (G4 / 64) * ((L + 15) / 16); p.rows = 1;
     p.oc0 = oc0; p.oc_stride = oc_stride; p.emb = emb; p.W_ih0 = W_ih0; p.b_ih0 = b_ih0; p.b_hh0 = b_hh0; p.pre = pre; p.T0 = T0;
     const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
     hipLaunchKernelGGL(arnn_gen_prep_kernel, dim3(p.nb_pre + nb_t0), dim3(256), 0, s, p);
@@ -429,7 +471,62 @@ int arnn_token_pass(int L, int E, int Hc, int V, const float* emb, const float* 
     ProfScope prof(PROF_GRU_FWD, 2.0 * L * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH), s, label,
                    4.0 * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH + (double)(L + V) * G4));
     const dim3 grid(13 * a.stride);
-    if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1>), grid, dim3(NT), 0, s, a);
-    else hipLaunchKernelGGL((arnn_token_pass_kernel<2>), grid, dim3(NT), 0, s, a);
+    if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1, false>), grid, dim3(NT), 0, s, a);
+    else hipLaunchKernelGGL((arnn_token_pass_kernel<2, false>), grid, dim3(NT), 0, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ---- the sampling build: R independent rows, up to 8 teams of 13 workgroups per launch ----
+namespace {
+// teams per launch: at most 8 (the stride-8 placement has 8 residues), and 13 x teams workgroups inside the chain capacity
+int sample_teams(int R) {
+    const int cap = chain_capacity() / 13;
+    return std::max(1, std::min(std::min(R, 8), cap));
+}
+}  // namespace
+
+// pre [teams][L][4H] | T0 [V][4H] | exchange [teams][kExGranules] granules + the status word (64 floats) + 64
+size_t arnn_token_sample_ws_floats(int R, int L, int V) {
+    const size_t n = (size_t)sample_teams(R);
+    return n * L * G4 + (size_t)V * G4 + n * 2 * kExGranules + 64 + 64;
+}
+
+int arnn_token_sample(int R, int L, int E, int Hc, int V, const float* emb, const float* oc0, long oc_stride, long oc_bstride,
+                      const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0, const float* W_ih1,
+                      const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1, const float* W2,
+                      const float* b2, float temp, const double* uniforms, const float* hc_init, long long* tokens, float* ws,
+                      hipStream_t s) {
+    const int n = sample_teams(R);
+    float* pre = ws;
+    float* T0 = pre + (size_t)n * L * G4;
+    unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
+    const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
+    char label[64];
+    std::snprintf(label, sizeof label, "arnn_token_sample R%d L%d V%d", R, L, V);
+    for (int r0 = 0; r0 < R; r0 += n) {                          // R > teams: successive launches of up to `n` rows
+        const int rows = std::min(n, R - r0);
+        unsigned* status = reinterpret_cast<unsigned*>(ex + rows * kExGranules);
+        if (hipMemsetAsync(ex, 0, ((size_t)rows * 2 * kExGranules + 64) * sizeof(float), s) != hipSuccess) return -2;
+        PrepArgs p{};
+        p.L = L; p.V = V; p.E = E; p.Hc = Hc; p.K0 = E + Hc;
+        p.nb_pre = (G4 / 64) * ((L + 15) / 16); p.rows = rows;
+        p.oc0 = oc0 + (long)r0 * oc_bstride; p.oc_stride = oc_stride; p.oc_bstride = oc_bstride;
+        p.emb = emb; p.W_ih0 = W_ih0; p.b_ih0 = b_ih0; p.b_hh0 = b_hh0; p.pre = pre; p.T0 = T0;
+        hipLaunchKernelGGL(arnn_gen_prep_kernel, dim3(p.nb_pre * rows + (r0 == 0 ? nb_t0 : 0)), dim3(256), 0, s, p);
+        GenArgs a{};
+        a.L = L; a.V = V; a.E = E; a.K0 = E + Hc; a.stride = (mode() == 2 || mode() == 3) ? 8 : 1; a.near = mode() >= 3;
+        a.emb = emb; a.W_ih0 = W_ih0; a.W_hh0 = W_hh0; a.W_ih1 = W_ih1; a.b_ih1 = b_ih1; a.W_hh1 = W_hh1; a.b_hh1 = b_hh1;
+        a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.pre = pre; a.T0 = T0;
+        a.hc_init = hc_init ? hc_init + (long)r0 * 4 * GH : nullptr; a.first_tok = nullptr; a.tokens = tokens + (long)r0 * L; a.ex = ex;
+        a.stamps = nullptr;
+        a.status = chain_status_for(status);
+        a.rows = rows; a.temp = temp; a.uniforms = uniforms + (long)r0 * L;
+        ProfScope prof(PROF_GRU_FWD, 2.0 * rows * L * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH), s, label,
+                       4.0 * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH + (double)(rows * L + V) * G4));
+        const dim3 grid(a.stride == 8 ? 13 * 8 : 13 * rows);
+        if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true>), grid, dim3(NT), 0, s, a);
+        else hipLaunchKernelGGL((arnn_token_pass_kernel<2, true>), grid, dim3(NT), 0, s, a);
+        if (hipGetLastError() != hipSuccess) return -2;
+    }
+    return 0;
 }

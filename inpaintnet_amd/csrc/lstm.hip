@@ -10,6 +10,7 @@
 #include "prof.h"
 #include "seq.h"
 #include "lstm.h"
+#include "sample.h"
 
 using namespace ksplit;
 
@@ -1039,6 +1040,22 @@ __device__ __forceinline__ bool argmax_better(float b2, int i2, float best, int 
     return b2 > best || (b2 == best && i2 < bi);
 }
 
+// np.argmax order over lg[0 .. V) (anticipation_rnn_gauss_reg_model.py:253) by one wave: a NaN is the maximum, the lowest index wins
+// among equals -- an all-NaN or all -inf row yields a token INSIDE the vocabulary (the next tick gathers the embedding row by it)
+__device__ __forceinline__ int argmax_wave(const float* lg, int V, int lane) {
+    float best = lane < V ? lg[lane] : -INFINITY;
+    int bi = lane < V ? lane : 0x7fffffff;
+    for (int v = lane + 64; v < V; v += 64)
+        if (argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float b2 = __shfl_xor(best, o, 64);
+        const int i2 = __shfl_xor(bi, o, 64);
+        if (argmax_better(b2, i2, best, bi)) { best = b2; bi = i2; }
+    }
+    return bi;
+}
+
 // token = argmax_v (W[v,:] . x + b[v]), lowest index on ties, V <= 256: ONE workgroup of 16 waves; a wave's rows (V = 48: three) are all
 // requested before the first sum, the logits meet in LDS and the first wave takes the argmax with shuffles
 template <int NI>
@@ -1064,19 +1081,52 @@ __global__ __launch_bounds__(1024) void head_argmax_b1_kernel(const float* __res
     }
     __syncthreads();
     if (w == 0) {
-        // np.argmax order (anticipation_rnn_gauss_reg_model.py:253): a NaN is the maximum, the lowest index wins among equals -- an
-        // all-NaN or all -inf row yields a token INSIDE the vocabulary (the next tick gathers the embedding row by it)
-        float best = lane < V ? lg[lane] : -INFINITY;
-        int bi = lane < V ? lane : 0x7fffffff;
-        for (int v = lane + 64; v < V; v += 64)
-            if (argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float b2 = __shfl_xor(best, o, 64);
-            const int i2 = __shfl_xor(bi, o, 64);
-            if (argmax_better(b2, i2, best, bi)) { best = b2; bi = i2; }
-        }
+        const int bi = argmax_wave(lg, V, lane);
         if (lane == 0) *tok = bi < V ? bi : 0;
+    }
+}
+
+// head_argmax_b1_kernel's products, then token = a draw from softmax(temp * logits) with the uniform *u (sample.h: numpy's
+// np.random.choice order, anticipation_rnn_gauss_reg_model.py:655-667); a NaN logit, a non-finite total or a uniform outside [0, 1)
+// keep the argmax rule.  V <= 256.
+template <int NI>
+__global__ __launch_bounds__(1024) void head_sample_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                              const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
+                                                              float temp, const double* __restrict__ u) {
+    __shared__ float lg[256];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float xv[NI];
+    load_x<NI>(xv, x, K, nullptr, K, lane);
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        if (v < V) {
+            const float a = wave_sum(part[r]);
+            if (lane == 0) lg[v] = a + b[v];
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        float sv[4], ms = -INFINITY;
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = lane + 64 * j;
+            sv[j] = v < V ? lg[v] * temp : -INFINITY;
+            nan |= sv[j] != sv[j];
+            ms = fmaxf(ms, sv[j]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
+        int bi = __ballot(nan) ? -1 : sample::pick<4>(sv, ms, *u, V, lane);
+        if (bi < 0) bi = argmax_wave(lg, V, lane);
+        if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
     }
 }
 }  // namespace
@@ -1115,6 +1165,48 @@ int arnn_generate(int L, int E, int Hc, int H, int U, int V, const float* emb, c
                            (const float*)C_(1, p), W_hh1, b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
         hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), W1, b1, u, U, H);
         hipLaunchKernelGGL((head_argmax_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, W2, b2, tokens + t, V, U);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+size_t arnn_sample_ws_floats(int R, int L, int E, int Hc, int H, int U, int V) {
+    const size_t ticks = (size_t)(E + Hc) + 4 * (size_t)H + 8 * (size_t)H + U + V + 64;
+    const size_t pass = arnn_token_pass_ok(H, U, V) ? arnn_token_sample_ws_floats(R, L, V) : 0;
+    return ticks > pass ? ticks : pass;
+}
+
+int arnn_sample(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, long oc_stride, long oc_bstride,
+                const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0, const float* W_ih1, const float* b_ih1,
+                const float* W_hh1, const float* b_hh1, const float* W1, const float* b1, const float* W2, const float* b2, float temp,
+                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s) {
+    // the reference's configuration: the persistent token pass with the sampling head, up to 8 rows per launch (arnn_gen.hip)
+    if (arnn_token_pass_ok(H, U, V))
+        return arnn_token_sample(R, L, E, Hc, V, emb, oc0, oc_stride, oc_bstride, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
+                                 W1, b1, W2, b2, temp, uniforms, hc_init, tokens, ws, s);
+    if (V > 256 || E + Hc > 320 || H > 256 || U > 256) return -1;      // (the template bounds of the one-row kernels)
+    float* hc = ws;                                            // [layer][h|c][ping-pong][H]
+    float* u = hc + 8 * H;
+    auto H_ = [&](int l, int p) { return hc + ((l * 2 + 0) * 2 + p) * H; };
+    auto C_ = [&](int l, int p) { return hc + ((l * 2 + 1) * 2 + p) * H; };
+    for (int r = 0; r < R; ++r) {                              // the rows one after the other, arnn_generate's four launches per tick
+        const float* oc = oc0 + (long)r * oc_bstride;
+        long long* tk = tokens + (long)r * L;
+        if (pw_zero(hc, 8L * H, s) != 0) return -2;
+        if (hc_init)
+            for (int l = 0; l < 2; ++l)
+                if (pw_copy_bytes(H_(l, 0), hc_init + ((long)r * 4 + 2 * l) * H, H * sizeof(float), s) != 0 ||
+                    pw_copy_bytes(C_(l, 0), hc_init + ((long)r * 4 + 2 * l + 1) * H, H * sizeof(float), s) != 0) return -2;
+        for (int t = 0, p = 0; t < L; ++t, p ^= 1) {
+            hipLaunchKernelGGL((lstm_cell_b1_kernel<5, 4>), dim3(H / 4), dim3(256), 0, s, emb, t ? tk + t - 1 : (const long long*)nullptr,
+                               (const float*)nullptr, E, oc + (long)t * oc_stride, Hc, W_ih0, b_ih0, (const float*)H_(0, p),
+                               (const float*)C_(0, p), W_hh0, b_hh0, H_(0, p ^ 1), C_(0, p ^ 1), H);
+            hipLaunchKernelGGL((lstm_cell_b1_kernel<4, 4>), dim3(H / 4), dim3(256), 0, s, (const float*)nullptr, (const long long*)nullptr,
+                               (const float*)H_(0, p ^ 1), H, (const float*)nullptr, 0, W_ih1, b_ih1, (const float*)H_(1, p),
+                               (const float*)C_(1, p), W_hh1, b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
+            hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), W1, b1, u, U, H);
+            hipLaunchKernelGGL((head_sample_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, W2, b2, tk + t, V, U, temp,
+                               uniforms + (long)r * L + t);
+        }
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

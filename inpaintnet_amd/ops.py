@@ -164,6 +164,35 @@ def arnn_generate(emb, oc0, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_h
 _ARNN_KEEP_WS = []
 
 
+def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2, temperature, uniforms, hc_init=None):
+    """inet_arnn_sample: AnticipationRNN's temperature-sampled generation for R independent rows.  oc [R,L,Hc] (the rows' constraint
+    outputs; strided rows and ticks allowed); uniforms [R,L] float64 (one np.random.random_sample() double per tick; a host array is
+    copied to the device); hc_init [R,2,2,H] (layer, h|c) or None (zeros).  Token t of row r is the first v whose softmax(temperature *
+    logits) prefix exceeds uniforms[r, t] (np.random.choice's rule) -> tokens [R,L] int64 on the device, no host round trip."""
+    R, L, Hc = oc.shape
+    assert oc.is_cuda and oc.dtype == torch.float32 and oc.stride(2) == 1
+    E, H, U, V = emb.shape[1], W_hh0.shape[1], W1.shape[0], W2.shape[0]
+    for t in (emb, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2):
+        _f32c(t)
+    u = torch.as_tensor(uniforms, dtype=torch.float64).to(emb.device).contiguous()
+    if tuple(u.shape) != (R, L):
+        raise ValueError(f"arnn_sample: uniforms of shape {tuple(u.shape)}, expected {(R, L)}")
+    if hc_init is not None and tuple(hc_init.shape) != (R, 2, 2, H):
+        raise ValueError(f"arnn_sample: hc_init of shape {tuple(hc_init.shape)}, expected {(R, 2, 2, H)}")
+    nws = int(_lib.lib().inet_arnn_sample_ws_floats(R, L, E, Hc, H, U, V))
+    if nws < 0:
+        raise ValueError("inet_arnn_sample_ws_floats: invalid arguments")
+    ws = torch.empty(nws, dtype=torch.float32, device=emb.device)
+    tokens = torch.empty(R, L, dtype=torch.int64, device=emb.device)
+    check(_lib.lib().inet_arnn_sample(R, L, E, Hc, H, U, V, ptr(emb), ptr(oc), oc.stride(1), oc.stride(0), ptr(W_ih0), ptr(b_ih0),
+                                      ptr(W_hh0), ptr(b_hh0), ptr(W_ih1), ptr(b_ih1), ptr(W_hh1), ptr(b_hh1), ptr(W1), ptr(b1), ptr(W2),
+                                      ptr(b2), float(temperature), ptr(u),
+                                      ptr(_f32c(hc_init) if hc_init is not None else None), ptr(tokens), ptr(ws), nws,
+                                      stream_ptr()), "inet_arnn_sample")
+    _hold(ws, oc, u, hc_init)
+    return tokens
+
+
 _twin = {}
 
 
