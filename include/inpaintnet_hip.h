@@ -405,9 +405,12 @@ int inet_slow_waits(unsigned* dst, int max_entries, int reset, int64_t* noted);
 /* The launch plan of the register-resident decode (csrc/decode_b1.hip) for a call of B measures with V notes and latent size Z, and
  * a host-side self-check of it -- no GPU needed (tests/test_decode_plan.py).  out8 = {teams, rows per team, shared recurrent groups,
  * critical workgroups per team, placed (1: workgroup ids are mapped to roles so that a team's critical workgroups share a residue mod
- * 8), grid, live workgroups, ok}; ok = every (team, role) the kernel expects appears exactly once among the ids of the grid, every
- * team's critical roles sit on ONE residue, no residue carries more than 32 live workgroups, the grid fits the chip.  0, or -1 for a
- * call the register-resident launch does not take (B > 16, V > 128, ...). */
+ * 8), grid, live workgroups, ok}; Z != 256 gives the plan of a call whose beat path runs as launches of its own (as a beat dropout
+ * mask does).  ok = the plan names an instantiation of the kernel, every row is in one team, the rows that the teams, the shared groups
+ * and the folded beat path address are inside the call's granule areas, the build is merged exactly where no C role is placed, shared
+ * groups only in a placed launch, every (team, role) the kernel expects appears exactly once among the ids of the grid, every team's
+ * critical roles sit on ONE residue, no residue carries more than 32 live workgroups, grid and live workgroups fit the chip.  0, or -1
+ * for a call the register-resident launch does not take (B > 16, V > 128, no plan fits the chip's INET_CHAIN_CUS / CU count, ...). */
 int inet_decode_b1_plan(int B, int V, int Z, int* out8);
 /* Loads every kernel of the library on the CURRENT device (code objects and function objects, which the HIP runtime otherwise
  * builds lazily on the launch path of each kernel's first launch: csrc/preload.hip) without launching anything.  Idempotent per

@@ -54,6 +54,7 @@
 // instead of two.  The 16 copies run the same instructions on the same values and agree bit for bit.  3.95 -> 3.78 us per tick:
 // less than the 0.8 us a hand-off costs, because an all-gather among 16 waits for the slowest of 16 (1.5 us, profiles/r05_decode_b1_*).
 // Shapes: H = 512, Z = 256, V <= 128, <= 4 beats, B <= 16, inference (no dropout mask, no backward saves); else decode_chain.hip.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include "chain.h"
@@ -936,94 +937,194 @@ int placed_grid(int teams, int rteams, int beat_wgs, int crit = kCrit) {
 
 // The launch plan per call size under mode 4 (the default), in one place.  "critical" = the workgroups on a tick's critical path, which get
 // workgroup ids of one residue mod 8 (one XCD) and XCD-local copies of what they exchange; M = merged build (rows x ceil(V / 32) <= 2).
-//   B = 1        one team, beat path folded in.            M: 16 CB + 16 TA critical (kCritTA), 16 TBh, 80 beat = 129 workgroups
-//   B = 2, 3     B one-row teams, beat path folded in (serves three rows).  M: 32 critical per team                  <= 224
-//   B = 4 (M)    four one-row teams with CB + TA critical, TBh shared in pairs of rows, beat path folded in             240
-//   B = 4 .. 6   B one-row critical teams (16 CB, or C + 16 TBi), TA + TBh shared by groups of three rows, beat folded <= 246
-//   B = 7 .. 10  whole two-row teams (49 workgroups, 17 critical) behind the beat path's own launches                  <= 245
-//   B = 11 .. 16 two-row critical teams (17) + TA / TBh shared by groups of six rows, behind the beat path's launches  <= 232
+// With the beat path folded into the launch (Z = 256, no beat mask):
+//   B = 1        one team.                                  M: 16 CB + 16 TA critical (kCritTA), 16 TBh, 80 beat = 129 workgroups
+//   B = 2, 3     B one-row teams (the beat path serves three rows).  M: 32 critical per team                          <= 224
+//   B = 4 (M)    four one-row teams with CB + TA critical, TBh shared in pairs of rows                                    240
+//   B = 4 .. 6   B one-row critical teams (16 CB, or C + 16 TBi), TA + TBh shared by groups of three rows              <= 246
+// Behind the beat path's own launches (another latent size, a beat mask, or B > 6):
+//   B = 1 .. 3   as above without the beat path's 80 workgroups
+//   B = 4 .. 10  whole two-row teams (49 workgroups, 17 critical; M with V <= 32: 16 CB + 16 TA)                     <= 245
+//   B = 11 .. 16 two-row critical teams (17) + TA / TBh shared by groups of six rows                                  <= 232
 // Modes 1-3 keep round 5's plans (one team up to two rows, two-row teams to ten, four-row teams beyond); mode 5 = test hook.
+// Below the full chip (a partition, INET_CHAIN_CUS): a merged team whose 32 critical workgroups do not fit keeps its 16 CB alone on one
+// residue (never C's idle slot); four measures whose TBh pairs do not fit take the groups of three rows; a plan whose placed grid does
+// not fit runs on consecutive ids -- except shared groups, which exist only placed.  A call with no plan that fits takes the beat path's
+// own launches (folded beat path) or decode_chain.hip's exchange kernel.
 constexpr int kSharedRows = 6;                   // rows a shared recurrent group serves beyond ten measures (8: the group's tick is longer than the two-row teams' and sets the pace)
 constexpr int kSharedRowsSmall = 3;              // ... and for four to six measures, where the critical teams have ONE row
-// Shared recurrent groups under mode 4 (the kernel's "Shared recurrent groups"): four to six measures = one-row critical teams (the
-// 16 CB of the merged build, or C + 16 TBi) + groups of three rows + the beat path's 80 workgroups in the same launch (6 x 17 + 2 x 32
-// + 80 = 246); eleven and more = two-row critical teams + groups of six rows.  (Seven to ten: five whole two-row teams fit the chip.)
-static bool shared_groups(int B) { return mode() == 4 && (B > 10 || (B > kDecodeB1OneRowTeamsMax && B <= kDecodeB1BeatRowsMax)); }
-static int shared_rows(int B) { return B <= kDecodeB1BeatRowsMax ? kSharedRowsSmall : kSharedRows; }
-static int shared_group_count(int B) {
-    const int rows = B <= kDecodeB1BeatRowsMax ? B : 2 * ((B + 1) / 2);         // rows that have a critical team
-    return (rows + shared_rows(B) - 1) / shared_rows(B);
+
+// What launch_decode_b1 launches for a call, as a value (also behind inet_decode_b1_plan: the planner is tested without a GPU).  The
+// plan names its instantiation decode_b1_kernel<nj, fused, nb, nbb, nbr> itself (dispatch_b1).
+struct B1Plan {
+    int fused;                                   // the beat path's workgroups are part of the launch
+    int teams, nb;                               // teams of the tick path's critical workgroups, NB rows each
+    int nbb;                                     // rows the folded beat path computes (NBB; nb without it)
+    int rgroups, nbr;                            // > 0: SHARED recurrent groups of NBR rows each (nbr = nb without them)
+    int nj;                                      // 32-logit blocks of the head
+    int crit;                                    // critical workgroups per team under place_role: kCritTA, NU (merged build) or kCrit
+    int place, stride, grid, live, beat_wgs;
+    int rows;                                    // granule rows the launch addresses
+    bool ok;                                     // the plan fits the chip
+};
+// a candidate plan's rows: teams of nb rows, the folded beat path's nbb, shared groups (ta_crit: the TA stay critical beside the
+// CB of their team and only the TBh are shared)
+struct B1Shape { int nb, nbb, rgroups, nbr; bool ta_crit; };
+
+// the plans a call may get, best first: make_plan takes the first that fits the chip
+static int candidates(int B, int nj, bool fused, B1Shape (&c)[2]) {
+    int n = 0;
+    const auto team = [&](int nb, int nbb) { c[n++] = B1Shape{nb, fused ? nbb : nb, 0, nb, false}; };
+    if (mode() == 4) {
+        if (fused) {
+            // one to three measures: whole one-row teams (round 6).  Two or three of them and the beat path's 80 workgroups fit the chip
+            // (3 x 48 + 80), a one-row tick is 3.2 us (merged build, V <= 64) against 4.6 for a two-row team, and each team's 32
+            // critical workgroups get an XCD of their own -- the reference's non-auto-regressive inpainting call decodes its 2 .. 4
+            // target measures in one call (LatentRNN/latent_rnn.py:237-240)
+            if (B <= kDecodeB1OneRowTeamsMax) team(1, B == 1 ? 1 : kDecodeB1OneRowTeamsMax);
+            else if (B <= kDecodeB1BeatRowsMax) {
+                // four to six: one-row critical teams + shared recurrent groups + the beat path's 80 workgroups (6 x 17 + 2 x 32 + 80 =
+                // 246).  FOUR with the merged build: every team keeps its 16 TA next to its 16 CB on an XCD of its own (layer 0's
+                // recurrent summands stay inside the XCD), only the TBh are shared, two rows per group: 4 x 32 + 2 x 16 + 80 = 240.
+                // (Five and six would need 288 / 336: they keep the groups of three rows for both recurrent sides.)
+                if (B == 4 && nj <= 2) c[n++] = B1Shape{1, kDecodeB1BeatRowsMax, 2, 2, true};
+                c[n++] = B1Shape{1, kDecodeB1BeatRowsMax, (B + kSharedRowsSmall - 1) / kSharedRowsSmall, kSharedRowsSmall, false};
+            }
+        } else if (B <= kDecodeB1OneRowTeamsMax) {
+            team(1, 1);
+        } else if (B <= 10) {
+            // whole two-row teams while five of them fit the chip -- four to six measures too: their one-row teams and groups of three
+            // rows exist for the folded beat path (behind its launches four one-row teams measured 0.181 ms against 0.169 for two
+            // two-row teams)
+            team(2, 2);
+        } else {
+            // eleven and more: two-row critical teams + groups of six rows (8 x 17 + 3 x 32 = 232 at sixteen)
+            c[n++] = B1Shape{2, 2, (2 * ((B + 1) / 2) + kSharedRows - 1) / kSharedRows, kSharedRows, false};
+        }
+    } else if (fused) {                          // modes 3, 5: one team up to two rows, two-row teams up to six with the beat path
+        if (B <= 2) team(B, B);
+        else if (B <= kDecodeB1BeatRowsMax) team(2, kDecodeB1BeatRowsMax);
+    } else {
+        team(B == 1 ? 1 : B <= 10 ? 2 : 4, 0);  // (two-row teams while five fit the chip, four-row teams beyond)
+    }
+    return n;
 }
-int decode_b1_team_rows(int B) {
-    if (B <= 1) return 1;
-    // two or three measures under mode 4: ONE row per team (round 6).  Two or three one-row teams and the beat path's 80 workgroups fit
-    // the chip (3 x 48 + 80), a one-row tick is 3.2 us (merged build, V <= 64) against 4.6 for a two-row team, and each team's 32
-    // critical workgroups get an XCD of their own -- the reference's non-auto-regressive inpainting call decodes its 2 .. 4 target
-    // measures in one call (LatentRNN/latent_rnn.py:237-240)
-    if (mode() == 4 && B <= kDecodeB1BeatRowsMax) return 1;          // (two, three: whole one-row teams; four to six: one-row CRITICAL teams + shared groups)
-    if (B <= 2 || shared_groups(B)) return 2;
-    return B <= 10 ? 2 : 4;                                    // (whole two-row teams while five of them fit the chip; modes 1-3 beyond: four rows)
+
+static B1Plan plan_of(int B, int nj, bool fused, const B1Shape& sh) {
+    B1Plan p{};
+    p.fused = fused; p.nj = nj; p.nb = sh.nb; p.nbb = sh.nbb; p.rgroups = sh.rgroups; p.nbr = sh.nbr;
+    p.teams = (B + sh.nb - 1) / sh.nb;
+    p.beat_wgs = fused ? kFusedRoles - kTickRoles : 0;
+    p.rows = std::max(p.teams * p.nb, p.nbb);    // (a shared group's rows without a team are never touched: Ctx.nact)
+    p.stride = (!fused && mode() == 2 && p.teams == 1) ? 4 : 1;
+    return p;
+}
+
+static B1Plan make_plan(int B, int V, bool fused) {
+    const int nj = (V + 31) / 32, cap = chain_capacity();
+    B1Shape c[2];
+    const int n = (fused && mode() < 3) ? 0 : candidates(B, nj, fused, c);
+    B1Plan p{};
+    for (int i = 0; i < n; ++i) {
+        p = plan_of(B, nj, fused, c[i]);
+        const bool merged = p.nb * nj <= 2;
+        const int rteams = p.rgroups ? p.rgroups : p.teams;
+        const auto grid_of = [&](int crit) { return p.teams <= 8 ? placed_grid(p.teams, rteams, p.beat_wgs, crit) : cap + 1; };
+        // critical workgroups per team: the merged build's TA join its 16 CB where the 32 fit (one XCD per team), else the 16 CB alone
+        p.crit = c[i].ta_crit ? kCritTA : !merged ? kCrit : (!p.rgroups && grid_of(kCritTA) <= cap) ? kCritTA : NU;
+        if (mode() == 4 && grid_of(p.crit) <= cap) {
+            p.place = 1;
+            p.grid = grid_of(p.crit);
+            p.live = p.teams * p.crit + rteams * (p.crit == kCritTA ? NU : 2 * NU) + p.beat_wgs;
+        } else if (!p.rgroups) {                       // (consecutive ids: shared groups exist only placed)
+            p.place = (mode() == 5 && p.stride == 1) ? 2 : 0;
+            p.crit = merged ? NU : kCrit;
+            p.live = p.teams * kTickRoles + p.beat_wgs;
+            p.grid = p.live * p.stride;
+        }
+        p.ok = p.grid > 0 && p.grid <= cap;
+        if (p.ok) return p;
+    }
+    return p;
+}
+
+// The instantiation a plan names: launched, or only looked up (a == null: decode_b1_plan_check).  False where there is none.
+template <int NJ>
+static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
+#define B1_INST(F, NB, NBB, NBR)                                                                                             \
+    if (p.fused == (F) && p.nb == (NB) && p.nbb == (NBB) && p.nbr == (NBR)) {                                               \
+        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR>), dim3(p.grid), dim3(NT), 0, s, *a);                \
+        return true;                                                                                                        \
+    }
+    B1_INST(true, 1, 1, 1)                       // one team, one row, beat path folded in
+    B1_INST(true, 2, 2, 2)                       // ... two rows (modes 3, 5)
+    B1_INST(true, 1, kDecodeB1OneRowTeamsMax, 1) // two / three one-row teams
+    B1_INST(true, 2, kDecodeB1BeatRowsMax, 2)    // two / three two-row teams (modes 3, 5)
+    B1_INST(true, 1, kDecodeB1BeatRowsMax, kSharedRowsSmall)   // one-row critical teams + groups of three rows
+    if constexpr (NJ <= 2) { B1_INST(true, 1, kDecodeB1BeatRowsMax, 2) }   // four merged one-row teams + TBh pairs
+    B1_INST(false, 1, 1, 1)                      // teams of one, two or four rows behind the beat path's launches
+    B1_INST(false, 2, 2, 2)
+    B1_INST(false, 4, 4, 4)
+    B1_INST(false, 2, 2, kSharedRows)            // two-row critical teams + groups of six rows
+#undef B1_INST
+    return false;
+}
+static bool dispatch_b1(const B1Plan& p, const B1Args* a, hipStream_t s) {
+    switch (p.nj) {
+        case 1: return dispatch_b1_nj<1>(p, a, s);
+        case 2: return dispatch_b1_nj<2>(p, a, s);
+        case 3: return dispatch_b1_nj<3>(p, a, s);
+        case 4: return dispatch_b1_nj<4>(p, a, s);
+        default: return false;
+    }
+}
+
+int decode_b1_rows(int B) {
+    int rows = 1;
+    for (int f = 0; f < 2; ++f)
+        for (int nj = 1; nj <= 4; ++nj) {
+            B1Shape c[2];
+            const int n = candidates(B, nj, f != 0, c);
+            for (int i = 0; i < n; ++i) rows = std::max(rows, plan_of(B, nj, f != 0, c[i]).rows);
+        }
+    return rows;
 }
 
 void decode_b1_set_mode(int m) { g_mode = (m < 0 || m > 5) ? 4 : m; }
 
 bool decode_b1_shape_ok(int B, int H, int V, int T, int G) {
     return mode() != 0 && chain_enabled() && B >= 1 && B <= kDecodeB1MaxRows && H == DH && V >= 1 && V <= 128 && T % G == 0 && T / G <= 4 &&
-           kFusedRoles <= chain_capacity() &&
-           (shared_groups(B) ? placed_grid(decode_b1_teams(B), shared_group_count(B), B <= kDecodeB1BeatRowsMax ? kFusedRoles - kTickRoles : 0)
-                             : decode_b1_teams(B) * kTickRoles) <= chain_capacity();
+           kFusedRoles <= chain_capacity() && make_plan(B, V, false).ok;
 }
-// the beat path's 80 workgroups go into the same launch when they fit beside the teams: one team, or two / three two-row teams (B <= 6:
-// 3 x 49 + 80 = 227 of 256 CUs); they then serve all (up to kBeatRowsMax) rows of the call
-bool decode_b1_fused(int Z, int B) {
-    const int teams = decode_b1_teams(B);
-    if (mode() < 3 || Z != DZ) return false;
-    if (shared_groups(B))                                      // four to six measures: one-row critical teams + shared groups + the beat path
-        return B <= kDecodeB1BeatRowsMax && placed_grid(teams, shared_group_count(B), kFusedRoles - kTickRoles) <= chain_capacity();
-    return (teams == 1 || (decode_b1_team_rows(B) == 2 && teams * 2 <= kDecodeB1BeatRowsMax) || (decode_b1_team_rows(B) == 1 && teams <= kDecodeB1OneRowTeamsMax)) &&
-           teams * kTickRoles + (kFusedRoles - kTickRoles) <= chain_capacity();
-}
+bool decode_b1_fused(int Z, int B, int V) { return Z == DZ && make_plan(B, V, true).ok; }
 bool decode_b1_ok(const DecodeChainArgs& a) {
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;
-    return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G) && !train && a.b1ex;
-}
-
-// What launch_decode_b1 decides for a call, as a value (also behind inet_decode_b1_plan: the planner is tested without a GPU).
-struct B1Plan { int teams, nbr, nj, rgroups, crit, place, grid, beat_wgs; bool tbh_pairs; };
-static B1Plan make_plan(int B, int V, bool fused, int stride) {
-    B1Plan p{};
-    p.teams = decode_b1_teams(B);
-    p.rgroups = shared_groups(B) ? shared_group_count(B) : 0;
-    p.nj = (V + 31) / 32; p.nbr = decode_b1_team_rows(B);
-    // FOUR measures with the merged build (V <= 64): every team keeps its 16 TA next to its 16 CB on an XCD of its own (layer 0's
-    // recurrent summands stay inside the XCD), only the TBh are shared, two rows per group: 4 x 32 + 2 x 16 + 80 = 240 workgroups.
-    // (Five and six would need 288 / 336: they keep the groups of three rows for both recurrent sides.)
-    p.tbh_pairs = fused && p.rgroups && B == 4 && p.nbr == 1 && p.nj <= 2;
-    if (p.tbh_pairs) p.rgroups = 2;
-    const int rteams = p.rgroups ? p.rgroups : p.teams;
-    p.beat_wgs = fused ? kFusedRoles - kTickRoles : 0;
-    // teams of the merged build (one row with V <= 64, two with V <= 32): the TA join the critical set -- 32 workgroups = one XCD per team
-    p.crit = p.tbh_pairs ? kCritTA
-             : (!p.rgroups && p.nbr * p.nj <= 2 && placed_grid(p.teams, p.teams, p.beat_wgs, kCritTA) <= chain_capacity()) ? kCritTA
-             : (p.rgroups && p.nbr * p.nj <= 2) ? NU : kCrit;    // (merged build with shared groups: the 16 CB alone are a team's critical set)
-    p.place = mode() == 4 && stride == 1 && placed_grid(p.teams, rteams, p.beat_wgs, p.crit) <= chain_capacity();
-    if (mode() == 5 && stride == 1) { p.place = 2; p.crit = kCrit; }   // (test hook: the request without the placement)
-    p.grid = p.place == 1 ? placed_grid(p.teams, rteams, p.beat_wgs, p.crit) : (p.teams * kTickRoles + p.beat_wgs) * stride;
-    return p;
+    return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr).ok;
 }
 
 // Planner self-check without a GPU (tests/test_decode_plan.py): out[8] = {teams, rows per team, shared groups, critical workgroups per
-// team, placed, grid, live workgroups, ok}.  ok = every (team, role) the kernel expects appears exactly once among the ids of a placed
-// grid, every team's critical roles sit on ids of ONE residue mod 8, no residue carries more than 32 live workgroups (one XCD's CUs),
-// and the grid fits the chip.  Returns 0, or -1 for a call the register-resident launch does not take.
+// team, placed, grid, live workgroups, ok}.  ok = the plan fits the chip and names an instantiation of decode_b1_kernel; every row of
+// the call is in exactly one team; the rows the teams, the shared groups and the folded beat path address are in the call's granule
+// areas (decode_b1_rows), and the beat path computes every team's rows; the kernel shares the recurrent side exactly when the plan
+// has groups, and then the launch is placed; where placed: every (team, role) the kernel expects appears exactly once among the ids of
+// the grid, C's role exactly where the build is not merged, every team's critical roles on ONE residue mod 8, no residue with more than
+// 32 live workgroups (one XCD's CUs).  Returns 0, or -1 for a call the register-resident launch does not take.
 int decode_b1_plan_check(int B, int V, int Z, int* out) {
     if (!out || !decode_b1_shape_ok(B, DH, V, 24, 6)) return -1;
-    const bool fused = decode_b1_fused(Z, B);
-    const B1Plan p = make_plan(B, V, fused, 1);
-    int live = 0, ok = 1;
+    const bool fused = decode_b1_fused(Z, B, V);
+    const B1Plan p = make_plan(B, V, fused);
+    const int cap = chain_capacity();
+    const bool merged = p.nb * p.nj <= 2;                             // the kernel's MG
+    const int team_rows = p.teams * p.nb, group_rows = p.rgroups ? std::min(p.rgroups * p.nbr, team_rows) : 0;
+    bool ok = p.ok && p.fused == (int)fused && dispatch_b1(p, nullptr, nullptr);
+    ok = ok && team_rows >= B && team_rows - p.nb < B;               // every row in a team, no team without a row
+    ok = ok && std::max(team_rows, std::max(group_rows, p.fused ? p.nbb : 0)) <= decode_b1_rows(B);
+    ok = ok && (!p.fused || p.nbb >= team_rows);
+    ok = ok && (p.rgroups > 0) == (p.nbr != p.nb) && (!p.rgroups || (p.rgroups - 1) * p.nbr < team_rows);   // (Ctx.nact >= 1)
+    ok = ok && (!p.rgroups || p.place == 1) && (p.crit != kCritTA || merged) && p.grid <= cap;
+    int live = 0;
     if (p.place == 1) {
         const int rteams = p.rgroups ? p.rgroups : p.teams;
-        const bool merged = p.nbr * p.nj <= 2;
         int per_residue[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         // expected roles: per team the critical ones (+ its own recurrent side unless shared), per shared group its recurrent roles, the beat path
         static int seen[16][kFusedRoles], crit_res[16];
@@ -1031,38 +1132,39 @@ int decode_b1_plan_check(int B, int V, int Z, int* out) {
         for (int b = 0; b < p.grid; ++b) {
             int team = 0, role = 0;
             if (!place_role(b, p.teams, rteams, p.beat_wgs, p.crit, team, role)) continue;
-            if (team < 0 || team >= 16 || role < 0 || role >= kFusedRoles) { ok = 0; continue; }
+            if (team < 0 || team >= 16 || role < 0 || role >= kFusedRoles) { ok = false; continue; }
             ++seen[team][role]; ++live; ++per_residue[b & 7];
             const bool critical = role == R_C || (role >= R_TBI && role < R_TBH) || (p.crit == kCritTA && role >= R_TA && role < R_TBI);
             if (critical && role < kTickRoles) {
                 if (crit_res[team] < 0) crit_res[team] = b & 7;
-                else if (crit_res[team] != (b & 7)) ok = 0;
+                else if (crit_res[team] != (b & 7)) ok = false;
             }
         }
         for (int t = 0; t < p.teams; ++t) {
-            for (int r = R_TBI; r < R_TBH; ++r) if (seen[t][r] != 1) ok = 0;
-            if (!merged && seen[t][R_C] != 1) ok = 0;
-            if (merged && seen[t][R_C] != 0) ok = 0;
+            for (int r = R_TBI; r < R_TBH; ++r) if (seen[t][r] != 1) ok = false;
+            if (seen[t][R_C] != (merged ? 0 : 1)) ok = false;
         }
-        const bool ta_shared = p.rgroups && p.crit != kCritTA;
-        for (int t = 0; t < (ta_shared ? p.rgroups : p.teams); ++t) for (int r = R_TA; r < R_TBI; ++r) if (seen[t][r] != 1) ok = 0;
-        for (int t = 0; t < (p.rgroups ? p.rgroups : p.teams); ++t) for (int r = R_TBH; r < kTickRoles; ++r) if (seen[t][r] != 1) ok = 0;
-        for (int r = kTickRoles; r < kFusedRoles; ++r) if (seen[0][r] != (fused ? 1 : 0)) ok = 0;
-        for (int x = 0; x < 8; ++x) if (per_residue[x] > 32) ok = 0;
-        if (p.grid > chain_capacity() || live > chain_capacity()) ok = 0;
+        // (the kernel's TA are a shared group's where NBR != NB and they are not critical, its TBh wherever NBR != NB)
+        const bool ta_shared = p.nbr != p.nb && p.crit != kCritTA;
+        for (int t = 0; t < (ta_shared ? p.rgroups : p.teams); ++t) for (int r = R_TA; r < R_TBI; ++r) if (seen[t][r] != 1) ok = false;
+        for (int t = 0; t < (p.nbr != p.nb ? p.rgroups : p.teams); ++t) for (int r = R_TBH; r < kTickRoles; ++r) if (seen[t][r] != 1) ok = false;
+        for (int r = kTickRoles; r < kFusedRoles; ++r) if (seen[0][r] != (p.fused ? 1 : 0)) ok = false;
+        for (int x = 0; x < 8; ++x) if (per_residue[x] > 32) ok = false;
+        if (live != p.live) ok = false;
     } else {
-        live = p.grid;
-        if (p.grid > chain_capacity()) ok = 0;
+        live = p.live;
     }
-    out[0] = p.teams; out[1] = p.nbr; out[2] = p.rgroups; out[3] = p.crit; out[4] = p.place; out[5] = p.grid; out[6] = live; out[7] = ok;
+    if (live > cap) ok = false;
+    out[0] = p.teams; out[1] = p.nb; out[2] = p.rgroups; out[3] = p.crit; out[4] = p.place; out[5] = p.grid; out[6] = live; out[7] = ok;
     return 0;
 }
 
 int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
+    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr);
+    if (!pl.ok || pl.rows > decode_b1_rows(d.B)) return -1;   // (decode_b1_ok has accepted the call: not reached)
     B1Args a{};
-    a.fused = d.beat.z != nullptr;
-    a.teams = decode_b1_teams(d.B);
-    a.B = d.B; a.T = d.T; a.G = d.G; a.V = d.V; a.Z = DZ; a.stride = (!a.fused && mode() == 2 && a.teams == 1) ? 4 : 1;
+    a.fused = pl.fused; a.teams = pl.teams; a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place; a.stride = pl.stride;
+    a.B = d.B; a.T = d.T; a.G = d.G; a.V = d.V; a.Z = DZ;
     a.W_hh0 = d.W_hh0; a.b_hh0 = d.b_hh0; a.cgi = d.cgi; a.table = d.table;
     a.W_ih1 = d.W_ih1; a.b_ih1 = d.b_ih1; a.W_hh1 = d.W_hh1; a.b_hh1 = d.b_hh1;
     a.W_out = d.W_out; a.b_out = d.b_out; a.ht0 = d.ht0;
@@ -1070,6 +1172,7 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     a.bp = d.beat;
     a.stamps = d.b1stamps;
     a.status = d.status;
+    if (!dispatch_b1(pl, nullptr, nullptr)) return -1;        // (a plan without an instantiation launches nothing)
     char label[64];
     std::snprintf(label, sizeof label, "decode_b1%s T%d B%d H%d V%d", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
     // algorithmic work: the tick GRU + head per tick and row; fused: + the beat path (z2b, two beat layers, three projections per beat)
@@ -1078,26 +1181,6 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     const double beat_w = a.fused ? 2.0 * DH * DZ + 9.0 * DH * DH + 3.0 * DH * DH + 3.0 * DH * DH : 0.0;
     ProfScope prof(PROF_GRU_FWD, 2.0 * d.B * (d.T * (9.0 * DH * DH + (double)d.V * DH) + beat_mac), s, label,
                    4.0 * (9.0 * DH * DH + (double)d.V * DH + (double)d.B * d.T * d.V + beat_w));
-    const B1Plan pl = make_plan(d.B, d.V, a.fused != 0, a.stride);
-    a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place;
-    const int nj = pl.nj, nbr = pl.nbr;
-    const bool tbh_pairs = pl.tbh_pairs;
-    if (pl.rgroups && pl.place != 1) return -1;                // (decode_b1_shape_ok has checked that the placed launch fits)
-    const dim3 grid(pl.grid);
-    if (a.fused && a.teams > 1 && (nbr > 2 || a.teams * nbr > ((nbr == 1 && !a.rgroups) ? kDecodeB1OneRowTeamsMax : kDecodeB1BeatRowsMax))) return -1;
-#define DISPATCH_B1(NJ, NBR)                                                                                                    \
-    do {                                                                                                                    \
-        if (tbh_pairs && NJ <= 2) hipLaunchKernelGGL((decode_b1_kernel<(NJ <= 2 ? NJ : 1), true, 1, kDecodeB1BeatRowsMax, 2>), grid, dim3(NT), 0, s, a); \
-        else if (a.fused && a.rgroups) hipLaunchKernelGGL((decode_b1_kernel<NJ, true, 1, kDecodeB1BeatRowsMax, kSharedRowsSmall>), grid, dim3(NT), 0, s, a); \
-        else if (a.fused && a.teams > 1 && nbr == 1) hipLaunchKernelGGL((decode_b1_kernel<NJ, true, 1, kDecodeB1OneRowTeamsMax>), grid, dim3(NT), 0, s, a); \
-        else if (a.fused && a.teams > 1) hipLaunchKernelGGL((decode_b1_kernel<NJ, true, 2, kDecodeB1BeatRowsMax>), grid, dim3(NT), 0, s, a); \
-        else if (a.fused) hipLaunchKernelGGL((decode_b1_kernel<NJ, true, NBR, NBR>), grid, dim3(NT), 0, s, a);             \
-        else if (a.rgroups) hipLaunchKernelGGL((decode_b1_kernel<NJ, false, 2, 2, kSharedRows>), grid, dim3(NT), 0, s, a);     \
-        else hipLaunchKernelGGL((decode_b1_kernel<NJ, false, NBR, NBR>), grid, dim3(NT), 0, s, a);                        \
-    } while (0)
-#define DISPATCH_B1N(NJ) do { if (nbr == 1) DISPATCH_B1(NJ, 1); else if (nbr == 2) DISPATCH_B1(NJ, 2); else DISPATCH_B1(NJ, 4); } while (0)
-    if (nj <= 1) DISPATCH_B1N(1); else if (nj == 2) DISPATCH_B1N(2); else if (nj == 3) DISPATCH_B1N(3); else DISPATCH_B1N(4);
-#undef DISPATCH_B1N
-#undef DISPATCH_B1
+    dispatch_b1(pl, &a, s);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

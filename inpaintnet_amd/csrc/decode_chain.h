@@ -56,24 +56,17 @@ constexpr int kDecodeB1WordsPerRow = 2 * 35392;   // 32-bit words of ONE row's g
 constexpr int kDecodeB1StampWords = 2 * 2 * 32 * 8;   // 32-bit words of the stamp area (2 roles x <= 32 ticks x 8 stamps of 8 bytes)
 constexpr int kDecodeB1MaxRows = 16;              // rows (measures) per call the register-resident launch takes: 1 / 2 / 4 per team of
                                                   // workgroups, up to five teams (tick path only beyond one team)
-// rows per team and teams for a call of B rows.  One team up to B = 2; beyond, teams of TWO rows while they fit
-// the chip (a two-row tick is 5.5 us, a four-row tick 8.4: 5 teams x 49 workgroups = 245 of 256 CUs -> B <= 10), else of four.
-int decode_b1_team_rows(int B);                   // (decode_b1.hip: the rule above; mode 4 shares the recurrent groups beyond ten measures)
-inline int decode_b1_teams(int B) { const int r = decode_b1_team_rows(B); return (B + r - 1) / r; }
+// How a call of B rows is split into teams of the tick path's workgroups, whether the beat path goes into the same launch and
+// which kernel instantiation runs it is ONE decision: decode_b1.hip's make_plan (the plans per call size are listed above it).
 constexpr int kDecodeB1BeatRowsMax = 6;           // rows the beat path's workgroups serve when they share the launch with several teams
 constexpr int kDecodeB1OneRowTeamsMax = 3;        // ... with ONE-row teams (two or three measures under mode 4): the beat path serves three rows
-// granule areas of a call: one per row of every team; three to six measures: at least kDecodeB1BeatRowsMax (the folded beat path
-// computes that many rows, whatever B is -- rows beyond B repeat row B - 1)
-inline int decode_b1_rows(int B) {
-    const int r = decode_b1_teams(B) * decode_b1_team_rows(B);
-    if (decode_b1_teams(B) > 1 && decode_b1_team_rows(B) == 1)          // (one-row teams: the folded beat path computes three rows, or six)
-        return r <= kDecodeB1OneRowTeamsMax ? kDecodeB1OneRowTeamsMax : kDecodeB1BeatRowsMax;
-    return (decode_b1_teams(B) > 1 && B <= kDecodeB1BeatRowsMax && r < kDecodeB1BeatRowsMax) ? kDecodeB1BeatRowsMax : r;
-}
+// granule areas of a call: the most rows any plan of B measures addresses under the current mode -- fused or not, any V, any capacity
+// (the workspace is carved before the call knows whether its beat path is folded in; rows beyond B repeat row B - 1)
+int decode_b1_rows(int B);
 inline long decode_b1_words(int B) { return (long)decode_b1_rows(B) * kDecodeB1WordsPerRow; }
-bool decode_b1_shape_ok(int B, int H, int V, int T, int G);
-bool decode_b1_fused(int Z, int B);                    // ... and the beat path goes into the same launch
-bool decode_b1_ok(const DecodeChainArgs& a);
+bool decode_b1_shape_ok(int B, int H, int V, int T, int G);   // a launchable plan with the beat path's own launches in front
+bool decode_b1_fused(int Z, int B, int V);                    // ... and one with the beat path folded into the same launch
+bool decode_b1_ok(const DecodeChainArgs& a);                  // the plan of this call (beat.z != null: folded) is launchable
 int launch_decode_b1(const DecodeChainArgs& a, hipStream_t s);
 void decode_b1_set_mode(int m);
 // the launch plan of a call of B measures (V notes, latent size Z) and a host-side self-check of it: decode_b1.hip, no GPU needed
