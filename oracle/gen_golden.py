@@ -11,11 +11,25 @@ inputs + the reference's outputs to tests/golden/*.npz.  Those fixtures are
 data; no reference source travels.
 
     python oracle/gen_golden.py            # regenerates every fixture
+    python oracle/gen_golden.py dropout    # only the *_drop.npz fixtures (reference in train() with dropout on)
 
 Control of randomness in the reference:
   * eps of Normal.rsample    -> torch.distributions.normal._standard_normal patched
   * teacher-forcing coin     -> random.random patched in MeasureVAE.decoder / LatentRNN.latent_rnn
-  * dropout                  -> model.eval(), or dropout prob 0.0 in the constructors
+  * dropout, plain fixtures  -> model.eval(), or dropout prob 0.0 in the constructors
+  * dropout, *_drop fixtures -> left ON (0.5 in every GRU, Dropout2d(0.2) on the AnticipationRNN's inputs) and RECORDED:
+                                MaskRecorder snapshots torch's generator in front of every recurrent / Dropout2d call and
+                                replays the draw afterwards.  A fused 2-layer nn.GRU draws its inter-layer mask as
+                                empty((T, B, D*H)).bernoulli_(1 - p).div_(1 - p): time-major also for batch_first modules.
+                                Every recovered mask is checked bit-exactly against the reference module itself (fused
+                                module == two one-layer modules with the mask between them), never against the oracle.
+
+What the *_drop fixtures pin to the reference: where each mask acts (between the layers, never after the last), its memory
+order, its 1/(1-p) scale, which of the 24 single-tick calls gets which mask, that LatentRNN.train() leaves the frozen VAE
+in training mode (its encoder and decoder drop too), and that the AnticipationRNN's `dropout_prob` does nothing (its LSTMs
+are one-layer modules called without a dropout layer).  What they do not pin: the product's mask GENERATOR
+(inet_dropout_mask is the project's own counter-based stream and is not meant to reproduce torch's), and the backward of
+the free-running AnticipationRNN pass (the reference's own backward of that path fails on the CPU under torch 2.x).
 """
 import os
 import sys
@@ -389,6 +403,312 @@ def gen_arnn(name, c):
     print("wrote arnn_%s.npz (%d arrays)" % (name, len(fx)))
 
 
+# ----------------------------------------------------------------------------
+# Dropout ON: recorded masks (fixtures *_drop.npz)
+# ----------------------------------------------------------------------------
+class MaskRecorder:
+    """Hooks on every nn.GRU / nn.LSTM / nn.Dropout2d below `model`.  The pre-hook stores torch's generator state; the
+    forward hook replays the module's draw from that state (so nobody has to model the order in which the reference draws:
+    Normal.sample() of the prior sits between the encoder's and the decoder's masks), checks the recovered mask against the
+    module's own output WITHOUT the oracle, and appends (tag, keep flags, p) in call order.
+
+      GRU, 2 layers, training, p > 0: mask = empty((T, B, D*H)).bernoulli_(1 - p).div_(1 - p)  (time-major also for
+          batch_first); check: layer 0 and layer 1 as two one-layer nn.GRU's built from the module's weights, the mask
+          between them, torch.equal with the fused module's output and final hidden state.
+      Dropout2d on (B, L, E, 1): mask (B, L, 1, 1); check: torch.equal(output, input * mask).
+      one-layer LSTM (AnticipationRNN, constructed with dropout=dropout_prob): must not touch the generator at all."""
+
+    def __init__(self, model):
+        self.records = []          # (tag, keep uint8 (T, B, D*H) | (B, L), p)
+        self.calls = {}            # tag -> number of calls seen
+        self.untouched = 0         # recurrent calls checked to draw nothing
+        self._state = {}
+        self._handles = []
+        for name, mod in model.named_modules():
+            if isinstance(mod, (torch.nn.GRU, torch.nn.LSTM, torch.nn.Dropout2d)):
+                self._handles.append(mod.register_forward_pre_hook(self._pre))
+                self._handles.append(mod.register_forward_hook(lambda m, a, o, tag=name: self._post(tag, m, a, o)))
+
+    def close(self):
+        for h in self._handles:
+            h.remove()
+
+    def _pre(self, mod, args):
+        self._state[id(mod)] = torch.get_rng_state()
+
+    @staticmethod
+    def _draw(state, shape, p):
+        g = torch.Generator()
+        g.set_state(state)
+        return torch.empty(shape).bernoulli_(1 - p, generator=g).div_(1 - p)
+
+    def _post(self, tag, mod, args, out):
+        state = self._state.pop(id(mod))
+        self.calls[tag] = self.calls.get(tag, 0) + 1
+        if isinstance(mod, torch.nn.Dropout2d):
+            assert mod.training and mod.p > 0
+            x = args[0]
+            mask = self._draw(state, (x.shape[0], x.shape[1], 1, 1), mod.p)
+            assert x.shape[3] == 1 and torch.equal(out, x * mask), f"{tag}: Dropout2d mask not recovered"
+            self.records.append((tag, (mask[:, :, 0, 0] != 0).numpy().astype(np.uint8), mod.p))
+            return
+        if not (mod.training and mod.dropout > 0 and mod.num_layers > 1):
+            assert torch.equal(torch.get_rng_state(), state), f"{tag}: a call without inter-layer dropout drew random numbers"
+            self.untouched += 1
+            return
+        assert isinstance(mod, torch.nn.GRU) and mod.num_layers == 2 and mod.batch_first
+        x, hx = args
+        y, hn = out
+        D = 2 if mod.bidirectional else 1
+        B, T, H = x.shape[0], x.shape[1], mod.hidden_size
+        mask = self._draw(state, (T, B, D * H), mod.dropout)
+        with torch.no_grad():
+            halves = []
+            for layer in range(2):
+                g1 = torch.nn.GRU(mod.input_size if layer == 0 else D * H, H, num_layers=1, bidirectional=mod.bidirectional,
+                                  batch_first=True)
+                for d in range(D):
+                    sfx = "_reverse" if d else ""
+                    for w in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+                        getattr(g1, f"{w}_l0{sfx}").copy_(getattr(mod, f"{w}_l{layer}{sfx}"))
+                halves.append(g1)
+            y0, h0 = halves[0](x.detach(), hx.detach()[:D].contiguous())
+            y1, h1 = halves[1](y0 * mask.transpose(0, 1), hx.detach()[D:].contiguous())
+        ok = torch.equal(y1, y.detach()) and torch.equal(torch.cat((h0, h1), 0), hn.detach())
+        assert ok, f"{tag} call {self.calls[tag]}: recovered mask does not reproduce the fused module bit-exactly"
+        self.records.append((tag, (mask != 0).numpy().astype(np.uint8), mod.dropout))
+
+    def take(self):
+        r, self.records = self.records, []
+        return r
+
+
+def pack_masks(records, prefix=""):
+    """Keep flags as packed bits, in the reference's call order: `mask_tags` (n,), `mask_shapes` (n, 3) (Dropout2d: (B, L, 1)),
+    `mask_p` (n,), `mask_bits` (all masks' flags concatenated, np.packbits)."""
+    shapes = np.array([tuple(k.shape) + (1,) * (3 - k.ndim) for _, k, _ in records], dtype=np.int64).reshape(-1, 3)
+    flat = np.concatenate([k.reshape(-1) for _, k, _ in records]) if records else np.zeros(0, np.uint8)
+    return {prefix + "mask_tags": np.array([t for t, _, _ in records]),
+            prefix + "mask_shapes": shapes,
+            prefix + "mask_p": np.array([p for _, _, p in records], dtype=np.float64),
+            prefix + "mask_bits": np.packbits(flat)}
+
+
+def differs_enough(name, what, with_dropout, without):
+    """The control that keeps a *_drop fixture from being vacuous: the captured output must differ from the same model's
+    dropout-0 output (same weights, inputs, eps, coin) by more than 10 % of its maximum."""
+    a, b = with_dropout.detach().double(), without.detach().double()
+    d = float((a - b).abs().max() / a.abs().max())
+    print("    %s %s: |dropout - no dropout| = %.3f of max" % (name, what, d))
+    assert d > 0.10, f"{name} {what}: dropout moves the output by only {d:.3g} of its maximum; fixture refused"
+
+
+def gen_vae_drop(name, c):
+    """MeasureVAE in train() with encoder / decoder dropout 0.5, both coins, five steps of the reference VAETrainer with
+    fresh masks every step; stored like gen_vae's step_* entries plus every mask (1 encoder + 1 beat + 24 tick per step)."""
+    V, Z, B = c["V"], c["Z"], c["B"]
+    full_tensors = name != "full"
+    tokens = torch.from_numpy(synthetic.det_tokens("tokens/" + name, (B, 24), V))
+    fx = {"tokens": tokens.numpy()}
+    torch.manual_seed(20250 + len(name))
+    for mode, coin in (("tf", 0.0), ("fr", 0.9)):
+        model = build_vae(c, dropout=0.5)
+        load_det_weights(model)
+        twin = build_vae(c, dropout=0.0)
+        load_det_weights(twin)
+        trainer = VAETrainer(FakeDataset(V), model, lr=1e-4)
+        model.train()
+        twin.train()
+        set_coin(coin)
+        rec = MaskRecorder(model)
+        losses, records, steps = [], [], []
+        with EpsQueue() as q:
+            for step in range(5):
+                eps = q.push(f"eps/{name}/{step}", (B, Z))
+                fx[f"step_{mode}_eps{step}"] = eps.numpy()
+                if step == 0:
+                    q.q.append(eps)
+                    with torch.no_grad():
+                        w0 = twin(tokens, train=True)[0]
+                trainer.zero_grad()
+                weights_, samples_, z_dist, prior_dist, z_tilde, z_prior = model(tokens, train=True)
+                ce = trainer.mean_crossentropy_loss(weights=weights_, targets=tokens)
+                kl = trainer.compute_kld_loss(z_dist, prior_dist)
+                acc = trainer.mean_accuracy(weights=weights_, targets=tokens)
+                loss = ce + kl
+                loss.backward()
+                got = rec.take()
+                assert [t for t, _, _ in got] == ["encoder.lstm", "decoder.rnn_beat"] + ["decoder.rnn_tick"] * 24
+                records += got
+                steps += [step] * len(got)
+                if step == 0:
+                    differs_enough(f"vae_{name}_drop", mode + " weights", weights_, w0)
+                    fx[f"step_{mode}_weights"] = weights_.detach().numpy()
+                    fx[f"step_{mode}_samples"] = samples_.detach().numpy()
+                    fx[f"step_{mode}_margin"] = top2_margin(weights_.detach())
+                    fx[f"step_{mode}_z"] = z_tilde.detach().numpy()
+                    # `mid` keeps whole gradient tensors for the teacher-forced pass and digests (norm, sum, first and last 64
+                    # elements) for the free-running one, which goes through the same backward kernels with other tokens fed:
+                    # gradients do not compress, and two whole sets (1.3 MB) would make this fixture the largest file in the
+                    # repository bar vae_mid.npz; small carries both passes whole
+                    for k, v in grads_of(model, full_tensors and not (name == "mid" and mode == "fr")).items():
+                        fx[f"step_{mode}_{k}"] = v
+                assert not q.q, "eps queue must be fully consumed each step"
+                trainer.step()
+                losses.append([loss.item(), ce.item(), kl.item(), acc.item()])
+                if step in (0, 4):
+                    for k, v in param_digest(model, name == "small").items():
+                        fx[f"step_{mode}_after{step + 1}/{k}"] = v
+        rec.close()
+        fx[f"step_{mode}_losses"] = np.array(losses, dtype=np.float64)
+        fx.update(pack_masks(records, f"step_{mode}_"))
+        fx[f"step_{mode}_mask_step"] = np.array(steps, dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, f"vae_{name}_drop.npz"), **fx)
+    print("wrote vae_%s_drop.npz  (%d arrays)" % (name, len(fx)))
+
+
+def gen_latent_drop(name, c, auto_reg, coin):
+    """gen_latent with dropout 0.5 in the LatentRNN AND in the VAE it was built over: LatentRNN.train() puts the frozen VAE
+    in training mode too, so its encoder and decoder drop (106 recorded GRU calls; 113 on the free-running AR path)."""
+    V, Z, B, H = c["V"], c["Z"], c["B"], c["H"]
+    full_tensors = name != "full"
+    tag = f"latent_{name}_{'ar' if auto_reg else 'nar'}_{'tf' if coin < 0.5 else 'fr'}"
+    n_past, n_target, n_future = 6, 4, 6
+    score = torch.from_numpy(synthetic.folk_score(B, V, seed=3))
+    fx = {"score": score.numpy(), "split": np.array([n_past, n_target, n_future])}
+    past, future, target = LatentRNNTrainer.split_score(score, n_past, n_future, n_target, 24)
+    torch.manual_seed(20260 + len(tag))
+
+    def run(dropout, rec_on):
+        vae = build_vae(c, dropout=dropout)
+        load_det_weights(vae)
+        model = LatentRNN(FakeDataset(V), vae, num_rnn_layers=2, rnn_hidden_size=H, dropout=dropout,
+                          rnn_class=torch.nn.GRU, auto_reg=auto_reg, teacher_forcing=True)
+        load_det_weights(model)
+        trainer = LatentRNNTrainer(FakeDataset(V), model, lr=1e-4)
+        model.train()
+        set_coin(coin)
+        rec = MaskRecorder(model) if rec_on else None
+        with EpsQueue() as q:
+            e_p = q.push(f"eps_p/{tag}", (B * n_past, Z))
+            e_f = q.push(f"eps_f/{tag}", (B * n_future, Z))
+            e_t = q.push(f"eps_t/{tag}", (B * n_target, Z))
+            fx["eps_past"], fx["eps_future"], fx["eps_target"] = e_p.numpy(), e_f.numpy(), e_t.numpy()
+            if auto_reg and coin >= 0.5:
+                for i in range(n_target):
+                    fx[f"eps_ar{i}"] = q.push(f"eps_ar{i}/{tag}", (B, Z)).numpy()
+            trainer.zero_grad()
+            assert vae.training and vae.encoder.lstm.training and vae.decoder.rnn_tick.training
+            out = model(past, future, target, n_target, train=True)
+            assert vae.training and not q.q
+        return vae, model, trainer, rec, out
+
+    with torch.no_grad():
+        w0 = run(0.0, False)[4][0]
+    vae, model, trainer, rec, (weights, samples, gen_z) = run(0.5, True)
+    differs_enough(tag + "_drop", "weights", weights, w0)
+    records = rec.take()
+    rec.close()
+    dec = ["vae_model.decoder.rnn_beat"] + ["vae_model.decoder.rnn_tick"] * 24
+    enc = ["vae_model.encoder.lstm"]
+    if auto_reg and coin >= 0.5:
+        expect = enc * 3 + ["context_rnn_past", "context_rnn_future"] + (["generation_rnn"] + dec + enc) * n_target
+    else:
+        expect = enc * 3 + ["context_rnn_past", "context_rnn_future", "generation_rnn"] + dec * n_target
+    assert [t for t, _, _ in records] == expect, "the reference's call order is not the one the fixture documents"
+    fx.update(pack_masks(records))
+    loss = trainer.mean_crossentropy_loss_alt(weights=weights, targets=target)
+    acc = trainer.mean_accuracy_alt(weights=weights, targets=target)
+    loss.backward()
+    fx["weights"] = weights.detach().numpy()
+    fx["samples"] = samples.detach().numpy()
+    fx["margin"] = top2_margin(weights.detach())
+    fx["gen_z"] = gen_z.detach().numpy()
+    fx["loss_acc"] = np.array([loss.item(), acc.item()], dtype=np.float64)
+    for k, v in grads_of(model, full_tensors).items():
+        fx[k] = v
+    assert all(p.grad is None for p in vae.parameters()), "the frozen VAE must not receive gradients"
+    trainer.step()
+    for k, p in model.named_parameters():
+        if p.requires_grad:
+            v = p.detach().numpy()
+            if full_tensors:
+                fx["after1/" + k] = v.copy()
+            else:
+                fx["after1sum/" + k] = np.float64(v.astype(np.float64).sum())
+                fx["after1head/" + k] = v.reshape(-1)[:64].copy()
+    np.savez_compressed(os.path.join(OUT, tag + "_drop.npz"), **fx)
+    print("wrote %s_drop.npz (%d arrays, %d masks)" % (tag, len(fx), len(records)))
+
+
+def gen_arnn_drop(name, c):
+    """gen_arnn's teacher-forced step with dropout_input_prob=0.2 (Dropout2d on the shifted note embeddings: one keep flag per
+    (sequence, tick), batch-major) and dropout_prob=0.5, which must do NOTHING: the reference's LSTMs are lists of one-layer
+    modules called without a dropout layer (MaskRecorder asserts that none of the four calls touches the generator)."""
+    V, B, L = c["V"], c["B"], 384
+    full_tensors = name != "full"
+    ds = FakeDataset(V)
+
+    def build(p_in, p):
+        m = ConstraintModelGaussianReg(ds, note_embedding_dim=c["E"], metadata_embedding_dim=c["Em"],
+                                       num_lstm_constraints_units=c["H"], num_lstm_generation_units=c["H"],
+                                       linear_hidden_size=c["LH"], num_layers=2, dropout_input_prob=p_in,
+                                       dropout_prob=p, unary_constraint=True, teacher_forcing=True)
+        load_det_weights(m)
+        with torch.no_grad():
+            for k, t in m.named_parameters():
+                if "embeddings" in k:
+                    # nn.Embedding's own N(0, 1) scale, which the reference keeps for this model (it has no xavier pass);
+                    # at det_param's xavier scale the notes move the logits too little for the 10 % control below
+                    t.mul_(float(np.sqrt((t.shape[0] + t.shape[1]) / 2.0)))
+        m.train()
+        return m
+    model = build(0.2, 0.5)
+    fx = {"param/" + k: v.numpy().copy() for k, v in model.state_dict().items() if full_tensors or "embeddings" in k}
+    fx.update({"param_keys": np.array(list(model.state_dict().keys())),
+          "param_shapes": np.array([",".join(str(d) for d in v.shape) for v in model.state_dict().values()])})
+    score = torch.from_numpy(synthetic.folk_score(B, V, seed=11)).long()
+    metadata = torch.from_numpy(synthetic.folk_metadata(B)).long()
+    metadata[..., 0] = torch.from_numpy(synthetic.det_tokens("arnn/md0", (B, 1, L), 6))
+    n_past, n_target = 6, 4
+    start_tick, end_tick = (n_past + 1) * 24, (n_past + 1) * 24 + n_target * 24
+    loc = torch.zeros_like(score)
+    loc[:, :, :start_tick] = 1
+    loc[:, :, end_tick:] = 1
+    fx["score"], fx["metadata"], fx["constraints_loc"] = score.numpy(), metadata.numpy(), loc.numpy()
+    fx["ticks"] = np.array([start_tick, end_tick])
+    set_coin(0.0)
+    with torch.no_grad():
+        w0 = build(0.0, 0.0)._forward_tf(score, metadata, loc)[0][0]
+    torch.manual_seed(20270 + len(name))
+    trainer = AnticipationRNNGaussianRegTrainer(ds, model, lr=1e-4)
+    rec = MaskRecorder(model)
+    seen = []
+    h = model.linear_ouput_notes[0].register_forward_hook(lambda m, a, o: seen.append(o.detach().clone()))
+    trainer.zero_grad()
+    loss, acc = trainer.loss_and_acc_for_batch((score, metadata, loc, start_tick, end_tick), 0, train=True)
+    loss.backward()
+    h.remove()
+    records = rec.take()
+    rec.close()
+    assert [t for t, _, _ in records] == ["dropout_layer"] and rec.untouched == 4 and len(seen) == 1
+    differs_enough(f"arnn_{name}_drop", "weights", seen[0], w0)
+    fx.update(pack_masks(records))
+    fx["tf_weights_all"] = seen[0].numpy()
+    fx["tf_loss_acc"] = np.array([loss.item(), acc.item()], dtype=np.float64)
+    for k, v in grads_of(model, full_tensors).items():
+        fx["tf_" + k] = v
+    trainer.step()
+    for k, p in model.named_parameters():
+        v = p.detach().numpy()
+        if full_tensors:
+            fx["tf_after1/" + k] = v.copy()
+        else:
+            fx["tf_after1head/" + k] = v.reshape(-1)[:64].copy()
+    np.savez_compressed(os.path.join(OUT, f"arnn_{name}_drop.npz"), **fx)
+    print("wrote arnn_%s_drop.npz (%d arrays)" % (name, len(fx)))
+
+
 def gen_split_helpers():
     """split_score / split_to_measures / process_batch_data index contract (a9, a15)."""
     V = 12
@@ -601,7 +921,7 @@ def gen_feed_helpers():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["vae", "latent", "arnn", "split", "feed", "ablation", "inference", "inpaint"]
+    which = sys.argv[1:] or ["vae", "latent", "arnn", "split", "feed", "ablation", "inference", "inpaint", "dropout"]
     if "vae" in which:
         for n, c in CFGS.items():
             gen_vae(n, c)
@@ -627,3 +947,15 @@ if __name__ == "__main__":
         gen_inference()
     if "inpaint" in which:
         gen_arnn_inpaint()
+    if "dropout" in which:
+        # last: these draw from torch's global generator, which none of the fixtures above depends on
+        for n, c in CFGS.items():
+            gen_vae_drop(n, c)
+        c = dict(CFGS["small"])
+        gen_latent_drop("small", c, auto_reg=False, coin=0.9)
+        gen_latent_drop("small", c, auto_reg=True, coin=0.0)
+        gen_latent_drop("small", c, auto_reg=True, coin=0.9)
+        c = dict(CFGS["full"], B=2)
+        gen_latent_drop("full", c, auto_reg=True, coin=0.9)
+        for n, c in ARNN_CFGS.items():
+            gen_arnn_drop(n, c)

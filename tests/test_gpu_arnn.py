@@ -203,7 +203,8 @@ def test_arnn_free_running_forward_golden(name):
 
 def test_arnn_free_running_backward_vs_oracle():
     """The reference trains through this path on GPU; its backward cannot run on CPU (in-place on a saved view), so
-    the gradient check is against the oracle's autograd over the same arithmetic."""
+    the gradient check is against the oracle's autograd over the same arithmetic.  This stays ORACLE-ONLY also with dropout on: the
+    *_drop fixtures (tests/test_gpu_dropout_golden.py) pin the teacher-forced step to the reference, not this path's backward."""
     name = "small"
     fx = G.load("arnn_" + name)
     ds, model = build(name)
