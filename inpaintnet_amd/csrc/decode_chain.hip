@@ -460,8 +460,6 @@ inline int groups_of(int B) { const int ms = rows_ms(B); return (B + 16 * ms - 1
 bool decode_chain_ok(int B, int H, int V, int T, int G) {
     if (!chain_enabled() || (H != 256 && H != 512) || B < 1 || V < 1 || V > 128 || T % G != 0) return false;
     if (groups_of(B) > kDecodeMaxGroups || groups_of(B) * (H / 16) > chain_capacity()) return false;   // every workgroup resident at once
-    constexpr bool off = false;
-    if (off) return false;
     const int ms = rows_ms(B);
     return ((V + 15) / 16) * ms <= H / 16;                   // one member per (row block, 16-column block) logits tile
 }
@@ -507,12 +505,10 @@ int launch_decode_chain(DecodeChainArgs a, hipStream_t s) {
         else { if (ms == 1) DISPATCH_DC(1, 4, true); else if (ms == 2) DISPATCH_DC(2, 4, true); else DISPATCH_DC(4, 4, true); }
     } else {
         // small-batch inference (one row block per group, V <= 64): every member computes the whole logits row itself
-        constexpr bool fullv = true;
-        const int nv = (fullv && ms == 1 && a.V <= 64) ? (a.V <= 48 ? 3 : 4) : 0;
+        const int nv = (ms == 1 && a.V <= 64) ? (a.V <= 48 ? 3 : 4) : 0;
         // one row (b = 1 inpainting): the contractions on the VALU instead of one-sixteenth-full MFMA tiles
-        constexpr bool valu = true;
         // (one row only: the four-row build of the H = 512 kernel spills ~300 registers)
-        const int vr = (valu && nv > 0 && a.B == 1) ? 1 : 0;
+        const int vr = (nv > 0 && a.B == 1) ? 1 : 0;
         if (nv == 3 && vr == 1) { if (a.H == 512) DISPATCH_DC5(1, 8, false, 3, 1); else DISPATCH_DC5(1, 4, false, 3, 1); }
         else if (nv == 4 && vr == 1) { if (a.H == 512) DISPATCH_DC5(1, 8, false, 4, 1); else DISPATCH_DC5(1, 4, false, 4, 1); }
         else if (nv == 3) { if (a.H == 512) DISPATCH_DC4(1, 8, false, 3); else DISPATCH_DC4(1, 4, false, 3); }

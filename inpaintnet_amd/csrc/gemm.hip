@@ -711,7 +711,6 @@ __global__ void gemm_epilogue_kernel(float* __restrict__ C, long ldc, int M, int
     }
 }
 
-bool gemv_enabled() { return true; }
 int g_force_cfg = -2, g_force_split = 0;      // -2: not read yet (inet_set_option keys 2, 3), -1: cost model
 int g_direct = 1;    // direct kernels (inet_set_option key 5): 0 never, 1 (default) by shape, 2 direct whenever applicable, 3 big shapes only, 4 split-K first
 
@@ -730,11 +729,9 @@ int launch_gemm_direct(const GemmArgs& gin, hipStream_t s, int force_split) {
     const int kSplits[] = {1, 2, 4, 8, 16, 32};
     double best = 1e300;
     int bi = -1, bs = 1;
-    constexpr int only_cfg = -1;
     for (int ci = 0; ci < 3; ++ci) {
         const DirectCfg& c = kDirect[ci];
         if (g.M % (64 * c.ta) || g.N % (64 * c.tb)) continue;
-        if (only_cfg >= 0 && ci != only_cfg) continue;
         const long tiles = (long)(g.M / (64 * c.ta)) * (g.N / (64 * c.tb));
         for (int sp : kSplits) {
             if (sp > 1 && (g.K / sp < 64 || (nonlinear && g.acc != ACC_STORE))) break;
@@ -858,14 +855,13 @@ int launch_gemm_ks(const GemmArgs& gin, hipStream_t s, int force_split) {
     const double kL2[] = {1.0, 1.15, 1.5, 0.95, 0.95};
     int bi = -1, bs = 1;
     double best = 1e300;
-    constexpr bool wide46 = true;
     for (int ci = 0; ci < 5; ++ci) {
         const KsCfg& c = kKs[ci];
         if (g.M % (16 * c.ta) || g.N % (16 * c.tb)) continue;
         if (ci == 3 && !(g.a_kmajor && g.K >= 2048)) continue;
         // 64 x 96 tiles (k-contiguous A): products whose 64 x 64 tiling needs two rounds of workgroups and whose 64 x 32 tiling pays
         // for it in L2 traffic (M1024 N1536 K512: 256 tiles instead of 384 / 768)
-        if (ci == 4 && (g.a_kmajor || !wide46)) continue;
+        if (ci == 4 && g.a_kmajor) continue;
         const long tiles = (long)(g.M / (16 * c.ta)) * (g.N / (16 * c.tb));
         for (int sp = 1; sp <= 8; sp *= 2) {
             if (sp > 1 && (!g.a_kmajor || g.K / sp < 1024 || nonlinear)) break;
@@ -920,11 +916,10 @@ void launch_ks_group(const GemmGroupArgs& a, bool akm, bool bkm, dim3 grid, hipS
 }
 
 // Independent products in ONE launch of the workgroup split-K kernel when all of them have the same operand layout and a
-// common tile shape divides them (a switch of earlier rounds ran them one after the other); else one launch each.
+// common tile shape divides them; else one launch each.
 int launch_gemm_group(const GemmArgs* list, int n, hipStream_t s) {
-    constexpr bool grouped = true;
     {   // a group of few-row products of one M (the beat -> tick projections of a b = 1 decode call): one launch of the wave-per-column kernel
-        bool gv = grouped && n >= 2 && n <= kGemmGroupMax && g_force_cfg < 0 && gemv_enabled() && list[0].M >= 1 && list[0].M <= 8;
+        bool gv = n >= 2 && n <= kGemmGroupMax && g_force_cfg < 0 && list[0].M >= 1 && list[0].M <= 8;
         int maxN = 0;
         double flops = 0, bytes = 0;
         for (int i = 0; i < n && gv; ++i) {
@@ -957,7 +952,7 @@ int launch_gemm_group(const GemmArgs* list, int n, hipStream_t s) {
             return hipGetLastError() == hipSuccess ? 0 : -2;
         }
     }
-    bool ok = grouped && n >= 2 && n <= kGemmGroupMax && g_direct > 0 && g_direct != 3 && g_force_cfg < 0;
+    bool ok = n >= 2 && n <= kGemmGroupMax && g_direct > 0 && g_direct != 3 && g_force_cfg < 0;
     for (int i = 0; i < n && ok; ++i) {
         const GemmArgs& g = list[i];
         ok = g.M > 0 && g.N > 0 && g.K >= 64 && g.nbatch <= 1 && g.acc != ACC_ATOMIC && !(g.a_kmajor && !g.b_kmajor) &&
@@ -1039,9 +1034,8 @@ int launch_gemm(const GemmArgs& gin, hipStream_t s) {
     if (g.nbatch > 1) {
         // several products of one shape: one launch of the shared-strip direct kernel when it applies (half the split-K
         // factor of a single product for the same 256 workgroups), else one product after the other
-        constexpr bool batched = true;
         int rc = 1;
-        if (batched && g_direct > 0 && g_direct != 4 && g_force_cfg < 0) rc = launch_gemm_direct(gin, s, g_force_split > 0 ? g_force_split : 0);
+        if (g_direct > 0 && g_direct != 4 && g_force_cfg < 0) rc = launch_gemm_direct(gin, s, g_force_split > 0 ? g_force_split : 0);
         if (rc != 1) return rc;
         for (int i = 0; i < gin.nbatch; ++i) {
             GemmArgs one = gin;
@@ -1051,7 +1045,7 @@ int launch_gemm(const GemmArgs& gin, hipStream_t s) {
         }
         return 0;
     }
-    if (g.M <= 8 && !g.a_kmajor && !g.b_kmajor && g.nbatch <= 1 && g_force_cfg < 0 && g.acc != ACC_ATOMIC && gemv_enabled()) {
+    if (g.M <= 8 && !g.a_kmajor && !g.b_kmajor && g.nbatch <= 1 && g_force_cfg < 0 && g.acc != ACC_ATOMIC) {
         char label[64];
         std::snprintf(label, sizeof label, "M%d N%d K%d NT gemv e%d", g.M, g.N, g.K, g.epi);
         ProfScope prof(PROF_GEMM, 2.0 * g.M * g.N * g.K, s, label, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));

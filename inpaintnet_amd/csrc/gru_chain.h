@@ -27,7 +27,7 @@ struct ChainEmit {
     unsigned char* colsA; long colsA_piece; int colsA_rb0, colsA_n;
     unsigned char* colsB; long colsB_piece; int colsB_rb0;
     int B_full, r0;
-    int skip_dgi, skip_dgh;                       // backward: the f32 dgi / dgh arrays have no reader left, do not write them
+    int skip_dgi, skip_dgh;                       // nothing sets these two or colsA_n (the removed second-generation BPTT kernel's)
 };
 
 struct GruChainFwdProb {
@@ -51,7 +51,7 @@ struct GruChainFwdProb {
 };
 struct GruChainFwd {
     int H, B, T, nprob, tiles_per_prob, members, prio;
-    int h0_packed;                                // slot 1 of every hx already holds h0 (packed by the host: a removed A/B switch of round 2)
+    int h0_packed;                                // nothing sets it: the kernels publish h0 into slot 1 of every hx themselves
     int fault;                                    // test hook (inet_set_option key 6): workgroup 0 leaves at once, so its
                                                   // group runs into the bounded spin and the failure path can be tested
     int shared_chip;                              // this launch runs beside another chain launch (two workgroups per CU):
@@ -89,17 +89,13 @@ struct GruChainBwd {
 
 bool gru_chain_ok(int H, int B, int T, int nprob);
 bool gru_chain_bwd_ok(int H, int B, int T, int nprob);      // as above, with two row tiles per workgroup when needed
-int launch_gru_chain_fwd(GruChainFwd a, hipStream_t s);     // (dispatches to the second generation where it applies)
-int launch_gru_chain_bwd(GruChainBwd a, hipStream_t s);
-// which generation the two launchers above pick for a shape (second: the ChainEmit outputs are written)
-bool gru_chain_fwd_is_v2(int H, int B, int T, int nprob, int h0_packed);
-bool gru_chain_bwd_is_v2(int H, int B, int T, int nprob);
+int launch_gru_chain_fwd(GruChainFwd a, hipStream_t s);     // (dispatches to the second generation where gru_chain2_ok)
+int launch_gru_chain_bwd(GruChainBwd a, hipStream_t s);     // (always the first generation)
 bool gru_chain_bwd_emits_rows(int H, int B, int T, int nprob);   // first-generation BPTT launch that writes ChainEmit.rows
 // Second generation (gru_chain2.hip): one row block per wave, W in LDS, contraction on the bf16 matrix cores at fp32
 // accuracy (three-way exact split, 9 or 6 piece products).  Its exchange holds three bf16 pieces per state: rings must be
 // sized 3 * pk_floats(B, K) floats (seq.h chain_ring_floats) instead of 2 * pk_floats.
 int chain2_mode();                                          // 0 = off (INET_CHAIN2=0), 9 piece products (default)
 void chain2_set_mode(int np);
-bool gru_chain2_ok(int H, int B, int T, int nprob);
-bool gru_chain2_emits(int H, int B, int T, int nprob);      // ... and its build writes the ChainEmit outputs (four waves)
+bool gru_chain2_ok(int H, int B, int T, int nprob);         // the forward launch is second-generation: it writes the ChainEmit outputs
 int launch_gru_chain2_fwd(GruChainFwd a, hipStream_t s);

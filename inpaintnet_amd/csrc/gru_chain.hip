@@ -374,27 +374,17 @@ __global__ __launch_bounds__(256) void gru_chain_bwd_kernel(GruChainBwd A) {
 // kChainMaxGroups groups).  A chain step is hand-off latency plus the MFMAs of ONE workgroup, so more, smaller groups
 // shorten every step: B = 128 with two directions runs 8 groups of 32 rows instead of 4 of 64.
 int rows_ms(int B, int H, int nprob) {
-    constexpr int force = 0;
-    if (force > 0) return B <= 16 ? 1 : (B <= 32 ? 2 : 4);                 // the fixed rule of the first chain kernels
     for (int ms = 1; ms <= 4; ms *= 2) {
         const int groups = nprob * ((B + 16 * ms - 1) / (16 * ms));
         if (groups * (H / 16) <= chain_capacity() && groups <= kChainMaxGroups) return ms;
     }
     return 4;
 }
-int chain_prio() {
-    static int v = -1;
-    if (v < 0) v = 1;
-    return v;
-}
-
 }  // namespace
 
 // H = 1024 (LatentRNN's generator; round 4): first-generation kernels with 192 registers of W_hh per lane, a group's 64 members
-// on two XCDs (chain.h decode_block); (rounds 1-3 ran that layer on the per-step kernels)
-static bool h1024_on() { return true; }
+// on two XCDs (chain.h decode_block)
 bool gru_chain_ok(int H, int B, int T, int nprob) {
-    if (H == 1024 && !h1024_on()) return false;
     if ((double)T * B * 6.0 * H >= 2.0e9) return false;   // the kernels index with 32-bit element offsets
     if (!chain_enabled() || (H != 256 && H != 512 && H != 1024) || T < 2 || nprob < 1 || nprob > 4 || B < 1) return false;
     const int ms = rows_ms(B, H, nprob), tiles = (B + 16 * ms - 1) / (16 * ms);
@@ -405,37 +395,25 @@ bool gru_chain_ok(int H, int B, int T, int nprob) {
 // workgroups: the decoder's tick layers run their 4 beats as 4 problems x 256 rows.
 int rows_ms_bwd(int H, int B, int nprob) {
     const int ms = rows_ms(B, H, nprob);
-    constexpr bool wide = true;
-    if (wide && H <= 512 && ms == 4 && B >= 128 && nprob * ((B + 63) / 64) * (H / 16) > chain_capacity()) return 8;
+    if (H <= 512 && ms == 4 && B >= 128 && nprob * ((B + 63) / 64) * (H / 16) > chain_capacity()) return 8;
     return ms;
 }
 bool gru_chain_bwd_ok(int H, int B, int T, int nprob) {
-    if (H == 1024 && !h1024_on()) return false;
     if ((double)T * B * 6.0 * H >= 2.0e9) return false;
     if (!chain_enabled() || (H != 256 && H != 512 && H != 1024) || T < 2 || nprob < 1 || nprob > 4 || B < 1) return false;
     const int ms = rows_ms_bwd(H, B, nprob), tiles = (B + 16 * ms - 1) / (16 * ms);
     return nprob * tiles * (H / 16) <= chain_capacity() && nprob * tiles <= kChainMaxGroups;
 }
 
-bool gru_chain_fwd_is_v2(int H, int B, int T, int nprob, int h0_packed) {
-    constexpr bool v2f = true;
-    return v2f && !h0_packed && gru_chain2_ok(H, B, T, nprob);
-}
-// The BPTT chains run on the FIRST generation: its kernel takes 28 KB of LDS and ~300 registers per lane, so the leaf work of the
-// backward pass (weight-gradient products, column sums, the bf16-pipe products' split launches) shares the CUs with it.  A
-// second-generation BPTT kernel existed in round 3 (the faster kernel alone, 220 vs 232 us per 24-step launch; the slower step, 3.73
-// vs 3.62 ms: a workgroup held 148-160 KB of its CU's LDS for the length of the chain) and was removed in round 4 (HISTORY.md).
-bool gru_chain_bwd_is_v2(int, int, int, int) { return false; }
-
 int launch_gru_chain_fwd(GruChainFwd a, hipStream_t s) {
-    if (gru_chain_fwd_is_v2(a.H, a.B, a.T, a.nprob, a.h0_packed)) return launch_gru_chain2_fwd(a, s);
+    if (gru_chain2_ok(a.H, a.B, a.T, a.nprob)) return launch_gru_chain2_fwd(a, s);
     if (!gru_chain_ok(a.H, a.B, a.T, a.nprob)) return -1;
     const int ms = rows_ms(a.B, a.H, a.nprob);
     a.tiles_per_prob = (a.B + 16 * ms - 1) / (16 * ms);
     a.members = a.H / 16;
     const int groups = a.nprob * a.tiles_per_prob;
     if (groups > kChainMaxGroups) return -1;
-    a.prio = chain_prio();
+    a.prio = 1;
     a.fault = chain_take_fault();
     if (!a.prezeroed && hipMemsetAsync(a.counters, 0, kChainSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
     a.status = chain_status_for(a.counters + kChainStatusWord);
@@ -456,8 +434,12 @@ int launch_gru_chain_fwd(GruChainFwd a, hipStream_t s) {
 
 // the first-generation BPTT launch for this shape writes ChainEmit.rows itself (H = 512, 64 rows per workgroup)
 bool gru_chain_bwd_emits_rows(int H, int B, int T, int nprob) {
-    return !gru_chain_bwd_is_v2(H, B, T, nprob) && H == 512 && gru_chain_bwd_ok(H, B, T, nprob) && rows_ms_bwd(H, B, nprob) == 4;
+    return H == 512 && gru_chain_bwd_ok(H, B, T, nprob) && rows_ms_bwd(H, B, nprob) == 4;
 }
+// The BPTT chains run on the FIRST generation: its kernel takes 28 KB of LDS and ~300 registers per lane, so the leaf work of the
+// backward pass (weight-gradient products, column sums, the bf16-pipe products' split launches) shares the CUs with it.  A
+// second-generation BPTT kernel existed in round 3 (the faster kernel alone, 220 vs 232 us per 24-step launch; the slower step, 3.73
+// vs 3.62 ms: a workgroup held 148-160 KB of its CU's LDS for the length of the chain) and was removed in round 4 (HISTORY.md).
 int launch_gru_chain_bwd(GruChainBwd a, hipStream_t s) {
     if (!gru_chain_bwd_ok(a.H, a.B, a.T, a.nprob)) return -1;
     const int ms = rows_ms_bwd(a.H, a.B, a.nprob);
@@ -465,16 +447,13 @@ int launch_gru_chain_bwd(GruChainBwd a, hipStream_t s) {
     a.members = a.H / 16;
     const int groups = a.nprob * a.tiles_per_prob;
     if (groups > kChainMaxGroups) return -1;
-    a.prio = chain_prio();
+    a.prio = 1;
     if (!a.prezeroed && hipMemsetAsync(a.counters, 0, kChainSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
     a.status = chain_status_for(a.counters + kChainStatusWord);
-    // row pieces of dgi (ChainEmit.rows): written by the H = 512, 64-rows-per-workgroup build; everything else of the descriptor is
-    // the second generation's (the callers split what was not written)
+    // row pieces of dgi (ChainEmit.rows): written by the H = 512, 64-rows-per-workgroup build; nothing else of the descriptor is
+    // read (the callers split what was not written)
     bool emr = a.H == 512 && ms == 4;
-    for (int i = 0; i < a.nprob; ++i) {
-        emr = emr && a.p[i].em.rows;
-        a.p[i].em.colsA = a.p[i].em.colsB = nullptr; a.p[i].em.skip_dgi = a.p[i].em.skip_dgh = 0;
-    }
+    for (int i = 0; i < a.nprob; ++i) emr = emr && a.p[i].em.rows;
     if (!emr) for (int i = 0; i < a.nprob; ++i) a.p[i].em.rows = nullptr;
     char label[72];
     std::snprintf(label, sizeof label, "gru_chain_bwd ms%d%s np%d T%d B%d H%d", ms, emr ? "e" : "", a.nprob, a.T, a.B, a.H);

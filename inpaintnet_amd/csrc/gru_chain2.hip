@@ -18,7 +18,7 @@
 // Semantics (operand sources, masks, saves, h0 / hlast / dh0, reverse, row chunks) are those of the first-generation kernels;
 // tests run both against the oracle (INET_CHAIN2=0 selects the first generation).  The forward kernel is the default for chains of
 // >= 6 steps; the second-generation BPTT kernel was removed in round 4: it was the faster kernel alone and the slower step, because a workgroup
-// of it holds the CU's LDS and keeps the backward pass's leaf work out (gru_chain.hip gru_chain_bwd_is_v2).
+// of it holds the CU's LDS and keeps the backward pass's leaf work out (gru_chain.hip launch_gru_chain_bwd).
 #include <cstdio>
 #include <cstdlib>
 #include "chain.h"
@@ -415,66 +415,54 @@ int chain2_mode() {
 }
 void chain2_set_mode(int np) { g_chain2 = np == 9 ? 9 : 0; }
 
-// waves per workgroup (4 or 8) with which the launch fits the chip and the sync area, or 0
-static int chain2_waves(int H, int B, int T, int nprob) {
+// The launch fits the chip and the sync area: four waves per workgroup (one per SIMD), one row block each.
+bool gru_chain2_ok(int H, int B, int T, int nprob) {
     // (T >= 6: a launch first splits its 96 KB W slice into 144 KB of bf16 pieces in LDS; over the beat GRU's four steps that
     //  costs more than the faster steps give back: 31 -> 43 us per launch)
-    if (!chain_enabled() || chain2_mode() == 0 || (H != 256 && H != 512) || T < 6 || nprob < 1 || nprob > 4 || B < 1) return 0;
-    if ((double)T * B * 6.0 * H >= 2.0e9) return 0;
+    if (!chain_enabled() || chain2_mode() == 0 || (H != 256 && H != 512) || T < 6 || nprob < 1 || nprob > 4 || B < 1) return false;
+    if ((double)T * B * 6.0 * H >= 2.0e9) return false;
     const int nrb = (B + 15) / 16;
-    if (nprob * nrb > kChainMaxGroups) return 0;               // one counter per (problem, row block)
-    // Four waves per workgroup (one per SIMD).  (Eight -- two row blocks per SIMD -- fit the decoder's four-beat tick BPTT into one
-    // launch, but two waves of a SIMD do not overlap: 128 us against 127 for the first generation's two-tiles-per-workgroup form;
-    // that build was removed in round 4, those shapes stay on the first generation.)
-    return nprob * ((nrb + 3) / 4) * (H / 16) <= chain_capacity() ? 4 : 0;
+    if (nprob * nrb > kChainMaxGroups) return false;           // one counter per (problem, row block)
+    // (Eight waves -- two row blocks per SIMD -- fit the decoder's four-beat tick BPTT into one launch, but two waves of a SIMD do
+    // not overlap: 128 us against 127 for the first generation's two-tiles-per-workgroup form; that build was removed in round 4,
+    // those shapes stay on the first generation.)
+    return nprob * ((nrb + 3) / 4) * (H / 16) <= chain_capacity();
 }
-bool gru_chain2_ok(int H, int B, int T, int nprob) { return chain2_waves(H, B, T, nprob) > 0; }
-bool gru_chain2_emits(int H, int B, int T, int nprob) { return chain2_waves(H, B, T, nprob) == 4; }
 
 int launch_gru_chain2_fwd(GruChainFwd a, hipStream_t s) {
-    const int wv = chain2_waves(a.H, a.B, a.T, a.nprob);
-    if (!wv) return -1;
+    if (!gru_chain2_ok(a.H, a.B, a.T, a.nprob)) return -1;
     const int nrb = (a.B + 15) / 16;
-    a.tiles_per_prob = (nrb + wv - 1) / wv;
+    a.tiles_per_prob = (nrb + 3) / 4;
     a.members = a.H / 16;
     const int groups = a.nprob * a.tiles_per_prob;
     a.prio = 1;
     a.fault = chain_take_fault();
     if (!a.prezeroed && hipMemsetAsync(a.counters, 0, kChainSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
     a.status = chain_status_for(a.counters + kChainStatusWord);
-    const int np = chain2_mode();
     const double rows = (double)a.nprob * a.T * a.B;
-    bool em = false;                                           // piece outputs wanted (four-wave build only): the EM build
+    bool em = false;                                           // piece outputs wanted: the EM build
     for (int i = 0; i < a.nprob; ++i) em = em || a.p[i].em.rows || a.p[i].em.colsA || a.p[i].em.colsB;
-    if (wv != 4) { em = false; for (int i = 0; i < a.nprob; ++i) a.p[i].em = ChainEmit{}; }
-    char label[72];                                            // "v2w4e": the build that writes piece outputs
-    std::snprintf(label, sizeof label, "gru_chain_fwd v2w%d%s p%d np%d T%d B%d H%d", wv, em ? "e" : "", np, a.nprob, a.T, a.B, a.H);
+    char label[72];                                            // "v2w4e": the build that writes piece outputs; p9: nine piece products
+    std::snprintf(label, sizeof label, "gru_chain_fwd v2w4%s p9 np%d T%d B%d H%d", em ? "e" : "", a.nprob, a.T, a.B, a.H);
     double em_bytes = 0.0;                                     // piece outputs: 6 bytes per element and layout
     for (int i = 0; i < a.nprob; ++i)
         em_bytes += 6.0 * a.T * a.B * a.H * ((a.p[i].em.rows ? 1 : 0) + (a.p[i].em.colsA ? 1 : 0) + (a.p[i].em.colsB ? 1 : 0));
     ProfScope prof(PROF_GRU_FWD, 2.0 * rows * 3.0 * a.H * a.H, s, label,
                    4.0 * (a.nprob * 3.0 * a.H * a.H + rows * a.H * (2 + 3 + (a.p[0].sv ? 5 : 0))) + em_bytes);
     const dim3 grid(chain::blocks_for(groups, a.members));
-    const size_t lds = (size_t)3 * 3 * (a.H / 32) * 1024 + (size_t)wv * 256 * 4 * (em ? 4 : 1);
-#define DISPATCH_C2F_(W, S, N, E)                                                                                           \
+    const size_t lds = (size_t)3 * 3 * (a.H / 32) * 1024 + (size_t)4 * 256 * 4 * (em ? 4 : 1);
+#define DISPATCH_C2F(S, E)                                                                                              \
     do {                                                                                                                \
         static bool attr = false;                                                                                       \
         if (!attr) {                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_chain2_fwd_kernel<W, S, N, E>),                \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_chain2_fwd_kernel<4, S, 9, E>),                \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                          \
             attr = true;                                                                                                \
         }                                                                                                               \
-        hipLaunchKernelGGL((gru_chain2_fwd_kernel<W, S, N, E>), grid, dim3(64 * W), lds, s, a);                         \
+        hipLaunchKernelGGL((gru_chain2_fwd_kernel<4, S, 9, E>), grid, dim3(256), lds, s, a);                            \
     } while (0)
-#define DISPATCH_C2F(W, S, N)                                                                                               \
-    do {                                                                                                                \
-        if (em) DISPATCH_C2F_(4, S, N, true);                                                                               \
-        else DISPATCH_C2F_(4, S, N, false);                                                                                 \
-    } while (0)
-    if (np != 9 || wv != 4) return -1;
-    if (a.H == 512) DISPATCH_C2F(4, 16, 9);
-    else DISPATCH_C2F(4, 8, 9);
+    if (a.H == 512) { if (em) DISPATCH_C2F(16, true); else DISPATCH_C2F(16, false); }
+    else { if (em) DISPATCH_C2F(8, true); else DISPATCH_C2F(8, false); }
 #undef DISPATCH_C2F
-#undef DISPATCH_C2F_
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

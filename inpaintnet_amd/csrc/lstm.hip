@@ -590,8 +590,6 @@ int launch_chain(K kernel, const A& a, int groups, hipStream_t s) {
 // hand-off latency plus the MFMAs of ONE workgroup (B = 32, H = 256: 1.9 of 4.1 us with 32 rows per workgroup), so more,
 // smaller groups shorten every step (AnticipationRNN: two 16-row groups instead of one 32-row group)
 inline int chain_ms(int B, int H) {
-    constexpr int force = 0;
-    if (force == 1 || force == 2 || force == 4) return force;
     for (int ms = 1; ms <= 4; ms *= 2) {
         const int groups = (B + 16 * ms - 1) / (16 * ms);
         if (groups * (H / 16) <= chain_capacity() && groups <= 32) return ms;
@@ -695,19 +693,17 @@ namespace {
 // (the state after step s_lo - 1: rows of `out` / `cseq`, or zeros).  The kernel sees a sequence of nt steps whose
 // buffers start at the chunk's lowest time index; the saves keep the full sequence's array stride.
 int lstm_chunk_fwd(int B, int T, int H, const float* gi, const float* W_hh, const float* b_hh, const float* hprev,
-                   const float* cprev, int reverse, float* out, LstmWs& w, int save, int s_lo, int nt, hipStream_t s, int xrot = 0,
-                   bool ring_goes_on = false) {
+                   const float* cprev, int reverse, float* out, LstmWs& w, int save, int s_lo, int nt, hipStream_t s, int xrot) {
     const long BH = (long)B * H, TBH = (long)T * BH;
     const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
     const long t_lo = reverse ? T - (s_lo + nt) : s_lo;
     // tagged hand-off (lstm_chain_fwd_tag_kernel) for the small tiles; the counter protocol otherwise.  (The same
     // for the backward chain -- 16 fragments per lane to poll, four gate blocks per member to wait for -- measured slower
     // than its counter: 9.34 vs 9.23 ms per AnticipationRNN step with both, 8.87 with the forward chains only.)
-    constexpr bool tag_on = true;
-    const bool tagged = tag_on && H == 256 && chain_ms(B, H) <= 2;
+    const bool tagged = H == 256 && chain_ms(B, H) <= 2;
     // counters zeroed; tagged: slots 0, 1 armed and slot 3 = the previous step's h; counter protocol: slot 1 = that h
-    // (a tagged chunk behind another chunk of the same layer and call finds all of that in the ring: ring_goes_on)
-    const bool cont = tagged && ring_goes_on && s_lo > 0;
+    // (a tagged chunk behind another chunk of the same layer and call finds all of that in the ring)
+    const bool cont = tagged && s_lo > 0;
     if (!cont) {
         hipLaunchKernelGGL(lstm_chunk_prologue_kernel, dim3(16, 2), dim3(256), 0, s, w.sync, kSyncWords,
                            reinterpret_cast<unsigned*>(w.hx), tagged ? 2L * (long)pk_floats(B, H) : 0L, hprev, B, H,
@@ -800,21 +796,19 @@ int lstm2_seq_fwd(int B, int T, int H, const float* gi0, const float* W_hh0, con
     const long BH = (long)B * H;
     if (pw_zero(w0.zeros, BH, s) != 0 || pw_zero(w1.zeros, BH, s) != 0) return -2;
     hipStream_t s2 = twin_fork(s);
-    constexpr bool third = true;
-    constexpr bool ring_on = true;
     for (int s_lo = 0; s_lo < T; s_lo += CH) {
         const int nt = T - s_lo < CH ? T - s_lo : CH;
         const long t_lo = reverse ? T - (s_lo + nt) : s_lo, tp = reverse ? t_lo + nt : t_lo - 1;
         INET_TRY(lstm_chunk_fwd(B, T, H, gi0, W_hh0, b_hh0, s_lo ? out0 + tp * BH : w0.zeros, s_lo ? w0.cseq + tp * BH : w0.zeros,
-                                reverse, out0, w0, save, s_lo, nt, s, 0, ring_on));
+                                reverse, out0, w0, save, s_lo, nt, s, 0));
         // the chunk's projection gi1 = out0 W_ih1^T + b_ih1 on a THIRD stream (a side stream forked behind layer 0's chunk), so
         // that layer 1's queue holds nothing but its chain launches: the product (30 us) runs under layer 1's previous chunk
-        hipStream_t s3 = third ? side_fork(s) : s2;
+        hipStream_t s3 = side_fork(s);
         if (s3 == s2 || s3 == s) { s3 = s2; INET_TRY(stream_wait(s2, s)); }
         INET_TRY(linear_fwd(out0 + t_lo * BH, H, W_ih1, H, b_ih1, gi1 + t_lo * B * 4 * H, 4L * H, nt * B, 4 * H, H, EPI_NONE, s3));
         if (s3 != s2) INET_TRY(stream_wait(s2, s3));
         INET_TRY(lstm_chunk_fwd(B, T, H, gi1, W_hh1, b_hh1, s_lo ? out1 + tp * BH : w1.zeros, s_lo ? w1.cseq + tp * BH : w1.zeros,
-                                reverse, out1, w1, save, s_lo, nt, s2, lstm_pipe_xrot(), ring_on));
+                                reverse, out1, w1, save, s_lo, nt, s2, lstm_pipe_xrot()));
     }
     return s2 != s ? twin_join(s) : 0;
 }
@@ -835,7 +829,6 @@ int lstm2_seq_bwd(int B, int T, int H, const float* W_hh0, const float* W_ih1, c
     INET_TRY(pw_transpose(W_hh0, H, w0.whhT, 4L * H, 4 * H, H, s));
     INET_TRY(pw_transpose(W_hh1, H, w1.whhT, 4L * H, 4 * H, H, s));
     hipStream_t s2 = twin_fork(s);
-    constexpr bool third = true;
     const int nchunks = (T + CH - 1) / CH;
     const bool areas = nchunks <= kMaxChunks;            // one pre-zeroed counter area per chunk and layer
     if (areas && (hipMemsetAsync(w0.sync + kSyncWords, 0, (kSyncWordsAll - kSyncWords) * sizeof(unsigned), s) != hipSuccess ||
@@ -851,7 +844,7 @@ int lstm2_seq_bwd(int B, int T, int H, const float* W_hh0, const float* W_ih1, c
         float* ou0 = w0.carry + (long)(c & 1) * 2 * BH;
         INET_TRY(lstm_chunk_bwd(B, T, H, dout1, c ? in1 : nullptr, c ? in1 + BH : nullptr, reverse, dgi1, db_ih1, db_hh1,
                                 s_lo ? ou1 : nullptr, s_lo ? ou1 + BH : nullptr, w1, s_lo, nt, s, areas ? c : -1));
-        hipStream_t s3 = third ? side_fork(s) : s2;          // (as in the forward pipeline: the chunk's product on a third stream)
+        hipStream_t s3 = side_fork(s);                       // (as in the forward pipeline: the chunk's product on a third stream)
         if (s3 == s2 || s3 == s) { s3 = s2; INET_TRY(stream_wait(s2, s)); }
         INET_TRY(linear_dgrad(dgi1 + t_lo * B4H, 4L * H, W_ih1, H, dout0 + t_lo * BH, H, nt * B, 4 * H, H, EPI_NONE, nullptr, 0,
                               ACC_STORE, s3));
@@ -863,18 +856,15 @@ int lstm2_seq_bwd(int B, int T, int H, const float* W_hh0, const float* W_ih1, c
     // was slower -- 9.2 -> 10.5 ms per AnticipationRNN step: beside the chains they slow every hand-off):
     // dW_hh += sum_t dg(t)^T h_prev(t) with h_prev(t) = out(t -/+ 1) (zero initial state); dW_ih1 += dgi1^T out0.
     // Layer 1's two products start when ITS last chunk is done -- the caller's stream, before it joins layer 0's -- and run under
-    // layer 0's last chunk; only dW_hh0 is left behind the pipeline (a switch of round 4 put all three behind it).
-    constexpr bool early = true;
-    auto wgrad1 = [&](hipStream_t ss) -> int {
+    // layer 0's last chunk; only dW_hh0 is left behind the pipeline.
+    if (dW_hh0) {
+        hipStream_t ss = side_fork(s);
         INET_TRY(linear_wgrad(reverse ? dgi1 : dgi1 + B4H, 4L * H, reverse ? out1 + BH : out1, H, dW_hh1, H, (T - 1) * B, 4 * H, H, ss));
         INET_TRY(linear_wgrad(dgi1, 4L * H, out0, H, dW_ih1, H, T * B, 4 * H, H, ss));
-        return 0;
-    };
-    if (dW_hh0 && early) INET_TRY(wgrad1(side_fork(s)));
+    }
     if (s2 != s) INET_TRY(twin_join(s));
     if (dW_hh0) {
         hipStream_t ss = side_fork(s);
-        if (!early) INET_TRY(wgrad1(ss));
         INET_TRY(linear_wgrad(reverse ? dgi0 : dgi0 + B4H, 4L * H, reverse ? out0 + BH : out0, H, dW_hh0, H, (T - 1) * B, 4 * H, H, ss));
     }
     return side_join(s);

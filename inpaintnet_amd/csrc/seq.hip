@@ -17,10 +17,8 @@ static int chunk_max_rows() {
 }
 int chain_chunk_rows(int H, int B, int T, int nd, int save) {
     if (gru_chain_ok(H, B, T, nd)) return B;
-    // (forward-only passes -- LatentRNN's frozen encoder, 2048 rows -- chunk at any size: two chunks run side by side there;
-    //  no cap)
-    constexpr int fwd_cap = 1 << 30;
-    if (B > (save ? chunk_max_rows() : fwd_cap)) return 0;
+    // (forward-only passes -- LatentRNN's frozen encoder, 2048 rows -- chunk at any size: two chunks run side by side there)
+    if (save && B > chunk_max_rows()) return 0;
     for (int ch = 1024; ch >= 64; ch >>= 1)
         if (ch < B && B % ch == 0 && gru_chain_ok(H, ch, T, nd)) return ch;
     return 0;
@@ -49,9 +47,27 @@ void bf3_set_emit_mask(int m) { g_emit_mask = m & 7; }
 bool gru_layer_fwd_emits(int H, int B, int T, int nd, bool save) {
     if (!pk_ok(H) || B % 32) return false;
     if (!gru_chain_ok(H, B, T, nd) && gru_step_bf3_ok(H, B, T, nd)) return false;   // (the step kernels write row pieces only)
-    if (gru_chain_ok(H, B, T, nd)) return gru_chain_fwd_is_v2(H, B, T, nd, 0) && gru_chain2_emits(H, B, T, nd);
+    if (gru_chain_ok(H, B, T, nd)) return gru_chain2_ok(H, B, T, nd);
     const int CH = chain_chunk_rows(H, B, T, nd, save);
-    return CH > 0 && CH < B && CH % 32 == 0 && gru_chain_fwd_is_v2(H, CH, T, nd, 0) && gru_chain2_emits(H, CH, T, nd);
+    return CH > 0 && CH < B && CH % 32 == 0 && gru_chain2_ok(H, CH, T, nd);
+}
+// One direction's descriptor for the chain / bf16-pipe step launches over the rows from r0 on.  The caller sets the exchange ring
+// (hx, hx_slot_bytes), the piece outputs (em) and, for a row chunk, the saves' full-batch time stride (sv_ts).
+static GruChainFwdProb fwd_prob(const DirFwd& D, long r0, int H) {
+    GruChainFwdProb P{};
+    P.W_hh = D.W_hh; P.b_hh = D.b_hh;
+    P.h0 = D.h0 ? D.h0 + r0 * D.h0_ld : nullptr; P.ld_h0 = D.h0_ld;
+    P.gi_dense = D.gi ? D.gi + r0 * D.gi_ld : nullptr; P.ld_gi = D.gi_ld; P.ts_gi = D.gi_ts;
+    P.gi_table = D.table; P.ld_table = D.table_ld;
+    P.idx = D.idx ? D.idx + r0 * D.idx_bs : nullptr; P.idx_bs = D.idx_bs; P.idx_ts = D.idx_ts;
+    P.gi_vec = D.gvec;
+    P.out = D.out + r0 * D.out_ld; P.ld_out = D.out_ld; P.ts_out = D.out_ts;
+    P.outm = D.outm ? D.outm + r0 * D.outm_ld : nullptr; P.ld_outm = D.outm_ld; P.ts_outm = D.outm_ts;
+    P.mask = D.mask ? D.mask + r0 * D.mask_ld : nullptr; P.ld_mask = D.mask_ld; P.ts_mask = D.mask_ts;
+    P.hlast = D.hlast ? D.hlast + r0 * D.hlast_ld : nullptr; P.ld_hlast = D.hlast_ld;
+    P.sv = D.sv ? D.sv + r0 * H : nullptr; P.sv_astride = D.sv_astride;
+    P.reverse = D.reverse;
+    return P;
 }
 int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
     for (int i = 0; i < nd; ++i) d[i].emitted = 0;
@@ -59,39 +75,18 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
     const long pkh = (long)pk_floats(B, H);
     bool pk = pk_ok(H);
     for (int i = 0; i < nd; ++i) if (!d[i].Wpk_hh || !d[i].hpk) pk = false;
-    // A/B switch: (round 2 had a switch that packed the initial state into slot 1 with a launch in front of the chain; removed in round 5)
-    constexpr bool h0pack = false;
-    bool all_h0 = true;
-    for (int i = 0; i < nd; ++i) all_h0 = all_h0 && d[i].h0;
-    auto pack_h0 = [&]() -> int {
-        bool same_ld = true;
-        const float* ins[4]; float* outs[4];
-        for (int i = 0; i < nd; ++i) { ins[i] = d[i].h0; outs[i] = d[i].hpk + pkh; same_ld = same_ld && d[i].h0_ld == d[0].h0_ld; }
-        if (same_ld) return pw_pack_frag_multi(ins, outs, nd, d[0].h0_ld, B, H, 0, s);
-        for (int i = 0; i < nd; ++i) INET_TRY(pw_pack_frag(d[i].h0, d[i].h0_ld, B, H, d[i].hpk + pkh, 0, 1, 0, 0, s));
-        return 0;
-    };
     if (pk && d[0].sync && gru_chain_ok(H, B, T, nd)) {
         // one persistent launch for all T steps (gru_chain.hip); the exchange buffer is the hpk ring, slot 1 = h0 (published
         // by the kernel itself; a null h0 = zeros)
         GruChainFwd a{};
         a.H = H; a.B = B; a.T = T; a.nprob = nd;
-        if (h0pack && all_h0 && !gru_chain2_ok(H, B, T, nd)) { INET_TRY(pack_h0()); a.h0_packed = 1; }
+        const bool emits = B % 32 == 0 && gru_chain2_ok(H, B, T, nd);      // (the second generation writes the piece outputs)
         for (int i = 0; i < nd; ++i) {
             const DirFwd& D = d[i];
             GruChainFwdProb& P = a.p[i];
-            P.W_hh = D.W_hh; P.b_hh = D.b_hh;
-            P.h0 = D.h0; P.ld_h0 = D.h0_ld;
-            P.gi_dense = D.gi; P.ld_gi = D.gi_ld; P.ts_gi = D.gi_ts;
-            P.gi_table = D.table; P.ld_table = D.table_ld; P.idx = D.idx; P.idx_bs = D.idx_bs; P.idx_ts = D.idx_ts;
-            P.gi_vec = D.gvec;
-            P.out = D.out; P.ld_out = D.out_ld; P.ts_out = D.out_ts;
-            P.outm = D.outm; P.ld_outm = D.outm_ld; P.ts_outm = D.outm_ts;
-            P.mask = D.mask; P.ld_mask = D.mask_ld; P.ts_mask = D.mask_ts;
-            P.hlast = D.hlast; P.ld_hlast = D.hlast_ld;
-            P.sv = D.sv; P.sv_astride = D.sv_astride;
-            P.hx = D.hpk; P.reverse = D.reverse;
-            if (B % 32 == 0 && gru_chain_fwd_is_v2(H, B, T, nd, a.h0_packed) && gru_chain2_emits(H, B, T, nd)) { P.em = D.em; P.em.B_full = B; P.em.r0 = 0; D.emitted = 3; }
+            P = fwd_prob(D, 0, H);
+            P.hx = D.hpk;
+            if (emits) { P.em = D.em; P.em.B_full = B; P.em.r0 = 0; D.emitted = 3; }
         }
         a.counters = d[0].sync; a.prezeroed = d[0].sync_prezeroed;
         return launch_gru_chain_fwd(a, s);
@@ -107,17 +102,8 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
         for (int i = 0; i < nd; ++i) {
             const DirFwd& D = d[i];
             GruChainFwdProb& P = L.p[i];
-            P.b_hh = D.b_hh;
-            P.h0 = D.h0; P.ld_h0 = D.h0_ld;
-            P.gi_dense = D.gi; P.ld_gi = D.gi_ld; P.ts_gi = D.gi_ts;
-            P.gi_table = D.table; P.ld_table = D.table_ld; P.idx = D.idx; P.idx_bs = D.idx_bs; P.idx_ts = D.idx_ts;
-            P.gi_vec = D.gvec;
-            P.out = D.out; P.ld_out = D.out_ld; P.ts_out = D.out_ts;
-            P.outm = D.outm; P.ld_outm = D.outm_ld; P.ts_outm = D.outm_ts;
-            P.mask = D.mask; P.ld_mask = D.mask_ld; P.ts_mask = D.mask_ts;
-            P.hlast = D.hlast; P.ld_hlast = D.hlast_ld;
-            P.sv = D.sv; P.sv_astride = D.sv_astride;
-            P.hx = D.hpk; P.reverse = D.reverse;
+            P = fwd_prob(D, 0, H);
+            P.hx = D.hpk;
             if (D.em.rows) { P.em.rows = D.em.rows; P.em.rows_piece = D.em.rows_piece; P.em.rows_kb = D.em.rows_kb; P.em.rows_kb0 = D.em.rows_kb0;
                              P.em.B_full = B; P.em.r0 = 0; D.emitted = 1;
                              // forward-only: the masked output's only reader is the layer-1 product, which takes these pieces
@@ -144,12 +130,12 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
         // chunk's hand-off latency (a third of each step) is filled by the other chunk's MFMAs.  Chunk c works on its rows
         // of the two slots of the full-batch ring (row blocks are the outermost index of the fragment-major layout); even /
         // odd chunks count on different sync areas (the caller's and the one behind it).
-        constexpr bool twin = true;
         const long pkc = (long)pk_floats(CH, H);
         // (the second-generation kernel keeps its W slice in 144 KB of LDS: one workgroup per CU, nothing to gain from two
         // streams; every chunk gets its own contiguous ring of three-piece slots)
         const bool v2 = gru_chain2_ok(H, CH, T, nd);
-        hipStream_t s2 = twin && !v2 ? twin_fork(s) : s;
+        const bool emits = v2 && B % 32 == 0 && CH % 32 == 0;
+        hipStream_t s2 = !v2 ? twin_fork(s) : s;
         for (int c = 0; c < B / CH; ++c) {
             const long r0 = (long)c * CH;
             GruChainFwd a{};
@@ -158,23 +144,11 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
             for (int i = 0; i < nd; ++i) {
                 const DirFwd& D = d[i];
                 GruChainFwdProb& P = a.p[i];
-                P.W_hh = D.W_hh; P.b_hh = D.b_hh;
-                P.h0 = D.h0 ? D.h0 + r0 * D.h0_ld : nullptr; P.ld_h0 = D.h0_ld;
-                P.gi_dense = D.gi ? D.gi + r0 * D.gi_ld : nullptr; P.ld_gi = D.gi_ld; P.ts_gi = D.gi_ts;
-                P.gi_table = D.table; P.ld_table = D.table_ld;
-                P.idx = D.idx ? D.idx + r0 * D.idx_bs : nullptr; P.idx_bs = D.idx_bs; P.idx_ts = D.idx_ts;
-                P.gi_vec = D.gvec;
-                P.out = D.out + r0 * D.out_ld; P.ld_out = D.out_ld; P.ts_out = D.out_ts;
-                P.outm = D.outm ? D.outm + r0 * D.outm_ld : nullptr; P.ld_outm = D.outm_ld; P.ts_outm = D.outm_ts;
-                P.mask = D.mask ? D.mask + r0 * D.mask_ld : nullptr; P.ld_mask = D.mask_ld; P.ts_mask = D.mask_ts;
-                P.hlast = D.hlast ? D.hlast + r0 * D.hlast_ld : nullptr; P.ld_hlast = D.hlast_ld;
-                if (D.sv) { P.sv = D.sv + r0 * H; P.sv_astride = D.sv_astride; P.sv_ts = BH; }
+                P = fwd_prob(D, r0, H);
+                if (P.sv) P.sv_ts = BH;
                 if (v2) P.hx = D.hpk + (long)c * 3 * pkc;
                 else { P.hx = D.hpk + (long)c * pkc; P.hx_slot_bytes = (int)(pkh * sizeof(float)); }
-                P.reverse = D.reverse;
-                if (v2 && B % 32 == 0 && CH % 32 == 0 && gru_chain_fwd_is_v2(H, CH, T, nd, 0) && gru_chain2_emits(H, CH, T, nd)) {
-                    P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 3;
-                }
+                if (emits) { P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 3; }
             }
             a.counters = d[0].sync + (c & 1) * kChainSyncWords;
             INET_TRY(launch_gru_chain_fwd(a, (c & 1) ? s2 : s));
@@ -182,6 +156,14 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
         return s2 != s ? twin_join(s) : 0;
     }
     // one launch per step (gru.hip): the fragment-major ring's slot 1 is packed from h0 here (step 0 reads it)
+    auto pack_h0 = [&]() -> int {
+        bool same_ld = true;
+        const float* ins[4]; float* outs[4];
+        for (int i = 0; i < nd; ++i) { ins[i] = d[i].h0; outs[i] = d[i].hpk + pkh; same_ld = same_ld && d[i].h0_ld == d[0].h0_ld; }
+        if (same_ld) return pw_pack_frag_multi(ins, outs, nd, d[0].h0_ld, B, H, 0, s);
+        for (int i = 0; i < nd; ++i) INET_TRY(pw_pack_frag(d[i].h0, d[i].h0_ld, B, H, d[i].hpk + pkh, 0, 1, 0, 0, s));
+        return 0;
+    };
     for (int i = 0; i < nd; ++i) if (!d[i].h0) return -1;     // (a null h0 is the chain kernels' shorthand for zeros)
     if (pk) INET_TRY(pack_h0());
     for (int step = 0; step < T; ++step) {
@@ -224,12 +206,26 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
     return 0;
 }
 
-int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s) {
-    return gru_layer_bwd_range(H, B, T, nd, d, T - 1, 0, s);
+// One direction's descriptor for the BPTT chain / bf16-pipe step launches over the rows from r0 on of a batch of B (saves and dgh
+// keep the full batch's time stride).  The caller sets the exchange ring (gx, gx_slot_bytes) and the piece outputs (em).
+// (The step launcher takes sv_ts / dgh_ts as 0 or the full-batch stride, which is what they are here; it does not read W_hh.)
+static GruChainBwdProb bwd_prob(const DirBwd& D, long r0, int H, int B) {
+    GruChainBwdProb P{};
+    P.W_hh = D.W_hh;
+    P.dout = D.dout ? D.dout + r0 * D.dout_ld : nullptr; P.ld_dout = D.dout_ld; P.ts_dout = D.dout_ts;
+    P.dhn = D.dhn ? D.dhn + r0 * D.dhn_ld : nullptr; P.ld_dhn = D.dhn_ld;
+    P.sv = D.sv + r0 * H; P.sv_astride = D.sv_astride; P.sv_ts = (long)B * H;
+    P.dgi = D.dgi + r0 * D.dgi_ld; P.ld_dgi = D.dgi_ld; P.ts_dgi = D.dgi_ts;
+    P.dgh = D.dgh + r0 * 3 * H; P.dgh_ts = 3L * B * H;
+    P.db_ih = D.db_ih; P.db_hh = D.db_hh;
+    P.dh0 = D.dh0 ? D.dh0 + r0 * D.dh0_ld : nullptr; P.ld_dh0 = D.dh0_ld; P.dh0_accumulate = D.dh0_acc;
+    P.reverse = D.reverse;
+    P.dgi_sum = D.dgi_sum ? D.dgi_sum + r0 * 3 * H : nullptr;
+    return P;
 }
 
-// Steps step_hi .. step_lo (descending) of the BPTT chain; the gradient wrt the initial hidden follows step 0.
-int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_hi, int step_lo, hipStream_t s) {
+// The BPTT chain, steps T - 1 .. 0; the gradient wrt the initial hidden follows step 0.
+int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s) {
     for (int i = 0; i < nd; ++i) d[i].emitted = 0;
     const long BH = (long)B * H, B3H = 3 * BH;
     const long pkg = (long)pk_floats(B, 3 * H);
@@ -239,11 +235,14 @@ int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_h
         bool any0 = false, all0 = true, wok = true;
         for (int i = 0; i < nd; ++i) { if (d[i].dh0) any0 = true; else all0 = false; if (!d[i].W_hh) wok = false; }
         const int CHB = chain_chunk_rows_bwd(H, B, T, nd);
-        if (pk && wok && d[0].sync && step_hi == T - 1 && step_lo == 0 && (!any0 || all0) && CHB > 0) {
+        if (pk && wok && d[0].sync && (!any0 || all0) && CHB > 0) {
             // one persistent launch -- or, for a batch beyond one resident launch, one launch per chunk of CHB rows (the rows
             // are independent; saves / dgh keep the full batch's time stride; bias gradients accumulate with atomics)
             const long pkc = (long)pk_floats(CHB, 3 * H);
-            const bool v2b = gru_chain2_ok(H, CHB, T, nd);
+            // (the rings sit as the forward chains' do: a contiguous ring per chunk, chain_ring_floats apart, where the forward launch of
+            // this shape is second-generation; otherwise chunk c works on its rows of the two slots of the full-batch ring)
+            const bool own_rings = gru_chain2_ok(H, CHB, T, nd);
+            const bool emits_rows = B % 32 == 0 && CHB % 32 == 0 && gru_chain_bwd_emits_rows(H, CHB, T, nd);
             for (int c = 0; c < B / CHB; ++c) {
                 const long r0 = (long)c * CHB;
                 GruChainBwd a{};
@@ -251,23 +250,10 @@ int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_h
                 for (int i = 0; i < nd; ++i) {
                     const DirBwd& D = d[i];
                     GruChainBwdProb& P = a.p[i];
-                    P.W_hh = D.W_hh;
-                    P.dout = D.dout ? D.dout + r0 * D.dout_ld : nullptr; P.ld_dout = D.dout_ld; P.ts_dout = D.dout_ts;
-                    P.dhn = D.dhn ? D.dhn + r0 * D.dhn_ld : nullptr; P.ld_dhn = D.dhn_ld;
-                    P.sv = D.sv + r0 * H; P.sv_astride = D.sv_astride; P.sv_ts = BH;
-                    P.dgi = D.dgi + r0 * D.dgi_ld; P.ld_dgi = D.dgi_ld; P.ts_dgi = D.dgi_ts;
-                    P.dgh = D.dgh + r0 * 3 * H; P.dgh_ts = B3H;
-                    P.db_ih = D.db_ih; P.db_hh = D.db_hh;
-                    P.dh0 = D.dh0 ? D.dh0 + r0 * D.dh0_ld : nullptr; P.ld_dh0 = D.dh0_ld; P.dh0_accumulate = D.dh0_acc;
-                    if (v2b) P.gx = D.dghpk + (long)c * 3 * pkc;
+                    P = bwd_prob(D, r0, H, B);
+                    if (own_rings) P.gx = D.dghpk + (long)c * 3 * pkc;
                     else { P.gx = D.dghpk + (long)c * pkc; P.gx_slot_bytes = (int)(pkg * sizeof(float)); }
-                    P.reverse = D.reverse;
-                    P.dgi_sum = D.dgi_sum ? D.dgi_sum + r0 * 3 * H : nullptr;
-                    if (B % 32 == 0 && CHB % 32 == 0 && gru_chain_bwd_is_v2(H, CHB, T, nd) && gru_chain2_emits(H, CHB, T, nd)) {
-                        P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 3;
-                    } else if (B % 32 == 0 && CHB % 32 == 0 && D.em.rows && gru_chain_bwd_emits_rows(H, CHB, T, nd)) {
-                        P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 1;   // (the first generation: row pieces only)
-                    }
+                    if (emits_rows && D.em.rows) { P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 1; }   // (row pieces only)
                 }
                 a.counters = d[0].sync; a.prezeroed = (c == 0 && CHB == B) ? d[0].sync_prezeroed : 0;
                 INET_TRY(launch_gru_chain_bwd(a, s));
@@ -280,7 +266,7 @@ int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_h
     {
         // More rows than the chain launches take (chunks stop at INET_CHAIN_CHUNK_MAX rows): one bf16-pipe product per time step with
         // the gate derivatives as its epilogue (gru_step_bf3.hip) instead of the f32-input per-step kernels
-        bool any0 = false, all0 = true, stepb = pk && nd <= 2 && step_hi == T - 1 && step_lo == 0 && gru_step_bf3_bwd_ok(H, B, T, nd);
+        bool any0 = false, all0 = true, stepb = pk && nd <= 2 && gru_step_bf3_bwd_ok(H, B, T, nd);
         for (int i = 0; i < nd; ++i) {
             if (d[i].dh0) any0 = true; else all0 = false;
             stepb = stepb && d[i].wp3T && d[i].W_hh && d[i].dhz && !d[i].dgi_sum;
@@ -291,14 +277,8 @@ int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_h
             for (int i = 0; i < nd; ++i) {
                 const DirBwd& D = d[i];
                 GruChainBwdProb& P = L.p[i];
-                P.dout = D.dout; P.ld_dout = D.dout_ld; P.ts_dout = D.dout_ts;
-                P.dhn = D.dhn; P.ld_dhn = D.dhn_ld;
-                P.sv = D.sv; P.sv_astride = D.sv_astride;
-                P.dgi = D.dgi; P.ld_dgi = D.dgi_ld; P.ts_dgi = D.dgi_ts;
-                P.dgh = D.dgh;
-                P.db_ih = D.db_ih; P.db_hh = D.db_hh;
-                P.dh0 = D.dh0; P.ld_dh0 = D.dh0_ld; P.dh0_accumulate = D.dh0_acc;
-                P.gx = D.dghpk; P.reverse = D.reverse;
+                P = bwd_prob(D, 0, H, B);
+                P.gx = D.dghpk;
                 if (D.em.rows && B % 32 == 0) { P.em.rows = D.em.rows; P.em.rows_piece = D.em.rows_piece; P.em.rows_kb = D.em.rows_kb;
                                                 P.em.rows_kb0 = D.em.rows_kb0; P.em.B_full = B; P.em.r0 = 0; D.emitted = 1; }
                 INET_TRY(gru_step_bf3_split_wT(H, D.W_hh, D.wp3T, s));
@@ -307,7 +287,7 @@ int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_h
             return launch_gru_steps_bf3_bwd(L, s);
         }
     }
-    for (int step = step_hi; step >= step_lo; --step) {
+    for (int step = T - 1; step >= 0; --step) {
         GruBwdBatch bt{};
         bt.H = H; bt.nprob = nd;
         for (int i = 0; i < nd; ++i) {
@@ -336,7 +316,6 @@ int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_h
         }
         INET_TRY(launch_gru_bwd(bt, s));
     }
-    if (step_lo > 0) return 0;
     bool any = false, all = true;
     for (int i = 0; i < nd; ++i) { if (d[i].dh0) any = true; else all = false; }
     if (any) {
@@ -361,9 +340,6 @@ int gru_layer_bwd_range(int H, int B, int T, int nd, const DirBwd* d, int step_h
 
 int gru_dir_wgrad(int H, int B, int T, const float* dgh, const float* sv_hprev, float* dW_hh, hipStream_t s) {
     return linear_wgrad(dgh, 3L * H, sv_hprev, H, dW_hh, H, T * B, 3 * H, H, s);
-}
-int gru_dir_wgrad_range(int H, int B, int t_lo, int nt, const float* dgh, const float* sv_hprev, float* dW_hh, hipStream_t s) {
-    return linear_wgrad(dgh + (long)t_lo * B * 3 * H, 3L * H, sv_hprev + (long)t_lo * B * H, H, dW_hh, H, nt * B, 3 * H, H, s);
 }
 
 size_t bigru2_carve(Carver& c, int B, int T, int H, int save, BiGru2Ws& w) {
@@ -578,7 +554,7 @@ int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, 
     const long BH = (long)B * H, TBH = (long)T * BH;
     if (ws_opts_check(w.sync, opts_snapshot(), stage != 1) != 0) return -3;      // options changed since the forward call
     const bool wg = P[0].dw_hh != nullptr;
-    // both layers run as backward chains (they read W_hh as stored) iff the conditions of gru_layer_bwd_range hold:
+    // both layers run as backward chains (they read W_hh as stored) iff the conditions of gru_layer_bwd hold:
     // the transposed fragment-major twins are then never read
     const bool chained = w.wpkT[0] && w.dghpk[0] && w.sync && pk_ok(H) && chain_chunk_rows_bwd(H, B, T, 2) > 0;
     const bool bf3d_pre = bf3_mode() != 0 && w.dgi1pk && w.wih1Tpk && gemm_bf3_ok(T * B, 2 * H, 6 * H);
@@ -617,17 +593,15 @@ int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, 
             D.em.rows_kb0 = dir * 3 * H / 32;
         }
     }
-    // The chains can hand their weight-gradient products to the side stream a chunk of steps at a time (CH < T) instead
-    // of a layer's whole K = T*B product at the end of its chain.  Measured at B=256 with 2, 3, 4 chunks per layer:
-    // 5.12 / 5.17 / 5.21 ms per step against 5.12 for one -- during backward the two streams together already keep the
-    // chip busy, and smaller-K products are less efficient -- so one chunk.
-    const int CH = T;
+    // A layer's weight-gradient products go to the side stream whole (K = T*B), at the end of its chain.  (Handing them over a
+    // chunk of steps at a time measured, at B=256 with 2, 3, 4 chunks per layer, 5.12 / 5.17 / 5.21 ms per step against 5.12 for
+    // one -- during backward the two streams together already keep the chip busy, and smaller-K products are less efficient.)
     const float* x1 = mask ? w.x1m : w.x1raw;
-    const bool l1_gem = false;                                 // (the gate gradients' transposed pieces always come from split launches)
     // layer 1's weight gradients on the bf16 pipe: dW_hh (both directions), then dW_ih_d [3H, 2H] += dgi1_d^T x1 on the transposed
     // gate gradients just made
     auto l1_wgrads_bf3 = [&](hipStream_t ss) -> int {
-        INET_TRY(bigru2_wgrad_hh_bf3(B, T, H, 1, P, w, w.dgi1, true, l1_gem, fwd_emitted, ss));
+        // (gates_emitted = false: the gate gradients' transposed pieces always come from split launches)
+        INET_TRY(bigru2_wgrad_hh_bf3(B, T, H, 1, P, w, w.dgi1, true, false, fwd_emitted, ss));
         const long TBl = (long)T * B;
         const long gp = (long)bf3_piece_bytes(6 * H, TBl), xp = (long)bf3_piece_bytes(2 * H, TBl);
         const int KB = (int)(TBl / 32);
@@ -641,25 +615,17 @@ int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, 
     };
     const bool bf3d = bf3_mode() != 0 && w.dgi1pk && w.wih1Tpk && gemm_bf3_ok(T * B, 2 * H, 6 * H);
     const bool bf3w = bf3_mode() != 0 && w.gT[0] && w.hpT[0] && wg;
-    for (int hi = T - 1; hi >= 0 && stage != 2; hi -= CH) {
-        const int lo = hi - CH + 1 > 0 ? hi - CH + 1 : 0, nt = hi - lo + 1;
-        INET_TRY(gru_layer_bwd_range(H, B, T, 2, d, hi, lo, s));
+    if (stage != 2) {
+        INET_TRY(gru_layer_bwd(H, B, T, 2, d, s));
         if (wg) {
             hipStream_t ss = side_fork(s);                   // leaf work: overlaps the rest of the BPTT chains
-            if (nt == T && bf3w) {                            // both directions of a product in one launch (gemm_bf3.hip)
+            if (bf3w) {                                      // both directions of a product in one launch (gemm_bf3.hip)
                 INET_TRY(l1_wgrads_bf3(ss));
-            } else if (nt == T) {                            // both directions of a product in one launch
+            } else {                                         // ... or of the f32-input kernels (gemm.hip)
                 INET_TRY(linear_wgrad2(w.dgh[2], w.dgh[3], 3L * H, w.sv[2] + 4 * TBH, w.sv[3] + 4 * TBH, H, P[2].dw_hh,
                                        P[3].dw_hh, H, T * B, 3 * H, H, ss));
                 INET_TRY(linear_wgrad2(w.dgi1, w.dgi1 + 3L * H, 6L * H, x1, x1, 2L * H, P[2].dw_ih, P[3].dw_ih, 2L * H,
                                        T * B, 3 * H, 2 * H, ss));
-            } else
-            for (int dir = 0; dir < 2; ++dir) {
-                const int t_lo = dir ? T - 1 - hi : lo;       // the reverse direction walks time forwards
-                const float* dgi = w.dgi1 + dir * 3L * H + (long)t_lo * B * 6 * H;
-                INET_TRY(gru_dir_wgrad_range(H, B, t_lo, nt, w.dgh[2 + dir], w.sv[2 + dir] + 4 * TBH, P[2 + dir].dw_hh, ss));
-                INET_TRY(linear_wgrad(dgi, 6L * H, x1 + (long)t_lo * B * 2 * H, 2L * H, P[2 + dir].dw_ih, 2L * H, nt * B,
-                                      3 * H, 2 * H, ss));
             }
         }
     }
@@ -702,20 +668,9 @@ int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, 
         D.Wpk_hhT = w.wpkT[dir]; D.dghpk = w.dghpk[dir];
         D.W_hh = P[dir].w_hh; D.sync = chained ? w.sync + kChainSyncWords : w.sync; D.sync_prezeroed = chained; D.wp3T = w.wp3T[dir];
     }
-    for (int hi = T - 1; hi >= 0; hi -= CH) {
-        const int lo = hi - CH + 1 > 0 ? hi - CH + 1 : 0;
-        INET_TRY(gru_layer_bwd_range(H, B, T, 2, d, hi, lo, s));
-        if (wg) {
-            hipStream_t ss = side_fork(s);
-            if (hi - lo + 1 == T)
-                INET_TRY(linear_wgrad2(w.dgh[0], w.dgh[1], 3L * H, w.sv[0] + 4 * TBH, w.sv[1] + 4 * TBH, H, P[0].dw_hh,
-                                       P[1].dw_hh, H, T * B, 3 * H, H, ss));
-            else
-            for (int dir = 0; dir < 2; ++dir) {
-                const int t_lo = dir ? T - 1 - hi : lo;         // the reverse direction walks time forwards
-                INET_TRY(gru_dir_wgrad_range(H, B, t_lo, hi - lo + 1, w.dgh[dir], w.sv[dir] + 4 * TBH, P[dir].dw_hh, ss));
-            }
-        }
-    }
+    INET_TRY(gru_layer_bwd(H, B, T, 2, d, s));
+    if (wg)
+        INET_TRY(linear_wgrad2(w.dgh[0], w.dgh[1], 3L * H, w.sv[0] + 4 * TBH, w.sv[1] + 4 * TBH, H, P[0].dw_hh,
+                               P[1].dw_hh, H, T * B, 3 * H, H, side_fork(s)));
     return 0;
 }

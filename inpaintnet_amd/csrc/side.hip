@@ -7,11 +7,11 @@
 namespace {
 // Leaf work (weight-gradient products, bias sums) goes to low-priority side streams, one fork "session" per call of
 // side_fork().  Sessions are independent of each other (distinct gradient tensors, scratch private to a session), so
-// they rotate over kMaxSide streams: the tail of one 256-workgroup product (skewed finishers, atomics) overlaps the
+// they rotate over kSides streams: the tail of one 256-workgroup product (skewed finishers, atomics) overlaps the
 // start of the next (4.345 -> 4.231 ms per training step with two streams instead of one).
-constexpr int kMaxSide = 3;           // measured: 1 -> 4.35, 2 -> 4.24, 3 -> 4.29 ms per step; 4 -> 7.57 (the queues get multiplexed)
-hipStream_t g_sides[kMaxSide] = {nullptr, nullptr, nullptr};
-bool g_dirty[kMaxSide] = {false, false, false};          // something was queued on stream i since the last join
+constexpr int kSides = 2;             // measured: 1 -> 4.35, 2 -> 4.24, 3 -> 4.29 ms per step; 4 -> 7.57 (the queues get multiplexed)
+hipStream_t g_sides[kSides] = {nullptr, nullptr};
+bool g_dirty[kSides] = {false, false};                   // something was queued on stream i since the last join
 int g_nside = 0, g_turn = 0;
 bool g_init = false;
 int g_enabled = -1;
@@ -24,11 +24,10 @@ hipEvent_t next_event() {
     if (g_pool.empty()) {
         // These events only order streams of ONE device against each other: the system-scope fence an event performs by
         // default when it completes (cache write-back + invalidate, ~7 us of bubble on the recording stream per fork,
-        // profiles/r02_v_timeline_full_step.txt) buys nothing here.  (The switch that restored the default was removed in round 5.)
-        constexpr bool fence = false;
+        // profiles/r02_v_timeline_full_step.txt) buys nothing here.
         g_pool.resize(64);
         for (auto& e : g_pool)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming | (fence ? 0u : hipEventDisableSystemFence)) != hipSuccess &&
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess &&
                 hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) e = nullptr;
     }
     hipEvent_t e = g_pool[g_next];
@@ -58,14 +57,10 @@ hipStream_t side_fork(hipStream_t main_stream) {
     if (!side_enabled()) return main_stream;
     if (!g_init) {
         g_init = true;
-        // (the twin stream first, whoever asks first: see twin_fork.  a switch of round 4 created it only when a two-layer LSTM pipeline asked)
-        constexpr bool eager = true;
-        if (eager) twin_create();
+        twin_create();                                             // (the twin stream first, whoever asks first: see twin_fork)
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        int want = 2;                                              // (two rotating side streams: the header's measurement)
-        want = want < 1 ? 1 : (want > kMaxSide ? kMaxSide : want);
-        if (g_active > 0 && g_active < want) want = g_active;      // (key 13 set before the first fork: no more streams than will be used)
+        const int want = g_active > 0 && g_active < kSides ? g_active : kSides;   // (key 13 set before the first fork: no more streams than will be used)
         for (int i = 0; i < want; ++i) {
             if (hipStreamCreateWithPriority(&g_sides[g_nside], hipStreamNonBlocking, lo) != hipSuccess) break;
             ++g_nside;

@@ -140,8 +140,7 @@ int vae_encoder_bwd(const inet_vae_config& c, int B, const long long* tokens, co
     // step's backward pass and the side stream is still busy with the layer-0 dW_hh products (r02 timeline: queued behind
     // them they delayed the optimizer by ~0.14 ms).
     {
-        constexpr bool emb_main = true;
-        hipStream_t ss = emb_main ? s : side_fork(s);
+        hipStream_t ss = s;
         // dTable [V, 6H] (both directions side by side, as dgi0 holds them): the rows of dgi0 summed by token -- one pass over
         // dgi0 at HBM rate (it shares the chip with the layer-0 dW_hh products, which own the MFMA pipes); then
         // dW_ih_l0[dir] [3H,E] += dTable_dir^T . E_enc and dE_enc [V,E] += dTable_dir . W_ih_l0[dir] in one small launch
@@ -292,20 +291,16 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     DecWs w{};
     dec_carve(c, B, save, ws, w);
     const bool pk = w.wpk_t0 != nullptr;
-    constexpr bool tf_batch = true;
     const long pkh = (long)pk_floats(B, H);
-    constexpr bool beat_chain = true;                         // (rounds 2-4 had an environment switch for the per-step beat path)
-    constexpr bool train_chain = true;
     // Which kernels will run: the chain kernels read W_hh / W_ih as stored, only the per-step kernels want the
     // fragment-major twins -- each is packed only if its consumer runs.
-    const bool beats_chained = pk && beat_chain && chain_chunk_rows(H, B, nb, 1, save) > 0;   // (one launch, or one per row chunk)
-    const bool fused_shape = pk && !teacher_forced && !multinomial_seed && ((!save && !mask_tick) || train_chain);
+    const bool beats_chained = pk && chain_chunk_rows(H, B, nb, 1, save) > 0;   // (one launch, or one per row chunk)
+    const bool fused_shape = pk && !teacher_forced && !multinomial_seed;
     // batches beyond one resident launch (LatentRNN decodes 512 measures per step): the rows are independent, so the fused
     // kernel runs over chunks of 512 rows (the 64-row build: 27 us per tick instead of 2 x 20) or 256, one launch after the other
     const int kDecodeChunk = B % 512 == 0 ? 512 : 256;
-    constexpr bool dec_chunks = true;
     const bool fused_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
-    const bool fused_chunked = fused_shape && !fused_whole && dec_chunks && B > kDecodeChunk && B % kDecodeChunk == 0 &&
+    const bool fused_chunked = fused_shape && !fused_whole && B > kDecodeChunk && B % kDecodeChunk == 0 &&
                                decode_chain_ok(kDecodeChunk, H, V, T, G);
     const bool fused_decode = fused_whole || fused_chunked;
     // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
@@ -314,9 +309,8 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V);   // ... with the beat path inside the same launch
     // teacher-forced ticks: every input token is known and the 4 beats are independent, so each tick layer is a chain of
     // G steps over the beats as problems -- `npl` beats per launch, as many as fit the chip at once (2 at B = 256)
-    constexpr bool tf_chain = true;
     int npl = 0;
-    if (pk && teacher_forced && tf_batch && tf_chain) {
+    if (pk && teacher_forced) {
         for (int n = nb; n >= 1 && !npl; --n)                  // whole batch in one launch per `n` beats ...
             if (nb % n == 0 && 3 + 2 * (nb / n) <= kSyncAreas && gru_chain_ok(H, B, G, n)) npl = n;
         for (int n = nb; n >= 1 && !npl; --n)                  // ... else row chunks
@@ -361,7 +355,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
             ins[n] = p + L.tick[1].w_ih; outs[n++] = w.wpk_t1ih;
         }
         if (n) INET_TRY(pw_pack_frag_multi(ins, outs, n, H, 3 * H, H, 0, s));
-        if (w.wpk_out && !fused_decode && !(teacher_forced && tf_batch))
+        if (w.wpk_out && !fused_decode && !teacher_forced)
             INET_TRY(pw_pack_frag(p + L.out_w, H, V, H, w.wpk_out, 0, 1, 0, 0, s));
     }
 
@@ -444,7 +438,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
         INET_TRY(pw_swap01(w.wtm, T, B, V, weights, s));             // [T,B,V] -> [B,T,V]
         return 0;
     }
-    if (teacher_forced && tf_batch) {
+    if (teacher_forced) {
         // Every input token is known, and the tick GRU's hidden state is re-initialised per beat, so the 4 beats are
         // independent: 6 steps x 4 problems per layer instead of 24 dependent steps, and ONE output projection.
         const long as = (long)T * BH;
@@ -529,7 +523,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
         }
         return 0;
     }
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < T; ++t) {                              // free-running ticks, one launch per layer and tick
         const int i = t / G, j = t % G;
         GruFwdBatch b0{};
         b0.H = H; b0.nprob = 1;
@@ -567,9 +561,9 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
         INET_TRY(launch_gru_fwd(b1, s));
 
         // logits = ReLU(h_top . Wo^T + bo) straight into weights[:, t, :], fused with the argmax that feeds tick t+1
-        const bool draw = multinomial_seed != 0 && !teacher_forced;       // decoder.py:506-509: sample the fed-back token
+        const bool draw = multinomial_seed != 0;               // decoder.py:506-509: sample the fed-back token
         int rc = draw ? 1 : launch_logits_argmax(w.h1seq + (long)t * BH, H, B, H, p + L.out_w, p + L.out_b, V,
-                                                 weights + (long)t * V, (long)T * V, teacher_forced ? nullptr : samples + t,
+                                                 weights + (long)t * V, (long)T * V, samples + t,
                                                  T, s, pk ? P1.hpk_new : nullptr, w.wpk_out);
         if (rc < 0) return rc;
         if (rc == 1) {                                         // V not a multiple of 16 (or > 64), or sampling: two kernels
@@ -577,7 +571,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
                                 (long)T * V, B, V, H, EPI_RELU, s));
             if (draw) INET_TRY(pw_sample_multinomial(weights + (long)t * V, (long)T * V, B, V, samples + t, T,
                                                      multinomial_seed, (uint64_t)t * B, s));
-            else if (!teacher_forced) INET_TRY(pw_argmax(weights + (long)t * V, (long)T * V, B, V, samples + t, T, s));
+            else INET_TRY(pw_argmax(weights + (long)t * V, (long)T * V, B, V, samples + t, T, s));
         }
     }
     return 0;
@@ -592,10 +586,9 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
     DecWs w{};
     dec_carve(c, B, 1, ws, w);
     const GruDirOff* gr[4] = {&L.beat[0], &L.beat[1], &L.tick[0], &L.tick[1]};
-    constexpr bool beat_chain = true;                         // (rounds 2-4 had an environment switch for the per-step beat path)
     // the backward chain kernels read W_hh as stored (transposed on the fly, once): the fragment-major W_hh^T twins are
     // only packed for layers that fall back to one launch per step
-    const bool beats_chained = w.wpkT[0] && w.dghpk && beat_chain && chain_chunk_rows_bwd(H, B, nb, 1) > 0;
+    const bool beats_chained = w.wpkT[0] && w.dghpk && chain_chunk_rows_bwd(H, B, nb, 1) > 0;
     const bool ticks_chained = w.wpkT[0] && w.dghpk && chain_chunk_rows_bwd(H, B, G, nb) > 0;
     // one memset: the chain kernels' sync areas and, right behind them, the accumulator of the beat GRU's input-gate column sum
     if (hipMemsetAsync(w.sync, 0, (size_t)((char*)(w.tmp3h + 3 * H) - (char*)w.sync), s) != hipSuccess) return -2;
@@ -638,20 +631,7 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
     // Layer 1's leaf work is issued BEHIND the layer-0 chain, not beside it (round 5, profiles/r05_s_leaf_schedule.txt): beside the
     // chain its 6144-row products doubled the chain's time (231 us against 124 alone -- a persistent chain and a throughput product on
     // the same CUs overlap almost not at all), behind it they run beside the beat path's small latency-bound products, which lose
-    // little: 3.60 -> 3.55 ms per step.  (leaf_when 0: beside the layer-0 chain, as rounds 2-4 had it; 2: with the beat path's
-    // session at the end -- beside the encoder's layer-1 BPTT chain, 3.76 ms.)
-    constexpr int leaf_when = 1;
-    auto layer1_leaf = [&](hipStream_t ss) -> int {
-        INET_TRY(linear_wgrad2(w.dgh1t, w.dgi1t, 3L * H, w.svt1 + 4 * TBH, x1, H, g + L.tick[1].w_hh, g + L.tick[1].w_ih, H,
-                               T * B, 3 * H, H, ss));      // recurrent and input weights of layer 1 in one launch
-        INET_TRY(linear_wgrad(w.dlg, V, w.h1seq, H, g + L.out_w, H, T * B, V, H, ss));
-        INET_TRY(pw_colsum(w.dlg, V, T * B, V, g + L.out_b, ss));
-        return 0;
-    };
-    if (g && leaf_when == 0) {
-        hipStream_t ss = side_fork(s);
-        INET_TRY(layer1_leaf(ss));
-    }
+    // little: 3.60 -> 3.55 ms per step.  (With the beat path's session at the end -- beside the encoder's layer-1 BPTT chain -- 3.76 ms.)
     INET_TRY(linear_dgrad(w.dgi1t, 3L * H, p + L.tick[1].w_ih, H, w.dx1t, H, T * B, 3 * H, H,
                           mask_tick ? EPI_MUL_AUX : EPI_NONE, mask_tick, H, ACC_STORE, s));
 
@@ -681,7 +661,10 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
                           ACC_STORE, s));
     if (g) {
         hipStream_t ss = side_fork(s);
-        if (leaf_when == 1) INET_TRY(layer1_leaf(ss));
+        INET_TRY(linear_wgrad2(w.dgh1t, w.dgi1t, 3L * H, w.svt1 + 4 * TBH, x1, H, g + L.tick[1].w_hh, g + L.tick[1].w_ih, H,
+                               T * B, 3 * H, H, ss));      // recurrent and input weights of layer 1 in one launch
+        INET_TRY(linear_wgrad(w.dlg, V, w.h1seq, H, g + L.out_w, H, T * B, V, H, ss));
+        INET_TRY(pw_colsum(w.dlg, V, T * B, V, g + L.out_b, ss));
         INET_TRY(gru_dir_wgrad(H, B, T, w.dgh0t, w.svt0 + 4 * TBH, g + L.tick[0].w_hh, ss));
         INET_TRY(linear_wgrad(w.dcgi, 3L * H, w.c_all, H, g + L.tick[0].w_ih + E, ldw0, nb * B, 3 * H, H, ss));
         // token-embedding half through the gather table (rows 0..V-1 = the embeddings, row V = the start symbol x_0)
@@ -744,7 +727,6 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
     if (g) {
         // the beat path's leaf work in one session: six weight gradients in two grouped launches, four column sums in one
         hipStream_t ss = side_fork(s);
-        if (leaf_when == 2) INET_TRY(layer1_leaf(ss));
         const GemmArgs ga[4] = {linear_wgrad_args(w.dht0, 2L * H, w.beat_out, H, g + L.bh_w, H, nb * B, 2 * H, H),
                                 linear_wgrad_args(w.dc_all, H, w.beat_out, H, g + L.bi_w, H, nb * B, H, H),
                                 linear_wgrad_args(w.dgh1b, 3L * H, w.svb1 + 4 * nb * BH, H, g + L.beat[1].w_hh, H, nb * B, 3 * H, H),

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Registers, spills, scratch and LDS of every kernel of a HIP source, from hipcc's own remarks (no GPU needed):
     python tools/kernel_resources.py inpaintnet_amd/csrc/decode_b1.hip [more.hip ...] [--ref <git rev>]
---ref REV compiles the same files as of that revision next to the working tree and prints only the kernels whose numbers moved."""
+--ref REV compiles the same files as of that revision next to the working tree and prints only the kernels whose numbers moved.
+--ref REV --asm compares the gfx950 assembly of the two instead: a host-only change must leave it identical."""
 import os
 import re
 import subprocess
@@ -30,6 +31,14 @@ def resources(src, incdir):
     return out
 
 
+def device_asm(src, incdir):
+    """The file's device assembly without the lines that carry its content hash (__hip_cuid_*: they move with any edit)."""
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "--cuda-device-only", "-S", src,
+           "-o", "-", "-I", incdir, "-I", os.path.join(REPO, "include")]
+    out = subprocess.run(cmd, capture_output=True, text=True, cwd=incdir, check=True).stdout
+    return [l for l in out.splitlines() if "__hip_cuid_" not in l]
+
+
 def fmt(r):
     return " ".join(f"{k}={v}" for k, v in r.items())
 
@@ -41,15 +50,29 @@ def main():
         i = args.index("--ref")
         ref = args[i + 1]
         del args[i:i + 2]
+    asm = "--asm" in args
+    if asm:
+        args.remove("--asm")
+        if ref is None:
+            sys.exit("--asm compares with a revision: give --ref REV")
     for src in args:
         src = os.path.abspath(src)
+        if asm and ref is not None:
+            with tempfile.TemporaryDirectory() as tmp:
+                subprocess.check_call(f"git -C {REPO} archive {ref} inpaintnet_amd/csrc include | tar -x -C {tmp}", shell=True)
+                old = device_asm(os.path.join(tmp, "inpaintnet_amd", "csrc", os.path.basename(src)), os.path.join(tmp, "inpaintnet_amd", "csrc"))
+            new = device_asm(src, CSRC)
+            first = next((i + 1 for i, (a, b) in enumerate(zip(old, new)) if a != b), None if len(old) == len(new) else min(len(old), len(new)) + 1)
+            print(f"{os.path.basename(src)}: device code " + (f"identical to {ref} ({len(new)} lines)" if first is None else
+                                                              f"DIFFERS from {ref} (first at line {first}; {len(old)} -> {len(new)} lines)"))
+            continue
         new = resources(src, CSRC)
         if ref is None:
             for k, v in new.items():
                 print(f"{os.path.basename(src)}: {k}: {fmt(v)}")
             continue
         with tempfile.TemporaryDirectory() as tmp:
-            subprocess.check_call(f"git -C {REPO} archive {ref} inpaintnet_amd/csrc | tar -x -C {tmp}", shell=True)
+            subprocess.check_call(f"git -C {REPO} archive {ref} inpaintnet_amd/csrc include | tar -x -C {tmp}", shell=True)
             old = resources(os.path.join(tmp, "inpaintnet_amd", "csrc", os.path.basename(src)), os.path.join(tmp, "inpaintnet_amd", "csrc"))
         for k in sorted(set(new) | set(old)):
             if new.get(k) != old.get(k):
