@@ -112,8 +112,8 @@ int inet_vae_ws_field(const inet_vae_config* cfg, int batch, int which, const ch
 
 /* ---- losses: VAETrainer.loss_and_acc_for_batch, vae_trainer.py:16-40,128-139; utils/trainer.py:271-306 */
 /* rows of V logits (row stride ld_w); *loss_sum += out_scale * sum_rows (lse - w[target]); *correct += out_scale *
- * #correct (argmax_first) -- out_scale = 1/rows gives the reference's means without a follow-up kernel;
- * dW (nullable, row stride ld_dw) = (softmax - onehot) * scale */
+ * #correct (argmax_first: the rule of inet_argmax, NaN included) -- out_scale = 1/rows gives the reference's means without a
+ * follow-up kernel; dW (nullable, row stride ld_dw) = (softmax - onehot) * scale.  Targets must lie in [0, V). */
 int inet_cross_entropy(const float* weights, int64_t ld_w, int rows, int V, const int64_t* targets, float* dW,
                        int64_t ld_dw, float scale, float out_scale, float* loss_sum, float* correct, void* stream);
 /* The same with the glue of VAETrainer.loss_and_acc_for_batch (vae_trainer.py:29-40) folded in: loss_sum / correct may be
@@ -134,7 +134,9 @@ int inet_latent_bwd(const float* dz, const float* mu, const float* logsigma, con
                     const float* kscale_dev, float* dmu, float* dlogsigma, int64_t n, void* stream);
 
 /* rows of V (post-ReLU) logits -> out[row*stride] ~ Multinomial(softmax(row))  (decoder.py:506-509): inverse-CDF draw with
- * one counter-based uniform per row keyed (seed, offset + row) */
+ * one counter-based uniform per row keyed (seed, offset + row): row r of a call at `offset` is row 0 of a call at offset + r.
+ * The token drawn always has mass (exp(w - max) > 0 in float32): where rounding leaves every prefix sum at or below
+ * u * total (u close to 1), it is the last token with mass, never a trailing token without any. */
 int inet_sample_multinomial(const float* weights, int64_t ld_w, int rows, int V, int64_t* out, int64_t stride,
                             uint64_t seed, uint64_t offset, void* stream);
 
@@ -292,12 +294,18 @@ int inet_arnn_sample(int R, int L, int E, int Hc, int H, int U, int V, const flo
  * (drop_input, anticipation_rnn_gauss_reg_model.py:437-442) and the all-zero first time step (:373-376). */
 int inet_embedding_fwd(const float* table, const int64_t* idx, int64_t rows, int E, float* out, const float* row_scale,
                        void* stream);
-/* num_embeddings: rows of the table (0 = not told): small tables take a segment-sum kernel instead of per-element atomics */
+/* num_embeddings: rows of the table (0 = not told): small tables take a segment-sum kernel instead of per-element atomics.
+ * dtable is accumulated into (zero it first for a fresh gradient); rows whose row_scale is 0 add nothing.
+ * Every index MUST lie in [0, num_embeddings) -- the table's row count where num_embeddings is 0.  Nothing checks it (the models'
+ * tokens are range-checked where they enter: inet_token_status): the segment-sum path (num_embeddings <= 128 and rows >= 1024)
+ * happens to drop a row whose index does not, the atomic path (and inet_embedding_fwd) addresses through it, outside the table. */
 int inet_embedding_bwd(const float* dout, const int64_t* idx, int64_t rows, int E, float* dtable, const float* row_scale,
                        int num_embeddings, void* stream);
 /* dpre = dy where y > 0 else 0   (backward of the ReLU fused into inet_linear_fwd epi=2) */
 int inet_relu_bwd(const float* dy, const float* y, float* dpre, int64_t n, void* stream);
-/* out[r*stride] = argmax_v w[r*ld + v], lowest index on ties (Tensor.max(1) / np.argmax semantics) */
+/* out[r*stride] = argmax_v w[r*ld + v] by np.argmax's rule (Tensor.max(1)): the lowest index among equal maxima (-0.0 == +0.0),
+ * and a NaN counts as the maximum -- the lowest NaN of a row wins, before any +inf.  The result always lies in [0, V), whatever the
+ * row holds (callers gather with it).  inet_arnn_generate and the `correct` count of inet_cross_entropy follow the same rule. */
 int inet_argmax(const float* w, int64_t ld, int rows, int V, int64_t* out, int64_t stride, void* stream);
 
 /* ---- input feed: the dataset tensors are int32 `score (N,1,384)` (DatasetManager/the_session/folk_dataset.py:852-861),

@@ -27,6 +27,13 @@ __device__ __forceinline__ int wave_min_i(int v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
     return v;
 }
+// argmax_first, np.argmax's rule (the one arnn_gen.hip follows): a NaN is the maximum, the lowest index wins among equals.  `m` is
+// the row's maximum as fmaxf leaves it (NaN skipped).  A lane folds the candidates of its elements into ONE key, so that one wave
+// minimum decides: a NaN at v -> v, an element equal to m -> kAmEq + v (V < 2^30), anything else -> kAmNone; am_index() of the
+// minimum is the row's argmax (every row has a candidate: its maximum, or a NaN).
+constexpr int kAmEq = 0x40000000, kAmNone = 0x7fffffff;
+__device__ __forceinline__ int am_key(float x, float m, int v) { return x != x ? v : (x == m ? kAmEq + v : kAmNone); }
+__device__ __forceinline__ int am_index(int key) { return key & (kAmEq - 1); }
 
 // out[c*ld_out + r] = in[r*ld_in + c]
 __global__ void transpose_kernel(const float* __restrict__ in, long ld_in, float* __restrict__ out, long ld_out,
@@ -125,14 +132,14 @@ __global__ void ce_kernel(const float* __restrict__ W, long ld_w, int rows, int 
         for (int v = lane; v < V; v += 64) m = fmaxf(m, w[v]);
         m = wave_max(m);
         float se = 0.f;
-        int am = 0x7fffffff;
+        int am = kAmNone;
         for (int v = lane; v < V; v += 64) {
             const float x = w[v];
             se += expf(x - m);
-            if (x == m) am = min(am, v);
+            am = min(am, am_key(x, m, v));
         }
         se = wave_sum(se);
-        am = wave_min_i(am);
+        am = am_index(wave_min_i(am));
         const int tg = (int)tgt[row];
         const float lse = m + logf(se);
         if (lane == 0) {
@@ -475,9 +482,9 @@ __global__ void argmax_kernel(const float* __restrict__ W, long ld_w, int rows, 
         float m = -INFINITY;
         for (int v = lane; v < V; v += 64) m = fmaxf(m, w[v]);
         m = wave_max(m);
-        int am = 0x7fffffff;
-        for (int v = lane; v < V; v += 64) if (w[v] == m) am = min(am, v);
-        am = wave_min_i(am);
+        int am = kAmNone;
+        for (int v = lane; v < V; v += 64) am = min(am, am_key(w[v], m, v));
+        am = am_index(wave_min_i(am));
         if (lane == 0) out[(long)row * stride] = am;
     }
 }
@@ -614,22 +621,30 @@ __global__ void sample_multinomial_kernel(const float* __restrict__ W, long ld_w
         tot = wave_sum(tot);
         const uint64_t h = mix64(mix64(seed) ^ (offset + (uint64_t)row));
         const float target = (float)((uint32_t)(h >> 40)) * (1.f / 16777216.f) * tot;     // u in [0, 1) times the total mass
+        // `tot` was summed lane-strided and across the wave, the prefix below runs in index order: the two can differ in the last
+        // bits, so for u close to 1 no prefix need exceed the target.  The draw then is the LAST TOKEN WITH MASS (the inverse CDF at
+        // u -> 1), not index V - 1, whose mass may be zero.  (The maximum has e = 1, so there is one; a row of NaN keeps V - 1.)
         float base = 0.f;
-        int pick = V - 1;
+        int pick, last = V - 1;
         bool found = false;
         for (int v0 = 0; v0 < V && !found; v0 += 64) {
             const int v = v0 + lane;
             const float e = v < V ? expf(w[v] - m) : 0.f;
+            const unsigned long long mass = __ballot(e > 0.f);
+            if (mass) last = v0 + 63 - __builtin_clzll(mass);
             float incl = e;                                     // inclusive prefix sum over the 64 lanes
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
                 const float up = __shfl_up(incl, o, 64);
                 if (lane >= o) incl += up;
             }
-            const unsigned long long hit = __ballot(v < V && base + incl > target);
+            // e > 0: the lanes' prefixes are summed in different tree orders, so behind the last token with mass a lane's prefix can
+            // come out an ulp ABOVE its neighbour's and cross the target where no lane with mass did
+            const unsigned long long hit = __ballot(v < V && e > 0.f && base + incl > target);
             if (hit) { pick = v0 + __ffsll((long long)hit) - 1; found = true; }
             base += __shfl(incl, 63, 64);
         }
+        if (!found) pick = last;
         if (lane == 0) out[(long)row * stride] = pick;
     }
 }
