@@ -271,6 +271,14 @@ class ConstraintModelGaussianReg(Model):
         w = self._head(h.view(L * B, -1)).view(L, B, -1).permute(1, 0, 2)
         return [w], None
 
+    def _generation_weights(self):
+        """The generation network as ops.arnn_generate / ops.arnn_sample take it: the embedding, then (weight_ih, bias_ih, weight_hh,
+        bias_hh) of the two LSTM layers, linear_1 and the note head."""
+        pr = self.param
+        lstm = [pr(f"lstm_generation.{l}.{n}_l0") for l in range(2) for n in ("weight_ih", "bias_ih", "weight_hh", "bias_hh")]
+        return [pr("note_embeddings.0.weight"), *lstm, pr("linear_1.weight"), pr("linear_1.bias"),
+                pr("linear_ouput_notes.0.weight"), pr("linear_ouput_notes.0.bias")]
+
     def _batched_free_run(self, oc):
         """Whether the free-running passes take the [token pass over batch element 0 + batched kernels] form (else: the per-tick loop)."""
         if not (_FREE_RUN_BATCHED and self.num_layers == 2 and oc.is_cuda):
@@ -297,15 +305,9 @@ class ConstraintModelGaussianReg(Model):
             # The tokens come from fp32 one-row kernels, the returned logits from the batched MFMA kernels (another summation
             # order): gen_chorale equals argmax(weights[0]) except possibly on rows whose top-2 logits agree to rounding (~1e-6
             # relative) -- the equivalence test compares them on rows with a clear margin.
-            pr = self.param
+            emb, *net = self._generation_weights()
             with torch.no_grad():
-                toks = ops.arnn_generate(pr("note_embeddings.0.weight"), oc.detach()[:, 0, :],
-                                         pr("lstm_generation.0.weight_ih_l0"), pr("lstm_generation.0.bias_ih_l0"),
-                                         pr("lstm_generation.0.weight_hh_l0"), pr("lstm_generation.0.bias_hh_l0"),
-                                         pr("lstm_generation.1.weight_ih_l0"), pr("lstm_generation.1.bias_ih_l0"),
-                                         pr("lstm_generation.1.weight_hh_l0"), pr("lstm_generation.1.bias_hh_l0"),
-                                         pr("linear_1.weight"), pr("linear_1.bias"),
-                                         pr("linear_ouput_notes.0.weight"), pr("linear_ouput_notes.0.bias"))
+                toks = ops.arnn_generate(emb, oc.detach()[:, 0, :], *net)
                 prev_tm = torch.cat((torch.zeros(1, dtype=torch.int64, device=dev), toks[:-1])).view(L, 1).expand(L, B).contiguous()
             h = torch.cat((self._embed("note_embeddings.0.weight", prev_tm), oc), 2)
             h = self._lstm_stack("lstm_generation", h, False)
@@ -364,19 +366,13 @@ class ConstraintModelGaussianReg(Model):
             # as in _forward_no_tf: the window's tokens depend on batch element 0 alone (its state behind the prefix, its token in
             # front of the window) -- one sequential pass over that row, then the window for the whole batch in one batched pass
             W, H, dev = end_tick - start_tick, self.num_lstm_generation_units, gen.device
-            pr = self.param
+            emb, *net = self._generation_weights()
             with torch.no_grad():
                 hc = None
                 if start_tick > 0:
                     hc = torch.stack([torch.stack((states[l][0].reshape(-1, H)[0], states[l][1].reshape(-1, H)[0])) for l in range(2)])
                 first = gen[0, 0, start_tick - 1].reshape(1).contiguous() if start_tick > 0 else None
-                toks = ops.arnn_generate(pr("note_embeddings.0.weight"), oc.detach()[start_tick:end_tick, 0, :],
-                                         pr("lstm_generation.0.weight_ih_l0"), pr("lstm_generation.0.bias_ih_l0"),
-                                         pr("lstm_generation.0.weight_hh_l0"), pr("lstm_generation.0.bias_hh_l0"),
-                                         pr("lstm_generation.1.weight_ih_l0"), pr("lstm_generation.1.bias_ih_l0"),
-                                         pr("lstm_generation.1.weight_hh_l0"), pr("lstm_generation.1.bias_hh_l0"),
-                                         pr("linear_1.weight"), pr("linear_1.bias"),
-                                         pr("linear_ouput_notes.0.weight"), pr("linear_ouput_notes.0.bias"),
+                toks = ops.arnn_generate(emb, oc.detach()[start_tick:end_tick, 0, :], *net,
                                          hc_init=hc.contiguous() if hc is not None else None, first_tok=first)
                 gen[:, 0, start_tick:end_tick] = toks.view(1, W)
                 # the token in front of the window is each row's own ground truth (or the start symbol), behind it the generated ones
@@ -441,14 +437,8 @@ class ConstraintModelGaussianReg(Model):
             x, hT, cT = self._lstm(f"lstm_generation.{l}", x, False)
             hc[:, l, 0], hc[:, l, 1] = hT.reshape(B, H), cT.reshape(B, H)
         u = np.random.random_sample((B, L))
-        pr = self.param
-        toks = ops.arnn_sample(pr("note_embeddings.0.weight"), oc.permute(1, 0, 2),
-                               pr("lstm_generation.0.weight_ih_l0"), pr("lstm_generation.0.bias_ih_l0"),
-                               pr("lstm_generation.0.weight_hh_l0"), pr("lstm_generation.0.bias_hh_l0"),
-                               pr("lstm_generation.1.weight_ih_l0"), pr("lstm_generation.1.bias_ih_l0"),
-                               pr("lstm_generation.1.weight_hh_l0"), pr("lstm_generation.1.bias_hh_l0"),
-                               pr("linear_1.weight"), pr("linear_1.bias"),
-                               pr("linear_ouput_notes.0.weight"), pr("linear_ouput_notes.0.bias"), temperature, u, hc_init=hc)
+        emb, *net = self._generation_weights()
+        toks = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc)
         torch.cuda.synchronize()
         ops.check_chains("generate")                                           # never hand back tokens of a failed launch
         gen = toks.view(B, 1, L)

@@ -5,6 +5,7 @@
 #include "layout.h"
 #include "vae.h"
 #include "lstm.h"
+#include "arnn_gen.h"
 #include "chain.h"
 #include "decode_chain.h"
 #include "gemm_bf3.h"
@@ -381,7 +382,7 @@ int inet_lstm2_fwd(int B, int T, int H, const float* gi0, const float* W_hh0, co
 }
 int64_t inet_arnn_generate_ws_floats(int L, int E, int Hc, int H, int U, int V) {
     if (L <= 0 || E <= 0 || Hc < 0 || H <= 0 || H % 16 || U <= 0 || V <= 0) return -1;
-    return (int64_t)arnn_generate_ws_floats(L, E, Hc, H, U, V);
+    return (int64_t)arnn_generate_ws_floats(ArnnGenNet{E, Hc, H, U, V}, L);
 }
 int inet_arnn_generate(int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_stride,
                        const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0, const float* W_ih1,
@@ -391,13 +392,13 @@ int inet_arnn_generate(int L, int E, int Hc, int H, int U, int V, const float* e
     if (L <= 0 || E <= 0 || Hc < 0 || H <= 0 || H % 16 || U <= 0 || V <= 0 || !emb || (Hc && !oc0) || !W_ih0 || !b_ih0 || !W_hh0 ||
         !b_hh0 || !W_ih1 || !b_ih1 || !W_hh1 || !b_hh1 || !W1 || !b1 || !W2 || !b2 || !tokens || !ws)
         return -1;
-    if (ws_floats < (int64_t)arnn_generate_ws_floats(L, E, Hc, H, U, V)) return -1;
-    return arnn_generate(L, E, Hc, H, U, V, emb, oc0, (long)oc_stride, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1,
-                         W2, b2, hc_init, (const long long*)first_tok, (long long*)tokens, ws, (hipStream_t)stream);
+    const ArnnGenNet net{E, Hc, H, U, V, emb, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2};
+    if (ws_floats < (int64_t)arnn_generate_ws_floats(net, L)) return -1;
+    return arnn_generate(net, L, oc0, (long)oc_stride, hc_init, (const long long*)first_tok, (long long*)tokens, ws, (hipStream_t)stream);
 }
 int64_t inet_arnn_sample_ws_floats(int R, int L, int E, int Hc, int H, int U, int V) {
     if (R < 1 || L < 1 || E <= 0 || Hc < 0 || H <= 0 || H % 16 || U <= 0 || V <= 0) return -1;
-    return (int64_t)arnn_sample_ws_floats(R, L, E, Hc, H, U, V);
+    return (int64_t)arnn_sample_ws_floats(ArnnGenNet{E, Hc, H, U, V}, R, L);
 }
 int inet_arnn_sample(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
                      int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,
@@ -408,9 +409,10 @@ int inet_arnn_sample(int R, int L, int E, int Hc, int H, int U, int V, const flo
         !W_hh0 || !b_hh0 || !W_ih1 || !b_ih1 || !W_hh1 || !b_hh1 || !W1 || !b1 || !W2 || !b2 || !uniforms || !tokens || !ws)
         return -1;
     if (!std::isfinite(temperature) || oc_row_stride < 0 || oc_batch_stride < 0) return -1;
-    if (ws_floats < (int64_t)arnn_sample_ws_floats(R, L, E, Hc, H, U, V)) return -1;
-    return arnn_sample(R, L, E, Hc, H, U, V, emb, oc0, (long)oc_row_stride, (long)oc_batch_stride, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1,
-                       b_ih1, W_hh1, b_hh1, W1, b1, W2, b2, temperature, uniforms, hc_init, (long long*)tokens, ws, (hipStream_t)stream);
+    const ArnnGenNet net{E, Hc, H, U, V, emb, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2};
+    if (ws_floats < (int64_t)arnn_sample_ws_floats(net, R, L)) return -1;
+    return arnn_sample(net, R, L, oc0, (long)oc_row_stride, (long)oc_batch_stride, temperature, uniforms, hc_init, (long long*)tokens, ws,
+                       (hipStream_t)stream);
 }
 int inet_lstm2_bwd(int B, int T, int H, const float* W_hh0, const float* W_ih1, const float* W_hh1, const float* out0,
                    const float* out1, const float* dout1, int reverse, float* dgi0, float* dgi1, float* dout0,

@@ -1,9 +1,10 @@
-// AnticipationRNN's free-running token pass as ONE persistent launch (round 5).
+// AnticipationRNN's token generation (arnn_gen.h): the free-running token pass as ONE persistent launch (round 5), and the per-tick
+// launches behind it for every other shape.
 //
 // The reference's free-running forward (AnticipationRNN/anticipation_rnn_gauss_reg_model.py:190-259) feeds the argmax of BATCH
 // ELEMENT 0 back to the whole batch (:253-256): the L tokens depend on that one row, and producing them is strictly sequential --
 // per tick  [embedding of the previous token | constraint output of the tick] -> LSTM 0 -> LSTM 1 -> ReLU(linear_1) -> note head ->
-// argmax.  Round 4 queued that as four small launches per tick (lstm.hip arnn_generate): 14.3 us per tick = 4 x 3.6 us per dependent
+// argmax.  Round 4 queued that as four small launches per tick (arnn_ticks at the end of this file): 14.3 us per tick = 4 x 3.6 us per dependent
 // launch, 5.5 ms of the 14.4 ms free-running training step.  Here 13 workgroups of 512 threads stay resident for the whole
 // sequence, every one with its weights in REGISTERS (a 256 x 256 f32 slice: 128 VGPRs per thread, see "Threads and products"
 // below), and 1-KB vectors move between them as 8-byte {value, tick} granules (one relaxed agent-scope 64-bit store / polled load
@@ -41,7 +42,7 @@
 #define INET_GRANULE_KID chain::K_ARNN_GEN
 #include "granule.h"
 #include "prof.h"
-#include "lstm.h"
+#include "arnn_gen.h"
 #include "pointwise.h"
 #include "sample.h"
 
@@ -430,41 +431,51 @@ int mode() {
     return g_mode;
 }
 constexpr long kExFloats = 2 * kExGranules + 64; // ... as floats, + the launch's status word (64 floats behind them)
-}  // namespace
 
-void arnn_gen_set_mode(int m) { g_mode = (m < 0 || m > 4) ? 3 : m; }
-
-bool arnn_token_pass_ok(int H, int U, int V) { return mode() != 0 && chain_enabled() && H == GH && U == GH && V >= 1 && V <= 128; }
+bool arnn_token_pass_ok(const ArnnGenNet& n) {
+    return mode() != 0 && chain_enabled() && n.H == GH && n.U == GH && n.V >= 1 && n.V <= 128;
+}
 
 // tables | exchange + status | stamps (2 x L x 8 64-bit words, written only under INET_ARNN_GEN_STAMPS=1: tools/arnn_token_pass.py)
 size_t arnn_token_pass_ws_floats(int L, int V) { return (size_t)L * G4 + (size_t)V * G4 + (size_t)kExFloats + 64 + (size_t)32 * L; }
 long arnn_token_pass_stamps_offset(int L, int V) { return (long)L * G4 + (long)V * G4 + kExFloats + 64; }
 
-int arnn_token_pass(int L, int E, int Hc, int V, const float* emb, const float* oc0, long oc_stride, const float* W_ih0,
-                    const float* b_ih0, const float* W_hh0, const float* b_hh0, const float* W_ih1, const float* b_ih1,
-                    const float* W_hh1, const float* b_hh1, const float* W1, const float* b1, const float* W2, const float* b2,
-                    const float* hc_init, const long long* first_tok, long long* tokens, float* ws, hipStream_t s) {
+// the prep launch of `rows` rows (row i from oc0 + i * oc_bstride) and the pass behind it, as far as the network and the workspace decide
+PrepArgs prep_args(const ArnnGenNet& n, int L, int rows, const float* oc0, long oc_stride, long oc_bstride, float* pre, float* T0) {
+    PrepArgs p{};
+    p.L = L; p.V = n.V; p.E = n.E; p.Hc = n.Hc; p.K0 = n.E + n.Hc;
+    p.nb_pre = (G4 / 64) * ((L + 15) / 16); p.rows = rows;
+    p.oc0 = oc0; p.oc_stride = oc_stride; p.oc_bstride = oc_bstride;
+    p.emb = n.emb; p.W_ih0 = n.W_ih0; p.b_ih0 = n.b_ih0; p.b_hh0 = n.b_hh0; p.pre = pre; p.T0 = T0;
+    return p;
+}
+GenArgs gen_args(const ArnnGenNet& n, int L, const float* pre, const float* T0, unsigned long long* ex, unsigned* status) {
+    GenArgs a{};
+    a.L = L; a.V = n.V; a.E = n.E; a.K0 = n.E + n.Hc;
+    // (mode 4: test hook -- XCD-local stores REQUESTED on consecutive ids: the workgroups must find out that they do not share an XCD)
+    a.stride = (mode() == 2 || mode() == 3) ? 8 : 1; a.near = mode() >= 3;
+    a.emb = n.emb; a.W_ih0 = n.W_ih0; a.W_hh0 = n.W_hh0; a.W_ih1 = n.W_ih1; a.b_ih1 = n.b_ih1; a.W_hh1 = n.W_hh1; a.b_hh1 = n.b_hh1;
+    a.W1 = n.W1; a.b1 = n.b1; a.W2 = n.W2; a.b2 = n.b2; a.pre = pre; a.T0 = T0;
+    a.ex = ex; a.status = chain_status_for(status);
+    return a;
+}
+
+int arnn_token_pass(const ArnnGenNet& n, int L, const float* oc0, long oc_stride, const float* hc_init, const long long* first_tok,
+                    long long* tokens, float* ws, hipStream_t s) {
+    const int V = n.V;
     float* pre = ws;
     float* T0 = pre + (size_t)L * G4;
     // (the exchange starts on a 16-float boundary behind the tables: L * 4H and V * 4H are multiples of 1024)
     unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
     unsigned* status = reinterpret_cast<unsigned*>(ex + kExGranules);
     if (hipMemsetAsync(ex, 0, (size_t)kExFloats * sizeof(float), s) != hipSuccess) return -2;
-    PrepArgs p{};
-    p.L = L; p.V = V; p.E = E; p.Hc = Hc; p.K0 = E + Hc;
-    p.nb_pre = (G4 / 64) * ((L + 15) / 16); p.rows = 1;
-    p.oc0 = oc0; p.oc_stride = oc_stride; p.emb = emb; p.W_ih0 = W_ih0; p.b_ih0 = b_ih0; p.b_hh0 = b_hh0; p.pre = pre; p.T0 = T0;
+    const PrepArgs p = prep_args(n, L, 1, oc0, oc_stride, 0, pre, T0);
     const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
     hipLaunchKernelGGL(arnn_gen_prep_kernel, dim3(p.nb_pre + nb_t0), dim3(256), 0, s, p);
-    GenArgs a{};
-    a.L = L; a.V = V; a.E = E; a.K0 = E + Hc; a.stride = (mode() == 2 || mode() == 3) ? 8 : 1; a.near = mode() >= 3;   // (4: test hook -- XCD-local stores REQUESTED on
-                                                                                // consecutive ids: the workgroups must find out that they do not share an XCD)
-    a.emb = emb; a.W_ih0 = W_ih0; a.W_hh0 = W_hh0; a.W_ih1 = W_ih1; a.b_ih1 = b_ih1; a.W_hh1 = W_hh1; a.b_hh1 = b_hh1;
-    a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.pre = pre; a.T0 = T0;
-    a.hc_init = hc_init; a.first_tok = first_tok; a.tokens = tokens; a.ex = ex;
+    GenArgs a = gen_args(n, L, pre, T0, ex, status);
+    a.hc_init = hc_init; a.first_tok = first_tok; a.tokens = tokens;
     static const bool stamps = [] { const char* v = std::getenv("INET_ARNN_GEN_STAMPS"); return v && v[0] == '1'; }();
     a.stamps = stamps ? reinterpret_cast<unsigned long long*>(ws + arnn_token_pass_stamps_offset(L, V)) : nullptr;
-    a.status = chain_status_for(status);
     char label[64];
     std::snprintf(label, sizeof label, "arnn_token_pass L%d V%d", L, V);
     // per tick: four 1024 x 256 products (one of them, the input side of layer 0, in the prep launch), linear_1, the head
@@ -477,13 +488,11 @@ int arnn_token_pass(int L, int E, int Hc, int V, const float* emb, const float* 
 }
 
 // ---- the sampling build: R independent rows, up to 8 teams of 13 workgroups per launch ----
-namespace {
 // teams per launch: at most 8 (the stride-8 placement has 8 residues), and 13 x teams workgroups inside the chain capacity
 int sample_teams(int R) {
     const int cap = chain_capacity() / 13;
     return std::max(1, std::min(std::min(R, 8), cap));
 }
-}  // namespace
 
 // pre [teams][L][4H] | T0 [V][4H] | exchange [teams][kExGranules] granules + the status word (64 floats) + 64
 size_t arnn_token_sample_ws_floats(int R, int L, int V) {
@@ -491,12 +500,9 @@ size_t arnn_token_sample_ws_floats(int R, int L, int V) {
     return n * L * G4 + (size_t)V * G4 + n * 2 * kExGranules + 64 + 64;
 }
 
-int arnn_token_sample(int R, int L, int E, int Hc, int V, const float* emb, const float* oc0, long oc_stride, long oc_bstride,
-                      const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0, const float* W_ih1,
-                      const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1, const float* W2,
-                      const float* b2, float temp, const double* uniforms, const float* hc_init, long long* tokens, float* ws,
-                      hipStream_t s) {
-    const int n = sample_teams(R);
+int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
+                      const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s) {
+    const int V = net.V, n = sample_teams(R);
     float* pre = ws;
     float* T0 = pre + (size_t)n * L * G4;
     unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
@@ -507,19 +513,10 @@ int arnn_token_sample(int R, int L, int E, int Hc, int V, const float* emb, cons
         const int rows = std::min(n, R - r0);
         unsigned* status = reinterpret_cast<unsigned*>(ex + rows * kExGranules);
         if (hipMemsetAsync(ex, 0, ((size_t)rows * 2 * kExGranules + 64) * sizeof(float), s) != hipSuccess) return -2;
-        PrepArgs p{};
-        p.L = L; p.V = V; p.E = E; p.Hc = Hc; p.K0 = E + Hc;
-        p.nb_pre = (G4 / 64) * ((L + 15) / 16); p.rows = rows;
-        p.oc0 = oc0 + (long)r0 * oc_bstride; p.oc_stride = oc_stride; p.oc_bstride = oc_bstride;
-        p.emb = emb; p.W_ih0 = W_ih0; p.b_ih0 = b_ih0; p.b_hh0 = b_hh0; p.pre = pre; p.T0 = T0;
+        const PrepArgs p = prep_args(net, L, rows, oc0 + (long)r0 * oc_bstride, oc_stride, oc_bstride, pre, T0);
         hipLaunchKernelGGL(arnn_gen_prep_kernel, dim3(p.nb_pre * rows + (r0 == 0 ? nb_t0 : 0)), dim3(256), 0, s, p);
-        GenArgs a{};
-        a.L = L; a.V = V; a.E = E; a.K0 = E + Hc; a.stride = (mode() == 2 || mode() == 3) ? 8 : 1; a.near = mode() >= 3;
-        a.emb = emb; a.W_ih0 = W_ih0; a.W_hh0 = W_hh0; a.W_ih1 = W_ih1; a.b_ih1 = b_ih1; a.W_hh1 = W_hh1; a.b_hh1 = b_hh1;
-        a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.pre = pre; a.T0 = T0;
-        a.hc_init = hc_init ? hc_init + (long)r0 * 4 * GH : nullptr; a.first_tok = nullptr; a.tokens = tokens + (long)r0 * L; a.ex = ex;
-        a.stamps = nullptr;
-        a.status = chain_status_for(status);
+        GenArgs a = gen_args(net, L, pre, T0, ex, status);
+        a.hc_init = hc_init ? hc_init + (long)r0 * 4 * GH : nullptr; a.tokens = tokens + (long)r0 * L;
         a.rows = rows; a.temp = temp; a.uniforms = uniforms + (long)r0 * L;
         ProfScope prof(PROF_GRU_FWD, 2.0 * rows * L * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH), s, label,
                        4.0 * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH + (double)(rows * L + V) * G4));
@@ -529,4 +526,247 @@ int arnn_token_sample(int R, int L, int E, int Hc, int V, const float* emb, cons
         if (hipGetLastError() != hipSuccess) return -2;
     }
     return 0;
+}
+}  // namespace
+
+void arnn_gen_set_mode(int m) { g_mode = (m < 0 || m > 4) ? 3 : m; }
+
+// ---- The per-tick launches: every shape the persistent pass does not take (and mode 0) ---------------------------------------------
+// L ticks of ONE row -- per tick: input = [embedding of the previous token | constraint output of the tick], two LSTM cells,
+// linear_1 + ReLU, the note head, argmax or draw -- as 4 small launches per tick queued from here (no host round trip: the token
+// stays on the device).  (The free-running pass needs batch element 0 alone, see the head of this file; with its tokens the caller
+// runs the whole batch through the batched, teacher-forced-shaped kernels: 195 -> 14 ms per training step.)
+namespace {
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// dot products of ONE row against weight rows, lanes striding over k: every load of a wave is issued before the first multiply (NI =
+// ceil(K / 64) is a template bound: a runtime k loop waits for each 64-wide slice in turn -- 7 us per launch instead of 2)
+template <int NI>
+__device__ __forceinline__ void load_x(float (&xv)[NI], const float* pa, int Ka, const float* pb, int K, int lane) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        const int k = lane + 64 * i;
+        xv[i] = k < Ka ? pa[k] : (k < K ? pb[k - Ka] : 0.f);
+    }
+}
+template <int NI>
+__device__ __forceinline__ float dot_row(const float* __restrict__ Wrow, const float (&xv)[NI], int K, int lane) {
+    float wv[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) { const int k = lane + 64 * i; wv[i] = k < K ? Wrow[k] : 0.f; }
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) a = fmaf(wv[i], xv[i], a);
+    return a;
+}
+
+// One LSTM cell for ONE row, both products in the launch: gates = W_ih [xa | xb] + b_ih + W_hh h_prev + b_hh.  One wave per hidden
+// unit (its four gate rows), four units per workgroup.  xa = the embedding row of *tok (tok null: token 0) when `emb` is given.
+template <int NI, int NH>
+__global__ __launch_bounds__(256) void lstm_cell_b1_kernel(const float* __restrict__ emb, const long long* __restrict__ tok,
+                                                           const float* __restrict__ xa, int Ka, const float* __restrict__ xb, int Kb,
+                                                           const float* __restrict__ W_ih, const float* __restrict__ b_ih,
+                                                           const float* __restrict__ h_prev, const float* __restrict__ c_prev,
+                                                           const float* __restrict__ W_hh, const float* __restrict__ b_hh,
+                                                           float* __restrict__ h_new, float* __restrict__ c_new, int H) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + w;
+    const int K = Ka + Kb;
+    const float* pa = emb ? emb + (tok ? *tok : 0) * Ka : xa;
+    float xv[NI], hv[NH];
+    load_x<NI>(xv, pa, Ka, xb, K, lane);
+    load_x<NH>(hv, h_prev, H, nullptr, H, lane);
+    float pre[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+        pre[g] = dot_row<NI>(W_ih + (long)(g * H + j) * K, xv, K, lane) + dot_row<NH>(W_hh + (long)(g * H + j) * H, hv, H, lane);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) pre[g] = wave_sum(pre[g]);
+    if (lane == 0) {
+        const float i = sigmoid_f(pre[0] + b_ih[j] + b_hh[j]);
+        const float f = sigmoid_f(pre[1] + b_ih[H + j] + b_hh[H + j]);
+        const float g = tanh_f(pre[2] + b_ih[2 * H + j] + b_hh[2 * H + j]);
+        const float o = sigmoid_f(pre[3] + b_ih[3 * H + j] + b_hh[3 * H + j]);
+        const float c = f * c_prev[j] + i * g;
+        c_new[j] = c;
+        h_new[j] = o * tanh_f(c);
+    }
+}
+
+// y[j] = ReLU(W[j,:] . x + b[j]) for ONE row: a wave per output
+template <int NI>
+__global__ __launch_bounds__(256) void relu_linear_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                             const float* __restrict__ b, float* __restrict__ y, int N, int K) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + w;
+    if (j >= N) return;
+    float xv[NI];
+    load_x<NI>(xv, x, K, nullptr, K, lane);
+    const float v = wave_sum(dot_row<NI>(W + (long)j * K, xv, K, lane));
+    if (lane == 0) y[j] = fmaxf(v + b[j], 0.f);
+}
+
+// does (b2, i2) come before (best, bi) in numpy's argmax order?  NaN > everything, ties to the lower index
+__device__ __forceinline__ bool argmax_better(float b2, int i2, float best, int bi) {
+    const bool n2 = b2 != b2, n1 = best != best;
+    if (n2 || n1) return n2 && (!n1 || i2 < bi);
+    return b2 > best || (b2 == best && i2 < bi);
+}
+
+// np.argmax order over lg[0 .. V) (anticipation_rnn_gauss_reg_model.py:253) by one wave: a NaN is the maximum, the lowest index wins
+// among equals -- an all-NaN or all -inf row yields a token INSIDE the vocabulary (the next tick gathers the embedding row by it)
+__device__ __forceinline__ int argmax_wave(const float* lg, int V, int lane) {
+    float best = lane < V ? lg[lane] : -INFINITY;
+    int bi = lane < V ? lane : 0x7fffffff;
+    for (int v = lane + 64; v < V; v += 64)
+        if (argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float b2 = __shfl_xor(best, o, 64);
+        const int i2 = __shfl_xor(bi, o, 64);
+        if (argmax_better(b2, i2, best, bi)) { best = b2; bi = i2; }
+    }
+    return bi;
+}
+
+// token = argmax_v (W[v,:] . x + b[v]), lowest index on ties, V <= 256: ONE workgroup of 16 waves; a wave's rows (V = 48: three) are all
+// requested before the first sum, the logits meet in LDS and the first wave takes the argmax with shuffles
+template <int NI>
+__global__ __launch_bounds__(1024) void head_argmax_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                              const float* __restrict__ b, long long* __restrict__ tok, int V, int K) {
+    __shared__ float lg[256];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float xv[NI];
+    load_x<NI>(xv, x, K, nullptr, K, lane);
+    float part[16];                                            // rows w, w + 16, ...: V <= 256
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        if (v < V) {                                           // (wave-uniform)
+            const float a = wave_sum(part[r]);
+            if (lane == 0) lg[v] = a + b[v];
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        const int bi = argmax_wave(lg, V, lane);
+        if (lane == 0) *tok = bi < V ? bi : 0;
+    }
+}
+
+// head_argmax_b1_kernel's products, then token = a draw from softmax(temp * logits) with the uniform *u (sample.h: numpy's
+// np.random.choice order, anticipation_rnn_gauss_reg_model.py:655-667); a NaN logit, a non-finite total or a uniform outside [0, 1)
+// keep the argmax rule.  V <= 256.
+template <int NI>
+__global__ __launch_bounds__(1024) void head_sample_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                              const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
+                                                              float temp, const double* __restrict__ u) {
+    __shared__ float lg[256];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float xv[NI];
+    load_x<NI>(xv, x, K, nullptr, K, lane);
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        if (v < V) {
+            const float a = wave_sum(part[r]);
+            if (lane == 0) lg[v] = a + b[v];
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        float sv[4], ms = -INFINITY;
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = lane + 64 * j;
+            sv[j] = v < V ? lg[v] * temp : -INFINITY;
+            nan |= sv[j] != sv[j];
+            ms = fmaxf(ms, sv[j]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
+        int bi = __ballot(nan) ? -1 : sample::pick<4>(sv, ms, *u, V, lane);
+        if (bi < 0) bi = argmax_wave(lg, V, lane);
+        if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
+    }
+}
+
+// the template bounds of the one-row kernels (ops.arnn_generate_ok in Python)
+bool arnn_ticks_ok(const ArnnGenNet& n) { return n.E + n.Hc <= 320 && n.H <= 256 && n.U <= 256 && n.V <= 256; }
+size_t arnn_ticks_ws_floats(const ArnnGenNet& n) { return (size_t)(n.E + n.Hc) + 4 * (size_t)n.H + 8 * (size_t)n.H + n.U + n.V + 64; }
+
+// L ticks of one row from the state hc_init [layer][h | c][H] (null: zeros; inpainting: the state after the prefix) and the token
+// *first_tok (null: 0); `uniforms` [L]: the sampling head, null: the argmax head
+int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, const float* hc_init, const long long* first_tok,
+               float temp, const double* uniforms, long long* tokens, float* ws, hipStream_t s) {
+    const int H = n.H;
+    float* hc = ws;                                            // [layer][h|c][ping-pong][H]
+    float* u = hc + 8 * H;
+    if (pw_zero(hc, 8L * H, s) != 0) return -2;
+    auto H_ = [&](int l, int p) { return hc + ((l * 2 + 0) * 2 + p) * H; };
+    auto C_ = [&](int l, int p) { return hc + ((l * 2 + 1) * 2 + p) * H; };
+    if (hc_init)
+        for (int l = 0; l < 2; ++l)
+            if (pw_copy_bytes(H_(l, 0), hc_init + (2 * l) * H, H * sizeof(float), s) != 0 ||
+                pw_copy_bytes(C_(l, 0), hc_init + (2 * l + 1) * H, H * sizeof(float), s) != 0) return -2;
+    for (int t = 0, p = 0; t < L; ++t, p ^= 1) {
+        hipLaunchKernelGGL((lstm_cell_b1_kernel<5, 4>), dim3(H / 4), dim3(256), 0, s, n.emb, t ? tokens + t - 1 : first_tok,
+                           (const float*)nullptr, n.E, oc + (long)t * oc_stride, n.Hc, n.W_ih0, n.b_ih0, (const float*)H_(0, p),
+                           (const float*)C_(0, p), n.W_hh0, n.b_hh0, H_(0, p ^ 1), C_(0, p ^ 1), H);
+        hipLaunchKernelGGL((lstm_cell_b1_kernel<4, 4>), dim3(H / 4), dim3(256), 0, s, (const float*)nullptr, (const long long*)nullptr,
+                           (const float*)H_(0, p ^ 1), H, (const float*)nullptr, 0, n.W_ih1, n.b_ih1, (const float*)H_(1, p),
+                           (const float*)C_(1, p), n.W_hh1, n.b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
+        hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((n.U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), n.W1, n.b1, u,
+                           n.U, H);
+        if (uniforms)
+            hipLaunchKernelGGL((head_sample_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
+                               temp, uniforms + t);
+        else
+            hipLaunchKernelGGL((head_argmax_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+}  // namespace
+
+// ---- The entry points: the persistent pass where it applies (the reference's configuration), the ticks otherwise ------------------
+size_t arnn_generate_ws_floats(const ArnnGenNet& n, int L) {
+    return std::max(arnn_ticks_ws_floats(n), arnn_token_pass_ok(n) ? arnn_token_pass_ws_floats(L, n.V) : (size_t)0);
+}
+size_t arnn_sample_ws_floats(const ArnnGenNet& n, int R, int L) {
+    return std::max(arnn_ticks_ws_floats(n), arnn_token_pass_ok(n) ? arnn_token_sample_ws_floats(R, L, n.V) : (size_t)0);
+}
+
+int arnn_generate(const ArnnGenNet& n, int L, const float* oc0, long oc_stride, const float* hc_init, const long long* first_tok,
+                  long long* tokens, float* ws, hipStream_t s) {
+    if (arnn_token_pass_ok(n)) return arnn_token_pass(n, L, oc0, oc_stride, hc_init, first_tok, tokens, ws, s);   // 14.3 -> ~3.5 us per tick
+    if (!arnn_ticks_ok(n)) return -1;
+    return arnn_ticks(n, L, oc0, oc_stride, hc_init, first_tok, 0.f, nullptr, tokens, ws, s);
+}
+
+int arnn_sample(const ArnnGenNet& n, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
+                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s) {
+    if (arnn_token_pass_ok(n))                                 // up to 8 rows per launch
+        return arnn_token_sample(n, R, L, oc0, oc_stride, oc_bstride, temp, uniforms, hc_init, tokens, ws, s);
+    if (!arnn_ticks_ok(n)) return -1;
+    int rc = 0;
+    for (int r = 0; r < R && rc == 0; ++r)                     // the rows one after the other
+        rc = arnn_ticks(n, L, oc0 + (long)r * oc_bstride, oc_stride, hc_init ? hc_init + (long)r * 4 * n.H : nullptr, nullptr, temp,
+                        uniforms + (long)r * L, tokens + (long)r * L, ws, s);
+    return rc;
 }

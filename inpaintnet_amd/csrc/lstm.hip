@@ -10,7 +10,6 @@
 #include "prof.h"
 #include "seq.h"
 #include "lstm.h"
-#include "sample.h"
 
 using namespace ksplit;
 
@@ -586,6 +585,26 @@ int launch_chain(K kernel, const A& a, int groups, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// the chain kernels by tile (ms = 1, 2, 4) and width (H = 256, 512); tagged: the tagged hand-off, built for H = 256 and ms <= 2
+int launch_lstm_chain_fwd(const LstmChainFwdArgs& a, int ms, int groups, bool tagged, hipStream_t s) {
+    if (tagged)
+        return ms == 1 ? launch_chain(lstm_chain_fwd_tag_kernel<1, 4>, a, groups, s) : launch_chain(lstm_chain_fwd_tag_kernel<2, 4>, a, groups, s);
+    if (a.H == 256) return ms == 1 ? launch_chain(lstm_chain_fwd_kernel<1, 4>, a, groups, s)
+                         : ms == 2 ? launch_chain(lstm_chain_fwd_kernel<2, 4>, a, groups, s)
+                                   : launch_chain(lstm_chain_fwd_kernel<4, 4>, a, groups, s);
+    return ms == 1 ? launch_chain(lstm_chain_fwd_kernel<1, 8>, a, groups, s)
+           : ms == 2 ? launch_chain(lstm_chain_fwd_kernel<2, 8>, a, groups, s)
+                     : launch_chain(lstm_chain_fwd_kernel<4, 8>, a, groups, s);
+}
+int launch_lstm_chain_bwd(const LstmChainBwdArgs& a, int ms, int groups, hipStream_t s) {
+    if (a.H == 256) return ms == 1 ? launch_chain(lstm_chain_bwd_kernel<1, 16>, a, groups, s)
+                         : ms == 2 ? launch_chain(lstm_chain_bwd_kernel<2, 16>, a, groups, s)
+                                   : launch_chain(lstm_chain_bwd_kernel<4, 16>, a, groups, s);
+    return ms == 1 ? launch_chain(lstm_chain_bwd_kernel<1, 32>, a, groups, s)
+           : ms == 2 ? launch_chain(lstm_chain_bwd_kernel<2, 32>, a, groups, s)
+                     : launch_chain(lstm_chain_bwd_kernel<4, 32>, a, groups, s);
+}
+
 // rows per group (16 * MS): the smallest tile that still fits the launch on the chip -- a step of these chains is mostly
 // hand-off latency plus the MFMAs of ONE workgroup (B = 32, H = 256: 1.9 of 4.1 us with 32 rows per workgroup), so more,
 // smaller groups shorten every step (AnticipationRNN: two 16-row groups instead of one 32-row group)
@@ -631,6 +650,28 @@ size_t lstm_carve(int B, int T, int H, int save, void* base, LstmWs& w) {
     return cv.bytes();
 }
 
+// Forward steps [s_lo, s_lo + nt) of a T-step layer as ONE chain launch from the cell state cprev [B,H]; the caller has zeroed the
+// counters and put the previous h into its slot of w.hx.  The kernel sees a sequence of nt steps whose buffers start at the chunk's
+// lowest time index; the saves keep the full sequence's array stride.  (The whole sequence: s_lo = 0, nt = T.)
+int lstm_chain_fwd_steps(int B, int T, int H, const float* gi, const float* W_hh, const float* b_hh, const float* cprev, int reverse,
+                         float* out, LstmWs& w, int save, int s_lo, int nt, bool tagged, int xrot, int phase, hipStream_t s) {
+    const long BH = (long)B * H, TBH = (long)T * BH;
+    const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
+    const long t_lo = reverse ? T - (s_lo + nt) : s_lo;
+    LstmChainFwdArgs a{};
+    a.B = B; a.H = H; a.T = nt; a.reverse = reverse; a.members = H / 16;
+    a.gi = gi + t_lo * B * 4 * H; a.W_hh = W_hh; a.b_hh = b_hh; a.c0 = cprev;
+    a.out = out + t_lo * BH; a.cseq = w.cseq + t_lo * BH;
+    if (save) { a.sv = w.sv + t_lo * BH; a.sv_stride = TBH; }
+    a.hx = w.hx; a.counters = w.sync; a.status = chain_status_for(w.sync + kStatusWord); a.xrot = xrot & 7;
+    a.phase = phase;
+    char label[64];
+    std::snprintf(label, sizeof label, "lstm_chain_fwd ms%d T%d B%d H%d", ms, nt, B, H);
+    ProfScope prof(PROF_GRU_FWD, 2.0 * nt * B * 4.0 * H * H, s, label,
+                   4.0 * (4.0 * H * H + (double)nt * B * H * (4 + 2 + (save ? 6 : 0))));
+    return launch_lstm_chain_fwd(a, ms, groups, tagged, s);
+}
+
 }  // namespace
 
 size_t lstm_ws_bytes(int B, int T, int H, int save) {
@@ -646,27 +687,9 @@ int lstm_seq_fwd(int B, int T, int H, const float* gi, const float* W_hh, const 
     const long BH = (long)B * H, TBH = (long)T * BH;
     if ((!h0 || !c0) && pw_zero(w.zeros, BH, s) != 0) return -2;
     if (lstm_chain_ok(B, H)) {
-        const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
         if (hipMemsetAsync(w.sync, 0, kSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
         INET_TRY(pw_pack_frag(h0 ? h0 : w.zeros, H, B, H, w.hx + pk_floats(B, H), 0, 1, 0, 0, s));   // slot 1 = h0
-        LstmChainFwdArgs a{};
-        a.B = B; a.H = H; a.T = T; a.reverse = reverse; a.members = H / 16;
-        a.gi = gi; a.W_hh = W_hh; a.b_hh = b_hh; a.c0 = c0 ? c0 : w.zeros;
-        a.out = out; a.cseq = w.cseq;
-        if (save) { a.sv = w.sv; a.sv_stride = TBH; }
-        a.hx = w.hx; a.counters = w.sync; a.status = chain_status_for(w.sync + kStatusWord);
-        char label[64];
-        std::snprintf(label, sizeof label, "lstm_chain_fwd ms%d T%d B%d H%d", ms, T, B, H);
-        ProfScope prof(PROF_GRU_FWD, 2.0 * T * B * 4.0 * H * H, s, label,
-                       4.0 * (4.0 * H * H + (double)T * B * H * (4 + 2 + (save ? 6 : 0))));
-        int rc;
-        if (H == 256) rc = ms == 1 ? launch_chain(lstm_chain_fwd_kernel<1, 4>, a, groups, s)
-                           : ms == 2 ? launch_chain(lstm_chain_fwd_kernel<2, 4>, a, groups, s)
-                                     : launch_chain(lstm_chain_fwd_kernel<4, 4>, a, groups, s);
-        else rc = ms == 1 ? launch_chain(lstm_chain_fwd_kernel<1, 8>, a, groups, s)
-                  : ms == 2 ? launch_chain(lstm_chain_fwd_kernel<2, 8>, a, groups, s)
-                            : launch_chain(lstm_chain_fwd_kernel<4, 8>, a, groups, s);
-        INET_TRY(rc);
+        INET_TRY(lstm_chain_fwd_steps(B, T, H, gi, W_hh, b_hh, c0 ? c0 : w.zeros, reverse, out, w, save, 0, T, false, 0, 0, s));
     } else
     for (int step = 0; step < T; ++step) {
         const int t = reverse ? T - 1 - step : step;
@@ -689,14 +712,10 @@ int lstm_seq_fwd(int B, int T, int H, const float* gi, const float* W_hh, const 
 
 namespace {
 
-// Forward steps [s_lo, s_lo + nt) of a T-step layer as ONE chain launch that continues from (hprev, cprev) [B,H]
-// (the state after step s_lo - 1: rows of `out` / `cseq`, or zeros).  The kernel sees a sequence of nt steps whose
-// buffers start at the chunk's lowest time index; the saves keep the full sequence's array stride.
+// lstm_chain_fwd_steps as a chunk of a pipeline: continues from (hprev, cprev) [B,H] (the state after step s_lo - 1: rows of `out` /
+// `cseq`, or zeros), one prologue launch in front.
 int lstm_chunk_fwd(int B, int T, int H, const float* gi, const float* W_hh, const float* b_hh, const float* hprev,
                    const float* cprev, int reverse, float* out, LstmWs& w, int save, int s_lo, int nt, hipStream_t s, int xrot) {
-    const long BH = (long)B * H, TBH = (long)T * BH;
-    const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
-    const long t_lo = reverse ? T - (s_lo + nt) : s_lo;
     // tagged hand-off (lstm_chain_fwd_tag_kernel) for the small tiles; the counter protocol otherwise.  (The same
     // for the backward chain -- 16 fragments per lane to poll, four gate blocks per member to wait for -- measured slower
     // than its counter: 9.34 vs 9.23 ms per AnticipationRNN step with both, 8.87 with the forward chains only.)
@@ -710,25 +729,7 @@ int lstm_chunk_fwd(int B, int T, int H, const float* gi, const float* W_hh, cons
                            w.hx + (tagged ? 3 : 1) * pk_floats(B, H));
         if (hipGetLastError() != hipSuccess) return -2;
     }
-    LstmChainFwdArgs a{};
-    a.B = B; a.H = H; a.T = nt; a.reverse = reverse; a.members = H / 16;
-    a.gi = gi + t_lo * B * 4 * H; a.W_hh = W_hh; a.b_hh = b_hh; a.c0 = cprev;
-    a.out = out + t_lo * BH; a.cseq = w.cseq + t_lo * BH;
-    if (save) { a.sv = w.sv + t_lo * BH; a.sv_stride = TBH; }
-    a.hx = w.hx; a.counters = w.sync; a.status = chain_status_for(w.sync + kStatusWord); a.xrot = xrot & 7;
-    a.phase = cont ? s_lo : 0;
-    char label[64];
-    std::snprintf(label, sizeof label, "lstm_chain_fwd ms%d T%d B%d H%d", ms, nt, B, H);
-    ProfScope prof(PROF_GRU_FWD, 2.0 * nt * B * 4.0 * H * H, s, label,
-                   4.0 * (4.0 * H * H + (double)nt * B * H * (4 + 2 + (save ? 6 : 0))));
-    if (tagged)
-        return ms == 1 ? launch_chain(lstm_chain_fwd_tag_kernel<1, 4>, a, groups, s) : launch_chain(lstm_chain_fwd_tag_kernel<2, 4>, a, groups, s);
-    if (H == 256) return ms == 1 ? launch_chain(lstm_chain_fwd_kernel<1, 4>, a, groups, s)
-                       : ms == 2 ? launch_chain(lstm_chain_fwd_kernel<2, 4>, a, groups, s)
-                                 : launch_chain(lstm_chain_fwd_kernel<4, 4>, a, groups, s);
-    return ms == 1 ? launch_chain(lstm_chain_fwd_kernel<1, 8>, a, groups, s)
-           : ms == 2 ? launch_chain(lstm_chain_fwd_kernel<2, 8>, a, groups, s)
-                     : launch_chain(lstm_chain_fwd_kernel<4, 8>, a, groups, s);
+    return lstm_chain_fwd_steps(B, T, H, gi, W_hh, b_hh, cprev, reverse, out, w, save, s_lo, nt, tagged, xrot, cont ? s_lo : 0, s);
 }
 
 // Backward through forward steps [s_lo, s_lo + nt) as one chain launch: (dhT, dcT) = the gradient into the state after
@@ -755,12 +756,7 @@ int lstm_chunk_bwd(int B, int T, int H, const float* dout, const float* dhT, con
     std::snprintf(label, sizeof label, "lstm_chain_bwd ms%d T%d B%d H%d", ms, nt, B, H);
     ProfScope prof(PROF_GRU_BWD, 2.0 * nt * B * 4.0 * H * H, s, label,
                    4.0 * (4.0 * H * H + (double)nt * B * H * (6 + 4 + 1)));
-    if (H == 256) return ms == 1 ? launch_chain(lstm_chain_bwd_kernel<1, 16>, a, groups, s)
-                       : ms == 2 ? launch_chain(lstm_chain_bwd_kernel<2, 16>, a, groups, s)
-                                 : launch_chain(lstm_chain_bwd_kernel<4, 16>, a, groups, s);
-    return ms == 1 ? launch_chain(lstm_chain_bwd_kernel<1, 32>, a, groups, s)
-           : ms == 2 ? launch_chain(lstm_chain_bwd_kernel<2, 32>, a, groups, s)
-                     : launch_chain(lstm_chain_bwd_kernel<4, 32>, a, groups, s);
+    return launch_lstm_chain_bwd(a, ms, groups, s);
 }
 
 // XCD the second chain of a two-layer pipeline starts its groups on (the first starts on XCD 0)
@@ -880,28 +876,8 @@ int lstm_seq_bwd(int B, int T, int H, const float* W_hh, const float* h0, const 
     const long BH = (long)B * H, TBH = (long)T * BH, B4H = 4 * BH;
     INET_TRY(pw_transpose(W_hh, H, w.whhT, 4L * H, 4 * H, H, s));
     const bool use_chain = lstm_chain_ok(B, H);
-    if (use_chain) {
-        const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
-        if (hipMemsetAsync(w.sync + kBwdCounters, 0, kBwdCounters * sizeof(unsigned), s) != hipSuccess) return -2;
-        LstmChainBwdArgs a{};
-        a.B = B; a.H = H; a.T = T; a.reverse = reverse; a.members = H / 16;
-        a.W_hhT = w.whhT; a.dout = dout; a.dhT = dhT; a.dcT = dcT;
-        a.sv = w.sv; a.sv_stride = TBH;
-        a.dg = dgi; a.dh0 = dh0; a.dc0 = dc0;
-        a.db_ih = db_ih; a.db_hh = db_hh;
-        a.gx = w.gx; a.counters = w.sync + kBwdCounters; a.status = chain_status_for(w.sync + kStatusWord);
-        char label[64];
-        std::snprintf(label, sizeof label, "lstm_chain_bwd ms%d T%d B%d H%d", ms, T, B, H);
-        ProfScope prof(PROF_GRU_BWD, 2.0 * T * B * 4.0 * H * H, s, label,
-                       4.0 * (4.0 * H * H + (double)T * B * H * (6 + 4 + 1)));
-        int rc;
-        if (H == 256) rc = ms == 1 ? launch_chain(lstm_chain_bwd_kernel<1, 16>, a, groups, s)
-                           : ms == 2 ? launch_chain(lstm_chain_bwd_kernel<2, 16>, a, groups, s)
-                                     : launch_chain(lstm_chain_bwd_kernel<4, 16>, a, groups, s);
-        else rc = ms == 1 ? launch_chain(lstm_chain_bwd_kernel<1, 32>, a, groups, s)
-                  : ms == 2 ? launch_chain(lstm_chain_bwd_kernel<2, 32>, a, groups, s)
-                            : launch_chain(lstm_chain_bwd_kernel<4, 32>, a, groups, s);
-        INET_TRY(rc);
+    if (use_chain) {                                           // the whole sequence as one chunk on the base counter area
+        INET_TRY(lstm_chunk_bwd(B, T, H, dout, dhT, dcT, reverse, dgi, db_ih, db_hh, dh0, dc0, w, 0, T, s));
     } else
     for (int step = T - 1; step >= 0; --step) {
         const int t = reverse ? T - 1 - step : step;
@@ -941,262 +917,4 @@ int lstm_seq_bwd(int B, int T, int H, const float* W_hh, const float* h0, const 
         if (h0) INET_TRY(linear_wgrad(dgi + (long)t0 * B4H, 4L * H, h0, H, dW_hh, H, B, 4 * H, H, ss));
     }
     return side_join(s);
-}
-
-// ---- AnticipationRNN's free-running pass, the part that is sequential (anticipation_rnn_gauss_reg_model.py:190-259) ---------------
-// The generation LSTMs feed back the argmax of BATCH ELEMENT 0 to the whole batch (:253-256) and nothing else of a tick's output:
-// the token sequence depends on batch element 0 alone.  This runs those L ticks for that one row -- per tick: input = [embedding of
-// the previous token | constraint output of the tick], two LSTM cells, linear_1 + ReLU, the note head, argmax -- as 4 small launches
-// per tick queued from here (no host round trip: the token stays on the device), and hands back the L tokens.  With them the
-// caller runs the whole batch through the batched (teacher-forced-shaped) kernels: 195 -> 14 ms per training step.
-namespace {
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// dot products of ONE row against weight rows, lanes striding over k: every load of a wave is issued before the first multiply (NI =
-// ceil(K / 64) is a template bound: a runtime k loop waits for each 64-wide slice in turn -- 7 us per launch instead of 2)
-template <int NI>
-__device__ __forceinline__ void load_x(float (&xv)[NI], const float* pa, int Ka, const float* pb, int K, int lane) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int k = lane + 64 * i;
-        xv[i] = k < Ka ? pa[k] : (k < K ? pb[k - Ka] : 0.f);
-    }
-}
-template <int NI>
-__device__ __forceinline__ float dot_row(const float* __restrict__ Wrow, const float (&xv)[NI], int K, int lane) {
-    float wv[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) { const int k = lane + 64 * i; wv[i] = k < K ? Wrow[k] : 0.f; }
-    float a = 0.f;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) a = fmaf(wv[i], xv[i], a);
-    return a;
-}
-
-// One LSTM cell for ONE row, both products in the launch: gates = W_ih [xa | xb] + b_ih + W_hh h_prev + b_hh.  One wave per hidden
-// unit (its four gate rows), four units per workgroup.  xa = the embedding row of *tok (tok null: token 0) when `emb` is given.
-template <int NI, int NH>
-__global__ __launch_bounds__(256) void lstm_cell_b1_kernel(const float* __restrict__ emb, const long long* __restrict__ tok,
-                                                           const float* __restrict__ xa, int Ka, const float* __restrict__ xb, int Kb,
-                                                           const float* __restrict__ W_ih, const float* __restrict__ b_ih,
-                                                           const float* __restrict__ h_prev, const float* __restrict__ c_prev,
-                                                           const float* __restrict__ W_hh, const float* __restrict__ b_hh,
-                                                           float* __restrict__ h_new, float* __restrict__ c_new, int H) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + w;
-    const int K = Ka + Kb;
-    const float* pa = emb ? emb + (tok ? *tok : 0) * Ka : xa;
-    float xv[NI], hv[NH];
-    load_x<NI>(xv, pa, Ka, xb, K, lane);
-    load_x<NH>(hv, h_prev, H, nullptr, H, lane);
-    float pre[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-        pre[g] = dot_row<NI>(W_ih + (long)(g * H + j) * K, xv, K, lane) + dot_row<NH>(W_hh + (long)(g * H + j) * H, hv, H, lane);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) pre[g] = wave_sum(pre[g]);
-    if (lane == 0) {
-        const float i = sigmoid_f(pre[0] + b_ih[j] + b_hh[j]);
-        const float f = sigmoid_f(pre[1] + b_ih[H + j] + b_hh[H + j]);
-        const float g = tanh_f(pre[2] + b_ih[2 * H + j] + b_hh[2 * H + j]);
-        const float o = sigmoid_f(pre[3] + b_ih[3 * H + j] + b_hh[3 * H + j]);
-        const float c = f * c_prev[j] + i * g;
-        c_new[j] = c;
-        h_new[j] = o * tanh_f(c);
-    }
-}
-
-// y[j] = ReLU(W[j,:] . x + b[j]) for ONE row: a wave per output
-template <int NI>
-__global__ __launch_bounds__(256) void relu_linear_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                             const float* __restrict__ b, float* __restrict__ y, int N, int K) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int j = blockIdx.x * 4 + w;
-    if (j >= N) return;
-    float xv[NI];
-    load_x<NI>(xv, x, K, nullptr, K, lane);
-    const float v = wave_sum(dot_row<NI>(W + (long)j * K, xv, K, lane));
-    if (lane == 0) y[j] = fmaxf(v + b[j], 0.f);
-}
-
-// does (b2, i2) come before (best, bi) in numpy's argmax order?  NaN > everything, ties to the lower index
-__device__ __forceinline__ bool argmax_better(float b2, int i2, float best, int bi) {
-    const bool n2 = b2 != b2, n1 = best != best;
-    if (n2 || n1) return n2 && (!n1 || i2 < bi);
-    return b2 > best || (b2 == best && i2 < bi);
-}
-
-// np.argmax order over lg[0 .. V) (anticipation_rnn_gauss_reg_model.py:253) by one wave: a NaN is the maximum, the lowest index wins
-// among equals -- an all-NaN or all -inf row yields a token INSIDE the vocabulary (the next tick gathers the embedding row by it)
-__device__ __forceinline__ int argmax_wave(const float* lg, int V, int lane) {
-    float best = lane < V ? lg[lane] : -INFINITY;
-    int bi = lane < V ? lane : 0x7fffffff;
-    for (int v = lane + 64; v < V; v += 64)
-        if (argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float b2 = __shfl_xor(best, o, 64);
-        const int i2 = __shfl_xor(bi, o, 64);
-        if (argmax_better(b2, i2, best, bi)) { best = b2; bi = i2; }
-    }
-    return bi;
-}
-
-// token = argmax_v (W[v,:] . x + b[v]), lowest index on ties, V <= 256: ONE workgroup of 16 waves; a wave's rows (V = 48: three) are all
-// requested before the first sum, the logits meet in LDS and the first wave takes the argmax with shuffles
-template <int NI>
-__global__ __launch_bounds__(1024) void head_argmax_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                              const float* __restrict__ b, long long* __restrict__ tok, int V, int K) {
-    __shared__ float lg[256];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float xv[NI];
-    load_x<NI>(xv, x, K, nullptr, K, lane);
-    float part[16];                                            // rows w, w + 16, ...: V <= 256
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        if (v < V) {                                           // (wave-uniform)
-            const float a = wave_sum(part[r]);
-            if (lane == 0) lg[v] = a + b[v];
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        const int bi = argmax_wave(lg, V, lane);
-        if (lane == 0) *tok = bi < V ? bi : 0;
-    }
-}
-
-// head_argmax_b1_kernel's products, then token = a draw from softmax(temp * logits) with the uniform *u (sample.h: numpy's
-// np.random.choice order, anticipation_rnn_gauss_reg_model.py:655-667); a NaN logit, a non-finite total or a uniform outside [0, 1)
-// keep the argmax rule.  V <= 256.
-template <int NI>
-__global__ __launch_bounds__(1024) void head_sample_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                              const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
-                                                              float temp, const double* __restrict__ u) {
-    __shared__ float lg[256];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float xv[NI];
-    load_x<NI>(xv, x, K, nullptr, K, lane);
-    float part[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        if (v < V) {
-            const float a = wave_sum(part[r]);
-            if (lane == 0) lg[v] = a + b[v];
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        float sv[4], ms = -INFINITY;
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int v = lane + 64 * j;
-            sv[j] = v < V ? lg[v] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-            ms = fmaxf(ms, sv[j]);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
-        int bi = __ballot(nan) ? -1 : sample::pick<4>(sv, ms, *u, V, lane);
-        if (bi < 0) bi = argmax_wave(lg, V, lane);
-        if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
-    }
-}
-}  // namespace
-
-size_t arnn_generate_ws_floats(int L, int E, int Hc, int H, int U, int V) {
-    const size_t ticks = (size_t)(E + Hc) + 4 * (size_t)H + 8 * (size_t)H + U + V + 64;
-    const size_t pass = arnn_token_pass_ok(H, U, V) ? arnn_token_pass_ws_floats(L, V) : 0;
-    return ticks > pass ? ticks : pass;
-}
-
-int arnn_generate(int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, long oc_stride, const float* W_ih0,
-                  const float* b_ih0, const float* W_hh0, const float* b_hh0, const float* W_ih1, const float* b_ih1,
-                  const float* W_hh1, const float* b_hh1, const float* W1, const float* b1, const float* W2, const float* b2,
-                  const float* hc_init, const long long* first_tok, long long* tokens, float* ws, hipStream_t s) {
-    // the reference's configuration: ONE persistent launch for all L ticks (arnn_gen.hip): 14.3 -> ~3.5 us per tick
-    if (arnn_token_pass_ok(H, U, V))
-        return arnn_token_pass(L, E, Hc, V, emb, oc0, oc_stride, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2,
-                               hc_init, first_tok, tokens, ws, s);
-    float* hc = ws;                                            // [layer][h|c][ping-pong][H]
-    float* u = hc + 8 * H;
-    if (pw_zero(hc, 8L * H, s) != 0) return -2;
-    auto H_ = [&](int l, int p) { return hc + ((l * 2 + 0) * 2 + p) * H; };
-    auto C_ = [&](int l, int p) { return hc + ((l * 2 + 1) * 2 + p) * H; };
-    if (hc_init)                                               // [layer][h | c][H]: the state the ticks go on from (inpainting: after the prefix)
-        for (int l = 0; l < 2; ++l)
-            if (pw_copy_bytes(H_(l, 0), hc_init + (2 * l) * H, H * sizeof(float), s) != 0 ||
-                pw_copy_bytes(C_(l, 0), hc_init + (2 * l + 1) * H, H * sizeof(float), s) != 0) return -2;
-    // per tick four launches (round 4's first form had eight: input build, two GEMVs + two cell kernels, two head GEMVs, argmax)
-    if (V > 256 || E + Hc > 320 || H > 256 || U > 256) return -1;      // (the template bounds of the one-row kernels)
-    for (int t = 0, p = 0; t < L; ++t, p ^= 1) {
-        hipLaunchKernelGGL((lstm_cell_b1_kernel<5, 4>), dim3(H / 4), dim3(256), 0, s, emb, t ? tokens + t - 1 : first_tok,
-                           (const float*)nullptr, E, oc0 + (long)t * oc_stride, Hc, W_ih0, b_ih0, (const float*)H_(0, p),
-                           (const float*)C_(0, p), W_hh0, b_hh0, H_(0, p ^ 1), C_(0, p ^ 1), H);
-        hipLaunchKernelGGL((lstm_cell_b1_kernel<4, 4>), dim3(H / 4), dim3(256), 0, s, (const float*)nullptr, (const long long*)nullptr,
-                           (const float*)H_(0, p ^ 1), H, (const float*)nullptr, 0, W_ih1, b_ih1, (const float*)H_(1, p),
-                           (const float*)C_(1, p), W_hh1, b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
-        hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), W1, b1, u, U, H);
-        hipLaunchKernelGGL((head_argmax_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, W2, b2, tokens + t, V, U);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-size_t arnn_sample_ws_floats(int R, int L, int E, int Hc, int H, int U, int V) {
-    const size_t ticks = (size_t)(E + Hc) + 4 * (size_t)H + 8 * (size_t)H + U + V + 64;
-    const size_t pass = arnn_token_pass_ok(H, U, V) ? arnn_token_sample_ws_floats(R, L, V) : 0;
-    return ticks > pass ? ticks : pass;
-}
-
-int arnn_sample(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, long oc_stride, long oc_bstride,
-                const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0, const float* W_ih1, const float* b_ih1,
-                const float* W_hh1, const float* b_hh1, const float* W1, const float* b1, const float* W2, const float* b2, float temp,
-                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s) {
-    // the reference's configuration: the persistent token pass with the sampling head, up to 8 rows per launch (arnn_gen.hip)
-    if (arnn_token_pass_ok(H, U, V))
-        return arnn_token_sample(R, L, E, Hc, V, emb, oc0, oc_stride, oc_bstride, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
-                                 W1, b1, W2, b2, temp, uniforms, hc_init, tokens, ws, s);
-    if (V > 256 || E + Hc > 320 || H > 256 || U > 256) return -1;      // (the template bounds of the one-row kernels)
-    float* hc = ws;                                            // [layer][h|c][ping-pong][H]
-    float* u = hc + 8 * H;
-    auto H_ = [&](int l, int p) { return hc + ((l * 2 + 0) * 2 + p) * H; };
-    auto C_ = [&](int l, int p) { return hc + ((l * 2 + 1) * 2 + p) * H; };
-    for (int r = 0; r < R; ++r) {                              // the rows one after the other, arnn_generate's four launches per tick
-        const float* oc = oc0 + (long)r * oc_bstride;
-        long long* tk = tokens + (long)r * L;
-        if (pw_zero(hc, 8L * H, s) != 0) return -2;
-        if (hc_init)
-            for (int l = 0; l < 2; ++l)
-                if (pw_copy_bytes(H_(l, 0), hc_init + ((long)r * 4 + 2 * l) * H, H * sizeof(float), s) != 0 ||
-                    pw_copy_bytes(C_(l, 0), hc_init + ((long)r * 4 + 2 * l + 1) * H, H * sizeof(float), s) != 0) return -2;
-        for (int t = 0, p = 0; t < L; ++t, p ^= 1) {
-            hipLaunchKernelGGL((lstm_cell_b1_kernel<5, 4>), dim3(H / 4), dim3(256), 0, s, emb, t ? tk + t - 1 : (const long long*)nullptr,
-                               (const float*)nullptr, E, oc + (long)t * oc_stride, Hc, W_ih0, b_ih0, (const float*)H_(0, p),
-                               (const float*)C_(0, p), W_hh0, b_hh0, H_(0, p ^ 1), C_(0, p ^ 1), H);
-            hipLaunchKernelGGL((lstm_cell_b1_kernel<4, 4>), dim3(H / 4), dim3(256), 0, s, (const float*)nullptr, (const long long*)nullptr,
-                               (const float*)H_(0, p ^ 1), H, (const float*)nullptr, 0, W_ih1, b_ih1, (const float*)H_(1, p),
-                               (const float*)C_(1, p), W_hh1, b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
-            hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), W1, b1, u, U, H);
-            hipLaunchKernelGGL((head_sample_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, W2, b2, tk + t, V, U, temp,
-                               uniforms + (long)r * L + t);
-        }
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -133,8 +133,8 @@ def side_join_on(stream):
 
 
 def arnn_generate_ok(E, Hc, H, U, V):
-    """The shapes the one-row kernels of inet_arnn_generate are built for (csrc/lstm.hip: template bounds); callers keep their
-    per-tick loop for anything else."""
+    """The shapes the one-row kernels of inet_arnn_generate are built for (csrc/arnn_gen.hip: arnn_ticks_ok, the template bounds;
+    keep the two equal); callers keep their per-tick loop for anything else."""
     return E + Hc <= 320 and H <= 256 and H % 16 == 0 and U <= 256 and V <= 256
 
 
@@ -145,14 +145,12 @@ def arnn_generate(emb, oc0, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_h
     L, Hc = oc0.shape
     assert oc0.stride(1) == 1
     E, H, U, V = emb.shape[1], W_hh0.shape[1], W1.shape[0], W2.shape[0]
-    for t in (emb, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2):
-        _f32c(t)
+    net = [ptr(_f32c(t)) for t in (W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2)]
     nws = int(_lib.lib().inet_arnn_generate_ws_floats(L, E, Hc, H, U, V))
     ws = torch.empty(nws, dtype=torch.float32, device=emb.device)
     tokens = torch.empty(L, dtype=torch.int64, device=emb.device)
-    check(_lib.lib().inet_arnn_generate(L, E, Hc, H, U, V, ptr(emb), ptr(oc0), oc0.stride(0), ptr(W_ih0), ptr(b_ih0), ptr(W_hh0),
-                                        ptr(b_hh0), ptr(W_ih1), ptr(b_ih1), ptr(W_hh1), ptr(b_hh1), ptr(W1), ptr(b1), ptr(W2),
-                                        ptr(b2), ptr(_f32c(hc_init) if hc_init is not None else None),
+    check(_lib.lib().inet_arnn_generate(L, E, Hc, H, U, V, ptr(_f32c(emb)), ptr(oc0), oc0.stride(0), *net,
+                                        ptr(_f32c(hc_init) if hc_init is not None else None),
                                         ptr(_i64c(first_tok) if first_tok is not None else None), ptr(tokens), ptr(ws), nws,
                                         stream_ptr()), "inet_arnn_generate")
     _hold(ws, oc0, hc_init, first_tok)
@@ -172,8 +170,7 @@ def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
     R, L, Hc = oc.shape
     assert oc.is_cuda and oc.dtype == torch.float32 and oc.stride(2) == 1
     E, H, U, V = emb.shape[1], W_hh0.shape[1], W1.shape[0], W2.shape[0]
-    for t in (emb, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2):
-        _f32c(t)
+    net = [ptr(_f32c(t)) for t in (W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2)]
     u = torch.as_tensor(uniforms, dtype=torch.float64).to(emb.device).contiguous()
     if tuple(u.shape) != (R, L):
         raise ValueError(f"arnn_sample: uniforms of shape {tuple(u.shape)}, expected {(R, L)}")
@@ -184,9 +181,8 @@ def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
         raise ValueError("inet_arnn_sample_ws_floats: invalid arguments")
     ws = torch.empty(nws, dtype=torch.float32, device=emb.device)
     tokens = torch.empty(R, L, dtype=torch.int64, device=emb.device)
-    check(_lib.lib().inet_arnn_sample(R, L, E, Hc, H, U, V, ptr(emb), ptr(oc), oc.stride(1), oc.stride(0), ptr(W_ih0), ptr(b_ih0),
-                                      ptr(W_hh0), ptr(b_hh0), ptr(W_ih1), ptr(b_ih1), ptr(W_hh1), ptr(b_hh1), ptr(W1), ptr(b1), ptr(W2),
-                                      ptr(b2), float(temperature), ptr(u),
+    check(_lib.lib().inet_arnn_sample(R, L, E, Hc, H, U, V, ptr(_f32c(emb)), ptr(oc), oc.stride(1), oc.stride(0), *net,
+                                      float(temperature), ptr(u),
                                       ptr(_f32c(hc_init) if hc_init is not None else None), ptr(tokens), ptr(ws), nws,
                                       stream_ptr()), "inet_arnn_sample")
     _hold(ws, oc, u, hc_init)

@@ -4,7 +4,7 @@ tests/golden/arnn_generate.npz holds calls of the reference's ConstraintModelGau
 (AnticipationRNN/anticipation_rnn_gauss_reg_model.py:570-679) under np.random.seed(seed): the L uniforms np.random.choice drew and
 the tokens.  A CPU restatement -- 23 warm-up ticks on the start symbol with oc[1..23], then L ticks with oc[t], token t = the first v
 whose prefix of softmax(temperature * logits) exceeds u_t -- reproduces every stored sequence: this pins the reading of the reference
-that the GPU kernels (csrc/arnn_gen.hip, csrc/lstm.hip, csrc/sample.h) implement."""
+that the GPU kernels (csrc/arnn_gen.hip, csrc/sample.h) implement."""
 import types
 
 import numpy as np

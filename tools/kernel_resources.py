@@ -2,7 +2,9 @@
 """Registers, spills, scratch and LDS of every kernel of a HIP source, from hipcc's own remarks (no GPU needed):
     python tools/kernel_resources.py inpaintnet_amd/csrc/decode_b1.hip [more.hip ...] [--ref <git rev>]
 --ref REV compiles the same files as of that revision next to the working tree and prints only the kernels whose numbers moved.
---ref REV --asm compares the gfx950 assembly of the two instead: a host-only change must leave it identical."""
+--ref REV --asm compares the gfx950 assembly of the two instead: a host-only change must leave it identical.  Per file the whole-file
+verdict, then per kernel (matched by symbol across ALL the files given, so a kernel may change files): identical | identical, moved
+a.hip -> b.hip | DIFFERS | only in REV | only in tree."""
 import os
 import re
 import subprocess
@@ -39,6 +41,49 @@ def device_asm(src, incdir):
     return [l for l in out.splitlines() if "__hip_cuid_" not in l]
 
 
+def functions(lines):
+    """{symbol: its lines from `.globl SYM` to `.Lfunc_endN:`} without the function's index in its file (block labels, func_begin / end)"""
+    out, sym = {}, None
+    for l in lines:
+        m = re.match(r"\s*\.globl\s+(\S+).*-- Begin function", l)
+        if m:
+            sym = m.group(1)
+            out[sym] = []
+        if sym is not None:
+            l = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", re.sub(r"BB\d+_", "BB_", l))
+            out[sym].append(re.sub(r"\s+", " ", l))            # (the comment column behind a label moves with the index's width)
+            if l.startswith(".Lfunc_end:"):
+                sym = None
+    return out
+
+
+def pretty(sym):
+    name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
+    return re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", "").replace("void ", ""))
+
+
+def compare_asm(srcs, ref):
+    with tempfile.TemporaryDirectory() as tmp:
+        subprocess.check_call(f"git -C {REPO} archive {ref} inpaintnet_amd/csrc include | tar -x -C {tmp}", shell=True)
+        old_dir = os.path.join(tmp, "inpaintnet_amd", "csrc")
+        old = {os.path.basename(src): device_asm(os.path.join(old_dir, os.path.basename(src)), old_dir) for src in srcs}
+    new = {os.path.basename(src): device_asm(src, CSRC) for src in srcs}
+    where = [{}, {}]                                            # symbol -> (file, lines), in REV and in the tree
+    for side, files in zip(where, (old, new)):
+        for f, lines in files.items():
+            side.update({sym: (f, body) for sym, body in functions(lines).items()})
+    for f in new:
+        o, n = old[f], new[f]
+        first = next((i + 1 for i, (a, b) in enumerate(zip(o, n)) if a != b), None if len(o) == len(n) else min(len(o), len(n)) + 1)
+        print(f"{f}: device code " + (f"identical to {ref} ({len(n)} lines)" if first is None else
+                                      f"DIFFERS from {ref} (first at line {first}; {len(o)} -> {len(n)} lines)"))
+        for sym in sorted(s for side in where for s, (g, _) in side.items() if g == f and (side is where[1] or s not in where[1])):
+            (fo, bo), (fn, bn) = where[0].get(sym, (None, None)), where[1].get(sym, (None, None))
+            verdict = ("only in tree" if fo is None else f"only in {ref}" if fn is None else "DIFFERS" if bo != bn else
+                       "identical" if fo == fn else f"identical, moved {fo} -> {fn}")
+            print(f"    {pretty(sym)}: {verdict}")
+
+
 def fmt(r):
     return " ".join(f"{k}={v}" for k, v in r.items())
 
@@ -55,17 +100,10 @@ def main():
         args.remove("--asm")
         if ref is None:
             sys.exit("--asm compares with a revision: give --ref REV")
+    if asm:
+        return compare_asm([os.path.abspath(src) for src in args], ref)
     for src in args:
         src = os.path.abspath(src)
-        if asm and ref is not None:
-            with tempfile.TemporaryDirectory() as tmp:
-                subprocess.check_call(f"git -C {REPO} archive {ref} inpaintnet_amd/csrc include | tar -x -C {tmp}", shell=True)
-                old = device_asm(os.path.join(tmp, "inpaintnet_amd", "csrc", os.path.basename(src)), os.path.join(tmp, "inpaintnet_amd", "csrc"))
-            new = device_asm(src, CSRC)
-            first = next((i + 1 for i, (a, b) in enumerate(zip(old, new)) if a != b), None if len(old) == len(new) else min(len(old), len(new)) + 1)
-            print(f"{os.path.basename(src)}: device code " + (f"identical to {ref} ({len(new)} lines)" if first is None else
-                                                              f"DIFFERS from {ref} (first at line {first}; {len(old)} -> {len(new)} lines)"))
-            continue
         new = resources(src, CSRC)
         if ref is None:
             for k, v in new.items():
