@@ -95,6 +95,20 @@ int inet_vae_decoder_fwd(const inet_vae_config* cfg, int batch, const float* z, 
                          int teacher_forced, const float* params, const float* mask_beat, const float* mask_tick,
                          float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
                          uint64_t multinomial_seed, void* stream);
+/* The free-running decode with TEMPERATURE SAMPLING: inet_vae_decoder_fwd's arguments without target, teacher_forced and
+ * multinomial_seed, plus the temperature and one uniform per (row, tick), uniforms [B,T] doubles on the device (row-major).  For
+ * tick t of row b, with x = weights[b,t,:] (the post-ReLU logits, unchanged): s = temperature * x in f32, e_v = expf(s_v - max s),
+ * inclusive prefix in f64; samples[b,0,t] = the first v with prefix_v > uniforms[b,t] * total (np.random.choice's order, the rule of
+ * inet_arnn_sample) -- the token that is fed back into tick t + 1.  Where the rule does not apply (max s or the total not finite, a
+ * NaN among s, a uniform outside [0, 1) or NaN) the tick takes the argmax, lowest index among equals.  Tokens always lie in [0, V).
+ * One to sixteen rows with H = 512, V <= 128, no tick mask and save = 0 run as ONE register-resident launch (csrc/decode_b1.hip, its
+ * sampling build; inet_decode_b1_plan_sample); every other shape runs tick by tick with inet_sample_temperature's kernel behind each
+ * output projection.  A sampled call never runs a kernel that ignores its uniforms: the launch labels of the profile start with
+ * "sample_" (sample_decode_b1..., sample_temperature ...).  -1: a null pointer, a non-finite temperature, V > 512, a workspace
+ * smaller than inet_vae_decoder_ws_bytes(cfg, batch, save). */
+int inet_vae_decoder_sample(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
+                            const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
+                            float temperature, const double* uniforms, void* stream);
 /* dweights [B,T,V] = dLoss/dweights; weights = the forward output; grads may be null (frozen decoder:
  * LatentRNN/latent_rnn.py:42-43) in which case only dz [B,Z] is produced.  `tokens_in` are the tokens that
  * were fed back (= samples of the forward call). */
@@ -139,6 +153,13 @@ int inet_latent_bwd(const float* dz, const float* mu, const float* logsigma, con
  * u * total (u close to 1), it is the last token with mass, never a trailing token without any. */
 int inet_sample_multinomial(const float* weights, int64_t ld_w, int rows, int V, int64_t* out, int64_t stride,
                             uint64_t seed, uint64_t offset, void* stream);
+
+/* The sampling rule of inet_vae_decoder_sample on rows of V logits (row stride ld_w), one wavefront per row: out[row*stride] = the
+ * first v whose prefix of expf(temperature * w_v - max) (f64 prefix) exceeds uniforms[row*u_stride] * total; inet_argmax's rule for a
+ * row where that does not apply (a NaN among temperature * w, a maximum or total that is not finite, a uniform outside [0, 1) or
+ * NaN).  The result always lies in [0, V).  -1: a null pointer, rows <= 0, V <= 0, V > 512, a non-finite temperature. */
+int inet_sample_temperature(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
+                            int64_t u_stride, int64_t* out, int64_t stride, void* stream);
 
 /* ---- optimizer: torch.optim.Adam as built at utils/trainer.py:32-35, stepped at :172-177 -------- */
 /* p,g,m,v: arenas of n floats; step is 1-based; grads are multiplied by gscale first (1/world_size for DP) */
@@ -420,6 +441,9 @@ int inet_slow_waits(unsigned* dst, int max_entries, int reset, int64_t* noted);
  * critical roles sit on ONE residue, no residue carries more than 32 live workgroups, grid and live workgroups fit the chip.  0, or -1
  * for a call the register-resident launch does not take (B > 16, V > 128, no plan fits the chip's INET_CHAIN_CUS / CU count, ...). */
 int inet_decode_b1_plan(int B, int V, int Z, int* out8);
+/* The same for a temperature-sampled call (inet_vae_decoder_sample): the same planner with its `sample` input set, the same
+ * self-check.  -1 also under inet_set_option key 15 != 4: the sampling build exists for the default mode's plans. */
+int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8);
 /* Loads every kernel of the library on the CURRENT device (code objects and function objects, which the HIP runtime otherwise
  * builds lazily on the launch path of each kernel's first launch: csrc/preload.hip) without launching anything.  Idempotent per
  * device; returns the number of kernels touched (0 when the device was done already), -2 without a device or on a runtime

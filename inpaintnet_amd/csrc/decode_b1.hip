@@ -61,6 +61,7 @@
 #define INET_GRANULE_KID chain::K_DECODE_B1
 #include "granule.h"
 #include "prof.h"
+#include "sample.h"
 #include "decode_chain.h"
 
 namespace {
@@ -152,6 +153,7 @@ struct B1Args {
     unsigned long long* stamps;                  // diagnostics: [C, TBi_0][T][8] wall-clock ticks (10 ns), or null
     DecodeB1Beat bp;                             // the beat path's operands (fused)
     chain::Status status;
+    const double* uniforms; float temperature;   // the sampling build: one uniform per (row, tick) [B, T], the logits' factor
 };
 
 #define B1_STAMP(who, t, i) do { if (stamps && tid == 0) stamps[((who) * 32 + (t)) * 8 + (i)] = wall_clock64(); } while (0)
@@ -484,13 +486,40 @@ __device__ __forceinline__ void beat_path_role(const Ctx<NR>& c, int role, int n
     }
 }
 
+// TEMPERATURE SAMPLING (SAMPLE = true; sample.h has the rule): where the argmax wave of a row holds the row's post-ReLU logits
+// lg[j] of v = lane + 64 j, the token is the first v whose prefix of exp(T lg - max) exceeds u[row, tick] times the total.  Where the
+// rule does not apply (-1: a NaN among T lg -- an infinite logit times T = 0 --, a non-finite maximum or total, u outside [0, 1)) the
+// tick keeps the argmax rule.  The drawn token is the one fed back and stored.  The uniform of (row, tick) is requested at the start
+// of the tick through a wave-uniform address; rows beyond B read row B - 1's uniforms, as they repeat its logits.
+template <int NVL>
+__device__ __forceinline__ int sample_token(const float (&lg)[NVL], float temp, double u, int V, int lane) {
+    float sv[NVL], ms = -INFINITY;
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < NVL; ++j) {
+        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
+        nan |= sv[j] != sv[j];
+        ms = fmaxf(ms, sv[j]);
+    }
+    if (__ballot(nan)) return -1;
+    return sample::pick<NVL>(sv, wave_max_dpp(ms), u, V, lane);
+}
+constexpr int kSharedRows = 6;                   // rows a shared recurrent group serves beyond ten measures (8: the group's tick is longer than the two-row teams' and sets the pace)
+constexpr int kSharedRowsSmall = 3;              // ... and for four to six measures, where the critical teams have ONE row
+// The merged build's shapes (rows x ceil(V / 32) <= 2: what fits 256 registers without spills).  The kernel, the planner and its
+// self-check all ask here.  The SAMPLING build of two-row teams beside groups of six rows (V <= 32, eleven to sixteen measures) does
+// not fit: 256 VGPRs and two spilled (the argmax build: 253) -- it is not built, such a call runs workgroup C.
+__host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, bool sample) {
+    return nb * nj <= 2 && !(sample && nb == 2 && nbr == kSharedRows);
+}
+
 // Shared recurrent groups (round 6, NBR > NB): seven to sixteen measures used to run as teams of FOUR rows (49 workgroups each: four
 // two-row teams are all the chip holds) at 8-9 us per tick against 4.7 for a two-row team.  But only 17 of a team's 49 workgroups
 // are on the tick's critical path (C and the 16 TBi); TA and TBh produce the NEXT tick's recurrent summands and idle most of a
 // tick.  So they are shared: two-row critical teams (17 workgroups each, on one XCD) for every pair of rows, and recurrent groups
 // of 32 workgroups that serve NBR = 6 rows -- three teams -- each: 8 x 17 + 3 x 32 = 232 workgroups for sixteen measures, every
 // row on a two-row tick.  A group's rows without a team (the last group of a call) are skipped (Ctx.nact).
-template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB>
+template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB, bool SAMPLE = false>
 __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     constexpr int XROWS = NB > NBB ? (NB > NBR ? NB : NBR) : (NBB > NBR ? NBB : NBR);
     __shared__ __attribute__((aligned(16))) float xs[XROWS][2][XS];
@@ -517,12 +546,16 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     const int nb = a.T / a.G;
     const DecodeB1Beat& bp = a.bp;
     // MG, the merged build: workgroup C does not exist, every TBi_k does C's work for itself next to its own (CB below)
-    constexpr bool MG = NB * NJ <= 2;
+    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE);
 
     if (role == R_C) {
         if (MG) return;
         // ---- C: layer 0's cell (its three summands are made elsewhere and arrive), the output projection, argmax ----
         const bool near = a.place && same_xcd(ex + G_XCC, 0, kCrit, a.status, &near_s);
+        // the sampling build: where this wave's uniforms start -- wave r picks the token of row r (one row: every wave picks it), a row
+        // beyond B reads row B - 1's (this role's team has a row: 0 <= rb + min(r, nrow - 1) < B); the other waves read none
+        const bool picks = NB == 1 || wave < NB;
+        const long urow_at = (long)(rb + min(NB == 1 ? 0 : __builtin_amdgcn_readfirstlane(wave), nrow - 1)) * a.T;
         const int rv = tid >> 4, s = tid & 15;
         int row[NJ];
 #pragma unroll
@@ -546,6 +579,8 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         if (!get_2d<NB, 3>(ex + G_GH0 + u, G_END, DH, 1u, a.status, gh, hw)) *bad = 1;
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
+            double ut = 0.0;                                   // the sampling build: this tick's uniform, requested here and read behind the head
+            if constexpr (SAMPLE) { if (picks) ut = a.uniforms[urow_at + t]; }
             if (t % a.G == 0) {
                 const long beat = t / a.G;
                 if (FUSED) {
@@ -621,10 +656,14 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 }
                 m = wave_max_dpp(m);
                 int bi = 0;
+                if constexpr (SAMPLE) bi = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
+                if (!SAMPLE || bi < 0) {
+                    if (SAMPLE) bi = 0;
 #pragma unroll
-                for (int j = NVL - 1; j >= 0; --j) {
-                    const unsigned long long eq = __ballot(lg[j] == m);
-                    if (eq) bi = 64 * j + __builtin_ctzll(eq);
+                    for (int j = NVL - 1; j >= 0; --j) {
+                        const unsigned long long eq = __ballot(lg[j] == m);
+                        if (eq) bi = 64 * j + __builtin_ctzll(eq);
+                    }
                 }
                 bi = bi < a.V ? bi : 0;
                 if (NB == 1) {
@@ -664,7 +703,9 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         // ---- CB_k (merged build): C's work REPLICATED in every TBi_k.  Layer 0's cell needs no product (its summands arrive), the
         // head is V x 512: cheap enough to compute 16 times over, and then h0_t never leaves the workgroup and the token never
         // travels -- of the two hand-offs of a tick (C -> TBi -> C) only the all-gather of h1_t among the 16 workgroups is left.
-        // All of them run the same instructions on the same values, so they agree on every token bit for bit.  CB_0 alone
+        // All of them run the same instructions on the same values, so they agree on every token bit for bit -- the sampling build too:
+        // sample::pick is a pure function of the row's logits `lgs`, which every copy computes from the same gathered h1_t with the same
+        // instructions, and of the uniform u[row, t], which every copy reads from the same address; nothing else may enter a token.  CB_0 alone
         // publishes h0_t (for TA) and writes the outputs.  h0, h1 and gh0 alternate between two granule slots by tag parity: a CB
         // workgroup does not wait for its 15 peers to have READ a value before it writes the next one (a peer's read of h1_t is
         // ordered before its own h1_t+1, which the writer of h1_t+2 has to have seen: two slots are enough; likewise gh0, h0).
@@ -672,6 +713,10 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         const bool with_ta = a.place == 1 && a.crit == kCritTA;           // the 16 TA are part of the check (and of the XCD)
         const bool near = a.place && same_xcd(ex + G_XCC, k, with_ta ? 2 * NU : NU, a.status, &near_s);
         const bool gh0_near = near && with_ta;
+        // the sampling build: where this wave's uniforms start -- wave r picks the token of row r (one row: every wave picks it), a row
+        // beyond B reads row B - 1's (this role's team has a row: 0 <= rb + min(r, nrow - 1) < B); the other waves read none
+        const bool picks = NB == 1 || wave < NB;
+        const long urow_at = (long)(rb + min(NB == 1 ? 0 : __builtin_amdgcn_readfirstlane(wave), nrow - 1)) * a.T;
         const int row[3] = {uc, DH + uc, 2 * DH + uc};
         float w[3][32];
         load_rows<3, 32>(w, a.W_ih1, DH, row, s);
@@ -704,6 +749,8 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
             const unsigned tag = (unsigned)t + 1u;
+            double ut = 0.0;                                   // the sampling build: this tick's uniform, requested here and read behind the head
+            if constexpr (SAMPLE) { if (picks) ut = a.uniforms[urow_at + t]; }
             const int g_h1 = slot_h1(tag);
             float gh1[NB][3];
             unsigned long long hw1[NB][3];
@@ -810,10 +857,14 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 }
                 m = wave_max_dpp(m);
                 int best = 0;
+                if constexpr (SAMPLE) best = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
+                if (!SAMPLE || best < 0) {
+                    if (SAMPLE) best = 0;
 #pragma unroll
-                for (int j = NVL - 1; j >= 0; --j) {
-                    const unsigned long long eq = __ballot(lg[j] == m);
-                    if (eq) best = 64 * j + __builtin_ctzll(eq);
+                    for (int j = NVL - 1; j >= 0; --j) {
+                        const unsigned long long eq = __ballot(lg[j] == m);
+                        if (eq) best = 64 * j + __builtin_ctzll(eq);
+                    }
                 }
                 best = best < a.V ? best : 0;
                 if (NB == 1) {
@@ -951,8 +1002,8 @@ int placed_grid(int teams, int rteams, int beat_wgs, int crit = kCrit) {
 // residue (never C's idle slot); four measures whose TBh pairs do not fit take the groups of three rows; a plan whose placed grid does
 // not fit runs on consecutive ids -- except shared groups, which exist only placed.  A call with no plan that fits takes the beat path's
 // own launches (folded beat path) or decode_chain.hip's exchange kernel.
-constexpr int kSharedRows = 6;                   // rows a shared recurrent group serves beyond ten measures (8: the group's tick is longer than the two-row teams' and sets the pace)
-constexpr int kSharedRowsSmall = 3;              // ... and for four to six measures, where the critical teams have ONE row
+// A SAMPLED call (temperature + uniforms) gets the same plans from the same planner under mode 4, with merged_build() deciding which
+// shapes have a merged sampling build; under the other modes it has no plan here, and vae_decoder_fwd samples tick by tick.
 
 // What launch_decode_b1 launches for a call, as a value (also behind inet_decode_b1_plan: the planner is tested without a GPU).  The
 // plan names its instantiation decode_b1_kernel<nj, fused, nb, nbb, nbr> itself (dispatch_b1).
@@ -965,6 +1016,7 @@ struct B1Plan {
     int crit;                                    // critical workgroups per team under place_role: kCritTA, NU (merged build) or kCrit
     int place, stride, grid, live, beat_wgs;
     int rows;                                    // granule rows the launch addresses
+    int sample;                                  // the sampling build
     bool ok;                                     // the plan fits the chip
 };
 // a candidate plan's rows: teams of nb rows, the folded beat path's nbb, shared groups (ta_crit: the TA stay critical beside the
@@ -972,8 +1024,9 @@ struct B1Plan {
 struct B1Shape { int nb, nbb, rgroups, nbr; bool ta_crit; };
 
 // the plans a call may get, best first: make_plan takes the first that fits the chip
-static int candidates(int B, int nj, bool fused, B1Shape (&c)[2]) {
+static int candidates(int B, int nj, bool fused, bool sample, B1Shape (&c)[2]) {
     int n = 0;
+    if (sample && mode() != 4) return 0;         // (the sampling build is instantiated for the default mode's plans)
     const auto team = [&](int nb, int nbb) { c[n++] = B1Shape{nb, fused ? nbb : nb, 0, nb, false}; };
     if (mode() == 4) {
         if (fused) {
@@ -987,7 +1040,7 @@ static int candidates(int B, int nj, bool fused, B1Shape (&c)[2]) {
                 // 246).  FOUR with the merged build: every team keeps its 16 TA next to its 16 CB on an XCD of its own (layer 0's
                 // recurrent summands stay inside the XCD), only the TBh are shared, two rows per group: 4 x 32 + 2 x 16 + 80 = 240.
                 // (Five and six would need 288 / 336: they keep the groups of three rows for both recurrent sides.)
-                if (B == 4 && nj <= 2) c[n++] = B1Shape{1, kDecodeB1BeatRowsMax, 2, 2, true};
+                if (B == 4 && merged_build(1, nj, 2, sample)) c[n++] = B1Shape{1, kDecodeB1BeatRowsMax, 2, 2, true};
                 c[n++] = B1Shape{1, kDecodeB1BeatRowsMax, (B + kSharedRowsSmall - 1) / kSharedRowsSmall, kSharedRowsSmall, false};
             }
         } else if (B <= kDecodeB1OneRowTeamsMax) {
@@ -1010,9 +1063,9 @@ static int candidates(int B, int nj, bool fused, B1Shape (&c)[2]) {
     return n;
 }
 
-static B1Plan plan_of(int B, int nj, bool fused, const B1Shape& sh) {
+static B1Plan plan_of(int B, int nj, bool fused, bool sample, const B1Shape& sh) {
     B1Plan p{};
-    p.fused = fused; p.nj = nj; p.nb = sh.nb; p.nbb = sh.nbb; p.rgroups = sh.rgroups; p.nbr = sh.nbr;
+    p.fused = fused; p.nj = nj; p.sample = sample; p.nb = sh.nb; p.nbb = sh.nbb; p.rgroups = sh.rgroups; p.nbr = sh.nbr;
     p.teams = (B + sh.nb - 1) / sh.nb;
     p.beat_wgs = fused ? kFusedRoles - kTickRoles : 0;
     p.rows = std::max(p.teams * p.nb, p.nbb);    // (a shared group's rows without a team are never touched: Ctx.nact)
@@ -1020,14 +1073,14 @@ static B1Plan plan_of(int B, int nj, bool fused, const B1Shape& sh) {
     return p;
 }
 
-static B1Plan make_plan(int B, int V, bool fused) {
+static B1Plan make_plan(int B, int V, bool fused, bool sample) {
     const int nj = (V + 31) / 32, cap = chain_capacity();
     B1Shape c[2];
-    const int n = (fused && mode() < 3) ? 0 : candidates(B, nj, fused, c);
+    const int n = (fused && mode() < 3) ? 0 : candidates(B, nj, fused, sample, c);
     B1Plan p{};
     for (int i = 0; i < n; ++i) {
-        p = plan_of(B, nj, fused, c[i]);
-        const bool merged = p.nb * nj <= 2;
+        p = plan_of(B, nj, fused, sample, c[i]);
+        const bool merged = merged_build(p.nb, nj, p.nbr, sample);
         const int rteams = p.rgroups ? p.rgroups : p.teams;
         const auto grid_of = [&](int crit) { return p.teams <= 8 ? placed_grid(p.teams, rteams, p.beat_wgs, crit) : cap + 1; };
         // critical workgroups per team: the merged build's TA join its 16 CB where the 32 fit (one XCD per team), else the 16 CB alone
@@ -1049,32 +1102,33 @@ static B1Plan make_plan(int B, int V, bool fused) {
 }
 
 // The instantiation a plan names: launched, or only looked up (a == null: decode_b1_plan_check).  False where there is none.
-template <int NJ>
+template <int NJ, bool S>
 static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 #define B1_INST(F, NB, NBB, NBR)                                                                                             \
     if (p.fused == (F) && p.nb == (NB) && p.nbb == (NBB) && p.nbr == (NBR)) {                                               \
-        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR>), dim3(p.grid), dim3(NT), 0, s, *a);                \
+        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR, S>), dim3(p.grid), dim3(NT), 0, s, *a);             \
         return true;                                                                                                        \
     }
+    // (S, the sampling build: the default mode's plans only -- candidates())
     B1_INST(true, 1, 1, 1)                       // one team, one row, beat path folded in
-    B1_INST(true, 2, 2, 2)                       // ... two rows (modes 3, 5)
+    if constexpr (!S) { B1_INST(true, 2, 2, 2) } // ... two rows (modes 3, 5)
     B1_INST(true, 1, kDecodeB1OneRowTeamsMax, 1) // two / three one-row teams
-    B1_INST(true, 2, kDecodeB1BeatRowsMax, 2)    // two / three two-row teams (modes 3, 5)
+    if constexpr (!S) { B1_INST(true, 2, kDecodeB1BeatRowsMax, 2) }   // two / three two-row teams (modes 3, 5)
     B1_INST(true, 1, kDecodeB1BeatRowsMax, kSharedRowsSmall)   // one-row critical teams + groups of three rows
-    if constexpr (NJ <= 2) { B1_INST(true, 1, kDecodeB1BeatRowsMax, 2) }   // four merged one-row teams + TBh pairs
+    if constexpr (merged_build(1, NJ, 2, S)) { B1_INST(true, 1, kDecodeB1BeatRowsMax, 2) }   // four merged one-row teams + TBh pairs
     B1_INST(false, 1, 1, 1)                      // teams of one, two or four rows behind the beat path's launches
     B1_INST(false, 2, 2, 2)
-    B1_INST(false, 4, 4, 4)
+    if constexpr (!S) { B1_INST(false, 4, 4, 4) }
     B1_INST(false, 2, 2, kSharedRows)            // two-row critical teams + groups of six rows
 #undef B1_INST
     return false;
 }
 static bool dispatch_b1(const B1Plan& p, const B1Args* a, hipStream_t s) {
     switch (p.nj) {
-        case 1: return dispatch_b1_nj<1>(p, a, s);
-        case 2: return dispatch_b1_nj<2>(p, a, s);
-        case 3: return dispatch_b1_nj<3>(p, a, s);
-        case 4: return dispatch_b1_nj<4>(p, a, s);
+        case 1: return p.sample ? dispatch_b1_nj<1, true>(p, a, s) : dispatch_b1_nj<1, false>(p, a, s);
+        case 2: return p.sample ? dispatch_b1_nj<2, true>(p, a, s) : dispatch_b1_nj<2, false>(p, a, s);
+        case 3: return p.sample ? dispatch_b1_nj<3, true>(p, a, s) : dispatch_b1_nj<3, false>(p, a, s);
+        case 4: return p.sample ? dispatch_b1_nj<4, true>(p, a, s) : dispatch_b1_nj<4, false>(p, a, s);
         default: return false;
     }
 }
@@ -1084,22 +1138,23 @@ int decode_b1_rows(int B) {
     for (int f = 0; f < 2; ++f)
         for (int nj = 1; nj <= 4; ++nj) {
             B1Shape c[2];
-            const int n = candidates(B, nj, f != 0, c);
-            for (int i = 0; i < n; ++i) rows = std::max(rows, plan_of(B, nj, f != 0, c[i]).rows);
+            const int n = candidates(B, nj, f != 0, false, c);     // (a sampled call's candidates are among these)
+            for (int i = 0; i < n; ++i) rows = std::max(rows, plan_of(B, nj, f != 0, false, c[i]).rows);
         }
     return rows;
 }
 
 void decode_b1_set_mode(int m) { g_mode = (m < 0 || m > 5) ? 4 : m; }
 
-bool decode_b1_shape_ok(int B, int H, int V, int T, int G) {
+bool decode_b1_shape_ok(int B, int H, int V, int T, int G, bool sample) {
     return mode() != 0 && chain_enabled() && B >= 1 && B <= kDecodeB1MaxRows && H == DH && V >= 1 && V <= 128 && T % G == 0 && T / G <= 4 &&
-           kFusedRoles <= chain_capacity() && make_plan(B, V, false).ok;
+           kFusedRoles <= chain_capacity() && make_plan(B, V, false, sample).ok;
 }
-bool decode_b1_fused(int Z, int B, int V) { return Z == DZ && make_plan(B, V, true).ok; }
+bool decode_b1_fused(int Z, int B, int V, bool sample) { return Z == DZ && make_plan(B, V, true, sample).ok; }
 bool decode_b1_ok(const DecodeChainArgs& a) {
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;
-    return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr).ok;
+    const bool sample = a.uniforms != nullptr;
+    return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G, sample) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr, sample).ok;
 }
 
 // Planner self-check without a GPU (tests/test_decode_plan.py): out[8] = {teams, rows per team, shared groups, critical workgroups per
@@ -1109,14 +1164,14 @@ bool decode_b1_ok(const DecodeChainArgs& a) {
 // has groups, and then the launch is placed; where placed: every (team, role) the kernel expects appears exactly once among the ids of
 // the grid, C's role exactly where the build is not merged, every team's critical roles on ONE residue mod 8, no residue with more than
 // 32 live workgroups (one XCD's CUs).  Returns 0, or -1 for a call the register-resident launch does not take.
-int decode_b1_plan_check(int B, int V, int Z, int* out) {
-    if (!out || !decode_b1_shape_ok(B, DH, V, 24, 6)) return -1;
-    const bool fused = decode_b1_fused(Z, B, V);
-    const B1Plan p = make_plan(B, V, fused);
+int decode_b1_plan_check(int B, int V, int Z, int* out, bool sample) {
+    if (!out || !decode_b1_shape_ok(B, DH, V, 24, 6, sample)) return -1;
+    const bool fused = decode_b1_fused(Z, B, V, sample);
+    const B1Plan p = make_plan(B, V, fused, sample);
     const int cap = chain_capacity();
-    const bool merged = p.nb * p.nj <= 2;                             // the kernel's MG
+    const bool merged = merged_build(p.nb, p.nj, p.nbr, sample);            // the kernel's MG
     const int team_rows = p.teams * p.nb, group_rows = p.rgroups ? std::min(p.rgroups * p.nbr, team_rows) : 0;
-    bool ok = p.ok && p.fused == (int)fused && dispatch_b1(p, nullptr, nullptr);
+    bool ok = p.ok && p.fused == (int)fused && p.sample == (int)sample && dispatch_b1(p, nullptr, nullptr);
     ok = ok && team_rows >= B && team_rows - p.nb < B;               // every row in a team, no team without a row
     ok = ok && std::max(team_rows, std::max(group_rows, p.fused ? p.nbb : 0)) <= decode_b1_rows(B);
     ok = ok && (!p.fused || p.nbb >= team_rows);
@@ -1160,7 +1215,7 @@ int decode_b1_plan_check(int B, int V, int Z, int* out) {
 }
 
 int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
-    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr);
+    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms != nullptr);
     if (!pl.ok || pl.rows > decode_b1_rows(d.B)) return -1;   // (decode_b1_ok has accepted the call: not reached)
     B1Args a{};
     a.fused = pl.fused; a.teams = pl.teams; a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place; a.stride = pl.stride;
@@ -1172,9 +1227,11 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     a.bp = d.beat;
     a.stamps = d.b1stamps;
     a.status = d.status;
+    a.uniforms = d.uniforms; a.temperature = d.temperature;
     if (!dispatch_b1(pl, nullptr, nullptr)) return -1;        // (a plan without an instantiation launches nothing)
     char label[64];
-    std::snprintf(label, sizeof label, "decode_b1%s T%d B%d H%d V%d", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
+    // (a sampled call's launch has a label prefix of its own: the profile tells the two kinds of call apart)
+    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
     // algorithmic work: the tick GRU + head per tick and row; fused: + the beat path (z2b, two beat layers, three projections per beat)
     const double nbt = (double)d.T / d.G;
     const double beat_mac = a.fused ? 2.0 * DH * DZ + nbt * (3.0 * 3 * DH * DH + 2.0 * DH * DH + 1.0 * DH * DH + 3.0 * DH * DH) : 0.0;

@@ -45,6 +45,9 @@ struct DecodeChainArgs {
     float* sv0; float* sv1; long sv_stride;       // saves r,z,n,W_hn h + b_hn,h_prev of layer 0 / 1: [5][T,B,H], stride
     float* h0out;                                 // [T,B,H] layer-0 output as layer 1 saw it (masked if mask)
     float* h1seq;                                 // [T,B,H] layer-1 output (input of the output projection's gradients)
+    // temperature sampling (decode_b1.hip's sampling build only: launch_decode_chain refuses a sampled call it cannot hand there)
+    const double* uniforms;                       // [B,T] one uniform per (row, tick), or null: the argmax rule
+    float temperature;                            // the logits' factor in front of the softmax
 };
 
 bool decode_chain_ok(int B, int H, int V, int T, int G);
@@ -64,10 +67,11 @@ constexpr int kDecodeB1OneRowTeamsMax = 3;        // ... with ONE-row teams (two
 // (the workspace is carved before the call knows whether its beat path is folded in; rows beyond B repeat row B - 1)
 int decode_b1_rows(int B);
 inline long decode_b1_words(int B) { return (long)decode_b1_rows(B) * kDecodeB1WordsPerRow; }
-bool decode_b1_shape_ok(int B, int H, int V, int T, int G);   // a launchable plan with the beat path's own launches in front
-bool decode_b1_fused(int Z, int B, int V);                    // ... and one with the beat path folded into the same launch
+// (sample: the plan of a temperature-sampled call -- the same planner decides, and may decide otherwise)
+bool decode_b1_shape_ok(int B, int H, int V, int T, int G, bool sample = false);   // a launchable plan with the beat path's own launches in front
+bool decode_b1_fused(int Z, int B, int V, bool sample = false);                    // ... and one with the beat path folded into the same launch
 bool decode_b1_ok(const DecodeChainArgs& a);                  // the plan of this call (beat.z != null: folded) is launchable
 int launch_decode_b1(const DecodeChainArgs& a, hipStream_t s);
 void decode_b1_set_mode(int m);
 // the launch plan of a call of B measures (V notes, latent size Z) and a host-side self-check of it: decode_b1.hip, no GPU needed
-int decode_b1_plan_check(int B, int V, int Z, int* out8);
+int decode_b1_plan_check(int B, int V, int Z, int* out8, bool sample = false);

@@ -20,6 +20,10 @@ int pw_latent_bwd(const float* dz, const float* mu, const float* ls, const float
                   float* dmu, float* dls, long n, hipStream_t s);
 int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long* out, long stride, uint64_t seed,
                           uint64_t offset, hipStream_t s);
+// out[row*stride] = sample.h's token for softmax(temp * W[row,:]) and the uniform uniforms[row*u_stride]; argmax_first where the rule
+// does not apply.  V <= 512, else -1.
+int pw_sample_temperature(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride,
+                          long long* out, long stride, hipStream_t s);
 // step_flag (optional device float): non-zero = skip (the ranks' summed chain status); report (optional, 4 host-mapped words
 // zeroed by the caller): [0] = 1 executed, [1] = 1 skipped, [2] = 1 a parameter became non-finite
 int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,

@@ -5,10 +5,12 @@
 // atomics), transposes, dropout-mask generation.  All are grid-stride,
 // coalesced along the contiguous dimension, 64-lane wave reductions via DPP
 // shuffles.
+#include <cstdio>
 #include "common.h"
 #include "pointwise.h"
 #include "prof.h"
 #include "chain.h"
+#include "sample.h"
 
 namespace {
 
@@ -649,6 +651,42 @@ __global__ void sample_multinomial_kernel(const float* __restrict__ W, long ld_w
     }
 }
 
+// samples[row*stride] = the token sample.h's rule draws from softmax(temp * W[row,:]) with the uniform uniforms[row*u_stride] (the
+// decoder's temperature sampling outside decode_b1.hip's launch; the same rule): one wavefront per row, V <= 64 NV.  Where the rule
+// does not apply (a NaN among temp * W, a non-finite maximum or total, a uniform outside [0, 1)) the row takes argmax_first.
+template <int NV>
+__global__ void sample_temperature_kernel(const float* __restrict__ W, long ld_w, int rows, int V, float temp,
+                                          const double* __restrict__ uniforms, long u_stride, long long* __restrict__ out, long stride) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int row = wave; row < rows; row += nwaves) {
+        const float* w = W + (long)row * ld_w;
+        const double u = uniforms[(long)row * u_stride];
+        float x[NV], sv[NV], m = -INFINITY, ms = -INFINITY;
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int v = lane + 64 * j;
+            x[j] = v < V ? w[v] : -INFINITY;
+            sv[j] = v < V ? x[j] * temp : -INFINITY;
+            nan |= sv[j] != sv[j];
+            m = fmaxf(m, x[j]);
+            ms = fmaxf(ms, sv[j]);
+        }
+        int tok = __ballot(nan) ? -1 : sample::pick<NV>(sv, wave_max(ms), u, V, lane);
+        if (tok < 0) {
+            m = wave_max(m);
+            int am = kAmNone;
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (lane + 64 * j < V) am = min(am, am_key(x[j], m, lane + 64 * j));
+            tok = am_index(wave_min_i(am));
+        }
+        if (lane == 0) out[(long)row * stride] = tok;
+    }
+}
+
 __global__ void scale_kernel(float* __restrict__ x, long n, float a) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] *= a;
 }
@@ -918,6 +956,18 @@ int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long*
                           uint64_t offset, hipStream_t s) {
     hipLaunchKernelGGL(sample_multinomial_kernel, dim3(grid_for((long)rows * 64, 256, 1024)), dim3(256), 0, s, W, ld_w, rows, V,
                        out, stride, seed, offset);
+    return ok();
+}
+int pw_sample_temperature(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride,
+                          long long* out, long stride, hipStream_t s) {
+    if (V > 512) return -1;
+    char label[48];
+    std::snprintf(label, sizeof label, "sample_temperature B%d V%d", rows, V);
+    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 16.0));
+    const dim3 grid(grid_for((long)rows * 64, 256, 1024));
+#define PW_ST(NV) hipLaunchKernelGGL(sample_temperature_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, out, stride)
+    if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
+#undef PW_ST
     return ok();
 }
 int pw_scale(float* x, long n, float a, hipStream_t s) {

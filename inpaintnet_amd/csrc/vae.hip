@@ -282,11 +282,14 @@ size_t vae_decoder_ws_bytes(const inet_vae_config& c, int B, int save) {
 
 int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long long* target, int teacher_forced,
                     const float* p, const float* mask_beat, const float* mask_tick, float* weights,
-                    long long* samples, void* ws, int save, hipStream_t s, uint64_t multinomial_seed) {
+                    long long* samples, void* ws, int save, hipStream_t s, uint64_t multinomial_seed, const double* uniforms,
+                    float temperature) {
     const int nb = c.beats, G = c.ticks_per_beat, T = nb * G, H = c.dec_hidden, V = c.num_notes, E = c.emb_dim, Z = c.z_dim;
     const long BH = (long)B * H;
     if (nb > 4) return -1;
     if (teacher_forced && !target) return -1;
+    const bool sampled = uniforms != nullptr;                  // temperature sampling (sample.h): a free-running inference call
+    if (sampled && (teacher_forced || multinomial_seed || V > 512)) return -1;
     VaeLayout L(c);
     DecWs w{};
     dec_carve(c, B, save, ws, w);
@@ -299,14 +302,16 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     // batches beyond one resident launch (LatentRNN decodes 512 measures per step): the rows are independent, so the fused
     // kernel runs over chunks of 512 rows (the 64-row build: 27 us per tick instead of 2 x 20) or 256, one launch after the other
     const int kDecodeChunk = B % 512 == 0 ? 512 : 256;
-    const bool fused_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
-    const bool fused_chunked = fused_shape && !fused_whole && B > kDecodeChunk && B % kDecodeChunk == 0 &&
+    const bool chain_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
+    // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
+    const bool b1_decode = chain_whole && !save && !mask_tick && w.b1ex && w.b1ex + decode_b1_words(B) == w.sync &&
+                           decode_b1_shape_ok(B, H, V, T, G, sampled);
+    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, sampled);   // ... with the beat path inside the same launch
+    // (a sampled call: the one fused launch that knows the rule is decode_b1.hip's; every other shape samples tick by tick below)
+    const bool fused_whole = chain_whole && (!sampled || b1_decode);
+    const bool fused_chunked = fused_shape && !sampled && !fused_whole && B > kDecodeChunk && B % kDecodeChunk == 0 &&
                                decode_chain_ok(kDecodeChunk, H, V, T, G);
     const bool fused_decode = fused_whole || fused_chunked;
-    // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
-    const bool b1_decode = fused_whole && !save && !mask_tick && w.b1ex && w.b1ex + decode_b1_words(B) == w.sync &&
-                           decode_b1_shape_ok(B, H, V, T, G);
-    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V);   // ... with the beat path inside the same launch
     // teacher-forced ticks: every input token is known and the 4 beats are independent, so each tick layer is a chain of
     // G steps over the beats as problems -- `npl` beats per launch, as many as fit the chip at once (2 at B = 256)
     int npl = 0;
@@ -514,6 +519,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
             }
             a.weights = weights + (long)r0 * T * V; a.samples = samples + (long)r0 * T;
             a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0;   // (later chunks: the launcher zeroes the area)
+            a.uniforms = uniforms; a.temperature = temperature;                 // (sampled: one whole launch, never chunks)
             if (mask_tick) { a.mask = mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
             if (save) {
                 a.sv0 = w.svt0 + (long)r0 * H; a.sv1 = w.svt1 + (long)r0 * H; a.sv_stride = (long)T * BH;
@@ -562,7 +568,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
 
         // logits = ReLU(h_top . Wo^T + bo) straight into weights[:, t, :], fused with the argmax that feeds tick t+1
         const bool draw = multinomial_seed != 0;               // decoder.py:506-509: sample the fed-back token
-        int rc = draw ? 1 : launch_logits_argmax(w.h1seq + (long)t * BH, H, B, H, p + L.out_w, p + L.out_b, V,
+        int rc = draw || sampled ? 1 : launch_logits_argmax(w.h1seq + (long)t * BH, H, B, H, p + L.out_w, p + L.out_b, V,
                                                  weights + (long)t * V, (long)T * V, samples + t,
                                                  T, s, pk ? P1.hpk_new : nullptr, w.wpk_out);
         if (rc < 0) return rc;
@@ -571,6 +577,8 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
                                 (long)T * V, B, V, H, EPI_RELU, s));
             if (draw) INET_TRY(pw_sample_multinomial(weights + (long)t * V, (long)T * V, B, V, samples + t, T,
                                                      multinomial_seed, (uint64_t)t * B, s));
+            else if (sampled) INET_TRY(pw_sample_temperature(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T,
+                                                            samples + t, T, s));
             else INET_TRY(pw_argmax(weights + (long)t * V, (long)T * V, B, V, samples + t, T, s));
         }
     }

@@ -10,9 +10,11 @@ decoded by the frozen VAE decoder.  Differences that are the point of the build:
   * every GRU / Linear is a single autograd Function over the C-ABI (inet_bigru2_*, inet_linear_*);
     the decoder runs dgrad-only (frozen parameters, latent_rnn.py:42-43).
 """
+import math
 import os
 import random
 
+import numpy as np
 import torch
 
 from . import dp, layout, ops
@@ -197,17 +199,34 @@ class LatentRNN(Model):
         return torch.zeros(self.num_rnn_layers * self.rnn_num_direction, batch_size, self.rnn_hidden_size,
                            device=self.flat.device)
 
-    def _decode(self, z2d):
+    def _decode(self, z2d, temperature=None, uniforms=None):
         """frozen decoder, train=False (latent_rnn.py:238): dropout still follows module.training (the quirk)."""
         dummy = torch.zeros(z2d.shape[0], self.vae_model.num_ticks_per_measure, device=z2d.device)
-        return self.vae_model.decoder(z2d, dummy, train=False)
+        return self.vae_model.decoder(z2d, dummy, train=False, temperature=temperature, uniforms=uniforms)
 
     def forward(self, past_context, future_context, target, measures_to_generate, train=True, eps=None,
-                teacher_forcing=None, eps_ar=None):
+                teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None):
         """-> weights (B,nt,24,V), samples (B,1,24*nt), gen_z (B,nt,Z)   (latent_rnn.py:110-159).
         eps: optional (eps_past (B,np,Z), eps_future, eps_target) injection; eps_ar: list of (B,Z) for the
-        free-running auto-regressive path."""
+        free-running auto-regressive path.
+        temperature (inference only: ValueError with train=True): the generated measures' tokens are drawn from
+        softmax(temperature * weights) (HierarchicalDecoder.forward) -- all measures in one decoder call on the non-auto-regressive
+        path, measure by measure on the free-running auto-regressive one; uniforms (B, n_target, 24) float64 or None (drawn with one
+        np.random.random_sample call)."""
         batch_size, _, measure_seq_len = past_context.size()
+        if temperature is None and uniforms is not None:
+            raise ValueError("uniforms without a temperature")
+        if temperature is not None:
+            if train:
+                raise ValueError("temperature sampling is an inference call (train=False)")
+            if not math.isfinite(float(temperature)):
+                raise ValueError(f"temperature {temperature!r} is not finite")
+            shape = (batch_size, measures_to_generate, measure_seq_len)
+            if uniforms is None:
+                uniforms = np.random.random_sample(shape)
+            uniforms = torch.as_tensor(uniforms, dtype=torch.float64).to(self.flat.device)
+            if tuple(uniforms.shape) != shape:
+                raise ValueError(f"uniforms of shape {tuple(uniforms.shape)}, expected {shape}")
         n_past, n_future = past_context.size(1), future_context.size(1)
         n_target = target.size(1) if target is not None else 0        # inference: no target (latent_rnn_tester.py:231-236)
         # the teacher-forcing coin first (the reference draws it behind the context GRUs, :142-145: nothing else reads `random` in
@@ -246,11 +265,11 @@ class LatentRNN(Model):
         else:
             seed = zp[:, -1, :].unsqueeze(1)
         return self.forward_generation(comb_context, measures_to_generate, seed, measure_seq_len, teacher_forcing,
-                                       eps_ar=eps_ar)
+                                       eps_ar=eps_ar, temperature=temperature, uniforms=uniforms)
 
     def forward_generation(self, context_vector, measures_to_gen, seed, measure_seq_len, teacher_forcing=False,
-                           eps_ar=None):
-        """latent_rnn.py:211-263"""
+                           eps_ar=None, temperature=None, uniforms=None):
+        """latent_rnn.py:211-263; temperature / uniforms (B, measures_to_gen, 24): see forward"""
         batch_size = context_vector.size(1)
         Hg = self.gen_hidden
         if teacher_forcing or not self.auto_reg:
@@ -262,7 +281,8 @@ class LatentRNN(Model):
             z2d = _LinearFn.apply(out.reshape(batch_size * measures_to_gen, -1), self.flat_for_autograd(), self,
                                   "generation_linear.weight", "generation_linear.bias")
             z_out = z2d.view(batch_size, measures_to_gen, -1)
-            w, s = self._decode(z2d)                       # rows ordered (b, measure): all measures in one call
+            # rows ordered (b, measure): all measures in one call
+            w, s = self._decode(z2d, temperature, uniforms.reshape(batch_size * measures_to_gen, -1) if uniforms is not None else None)
             weights = w.view(batch_size, measures_to_gen, measure_seq_len, -1)
             samples = s.view(batch_size, 1, measures_to_gen * measure_seq_len)
             return weights, samples, z_out
@@ -274,7 +294,7 @@ class LatentRNN(Model):
             gen_z = _LinearFn.apply(rnn_out.reshape(batch_size, -1), self.flat_for_autograd(), self,
                                     "generation_linear.weight", "generation_linear.bias")
             z_out.append(gen_z.view(batch_size, 1, -1))
-            w, s = self._decode(gen_z)
+            w, s = self._decode(gen_z, temperature, uniforms[:, i] if uniforms is not None else None)
             samples.append(s)
             weights.append(w.unsqueeze(1))
             # (the reference re-encodes the LAST generated measure too, latent_rnn.py:259, and drops the result)

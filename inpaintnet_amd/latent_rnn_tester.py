@@ -34,9 +34,15 @@ class LatentRNNTester(object):
         fn = getattr(self.dataset, "tensor_to_score", None)
         return fn(tensor.cpu()) if fn is not None else None
 
-    def generate(self, tensor_past, tensor_future, tensor_target, num_target_measures, eval=False):
+    def generate(self, tensor_past, tensor_future, tensor_target, num_target_measures, eval=False, temperature=None,
+                 num_variations=1):
         """-> (gen_score | None, gen_score_tensor (B, n_past + n_target + n_future, 24), original_score | None)
-        (latent_rnn_tester.py:197-266)"""
+        (latent_rnn_tester.py:197-266)
+        temperature (a finite float): `num_variations` fillings of the same gap -- the (one-row) contexts are expanded to that many
+        rows, every row's tokens are drawn from softmax(temperature * weights) with its own uniforms (one
+        np.random.random_sample((num_variations, n_target, 24)) call: np.random.seed reproduces a call) and gen_score_tensor has
+        num_variations rows.  Up to sixteen decoder rows (variations x target measures on the non-auto-regressive path) are one
+        register-resident launch.  temperature None: one filling by the argmax, as before."""
         if tensor_target is not None:
             if num_target_measures is not None:
                 assert num_target_measures == tensor_target.size(1)
@@ -47,9 +53,21 @@ class LatentRNNTester(object):
             tensor_past = self.create_empty_context('start')
         if tensor_future is None:
             tensor_future = self.create_empty_context('end')
+        if temperature is None:
+            if num_variations != 1:
+                raise ValueError("several variations need a temperature: the argmax has one answer per latent")
+        else:
+            if num_variations < 1:
+                raise ValueError("num_variations must be at least 1")
+            if tensor_past.size(0) != 1 or tensor_future.size(0) != 1:
+                raise ValueError("variations are drawn for one context (batch size 1)")
+            tensor_past = tensor_past.expand(num_variations, -1, -1).contiguous()
+            tensor_future = tensor_future.expand(num_variations, -1, -1).contiguous()
+            if tensor_target is not None:
+                tensor_target = tensor_target.expand(num_variations, -1, -1).contiguous()
         with torch.no_grad():
             weights, gen_target, _ = self.model(past_context=tensor_past, future_context=tensor_future, target=None,
-                                                measures_to_generate=num_target_measures, train=False)
+                                                measures_to_generate=num_target_measures, train=False, temperature=temperature)
         self.last_weights = weights
         torch.cuda.synchronize()
         ops.check_chains("LatentRNNTester.generate")                   # persistent kernels: never hand back results of a failed launch

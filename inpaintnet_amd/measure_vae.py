@@ -7,8 +7,11 @@ torch.autograd.Function whose forward/backward are single calls into the C-ABI
 (include/inpaintnet_hip.h); parameter gradients are accumulated straight into
 the model's flat gradient arena (`model.grad`) by the backward kernels.
 """
+import math
 import os
 import random
+
+import numpy as np
 
 import torch
 from torch import distributions
@@ -64,10 +67,12 @@ class _EncoderFn(ops.TrackedFunction):
 
 class _DecoderFn(ops.TrackedFunction):
     @staticmethod
-    def forward(ctx, z, flat, dec, target, teacher_forced, mask_beat, mask_tick, multinomial_seed=0):
+    def forward(ctx, z, flat, dec, target, teacher_forced, mask_beat, mask_tick, multinomial_seed=0, temperature=None,
+                uniforms=None):
         need = ops.outer_grad() and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         weights, samples, ws = ops.decoder_fwd(dec.cfg, z.contiguous(), target, teacher_forced, flat, mask_beat,
-                                               mask_tick, save=need, multinomial_seed=multinomial_seed)
+                                               mask_tick, save=need, multinomial_seed=multinomial_seed,
+                                               temperature=temperature, uniforms=uniforms)
         ctx.dec, ctx.ws, ctx.mb, ctx.mt = dec, ws, mask_beat, mask_tick
         if getattr(dec, "keep_ws", False):         # test hook: lets a parity test read intermediates (ops.ws_field)
             dec.last_ws = ws
@@ -83,7 +88,7 @@ class _DecoderFn(ops.TrackedFunction):
         dec = ctx.dec
         if dweights is None:                            # nothing downstream depends on the weights
             ctx.ws = None
-            return None, None, None, None, None, None, None, None
+            return (None,) * 10
         weights, samples = ctx.saved_tensors
         grads = dec.owner.grad if dec.owner.trainable else None
         dz = ops.decoder_bwd(dec.cfg, dweights.contiguous(), weights, samples, dec.owner.flat, grads, ctx.mb, ctx.mt,
@@ -94,7 +99,7 @@ class _DecoderFn(ops.TrackedFunction):
             if dp.world_size() > 1:
                 # behind the decoder's leaf GEMMs on the side streams, without holding up the encoder's backward
                 dp.start_bucket(grads, dec.owner.decoder_arena_start, grads.numel(), join_side=True)
-        return dz, None, None, None, None, None, None, None
+        return (dz,) + (None,) * 9
 
 
 class _ReparamFn(torch.autograd.Function):
@@ -253,10 +258,27 @@ class HierarchicalDecoder(torch.nn.Module):
                f'{self.dropout},' \
                f')'
 
-    def forward(self, z, score_tensor, train, masks=None, teacher_forced=None):
+    def forward(self, z, score_tensor, train, masks=None, teacher_forced=None, temperature=None, uniforms=None):
         """z (B,Z), score_tensor (B,24) -> weights (B,24,V), samples (B,1,24)   (decoder.py:412-453).
         One Bernoulli(0.5) teacher-forcing coin per call when train=True (decoder.py:431-434); it can be
-        injected with `teacher_forced=`."""
+        injected with `teacher_forced=`.
+        temperature (a finite float): a FREE-RUNNING call draws every token from softmax(temperature * weights[b, t]) with the uniform
+        uniforms[b, t] (csrc/sample.h: np.random.choice's order, as ConstraintModelGaussianReg.generate) and feeds it back; uniforms
+        (B,24) float64, host or device, or None: one np.random.random_sample((B, 24)) call.  Inference only (ValueError with
+        train=True); a call whose `teacher_forced=True` was injected ignores both.  `sampling = 'multinomial'` and the training path
+        are as they were.  The arguments are checked before anything random is drawn: a rejected call leaves every stream alone."""
+        T = self.cfg.beats * self.cfg.ticks_per_beat
+        if uniforms is not None and temperature is None:
+            raise ValueError("uniforms without a temperature")
+        if temperature is not None:
+            if train:
+                raise ValueError("temperature sampling is an inference call (train=False)")
+            if not math.isfinite(float(temperature)):
+                raise ValueError(f"temperature {temperature!r} is not finite")
+            if uniforms is not None:
+                uniforms = torch.as_tensor(uniforms, dtype=torch.float64)
+                if tuple(uniforms.shape) != (z.size(0), T):
+                    raise ValueError(f"uniforms of shape {tuple(uniforms.shape)}, expected {(z.size(0), T)}")
         if teacher_forced is None:
             if self.use_teacher_forcing and train:
                 teacher_forced = random.random() < self.teacher_forcing_prob
@@ -268,7 +290,6 @@ class HierarchicalDecoder(torch.nn.Module):
         assert z_dim == self.z_dim
         batch_size = score_tensor.size(0)
         assert batch_size == batch_size_z
-        T = self.cfg.beats * self.cfg.ticks_per_beat
         target = None
         if teacher_forced:
             target = score_tensor.detach()
@@ -285,6 +306,11 @@ class HierarchicalDecoder(torch.nn.Module):
                                   _next_mask_offset(self.cfg.beats * batch_size * H), dev)
             mt = ops.dropout_mask((T, batch_size, H), self.dropout, _DropState.seed,
                                   _next_mask_offset(T * batch_size * H), dev)
+        if temperature is not None and not teacher_forced:
+            if uniforms is None:
+                uniforms = torch.from_numpy(np.random.random_sample((batch_size, T)))
+            u = uniforms.to(z.device).contiguous()
+            return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u)
         seed = 0
         if self.sampling == 'multinomial' and not teacher_forced:
             # one counter-based stream per call, derived from the dropout seed (set_dropout_seed) and the call counter
@@ -387,6 +413,12 @@ class MeasureVAE(Model):
         weights, samples = self.decoder(z=z_tilde, score_tensor=measure_score_tensor, train=train,
                                         teacher_forced=teacher_forced, masks=dec_masks)
         return weights, samples, z_dist, prior_dist, z_tilde, z_prior
+
+    def decode(self, z, temperature=None, uniforms=None):
+        """z (B,Z) -> (weights (B,24,V), samples (B,1,24)): the free-running decoder alone (what VAETester.decode_mid_point does with
+        a latent), by the argmax or -- temperature set -- drawn from softmax(temperature * weights) (HierarchicalDecoder.forward)."""
+        dummy = torch.zeros(z.shape[0], self.num_ticks_per_measure, device=z.device)
+        return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms)
 
     def _standard_normal(self, like):
         """N(0, 1) of the latent's shape (measure_vae.py:122-125): the constant loc / scale tensors are built once."""

@@ -5,6 +5,7 @@ is produced by the HIP kernels behind include/inpaintnet_hip.h.  All functions
 are asynchronous on torch's current stream.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -228,18 +229,35 @@ def decoder_ws(cfg, B, save, device):
 
 
 def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tick=None, save=False, ws=None,
-                multinomial_seed=0):
+                multinomial_seed=0, temperature=None, uniforms=None):
     """z [B,Z] -> weights [B,T,V], samples [B,1,T] int64, ws.  multinomial_seed != 0: the fed-back tokens are drawn from
-    softmax(weights) (decoder.py:506-509) instead of the argmax."""
+    softmax(weights) (decoder.py:506-509) instead of the argmax.  temperature + uniforms ([B,T] float64 on the device, one uniform
+    per row and tick): inet_vae_decoder_sample -- a free-running call whose tokens are drawn from softmax(temperature * weights) by
+    csrc/sample.h's rule."""
+    if (temperature is None) != (uniforms is None):
+        raise ValueError("decoder_fwd: temperature and uniforms go together")
     _f32c(z); _f32c(params)
     B = z.shape[0]
     T = cfg.beats * cfg.ticks_per_beat
+    if temperature is not None:
+        if teacher_forced or multinomial_seed:
+            raise ValueError("decoder_fwd: temperature sampling is a free-running call without a multinomial seed")
+        if not math.isfinite(float(temperature)):
+            raise ValueError(f"decoder_fwd: temperature {temperature!r} is not finite")
+        if not (uniforms.is_cuda and uniforms.dtype == torch.float64 and uniforms.is_contiguous() and tuple(uniforms.shape) == (B, T)):
+            raise ValueError(f"decoder_fwd: uniforms must be a contiguous float64 device tensor of shape {(B, T)}")
     if target is not None:
         _i64c(target)
     if ws is None:
         ws = decoder_ws(cfg, B, save, z.device)
     weights = torch.empty(B, T, cfg.num_notes, dtype=torch.float32, device=z.device)
     samples = torch.empty(B, 1, T, dtype=torch.int64, device=z.device)
+    if temperature is not None:
+        check(_lib.lib().inet_vae_decoder_sample(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
+                                                 ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
+                                                 stream_ptr()), "inet_vae_decoder_sample")
+        _hold(uniforms)
+        return weights, samples, ws
     check(_lib.lib().inet_vae_decoder_fwd(C.byref(cfg), B, ptr(z), ptr(target), int(bool(teacher_forced)), ptr(params),
                                           ptr(mask_beat), ptr(mask_tick), ptr(weights), ptr(samples), ptr(ws),
                                           ws.numel() * 4, int(save), int(multinomial_seed) & (2 ** 64 - 1), stream_ptr()),
@@ -289,6 +307,18 @@ def sample_multinomial(weights2d, seed, offset=0):
     out = torch.empty(rows, dtype=torch.int64, device=weights2d.device)
     check(_lib.lib().inet_sample_multinomial(ptr(weights2d), weights2d.stride(0), rows, V, ptr(out), 1,
                                              int(seed) & (2 ** 64 - 1), int(offset), stream_ptr()), "inet_sample_multinomial")
+    return out
+
+
+def sample_temperature(weights2d, temperature, uniforms):
+    """inet_sample_temperature: one token per row of weights2d [rows,V] (row stride = stride(0)) from softmax(temperature * row) with
+    the row's uniform (uniforms [rows] float64 on the device, any stride), by csrc/sample.h's rule."""
+    rows, V = weights2d.shape
+    assert weights2d.stride(1) == 1 and weights2d.dtype == torch.float32
+    assert uniforms.is_cuda and uniforms.dtype == torch.float64 and tuple(uniforms.shape) == (rows,)
+    out = torch.empty(rows, dtype=torch.int64, device=weights2d.device)
+    check(_lib.lib().inet_sample_temperature(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
+                                             uniforms.stride(0), ptr(out), 1, stream_ptr()), "inet_sample_temperature")
     return out
 
 

@@ -1,10 +1,40 @@
-"""eval-mode decode latency at small batch (bench.decode_latency_extra): python tools/decode_latency.py"""
+"""eval-mode decode latency at small batch (bench.decode_latency_extra): python tools/decode_latency.py
+--temperature T: only the sampled decode (temperature T, uniforms on the device) beside the argmax decode of the same build, b = 1, 4
+and 16, five rounds of 300 calls each (median and range per call)."""
 import os, sys
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
 sys.stdout = sys.stderr
 wl = bench.VaeWorkload(torch.device("cuda", 0), 0)
+if "--temperature" in sys.argv:
+    import statistics, time
+    from inpaintnet_amd import ops
+    temperature = float(sys.argv[sys.argv.index("--temperature") + 1])
+    vae = wl.model
+    vae.eval()
+
+    def rounds(call, n=300, k=5):
+        out = []
+        with torch.no_grad():
+            for _ in range(20):
+                call()
+            for _ in range(k):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(n):
+                    call()
+                torch.cuda.synchronize()
+                out.append(1e3 * (time.perf_counter() - t0) / n)
+        return f"{statistics.median(out):.4f} ms ({min(out):.4f} .. {max(out):.4f})"
+
+    for b in (1, 4, 16):
+        z = torch.randn(b, vae.latent_space_dim, device="cuda")
+        dummy = torch.zeros(b, 24, device="cuda")
+        u = torch.rand(b, 24, dtype=torch.float64, device="cuda")
+        print(f"b = {b}: argmax {rounds(lambda: vae.decoder(z, dummy, train=False))}, temperature {temperature} "
+              f"{rounds(lambda: vae.decoder(z, dummy, train=False, temperature=temperature, uniforms=u))}, chain status {ops.chain_status()}")
+    sys.exit(0)
 r = bench.decode_latency_extra(wl.model, iters=200)["decoder_eval"]
 print({k: v["ms_per_call"] for k, v in r.items() if isinstance(v, dict)})
 # b = 1 under the decode kernels (inet_set_option key 15: 0 = decode_chain.hip's exchange kernel, 1 / 2 = decode_b1.hip behind the beat
