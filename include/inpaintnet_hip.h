@@ -348,7 +348,8 @@ int inet_gru_step(int batch, int H, const float* gi, const float* h_prev, const 
  * a second, lower-priority HIP stream (default 1; also INET_SIDE_STREAM=0 in the environment) */
 int inet_set_option(int key, int value);
 /* key 2 = force the batched-GEMM tile configuration: value -1 = cost model (default), 0..4 = 64x64, 128x128, 192x64,
- * 192x128, 192x192 block tiles; key 3 = forced split-K factor (0 = none) used while key 2 is forced.  Test hooks: the
+ * 192x128, 192x192 block tiles; key 3 = forced split-K factor (0 = cost model) of the
+ * LDS-tiled kernel while key 2 is forced, and of the TN-direct and workgroup split-K kernels where they take the shape.  Test hooks: the
  * parity tests drive every tile configuration through the same shapes (keys 2 and 3). */
 /* key 1 = deferred joins (default 0).  With 0 every *_bwd entry point makes `stream` wait for the side stream before
  * it returns.  With 1 it does not: the caller must keep every workspace passed to a *_bwd call alive and call
@@ -444,6 +445,21 @@ int inet_decode_b1_plan(int B, int V, int Z, int* out8);
 /* The same for a temperature-sampled call (inet_vae_decoder_sample): the same planner with its `sample` input set, the same
  * self-check.  -1 also under inet_set_option key 15 != 4: the sampling build exists for the default mode's plans. */
 int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8);
+/* What inet_gemm (nbatch = 1) / inet_gemm_batched (nbatch 2..8: no bias, epi 0, acc 1) launch for a call, under the options set now
+ * (inet_set_option keys 2, 3, 5), without a GPU: the dispatcher's planner (csrc/gemm.hip gemm_plan) behind the C-ABI.  out16 = {family
+ * (0 = few-row gemv, 1 = TN-direct, 2 = kc-direct, 3 = workgroup split-K, 4 = LDS-tiled), tile configuration, tile rows, tile columns,
+ * splits, K per split, tiles along N, tiles, grid x, y, z, zero fill in front (split-K of a storing call), epilogue pass behind (split-K
+ * with a non-linear epilogue), kernel launches in all, products run one after the other (1: one launch takes the call; nbatch: a batched
+ * call no batched kernel takes -- the plan is then that of one product), 0}; work2 = algorithmic {FLOPs, bytes} of the launch; label (cap
+ * bytes) = its name in the profile (inet_prof_dump).  0, or -1 for what the two entries reject (sizes <= 0, epi outside 0..5, acc
+ * outside 0..1, nbatch outside 1..8) and for a null output -- nothing is written then. */
+int inet_gemm_plan(int a_kmajor, int b_kmajor, int M, int N, int K, int64_t lda, int64_t ldb, int has_bias, int epi, int acc,
+                   int nbatch, int32_t* out16, double* work2, char* label, int cap);
+/* The same for n = 1..4 independent products handed to the library's grouped launch (the two heads of the encoder, a module's leaf
+ * weight gradients): desc = n x {a_kmajor, b_kmajor, M, N, K, lda, ldb, has_bias, epi, acc}.  One launch takes the group (few-row gemv
+ * group, workgroup split-K group): row 0 of out [n][16], work [n][2], label [n][cap] describes it and out[14] = 1; else every product
+ * runs on its own plan, row i describes product i and out[14] = n. */
+int inet_gemm_group_plan(int n, const int64_t* desc, int32_t* out, double* work, char* label, int cap);
 /* Loads every kernel of the library on the CURRENT device (code objects and function objects, which the HIP runtime otherwise
  * builds lazily on the launch path of each kernel's first launch: csrc/preload.hip) without launching anything.  Idempotent per
  * device; returns the number of kernels touched (0 when the device was done already), -2 without a device or on a runtime

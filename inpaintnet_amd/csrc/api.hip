@@ -1,5 +1,6 @@
 // extern "C" surface declared in include/inpaintnet_hip.h.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include "seq.h"
 #include "layout.h"
@@ -481,8 +482,8 @@ int inet_set_option(int key, int value) {
     if (key == 0) { side_set_enabled(value); return 0; }
     if (key == 1) { side_set_defer(value); return 0; }
     if (key == 4) { chain_set_enabled(value); return 0; }
-    if (key == 2) { if (value < -1 || value > 4) return -1; gemm_set_force(value, -1); return 0; }
-    if (key == 3) { if (value < 0) return -1; gemm_set_force(-2, value); return 0; }
+    if (key == 2) { if (value < -1 || value > 4) return -1; gemm_set_force_cfg(value); return 0; }
+    if (key == 3) { if (value < 0) return -1; gemm_set_force_split(value); return 0; }
     if (key == 5) { if (value < 0 || value > 4) return -1; gemm_set_direct(value); return 0; }
     if (key == 6) { chain_arm_fault(value); return 0; }
     if (key == 7) { if (value != 0 && value != 9) return -1; chain2_set_mode(value); return 0; }
@@ -538,6 +539,53 @@ int inet_slow_waits(unsigned* dst, int max_entries, int reset, int64_t* noted) {
 
 int inet_decode_b1_plan(int B, int V, int Z, int* out8) { return decode_b1_plan_check(B, V, Z, out8); }
 int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8) { return decode_b1_plan_check(B, V, Z, out8, true); }
+
+namespace {
+// the arguments of a product as the planners read them (shape, layout, leading dimensions, modes; no operand is touched)
+bool plan_args(int64_t akm, int64_t bkm, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t has_bias, int64_t epi,
+               int64_t acc, GemmArgs* g) {
+    static const float some_bias = 0.f;
+    if (M <= 0 || N <= 0 || K <= 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || epi < 0 || epi > 5 || acc < 0 || acc > 1) return false;
+    *g = gemm_args(nullptr, lda, akm != 0, nullptr, ldb, bkm != 0, nullptr, N, (int)M, (int)N, (int)K, has_bias ? &some_bias : nullptr,
+                   (int)epi, nullptr, 0, (int)acc);
+    return true;
+}
+void plan_out(const GemmPlan& p, int repeat, int products, int32_t* out, double* work, char* label, int cap) {
+    const int32_t v[16] = {p.family, p.cfg, p.tile_m, p.tile_n, p.splits, p.k_per_split, p.tiles_n, p.tiles, (int32_t)p.grid.x,
+                           (int32_t)p.grid.y, (int32_t)p.grid.z, p.zero_fill, p.two_pass, repeat * (1 + p.zero_fill + p.two_pass),
+                           products, 0};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    work[0] = p.flops; work[1] = p.bytes;
+    std::snprintf(label, (size_t)cap, "%s", p.label);
+}
+}  // namespace
+
+int inet_gemm_plan(int a_kmajor, int b_kmajor, int M, int N, int K, int64_t lda, int64_t ldb, int has_bias, int epi, int acc,
+                   int nbatch, int32_t* out16, double* work2, char* label, int cap) {
+    GemmArgs g;
+    if (!out16 || !work2 || !label || cap <= 0 || nbatch < 1 || nbatch > 8) return -1;
+    if (!plan_args(a_kmajor, b_kmajor, M, N, K, lda, ldb, has_bias, epi, acc, &g)) return -1;
+    if (nbatch > 1 && (has_bias || epi != EPI_NONE || acc != ACC_ADD)) return -1;       // (what inet_gemm_batched computes)
+    g.nbatch = nbatch;
+    GemmPlan p = gemm_plan(g);
+    const bool each = p.family == GEMM_EACH;
+    if (each) { g.nbatch = 0; p = gemm_plan(g); }
+    plan_out(p, each ? nbatch : 1, each ? nbatch : 1, out16, work2, label, cap);
+    return 0;
+}
+
+int inet_gemm_group_plan(int n, const int64_t* desc, int32_t* out, double* work, char* label, int cap) {
+    GemmArgs list[kGemmGroupMax];
+    if (n < 1 || n > kGemmGroupMax || !desc || !out || !work || !label || cap <= 0) return -1;
+    for (int i = 0; i < n; ++i) {
+        const int64_t* d = desc + 10 * i;
+        if (!plan_args(d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], &list[i])) return -1;
+    }
+    const GemmPlan p = gemm_group_plan(list, n);
+    if (p.family != GEMM_EACH) { plan_out(p, 1, 1, out, work, label, cap); return 0; }
+    for (int i = 0; i < n; ++i) plan_out(gemm_plan(list[i]), 1, n, out + 16 * i, work + 2 * i, label + (size_t)cap * i, cap);
+    return 0;
+}
 
 int inet_preload(void) { return preload_kernels(); }
 int inet_kernel_count(void) { return preload_kernel_count(); }

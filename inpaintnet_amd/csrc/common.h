@@ -139,8 +139,24 @@ int launch_gemm(const GemmArgs& g, hipStream_t s);
 constexpr int kGemmGroupMax = 4;
 // n independent products: one launch when a grouped kernel applies (gemm.hip), else one after the other
 int launch_gemm_group(const GemmArgs* list, int n, hipStream_t s);
-void gemm_set_force(int cfg, int split);      // cfg: -1 cost model, 0..4 tile configuration; split: 0 = 1, else forced
-void gemm_set_direct(int mode);                 // 0 never, 1 cost model, 2 whenever applicable (k-major x k-major products)
+// What those two launch, as a value (gemm.hip: pure host arithmetic on the shape and the options below).  GEMM_EACH: no single
+// launch takes the call -- the products of a batched call / a group run one after the other, each on a plan of its own.
+enum { GEMM_GEMV = 0, GEMM_TN_DIRECT = 1, GEMM_KC_DIRECT = 2, GEMM_KS = 3, GEMM_TILED = 4, GEMM_EACH = 5 };
+struct GemmPlan {
+    int family, cfg;                          // GEMM_*, index into the family's tile table (gemv: rows - 1)
+    int tile_m, tile_n;
+    int splits, k_per_split;                  // k ranges (they meet in atomics), K per range
+    int tiles_n, tiles;                       // output tiles along N, in all (a ks group: tiles_n is per product)
+    dim3 grid;                                // tiles x splits x batch workgroups
+    bool zero_fill, two_pass;                 // a zero fill in front (split, storing call), an epilogue pass behind (split, non-linear)
+    double flops, bytes;                      // algorithmic work of the launch
+    char label[96];                           // the launch's name in the profile (bench.py groups kernels by it)
+};
+GemmPlan gemm_plan(const GemmArgs& g);
+GemmPlan gemm_group_plan(const GemmArgs* list, int n);
+void gemm_set_force_cfg(int cfg);               // inet_set_option key 2: -1 cost model, 0..4 tile configuration of the LDS-tiled kernel
+void gemm_set_force_split(int split);           // key 3: 0 cost model, else the split-K factor
+void gemm_set_direct(int mode);                 // key 5: 0 LDS-tiled only, 1 by shape, 2 direct whenever applicable, 3 no ks, 4 ks first
 int launch_gru_fwd(const GruFwdBatch& b, hipStream_t s);
 int launch_gru_bwd(const GruBwdBatch& b, hipStream_t s);
 // hpk / Wpk: optional fragment-major twins of h and W (used when both are given and H % 256 == 0)

@@ -21,7 +21,7 @@
 // of a 32-chunk is 8*(i/4) + 4*h + i%4 for both operands.
 #include "common.h"
 #include <cstdio>
-#include <cstdlib>
+#include <cstring>
 #include "prof.h"
 #include "side.h"
 #include "pointwise.h"
@@ -684,22 +684,6 @@ __global__ __launch_bounds__(256) void gemm_ks_group_kernel(GemmGroupArgs a) {
     gemm_ks_body<TA, TB, AKM, BKM>(a.g[i], v - a.first[i], a.tiles_n[i], a.first[i + 1] - a.first[i]);
 }
 
-template <int TM, int TN>
-int launch_cfg(const GemmArgs& g, dim3 grid, hipStream_t s, unsigned pad) {
-    if (!g.a_kmajor && !g.b_kmajor) hipLaunchKernelGGL((gemm_kernel<TM, TN, false, false>), grid, dim3(256), pad, s, g);
-    else if (!g.a_kmajor && g.b_kmajor) hipLaunchKernelGGL((gemm_kernel<TM, TN, false, true>), grid, dim3(256), pad, s, g);
-    else if (g.a_kmajor && g.b_kmajor) hipLaunchKernelGGL((gemm_kernel<TM, TN, true, true>), grid, dim3(256), pad, s, g);
-    else hipLaunchKernelGGL((gemm_kernel<TM, TN, true, false>), grid, dim3(256), pad, s, g);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-struct TileCfg { int tm, tn, wgs_per_cu; double eff; };
-// block tile = 64*tm x 64*tn; residency from the LDS footprint (2 stages); eff = relative MFMA efficiency
-const TileCfg kCfgs[] = {
-    {1, 1, 4, 0.70}, {2, 2, 2, 0.60}, {3, 1, 2, 0.70}, {3, 2, 1, 0.70}, {3, 3, 1, 0.85},
-};
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
 // second pass of a split-K product with a non-linear epilogue: C = epi(C, aux)   (bias was added by split 0)
 __global__ void gemm_epilogue_kernel(float* __restrict__ C, long ldc, int M, int N, const float* __restrict__ aux,
                                      long ldaux, int epi) {
@@ -711,100 +695,118 @@ __global__ void gemm_epilogue_kernel(float* __restrict__ C, long ldc, int M, int
     }
 }
 
-int g_force_cfg = -2, g_force_split = 0;      // -2: not read yet (inet_set_option keys 2, 3), -1: cost model
+// ---- Planning: which kernel, tile and split a product gets.  Pure host arithmetic on the shape and the options below: no
+// stream, no launch, no allocation (gemm_plan / gemm_group_plan; inet_gemm_plan shows the answer to tests on a CPU). ----
+int g_force_cfg = -1, g_force_split = 0;      // inet_set_option keys 2, 3: tile configuration of kCfgs (-1: cost model), split-K factor (0: cost model)
 int g_direct = 1;    // direct kernels (inet_set_option key 5): 0 never, 1 (default) by shape, 2 direct whenever applicable, 3 big shapes only, 4 split-K first
 
-struct DirectCfg { int ta, tb; };
-const DirectCfg kDirect[] = {{3, 2}, {2, 2}, {3, 3}};
-inline long tiles_of(const DirectCfg& c, const GemmArgs& g) { return (long)(g.M / (64 * c.ta)) * (g.N / (64 * c.tb)); }
+struct Tile { int ta, tb; };                  // in units of the family's granule
+struct TileCfg { int tm, tn, wgs_per_cu; double eff; };
+// LDS-tiled: block tile = 64*tm x 64*tn; residency from the LDS footprint (2 stages); eff = relative MFMA efficiency
+const TileCfg kCfgs[] = {
+    {1, 1, 4, 0.70}, {2, 2, 2, 0.60}, {3, 1, 2, 0.70}, {3, 2, 1, 0.70}, {3, 3, 1, 0.85},
+};
+constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+const Tile kDirect[] = {{3, 2}, {2, 2}, {3, 3}};                     // TN-direct, x 64
+const Tile kKc[] = {{6, 6}, {6, 4}, {6, 2}, {4, 4}};                 // kc-direct, x 32
+const Tile kKs[] = {{4, 4}, {4, 2}, {2, 2}, {6, 4}, {4, 6}};         // workgroup split-K, x 16 (the group kernel: the first three)
 
-// Direct (LDS-free) k-major x k-major product: returns 1 when the shape does not qualify, else the launch status.
-int launch_gemm_direct(const GemmArgs& gin, hipStream_t s, int force_split) {
-    GemmArgs g = gin;
-    const bool nonlinear = g.epi != EPI_NONE;
+inline bool nonlinear(const GemmArgs& g) { return g.epi != EPI_NONE; }
+
+// the buffer descriptors of the direct kernels hold an operand's extent in bytes as 32 bits
+inline bool operands_below_2e9(const GemmArgs& g) {
+    return (double)(g.a_kmajor ? g.K : g.M) * g.lda * 4 < 2.0e9 && (double)(g.b_kmajor ? g.K : g.N) * g.ldb * 4 < 2.0e9;
+}
+
+// algorithmic work of `products` products of one shape: operands read once, the result written once
+inline void add_work(const GemmArgs& g, int products, GemmPlan& p) {
+    p.flops += 2.0 * g.M * g.N * g.K * products;
+    p.bytes += 4.0 * products * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N);
+}
+
+// a plan of family `family` over `tiles_m x tiles_n` tiles of tile configuration `cfg`; one k range until split_k says otherwise
+inline GemmPlan plan_of(int family, int cfg, int tile_m, int tile_n, int tiles_m, int tiles_n, const GemmArgs& g) {
+    GemmPlan p{};
+    p.family = family; p.cfg = cfg; p.tile_m = tile_m; p.tile_n = tile_n;
+    p.tiles_n = tiles_n; p.tiles = tiles_m * tiles_n;
+    p.splits = 1; p.k_per_split = g.K;
+    p.grid = dim3(p.tiles);
+    return p;
+}
+
+// `want` k ranges of a multiple of the family's granule each: the count that is left after rounding, and what a split costs --
+// a zero fill in front when the call stores (the ranges meet in atomics), a pass behind when the epilogue is non-linear
+inline void split_k(const GemmArgs& g, int want, int granule, GemmPlan& p) {
+    const int kps = ((g.K + want - 1) / want + granule - 1) / granule * granule;
+    p.k_per_split = kps;
+    p.splits = (g.K + kps - 1) / kps;
+    p.zero_fill = p.splits > 1 && g.acc == ACC_STORE;
+    p.two_pass = p.splits > 1 && nonlinear(g);
+}
+
+inline const char* layout_name(const GemmArgs& g) {
+    return g.a_kmajor ? (g.b_kmajor ? "TN" : "TT") : (g.b_kmajor ? "NN" : "NT");
+}
+
+// the launch's work and its name in the profile: shape, layout, kernel letter (d, k, t) with its tile, splits, epilogue
+inline void finish(const GemmArgs& g, int products, char kernel, GemmPlan& p) {
+    add_work(g, products, p);
+    std::snprintf(p.label, sizeof p.label, "M%d N%d K%d %s %c%dx%d s%d e%d", g.M, g.N, g.K, layout_name(g), kernel, p.tile_m, p.tile_n,
+                  p.splits, g.epi);
+}
+
+// Few-row products (the small projections of a b = 1 decode call): one wave per column.
+bool plan_gemv(const GemmArgs& g, GemmPlan& p) {
+    if (g.M > 8 || g.a_kmajor || g.b_kmajor || g.nbatch > 1 || g_force_cfg >= 0 || g.acc == ACC_ATOMIC) return false;
+    p = plan_of(GEMM_GEMV, g.M - 1, g.M, 4, 1, (g.N + 3) / 4, g);
+    add_work(g, 1, p);
+    std::snprintf(p.label, sizeof p.label, "M%d N%d K%d NT gemv e%d", g.M, g.N, g.K, g.epi);
+    return true;
+}
+
+// Direct (LDS-free) k-major x k-major product, also nbatch of them on one grid.
+bool plan_tn_direct(const GemmArgs& g, int force_split, GemmPlan& p) {
     const int nbt = g.nbatch > 1 ? g.nbatch : 1;
-    if (!g.a_kmajor || !g.b_kmajor || (g.M & 63) || (g.N & 63) || g.K < 64) return 1;
-    if ((double)g.K * g.lda * 4 >= 2.0e9 || (double)g.K * g.ldb * 4 >= 2.0e9) return 1;
-    if (nbt > 1 && (g.bias || nonlinear || g.acc == ACC_STORE)) return 1;
+    if (!g.a_kmajor || !g.b_kmajor || (g.M & 63) || (g.N & 63) || g.K < 64 || !operands_below_2e9(g)) return false;
+    if (nbt > 1 && (g.bias || nonlinear(g) || g.acc == ACC_STORE)) return false;
     const int kSplits[] = {1, 2, 4, 8, 16, 32};
     double best = 1e300;
     int bi = -1, bs = 1;
     for (int ci = 0; ci < 3; ++ci) {
-        const DirectCfg& c = kDirect[ci];
+        const Tile& c = kDirect[ci];
         if (g.M % (64 * c.ta) || g.N % (64 * c.tb)) continue;
         const long tiles = (long)(g.M / (64 * c.ta)) * (g.N / (64 * c.tb));
         for (int sp : kSplits) {
-            if (sp > 1 && (g.K / sp < 64 || (nonlinear && g.acc != ACC_STORE))) break;
+            if (sp > 1 && (g.K / sp < 64 || (nonlinear(g) && g.acc != ACC_STORE))) break;
             if (force_split > 0 && sp != force_split) continue;
             const long wgs = tiles * sp * nbt;
             const long rounds = (wgs + 255) / 256;
             const double steps = (double)((g.K + sp - 1) / sp + 1) / 2;
             double cost = rounds * (steps * c.ta * c.tb * (64.0 / 2400.0) + 4.0);
-            if (sp > 1) cost += 2.0 + (double)g.M * g.N * sp * nbt / 6.0e5 + (nonlinear ? 3.0 : 0.0);
+            if (sp > 1) cost += 2.0 + (double)g.M * g.N * sp * nbt / 6.0e5 + (nonlinear(g) ? 3.0 : 0.0);
             if (cost < best) { best = cost; bi = ci; bs = sp; }
         }
     }
-    if (bi < 0 || (g_direct != 2 && (g.K / bs < 768 || (long)tiles_of(kDirect[bi], g) * bs * nbt < 192))) return 1;
-    const DirectCfg& c = kDirect[bi];
-    int kps = (g.K + bs - 1) / bs;
-    kps = (kps + 1) / 2 * 2;
-    const int splits = (g.K + kps - 1) / kps;
-    g.k_per_split = kps;
-    const bool two_pass = splits > 1 && nonlinear;
-    if (splits > 1) {
-        if (g.acc == ACC_STORE && pw_zero2d(g.C, g.ldc, g.M, g.N, s) != 0) return -2;
-        g.acc = ACC_ATOMIC;
-        if (two_pass) g.epi = EPI_NONE;
-    }
-    const int tiles_n = g.N / (64 * c.tb), tiles = tiles_n * (g.M / (64 * c.ta));
-    char label[96];
-    if (nbt > 1 && (g.K + kps - 1) / kps * kps != g.K) return 1;   // (the kernel derives the split count from the grid)
-    if (nbt > 1) std::snprintf(label, sizeof label, "M%d N%d K%d TN d%dx%d s%d e%d x%d", g.M, g.N, g.K, 64 * c.ta, 64 * c.tb,
-                               splits, gin.epi, nbt);
-    else std::snprintf(label, sizeof label, "M%d N%d K%d TN d%dx%d s%d e%d", g.M, g.N, g.K, 64 * c.ta, 64 * c.tb, splits, gin.epi);
-    ProfScope prof(PROF_GEMM, 2.0 * g.M * g.N * g.K * nbt, s, label,
-                   4.0 * nbt * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
-    const dim3 grid(tiles * splits * nbt);
-    if (bi == 0) hipLaunchKernelGGL((gemm_tn_direct_kernel<3, 2>), grid, dim3(256), 0, s, g, tiles_n, tiles);
-    else if (bi == 1) hipLaunchKernelGGL((gemm_tn_direct_kernel<2, 2>), grid, dim3(256), 0, s, g, tiles_n, tiles);
-    else hipLaunchKernelGGL((gemm_tn_direct_kernel<3, 3>), grid, dim3(256), 0, s, g, tiles_n, tiles);
-    int rc = hipGetLastError() == hipSuccess ? 0 : -2;
-    if (rc == 0 && two_pass) {
-        long n = (long)g.M * g.N;
-        int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-        hipLaunchKernelGGL(gemm_epilogue_kernel, dim3(blocks), dim3(256), 0, s, g.C, g.ldc, g.M, g.N, gin.aux, gin.ldaux,
-                           gin.epi);
-        rc = hipGetLastError() == hipSuccess ? 0 : -2;
-    }
-    return rc;
-}
-
-}  // namespace
-
-// inet_set_option keys 2 / 3: force tile configuration `cfg` (index into kCfgs, -1 = cost model) / split-K factor
-void gemm_set_force(int cfg, int split) {
-    if (cfg >= -1) g_force_cfg = cfg;
-    if (split >= 0) g_force_split = split;
-}
-
-struct KcCfg { int ta, tb; };
-const KcCfg kKc[] = {{6, 6}, {6, 4}, {6, 2}, {4, 4}};
-
-template <int TA, int TB>
-void launch_kc(const GemmArgs& g, dim3 grid, hipStream_t s, int tiles_n) {
-    if (g.b_kmajor) hipLaunchKernelGGL((gemm_kc_direct_kernel<TA, TB, true>), grid, dim3(256), 0, s, g, tiles_n);
-    else hipLaunchKernelGGL((gemm_kc_direct_kernel<TA, TB, false>), grid, dim3(256), 0, s, g, tiles_n);
+    if (bi < 0) return false;
+    const Tile& c = kDirect[bi];
+    p = plan_of(GEMM_TN_DIRECT, bi, 64 * c.ta, 64 * c.tb, g.M / (64 * c.ta), g.N / (64 * c.tb), g);
+    if (g_direct != 2 && (g.K / bs < 768 || (long)p.tiles * bs * nbt < 192)) return false;
+    split_k(g, bs, 2, p);
+    if (nbt > 1 && p.splits * p.k_per_split != g.K) return false;       // (the kernel derives the split count from the grid)
+    p.grid = dim3(p.tiles * p.splits * nbt);
+    finish(g, nbt, 'd', p);
+    if (nbt > 1) std::snprintf(p.label + std::strlen(p.label), 8, " x%d", nbt);
+    return true;
 }
 
 // Direct kernel for a k-contiguous A (forward and data-gradient products): no split-K, so it needs a tile
-// configuration whose grid fills the chip by itself.  Returns 1 when the shape does not qualify.
-int launch_gemm_kc_direct(const GemmArgs& g, hipStream_t s) {
-    if (g.a_kmajor || (g.K & 63) || g.acc == ACC_ATOMIC) return 1;
-    if ((double)g.M * g.lda * 4 >= 2.0e9 || (double)(g.b_kmajor ? g.K : g.N) * g.ldb * 4 >= 2.0e9) return 1;
+// configuration whose grid fills the chip by itself.
+bool plan_kc_direct(const GemmArgs& g, GemmPlan& p) {
+    if (g.a_kmajor || (g.K & 63) || g.acc == ACC_ATOMIC || !operands_below_2e9(g)) return false;
     double best = 1e300;
     int bi = -1;
     for (int ci = 0; ci < 4; ++ci) {
-        const KcCfg& c = kKc[ci];
+        const Tile& c = kKc[ci];
         if (g.M % (32 * c.ta) || g.N % (32 * c.tb)) continue;
         const long wgs = (long)(g.M / (32 * c.ta)) * (g.N / (32 * c.tb));
         if (wgs < 192 && g_direct != 2) continue;
@@ -812,51 +814,31 @@ int launch_gemm_kc_direct(const GemmArgs& g, hipStream_t s) {
         const double cost = rounds * ((double)g.K / 4 * c.ta * c.tb * (32.0 / 1900.0) + 8.0);
         if (cost < best) { best = cost; bi = ci; }
     }
-    if (bi < 0 || (g_direct != 2 && g.K < 256)) return 1;
-    const KcCfg& c = kKc[bi];
-    const int tiles_n = g.N / (32 * c.tb);
-    const dim3 grid(tiles_n * (g.M / (32 * c.ta)));
-    char label[96];
-    std::snprintf(label, sizeof label, "M%d N%d K%d N%c d%dx%d s1 e%d", g.M, g.N, g.K, g.b_kmajor ? 'N' : 'T', 32 * c.ta,
-                  32 * c.tb, g.epi);
-    ProfScope prof(PROF_GEMM, 2.0 * g.M * g.N * g.K, s, label,
-                   4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
-    switch (bi) {
-        case 0: launch_kc<6, 6>(g, grid, s, tiles_n); break;
-        case 1: launch_kc<6, 4>(g, grid, s, tiles_n); break;
-        case 2: launch_kc<6, 2>(g, grid, s, tiles_n); break;
-        default: launch_kc<4, 4>(g, grid, s, tiles_n); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if (bi < 0 || (g_direct != 2 && g.K < 256)) return false;
+    const Tile& c = kKc[bi];
+    p = plan_of(GEMM_KC_DIRECT, bi, 32 * c.ta, 32 * c.tb, g.M / (32 * c.ta), g.N / (32 * c.tb), g);
+    finish(g, 1, 'd', p);
+    return true;
 }
 
-struct KsCfg { int ta, tb; };
-const KsCfg kKs[] = {{4, 4}, {4, 2}, {2, 2}, {6, 4}, {4, 6}};
-
-template <int TA, int TB>
-void launch_ks(const GemmArgs& g, dim3 grid, hipStream_t s, int tiles_n, int tiles) {
-    if (g.a_kmajor) hipLaunchKernelGGL((gemm_ks_kernel<TA, TB, true, true>), grid, dim3(256), 0, s, g, tiles_n, tiles);
-    else if (g.b_kmajor) hipLaunchKernelGGL((gemm_ks_kernel<TA, TB, false, true>), grid, dim3(256), 0, s, g, tiles_n, tiles);
-    else hipLaunchKernelGGL((gemm_ks_kernel<TA, TB, false, false>), grid, dim3(256), 0, s, g, tiles_n, tiles);
+// what the workgroup split-K kernel takes at all (the group kernel too): every layout but k-major A x k-contiguous B
+inline bool ks_takes(const GemmArgs& g) {
+    if (g.a_kmajor && !g.b_kmajor) return false;
+    if (!g.a_kmajor && (g.K & 15)) return false;         // a k-contiguous operand has no zero-returning K tail
+    return g.acc != ACC_ATOMIC && g.K >= 64 && operands_below_2e9(g);
 }
 
 // In-workgroup split-K kernel.  Medium / small products: one workgroup per output tile, the largest tile that still
 // fills the chip.  Long weight-gradient products (k-major x k-major, K = T*B): 96x64 tiles, and when those are fewer than
 // the CUs the k range is also split over the grid (2 ranges for M1536 N512: 1/4 of the atomics of an 8-way split).
-// Returns 1 when the shape does not qualify.
-int launch_gemm_ks(const GemmArgs& gin, hipStream_t s, int force_split) {
-    GemmArgs g = gin;
-    if (g.a_kmajor && !g.b_kmajor) return 1;
-    if (!g.a_kmajor && (g.K & 15)) return 1;             // a k-contiguous operand has no zero-returning K tail
-    if (g.acc == ACC_ATOMIC || g.K < 64) return 1;
-    if ((double)(g.a_kmajor ? g.K : g.M) * g.lda * 4 >= 2.0e9 || (double)(g.b_kmajor ? g.K : g.N) * g.ldb * 4 >= 2.0e9) return 1;
-    const bool nonlinear = g.epi != EPI_NONE;
+bool plan_ks(const GemmArgs& g, int force_split, GemmPlan& p) {
+    if (!ks_takes(g)) return false;
     // rounds of 256 workgroups x MFMAs per workgroup, the smaller tiles charged for their higher L2 traffic per MFMA
     const double kL2[] = {1.0, 1.15, 1.5, 0.95, 0.95};
     int bi = -1, bs = 1;
     double best = 1e300;
     for (int ci = 0; ci < 5; ++ci) {
-        const KsCfg& c = kKs[ci];
+        const Tile& c = kKs[ci];
         if (g.M % (16 * c.ta) || g.N % (16 * c.tb)) continue;
         if (ci == 3 && !(g.a_kmajor && g.K >= 2048)) continue;
         // 64 x 96 tiles (k-contiguous A): products whose 64 x 64 tiling needs two rounds of workgroups and whose 64 x 32 tiling pays
@@ -864,7 +846,7 @@ int launch_gemm_ks(const GemmArgs& gin, hipStream_t s, int force_split) {
         if (ci == 4 && g.a_kmajor) continue;
         const long tiles = (long)(g.M / (16 * c.ta)) * (g.N / (16 * c.tb));
         for (int sp = 1; sp <= 8; sp *= 2) {
-            if (sp > 1 && (!g.a_kmajor || g.K / sp < 1024 || nonlinear)) break;
+            if (sp > 1 && (!g.a_kmajor || g.K / sp < 1024 || nonlinear(g))) break;
             if (force_split > 0 && sp != force_split) continue;
             const long wgs = tiles * sp;
             double cost = (double)((wgs + 255) / 256) * c.ta * c.tb * kL2[ci] / sp;
@@ -872,99 +854,126 @@ int launch_gemm_ks(const GemmArgs& gin, hipStream_t s, int force_split) {
             if (cost < best) { best = cost; bi = ci; bs = sp; }
         }
     }
-    if (bi < 0) return 1;
-    const KsCfg& c = kKs[bi];
+    if (bi < 0) return false;
+    const Tile& c = kKs[bi];
+    p = plan_of(GEMM_KS, bi, 16 * c.ta, 16 * c.tb, g.M / (16 * c.ta), g.N / (16 * c.tb), g);
     // many tiles (several rounds of workgroups that share nothing): the LDS-tiled kernel is the better one there
     // (M12288 N1024 K256: 133 us here, 85 us LDS-tiled)
-    if ((long)(g.M / (16 * c.ta)) * (g.N / (16 * c.tb)) * bs > 1024 && g_direct != 4) return 1;
-    int kps = (g.K + bs - 1) / bs;
-    kps = (kps + 15) / 16 * 16;
-    const int splits = (g.K + kps - 1) / kps;
-    g.k_per_split = kps;
-    if (splits > 1) {
-        if (g.acc == ACC_STORE && pw_zero2d(g.C, g.ldc, g.M, g.N, s) != 0) return -2;
-        g.acc = ACC_ATOMIC;
-    }
-    const int tiles_n = g.N / (16 * c.tb), tiles = tiles_n * (g.M / (16 * c.ta));
-    const dim3 grid(tiles * splits);
-    char label[96];
-    std::snprintf(label, sizeof label, "M%d N%d K%d %c%c k%dx%d s%d e%d", g.M, g.N, g.K, g.a_kmajor ? 'T' : 'N',
-                  g.b_kmajor ? 'N' : 'T', 16 * c.ta, 16 * c.tb, splits, g.epi);
-    ProfScope prof(PROF_GEMM, 2.0 * g.M * g.N * g.K, s, label,
-                   4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
-    switch (bi) {
-        case 0: launch_ks<4, 4>(g, grid, s, tiles_n, tiles); break;
-        case 1: launch_ks<4, 2>(g, grid, s, tiles_n, tiles); break;
-        case 2: launch_ks<2, 2>(g, grid, s, tiles_n, tiles); break;
-        case 4: launch_ks<4, 6>(g, grid, s, tiles_n, tiles); break;
-        default:
-            if (!g.a_kmajor) return 1;
-            hipLaunchKernelGGL((gemm_ks_kernel<6, 4, true, true>), grid, dim3(256), 0, s, g, tiles_n, tiles);
-            break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    if ((long)p.tiles * bs > 1024 && g_direct != 4) return false;
+    split_k(g, bs, 16, p);
+    p.grid = dim3(p.tiles * p.splits);
+    finish(g, 1, 'k', p);
+    return true;
 }
 
-// inet_set_option key 5: 0 = LDS-tiled kernels only, 1 = cost model (default), 2 = the direct kernel whenever it applies
+// LDS-tiled kernel: takes every product.  Tile / split-K selection by a small cost model (microseconds), calibrated on
+// MI355X (profiles/r01_*):
+//  * a workgroup alone on a CU spends ~0.7 us per 32-deep chunk on the load -> LDS -> MFMA dependency, whatever the
+//    tile; co-resident workgroups overlap that latency until the CU's MFMA pipe (tm*tn*0.43 us per chunk) is full;
+//  * the grid runs in ceil(WGs / (256 * residency)) rounds;
+//  * split-K adds a zero-fill, f32 atomics (~6e5 elements/us chip-wide) and, when the epilogue is non-linear, a
+//    second elementwise pass.
+// Constants refitted against tools/gemm_sweep.py (7 shapes x 25 forced tile/split points): the picks are within 3 % of
+// the best forced configuration on every swept shape.
+// Big shapes (M or K = T*B = 6144) end up on 192-wide tiles with exactly 256 workgroups; small ones on 64x64
+// tiles split until every CU holds several workgroups.
+void plan_tiled(const GemmArgs& g, GemmPlan& p) {
+    const bool may_split = !(nonlinear(g) && g.acc != ACC_STORE);
+    int bi = 0, bs = 1;
+    if (g_force_cfg >= 0 && g_force_cfg < kNumCfgs) {
+        bi = g_force_cfg;
+        bs = may_split && g_force_split > 0 ? g_force_split : 1;
+    } else {
+        const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
+        double best = 1e300;
+        for (int ci = 0; ci < kNumCfgs; ++ci) {
+            const TileCfg& c = kCfgs[ci];
+            const long tiles = (long)((g.M + 64 * c.tm - 1) / (64 * c.tm)) * ((g.N + 64 * c.tn - 1) / (64 * c.tn));
+            for (int sp : kSplits) {
+                if (sp > 1 && (g.K / sp < 128 || !may_split)) break;
+                const long wgs = tiles * sp;
+                const long slots = 256L * c.wgs_per_cu;
+                const long rounds = (wgs + slots - 1) / slots;
+                const double conc = (double)(wgs < slots ? (wgs + 255) / 256 : c.wgs_per_cu);
+                const double chunks = (double)(((g.K + sp - 1) / sp + 31) / 32);
+                const double t_mfma = c.tm * c.tn * 0.4267 / c.eff;
+                const double lat = 0.7 + 0.1 * (c.tm + c.tn - 2);
+                double cost = rounds * ((chunks * lat > conc * chunks * t_mfma ? chunks * lat : conc * chunks * t_mfma) + 1.5);
+                if (sp > 1) cost += 2.0 + (double)g.M * g.N * sp / 6.0e5 + (nonlinear(g) ? 3.0 : 0.0);
+                if (cost < best) { best = cost; bi = ci; bs = sp; }
+            }
+        }
+    }
+    const int BM = 64 * kCfgs[bi].tm, BN = 64 * kCfgs[bi].tn;
+    p = plan_of(GEMM_TILED, bi, BM, BN, (g.M + BM - 1) / BM, (g.N + BN - 1) / BN, g);
+    split_k(g, bs, 32, p);
+    p.grid = dim3(p.tiles_n, p.tiles / p.tiles_n, p.splits);
+    finish(g, 1, 't', p);
+}
+
+}  // namespace
+
+void gemm_set_force_cfg(int cfg) { g_force_cfg = cfg; }
+void gemm_set_force_split(int split) { g_force_split = split; }
 void gemm_set_direct(int mode) { g_direct = mode; }
 
-template <int TA, int TB>
-void launch_ks_group(const GemmGroupArgs& a, bool akm, bool bkm, dim3 grid, hipStream_t s) {
-    if (akm) hipLaunchKernelGGL((gemm_ks_group_kernel<TA, TB, true, true>), grid, dim3(256), 0, s, a);
-    else if (bkm) hipLaunchKernelGGL((gemm_ks_group_kernel<TA, TB, false, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gemm_ks_group_kernel<TA, TB, false, false>), grid, dim3(256), 0, s, a);
+// The ladder, once.  Few rows: gemv.  A forced tile configuration (key 2) or key 5 = 0: LDS-tiled.  Else per key-5 mode, for a
+// k-major A (weight gradients) | a k-contiguous A (forward, data gradients), each ending on LDS-tiled:
+//   1, 2  TN-direct, ks | kc-direct, ks     (2: the direct kernels without their size thresholds)
+//   3     TN-direct     | kc-direct
+//   4     ks, TN-direct | kc-direct, ks
+// The long weight-gradient products go to the shared-strip direct kernel first: workgroup split-K with 96x64 tiles (mode 4
+// tries it first) is 8-15 % faster alone (no zero-fill, 1/4 of the atomics) but 1 % slower in the training step, where its
+// doubled L2 traffic competes with the BPTT chain on the other stream.
+GemmPlan gemm_plan(const GemmArgs& g) {
+    GemmPlan p{};
+    const bool direct = g_direct > 0 && g_force_cfg < 0;
+    const int fs = g_force_split;
+    if (g.nbatch > 1) {
+        // several products of one shape: one launch of the shared-strip direct kernel when it applies (half the split-K
+        // factor of a single product for the same 256 workgroups), else one product after the other
+        if (!(direct && g_direct != 4 && plan_tn_direct(g, fs, p))) { p = GemmPlan{}; p.family = GEMM_EACH; }
+        return p;
+    }
+    if (plan_gemv(g, p)) return p;
+    if (direct && g.a_kmajor) {
+        if (g_direct == 4 && plan_ks(g, fs, p)) return p;
+        if (plan_tn_direct(g, fs, p)) return p;
+        if (g_direct != 3 && g_direct != 4 && plan_ks(g, fs, p)) return p;
+    } else if (direct) {
+        if (plan_kc_direct(g, p) || (g_direct != 3 && plan_ks(g, fs, p))) return p;
+    }
+    plan_tiled(g, p);
+    return p;
 }
 
-// Independent products in ONE launch of the workgroup split-K kernel when all of them have the same operand layout and a
-// common tile shape divides them; else one launch each.
-int launch_gemm_group(const GemmArgs* list, int n, hipStream_t s) {
-    {   // a group of few-row products of one M (the beat -> tick projections of a b = 1 decode call): one launch of the wave-per-column kernel
-        bool gv = n >= 2 && n <= kGemmGroupMax && g_force_cfg < 0 && list[0].M >= 1 && list[0].M <= 8;
-        int maxN = 0;
-        double flops = 0, bytes = 0;
-        for (int i = 0; i < n && gv; ++i) {
-            const GemmArgs& g = list[i];
-            gv = g.M == list[0].M && g.N > 0 && g.K > 0 && !g.a_kmajor && !g.b_kmajor && g.nbatch <= 1 && g.acc != ACC_ATOMIC;
-            maxN = g.N > maxN ? g.N : maxN;
-            flops += 2.0 * g.M * g.N * g.K; bytes += 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N);
-        }
-        if (gv) {
-            GemmGroupArgs a{};
-            a.n = n;
-            for (int i = 0; i < n; ++i) {
-                if (list[i].acc == ACC_ADD && side_is(s) && side_order_dest(list[i].C, s) != 0) return -2;
-                a.g[i] = list[i];
-            }
-            char label[64];
-            std::snprintf(label, sizeof label, "group%d M%d N%d K%d NT gemv e%d", n, list[0].M, list[0].N, list[0].K, list[0].epi);
-            ProfScope prof(PROF_GEMM, flops, s, label, bytes);
-            const dim3 grid((maxN + 3) / 4, n);
-            switch (list[0].M) {
-                case 1: hipLaunchKernelGGL(gemv_rows_group_kernel<1>, grid, dim3(256), 0, s, a); break;
-                case 2: hipLaunchKernelGGL(gemv_rows_group_kernel<2>, grid, dim3(256), 0, s, a); break;
-                case 3: hipLaunchKernelGGL(gemv_rows_group_kernel<3>, grid, dim3(256), 0, s, a); break;
-                case 4: hipLaunchKernelGGL(gemv_rows_group_kernel<4>, grid, dim3(256), 0, s, a); break;
-                case 5: hipLaunchKernelGGL(gemv_rows_group_kernel<5>, grid, dim3(256), 0, s, a); break;
-                case 6: hipLaunchKernelGGL(gemv_rows_group_kernel<6>, grid, dim3(256), 0, s, a); break;
-                case 7: hipLaunchKernelGGL(gemv_rows_group_kernel<7>, grid, dim3(256), 0, s, a); break;
-                default: hipLaunchKernelGGL(gemv_rows_group_kernel<8>, grid, dim3(256), 0, s, a); break;
-            }
-            return hipGetLastError() == hipSuccess ? 0 : -2;
-        }
-    }
-    bool ok = n >= 2 && n <= kGemmGroupMax && g_direct > 0 && g_direct != 3 && g_force_cfg < 0;
-    for (int i = 0; i < n && ok; ++i) {
+// Independent products in ONE launch: the wave-per-column kernel for few-row products of one M (the beat -> tick projections of
+// a b = 1 decode call), the workgroup split-K kernel when all of them have the same operand layout and a common tile shape
+// divides them; else one launch each (GEMM_EACH).
+GemmPlan gemm_group_plan(const GemmArgs* list, int n) {
+    GemmPlan p{};
+    p.family = GEMM_EACH;
+    if (n < 2 || n > kGemmGroupMax || g_force_cfg >= 0) return p;
+    const GemmArgs& g0 = list[0];
+    bool gv = g0.M >= 1 && g0.M <= 8, ks = g_direct > 0 && g_direct != 3;
+    int maxN = 0;
+    for (int i = 0; i < n; ++i) {
         const GemmArgs& g = list[i];
-        ok = g.M > 0 && g.N > 0 && g.K >= 64 && g.nbatch <= 1 && g.acc != ACC_ATOMIC && !(g.a_kmajor && !g.b_kmajor) &&
-             (g.a_kmajor || (g.K & 15) == 0) && g.a_kmajor == list[0].a_kmajor && g.b_kmajor == list[0].b_kmajor &&
-             (double)(g.a_kmajor ? g.K : g.M) * g.lda * 4 < 2.0e9 && (double)(g.b_kmajor ? g.K : g.N) * g.ldb * 4 < 2.0e9;
+        const bool one = g.M > 0 && g.N > 0 && g.nbatch <= 1 && g.acc != ACC_ATOMIC;
+        gv = gv && one && g.M == g0.M && g.K > 0 && !g.a_kmajor && !g.b_kmajor;
+        ks = ks && one && ks_takes(g) && g.a_kmajor == g0.a_kmajor && g.b_kmajor == g0.b_kmajor;
+        maxN = g.N > maxN ? g.N : maxN;
     }
-    int bi = -1;
-    long total = 0;
-    if (ok) {
+    if (gv) {
+        p = plan_of(GEMM_GEMV, g0.M - 1, g0.M, 4, 1, (maxN + 3) / 4, g0);
+        p.grid = dim3(p.tiles, n);
+        std::snprintf(p.label, sizeof p.label, "group%d M%d N%d K%d NT gemv e%d", n, g0.M, g0.N, g0.K, g0.epi);
+    } else if (ks) {
         // the largest tile that divides every product and still gives the launch >= 192 workgroups; else the smallest that divides
+        int bi = -1;
+        long total = 0;
         for (int ci = 0; ci < 3; ++ci) {
-            const KsCfg& c = kKs[ci];
+            const Tile& c = kKs[ci];
             bool div = true;
             long wgs = 0;
             for (int i = 0; i < n; ++i) {
@@ -975,171 +984,122 @@ int launch_gemm_group(const GemmArgs* list, int n, hipStream_t s) {
             bi = ci; total = wgs;
             if (wgs >= 192) break;
         }
-        if (bi < 0 || total > 2048) ok = false;
-    }
-    if (!ok) {
-        for (int i = 0; i < n; ++i) { const int rc = launch_gemm(list[i], s); if (rc != 0) return rc; }
-        return 0;
-    }
-    const KsCfg& c = kKs[bi];
-    GemmGroupArgs a{};
-    a.n = n;
-    double flops = 0, bytes = 0;
-    for (int i = 0; i < n; ++i) {
-        GemmArgs g = list[i];
-        if (g.acc == ACC_ADD && side_is(s) && side_order_dest(g.C, s) != 0) return -2;
-        g.k_per_split = (g.K + 15) / 16 * 16;
-        a.g[i] = g;
-        a.tiles_n[i] = g.N / (16 * c.tb);
-        a.first[i + 1] = a.first[i] + a.tiles_n[i] * (g.M / (16 * c.ta));
-        flops += 2.0 * g.M * g.N * g.K;
-        bytes += 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N);
-    }
-    char label[96];
-    std::snprintf(label, sizeof label, "group%d M%d N%d K%d %c%c k%dx%d e%d", n, list[0].M, list[0].N, list[0].K,
-                  list[0].a_kmajor ? 'T' : 'N', list[0].b_kmajor ? 'N' : 'T', 16 * c.ta, 16 * c.tb, list[0].epi);
-    ProfScope prof(PROF_GEMM, flops, s, label, bytes);
-    const dim3 grid(a.first[n]);
-    const bool akm = list[0].a_kmajor, bkm = list[0].b_kmajor;
-    switch (bi) {
-        case 0: launch_ks_group<4, 4>(a, akm, bkm, grid, s); break;
-        case 1: launch_ks_group<4, 2>(a, akm, bkm, grid, s); break;
-        default: launch_ks_group<2, 2>(a, akm, bkm, grid, s); break;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+        if (bi < 0 || total > 2048) return p;
+        p = plan_of(GEMM_KS, bi, 16 * kKs[bi].ta, 16 * kKs[bi].tb, 1, (int)total, g0);
+        p.tiles_n = 0;                                       // (per product: GemmGroupArgs)
+        std::snprintf(p.label, sizeof p.label, "group%d M%d N%d K%d %s k%dx%d e%d", n, g0.M, g0.N, g0.K, layout_name(g0), p.tile_m,
+                      p.tile_n, g0.epi);
+    } else return p;
+    for (int i = 0; i < n; ++i) add_work(list[i], 1, p);
+    return p;
 }
 
-// Tile / split-K selection by a small cost model (microseconds), calibrated on MI355X (profiles/r01_*):
-//  * a workgroup alone on a CU spends ~0.7 us per 32-deep chunk on the load -> LDS -> MFMA dependency, whatever the
-//    tile; co-resident workgroups overlap that latency until the CU's MFMA pipe (tm*tn*0.43 us per chunk) is full;
-//  * the grid runs in ceil(WGs / (256 * residency)) rounds;
-//  * split-K adds a zero-fill, f32 atomics (~6e5 elements/us chip-wide) and, when the epilogue is non-linear, a
-//    second elementwise pass.
-// Constants refitted against tools/gemm_sweep.py (7 shapes x 25 forced tile/split points): the picks are within 3 % of
-// the best forced configuration on every swept shape.
-// Big shapes (M or K = T*B = 6144) end up on 192-wide tiles with exactly 256 workgroups; small ones on 64x64
-// tiles split until every CU holds several workgroups.
-int launch_gemm(const GemmArgs& gin, hipStream_t s) {
+// ---- Launching a plan: the only part that sees a stream. ----
+namespace {
+
+inline int launched() { return hipGetLastError() == hipSuccess ? 0 : -2; }
+
+// The kernels behind the tile tables, per operand layout 2 * (a k-major) + (b k-major); null: not built, no planner asks for it.
+typedef void (*Kernel1)(GemmArgs);
+typedef void (*Kernel2)(GemmArgs, int);
+typedef void (*Kernel3)(GemmArgs, int, int);
+typedef void (*KernelG)(GemmGroupArgs);
+#define ROWS8(k) {k<1>, k<2>, k<3>, k<4>, k<5>, k<6>, k<7>, k<8>}
+#define LAYOUTS4(k, a, b) {k<a, b, false, false>, k<a, b, false, true>, k<a, b, true, false>, k<a, b, true, true>}
+#define LAYOUTS3(k, a, b) {k<a, b, false, false>, k<a, b, false, true>, nullptr, k<a, b, true, true>}
+const Kernel1 kGemvKernel[8] = ROWS8(gemv_rows_kernel);
+const KernelG kGemvGroupKernel[8] = ROWS8(gemv_rows_group_kernel);
+const Kernel1 kTiledKernel[kNumCfgs][4] = {LAYOUTS4(gemm_kernel, 1, 1), LAYOUTS4(gemm_kernel, 2, 2), LAYOUTS4(gemm_kernel, 3, 1),
+                                           LAYOUTS4(gemm_kernel, 3, 2), LAYOUTS4(gemm_kernel, 3, 3)};
+const Kernel3 kTnDirectKernel[3] = {gemm_tn_direct_kernel<3, 2>, gemm_tn_direct_kernel<2, 2>, gemm_tn_direct_kernel<3, 3>};
+const Kernel2 kKcKernel[4][2] = {{gemm_kc_direct_kernel<6, 6, false>, gemm_kc_direct_kernel<6, 6, true>},
+                                 {gemm_kc_direct_kernel<6, 4, false>, gemm_kc_direct_kernel<6, 4, true>},
+                                 {gemm_kc_direct_kernel<6, 2, false>, gemm_kc_direct_kernel<6, 2, true>},
+                                 {gemm_kc_direct_kernel<4, 4, false>, gemm_kc_direct_kernel<4, 4, true>}};
+const Kernel3 kKsKernel[5][4] = {LAYOUTS3(gemm_ks_kernel, 4, 4), LAYOUTS3(gemm_ks_kernel, 4, 2), LAYOUTS3(gemm_ks_kernel, 2, 2),
+                                 {nullptr, nullptr, nullptr, gemm_ks_kernel<6, 4, true, true>}, LAYOUTS3(gemm_ks_kernel, 4, 6)};
+const KernelG kKsGroupKernel[3][4] = {LAYOUTS3(gemm_ks_group_kernel, 4, 4), LAYOUTS3(gemm_ks_group_kernel, 4, 2),
+                                      LAYOUTS3(gemm_ks_group_kernel, 2, 2)};
+#undef ROWS8
+#undef LAYOUTS4
+#undef LAYOUTS3
+inline int layout_of(const GemmArgs& g) { return (g.a_kmajor ? 2 : 0) + (g.b_kmajor ? 1 : 0); }
+
+// One product as planned: zero fill, the kernel's view of the arguments, the launch and the epilogue pass under one ProfScope.
+int run(const GemmPlan& p, const GemmArgs& gin, hipStream_t s) {
+    GemmArgs g = gin;
+    if (p.zero_fill && pw_zero2d(g.C, g.ldc, g.M, g.N, s) != 0) return -2;
+    g.k_per_split = p.k_per_split;
+    if (p.splits > 1) g.acc = ACC_ATOMIC;
+    if (p.two_pass) g.epi = EPI_NONE;
+    ProfScope prof(PROF_GEMM, p.flops, s, p.label, p.bytes);
+    const int lay = layout_of(g);
+    // Leaf GEMMs on the side stream: 64x64 tiles would sit 4 to a CU and take 147 of its 160 KB of LDS, so a BPTT
+    // step kernel arriving on the main stream (16-32 KB) has to wait for one of them to retire.  A few KB of unused
+    // dynamic LDS caps them at 3 per CU and leaves the step kernels room to co-reside (5.22 -> 5.18 ms per step;
+    // capping at 2 per CU costs the GEMMs more than it gives: 5.40).
+    const unsigned pad = (p.family == GEMM_TILED && p.cfg == 0 && side_is(s)) ? 4608u : 0u;
+    switch (p.family) {
+        case GEMM_GEMV: hipLaunchKernelGGL(kGemvKernel[p.cfg], p.grid, dim3(256), 0, s, g); break;
+        case GEMM_TN_DIRECT: hipLaunchKernelGGL(kTnDirectKernel[p.cfg], p.grid, dim3(256), 0, s, g, p.tiles_n, p.tiles); break;
+        case GEMM_KC_DIRECT: hipLaunchKernelGGL(kKcKernel[p.cfg][lay], p.grid, dim3(256), 0, s, g, p.tiles_n); break;
+        case GEMM_KS: hipLaunchKernelGGL(kKsKernel[p.cfg][lay], p.grid, dim3(256), 0, s, g, p.tiles_n, p.tiles); break;
+        default: hipLaunchKernelGGL(kTiledKernel[p.cfg][lay], p.grid, dim3(256), pad, s, g); break;
+    }
+    int rc = launched();
+    if (rc == 0 && p.two_pass) {
+        const long n = (long)g.M * g.N;
+        const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+        hipLaunchKernelGGL(gemm_epilogue_kernel, dim3(blocks), dim3(256), 0, s, g.C, g.ldc, g.M, g.N, gin.aux, gin.ldaux, gin.epi);
+        rc = launched();
+    }
+    return rc;
+}
+
+}  // namespace
+
+int launch_gemm(const GemmArgs& g, hipStream_t s) {
     // Accumulations issued on the rotating side streams (leaf weight gradients): when a module is applied more than once per
     // step (a per-tick free-running pass) two of them may target the same tensor from different streams -- the second one is
     // ordered behind the first (side.hip side_order_dest; no cost when every tensor has one writer per step).
-    if (gin.acc == ACC_ADD && side_is(s)) {
-        for (int i = 0; i < (gin.nbatch > 1 ? gin.nbatch : 1); ++i)
-            if (side_order_dest(gin.C + i * gin.batchC, s) != 0) return -2;
+    if (g.acc == ACC_ADD && side_is(s)) {
+        for (int i = 0; i < (g.nbatch > 1 ? g.nbatch : 1); ++i)
+            if (side_order_dest(g.C + i * g.batchC, s) != 0) return -2;
     }
-    GemmArgs g = gin;
     if (g.M <= 0 || g.N <= 0) return 0;
     if (g.K <= 0) return -1;
-    if (g_force_cfg == -2) g_force_cfg = -1;
-    if (g.nbatch > 1) {
-        // several products of one shape: one launch of the shared-strip direct kernel when it applies (half the split-K
-        // factor of a single product for the same 256 workgroups), else one product after the other
-        int rc = 1;
-        if (g_direct > 0 && g_direct != 4 && g_force_cfg < 0) rc = launch_gemm_direct(gin, s, g_force_split > 0 ? g_force_split : 0);
-        if (rc != 1) return rc;
-        for (int i = 0; i < gin.nbatch; ++i) {
-            GemmArgs one = gin;
-            one.nbatch = 0;
-            one.A += i * gin.batchA; one.B += i * gin.batchB; one.C += i * gin.batchC;
-            if ((rc = launch_gemm(one, s)) != 0) return rc;
-        }
+    const GemmPlan p = gemm_plan(g);
+    if (p.family != GEMM_EACH) return run(p, g, s);
+    for (int i = 0; i < g.nbatch; ++i) {
+        GemmArgs one = g;
+        one.nbatch = 0;
+        one.A += i * g.batchA; one.B += i * g.batchB; one.C += i * g.batchC;
+        const int rc = launch_gemm(one, s);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
+int launch_gemm_group(const GemmArgs* list, int n, hipStream_t s) {
+    const GemmPlan p = gemm_group_plan(list, n);
+    if (p.family == GEMM_EACH) {
+        for (int i = 0; i < n; ++i) { const int rc = launch_gemm(list[i], s); if (rc != 0) return rc; }
         return 0;
     }
-    if (g.M <= 8 && !g.a_kmajor && !g.b_kmajor && g.nbatch <= 1 && g_force_cfg < 0 && g.acc != ACC_ATOMIC) {
-        char label[64];
-        std::snprintf(label, sizeof label, "M%d N%d K%d NT gemv e%d", g.M, g.N, g.K, g.epi);
-        ProfScope prof(PROF_GEMM, 2.0 * g.M * g.N * g.K, s, label, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
-        const dim3 grid((g.N + 3) / 4);
-        switch (g.M) {
-            case 1: hipLaunchKernelGGL(gemv_rows_kernel<1>, grid, dim3(256), 0, s, g); break;
-            case 2: hipLaunchKernelGGL(gemv_rows_kernel<2>, grid, dim3(256), 0, s, g); break;
-            case 3: hipLaunchKernelGGL(gemv_rows_kernel<3>, grid, dim3(256), 0, s, g); break;
-            case 4: hipLaunchKernelGGL(gemv_rows_kernel<4>, grid, dim3(256), 0, s, g); break;
-            case 5: hipLaunchKernelGGL(gemv_rows_kernel<5>, grid, dim3(256), 0, s, g); break;
-            case 6: hipLaunchKernelGGL(gemv_rows_kernel<6>, grid, dim3(256), 0, s, g); break;
-            case 7: hipLaunchKernelGGL(gemv_rows_kernel<7>, grid, dim3(256), 0, s, g); break;
-            default: hipLaunchKernelGGL(gemv_rows_kernel<8>, grid, dim3(256), 0, s, g); break;
+    GemmGroupArgs a{};
+    a.n = n;
+    for (int i = 0; i < n; ++i) {
+        GemmArgs g = list[i];
+        if (g.acc == ACC_ADD && side_is(s) && side_order_dest(g.C, s) != 0) return -2;
+        if (p.family == GEMM_KS) {
+            g.k_per_split = (g.K + 15) / 16 * 16;
+            a.tiles_n[i] = g.N / p.tile_n;
+            a.first[i + 1] = a.first[i] + a.tiles_n[i] * (g.M / p.tile_m);
         }
-        return hipGetLastError() == hipSuccess ? 0 : -2;
+        a.g[i] = g;
     }
-    const int force_cfg = g_force_cfg, force_split = g_force_split;
-    const int kSplits[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
-    const bool nonlinear = g.epi != EPI_NONE;
-    double best = 1e300;
-    int bi = 0, bs = 1;
-    for (int ci = 0; ci < kNumCfgs; ++ci) {
-        const TileCfg& c = kCfgs[ci];
-        const long tiles = (long)((g.M + 64 * c.tm - 1) / (64 * c.tm)) * ((g.N + 64 * c.tn - 1) / (64 * c.tn));
-        for (int sp : kSplits) {
-            if (sp > 1 && (g.K / sp < 128 || (nonlinear && g.acc != ACC_STORE))) break;
-            const long wgs = tiles * sp;
-            const long slots = 256L * c.wgs_per_cu;
-            const long rounds = (wgs + slots - 1) / slots;
-            const double conc = (double)(wgs < slots ? (wgs + 255) / 256 : c.wgs_per_cu);
-            const double chunks = (double)(((g.K + sp - 1) / sp + 31) / 32);
-            const double t_mfma = c.tm * c.tn * 0.4267 / c.eff;
-            const double lat = 0.7 + 0.1 * (c.tm + c.tn - 2);
-            double cost = rounds * ((chunks * lat > conc * chunks * t_mfma ? chunks * lat : conc * chunks * t_mfma) + 1.5);
-            if (sp > 1) cost += 2.0 + (double)g.M * g.N * sp / 6.0e5 + (nonlinear ? 3.0 : 0.0);
-            if (cost < best) { best = cost; bi = ci; bs = sp; }
-        }
-    }
-    if (g_direct > 0 && force_cfg < 0) {
-        // The long weight-gradient products go to the shared-strip direct kernel first.  Workgroup split-K with 96x64 tiles
-        // (g_direct = 4 tries it first) is 8-15 % faster alone (no zero-fill, 1/4 of the atomics) but 1 % slower
-        // in the training step, where its doubled L2 traffic competes with the BPTT chain on the other stream.
-        int rc = 1;
-        if (gin.a_kmajor && g_direct != 4) rc = launch_gemm_direct(gin, s, force_split);
-        else if (!gin.a_kmajor) rc = launch_gemm_kc_direct(gin, s);
-        if (rc == 1 && g_direct != 3) rc = launch_gemm_ks(gin, s, force_split);
-        if (rc == 1 && gin.a_kmajor) rc = launch_gemm_direct(gin, s, force_split);
-        if (rc != 1) return rc;
-    }
-    if (force_cfg >= 0 && force_cfg < kNumCfgs) {
-        bi = force_cfg;
-        bs = (nonlinear && g.acc != ACC_STORE) ? 1 : (force_split > 0 ? force_split : 1);
-    }
-    const TileCfg& c = kCfgs[bi];
-    const int BM = 64 * c.tm, BN = 64 * c.tn;
-    int splits = bs;
-    int kps = (g.K + splits - 1) / splits;
-    kps = (kps + 31) / 32 * 32;
-    splits = (g.K + kps - 1) / kps;
-    g.k_per_split = kps;
-    const bool two_pass = splits > 1 && nonlinear;
-    if (splits > 1) {
-        if (g.acc == ACC_STORE) {
-            if (pw_zero2d(g.C, g.ldc, g.M, g.N, s) != 0) return -2;
-        }
-        g.acc = ACC_ATOMIC;
-        if (two_pass) g.epi = EPI_NONE;
-    }
-    dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, splits);
-    char label[96];
-    std::snprintf(label, sizeof label, "M%d N%d K%d %c%c t%dx%d s%d e%d", g.M, g.N, g.K, g.a_kmajor ? 'T' : 'N',
-                  g.b_kmajor ? 'N' : 'T', 64 * c.tm, 64 * c.tn, splits, gin.epi);
-    int rc;
-    {
-        ProfScope prof(PROF_GEMM, 2.0 * g.M * g.N * g.K, s, label, 4.0 * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N));
-        // Leaf GEMMs on the side stream: 64x64 tiles would sit 4 to a CU and take 147 of its 160 KB of LDS, so a BPTT
-        // step kernel arriving on the main stream (16-32 KB) has to wait for one of them to retire.  A few KB of unused
-        // dynamic LDS caps them at 3 per CU and leaves the step kernels room to co-reside (5.22 -> 5.18 ms per step;
-        // capping at 2 per CU costs the GEMMs more than it gives: 5.40).
-        const unsigned pad = (bi == 0 && side_is(s)) ? 4608u : 0u;
-        switch (bi) {
-            case 0: rc = launch_cfg<1, 1>(g, grid, s, pad); break;
-            case 1: rc = launch_cfg<2, 2>(g, grid, s, 0); break;
-            case 2: rc = launch_cfg<3, 1>(g, grid, s, 0); break;
-            case 3: rc = launch_cfg<3, 2>(g, grid, s, 0); break;
-            default: rc = launch_cfg<3, 3>(g, grid, s, 0); break;
-        }
-        if (rc == 0 && two_pass) {
-            long n = (long)g.M * g.N;
-            int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
-            hipLaunchKernelGGL(gemm_epilogue_kernel, dim3(blocks), dim3(256), 0, s, g.C, g.ldc, g.M, g.N, gin.aux,
-                               gin.ldaux, gin.epi);
-            rc = hipGetLastError() == hipSuccess ? 0 : -2;
-        }
-    }
-    return rc;
+    ProfScope prof(PROF_GEMM, p.flops, s, p.label, p.bytes);
+    if (p.family == GEMM_GEMV) hipLaunchKernelGGL(kGemvGroupKernel[p.cfg], p.grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(kKsGroupKernel[p.cfg][layout_of(list[0])], p.grid, dim3(256), 0, s, a);
+    return launched();
 }

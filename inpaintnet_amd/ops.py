@@ -397,7 +397,8 @@ def prof_enable(on):
 
 def set_option(key, value):
     """inet_set_option (include/inpaintnet_hip.h): 0 side stream, 1 deferred joins, 2 GEMM tile force, 3 GEMM split force, 4 chain kernels,
-    5 direct k-major GEMM (0 never / 1 cost model / 2 always)."""
+    5 LDS-free GEMM kernels (0 never / 1 by shape / 2 whenever the shape qualifies / 3 direct kernels only, no workgroup split-K / 4
+    workgroup split-K first)."""
     check(_lib.lib().inet_set_option(int(key), int(value)), "inet_set_option")
 
 
@@ -428,6 +429,22 @@ def gemm(A, B, M, N, K, a_kmajor=False, b_kmajor=False, bias=None, epi=0, aux=No
                                out.stride(0), M, N, K, ptr(bias), ptr(aux), aux.stride(0) if aux is not None else 0,
                                int(epi), int(accumulate), stream_ptr()), "inet_gemm")
     return out
+
+
+GEMM_PLAN_KEYS = ("family", "cfg", "tile_m", "tile_n", "splits", "k_per_split", "tiles_n", "tiles", "grid_x", "grid_y", "grid_z",
+                  "zero_fill", "two_pass", "launches", "products")
+GEMM_FAMILIES = ("gemv", "tn_direct", "kc_direct", "ks", "tiled")
+
+
+def gemm_plan(M, N, K, a_kmajor=False, b_kmajor=False, lda=None, ldb=None, bias=False, epi=0, accumulate=False, nbatch=1):
+    """What gemm() (nbatch = 1) or gemm_batched() launches for a call under the options set now, without a GPU (inet_gemm_plan): a dict
+    of GEMM_PLAN_KEYS plus "flops", "bytes" and "label" -- the launch's name in a prof_dump()."""
+    out, work, label = (C.c_int32 * 16)(), (C.c_double * 2)(), C.create_string_buffer(96)
+    lda = (M if a_kmajor else K) if lda is None else lda
+    ldb = (N if b_kmajor else K) if ldb is None else ldb
+    check(_lib.lib().inet_gemm_plan(int(a_kmajor), int(b_kmajor), M, N, K, lda, ldb, int(bool(bias)), int(epi), int(accumulate), int(nbatch),
+                                    out, work, label, 96), "inet_gemm_plan")
+    return dict(zip(GEMM_PLAN_KEYS, list(out)), flops=work[0], bytes=work[1], label=label.value.decode())
 
 
 def epoch_stats_add(sums, loss, accuracy=None, step_flag=None):

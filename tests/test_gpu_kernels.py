@@ -27,6 +27,21 @@ def relmax(a, b):
     return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
+def dumped_labels(path):
+    """The labels of a prof_dump, launch by launch."""
+    return [line.split(",")[1] for line in open(str(path)).read().strip().splitlines()[1:]]
+
+
+@pytest.fixture
+def default_gemm_options():
+    """Whatever the test does with option 5 and the profiler, the next test finds the defaults."""
+    try:
+        yield
+    finally:
+        ops.set_option(5, 1)
+        ops.prof_enable(False)
+
+
 def pack(table, total, P, prefix=""):
     flat = torch.zeros(total, dtype=torch.float32)
     for name, off, shape in table:
@@ -81,7 +96,9 @@ def test_gemv_rows(M, N, K, tmp_path):
         ops.prof_dump(str(tmp_path / "_inet_gemv.csv"))
     finally:
         ops.prof_enable(False)
-    assert "gemv" in open(str(tmp_path / "_inet_gemv.csv")).read().strip().splitlines()[-1].split(",")[1]
+    plan = ops.gemm_plan(M, N, K)
+    assert plan["family"] == ops.GEMM_FAMILIES.index("gemv") and "gemv" in plan["label"]
+    assert dumped_labels(tmp_path / "_inet_gemv.csv") == [plan["label"]]      # the launch followed the plan
     assert relmax(C, ref) < 2e-5
     assert relmax(ops.gemm(Ad, Bd, M, N, K, bias=bias.to(DEV), epi=1), O.selu(ref + bias.double())) < 2e-5
     assert relmax(ops.gemm(Ad, Bd, M, N, K, bias=bias.to(DEV), epi=2), torch.relu(ref + bias.double())) < 2e-5
@@ -226,7 +243,9 @@ def test_gemm_direct_kmajor_products(M, N, K, tmp_path):
         torch.cuda.synchronize()
         ops.prof_dump(str(tmp_path / "_inet_direct.csv"))
         ops.prof_enable(False)
-        assert " d" in open(str(tmp_path / "_inet_direct.csv")).read().strip().splitlines()[-1].split(",")[1]
+        plan = ops.gemm_plan(M, N, K, a_kmajor=True, b_kmajor=True)
+        assert plan["family"] == ops.GEMM_FAMILIES.index("tn_direct") and " d" in plan["label"]
+        assert dumped_labels(tmp_path / "_inet_direct.csv") == [plan["label"]]  # the launch followed the plan
         assert relmax(C, ref) < 2e-5
         C0 = torch.randn(M, N, generator=g)
         C1 = C0.to(DEV).clone()
@@ -264,8 +283,9 @@ def test_gemm_batched_weight_gradients(M, N, K, nb, label, tmp_path):
     finally:
         ops.prof_enable(False)
     assert relmax(Cd, ref) < 2e-5
-    if label:
-        assert open(str(tmp_path / "_inet_batched.csv")).read().strip().splitlines()[-1].split(",")[1].endswith(label)
+    plan = ops.gemm_plan(M, N, K, a_kmajor=True, b_kmajor=True, lda=nb * M, accumulate=True, nbatch=nb)
+    assert not label or (plan["products"] == 1 and plan["label"].endswith(label))      # one launch of the batched kernel
+    assert dumped_labels(tmp_path / "_inet_batched.csv") == [plan["label"]] * plan["products"]   # the launches followed the plan
     # a negative stride: the same problems listed backwards
     Cd2 = C0.to(DEV).clone()
     ops.gemm_batched(Ad[:, (nb - 1) * M:], Bd[nb - 1], Cd2[nb - 1], M, N, K, nb, -M, -K * N, -M * N)
@@ -317,7 +337,9 @@ def test_gemm_direct_kcontiguous_products(M, N, K, bkm, tmp_path):
         torch.cuda.synchronize()
         ops.prof_dump(str(tmp_path / "_inet_direct.csv"))
         ops.prof_enable(False)
-        assert " d" in open(str(tmp_path / "_inet_direct.csv")).read().strip().splitlines()[-1].split(",")[1]
+        plan = ops.gemm_plan(M, N, K, b_kmajor=bool(bkm))
+        assert plan["family"] == ops.GEMM_FAMILIES.index("kc_direct") and " d" in plan["label"]
+        assert dumped_labels(tmp_path / "_inet_direct.csv") == [plan["label"]]  # the launch followed the plan
         assert relmax(C, ref) < 2e-5
         C0 = torch.randn(M, N, generator=g)
         C1 = C0.to(DEV).clone()
@@ -340,7 +362,7 @@ def test_gemm_direct_kcontiguous_products(M, N, K, bkm, tmp_path):
 @pytest.mark.parametrize("M,N,K", [(256, 1024, 2048), (1536, 512, 1024), (1024, 2048, 256), (256, 256, 1024),
                                    (64, 32, 64), (32, 32, 1008), (128, 96, 336),
                                    (1536, 512, 6144), (1536, 1024, 6144), (192, 128, 2064)])   # TN: 96x64 tiles (+ grid split)
-def test_gemm_workgroup_split_k(akm, bkm, M, N, K, tmp_path):
+def test_gemm_workgroup_split_k(akm, bkm, M, N, K, tmp_path, default_gemm_options):
     """The in-workgroup split-K kernel (csrc/gemm.hip gemm_ks_kernel) on the medium / small shapes of the step, every
     operand layout it takes: plain, accumulating, bias + SELU, aux epilogues, strided destination; for k-major
     operands also a K that is not a multiple of the 16-deep group."""
@@ -361,8 +383,10 @@ def test_gemm_workgroup_split_k(akm, bkm, M, N, K, tmp_path):
         torch.cuda.synchronize()
         ops.prof_dump(str(tmp_path / "_inet_ks.csv"))
         ops.prof_enable(False)
+        plan = ops.gemm_plan(M, N, Kx, a_kmajor=bool(akm), b_kmajor=bool(bkm))
         if Kx >= 64:                                          # shorter products stay on the LDS-tiled kernel
-            assert " k" in open(str(tmp_path / "_inet_ks.csv")).read().strip().splitlines()[-1].split(",")[1]
+            assert plan["family"] == ops.GEMM_FAMILIES.index("ks") and " k" in plan["label"]
+        assert dumped_labels(tmp_path / "_inet_ks.csv") == [plan["label"]]    # the launch followed the plan
         assert relmax(C, ref) < 2e-5
         C0 = torch.randn(M, N, generator=g)
         C1 = C0.to(DEV).clone()
@@ -378,7 +402,6 @@ def test_gemm_workgroup_split_k(akm, bkm, M, N, K, tmp_path):
         ops.gemm(Ad, Bd, M, N, Kx, out=big[:, 1, :], **kw)
         assert relmax(big[:, 1, :], ref) < 2e-5
         assert float(big[:, 0, :].abs().max()) == 0.0
-    ops.set_option(5, 1)
 
 
 def test_gemm_strided_unaligned_and_epilogues():
