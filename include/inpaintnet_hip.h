@@ -229,6 +229,23 @@ int inet_gemm(const float* A, int64_t lda, int a_kmajor, const float* B, int64_t
 int inet_gemm_batched(const float* A, int64_t lda, int a_kmajor, const float* B, int64_t ldb, int b_kmajor, float* C,
                       int64_t ldc, int M, int N, int K, int nbatch, int64_t batchA, int64_t batchB, int64_t batchC,
                       void* stream);
+/* n = 1..4 INDEPENDENT products in one launch where a grouped kernel applies (csrc/gemm.hip launch_gemm_group: few-row products of
+ * one M on the wave-per-column kernel, products of one operand layout and a common tile on the workgroup split-K kernel;
+ * inet_gemm_group_plan tells which), one after the other otherwise.  Every product is described by the arguments inet_gemm takes
+ * for it and keeps its own shape, K, leading dimensions, bias, epilogue and accumulation mode.  The destinations of one group must
+ * not overlap element for element (the products run concurrently); interleaved strided destinations -- rows of one product between
+ * the rows of another -- are allowed.  -1 and no launch for n outside 1..4, a null list and whatever inet_gemm rejects in any
+ * product (null A, B or C; M, N or K <= 0; epi outside 0..5; acc outside 0..1). */
+typedef struct inet_gemm_desc {
+    const float* A; int64_t lda; int32_t a_kmajor;
+    const float* B; int64_t ldb; int32_t b_kmajor;
+    float* C; int64_t ldc;
+    int32_t M, N, K;
+    const float* bias;
+    const float* aux; int64_t ldaux;
+    int32_t epi, acc;
+} inet_gemm_desc;
+int inet_gemm_group(int n, const inet_gemm_desc* list, void* stream);
 
 /* The same product on the bf16 matrix cores at fp32 accuracy (csrc/gemm_bf3.hip): both operands are split exactly into three
  * bf16 pieces in MFMA fragment order (a scratch allocated for the call: this entry exists for tests and benchmarks; inside the

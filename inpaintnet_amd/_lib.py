@@ -26,6 +26,16 @@ class LatentConfig(C.Structure):
     _fields_ = [("z_dim", C.c_int32), ("rnn_hidden", C.c_int32), ("auto_reg", C.c_int32)]
 
 
+class GemmDesc(C.Structure):
+    """inet_gemm_desc: one product of an inet_gemm_group call, the arguments inet_gemm takes for it."""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("a_kmajor", C.c_int32),
+                ("B", C.c_void_p), ("ldb", C.c_int64), ("b_kmajor", C.c_int32),
+                ("C", C.c_void_p), ("ldc", C.c_int64),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("bias", C.c_void_p), ("aux", C.c_void_p), ("ldaux", C.c_int64),
+                ("epi", C.c_int32), ("acc", C.c_int32)]
+
+
 def build(force=False, verbose=True):
     """Compile every HIP source for gfx950 into the in-tree shared library: one object per source (in parallel,
     only the stale ones), then one link."""
@@ -103,6 +113,7 @@ _SIGNATURES = {
     "inet_bigru2_fwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
     "inet_bigru2_bwd": (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "inet_gemm": (C.c_int, [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _P, _P, _L, _I, _I, _P]),
+    "inet_gemm_group": (C.c_int, [_I, C.POINTER(GemmDesc), _P]),
     "inet_epoch_stats_add": (C.c_int, [_P, _P, _P, _P]),
     "inet_gemm_bf3": (C.c_int, [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _P, _I, _I, _P]),
     "inet_gemm_batched": (C.c_int, [_P, _L, _I, _P, _L, _I, _P, _L, _I, _I, _I, _I, _L, _L, _L, _P]),

@@ -336,6 +336,17 @@ int inet_gemm_batched(const float* A, int64_t lda, int a_kmajor, const float* B,
     return launch_gemm(g, (hipStream_t)stream);
 }
 
+int inet_gemm_group(int n, const inet_gemm_desc* list, void* stream) {
+    GemmArgs g[kGemmGroupMax];
+    if (n < 1 || n > kGemmGroupMax || !list) return -1;
+    for (int i = 0; i < n; ++i) {
+        const inet_gemm_desc& d = list[i];
+        if (!d.A || !d.B || !d.C || d.M <= 0 || d.N <= 0 || d.K <= 0 || d.epi < 0 || d.epi > 5 || d.acc < 0 || d.acc > 1) return -1;
+        g[i] = gemm_args(d.A, d.lda, d.a_kmajor, d.B, d.ldb, d.b_kmajor, d.C, d.ldc, d.M, d.N, d.K, d.bias, d.epi, d.aux, d.ldaux, d.acc);
+    }
+    return launch_gemm_group(g, n, (hipStream_t)stream);
+}
+
 int inet_linear_fwd(const float* x, const float* W, const float* b, float* y, int M, int N, int K, int epi,
                     void* stream) {
     if (!x || !W || !y || M <= 0 || N <= 0 || K <= 0 || epi < 0 || epi > 2) return -1;

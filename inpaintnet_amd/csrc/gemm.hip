@@ -421,10 +421,12 @@ __global__ __launch_bounds__(256) void gemm_kc_direct_kernel(GemmArgs g, int til
     const int tm = v / tiles_n, tn = v - tm * tiles_n;
     const int m0 = tm * (32 * TA) + wr * (16 * TA), n0 = tn * (32 * TB) + wc * (16 * TB);
     const int lda = (int)g.lda, ldb = (int)g.ldb;
+    // a k-contiguous operand's range ends with element K - 1 of its last row, not with that row's pitch: the loads that run ahead
+    // of K return zero there (never used) and a column sub-view of a wider matrix is not read behind its parent's last row
     const __amdgpu_buffer_rsrc_t ra_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0, g.M * lda * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rb_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, (BKM ? g.K : g.N) * ldb * 4, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.A), 0, ((g.M - 1) * lda + g.K) * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(g.B), 0, (BKM ? g.K * ldb : (g.N - 1) * ldb + g.K) * 4, 0x00020000);
 
     int oa[TA];                                          // this lane's 16 bytes of k group 0, row tile i
 #pragma unroll
@@ -579,10 +581,12 @@ __device__ __forceinline__ void gemm_ks_body(const GemmArgs& g, int v, int tiles
     const int lda = (int)g.lda, ldb = (int)g.ldb;
     const int kbeg = split * g.k_per_split;
     const int kend = min(g.K, kbeg + g.k_per_split);
+    // a k-contiguous operand's range ends with element K - 1 of its last row (as in gemm_kc_direct_kernel): the loads that run
+    // ahead of K stay inside a column sub-view's parent
     const __amdgpu_buffer_rsrc_t ra_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(g.A) + (AKM ? (long)kbeg * lda : 0), 0, (AKM ? kend - kbeg : g.M) * lda * 4, 0x00020000);
+        const_cast<float*>(g.A) + (AKM ? (long)kbeg * lda : 0), 0, (AKM ? (kend - kbeg) * lda : (g.M - 1) * lda + g.K) * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t rb_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(g.B) + (BKM ? (long)kbeg * ldb : 0), 0, (BKM ? kend - kbeg : g.N) * ldb * 4, 0x00020000);
+        const_cast<float*>(g.B) + (BKM ? (long)kbeg * ldb : 0), 0, (BKM ? (kend - kbeg) * ldb : (g.N - 1) * ldb + g.K) * 4, 0x00020000);
 
     KsOperand<TA, AKM> a[D];
     KsOperand<TB, BKM> b[D];

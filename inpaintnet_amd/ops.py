@@ -447,6 +447,48 @@ def gemm_plan(M, N, K, a_kmajor=False, b_kmajor=False, lda=None, ldb=None, bias=
     return dict(zip(GEMM_PLAN_KEYS, list(out)), flops=work[0], bytes=work[1], label=label.value.decode())
 
 
+def gemm_group(products):
+    """Up to four INDEPENDENT products in one launch where a grouped kernel applies (inet_gemm_group; gemm_group_plan tells), one after
+    the other otherwise.  products: dicts of gemm()'s arguments -- A, B, M, N, K, out (required here), and optionally a_kmajor,
+    b_kmajor, bias, epi, aux, accumulate.  The destinations must not overlap element for element.  Returns the destinations."""
+    descs = (_lib.GemmDesc * max(len(products), 1))()
+    for d, p in zip(descs, products):
+        A, B, out, aux = p["A"], p["B"], p["out"], p.get("aux")
+        assert A.stride(1) == 1 and B.stride(1) == 1 and out.stride(1) == 1 and (aux is None or aux.stride(1) == 1)
+        d.A, d.lda, d.a_kmajor = A.data_ptr(), A.stride(0), int(p.get("a_kmajor", False))
+        d.B, d.ldb, d.b_kmajor = B.data_ptr(), B.stride(0), int(p.get("b_kmajor", False))
+        d.C, d.ldc = out.data_ptr(), out.stride(0)
+        d.M, d.N, d.K = p["M"], p["N"], p["K"]
+        d.bias = None if p.get("bias") is None else p["bias"].data_ptr()
+        d.aux, d.ldaux = (None, 0) if aux is None else (aux.data_ptr(), aux.stride(0))
+        d.epi, d.acc = int(p.get("epi", 0)), int(p.get("accumulate", False))
+    check(_lib.lib().inet_gemm_group(len(products), descs, stream_ptr()), "inet_gemm_group")
+    return [p["out"] for p in products]
+
+
+def gemm_group_plan(products):
+    """What gemm_group() launches for these products under the options set now, without a GPU (inet_gemm_group_plan).  products: dicts
+    of gemm_plan()'s arguments (M, N, K, and optionally a_kmajor, b_kmajor, lda, ldb, bias, epi, accumulate) or the dicts given to
+    gemm_group() (the leading dimensions are then those of A and B).  One dict like gemm_plan()'s per product: when one launch takes
+    the group, row 0 describes it ("products" == 1) and the other rows are empty; else row i is the plan of product i on its own and
+    "products" == len(products)."""
+    n = len(products)
+    desc = (C.c_int64 * (10 * max(n, 1)))()
+    for i, p in enumerate(products):
+        akm, bkm = bool(p.get("a_kmajor", False)), bool(p.get("b_kmajor", False))
+        lda = p["A"].stride(0) if "A" in p else p.get("lda")
+        ldb = p["B"].stride(0) if "B" in p else p.get("ldb")
+        lda = (p["M"] if akm else p["K"]) if lda is None else lda
+        ldb = (p["N"] if bkm else p["K"]) if ldb is None else ldb
+        bias = p.get("bias")
+        desc[10 * i:10 * i + 10] = [int(akm), int(bkm), p["M"], p["N"], p["K"], lda, ldb, int(bias is not None and bias is not False),
+                                    int(p.get("epi", 0)), int(p.get("accumulate", False))]
+    out, work, label = (C.c_int32 * (16 * max(n, 1)))(), (C.c_double * (2 * max(n, 1)))(), C.create_string_buffer(96 * max(n, 1))
+    check(_lib.lib().inet_gemm_group_plan(n, desc, out, work, label, 96), "inet_gemm_group_plan")
+    return [dict(zip(GEMM_PLAN_KEYS, out[16 * i:16 * i + 16]), flops=work[2 * i], bytes=work[2 * i + 1],
+                 label=label.raw[96 * i:96 * (i + 1)].split(b"\0")[0].decode()) for i in range(n)]
+
+
 def epoch_stats_add(sums, loss, accuracy=None, step_flag=None):
     """sums[:3] += (loss, accuracy, 1) on the device unless the step was skipped (step_flag: the ranks' summed chain status as
     given to adam_step; None: this process's own status word) -- inet_epoch_stats_add_ex."""

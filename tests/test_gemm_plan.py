@@ -217,3 +217,52 @@ def test_calls_the_entries_reject(L):
     assert L.inet_gemm_group_plan(1, d, None, work, label, CAP) == -1
     assert L.inet_gemm_group_plan(1, d, out, None, label, CAP) == -1
     assert L.inet_gemm_group_plan(1, d, out, work, None, CAP) == -1
+
+
+# ---- (e) the grouped launch behind the C-ABI: inet_gemm_group / ops.gemm_group, ops.gemm_group_plan -----------------------------------
+def test_gemm_group_entry_rejects(L):
+    """-1 before anything is launched (no device is touched: the pointers are not even memory)."""
+    def desc(**bad):
+        d = dict(A=0x1000, lda=64, a_kmajor=0, B=0x2000, ldb=64, b_kmajor=0, C=0x3000, ldc=64, M=64, N=64, K=64, bias=None, aux=None,
+                 ldaux=0, epi=0, acc=0)
+        d.update(bad)
+        return _lib.GemmDesc(**d)
+    two = (_lib.GemmDesc * 2)(desc(), desc())
+    five = (_lib.GemmDesc * 5)(*[desc()] * 5)
+    assert L.inet_gemm_group(0, two, None) == -1 and L.inet_gemm_group(-1, two, None) == -1
+    assert L.inet_gemm_group(5, five, None) == -1
+    assert L.inet_gemm_group(1, None, None) == -1 and L.inet_gemm_group(2, None, None) == -1
+    for bad in (dict(A=None), dict(B=None), dict(C=None), dict(M=0), dict(N=0), dict(K=0), dict(M=-1), dict(N=-5), dict(K=-64),
+                dict(epi=-1), dict(epi=6), dict(acc=-1), dict(acc=2)):
+        for n, at in ((1, 0), (2, 0), (2, 1), (4, 3)):     # the bad product alone, first, last
+            lst = (_lib.GemmDesc * n)(*[desc(**bad) if i == at else desc() for i in range(n)])
+            assert L.inet_gemm_group(n, lst, None) == -1, (bad, n, at)
+
+
+@pytest.mark.parametrize("site", list(VAE_GROUPS))
+def test_ops_group_plan_is_the_raw_group_plan(L, site):
+    """ops.gemm_group_plan over the call sites' descriptors: the dicts of ops.gemm_plan, value for value what the entry wrote."""
+    from inpaintnet_amd import ops
+    options(L)
+    descs = VAE_GROUPS[site][0]
+    rc, raw = group_plan(L, descs)
+    names = ("a_kmajor", "b_kmajor", "M", "N", "K", "lda", "ldb", "bias", "epi", "accumulate")
+    got = ops.gemm_group_plan([dict(zip(names, d)) for d in descs])
+    rename = {"gx": "grid_x", "gy": "grid_y", "gz": "grid_z"}
+    assert rc == 0 and len(got) == len(raw) == len(descs)
+    for g, r in zip(got, raw):
+        r = {rename.get(k, k): v for k, v in r.items() if k != "_"}
+        assert g == r and tuple(g)[:15] == ops.GEMM_PLAN_KEYS and set(g) == set(ops.gemm_plan(64, 64, 64))
+    assert got[0]["products"] == 1 and got[0]["label"] == VAE_GROUPS[site][1]
+
+
+def test_ops_group_plan_of_a_group_that_falls_apart(L):
+    from inpaintnet_amd import ops
+    options(L)
+    descs = [fwd(256, 512, 512, 0), dgrad(256, 512, 512, 0)]
+    got = ops.gemm_group_plan([dict(M=256, N=512, K=512, bias=True), dict(M=256, N=512, K=512, b_kmajor=True)])
+    assert [g["products"] for g in got] == [2, 2]
+    assert [g["label"] for g in got] == [r["label"] for r in group_plan(L, descs)[1]]
+    assert got[0] == dict(ops.gemm_plan(256, 512, 512, bias=True), products=2)
+    with pytest.raises(ValueError):
+        ops.gemm_group_plan([dict(M=64, N=64, K=64)] * 5)
