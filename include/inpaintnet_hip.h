@@ -109,6 +109,23 @@ int inet_vae_decoder_fwd(const inet_vae_config* cfg, int batch, const float* z, 
 int inet_vae_decoder_sample(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
                             const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
                             float temperature, const double* uniforms, void* stream);
+/* The same behind TOP-K / NUCLEUS TRUNCATION, with the drawn tokens' log-probabilities.  For one (row, tick), with s, m = max s and
+ * e_v = expf(s_v - m) as above:  order the tokens by (s_v descending, v ascending) -- over s, not x: the temperature may be negative;
+ * every zero logit ties with every other, and the lowest index ranks first --;  K = top_k if 1 <= top_k < V, else V (top_k <= 0 or
+ * >= V: off);  A_i = the f64 sum of e over the first i tokens of the order;  n = the smallest i <= K with A_i >= top_p * A_K (the
+ * nucleus is taken of what top-k kept; top_p = 1: n = K, nothing evaluated; n >= 1 always).  The first n tokens of the order are
+ * kept, and samples[b,0,t] = the first v in INDEX order among the kept whose inclusive f64 prefix of kept e exceeds uniforms[b,t] * S,
+ * S = the kept total: inet_vae_decoder_sample's rule on the truncated distribution, and with truncation off that rule bit for bit.
+ * logp (nullable; [B,T] floats on the device) receives (s_tok - m) - log(S) as f32, the drawn token's log-probability under the
+ * truncated distribution.  Where the sampling rule does not apply the tick takes the argmax as above and its logp is NaN.
+ * top_k = 1 with temperature > 0 is the argmax decode for any uniforms in [0, 1).  inet_vae_decoder_sample is this call with
+ * (top_k, top_p, logp) = (0, 1.0, null) and runs the kernels it always ran; a call with truncation on or a logp runs the truncating
+ * build of the register-resident launch (inet_decode_b1_plan_trunc) or, for every other shape, inet_sample_truncated's kernel tick
+ * by tick, and never a kernel that ignores top_k / top_p: its launch labels start with "trunc_" (trunc_decode_b1..., trunc_sample ...).
+ * -1 where inet_vae_decoder_sample returns it, and for a top_p that is NaN, <= 0 or > 1. */
+int inet_vae_decoder_sample_ex(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
+                               const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
+                               float temperature, const double* uniforms, int top_k, double top_p, float* logp, void* stream);
 /* dweights [B,T,V] = dLoss/dweights; weights = the forward output; grads may be null (frozen decoder:
  * LatentRNN/latent_rnn.py:42-43) in which case only dz [B,Z] is produced.  `tokens_in` are the tokens that
  * were fed back (= samples of the forward call). */
@@ -160,6 +177,13 @@ int inet_sample_multinomial(const float* weights, int64_t ld_w, int rows, int V,
  * NaN).  The result always lies in [0, V).  -1: a null pointer, rows <= 0, V <= 0, V > 512, a non-finite temperature. */
 int inet_sample_temperature(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                             int64_t u_stride, int64_t* out, int64_t stride, void* stream);
+/* The truncated rule of inet_vae_decoder_sample_ex on rows of V logits, one wavefront per row: out[row*stride] = the token,
+ * logp[row*logp_stride] (logp nullable) = its log-probability under the truncated distribution; inet_argmax's rule and a NaN logp
+ * for a row where the sampling rule does not apply.  -1 where inet_sample_temperature returns it, and for a top_p that is NaN, <= 0
+ * or > 1. */
+int inet_sample_truncated(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
+                          int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
+                          void* stream);
 
 /* ---- optimizer: torch.optim.Adam as built at utils/trainer.py:32-35, stepped at :172-177 -------- */
 /* p,g,m,v: arenas of n floats; step is 1-based; grads are multiplied by gscale first (1/world_size for DP) */
@@ -462,6 +486,9 @@ int inet_decode_b1_plan(int B, int V, int Z, int* out8);
 /* The same for a temperature-sampled call (inet_vae_decoder_sample): the same planner with its `sample` input set, the same
  * self-check.  -1 also under inet_set_option key 15 != 4: the sampling build exists for the default mode's plans. */
 int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8);
+/* ... and for a truncated call (inet_vae_decoder_sample_ex with truncation on or a logp): the truncating build has a merged build
+ * for one row with V <= 32 alone (the others would spill registers), so more of its plans place workgroup C. */
+int inet_decode_b1_plan_trunc(int B, int V, int Z, int* out8);
 /* What inet_gemm (nbatch = 1) / inet_gemm_batched (nbatch 2..8: no bias, epi 0, acc 1) launch for a call, under the options set now
  * (inet_set_option keys 2, 3, 5), without a GPU: the dispatcher's planner (csrc/gemm.hip gemm_plan) behind the C-ABI.  out16 = {family
  * (0 = few-row gemv, 1 = TN-direct, 2 = kc-direct, 3 = workgroup split-K, 4 = LDS-tiled), tile configuration, tile rows, tile columns,

@@ -95,6 +95,7 @@ _SIGNATURES = {
     "inet_vae_decoder_ws_bytes": (_L, [_CFG, _I, _I]),
     "inet_vae_decoder_fwd": (C.c_int, [_CFG, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I, C.c_uint64, _P]),
     "inet_vae_decoder_sample": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P]),
+    "inet_vae_decoder_sample_ex": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _I, C.c_double, _P, _P]),
     "inet_vae_decoder_bwd": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "inet_vae_ws_field": (C.c_int, [_CFG, _I, _I, C.c_char_p, C.POINTER(_L), C.POINTER(_L)]),
     "inet_cross_entropy": (C.c_int, [_P, _L, _I, _I, _P, _P, _L, _F, _F, _P, _P, _P]),
@@ -102,6 +103,7 @@ _SIGNATURES = {
     "inet_reparam_kl": (C.c_int, [_P, _P, _P, _P, _P, _L, _P, _P]),
     "inet_sample_multinomial": (C.c_int, [_P, _L, _I, _I, _P, _L, C.c_uint64, C.c_uint64, _P]),
     "inet_sample_temperature": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _P, _L, _P]),
+    "inet_sample_truncated": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _I, C.c_double, _P, _L, _P, _L, _P]),
     "inet_latent_bwd": (C.c_int, [_P, _P, _P, _P, _F, _P, _P, _P, _L, _P]),
     "inet_adam_step": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),
     "inet_adam_step_ex": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P, _P]),
@@ -145,6 +147,7 @@ _SIGNATURES = {
     "inet_slow_waits": (C.c_int, [_P, _I, _I, C.POINTER(_L)]),
     "inet_decode_b1_plan": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int)]),
     "inet_decode_b1_plan_sample": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int)]),
+    "inet_decode_b1_plan_trunc": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int)]),
     "inet_gemm_plan": (C.c_int, [_I] * 5 + [_L, _L] + [_I] * 4 + [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, _I]),
     "inet_gemm_group_plan": (C.c_int, [_I, C.POINTER(_L), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, _I]),
     "inet_preload": (C.c_int, []),

@@ -154,6 +154,7 @@ struct B1Args {
     DecodeB1Beat bp;                             // the beat path's operands (fused)
     chain::Status status;
     const double* uniforms; float temperature;   // the sampling build: one uniform per (row, tick) [B, T], the logits' factor
+    int top_k; double top_p; float* logp;        // the truncating build: sample.h's truncation in front of the draw; logp [B, T] or null
 };
 
 #define B1_STAMP(who, t, i) do { if (stamps && tid == 0) stamps[((who) * 32 + (t)) * 8 + (i)] = wall_clock64(); } while (0)
@@ -504,13 +505,57 @@ __device__ __forceinline__ int sample_token(const float (&lg)[NVL], float temp, 
     if (__ballot(nan)) return -1;
     return sample::pick<NVL>(sv, wave_max_dpp(ms), u, V, lane);
 }
+// TRUNCATED SAMPLING (TRUNC = true, the truncating build; sample.h has the rule): sample::truncate in front of the same pick -- top_k and
+// top_p are kernel arguments, so the token stays a pure function of `lgs`, u and two kernel arguments: the merged build's copies still agree
+// bit for bit.  The drawn token's log-probability under the truncated distribution is (s_tok - max s) - log(S): gap = its first half (NaN
+// where the tick keeps the argmax rule), S = the kept total (1 there); the wave that stores the token files both in LDS (lp_gap, lp_tot)
+// and takes the f64 logarithms of all ticks behind the last one, where the weights' registers are free (inside the tick the pick runs
+// with ~240 registers taken: an f64 log there spills).  Hence at most kTruncTicks ticks per call.
+constexpr int kTruncTicks = 64;
+template <int NVL>
+__device__ __forceinline__ int sample_token_trunc(const float (&lg)[NVL], float temp, double u, int V, int lane, int top_k, double top_p,
+                                                  float& gap, double& S) {
+    float sv[NVL], ms = -INFINITY;
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < NVL; ++j) {
+        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
+        nan |= sv[j] != sv[j];
+        ms = fmaxf(ms, sv[j]);
+    }
+    gap = __builtin_nanf("");
+    S = 1.0;
+    if (__ballot(nan)) return -1;
+    ms = wave_max_dpp(ms);
+    sample::truncate<NVL>(sv, ms, top_k, top_p, V, lane);
+    const int tok = sample::pick<NVL>(sv, ms, u, V, lane, S);
+    if (tok >= 0) gap = sample::logp_gap<NVL>(sv, ms, tok);
+    else S = 1.0;
+    return tok;
+}
+// ... behind the last tick: logp[row, t] of the team's rows, one (row, tick) per thread (the picking waves' LDS writes are ordered by the
+// barrier the caller's loop ends with or by this one)
+template <int NB>
+__device__ __forceinline__ void store_logp(const B1Args& a, const float (*gap)[kTruncTicks], const double (*tot)[kTruncTicks], int rb, int nrow,
+                                           int tid, int done) {
+    __syncthreads();
+    if (!a.logp) return;
+    for (int i = tid; i < NB * a.T; i += NT) {
+        const int r = i / a.T, t = i % a.T;
+        // (done: the ticks the loop finished -- a timeout leaves it early, and the ticks it never reached report NaN.  t >= kTruncTicks
+        //  does not occur: decode_b1_shape_ok refuses a truncated call of more ticks)
+        if (r < nrow && t < kTruncTicks) a.logp[(long)(rb + r) * a.T + t] = t < done ? sample::logp_of(gap[r][t], tot[r][t]) : __builtin_nanf("");
+    }
+}
 constexpr int kSharedRows = 6;                   // rows a shared recurrent group serves beyond ten measures (8: the group's tick is longer than the two-row teams' and sets the pace)
 constexpr int kSharedRowsSmall = 3;              // ... and for four to six measures, where the critical teams have ONE row
 // The merged build's shapes (rows x ceil(V / 32) <= 2: what fits 256 registers without spills).  The kernel, the planner and its
 // self-check all ask here.  The SAMPLING build of two-row teams beside groups of six rows (V <= 32, eleven to sixteen measures) does
-// not fit: 256 VGPRs and two spilled (the argmax build: 253) -- it is not built, such a call runs workgroup C.
-__host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, bool sample) {
-    return nb * nj <= 2 && !(sample && nb == 2 && nbr == kSharedRows);
+// not fit: 256 VGPRs and two spilled (the argmax build: 253) -- it is not built, such a call runs workgroup C.  The TRUNCATING build
+// (sample == 2) has a merged build for one row with V <= 32 alone: with two logit blocks per thread (one row, 32 < V <= 64; two rows, V <=
+// 32) it comes out at 255 / 256 VGPRs with 12 bytes of scratch -- not built either, workgroup C.
+__host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, int sample) {
+    return nb * nj <= 2 && !(sample && nb == 2 && nbr == kSharedRows) && !(sample == 2 && nb * nj == 2);
 }
 
 // Shared recurrent groups (round 6, NBR > NB): seven to sixteen measures used to run as teams of FOUR rows (49 workgroups each: four
@@ -519,12 +564,17 @@ __host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, bool sa
 // tick.  So they are shared: two-row critical teams (17 workgroups each, on one XCD) for every pair of rows, and recurrent groups
 // of 32 workgroups that serve NBR = 6 rows -- three teams -- each: 8 x 17 + 3 x 32 = 232 workgroups for sixteen measures, every
 // row on a two-row tick.  A group's rows without a team (the last group of a call) are skipped (Ctx.nact).
-template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB, bool SAMPLE = false>
+// (TRUNC, the truncating build of the sampling build: behind SAMPLE, so that every build without it keeps its parameters)
+template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB, bool SAMPLE = false, bool TRUNC = false>
 __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
+    static_assert(SAMPLE || !TRUNC, "the truncating build is a sampling build");
     constexpr int XROWS = NB > NBB ? (NB > NBR ? NB : NBR) : (NBB > NBR ? NBB : NBR);
     __shared__ __attribute__((aligned(16))) float xs[XROWS][2][XS];
     __shared__ float lgs[NB][32 * NJ];
     __shared__ int toks[NB];
+    // the truncating build: (s_tok - max s, kept total) of every (row, tick), filed by the wave that stores the token (lane 0; one row: wave 0's)
+    __shared__ float lp_gap[TRUNC ? NB : 1][TRUNC ? kTruncTicks : 1];
+    __shared__ double lp_tot[TRUNC ? NB : 1][TRUNC ? kTruncTicks : 1];
     __shared__ int bad_s;
     __shared__ int near_s;
     if (blockIdx.x % a.stride) return;
@@ -546,7 +596,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     const int nb = a.T / a.G;
     const DecodeB1Beat& bp = a.bp;
     // MG, the merged build: workgroup C does not exist, every TBi_k does C's work for itself next to its own (CB below)
-    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE);
+    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE + TRUNC);
 
     if (role == R_C) {
         if (MG) return;
@@ -577,6 +627,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
 #pragma unroll
             for (int g = 0; g < 3; ++g) tb[r][g] = a.table[(long)tok[r] * D3 + g * DH + u];
         if (!get_2d<NB, 3>(ex + G_GH0 + u, G_END, DH, 1u, a.status, gh, hw)) *bad = 1;
+        [[maybe_unused]] int done = 0;                         // (the truncating build: ticks finished)
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
             double ut = 0.0;                                   // the sampling build: this tick's uniform, requested here and read behind the head
@@ -656,9 +707,25 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 }
                 m = wave_max_dpp(m);
                 int bi = 0;
-                if constexpr (SAMPLE) bi = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
+                if constexpr (TRUNC) {
+                    float gap;
+                    double tot;
+                    bi = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
+                    if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
+                }
+                else if constexpr (SAMPLE) bi = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
                 if (!SAMPLE || bi < 0) {
                     if (SAMPLE) bi = 0;
+                    if constexpr (TRUNC) {                      // (the truncating build does not keep the logits across the draw: read again)
+                        m = -1.f;
+#pragma unroll
+                        for (int j = 0; j < NVL; ++j) {
+                            const int v = lane + 64 * j;
+                            lg[j] = v < a.V ? lgs[arow][v] : -1.f;
+                            m = fmaxf(m, lg[j]);
+                        }
+                        m = wave_max_dpp(m);
+                    }
 #pragma unroll
                     for (int j = NVL - 1; j >= 0; --j) {
                         const unsigned long long eq = __ballot(lg[j] == m);
@@ -688,7 +755,9 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             }
             if (more && !get_2d<NB, 3>(ex + G_GH0 + u, G_END, DH, (unsigned)t + 2u, a.status, gh, hw, false)) *bad = 1;
             B1_STAMP(0, t, 6);
+            if constexpr (TRUNC) done = t + 1;
         }
+        if constexpr (TRUNC) store_logp<NB>(a, lp_gap, lp_tot, rb, nrow, tid, done);
     } else if (role < R_TBI) {
         if (NBR != NB && a.crit != kCritTA) {                  // a shared group: rows [NBR team, NBR team + NBR) of the call
             const int rbr = team * NBR;
@@ -746,6 +815,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
 #pragma unroll
             for (int g = 0; g < 3; ++g) tb[r][g] = a.table[(long)tok[r] * D3 + g * DH + u];
         if (!get_2d<NB, 3>(ex + (gh0_near ? G_GH0N + D3 : G_GH0X) + u, G_END, DH, 1u, a.status, gh, hw)) *bad = 1;
+        [[maybe_unused]] int done = 0;                         // (the truncating build: ticks finished)
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
             const unsigned tag = (unsigned)t + 1u;
@@ -857,9 +927,25 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 }
                 m = wave_max_dpp(m);
                 int best = 0;
-                if constexpr (SAMPLE) best = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
+                if constexpr (TRUNC) {
+                    float gap;
+                    double tot;
+                    best = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
+                    if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
+                }
+                else if constexpr (SAMPLE) best = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
                 if (!SAMPLE || best < 0) {
                     if (SAMPLE) best = 0;
+                    if constexpr (TRUNC) {                      // (the truncating build does not keep the logits across the draw: read again)
+                        m = -1.f;
+#pragma unroll
+                        for (int j = 0; j < NVL; ++j) {
+                            const int v = lane + 64 * j;
+                            lg[j] = v < a.V ? lgs[arow][v] : -1.f;
+                            m = fmaxf(m, lg[j]);
+                        }
+                        m = wave_max_dpp(m);
+                    }
 #pragma unroll
                     for (int j = NVL - 1; j >= 0; --j) {
                         const unsigned long long eq = __ballot(lg[j] == m);
@@ -890,7 +976,9 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             if (more && !get_2d<NB, 3>(ex + (gh0_near ? G_GH0N + (int)((tag + 1u) & 1) * D3 : (((tag + 1u) & 1) ? G_GH0X : G_GH0)) + u, G_END, DH, tag + 1u,
                                        a.status, gh, hw, false)) *bad = 1;
             if (out) B1_STAMP(0, t, 6);
+            if constexpr (TRUNC) done = t + 1;
         }
+        if constexpr (TRUNC) { if (out) store_logp<NB>(a, lp_gap, lp_tot, rb, nrow, tid, done); }
     } else if (role < R_TBH) {
         // ---- TBi_k: tick layer 1's input-side product and its cell ----
         const int k = role - R_TBI, p = tid >> 4, s = tid & 15, u = UW * k + p;
@@ -1004,6 +1092,8 @@ int placed_grid(int teams, int rteams, int beat_wgs, int crit = kCrit) {
 // own launches (folded beat path) or decode_chain.hip's exchange kernel.
 // A SAMPLED call (temperature + uniforms) gets the same plans from the same planner under mode 4, with merged_build() deciding which
 // shapes have a merged sampling build; under the other modes it has no plan here, and vae_decoder_fwd samples tick by tick.
+// A TRUNCATED call (DecodeChainArgs.trunc: top-k / nucleus truncation, or the draws' log-probabilities wanted) likewise, with the
+// truncating builds (decode_b1_kernel<..., true, true>) and their merged_build(); at most kTruncTicks ticks.
 
 // What launch_decode_b1 launches for a call, as a value (also behind inet_decode_b1_plan: the planner is tested without a GPU).  The
 // plan names its instantiation decode_b1_kernel<nj, fused, nb, nbb, nbr> itself (dispatch_b1).
@@ -1016,7 +1106,7 @@ struct B1Plan {
     int crit;                                    // critical workgroups per team under place_role: kCritTA, NU (merged build) or kCrit
     int place, stride, grid, live, beat_wgs;
     int rows;                                    // granule rows the launch addresses
-    int sample;                                  // the sampling build
+    int sample;                                  // 1: the sampling build, 2: the truncating build
     bool ok;                                     // the plan fits the chip
 };
 // a candidate plan's rows: teams of nb rows, the folded beat path's nbb, shared groups (ta_crit: the TA stay critical beside the
@@ -1024,7 +1114,7 @@ struct B1Plan {
 struct B1Shape { int nb, nbb, rgroups, nbr; bool ta_crit; };
 
 // the plans a call may get, best first: make_plan takes the first that fits the chip
-static int candidates(int B, int nj, bool fused, bool sample, B1Shape (&c)[2]) {
+static int candidates(int B, int nj, bool fused, int sample, B1Shape (&c)[2]) {
     int n = 0;
     if (sample && mode() != 4) return 0;         // (the sampling build is instantiated for the default mode's plans)
     const auto team = [&](int nb, int nbb) { c[n++] = B1Shape{nb, fused ? nbb : nb, 0, nb, false}; };
@@ -1063,7 +1153,7 @@ static int candidates(int B, int nj, bool fused, bool sample, B1Shape (&c)[2]) {
     return n;
 }
 
-static B1Plan plan_of(int B, int nj, bool fused, bool sample, const B1Shape& sh) {
+static B1Plan plan_of(int B, int nj, bool fused, int sample, const B1Shape& sh) {
     B1Plan p{};
     p.fused = fused; p.nj = nj; p.sample = sample; p.nb = sh.nb; p.nbb = sh.nbb; p.rgroups = sh.rgroups; p.nbr = sh.nbr;
     p.teams = (B + sh.nb - 1) / sh.nb;
@@ -1073,7 +1163,7 @@ static B1Plan plan_of(int B, int nj, bool fused, bool sample, const B1Shape& sh)
     return p;
 }
 
-static B1Plan make_plan(int B, int V, bool fused, bool sample) {
+static B1Plan make_plan(int B, int V, bool fused, int sample) {
     const int nj = (V + 31) / 32, cap = chain_capacity();
     B1Shape c[2];
     const int n = (fused && mode() < 3) ? 0 : candidates(B, nj, fused, sample, c);
@@ -1102,14 +1192,14 @@ static B1Plan make_plan(int B, int V, bool fused, bool sample) {
 }
 
 // The instantiation a plan names: launched, or only looked up (a == null: decode_b1_plan_check).  False where there is none.
-template <int NJ, bool S>
+template <int NJ, int S>
 static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 #define B1_INST(F, NB, NBB, NBR)                                                                                             \
     if (p.fused == (F) && p.nb == (NB) && p.nbb == (NBB) && p.nbr == (NBR)) {                                               \
-        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR, S>), dim3(p.grid), dim3(NT), 0, s, *a);             \
+        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR, S != 0, S == 2>), dim3(p.grid), dim3(NT), 0, s, *a);  \
         return true;                                                                                                        \
     }
-    // (S, the sampling build: the default mode's plans only -- candidates())
+    // (S = 1 / 2, the sampling and the truncating builds: the default mode's plans only -- candidates())
     B1_INST(true, 1, 1, 1)                       // one team, one row, beat path folded in
     if constexpr (!S) { B1_INST(true, 2, 2, 2) } // ... two rows (modes 3, 5)
     B1_INST(true, 1, kDecodeB1OneRowTeamsMax, 1) // two / three one-row teams
@@ -1125,10 +1215,10 @@ static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 }
 static bool dispatch_b1(const B1Plan& p, const B1Args* a, hipStream_t s) {
     switch (p.nj) {
-        case 1: return p.sample ? dispatch_b1_nj<1, true>(p, a, s) : dispatch_b1_nj<1, false>(p, a, s);
-        case 2: return p.sample ? dispatch_b1_nj<2, true>(p, a, s) : dispatch_b1_nj<2, false>(p, a, s);
-        case 3: return p.sample ? dispatch_b1_nj<3, true>(p, a, s) : dispatch_b1_nj<3, false>(p, a, s);
-        case 4: return p.sample ? dispatch_b1_nj<4, true>(p, a, s) : dispatch_b1_nj<4, false>(p, a, s);
+        case 1: return p.sample == 2 ? dispatch_b1_nj<1, 2>(p, a, s) : p.sample ? dispatch_b1_nj<1, 1>(p, a, s) : dispatch_b1_nj<1, 0>(p, a, s);
+        case 2: return p.sample == 2 ? dispatch_b1_nj<2, 2>(p, a, s) : p.sample ? dispatch_b1_nj<2, 1>(p, a, s) : dispatch_b1_nj<2, 0>(p, a, s);
+        case 3: return p.sample == 2 ? dispatch_b1_nj<3, 2>(p, a, s) : p.sample ? dispatch_b1_nj<3, 1>(p, a, s) : dispatch_b1_nj<3, 0>(p, a, s);
+        case 4: return p.sample == 2 ? dispatch_b1_nj<4, 2>(p, a, s) : p.sample ? dispatch_b1_nj<4, 1>(p, a, s) : dispatch_b1_nj<4, 0>(p, a, s);
         default: return false;
     }
 }
@@ -1138,22 +1228,23 @@ int decode_b1_rows(int B) {
     for (int f = 0; f < 2; ++f)
         for (int nj = 1; nj <= 4; ++nj) {
             B1Shape c[2];
-            const int n = candidates(B, nj, f != 0, false, c);     // (a sampled call's candidates are among these)
-            for (int i = 0; i < n; ++i) rows = std::max(rows, plan_of(B, nj, f != 0, false, c[i]).rows);
+            const int n = candidates(B, nj, f != 0, 0, c);     // (a sampled call's candidates are among these)
+            for (int i = 0; i < n; ++i) rows = std::max(rows, plan_of(B, nj, f != 0, 0, c[i]).rows);
         }
     return rows;
 }
 
 void decode_b1_set_mode(int m) { g_mode = (m < 0 || m > 5) ? 4 : m; }
 
-bool decode_b1_shape_ok(int B, int H, int V, int T, int G, bool sample) {
+bool decode_b1_shape_ok(int B, int H, int V, int T, int G, int sample) {
+    if (sample == 2 && T > kTruncTicks) return false;           // (the truncating build files one (gap, total) per tick in LDS)
     return mode() != 0 && chain_enabled() && B >= 1 && B <= kDecodeB1MaxRows && H == DH && V >= 1 && V <= 128 && T % G == 0 && T / G <= 4 &&
            kFusedRoles <= chain_capacity() && make_plan(B, V, false, sample).ok;
 }
-bool decode_b1_fused(int Z, int B, int V, bool sample) { return Z == DZ && make_plan(B, V, true, sample).ok; }
+bool decode_b1_fused(int Z, int B, int V, int sample) { return Z == DZ && make_plan(B, V, true, sample).ok; }
 bool decode_b1_ok(const DecodeChainArgs& a) {
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;
-    const bool sample = a.uniforms != nullptr;
+    const int sample = a.uniforms ? (a.trunc ? 2 : 1) : 0;
     return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G, sample) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr, sample).ok;
 }
 
@@ -1164,14 +1255,14 @@ bool decode_b1_ok(const DecodeChainArgs& a) {
 // has groups, and then the launch is placed; where placed: every (team, role) the kernel expects appears exactly once among the ids of
 // the grid, C's role exactly where the build is not merged, every team's critical roles on ONE residue mod 8, no residue with more than
 // 32 live workgroups (one XCD's CUs).  Returns 0, or -1 for a call the register-resident launch does not take.
-int decode_b1_plan_check(int B, int V, int Z, int* out, bool sample) {
+int decode_b1_plan_check(int B, int V, int Z, int* out, int sample) {
     if (!out || !decode_b1_shape_ok(B, DH, V, 24, 6, sample)) return -1;
     const bool fused = decode_b1_fused(Z, B, V, sample);
     const B1Plan p = make_plan(B, V, fused, sample);
     const int cap = chain_capacity();
     const bool merged = merged_build(p.nb, p.nj, p.nbr, sample);            // the kernel's MG
     const int team_rows = p.teams * p.nb, group_rows = p.rgroups ? std::min(p.rgroups * p.nbr, team_rows) : 0;
-    bool ok = p.ok && p.fused == (int)fused && p.sample == (int)sample && dispatch_b1(p, nullptr, nullptr);
+    bool ok = p.ok && p.fused == (int)fused && p.sample == sample && dispatch_b1(p, nullptr, nullptr);
     ok = ok && team_rows >= B && team_rows - p.nb < B;               // every row in a team, no team without a row
     ok = ok && std::max(team_rows, std::max(group_rows, p.fused ? p.nbb : 0)) <= decode_b1_rows(B);
     ok = ok && (!p.fused || p.nbb >= team_rows);
@@ -1215,7 +1306,7 @@ int decode_b1_plan_check(int B, int V, int Z, int* out, bool sample) {
 }
 
 int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
-    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms != nullptr);
+    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms ? (d.trunc ? 2 : 1) : 0);
     if (!pl.ok || pl.rows > decode_b1_rows(d.B)) return -1;   // (decode_b1_ok has accepted the call: not reached)
     B1Args a{};
     a.fused = pl.fused; a.teams = pl.teams; a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place; a.stride = pl.stride;
@@ -1228,10 +1319,11 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     a.stamps = d.b1stamps;
     a.status = d.status;
     a.uniforms = d.uniforms; a.temperature = d.temperature;
+    a.top_k = d.top_k; a.top_p = d.top_p; a.logp = d.logp;
     if (!dispatch_b1(pl, nullptr, nullptr)) return -1;        // (a plan without an instantiation launches nothing)
     char label[64];
-    // (a sampled call's launch has a label prefix of its own: the profile tells the two kinds of call apart)
-    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
+    // (a sampled and a truncated call's launch have label prefixes of their own: the profile tells the kinds of call apart)
+    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample == 2 ? "trunc_" : pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
     // algorithmic work: the tick GRU + head per tick and row; fused: + the beat path (z2b, two beat layers, three projections per beat)
     const double nbt = (double)d.T / d.G;
     const double beat_mac = a.fused ? 2.0 * DH * DZ + nbt * (3.0 * 3 * DH * DH + 2.0 * DH * DH + 1.0 * DH * DH + 3.0 * DH * DH) : 0.0;

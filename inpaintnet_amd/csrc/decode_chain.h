@@ -48,6 +48,10 @@ struct DecodeChainArgs {
     // temperature sampling (decode_b1.hip's sampling build only: launch_decode_chain refuses a sampled call it cannot hand there)
     const double* uniforms;                       // [B,T] one uniform per (row, tick), or null: the argmax rule
     float temperature;                            // the logits' factor in front of the softmax
+    // ... behind sample.h's top-k / nucleus truncation (decode_b1.hip's truncating build only, likewise)
+    int trunc;                                    // 1: truncation is on or logp is wanted -- the truncating build's plan and kernels
+    int top_k; double top_p;                      // top_k <= 0 or >= V: off; top_p in (0, 1], 1: off
+    float* logp;                                  // [B,T] the drawn tokens' log-probabilities under the truncated distribution, or null
 };
 
 bool decode_chain_ok(int B, int H, int V, int T, int G);
@@ -67,11 +71,11 @@ constexpr int kDecodeB1OneRowTeamsMax = 3;        // ... with ONE-row teams (two
 // (the workspace is carved before the call knows whether its beat path is folded in; rows beyond B repeat row B - 1)
 int decode_b1_rows(int B);
 inline long decode_b1_words(int B) { return (long)decode_b1_rows(B) * kDecodeB1WordsPerRow; }
-// (sample: the plan of a temperature-sampled call -- the same planner decides, and may decide otherwise)
-bool decode_b1_shape_ok(int B, int H, int V, int T, int G, bool sample = false);   // a launchable plan with the beat path's own launches in front
-bool decode_b1_fused(int Z, int B, int V, bool sample = false);                    // ... and one with the beat path folded into the same launch
+// (sample: 1 = the plan of a temperature-sampled call, 2 = of a truncated one -- the same planner decides, and may decide otherwise)
+bool decode_b1_shape_ok(int B, int H, int V, int T, int G, int sample = 0);   // a launchable plan with the beat path's own launches in front
+bool decode_b1_fused(int Z, int B, int V, int sample = 0);                         // ... and one with the beat path folded into the same launch
 bool decode_b1_ok(const DecodeChainArgs& a);                  // the plan of this call (beat.z != null: folded) is launchable
 int launch_decode_b1(const DecodeChainArgs& a, hipStream_t s);
 void decode_b1_set_mode(int m);
 // the launch plan of a call of B measures (V notes, latent size Z) and a host-side self-check of it: decode_b1.hip, no GPU needed
-int decode_b1_plan_check(int B, int V, int Z, int* out8, bool sample = false);
+int decode_b1_plan_check(int B, int V, int Z, int* out8, int sample = 0);

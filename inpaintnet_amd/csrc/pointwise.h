@@ -24,6 +24,10 @@ int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long*
 // does not apply.  V <= 512, else -1.
 int pw_sample_temperature(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride,
                           long long* out, long stride, hipStream_t s);
+// The same behind sample.h's top-k / nucleus truncation (top_k <= 0 or >= V: off; top_p in (0, 1], 1 = off, else -1), and
+// logp[row*lp_stride] (nullable) = the drawn token's log-probability under the truncated distribution, NaN where the row took argmax_first.
+int pw_sample_truncated(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
+                        double top_p, long long* out, long stride, float* logp, long lp_stride, hipStream_t s);
 // step_flag (optional device float): non-zero = skip (the ranks' summed chain status); report (optional, 4 host-mapped words
 // zeroed by the caller): [0] = 1 executed, [1] = 1 skipped, [2] = 1 a parameter became non-finite
 int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,

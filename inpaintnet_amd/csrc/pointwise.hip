@@ -687,6 +687,54 @@ __global__ void sample_temperature_kernel(const float* __restrict__ W, long ld_w
     }
 }
 
+// The same draw behind sample.h's top-k / nucleus truncation (sample::truncate in front of sample::pick: the decoder's truncated
+// sampling outside decode_b1.hip's launch; the same rule), and logp[row*lp_stride] (nullable) = the drawn token's log-probability
+// under the truncated distribution, NaN for a row that took argmax_first.  One wavefront per row, V <= 64 NV.
+template <int NV>
+__global__ void sample_truncated_kernel(const float* __restrict__ W, long ld_w, int rows, int V, float temp,
+                                        const double* __restrict__ uniforms, long u_stride, int top_k, double top_p,
+                                        long long* __restrict__ out, long stride, float* __restrict__ logp, long lp_stride) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int row = wave; row < rows; row += nwaves) {
+        const float* w = W + (long)row * ld_w;
+        const double u = uniforms[(long)row * u_stride];
+        float x[NV], sv[NV], m = -INFINITY, ms = -INFINITY;
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int v = lane + 64 * j;
+            x[j] = v < V ? w[v] : -INFINITY;
+            sv[j] = v < V ? x[j] * temp : -INFINITY;
+            nan |= sv[j] != sv[j];
+            m = fmaxf(m, x[j]);
+            ms = fmaxf(ms, sv[j]);
+        }
+        int tok = -1;
+        float lp = __builtin_nanf("");
+        if (!__ballot(nan)) {
+            ms = wave_max(ms);
+            double S;
+            sample::truncate<NV>(sv, ms, top_k, top_p, V, lane);
+            tok = sample::pick<NV>(sv, ms, u, V, lane, S);
+            if (tok >= 0) lp = sample::logp_of(sample::logp_gap<NV>(sv, ms, tok), S);
+        }
+        if (tok < 0) {
+            m = wave_max(m);
+            int am = kAmNone;
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (lane + 64 * j < V) am = min(am, am_key(x[j], m, lane + 64 * j));
+            tok = am_index(wave_min_i(am));
+        }
+        if (lane == 0) {
+            out[(long)row * stride] = tok;
+            if (logp) logp[(long)row * lp_stride] = lp;
+        }
+    }
+}
+
 __global__ void scale_kernel(float* __restrict__ x, long n, float a) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] *= a;
 }
@@ -966,6 +1014,18 @@ int pw_sample_temperature(const float* W, long ld_w, int rows, int V, float temp
     ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 16.0));
     const dim3 grid(grid_for((long)rows * 64, 256, 1024));
 #define PW_ST(NV) hipLaunchKernelGGL(sample_temperature_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, out, stride)
+    if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
+#undef PW_ST
+    return ok();
+}
+int pw_sample_truncated(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
+                        double top_p, long long* out, long stride, float* logp, long lp_stride, hipStream_t s) {
+    if (V > 512 || !(top_p > 0.0 && top_p <= 1.0)) return -1;
+    char label[48];
+    std::snprintf(label, sizeof label, "trunc_sample B%d V%d", rows, V);
+    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 20.0));
+    const dim3 grid(grid_for((long)rows * 64, 256, 1024));
+#define PW_ST(NV) hipLaunchKernelGGL(sample_truncated_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride)
     if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
 #undef PW_ST
     return ok();

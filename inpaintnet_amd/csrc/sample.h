@@ -58,4 +58,112 @@ __device__ __forceinline__ int pick(const float (&s)[NV], float m, double u, int
     return tok;
 }
 
+// The same, and S = the total the threshold was taken of (the kept total behind truncate()): what logp_of() needs.  Same instructions
+// on the same values as pick() above, which AnticipationRNN's kernels keep using: the token is the same bit for bit.
+template <int NV>
+__device__ __forceinline__ int pick(const float (&s)[NV], float m, double u, int V, int lane, double& S) {
+    S = 0.0;
+    if (!(m > -INFINITY && m < INFINITY) || !(u >= 0.0 && u < 1.0)) return -1;
+    double pre[NV];
+    double carry = 0.0;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const double e = lane + 64 * j < V ? (double)expf(s[j] - m) : 0.0;
+        const double x = wave_scan(e, lane);
+        pre[j] = carry + x;
+        carry += readlane_d(x, 63);
+    }
+    if (!(carry > 0.0 && carry < INFINITY)) return -1;
+    S = carry;
+    const double thr = u * carry;
+    int tok = -1;
+#pragma unroll
+    for (int j = NV - 1; j >= 0; --j) {
+        const unsigned long long b = __ballot(lane + 64 * j < V && pre[j] > thr);
+        if (b) tok = 64 * j + __builtin_ctzll(b);
+    }
+    return tok;
+}
+
+// TOP-K / NUCLEUS TRUNCATION in front of pick().  Order the tokens by (s_v descending, v ascending); K = top_k if 1 <= top_k < V, else V;
+// A_i = the f64 sum of e_v = expf(s_v - m) over the first i tokens of the order; n = the smallest i <= K with A_i >= top_p A_K (top_p
+// >= 1: n = K, nothing evaluated); the first n tokens are kept.  A token with r tokens in front of it is kept iff r < K and A_r < top_p
+// A_K (A is monotone, A_0 = 0 < top_p A_K: the top-ranked token always stays, so m stays the maximum).  Dropped tokens get s = -inf:
+// e = 0 in pick(), which then is the rule on the truncated distribution.
+// How: passes over the V tokens w in index order, s_w by readlane with a wave-uniform lane, every lane looking at its own tokens v.
+// Top-k: count the w that rank in front of v -- exact integer counts of f32 comparisons, so ties (every zero logit ties with every
+// other) fall lowest index first with nothing to round -- and keep the ballot of rank < K.  Nucleus: A_K = the wave's f64 sum of e over
+// that ballot, then per 64-token chunk of v a second pass that adds up e_w (f64) of the w in front of v.  What stays live between the
+// passes are ballots (scalar registers); per lane a pass holds NV counters or ONE f64 sum next to s.  V x (a readlane + NV x (2
+// compares, an add)) for top-k, V x NV x (readlane, expf, 2 compares, an f64 add) for the nucleus: linear in V with no sort.  (Measured
+// against ONE pass that keeps e, the counters and the f64 sums per lane and reads e_w by a second readlane: that one is slower in the
+// decode kernel, +4.1 against +2.7 us per tick for top-k and +6.5 against +6.1 for the nucleus at b = 1 -- DESIGN.md section 11.)  A
+// radix descent over the 32 key bits with a masked f64 wave sum per bit would cost 32 x (NV selects + an f64 wave reduction of ~25
+// DPP / readlane steps), more than these passes for the decoder's V <= 128.
+// s[j] of v >= V must be -inf and no s may be NaN (as for pick()); m not finite: nothing is done (pick() refuses it).
+template <int NV>
+__device__ __forceinline__ void truncate(float (&s)[NV], float m, int top_k, double top_p, int V, int lane) {
+    const int K = (top_k >= 1 && top_k < V) ? top_k : V;
+    const bool nucleus = top_p < 1.0;
+    if ((K == V && !nucleus) || !(m > -INFINITY && m < INFINITY)) return;
+    unsigned long long keep[NV];                                            // ballots: token lane + 64 j stays
+#pragma unroll
+    for (int j = 0; j < NV; ++j) keep[j] = __ballot(lane + 64 * j < V);
+    if (K < V) {
+        int rank[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) rank[j] = 0;
+#pragma unroll
+        for (int jw = 0; jw < NV; ++jw) {
+            const int n = V - 64 * jw < 64 ? V - 64 * jw : 64;              // (wave-uniform; <= 0 beyond the vocabulary)
+            for (int l = 0; l < n; ++l) {
+                const float sw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s[jw]), l));
+                const int w = 64 * jw + l;
+#pragma unroll
+                for (int j = 0; j < NV; ++j) rank[j] += (sw > s[j] || (sw == s[j] && w < lane + 64 * j)) ? 1 : 0;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) keep[j] &= __ballot(rank[j] < K);
+    }
+    if (nucleus) {
+        double ak = 0.0;                                                    // A_K: the mass of what top-k kept
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            ak += readlane_d(wave_scan(((keep[j] >> lane) & 1) ? (double)expf(s[j] - m) : 0.0, lane), 63);
+        const double thr = top_p * ak;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            double before = 0.0;                                            // A_r of token v = lane + 64 j: the mass ranked in front of it
+#pragma unroll
+            for (int jw = 0; jw < NV; ++jw) {
+                const int n = V - 64 * jw < 64 ? V - 64 * jw : 64;
+                for (int l = 0; l < n; ++l) {
+                    const float sw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s[jw]), l));
+                    const double ew = (double)expf(sw - m);                 // (wave-uniform; the value pick() sums)
+                    before += (sw > s[j] || (sw == s[j] && 64 * jw + l < lane + 64 * j)) ? ew : 0.0;
+                }
+            }
+            // (a token in front of a kept one is kept: `before` of a token inside the top K is a sum over the top K alone)
+            keep[j] &= __ballot(before < thr);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        if (!((keep[j] >> lane) & 1)) s[j] = -INFINITY;
+}
+
+// The log-probability of the drawn token under the (truncated) distribution pick() drew from is (s_tok - m) - log(S), stored as f32, in
+// two halves: logp_gap() = s_tok - m (f32; tok in [0, V) from pick(); wave-uniform) where the draw is made, logp_of() where there are
+// registers for an f64 logarithm -- decode_b1.hip's pick has none to spare and takes the logarithms behind its last tick.
+template <int NV>
+__device__ __forceinline__ float logp_gap(const float (&s)[NV], float m, int tok) {
+    float st = m;
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        if ((tok >> 6) == j) st = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s[j]), tok & 63));
+    return st - m;
+}
+__device__ __forceinline__ float logp_of(float gap, double S) { return (float)((double)gap - log(S)); }
+
 }  // namespace sample

@@ -199,21 +199,29 @@ class LatentRNN(Model):
         return torch.zeros(self.num_rnn_layers * self.rnn_num_direction, batch_size, self.rnn_hidden_size,
                            device=self.flat.device)
 
-    def _decode(self, z2d, temperature=None, uniforms=None):
+    def _decode(self, z2d, temperature=None, uniforms=None, top_k=None, top_p=None):
         """frozen decoder, train=False (latent_rnn.py:238): dropout still follows module.training (the quirk)."""
         dummy = torch.zeros(z2d.shape[0], self.vae_model.num_ticks_per_measure, device=z2d.device)
-        return self.vae_model.decoder(z2d, dummy, train=False, temperature=temperature, uniforms=uniforms)
+        return self.vae_model.decoder(z2d, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p)
 
     def forward(self, past_context, future_context, target, measures_to_generate, train=True, eps=None,
-                teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None):
+                teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None):
         """-> weights (B,nt,24,V), samples (B,1,24*nt), gen_z (B,nt,Z)   (latent_rnn.py:110-159).
         eps: optional (eps_past (B,np,Z), eps_future, eps_target) injection; eps_ar: list of (B,Z) for the
         free-running auto-regressive path.
         temperature (inference only: ValueError with train=True): the generated measures' tokens are drawn from
         softmax(temperature * weights) (HierarchicalDecoder.forward) -- all measures in one decoder call on the non-auto-regressive
         path, measure by measure on the free-running auto-regressive one; uniforms (B, n_target, 24) float64 or None (drawn with one
-        np.random.random_sample call)."""
+        np.random.random_sample call).
+        top_k / top_p (with a temperature only: ValueError without): every draw behind top-k / nucleus truncation
+        (HierarchicalDecoder.forward); such a call leaves self.last_logp (B, n_target, 24), the drawn tokens' log-probabilities under
+        the truncated distribution (NaN where a tick took the argmax), every other call leaves it None."""
         batch_size, _, measure_seq_len = past_context.size()
+        if temperature is None and (top_k is not None or top_p is not None):
+            raise ValueError("top_k / top_p without a temperature")
+        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
+            raise ValueError(f"top_p {top_p!r} outside (0, 1]")
+        ops._top_k(top_k)                                          # (ValueError for a top_k that is no integer)
         if temperature is None and uniforms is not None:
             raise ValueError("uniforms without a temperature")
         if temperature is not None:
@@ -265,12 +273,15 @@ class LatentRNN(Model):
         else:
             seed = zp[:, -1, :].unsqueeze(1)
         return self.forward_generation(comb_context, measures_to_generate, seed, measure_seq_len, teacher_forcing,
-                                       eps_ar=eps_ar, temperature=temperature, uniforms=uniforms)
+                                       eps_ar=eps_ar, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p)
 
     def forward_generation(self, context_vector, measures_to_gen, seed, measure_seq_len, teacher_forcing=False,
-                           eps_ar=None, temperature=None, uniforms=None):
-        """latent_rnn.py:211-263; temperature / uniforms (B, measures_to_gen, 24): see forward"""
+                           eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None):
+        """latent_rnn.py:211-263; temperature / uniforms (B, measures_to_gen, 24) / top_k / top_p / self.last_logp: see forward"""
+        if temperature is None and (top_k is not None or top_p is not None):
+            raise ValueError("top_k / top_p without a temperature")
         batch_size = context_vector.size(1)
+        self.last_logp = None
         Hg = self.gen_hidden
         if teacher_forcing or not self.auto_reg:
             if self.auto_reg:
@@ -282,24 +293,30 @@ class LatentRNN(Model):
                                   "generation_linear.weight", "generation_linear.bias")
             z_out = z2d.view(batch_size, measures_to_gen, -1)
             # rows ordered (b, measure): all measures in one call
-            w, s = self._decode(z2d, temperature, uniforms.reshape(batch_size * measures_to_gen, -1) if uniforms is not None else None)
+            w, s = self._decode(z2d, temperature, uniforms.reshape(batch_size * measures_to_gen, -1) if uniforms is not None else None,
+                                top_k, top_p)
+            lp = self.vae_model.decoder.last_logp
+            self.last_logp = lp.view(batch_size, measures_to_gen, measure_seq_len) if lp is not None else None
             weights = w.view(batch_size, measures_to_gen, measure_seq_len, -1)
             samples = s.view(batch_size, 1, measures_to_gen * measure_seq_len)
             return weights, samples, z_out
         hidden = context_vector
         gen_rnn_input = seed
-        z_out, weights, samples = [], [], []
+        z_out, weights, samples, logps = [], [], [], []
         for i in range(measures_to_gen):
             rnn_out, hidden = self._bigru("generation_rnn", gen_rnn_input.contiguous(), None, hidden, Hg, self.z_dim)
             gen_z = _LinearFn.apply(rnn_out.reshape(batch_size, -1), self.flat_for_autograd(), self,
                                     "generation_linear.weight", "generation_linear.bias")
             z_out.append(gen_z.view(batch_size, 1, -1))
-            w, s = self._decode(gen_z, temperature, uniforms[:, i] if uniforms is not None else None)
+            w, s = self._decode(gen_z, temperature, uniforms[:, i] if uniforms is not None else None, top_k, top_p)
+            logps.append(self.vae_model.decoder.last_logp)
             samples.append(s)
             weights.append(w.unsqueeze(1))
             # (the reference re-encodes the LAST generated measure too, latent_rnn.py:259, and drops the result)
             if i + 1 < measures_to_gen or self.encode_unused_target:
                 gen_rnn_input = self.get_z_seq(s, eps_ar[i] if eps_ar is not None else None)
+        if logps and logps[0] is not None:
+            self.last_logp = torch.stack(logps, 1)
         return torch.cat(weights, 1), torch.cat(samples, 2), torch.cat(z_out, 1)
 
     def save(self):

@@ -35,14 +35,24 @@ class LatentRNNTester(object):
         return fn(tensor.cpu()) if fn is not None else None
 
     def generate(self, tensor_past, tensor_future, tensor_target, num_target_measures, eval=False, temperature=None,
-                 num_variations=1):
+                 num_variations=1, top_k=None, top_p=None):
         """-> (gen_score | None, gen_score_tensor (B, n_past + n_target + n_future, 24), original_score | None)
         (latent_rnn_tester.py:197-266)
         temperature (a finite float): `num_variations` fillings of the same gap -- the (one-row) contexts are expanded to that many
         rows, every row's tokens are drawn from softmax(temperature * weights) with its own uniforms (one
         np.random.random_sample((num_variations, n_target, 24)) call: np.random.seed reproduces a call) and gen_score_tensor has
         num_variations rows.  Up to sixteen decoder rows (variations x target measures on the non-auto-regressive path) are one
-        register-resident launch.  temperature None: one filling by the argmax, as before."""
+        register-resident launch.  temperature None: one filling by the argmax, as before.
+        top_k / top_p (with a temperature only: ValueError without; top_p in (0, 1]): every token is drawn behind top-k / nucleus
+        truncation (HierarchicalDecoder.forward) -- the remedy for the mass the many zero logits of a post-ReLU head carry.  Such a call
+        leaves self.last_logp (num_variations, n_target): per generated measure the sum of its 24 drawn tokens' log-probabilities
+        under the truncated distribution, NaN where a tick fell back to the argmax -- the score to rank the variations by (top_p=1.0
+        scores them without truncating); every other call leaves it None.  The return tuple is the same."""
+        if temperature is None and (top_k is not None or top_p is not None):
+            raise ValueError("top_k / top_p need a temperature")
+        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
+            raise ValueError(f"top_p {top_p!r} outside (0, 1]")
+        ops._top_k(top_k)                                          # (ValueError for a top_k that is no integer)
         if tensor_target is not None:
             if num_target_measures is not None:
                 assert num_target_measures == tensor_target.size(1)
@@ -67,8 +77,11 @@ class LatentRNNTester(object):
                 tensor_target = tensor_target.expand(num_variations, -1, -1).contiguous()
         with torch.no_grad():
             weights, gen_target, _ = self.model(past_context=tensor_past, future_context=tensor_future, target=None,
-                                                measures_to_generate=num_target_measures, train=False, temperature=temperature)
+                                                measures_to_generate=num_target_measures, train=False, temperature=temperature,
+                                                top_k=top_k, top_p=top_p)
         self.last_weights = weights
+        lp = getattr(self.model, "last_logp", None)
+        self.last_logp = lp.sum(-1) if lp is not None else None
         torch.cuda.synchronize()
         ops.check_chains("LatentRNNTester.generate")                   # persistent kernels: never hand back results of a failed launch
         if tensor_target is not None and eval:

@@ -68,11 +68,11 @@ class _EncoderFn(ops.TrackedFunction):
 class _DecoderFn(ops.TrackedFunction):
     @staticmethod
     def forward(ctx, z, flat, dec, target, teacher_forced, mask_beat, mask_tick, multinomial_seed=0, temperature=None,
-                uniforms=None):
+                uniforms=None, top_k=None, top_p=None, logp=None):
         need = ops.outer_grad() and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         weights, samples, ws = ops.decoder_fwd(dec.cfg, z.contiguous(), target, teacher_forced, flat, mask_beat,
                                                mask_tick, save=need, multinomial_seed=multinomial_seed,
-                                               temperature=temperature, uniforms=uniforms)
+                                               temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, logp=logp)
         ctx.dec, ctx.ws, ctx.mb, ctx.mt = dec, ws, mask_beat, mask_tick
         if getattr(dec, "keep_ws", False):         # test hook: lets a parity test read intermediates (ops.ws_field)
             dec.last_ws = ws
@@ -88,7 +88,7 @@ class _DecoderFn(ops.TrackedFunction):
         dec = ctx.dec
         if dweights is None:                            # nothing downstream depends on the weights
             ctx.ws = None
-            return (None,) * 10
+            return (None,) * 13
         weights, samples = ctx.saved_tensors
         grads = dec.owner.grad if dec.owner.trainable else None
         dz = ops.decoder_bwd(dec.cfg, dweights.contiguous(), weights, samples, dec.owner.flat, grads, ctx.mb, ctx.mt,
@@ -99,7 +99,7 @@ class _DecoderFn(ops.TrackedFunction):
             if dp.world_size() > 1:
                 # behind the decoder's leaf GEMMs on the side streams, without holding up the encoder's backward
                 dp.start_bucket(grads, dec.owner.decoder_arena_start, grads.numel(), join_side=True)
-        return (dz,) + (None,) * 9
+        return (dz,) + (None,) * 12
 
 
 class _ReparamFn(torch.autograd.Function):
@@ -258,7 +258,8 @@ class HierarchicalDecoder(torch.nn.Module):
                f'{self.dropout},' \
                f')'
 
-    def forward(self, z, score_tensor, train, masks=None, teacher_forced=None, temperature=None, uniforms=None):
+    def forward(self, z, score_tensor, train, masks=None, teacher_forced=None, temperature=None, uniforms=None, top_k=None,
+                top_p=None):
         """z (B,Z), score_tensor (B,24) -> weights (B,24,V), samples (B,1,24)   (decoder.py:412-453).
         One Bernoulli(0.5) teacher-forcing coin per call when train=True (decoder.py:431-434); it can be
         injected with `teacher_forced=`.
@@ -266,8 +267,18 @@ class HierarchicalDecoder(torch.nn.Module):
         uniforms[b, t] (csrc/sample.h: np.random.choice's order, as ConstraintModelGaussianReg.generate) and feeds it back; uniforms
         (B,24) float64, host or device, or None: one np.random.random_sample((B, 24)) call.  Inference only (ValueError with
         train=True); a call whose `teacher_forced=True` was injected ignores both.  `sampling = 'multinomial'` and the training path
-        are as they were.  The arguments are checked before anything random is drawn: a rejected call leaves every stream alone."""
+        are as they were.  The arguments are checked before anything random is drawn: a rejected call leaves every stream alone.
+        top_k (an int; None, <= 0 or >= V: off) / top_p (in (0, 1]; None or 1: off), with a temperature only (ValueError without):
+        every draw is taken from the top_k highest-ranked tokens, and among those from the shortest prefix of the ranking that
+        holds top_p of their mass (csrc/sample.h: ranked by temperature * weight descending, lowest index first among equals).  Such a
+        call leaves self.last_logp (B,24): the drawn tokens' log-probabilities under the truncated distribution, NaN where a tick
+        took the argmax; every other call leaves it None."""
         T = self.cfg.beats * self.cfg.ticks_per_beat
+        if temperature is None and (top_k is not None or top_p is not None):
+            raise ValueError("top_k / top_p without a temperature")
+        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
+            raise ValueError(f"top_p {top_p!r} outside (0, 1]")
+        ops._top_k(top_k)                                          # (ValueError for a top_k that is no integer)
         if uniforms is not None and temperature is None:
             raise ValueError("uniforms without a temperature")
         if temperature is not None:
@@ -279,6 +290,7 @@ class HierarchicalDecoder(torch.nn.Module):
                 uniforms = torch.as_tensor(uniforms, dtype=torch.float64)
                 if tuple(uniforms.shape) != (z.size(0), T):
                     raise ValueError(f"uniforms of shape {tuple(uniforms.shape)}, expected {(z.size(0), T)}")
+        self.last_logp = None
         if teacher_forced is None:
             if self.use_teacher_forcing and train:
                 teacher_forced = random.random() < self.teacher_forcing_prob
@@ -310,6 +322,12 @@ class HierarchicalDecoder(torch.nn.Module):
             if uniforms is None:
                 uniforms = torch.from_numpy(np.random.random_sample((batch_size, T)))
             u = uniforms.to(z.device).contiguous()
+            if top_k is not None or top_p is not None:
+                logp = torch.empty(batch_size, T, dtype=torch.float32, device=z.device)
+                out = _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u,
+                                      top_k, top_p, logp)
+                self.last_logp = logp
+                return out
             return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u)
         seed = 0
         if self.sampling == 'multinomial' and not teacher_forced:
@@ -414,11 +432,12 @@ class MeasureVAE(Model):
                                         teacher_forced=teacher_forced, masks=dec_masks)
         return weights, samples, z_dist, prior_dist, z_tilde, z_prior
 
-    def decode(self, z, temperature=None, uniforms=None):
+    def decode(self, z, temperature=None, uniforms=None, top_k=None, top_p=None):
         """z (B,Z) -> (weights (B,24,V), samples (B,1,24)): the free-running decoder alone (what VAETester.decode_mid_point does with
-        a latent), by the argmax or -- temperature set -- drawn from softmax(temperature * weights) (HierarchicalDecoder.forward)."""
+        a latent), by the argmax or -- temperature set -- drawn from softmax(temperature * weights), behind top-k / nucleus truncation
+        with top_k / top_p (HierarchicalDecoder.forward; the draws' log-probabilities: self.decoder.last_logp)."""
         dummy = torch.zeros(z.shape[0], self.num_ticks_per_measure, device=z.device)
-        return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms)
+        return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p)
 
     def _standard_normal(self, like):
         """N(0, 1) of the latent's shape (measure_vae.py:122-125): the constant loc / scale tensors are built once."""

@@ -229,13 +229,19 @@ def decoder_ws(cfg, B, save, device):
 
 
 def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tick=None, save=False, ws=None,
-                multinomial_seed=0, temperature=None, uniforms=None):
+                multinomial_seed=0, temperature=None, uniforms=None, top_k=None, top_p=None, logp=None):
     """z [B,Z] -> weights [B,T,V], samples [B,1,T] int64, ws.  multinomial_seed != 0: the fed-back tokens are drawn from
     softmax(weights) (decoder.py:506-509) instead of the argmax.  temperature + uniforms ([B,T] float64 on the device, one uniform
     per row and tick): inet_vae_decoder_sample -- a free-running call whose tokens are drawn from softmax(temperature * weights) by
-    csrc/sample.h's rule."""
+    csrc/sample.h's rule.  top_k / top_p / logp (with a temperature only): inet_vae_decoder_sample_ex -- the draw behind sample.h's
+    top-k / nucleus truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off, else in (0, 1)), and logp, a contiguous float32
+    [B,T] device tensor, receives the drawn tokens' log-probabilities under the truncated distribution (NaN where a tick took the argmax)."""
     if (temperature is None) != (uniforms is None):
         raise ValueError("decoder_fwd: temperature and uniforms go together")
+    if temperature is None and (top_k is not None or top_p is not None or logp is not None):
+        raise ValueError("decoder_fwd: top_k / top_p / logp without a temperature")
+    if top_p is not None and not (0.0 < float(top_p) <= 1.0):
+        raise ValueError(f"decoder_fwd: top_p {top_p!r} outside (0, 1]")
     _f32c(z); _f32c(params)
     B = z.shape[0]
     T = cfg.beats * cfg.ticks_per_beat
@@ -246,12 +252,21 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
             raise ValueError(f"decoder_fwd: temperature {temperature!r} is not finite")
         if not (uniforms.is_cuda and uniforms.dtype == torch.float64 and uniforms.is_contiguous() and tuple(uniforms.shape) == (B, T)):
             raise ValueError(f"decoder_fwd: uniforms must be a contiguous float64 device tensor of shape {(B, T)}")
+        if logp is not None and not (logp.is_cuda and logp.dtype == torch.float32 and logp.is_contiguous() and tuple(logp.shape) == (B, T)):
+            raise ValueError(f"decoder_fwd: logp must be a contiguous float32 device tensor of shape {(B, T)}")
     if target is not None:
         _i64c(target)
     if ws is None:
         ws = decoder_ws(cfg, B, save, z.device)
     weights = torch.empty(B, T, cfg.num_notes, dtype=torch.float32, device=z.device)
     samples = torch.empty(B, 1, T, dtype=torch.int64, device=z.device)
+    if temperature is not None and (top_k is not None or top_p is not None or logp is not None):
+        check(_lib.lib().inet_vae_decoder_sample_ex(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
+                                                    ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
+                                                    _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(logp), stream_ptr()),
+              "inet_vae_decoder_sample_ex")
+        _hold(uniforms, logp)
+        return weights, samples, ws
     if temperature is not None:
         check(_lib.lib().inet_vae_decoder_sample(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
                                                  ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
@@ -320,6 +335,31 @@ def sample_temperature(weights2d, temperature, uniforms):
     check(_lib.lib().inet_sample_temperature(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
                                              uniforms.stride(0), ptr(out), 1, stream_ptr()), "inet_sample_temperature")
     return out
+
+
+def _top_k(top_k):
+    """top_k as the C int the library takes: None = 0 (off), anything beyond an int's range is off as well; ValueError for a value
+    that is no integer (2.5, NaN)"""
+    if top_k is None:
+        return 0
+    if isinstance(top_k, bool) or top_k != top_k or top_k in (float("inf"), float("-inf")) or int(top_k) != top_k:
+        raise ValueError(f"top_k {top_k!r} is not an integer")
+    return max(0, min(int(top_k), 2 ** 31 - 1))
+
+
+def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, want_logp=True):
+    """inet_sample_truncated: sample_temperature() behind csrc/sample.h's top-k / nucleus truncation (top_k None, <= 0 or >= V: off;
+    top_p None or 1: off, else in (0, 1)) -> (tokens [rows] int64, logp [rows] float32: the drawn tokens' log-probabilities under
+    the truncated distribution, NaN where a row took the argmax rule; None with want_logp=False)."""
+    rows, V = weights2d.shape
+    assert weights2d.stride(1) == 1 and weights2d.dtype == torch.float32
+    assert uniforms.is_cuda and uniforms.dtype == torch.float64 and tuple(uniforms.shape) == (rows,)
+    out = torch.empty(rows, dtype=torch.int64, device=weights2d.device)
+    logp = torch.empty(rows, dtype=torch.float32, device=weights2d.device) if want_logp else None
+    check(_lib.lib().inet_sample_truncated(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
+                                           uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
+                                           ptr(logp), 1, stream_ptr()), "inet_sample_truncated")
+    return out, logp
 
 
 def reparam_kl(mu, ls, eps, kl_sum=None, want_sigma=False):

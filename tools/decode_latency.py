@@ -1,6 +1,8 @@
 """eval-mode decode latency at small batch (bench.decode_latency_extra): python tools/decode_latency.py
 --temperature T: only the sampled decode (temperature T, uniforms on the device) beside the argmax decode of the same build, b = 1, 4
-and 16, five rounds of 300 calls each (median and range per call)."""
+and 16, five rounds of 300 calls each (median and range per call).
+--top-k K / --top-p P (with --temperature): a third column, the truncated decode (top-k / nucleus truncation in front of every draw, and
+the draws' log-probabilities), and its cost per tick over the sampled decode."""
 import os, sys
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,6 +13,8 @@ if "--temperature" in sys.argv:
     import statistics, time
     from inpaintnet_amd import ops
     temperature = float(sys.argv[sys.argv.index("--temperature") + 1])
+    top_k = int(sys.argv[sys.argv.index("--top-k") + 1]) if "--top-k" in sys.argv else None
+    top_p = float(sys.argv[sys.argv.index("--top-p") + 1]) if "--top-p" in sys.argv else None
     vae = wl.model
     vae.eval()
 
@@ -26,14 +30,19 @@ if "--temperature" in sys.argv:
                     call()
                 torch.cuda.synchronize()
                 out.append(1e3 * (time.perf_counter() - t0) / n)
-        return f"{statistics.median(out):.4f} ms ({min(out):.4f} .. {max(out):.4f})"
+        return statistics.median(out), f"{statistics.median(out):.4f} ms ({min(out):.4f} .. {max(out):.4f})"
 
     for b in (1, 4, 16):
         z = torch.randn(b, vae.latent_space_dim, device="cuda")
         dummy = torch.zeros(b, 24, device="cuda")
         u = torch.rand(b, 24, dtype=torch.float64, device="cuda")
-        print(f"b = {b}: argmax {rounds(lambda: vae.decoder(z, dummy, train=False))}, temperature {temperature} "
-              f"{rounds(lambda: vae.decoder(z, dummy, train=False, temperature=temperature, uniforms=u))}, chain status {ops.chain_status()}")
+        _, argmax = rounds(lambda: vae.decoder(z, dummy, train=False))
+        sampled, text = rounds(lambda: vae.decoder(z, dummy, train=False, temperature=temperature, uniforms=u))
+        line = f"b = {b}: argmax {argmax}, temperature {temperature} {text}"
+        if top_k is not None or top_p is not None:
+            trunc, text = rounds(lambda: vae.decoder(z, dummy, train=False, temperature=temperature, uniforms=u, top_k=top_k, top_p=top_p))
+            line += f", top_k {top_k} top_p {top_p} {text} (+{1e3 * (trunc - sampled) / 24:.2f} us per tick)"
+        print(line + f", chain status {ops.chain_status()}")
     sys.exit(0)
 r = bench.decode_latency_extra(wl.model, iters=200)["decoder_eval"]
 print({k: v["ms_per_call"] for k, v in r.items() if isinstance(v, dict)})
