@@ -351,6 +351,25 @@ int inet_arnn_sample(int R, int L, int E, int Hc, int H, int U, int V, const flo
                      const float* W_ih1, const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
                      const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
                      int64_t* tokens, float* ws, int64_t ws_floats, void* stream);
+/* The same behind TOP-K / NUCLEUS TRUNCATION, with the drawn tokens' log-probabilities and the logits they were drawn from.  The rule
+ * is the one stated for inet_vae_decoder_sample_ex, applied to s = temperature * logits of the note head (not ReLU'd: ties are rare
+ * there, and still fall lowest index first).  logp (nullable; [R][L] floats on the device) receives (s_tok - m) - log(S) as f32; a
+ * tick that takes the argmax rule (a NaN among s, a maximum or total that is not finite, a uniform outside [0, 1) or NaN) has a NaN
+ * logp.  logits (nullable; [R][L][V] floats on the device) receives every tick's note-head output, the x of that rule.
+ * inet_arnn_sample is this call with (top_k, top_p, logp, logits) = (0, 1.0, null, null) and runs the kernels it always ran; a call
+ * with truncation on, a logp or a logits pointer runs the truncating build of the persistent token pass or, for the other shapes, the
+ * truncating head of the per-tick launches, and never a kernel that ignores them: its launch labels start with "trunc_"
+ * (trunc_arnn_token_sample R.. L.. V.., trunc_arnn_ticks L.. V..).  The persistent pass has a truncating build for V <= 64; with
+ * H = U = 256 and 64 < V <= 128 a truncated call runs the per-tick launches.  With (0, 1.0) and a logp or logits pointer the tokens
+ * equal inet_arnn_sample's bit for bit wherever both run the same kind of launch (every shape but that one, where the logits are
+ * summed in another order and the tokens agree outside the rule's rounding margins).
+ * The workspace is inet_arnn_sample_ws_floats'.  -1 where inet_arnn_sample returns it, and for a top_p that is NaN, <= 0 or > 1. */
+int inet_arnn_sample_ex(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
+                        int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,
+                        const float* W_ih1, const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
+                        const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
+                        int64_t* tokens, float* ws, int64_t ws_floats, int top_k, double top_p, float* logp, float* logits,
+                        void* stream);
 /* nn.Embedding forward / backward (rows of E floats gathered by int64 index; backward accumulates with atomics).
  * row_scale (nullable, [rows]) multiplies each gathered row: the Dropout2d on the shifted note embeddings
  * (drop_input, anticipation_rnn_gauss_reg_model.py:437-442) and the all-zero first time step (:373-376). */

@@ -397,7 +397,7 @@ class ConstraintModelGaussianReg(Model):
         return [torch.stack(ws, 1)], gen
 
     @torch.no_grad()
-    def generate(self, tensor_score, tensor_metadata, constraints_location, temperature=1.):
+    def generate(self, tensor_score, tensor_metadata, constraints_location, temperature=1., top_k=None, top_p=None, keep_weights=False):
         """Temperature-sampled generation (anticipation_rnn_gauss_reg_model.py:570-679).  Shapes (1, L), (1, L, M), (1, L) as the
         reference takes them, or a batch (B, 1, L), (B, 1, L, M), (B, 1, L) of independent rows.  Leaves the model in eval().
 
@@ -408,7 +408,17 @@ class ConstraintModelGaussianReg(Model):
         MULTIPLIES the logits.  Every tick is drawn, constrained ones included.  The draws are one np.random.random_sample() double
         per tick, all taken up front as np.random.random_sample((B, L)), row 0 first: with B = 1 the global stream is consumed
         exactly as by the reference.  -> (score | None (dataset.tensor_to_score where the dataset has it; a list per row for a
-        batch), gen_chorale int64 (1, L) or (B, 1, L) on the model's device, tensor_metadata)."""
+        batch), gen_chorale int64 (1, L) or (B, 1, L) on the model's device, tensor_metadata).
+
+        top_k / top_p: the draw behind top-k / nucleus truncation of softmax(temperature * logits) (csrc/sample.h's rule; top_k None,
+        <= 0 or >= V: off; top_p in (0, 1], None or 1: off).  With one of them given the call leaves self.last_logp, float32 of
+        gen_chorale's shape: every drawn token's log-probability under the distribution it was drawn from, NaN where a tick took the
+        argmax rule (top_p=1.0 scores without truncating); else None.  keep_weights: self.last_weights (B, L, V) = the note head's
+        logits of every tick; else None.  A call without the three runs the kernels it always ran."""
+        k = ops._top_k(top_k)
+        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
+            raise ValueError(f"generate: top_p {top_p!r} outside (0, 1]")
+        self.last_logp = self.last_weights = None
         self.eval()
         batched = tensor_score.dim() == 3
         score = tensor_score if batched else tensor_score[None]
@@ -438,10 +448,19 @@ class ConstraintModelGaussianReg(Model):
             hc[:, l, 0], hc[:, l, 1] = hT.reshape(B, H), cT.reshape(B, H)
         u = np.random.random_sample((B, L))
         emb, *net = self._generation_weights()
-        toks = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc)
+        score_it = top_k is not None or top_p is not None
+        logp = weights = None
+        if score_it or keep_weights:
+            toks, logp, weights = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc, top_k=k, top_p=top_p,
+                                                  want_logp=score_it, want_logits=bool(keep_weights))
+        else:
+            toks = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc)
         torch.cuda.synchronize()
         ops.check_chains("generate")                                           # never hand back tokens of a failed launch
         gen = toks.view(B, 1, L)
+        if logp is not None:
+            self.last_logp = logp.view(B, 1, L) if batched else logp.view(1, L)
+        self.last_weights = weights
         to_score = getattr(self.dataset, "tensor_to_score", None)
         if not batched:
             gen = gen[0]

@@ -16,6 +16,12 @@ from .arnn import AnticipationRNNGaussianRegTrainer
 from .helpers import to_cuda_variable_long
 
 
+def _num_variations(n):
+    if isinstance(n, bool) or n != n or int(n) != n or n < 1:
+        raise ValueError(f"generation: num_variations {n!r} is not a positive integer")
+    return int(n)
+
+
 class AnticipationRNNTester(object):
     def __init__(self, dataset, model):
         self.dataset = dataset
@@ -26,6 +32,7 @@ class AnticipationRNNTester(object):
         self.filepath = os.path.join('models/', self.model.__repr__())
         self.batch_size = 1
         self.measure_seq_len = 24                    # (:16-18: set from the dataset, then fixed to 24)
+        self.last_logp = None                        # generation(top_k= / top_p=): (num_variations, num_measures_gen)
 
     def _to_score(self, tensor):
         fn = getattr(self.dataset, "tensor_to_score", None)
@@ -93,15 +100,22 @@ class AnticipationRNNTester(object):
         return self._generate_window(tensor_score.view(num_voices, seq_len),
                                      tensor_metadata.view(num_voices, seq_len, num_metadata), start_measure=8, num_measures_gen=2)
 
-    def generation(self, tensor_score, start_measure, num_measures_gen, tensor_metadata=None):
+    def generation(self, tensor_score, start_measure, num_measures_gen, tensor_metadata=None, temperature=1.5, num_variations=1,
+                   top_k=None, top_p=None):
         """Generates measures start_measure .. start_measure + num_measures_gen - 1 (1-based) of a score with temperature 1.5
         (:185-243) -> (gen_score | None, gen_score_tensor (1, L): past | generated | future, original_score | None).
+
+        num_variations fillings of the one gap come from ONE batched generate() call over num_variations copies of the score, its
+        metadata and its constraints: gen_score_tensor is (num_variations, L), past and future the input's in every row.  top_k /
+        top_p: generate()'s truncation; with one of them self.last_logp is (num_variations, num_measures_gen) float32, the sum of the
+        window's log-probabilities per measure (NaN where a tick took the argmax rule) -- what to rank the fillings by; else None.
 
         tensor_score (1, L) tokens (None: a random score of dataset.iterator_gen()); its metadata come from
         dataset.transposed_score_and_metadata_tensors where the dataset has it and a score can be built, else from
         `tensor_metadata` (1, L, M).  Where the reference trims a score whose length is not a multiple of a measure it indexes
         one tick (`tensor_score[:, n * len]`, :211-212) and compares a tick count with 16 measures (`min(16, size(1))`, :213):
         here the score is cut to whole measures and to at most 16 of them."""
+        num_variations = _num_variations(num_variations)
         if tensor_score is None:
             if not hasattr(self.dataset, "iterator_gen"):
                 raise ValueError("generation: tensor_score is None and the dataset has no iterator_gen()")
@@ -122,9 +136,13 @@ class AnticipationRNNTester(object):
         num_measures = min(16, tensor_score.size(1) // self.measure_seq_len)
         tensor_score = tensor_score[:, :num_measures * self.measure_seq_len]
         tensor_metadata = tensor_metadata[:, :num_measures * self.measure_seq_len]
-        return self._generate_window(tensor_score, tensor_metadata, start_measure, num_measures_gen)
+        return self._generate_window(tensor_score, tensor_metadata, start_measure, num_measures_gen, temperature, num_variations,
+                                     top_k, top_p)
 
-    def _generate_window(self, tensor_score, tensor_metadata, start_measure, num_measures_gen):
+    def _generate_window(self, tensor_score, tensor_metadata, start_measure, num_measures_gen, temperature=1.5, num_variations=1,
+                         top_k=None, top_p=None):
+        num_variations = _num_variations(num_variations)
+        self.last_logp = None
         constraints_location = torch.zeros_like(tensor_score)
         measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
         start_tick = (start_measure - 1) * measure_seq_len
@@ -136,12 +154,25 @@ class AnticipationRNNTester(object):
         tensor_past = tensor_score[:, :start_tick]
         tensor_future = tensor_score[:, end_tick:]
         tensor_target = tensor_score[:, start_tick:end_tick]
-        _, gen_target, _ = self.model.generate(tensor_score=tensor_score, tensor_metadata=tensor_metadata,
-                                               constraints_location=constraints_location, temperature=1.5)
-        gen_target = gen_target[:, start_tick:end_tick]
-        gen_score_tensor = torch.cat((tensor_past, gen_target, tensor_future), 1)
         original_tensor = torch.cat((tensor_past, tensor_target, tensor_future), 1)
-        return self._to_score(gen_score_tensor), gen_score_tensor, self._to_score(original_tensor)
+        if num_variations == 1 and top_k is None and top_p is None:
+            _, gen_target, _ = self.model.generate(tensor_score=tensor_score, tensor_metadata=tensor_metadata,
+                                                   constraints_location=constraints_location, temperature=temperature)
+            gen_target = gen_target[:, start_tick:end_tick]
+            gen_score_tensor = torch.cat((tensor_past, gen_target, tensor_future), 1)
+            return self._to_score(gen_score_tensor), gen_score_tensor, self._to_score(original_tensor)
+        # the one row as num_variations rows of ONE batched call: (B, 1, L), (B, 1, L, M), (B, 1, L)
+        n, L = num_variations, tensor_score.size(1)
+        _, gen, _ = self.model.generate(tensor_score=tensor_score[:1].unsqueeze(0).expand(n, 1, L).contiguous(),
+                                        tensor_metadata=tensor_metadata[:1].unsqueeze(0).expand(n, 1, L, -1).contiguous(),
+                                        constraints_location=constraints_location[:1].unsqueeze(0).expand(n, 1, L).contiguous(),
+                                        temperature=temperature, top_k=top_k, top_p=top_p)
+        gen_target = gen[:, 0, start_tick:end_tick].to(tensor_score.dtype)
+        gen_score_tensor = torch.cat((tensor_past.expand(n, -1), gen_target, tensor_future.expand(n, -1)), 1)
+        if self.model.last_logp is not None:
+            self.last_logp = self.model.last_logp[:, 0, start_tick:end_tick].reshape(n, num_measures_gen, measure_seq_len).sum(-1)
+        scores = [self._to_score(row[None]) for row in gen_score_tensor]
+        return (scores[0] if n == 1 else scores) if scores[0] is not None else None, gen_score_tensor, self._to_score(original_tensor)
 
     def process_batch_data(self, batch):
         """(score, metadata) -> device tensors, the default constraint window (measures 8 and 9), start / end tick (:245-260)."""

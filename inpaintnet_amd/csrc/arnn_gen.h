@@ -18,5 +18,9 @@ int arnn_generate(const ArnnGenNet& net, int L, const float* oc0, long oc_stride
 // AnticipationRNN's generate (anticipation_rnn_gauss_reg_model.py:570-679): R independent rows, each L ticks with the token DRAWN from
 // softmax(temp * logits) by the uniform uniforms[r][t] (sample.h).  oc row r at oc0 + r * oc_bstride, hc_init [R][2][2][H] or null.
 size_t arnn_sample_ws_floats(const ArnnGenNet& net, int R, int L);
+// top_k / top_p: sample.h's truncation in front of the draw (0 / 1.0: off); logp [R][L] (nullable): the drawn tokens' log-probabilities
+// under the truncated distribution, NaN where a tick took the argmax rule; logits [R][L][V] (nullable): what each tick drew from.
+// Truncation on or one of the two pointers given: the truncating kernels (labels trunc_...); otherwise the kernels of the sampling build.
 int arnn_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
-                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s);
+                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k = 0,
+                double top_p = 1.0, float* logp = nullptr, float* logits = nullptr);

@@ -35,9 +35,13 @@
 // The sampling build (SAMPLE = true: ConstraintModelGaussianReg.generate, anticipation_rnn_gauss_reg_model.py:570-679) draws each token
 // from softmax(T * logits) with a host-drawn uniform (sample.h) instead of the argmax, and runs up to 8 independent rows ("teams" of 13
 // workgroups, each with its own exchange) in the workgroups that the argmax build leaves idle.
+// The truncating build (TRUNC = true, V <= 64: inet_arnn_sample_ex) puts sample.h's top-k / nucleus truncation in front of that draw,
+// reports the drawn tokens' log-probabilities (the logarithms are taken behind the last tick) and, where asked, every tick's logits;
+// head_trunc_b1_kernel does the same for the per-tick launches.  A call without truncation, logp or logits runs the sampling build.
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <optional>
 #include "chain.h"
 #define INET_GRANULE_KID chain::K_ARNN_GEN
 #include "granule.h"
@@ -66,6 +70,8 @@ struct GenArgs {
     // sampling build: `rows` independent teams of 13 workgroups (pre, hc_init, uniforms, tokens and the exchange per team; T0
     // shared), the head draws token t from softmax(temp * logits) with the uniform uniforms[team][t] (sample.h)
     int rows; float temp; const double* uniforms;
+    // truncating build (TRUNC: sample.h's truncation in front of the draw): logp [rows][L] or null, logits [rows][L][V] or null
+    int top_k; double top_p; float* logp; float* logits;
 };
 #define GEN_STAMP(who, t, i) do { if (a.stamps && tid == 0) a.stamps[((long)(who) * a.L + (t)) * 8 + (i)] = wall_clock64(); } while (0)
 
@@ -142,8 +148,16 @@ __device__ __forceinline__ void recurrent_role(const GenArgs& a, int k, const fl
 }
 
 // SAMPLE = false: the argmax head (the free-running forward's token pass); true: the sampling head and teams (generate)
-template <int NV, bool SAMPLE>
+// TRUNC (the truncating build of the sampling build; behind SAMPLE so that every build without it keeps its parameters): top-k / nucleus
+// truncation in front of the draw, the drawn token's log-probability and the tick's logits.  Every wave of C draws for itself; the
+// waves 4 .. 7 own no unit of layer 0 and reach the next tick's first barrier early (it waits for h1: Bi's product and two hand-offs),
+// so wave 6 stores the logits and wave 7 files the tick's (S, s_tok - m) there.  The f64 logarithm inside the tick spills (256 VGPRs, 2
+// spilled next to the 160 weight registers), as it did in decode_b1.hip: the workgroup takes all logarithms behind the last tick, one
+// tick per thread, where the weights' registers are free.  The terms are filed in the first three floats of the tick's own row of
+// `pre`: the row's 256 readers are this workgroup's unit threads, which consumed it in front of the tick's first barrier.
+template <int NV, bool SAMPLE, bool TRUNC = false>
 __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
+    static_assert(SAMPLE || !TRUNC, "the truncating build is a sampling build");
     __shared__ __attribute__((aligned(16))) float xs[2][XS];
     __shared__ __attribute__((aligned(16))) float us[GH];
     __shared__ float ps[8][64 * NV];
@@ -244,6 +258,9 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
             for (int g = 0; g < 4; ++g) pr[g] = pre[g * GH + tid];
             if (!get_n<4>(e_hh0 + tid, GH, 1u, a.status, hh, hw)) *bad = 1;
         }
+        [[maybe_unused]] int done = 0;                        // (truncating build: the ticks finished)
+        [[maybe_unused]] float* const lrow = TRUNC && a.logits ? a.logits + (long)team * a.L * a.V : nullptr;
+        [[maybe_unused]] float* const terms = TRUNC && a.logp ? const_cast<float*>(pre) : nullptr;
         for (int t = 0; t < a.L; ++t) {
             const bool more = t + 1 < a.L;
             if constexpr (SAMPLE) {
@@ -330,7 +347,31 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                         nan |= sv[j] != sv[j];
                         ms = fmaxf(ms, sv[j]);
                     }
-                    if (!__ballot(nan)) bi = sample::pick<NV>(sv, wave_max_dpp(ms), u, a.V, lane);
+                    if constexpr (TRUNC) {
+                        // (one wave: plain vector stores of what every wave holds)
+                        if (lrow && q == 6) {
+                            float* const row = lrow + (long)t * a.V;
+#pragma unroll
+                            for (int j = 0; j < NV; ++j)
+                                if (lane + 64 * j < a.V) row[lane + 64 * j] = lg[j];
+                        }
+                        float gap = 0.f;
+                        double tot = 0.0;
+                        if (!__ballot(nan)) {
+                            const float mw = wave_max_dpp(ms);
+                            sample::truncate<NV>(sv, mw, a.top_k, a.top_p, a.V, lane);
+                            bi = sample::pick<NV>(sv, mw, u, a.V, lane, tot);
+                            if (bi >= 0) gap = sample::logp_gap<NV>(sv, mw, bi);
+                        }
+                        // (a tick that falls back to the argmax rule below files S = NaN: its logp comes out NaN)
+                        if (terms && tid == NT - 64) {
+                            float* const term = terms + (long)t * G4;
+                            *reinterpret_cast<double*>(term) = bi >= 0 ? tot : (double)__builtin_nanf("");
+                            term[2] = gap;
+                        }
+                    } else {
+                        if (!__ballot(nan)) bi = sample::pick<NV>(sv, wave_max_dpp(ms), u, a.V, lane);
+                    }
                 }
                 if (bi < 0) {
 #pragma unroll
@@ -353,6 +394,18 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
             GEN_STAMP(0, t, 6);
             if (unit && more && !get_n<4>(e_hh0 + tid, GH, (unsigned)t + 2u, a.status, hh, hw, false)) *bad = 1;
             GEN_STAMP(0, t, 7);
+            if constexpr (TRUNC) done = t + 1;
+        }
+        if constexpr (TRUNC) {
+            // ... behind the last tick: the logarithms, one tick per thread (a tick that a timed-out launch never reached: NaN)
+            if (a.logp) {
+                __syncthreads();
+                for (int t = tid; t < a.L; t += NT) {
+                    const float* const term = pre + (long)t * G4;
+                    a.logp[(long)team * a.L + t] =
+                        t < done ? sample::logp_of(term[2], *reinterpret_cast<const double*>(term)) : __builtin_nanf("");
+                }
+            }
         }
     }
     __syncthreads();
@@ -436,6 +489,11 @@ bool arnn_token_pass_ok(const ArnnGenNet& n) {
     return mode() != 0 && chain_enabled() && n.H == GH && n.U == GH && n.V >= 1 && n.V <= 128;
 }
 
+// The truncating build exists for V <= 64 alone: with two logit chunks per lane (<2, true, true>, 64 < V <= 128) it can only be had
+// with spills (256 VGPRs, 40 spilled, 148 bytes of scratch -- the argmax and sampling builds of that shape spill 36 and 41), so it is
+// not built and a truncated call with V > 64 takes the per-tick launches.
+bool arnn_token_trunc_ok(const ArnnGenNet& n) { return arnn_token_pass_ok(n) && n.V <= 64; }
+
 // tables | exchange + status | stamps (2 x L x 8 64-bit words, written only under INET_ARNN_GEN_STAMPS=1: tools/arnn_token_pass.py)
 size_t arnn_token_pass_ws_floats(int L, int V) { return (size_t)L * G4 + (size_t)V * G4 + (size_t)kExFloats + 64 + (size_t)32 * L; }
 long arnn_token_pass_stamps_offset(int L, int V) { return (long)L * G4 + (long)V * G4 + kExFloats + 64; }
@@ -500,15 +558,17 @@ size_t arnn_token_sample_ws_floats(int R, int L, int V) {
     return n * L * G4 + (size_t)V * G4 + n * 2 * kExGranules + 64 + 64;
 }
 
+// trunc: the truncating build (truncation on, or a logp / logits pointer given); its labels start with trunc_
 int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
-                      const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s) {
+                      const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, bool trunc, int top_k,
+                      double top_p, float* logp, float* logits) {
     const int V = net.V, n = sample_teams(R);
     float* pre = ws;
     float* T0 = pre + (size_t)n * L * G4;
     unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
     const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
     char label[64];
-    std::snprintf(label, sizeof label, "arnn_token_sample R%d L%d V%d", R, L, V);
+    std::snprintf(label, sizeof label, "%sarnn_token_sample R%d L%d V%d", trunc ? "trunc_" : "", R, L, V);
     for (int r0 = 0; r0 < R; r0 += n) {                          // R > teams: successive launches of up to `n` rows
         const int rows = std::min(n, R - r0);
         unsigned* status = reinterpret_cast<unsigned*>(ex + rows * kExGranules);
@@ -518,10 +578,13 @@ int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, lon
         GenArgs a = gen_args(net, L, pre, T0, ex, status);
         a.hc_init = hc_init ? hc_init + (long)r0 * 4 * GH : nullptr; a.tokens = tokens + (long)r0 * L;
         a.rows = rows; a.temp = temp; a.uniforms = uniforms + (long)r0 * L;
+        a.top_k = top_k; a.top_p = top_p;
+        a.logp = logp ? logp + (long)r0 * L : nullptr; a.logits = logits ? logits + (long)r0 * L * V : nullptr;
         ProfScope prof(PROF_GRU_FWD, 2.0 * rows * L * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH), s, label,
                        4.0 * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH + (double)(rows * L + V) * G4));
         const dim3 grid(a.stride == 8 ? 13 * 8 : 13 * rows);
-        if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true>), grid, dim3(NT), 0, s, a);
+        if (trunc) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true>), grid, dim3(NT), 0, s, a);    // (V <= 64: arnn_token_trunc_ok)
+        else if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true>), grid, dim3(NT), 0, s, a);
         else hipLaunchKernelGGL((arnn_token_pass_kernel<2, true>), grid, dim3(NT), 0, s, a);
         if (hipGetLastError() != hipSuccess) return -2;
     }
@@ -707,15 +770,78 @@ __global__ __launch_bounds__(1024) void head_sample_b1_kernel(const float* __res
     }
 }
 
+// head_sample_b1_kernel behind sample.h's top-k / nucleus truncation: the draw is made of the truncated distribution, *logp (nullable)
+// receives the drawn token's log-probability under it (NaN where the tick takes the argmax rule) and logits [V] (nullable) the tick's
+// logits, from the LDS array the draw reads.  V <= 256.
+template <int NI>
+__global__ __launch_bounds__(1024) void head_trunc_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                             const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
+                                                             float temp, const double* __restrict__ u, int top_k, double top_p,
+                                                             float* __restrict__ logp, float* __restrict__ logits) {
+    __shared__ float lg[256];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float xv[NI];
+    load_x<NI>(xv, x, K, nullptr, K, lane);
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        if (v < V) {
+            const float a = wave_sum(part[r]);
+            if (lane == 0) lg[v] = a + b[v];
+        }
+    }
+    __syncthreads();
+    if (w == 1 && logits)
+        for (int v = lane; v < V; v += 64) logits[v] = lg[v];
+    if (w == 0) {
+        float sv[4], ms = -INFINITY;
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = lane + 64 * j;
+            sv[j] = v < V ? lg[v] * temp : -INFINITY;
+            nan |= sv[j] != sv[j];
+            ms = fmaxf(ms, sv[j]);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
+        int bi = -1;
+        float gap = 0.f;
+        double tot = 0.0;
+        if (!__ballot(nan)) {
+            sample::truncate<4>(sv, ms, top_k, top_p, V, lane);
+            bi = sample::pick<4>(sv, ms, *u, V, lane, tot);
+            if (bi >= 0) gap = sample::logp_gap<4>(sv, ms, bi);
+        }
+        if (logp && lane == 0) *logp = bi >= 0 ? sample::logp_of(gap, tot) : __builtin_nanf("");
+        if (bi < 0) bi = argmax_wave(lg, V, lane);
+        if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
+    }
+}
+
 // the template bounds of the one-row kernels (ops.arnn_generate_ok in Python)
 bool arnn_ticks_ok(const ArnnGenNet& n) { return n.E + n.Hc <= 320 && n.H <= 256 && n.U <= 256 && n.V <= 256; }
 size_t arnn_ticks_ws_floats(const ArnnGenNet& n) { return (size_t)(n.E + n.Hc) + 4 * (size_t)n.H + 8 * (size_t)n.H + n.U + n.V + 64; }
 
 // L ticks of one row from the state hc_init [layer][h | c][H] (null: zeros; inpainting: the state after the prefix) and the token
-// *first_tok (null: 0); `uniforms` [L]: the sampling head, null: the argmax head
+// *first_tok (null: 0); `uniforms` [L]: the sampling head, null: the argmax head; trunc (with uniforms): the truncating head, logp [L]
+// and logits [L][V] nullable, one label (trunc_arnn_ticks ...) around the row's launches
 int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, const float* hc_init, const long long* first_tok,
-               float temp, const double* uniforms, long long* tokens, float* ws, hipStream_t s) {
+               float temp, const double* uniforms, long long* tokens, float* ws, hipStream_t s, bool trunc = false, int top_k = 0,
+               double top_p = 1.0, float* logp = nullptr, float* logits = nullptr) {
     const int H = n.H;
+    std::optional<ProfScope> prof;                             // (an untruncated call files nothing, as before)
+    if (trunc) {
+        char label[64];
+        std::snprintf(label, sizeof label, "trunc_arnn_ticks L%d V%d", L, n.V);
+        prof.emplace(PROF_GRU_FWD, 2.0 * L * ((double)4 * H * (n.E + n.Hc + 3.0 * H) + (double)n.U * H + (double)n.V * n.U), s, label);
+    }
     float* hc = ws;                                            // [layer][h|c][ping-pong][H]
     float* u = hc + 8 * H;
     if (pw_zero(hc, 8L * H, s) != 0) return -2;
@@ -734,7 +860,10 @@ int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, cons
                            (const float*)C_(1, p), n.W_hh1, n.b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
         hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((n.U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), n.W1, n.b1, u,
                            n.U, H);
-        if (uniforms)
+        if (uniforms && trunc)
+            hipLaunchKernelGGL((head_trunc_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
+                               temp, uniforms + t, top_k, top_p, logp ? logp + t : nullptr, logits ? logits + (long)t * n.V : nullptr);
+        else if (uniforms)
             hipLaunchKernelGGL((head_sample_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
                                temp, uniforms + t);
         else
@@ -760,13 +889,18 @@ int arnn_generate(const ArnnGenNet& n, int L, const float* oc0, long oc_stride, 
 }
 
 int arnn_sample(const ArnnGenNet& n, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
-                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s) {
-    if (arnn_token_pass_ok(n))                                 // up to 8 rows per launch
-        return arnn_token_sample(n, R, L, oc0, oc_stride, oc_bstride, temp, uniforms, hc_init, tokens, ws, s);
+                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k, double top_p,
+                float* logp, float* logits) {
+    // truncation on, or an output only the truncating kernels write: never a kernel that ignores them
+    const bool trunc = (top_k >= 1 && top_k < n.V) || top_p < 1.0 || logp || logits;
+    if (trunc ? arnn_token_trunc_ok(n) : arnn_token_pass_ok(n))    // up to 8 rows per launch
+        return arnn_token_sample(n, R, L, oc0, oc_stride, oc_bstride, temp, uniforms, hc_init, tokens, ws, s, trunc, top_k, top_p, logp,
+                                 logits);
     if (!arnn_ticks_ok(n)) return -1;
     int rc = 0;
     for (int r = 0; r < R && rc == 0; ++r)                     // the rows one after the other
         rc = arnn_ticks(n, L, oc0 + (long)r * oc_bstride, oc_stride, hc_init ? hc_init + (long)r * 4 * n.H : nullptr, nullptr, temp,
-                        uniforms + (long)r * L, tokens + (long)r * L, ws, s);
+                        uniforms + (long)r * L, tokens + (long)r * L, ws, s, trunc, top_k, top_p, logp ? logp + (long)r * L : nullptr,
+                        logits ? logits + (long)r * L * n.V : nullptr);
     return rc;
 }

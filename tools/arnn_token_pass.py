@@ -2,7 +2,12 @@
 """The token pass of AnticipationRNN's free-running step alone (ops.arnn_generate, L = 384): python tools/arnn_token_pass.py
 With INET_ARNN_GEN_STAMPS=1 the persistent kernel (csrc/arnn_gen.hip) also leaves wall-clock stamps of the phases of a tick in its
 workspace: the anatomy of a tick as workgroup C (layer-0 cell, linear_1, head, argmax) and workgroup Bi_0 (layer-1 product + cell)
-see it is printed below the timings."""
+see it is printed below the timings.
+    python tools/arnn_token_pass.py [V] --sample [--rows 1,8] [--temperature 6.0] [--top-k 8] [--top-p 0.9] [--rounds 5] [--iters 20]
+times the SAMPLING build (ops.arnn_sample, L = 384, R independent rows) and the TRUNCATING build on the same inputs instead: the plain
+call, the call that only asks for logp (truncation off), and one call per truncation given -- top-k alone, top-p alone, both when both
+are given -- with device events, per round the median of --iters calls, over the rounds the median (range), and each truncating call's
+cost per tick over the sampling build."""
 import os, sys, time, types
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,7 +15,11 @@ import torch, bench
 from inpaintnet_amd import ops, synthetic
 from inpaintnet_amd.arnn import ConstraintModelGaussianReg
 sys.stdout = sys.stderr
-NOTES = int(sys.argv[1]) if len(sys.argv) > 1 else bench.NUM_NOTES          # (V > 64: the two-register-set build of the token pass)
+NOTES = int(sys.argv[1]) if len(sys.argv) > 1 and not sys.argv[1].startswith("--") else bench.NUM_NOTES    # (V > 64: the two-register-set build of the token pass)
+
+
+def _flag(name, default, conv):
+    return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
 ds = synthetic.SyntheticFolkDataset(num_notes=NOTES)
 ds.metadatas = [types.SimpleNamespace(num_values=6), types.SimpleNamespace(num_values=6)]
 m = ConstraintModelGaussianReg(ds, note_embedding_dim=10, metadata_embedding_dim=2, num_lstm_constraints_units=256,
@@ -22,6 +31,48 @@ args = (pr("note_embeddings.0.weight"), oc0, pr("lstm_generation.0.weight_ih_l0"
         pr("lstm_generation.0.weight_hh_l0"), pr("lstm_generation.0.bias_hh_l0"), pr("lstm_generation.1.weight_ih_l0"),
         pr("lstm_generation.1.bias_ih_l0"), pr("lstm_generation.1.weight_hh_l0"), pr("lstm_generation.1.bias_hh_l0"),
         pr("linear_1.weight"), pr("linear_1.bias"), pr("linear_ouput_notes.0.weight"), pr("linear_ouput_notes.0.bias"))
+
+
+def sample_builds():
+    import numpy as np
+    L, H = 384, 256
+    rows = _flag("--rows", (1, 8), lambda v: tuple(int(x) for x in v.split(",")))
+    temp, rounds, iters = _flag("--temperature", 6.0, float), _flag("--rounds", 5, int), _flag("--iters", 20, int)
+    top_k, top_p = _flag("--top-k", None, int), _flag("--top-p", None, float)
+    calls = [("sampling build", {}), ("truncating build, logp only", dict(want_logp=True))]
+    if top_k is not None:
+        calls.append((f"top_k={top_k}", dict(top_k=top_k, want_logp=True)))
+    if top_p is not None:
+        calls.append((f"top_p={top_p}", dict(top_p=top_p, want_logp=True)))
+    if top_k is not None and top_p is not None:
+        calls.append((f"top_k={top_k}, top_p={top_p}", dict(top_k=top_k, top_p=top_p, want_logp=True)))
+    for R in rows:
+        oc = torch.randn(R, L, H, device="cuda") * 0.5
+        u = torch.from_numpy(np.random.RandomState(1).random_sample((R, L))).cuda()
+        hc = torch.zeros(R, 2, 2, H, device="cuda")
+        med = {}
+        for name, kw in calls:
+            fn = lambda: ops.arnn_sample(args[0], oc, *args[2:], temp, u, hc_init=hc, **kw)
+            for _ in range(3): fn()
+            torch.cuda.synchronize()
+            per_round = []
+            for _ in range(rounds):
+                ts = []
+                for _ in range(iters):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record(); fn(); b.record(); b.synchronize()
+                    ts.append(a.elapsed_time(b))
+                per_round.append(sorted(ts)[len(ts) // 2])
+            med[name] = sorted(per_round)[len(per_round) // 2]
+            over = "" if not kw else f"  {1e3 * (med[name] - med['sampling build']) / L:+.2f} us per tick over the sampling build"
+            print(f"V = {NOTES}, R = {R}, T = {temp}: {name}: {med[name]:.4f} ms ({min(per_round):.4f} .. {max(per_round):.4f}), "
+                  f"{1e3 * med[name] / L:.2f} us per tick{over}  chain status {ops.chain_status()}")
+
+
+if "--sample" in sys.argv:
+    sample_builds()
+    sys.exit(0)
+
 # option key 14: 0 = four launches per tick (round 4), 1 = one persistent launch (csrc/arnn_gen.hip), 2 = ... on one XCD
 for mode in (0, 1, 2, 3):
     ops.set_option(14, mode)
