@@ -436,7 +436,9 @@ int inet_set_option(int key, int value);
  * piece products -- selected builds that lost their A/Bs or were not fp32 arithmetic; they were removed in round 4: -1.)
  * key 12 = big-batch GRU forward steps on the bf16 pipe (csrc/gru_step_bf3.hip): a layer whose single time
  * step has at least this many tiles of 128 rows x 64 units (default 256 = one per CU: B = 2048 at H = 512, two directions) runs one
- * product per step with the GRU cell as its epilogue instead of chunked chain launches; 0 = never.
+ * product per step with the GRU cell as its epilogue instead of chunked chain launches; 0 = never.  The threshold decides per shape
+ * whether a workspace holds the step kernels' W_hh pieces, so a *_bwd call compares the VALUE with the one its forward call ran under
+ * (-3 on any difference, before it writes anything), not what the two values mean for some shape.
  * key 13 = how many of the side streams take leaf work in rotation from now on (0 = all that exist, default; 1: what a process with
  * a gradient exchange beside its steps wants -- inpaintnet_amd.dp sets it: the runtime deals FOUR hardware queues, and caller + two
  * side streams + the exchange's two streams measured 4.94 ms per B = 256 step against 3.87 with one side stream).

@@ -290,6 +290,7 @@ int inet_bigru2_bwd(int B, int T, int K, int H, const float* x, const float* x_s
     GruDirPtr P[4];
     bigru_ptrs(weights, grads, K, H, P);
     const long BH = (long)B * H;
+    if (bigru2_ws_opts_peek(w.g) != 0) return -3;                    // (before the first write: the carve may differ)
     if (dout) INET_TRY(pw_swap01(dout, B, T, 2 * H, w.dout_tm, s));
     const float* dhn[4] = {nullptr, nullptr, nullptr, nullptr};
     if (dh_n) for (int i = 0; i < 4; ++i) dhn[i] = dh_n + i * BH;

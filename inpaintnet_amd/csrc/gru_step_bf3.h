@@ -15,6 +15,7 @@ struct GruStepsBf3 {
 // inet_set_option key 12 overrides, 0 = never)
 bool gru_step_bf3_ok(int H, int B, int T, int nd);
 void gru_step_bf3_set_min_tiles(int n);                    // inet_set_option key 12 (0: never take this path)
+int gru_step_bf3_min_tiles();                              // the threshold in force (what the workspace carve and the planners see)
 size_t gru_step_bf3_w_bytes(int H);
 int gru_step_bf3_split_w(int H, const float* const* W_hh, unsigned char* const* Wp, int nd, hipStream_t s);   // nd directions, one launch
 // all T steps (T launches on `s`); writes ChainEmit.rows if given (nothing else of the descriptor's `em`)

@@ -443,7 +443,10 @@ int launch_one_rm(const StepArgs& a, hipStream_t s) {
     constexpr int WM = 2, WN = 4;                                  // 8 waves; wave tile 16 RM rows x (16 units x 3 gates)
     constexpr int TMB = WM * RM, TNB = WN * RN;
     auto kern = &gru_step_bf3_kernel<TAB, DEN, SAVE, WM, WN, RM>;
-    const size_t lds = (size_t)2 * (TMB + TNB) * 3 * 1024;
+    // two operand stages, or the epilogue's wave-private transpose tiles (2 row blocks x NT tiles of 1 KB per wave) if those are
+    // larger: with saves they take 112 KB, the 96-row tile's stages 108 KB
+    constexpr size_t stages = (size_t)2 * (TMB + TNB) * 3 * 1024, tiles = (size_t)WM * WN * 2 * (SAVE ? 7 : 2) * 1024;
+    const size_t lds = stages > tiles ? stages : tiles;
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     const int grid = a.nprob * (a.B / (TMB * 16)) * (a.H / (16 * WN));
@@ -472,6 +475,7 @@ int min_tiles_now() {
 }
 }  // namespace
 void gru_step_bf3_set_min_tiles(int n) { g_min_tiles = n < 0 ? 0 : n; }
+int gru_step_bf3_min_tiles() { return min_tiles_now(); }
 bool gru_step_bf3_ok(int H, int B, int T, int nd) {
     const int min_tiles = min_tiles_now();
     if (bf3_mode() == 0 || min_tiles <= 0) return false;
@@ -507,7 +511,11 @@ int launch_gru_steps_bf3(const GruStepsBf3& L, hipStream_t s) {
     const bool tab = L.p[0].gi_table != nullptr, den = L.p[0].gi_dense != nullptr, save = L.p[0].sv != nullptr;
     for (int i = 1; i < nd; ++i)
         if ((L.p[i].gi_table != nullptr) != tab || (L.p[i].gi_dense != nullptr) != den || (L.p[i].sv != nullptr) != save) return -1;
-    if (tab == den) return -1;                               // one input-side source per layer (gather table: layer 0; dense: layer 1)
+    // one input-side source per layer: a gather table (the encoder's layer 0), dense pre-activations, or the broadcast vector alone
+    // (a scalar input: inet_bigru2_fwd with x_scalar)
+    if (tab && den) return -1;
+    for (int i = 0; i < nd; ++i)
+        if (!tab && !den && !L.p[i].gi_vec) return -1;
     char label[96];
     std::snprintf(label, sizeof label, "gru_step_bf3 p9 np%d B%d H%d%s", nd, B, H, save ? " sv" : "");
     for (int step = 0; step < T; ++step) {
@@ -545,7 +553,8 @@ int launch_gru_steps_bf3(const GruStepsBf3& L, hipStream_t s) {
                        nd * (6.0 * 3 * H * H + 12.0 * B * H + 4.0 * B * 3 * H + 4.0 * B * H * (save ? 7 : 2)));
         int rc;
         if (tab) rc = save ? launch_one<true, false, true>(a, s) : launch_one<true, false, false>(a, s);
-        else rc = save ? launch_one<false, true, true>(a, s) : launch_one<false, true, false>(a, s);
+        else if (den) rc = save ? launch_one<false, true, true>(a, s) : launch_one<false, true, false>(a, s);
+        else rc = save ? launch_one<false, false, true>(a, s) : launch_one<false, false, false>(a, s);
         if (rc != 0) return rc;
     }
     return 0;

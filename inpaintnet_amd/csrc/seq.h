@@ -177,3 +177,7 @@ int bigru2_core_fwd(int B, int T, int H, const GruDirPtr* P /*[4]*/, const BiGru
 // 2 = the rest (layer 0), on the state stage 1 left in the workspace
 int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, const float* dout1,
                     const float* const* dhn, long dhn_ld, float* dh0, BiGru2Ws& w, hipStream_t s, int stage = 0);
+// 0, or -3 if the forward call that wrote this workspace ran under other options than are in force now (what bigru2_core_bwd will
+// answer).  For the backward entry points, BEFORE their first write: under other options the carve behind `zeros` may sit elsewhere,
+// and a buffer of the caller's (the time-major dout, the heads' gradients) would land on what the forward call saved.
+int bigru2_ws_opts_peek(const BiGru2Ws& w);

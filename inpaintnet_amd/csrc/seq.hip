@@ -409,16 +409,27 @@ int ws_opts_check(const void* key, unsigned opts, bool consume) {
     if (consume || !same) g_ws_opts.erase(it);
     return same ? 0 : -3;
 }
+// Key 12 enters with its VALUE: every threshold decides for other shapes whether wp3 / wp3T exist, so two values carve the same
+// workspace differently (two probe shapes, as this once took, cannot tell 1 from 256).  20 bits: the predicates' size bound
+// (T B 6H < 2e9) keeps a launch below 2^17 tiles, so every threshold from 2^20 - 1 up means "never" for every shape alike.
 unsigned opts_snapshot() {
+    const int mt = gru_step_bf3_min_tiles();
+    const unsigned mt20 = mt < 0 ? 0u : (mt > 0xFFFFF ? 0xFFFFFu : (unsigned)mt);
     return (unsigned)chain_enabled() | ((unsigned)chain2_mode() << 1) | ((unsigned)bf3_mode() << 5) | ((unsigned)emit_mask() << 9) |
-           ((unsigned)(gru_step_bf3_ok(512, 2048, 24, 2) ? 1 : 0) << 12) | ((unsigned)(gru_step_bf3_ok(512, 1 << 20, 2, 2) ? 1 : 0) << 13);
+           (mt20 << 12);
 }
 }  // namespace
+
+int bigru2_ws_opts_peek(const BiGru2Ws& w) {
+    std::lock_guard<std::mutex> lk(g_ws_opts_mu);
+    const auto it = g_ws_opts.find(w.zeros);
+    return it == g_ws_opts.end() || it->second == opts_snapshot() ? 0 : -3;
+}
 
 int bigru2_core_fwd(int B, int T, int H, const GruDirPtr* P, const BiGru2In& in, const float* h0, const float* mask,
                     float* const* hn, long hn_ld, BiGru2Ws& w, int save, hipStream_t s, int sync_prezeroed) {
     const long BH = (long)B * H, TBH = (long)T * BH;
-    if (save) ws_opts_note(w.sync, opts_snapshot());
+    if (save) ws_opts_note(w.zeros, opts_snapshot());           // (keyed by the first field: its offset does not move with the options)
     // fragment-major W_hh twins: only the per-step kernels read them (the chain kernels take W_hh as stored)
     // (one launch, row chunks, or -- big batches -- the bf16-pipe step kernels, which take the same null h0)
     const bool stepf = w.wp3[0] && w.hpk[0] && pk_ok(H) && !gru_chain_ok(H, B, T, 2) && gru_step_bf3_ok(H, B, T, 2);
@@ -552,7 +563,7 @@ static int bigru2_wgrad_hh_bf3(int B, int T, int H, int layer, const GruDirPtr* 
 int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, const float* dout1,
                     const float* const* dhn, long dhn_ld, float* dh0, BiGru2Ws& w, hipStream_t s, int stage) {
     const long BH = (long)B * H, TBH = (long)T * BH;
-    if (ws_opts_check(w.sync, opts_snapshot(), stage != 1) != 0) return -3;      // options changed since the forward call
+    if (ws_opts_check(w.zeros, opts_snapshot(), stage != 1) != 0) return -3;     // options changed since the forward call
     const bool wg = P[0].dw_hh != nullptr;
     // both layers run as backward chains (they read W_hh as stored) iff the conditions of gru_layer_bwd hold:
     // the transposed fragment-major twins are then never read

@@ -110,6 +110,7 @@ int vae_encoder_bwd(const inet_vae_config& c, int B, const long long* tokens, co
     enc_carve(c, B, 1, ws, w);
     GruDirPtr P[4];
     enc_ptrs(L, p, g, P);
+    if (bigru2_ws_opts_peek(w.g) != 0) return -3;            // (before the first write: the carve may differ)
     // heads  (stage 2 of a staged call starts at the layer-0 BPTT: see vae.h)
     if (stage != 2) {
     {
