@@ -525,6 +525,19 @@ int inet_gemm_plan(int a_kmajor, int b_kmajor, int M, int N, int K, int64_t lda,
  * group, workgroup split-K group): row 0 of out [n][16], work [n][2], label [n][cap] describes it and out[14] = 1; else every product
  * runs on its own plan, row i describes product i and out[14] = n. */
 int inet_gemm_group_plan(int n, const int64_t* desc, int32_t* out, double* work, char* label, int cap);
+/* What one GRU layer of nprob independent problems (directions) over B rows, T steps and hidden size H launches, forward and -- with
+ * save != 0 -- backward, under the options set now (inet_set_option keys 4, 7, 8, 12) and for a workspace that carries every optional
+ * buffer (as inet_bigru2_ws_bytes carves them), without a GPU: the plan functions that gru_layer_fwd / gru_layer_bwd (csrc/seq.hip)
+ * branch on, behind the C-ABI.  out32 = the forward plan [0..15], the backward plan [16..31] (all -1 without save), each {route (0 =
+ * f32 kernels, one launch per step; 1 = first-generation chain; 2 = second-generation chain; 3 = bf16-pipe step kernels), rows per
+ * launch, launches (row chunks of a chain route; T on a step route), kernel generation, MS, SQ, OCC, EMR of the chain launch's build
+ * (csrc/gru_chain.h ChainBuild; EMR: the build that writes piece outputs is the one that runs when the caller gives their buffers; 0
+ * on a step route), chunk launches run two at a time on two streams, ring layout (0 = the layer's whole ring buffer, slots adjacent;
+ * 1 = a ring of its own per chunk; 2 = each chunk on its rows of the two slots of the full-batch ring), workgroup groups and members
+ * per group of one launch, floats of the ring buffer the launches address, floats the workspace carves for it, the chip's chain
+ * capacity in workgroups (CUs, or INET_CHAIN_CUS), group counters of a sync area}.  0, or -1 for H, B, T <= 0, nprob outside 1..4 or a
+ * null output -- nothing is written then. */
+int inet_gru_chain_plan(int H, int B, int T, int nprob, int save, int64_t* out32);
 /* Loads every kernel of the library on the CURRENT device (code objects and function objects, which the HIP runtime otherwise
  * builds lazily on the launch path of each kernel's first launch: csrc/preload.hip) without launching anything.  Idempotent per
  * device; returns the number of kernels touched (0 when the device was done already), -2 without a device or on a runtime

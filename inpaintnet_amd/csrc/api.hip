@@ -626,6 +626,19 @@ int inet_gemm_group_plan(int n, const int64_t* desc, int32_t* out, double* work,
     return 0;
 }
 
+int inet_gru_chain_plan(int H, int B, int T, int nprob, int save, int64_t* out32) {
+    if (H <= 0 || B <= 0 || T <= 0 || nprob < 1 || nprob > 4 || !out32) return -1;
+    const auto put = [&](int64_t* o, const GruLayerPlan& p, int K) {
+        const int64_t v[16] = {p.route, p.rows, p.launches, p.b.gen, p.b.MS, p.b.SQ, p.b.OCC, p.b.EMR, p.two_at_a_time, p.ring, p.groups,
+                               p.members, p.ring_floats, (int64_t)chain_ring_floats(B, K), chain_capacity(), kChainMaxGroups};
+        for (int i = 0; i < 16; ++i) o[i] = v[i];
+    };
+    put(out32, gru_layer_fwd_plan(H, B, T, nprob, save != 0, true, true, true), H);
+    if (save) put(out32 + 16, gru_layer_bwd_plan(H, B, T, nprob, true, true, true), 3 * H);
+    else for (int i = 16; i < 32; ++i) out32[i] = -1;
+    return 0;
+}
+
 int inet_preload(void) { return preload_kernels(); }
 int inet_kernel_count(void) { return preload_kernel_count(); }
 

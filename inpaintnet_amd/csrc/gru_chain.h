@@ -55,7 +55,8 @@ struct GruChainFwd {
     int fault;                                    // test hook (inet_set_option key 6): workgroup 0 leaves at once, so its
                                                   // group runs into the bounded spin and the failure path can be tested
     int shared_chip;                              // this launch runs beside another chain launch (two workgroups per CU):
-                                                  // the 256-register build of the kernel
+                                                  // the 256-register build of the kernel (callers set it only where the
+                                                  // plan's build has OCC = 2: chain_fwd_build)
     GruChainFwdProb p[4];
     unsigned* counters;                           // kChainSyncWords words owned by this launch (zeroed by the launcher
     int prezeroed;                                // unless the caller says they already are)
@@ -86,6 +87,21 @@ struct GruChainBwd {
     int prezeroed;
     chain::Status status;
 };
+
+// The kernel instantiation behind a launch.  gen 1: gru_chain_fwd_kernel<MS,SQ,OCC> / gru_chain_bwd_kernel<MS,SQ,EMR> (16 * MS rows
+// per workgroup; SQ = H / 64 forward, 3H / 64 backward); gen 2: gru_chain2_fwd_kernel<MS,SQ,9,EMR> (MS = 4 waves of one 16-row block
+// each, SQ = H / 32; EMR: the build that writes piece outputs).  chain_fwd_build / chain_bwd_build / chain2_fwd_build are the only
+// places that choose one: the launchers' dispatch switches and the plan queries read them.
+struct ChainBuild { int gen, MS, SQ, OCC, EMR; };
+ChainBuild chain_fwd_build(int H, int ms, bool shared_chip);
+ChainBuild chain_bwd_build(int H, int ms, bool emits_rows);
+ChainBuild chain2_fwd_build(int H, bool em);
+// One launch over B rows: ok = 0 where no chain kernel takes the shape; groups * members workgroups, all resident at once.
+// shared_chip: the caller wants to run two such launches side by side (granted where b.OCC == 2); em / rows_given: the
+// descriptors carry piece outputs (ChainEmit) for the kernel to write.
+struct ChainLaunchPlan { int ok; ChainBuild b; int groups, members; };
+ChainLaunchPlan gru_chain_fwd_plan(int H, int B, int T, int nprob, bool shared_chip, bool em);
+ChainLaunchPlan gru_chain_bwd_plan(int H, int B, int T, int nprob, bool rows_given);
 
 bool gru_chain_ok(int H, int B, int T, int nprob);
 bool gru_chain_bwd_ok(int H, int B, int T, int nprob);      // as above, with two row tiles per workgroup when needed

@@ -405,55 +405,93 @@ bool gru_chain_bwd_ok(int H, int B, int T, int nprob) {
     return nprob * tiles * (H / 16) <= chain_capacity() && nprob * tiles <= kChainMaxGroups;
 }
 
+// The instantiation a first-generation forward launch runs: THE place that names it -- the dispatch switch below and the plan query
+// (seq.hip gru_layer_fwd_plan behind inet_gru_chain_plan) both read it.  SQ = H / 64 always.  OCC = 2 (the 256-register build, two
+// launches per CU) exists for 64-row tiles at H <= 512 only: at H = 1024 a lane holds 192 registers of W_hh and a workgroup owns
+// its CU, so a launch that asks to share the chip still gets <MS,16,1> (and its caller runs the launches one after the other).
+ChainBuild chain_fwd_build(int H, int ms, bool shared_chip) {
+    return ChainBuild{1, ms, H / 64, shared_chip && ms == 4 && H <= 512 ? 2 : 1, 0};
+}
+// ... and a BPTT launch: SQ = 3H / 64; EMR (the build that writes ChainEmit.rows) is <4,24,true> alone
+ChainBuild chain_bwd_build(int H, int ms, bool emits_rows) {
+    return ChainBuild{1, ms, 3 * H / 64, 1, emits_rows && H == 512 && ms == 4 ? 1 : 0};
+}
+
+ChainLaunchPlan gru_chain_fwd_plan(int H, int B, int T, int nprob, bool shared_chip, bool em) {
+    ChainLaunchPlan p{};
+    if (gru_chain2_ok(H, B, T, nprob)) {
+        p.ok = 1; p.b = chain2_fwd_build(H, em); p.members = H / 16; p.groups = nprob * ((((B + 15) / 16) + 3) / 4);
+        return p;
+    }
+    if (!gru_chain_ok(H, B, T, nprob)) return p;
+    const int ms = rows_ms(B, H, nprob);
+    p.ok = 1; p.b = chain_fwd_build(H, ms, shared_chip); p.members = H / 16; p.groups = nprob * ((B + 16 * ms - 1) / (16 * ms));
+    return p;
+}
+ChainLaunchPlan gru_chain_bwd_plan(int H, int B, int T, int nprob, bool rows_given) {
+    ChainLaunchPlan p{};
+    if (!gru_chain_bwd_ok(H, B, T, nprob)) return p;
+    const int ms = rows_ms_bwd(H, B, nprob);
+    p.ok = 1; p.b = chain_bwd_build(H, ms, rows_given); p.members = H / 16; p.groups = nprob * ((B + 16 * ms - 1) / (16 * ms));
+    return p;
+}
+
 int launch_gru_chain_fwd(GruChainFwd a, hipStream_t s) {
     if (gru_chain2_ok(a.H, a.B, a.T, a.nprob)) return launch_gru_chain2_fwd(a, s);
-    if (!gru_chain_ok(a.H, a.B, a.T, a.nprob)) return -1;
-    const int ms = rows_ms(a.B, a.H, a.nprob);
+    const ChainLaunchPlan pl = gru_chain_fwd_plan(a.H, a.B, a.T, a.nprob, a.shared_chip != 0, false);
+    if (!pl.ok) return -1;
+    const ChainBuild b = pl.b;
+    const int ms = b.MS;
     a.tiles_per_prob = (a.B + 16 * ms - 1) / (16 * ms);
-    a.members = a.H / 16;
-    const int groups = a.nprob * a.tiles_per_prob;
+    a.members = pl.members;
+    const int groups = pl.groups;
     if (groups > kChainMaxGroups) return -1;
     a.prio = 1;
     a.fault = chain_take_fault();
     if (!a.prezeroed && hipMemsetAsync(a.counters, 0, kChainSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
     a.status = chain_status_for(a.counters + kChainStatusWord);
     char label[72];
-    std::snprintf(label, sizeof label, "gru_chain_fwd ms%d%s np%d T%d B%d H%d", ms, a.shared_chip && ms == 4 ? "x2" : "", a.nprob, a.T, a.B, a.H);
+    std::snprintf(label, sizeof label, "gru_chain_fwd ms%d%s np%d T%d B%d H%d", ms, b.OCC == 2 ? "x2" : "", a.nprob, a.T, a.B, a.H);
     const double rows = (double)a.nprob * a.T * a.B;
     ProfScope prof(PROF_GRU_FWD, 2.0 * rows * 3.0 * a.H * a.H, s, label,
                    4.0 * (a.nprob * 3.0 * a.H * a.H + rows * a.H * (2 + 3 + (a.p[0].sv ? 5 : 0))));
     const dim3 grid(chain::blocks_for(groups, a.members));
-#define DISPATCH_CF(M, Q, O) hipLaunchKernelGGL((gru_chain_fwd_kernel<M, Q, O>), grid, dim3(256), 0, s, a)
-    if (a.shared_chip && ms == 4) { if (a.H == 512) DISPATCH_CF(4, 8, 2); else DISPATCH_CF(4, 4, 2); }
-    else if (a.H == 1024) { if (ms == 1) DISPATCH_CF(1, 16, 1); else if (ms == 2) DISPATCH_CF(2, 16, 1); else DISPATCH_CF(4, 16, 1); }   // (LatentRNN's generator: 192 registers of W_hh per lane)
-    else if (a.H == 512) { if (ms == 1) DISPATCH_CF(1, 8, 1); else if (ms == 2) DISPATCH_CF(2, 8, 1); else DISPATCH_CF(4, 8, 1); }
-    else { if (ms == 1) DISPATCH_CF(1, 4, 1); else if (ms == 2) DISPATCH_CF(2, 4, 1); else DISPATCH_CF(4, 4, 1); }
+#define DISPATCH_CF(M, Q, O) if (b.MS == M && b.SQ == Q && b.OCC == O) hipLaunchKernelGGL((gru_chain_fwd_kernel<M, Q, O>), grid, dim3(256), 0, s, a); else
+    DISPATCH_CF(4, 8, 2) DISPATCH_CF(4, 4, 2)
+    DISPATCH_CF(1, 16, 1) DISPATCH_CF(2, 16, 1) DISPATCH_CF(4, 16, 1)   // (LatentRNN's generator: 192 registers of W_hh per lane)
+    DISPATCH_CF(1, 8, 1) DISPATCH_CF(2, 8, 1) DISPATCH_CF(4, 8, 1)
+    DISPATCH_CF(1, 4, 1) DISPATCH_CF(2, 4, 1) DISPATCH_CF(4, 4, 1)
+    return -1;
 #undef DISPATCH_CF
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // the first-generation BPTT launch for this shape writes ChainEmit.rows itself (H = 512, 64 rows per workgroup)
 bool gru_chain_bwd_emits_rows(int H, int B, int T, int nprob) {
-    return H == 512 && gru_chain_bwd_ok(H, B, T, nprob) && rows_ms_bwd(H, B, nprob) == 4;
+    const ChainLaunchPlan p = gru_chain_bwd_plan(H, B, T, nprob, true);
+    return p.ok && p.b.EMR;
 }
 // The BPTT chains run on the FIRST generation: its kernel takes 28 KB of LDS and ~300 registers per lane, so the leaf work of the
 // backward pass (weight-gradient products, column sums, the bf16-pipe products' split launches) shares the CUs with it.  A
 // second-generation BPTT kernel existed in round 3 (the faster kernel alone, 220 vs 232 us per 24-step launch; the slower step, 3.73
 // vs 3.62 ms: a workgroup held 148-160 KB of its CU's LDS for the length of the chain) and was removed in round 4 (HISTORY.md).
 int launch_gru_chain_bwd(GruChainBwd a, hipStream_t s) {
-    if (!gru_chain_bwd_ok(a.H, a.B, a.T, a.nprob)) return -1;
-    const int ms = rows_ms_bwd(a.H, a.B, a.nprob);
+    // row pieces of dgi (ChainEmit.rows): written by the H = 512, 64-rows-per-workgroup build; nothing else of the descriptor is
+    // read (the callers split what was not written)
+    bool rows_given = true;
+    for (int i = 0; i < a.nprob && i < 4; ++i) rows_given = rows_given && a.p[i].em.rows;
+    const ChainLaunchPlan pl = gru_chain_bwd_plan(a.H, a.B, a.T, a.nprob, rows_given);
+    if (!pl.ok) return -1;
+    const ChainBuild b = pl.b;
+    const int ms = b.MS;
     a.tiles_per_prob = (a.B + 16 * ms - 1) / (16 * ms);
-    a.members = a.H / 16;
-    const int groups = a.nprob * a.tiles_per_prob;
+    a.members = pl.members;
+    const int groups = pl.groups;
     if (groups > kChainMaxGroups) return -1;
     a.prio = 1;
     if (!a.prezeroed && hipMemsetAsync(a.counters, 0, kChainSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
     a.status = chain_status_for(a.counters + kChainStatusWord);
-    // row pieces of dgi (ChainEmit.rows): written by the H = 512, 64-rows-per-workgroup build; nothing else of the descriptor is
-    // read (the callers split what was not written)
-    bool emr = a.H == 512 && ms == 4;
-    for (int i = 0; i < a.nprob; ++i) emr = emr && a.p[i].em.rows;
+    const bool emr = b.EMR != 0;
     if (!emr) for (int i = 0; i < a.nprob; ++i) a.p[i].em.rows = nullptr;
     char label[72];
     std::snprintf(label, sizeof label, "gru_chain_bwd ms%d%s np%d T%d B%d H%d", ms, emr ? "e" : "", a.nprob, a.T, a.B, a.H);
@@ -461,12 +499,12 @@ int launch_gru_chain_bwd(GruChainBwd a, hipStream_t s) {
     ProfScope prof(PROF_GRU_BWD, 2.0 * rows * 3.0 * a.H * a.H, s, label,
                    4.0 * (a.nprob * 3.0 * a.H * a.H + rows * a.H * (6 + 5 + 1)) + (emr ? 18.0 * rows * a.H : 0.0));
     const dim3 grid(chain::blocks_for(groups, a.members));
-#define DISPATCH_CB(M, Q) hipLaunchKernelGGL((gru_chain_bwd_kernel<M, Q>), grid, dim3(256), 0, s, a)
-    if (emr) hipLaunchKernelGGL((gru_chain_bwd_kernel<4, 24, true>), grid, dim3(256), 0, s, a);
-    else
-    if (a.H == 1024) { if (ms == 1) DISPATCH_CB(1, 48); else if (ms == 2) DISPATCH_CB(2, 48); else if (ms == 4) DISPATCH_CB(4, 48); else return -1; }
-    else if (a.H == 512) { if (ms == 1) DISPATCH_CB(1, 24); else if (ms == 2) DISPATCH_CB(2, 24); else if (ms == 4) DISPATCH_CB(4, 24); else DISPATCH_CB(8, 24); }
-    else { if (ms == 1) DISPATCH_CB(1, 12); else if (ms == 2) DISPATCH_CB(2, 12); else if (ms == 4) DISPATCH_CB(4, 12); else DISPATCH_CB(8, 12); }
+#define DISPATCH_CB(M, Q, E) if (b.MS == M && b.SQ == Q && b.EMR == E) hipLaunchKernelGGL((gru_chain_bwd_kernel<M, Q, E != 0>), grid, dim3(256), 0, s, a); else
+    DISPATCH_CB(4, 24, 1)
+    DISPATCH_CB(1, 48, 0) DISPATCH_CB(2, 48, 0) DISPATCH_CB(4, 48, 0)
+    DISPATCH_CB(1, 24, 0) DISPATCH_CB(2, 24, 0) DISPATCH_CB(4, 24, 0) DISPATCH_CB(8, 24, 0)
+    DISPATCH_CB(1, 12, 0) DISPATCH_CB(2, 12, 0) DISPATCH_CB(4, 12, 0) DISPATCH_CB(8, 12, 0)
+    return -1;
 #undef DISPATCH_CB
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

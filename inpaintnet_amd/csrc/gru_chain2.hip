@@ -429,6 +429,9 @@ bool gru_chain2_ok(int H, int B, int T, int nprob) {
     return nprob * ((nrb + 3) / 4) * (H / 16) <= chain_capacity();
 }
 
+// the instantiation of a second-generation launch: four waves, S = H / 32 k blocks, nine piece products
+ChainBuild chain2_fwd_build(int H, bool em) { return ChainBuild{2, 4, H / 32, 1, em ? 1 : 0}; }
+
 int launch_gru_chain2_fwd(GruChainFwd a, hipStream_t s) {
     if (!gru_chain2_ok(a.H, a.B, a.T, a.nprob)) return -1;
     const int nrb = (a.B + 15) / 16;
@@ -461,8 +464,12 @@ int launch_gru_chain2_fwd(GruChainFwd a, hipStream_t s) {
         }                                                                                                               \
         hipLaunchKernelGGL((gru_chain2_fwd_kernel<4, S, 9, E>), grid, dim3(256), lds, s, a);                            \
     } while (0)
-    if (a.H == 512) { if (em) DISPATCH_C2F(16, true); else DISPATCH_C2F(16, false); }
-    else { if (em) DISPATCH_C2F(8, true); else DISPATCH_C2F(8, false); }
+    const ChainBuild b = chain2_fwd_build(a.H, em);
+    if (b.SQ == 16 && b.EMR) DISPATCH_C2F(16, true);
+    else if (b.SQ == 16) DISPATCH_C2F(16, false);
+    else if (b.SQ == 8 && b.EMR) DISPATCH_C2F(8, true);
+    else if (b.SQ == 8) DISPATCH_C2F(8, false);
+    else return -1;
 #undef DISPATCH_C2F
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -86,6 +86,21 @@ int chain_chunk_rows_bwd(int H, int B, int T, int nd);
 // whether gru_layer_fwd / gru_layer_bwd write ChainEmit outputs for this shape (the kernels that run are the second generation's,
 // rows in multiples of 32): the same decision the layer functions make, for callers that must know it in another library call
 bool gru_layer_fwd_emits(int H, int B, int T, int nd, bool save);
+// What a layer call launches (gru_layer_fwd_plan / gru_layer_bwd_plan: the functions gru_layer_fwd / gru_layer_bwd branch on; behind
+// inet_gru_chain_plan).  route: the kernels; rows per launch and launches (chain routes: the row chunks; step routes: one per time
+// step); b, groups, members: the chain launch's build and workgroups; two_at_a_time: chunk launches run in pairs on two streams;
+// ring: where a launch's exchange ring sits inside the layer's ring buffer; ring_floats: the floats of it the launches address.
+enum { GRU_ROUTE_STEP = 0, GRU_ROUTE_CHAIN1 = 1, GRU_ROUTE_CHAIN2 = 2, GRU_ROUTE_STEP_BF3 = 3 };
+enum { GRU_RING_FULL = 0,      // one launch (or the step kernels) on the whole buffer, slots adjacent
+       GRU_RING_OWN = 1,       // chunk c on its own contiguous ring, chain_ring_floats(rows, K) apart
+       GRU_RING_ROWS = 2 };    // chunk c on its rows of the two slots of the full-batch ring (hx_slot_bytes / gx_slot_bytes)
+struct GruLayerPlan {
+    int route, rows, launches;
+    ChainBuild b; int groups, members;
+    int two_at_a_time, ring; long ring_floats;
+};
+GruLayerPlan gru_layer_fwd_plan(int H, int B, int T, int nd, bool save, bool pk, bool sync, bool wp3);
+GruLayerPlan gru_layer_bwd_plan(int H, int B, int T, int nd, bool pk, bool chain_args, bool step_args);
 void bf3_set_emit_mask(int m);      // which piece outputs the chain kernels write themselves (inet_set_option key 9)
 int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s);
 int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s);

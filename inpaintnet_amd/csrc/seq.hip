@@ -69,18 +69,72 @@ static GruChainFwdProb fwd_prob(const DirFwd& D, long r0, int H) {
     P.reverse = D.reverse;
     return P;
 }
+// What gru_layer_fwd runs for a layer: the function branches on this plan and on nothing else, and inet_gru_chain_plan reports it.
+// pk: the fragment-major buffers (Wpk_hh, hpk) are given for every direction; sync: the counters; wp3: the step kernels' W pieces.
+GruLayerPlan gru_layer_fwd_plan(int H, int B, int T, int nd, bool save, bool pk, bool sync, bool wp3) {
+    GruLayerPlan p{};
+    const long pkh = (long)pk_floats(B, H);
+    pk = pk && pk_ok(H);
+    if (pk && sync && gru_chain_ok(H, B, T, nd)) {
+        // one persistent launch for all T steps (gru_chain.hip)
+        const ChainLaunchPlan lp = gru_chain_fwd_plan(H, B, T, nd, false, B % 32 == 0);   // (the second generation writes the piece outputs)
+        p.route = lp.b.gen == 2 ? GRU_ROUTE_CHAIN2 : GRU_ROUTE_CHAIN1;
+        p.rows = B; p.launches = 1; p.b = lp.b; p.groups = lp.groups; p.members = lp.members;
+        p.ring = GRU_RING_FULL; p.ring_floats = (lp.b.gen == 2 ? 3 : 2) * pkh;
+        return p;
+    }
+    // One time step of the layer fills the chip by itself (LatentRNN's frozen encoder: 2048 measures; the reference's default
+    // MeasureVAE batch: 4096): a bf16-pipe product per step with the GRU cell as its epilogue (gru_step_bf3.hip) instead of
+    // chunked chain launches at 0.37 of that pipe.
+    if (pk && wp3 && nd <= 2 && gru_step_bf3_ok(H, B, T, nd)) {
+        p.route = GRU_ROUTE_STEP_BF3; p.rows = B; p.launches = T; p.ring = GRU_RING_FULL; p.ring_floats = (long)chain_ring_floats(B, H);
+        return p;
+    }
+    // More rows than one resident launch can take: the rows are independent, so the chain kernel runs over chunks of rows, each
+    // on a chunk-sized exchange ring inside the hpk buffer.
+    const int CH = chain_chunk_rows(H, B, T, nd, save);
+    if (pk && sync && CH > 0 && CH < B) {
+        const long pkc = (long)pk_floats(CH, H);
+        const int n = B / CH;
+        // (the second-generation kernel keeps its W slice in 144 KB of LDS: one workgroup per CU, nothing to gain from two
+        // streams; every chunk gets its own contiguous ring of three-piece slots)
+        const bool v2 = gru_chain2_ok(H, CH, T, nd);
+        // Two chunks at a time, on two streams, where the launch's build is the 256-register one (OCC = 2: two launches share
+        // every CU, and one chunk's hand-off latency -- a third of each step -- is filled by the other chunk's MFMAs).  Every
+        // other build owns its CUs: those chunks run one after the other (two full-chip launches side by side would each wait
+        // for workgroups that cannot become resident).
+        const ChainLaunchPlan lp = gru_chain_fwd_plan(H, CH, T, nd, !v2, v2 && B % 32 == 0 && CH % 32 == 0);
+        p.route = v2 ? GRU_ROUTE_CHAIN2 : GRU_ROUTE_CHAIN1;
+        p.rows = CH; p.launches = n; p.b = lp.b; p.groups = lp.groups; p.members = lp.members;
+        p.two_at_a_time = lp.b.OCC == 2;
+        // Chunk c of a first-generation launch works on its rows of the two slots of the full-batch ring (row blocks are the
+        // outermost index of the fragment-major layout)
+        p.ring = v2 ? GRU_RING_OWN : GRU_RING_ROWS;
+        p.ring_floats = v2 ? (long)n * 3 * pkc : (long)(n - 1) * pkc + pkh + pkc;
+        return p;
+    }
+    p.route = GRU_ROUTE_STEP; p.rows = B; p.launches = T; p.ring = GRU_RING_FULL; p.ring_floats = pk ? 2 * pkh : 0;
+    return p;
+}
+
 int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
     for (int i = 0; i < nd; ++i) d[i].emitted = 0;
     const long BH = (long)B * H;
     const long pkh = (long)pk_floats(B, H);
-    bool pk = pk_ok(H);
-    for (int i = 0; i < nd; ++i) if (!d[i].Wpk_hh || !d[i].hpk) pk = false;
-    if (pk && d[0].sync && gru_chain_ok(H, B, T, nd)) {
+    bool pk = pk_ok(H), wp3 = true, any_sv = false;
+    for (int i = 0; i < nd; ++i) {
+        if (!d[i].Wpk_hh || !d[i].hpk) pk = false;
+        wp3 = wp3 && d[i].wp3;
+        any_sv = any_sv || d[i].sv;
+    }
+    const GruLayerPlan pl = gru_layer_fwd_plan(H, B, T, nd, any_sv, pk, d[0].sync != nullptr, wp3);
+    const bool chain = pl.route == GRU_ROUTE_CHAIN1 || pl.route == GRU_ROUTE_CHAIN2;
+    if (chain && pl.launches == 1) {
         // one persistent launch for all T steps (gru_chain.hip); the exchange buffer is the hpk ring, slot 1 = h0 (published
         // by the kernel itself; a null h0 = zeros)
         GruChainFwd a{};
         a.H = H; a.B = B; a.T = T; a.nprob = nd;
-        const bool emits = B % 32 == 0 && gru_chain2_ok(H, B, T, nd);      // (the second generation writes the piece outputs)
+        const bool emits = pl.b.gen == 2 && pl.b.EMR;                      // (the second generation writes the piece outputs)
         for (int i = 0; i < nd; ++i) {
             const DirFwd& D = d[i];
             GruChainFwdProb& P = a.p[i];
@@ -91,12 +145,7 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
         a.counters = d[0].sync; a.prezeroed = d[0].sync_prezeroed;
         return launch_gru_chain_fwd(a, s);
     }
-    // One time step of the layer fills the chip by itself (LatentRNN's frozen encoder: 2048 measures; the reference's default
-    // MeasureVAE batch: 4096): a bf16-pipe product per step with the GRU cell as its epilogue (gru_step_bf3.hip) instead of
-    // chunked chain launches at 0.37 of that pipe.
-    bool stepbf3 = pk && nd <= 2 && gru_step_bf3_ok(H, B, T, nd);
-    for (int i = 0; i < nd; ++i) stepbf3 = stepbf3 && d[i].wp3;
-    if (stepbf3) {
+    if (pl.route == GRU_ROUTE_STEP_BF3) {
         GruStepsBf3 L{};
         L.H = H; L.B = B; L.T = T; L.nprob = nd;
         for (int i = 0; i < nd; ++i) {
@@ -117,26 +166,15 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
         }
         return launch_gru_steps_bf3(L, s);
     }
-    // More rows than one resident launch can take (the frozen encoder of LatentRNN runs 2048 measures at once, the
-    // reference's default VAE batch is 4096 measures): the rows are independent, so the chain kernel runs over chunks of
-    // rows, one launch after the other, each on a chunk-sized exchange ring inside the hpk buffer; backward saves keep the
-    // full batch's time stride.
-    bool any_sv = false;
-    for (int i = 0; i < nd; ++i) any_sv = any_sv || d[i].sv;
-    const int CH = chain_chunk_rows(H, B, T, nd, any_sv);
-    const bool chunked = pk && d[0].sync && CH > 0 && CH < B;
-    if (chunked) {
-        // Two chunks at a time, on two streams: the kernel's 256-register build lets two launches share every CU, and one
-        // chunk's hand-off latency (a third of each step) is filled by the other chunk's MFMAs.  Chunk c works on its rows
-        // of the two slots of the full-batch ring (row blocks are the outermost index of the fragment-major layout); even /
-        // odd chunks count on different sync areas (the caller's and the one behind it).
+    if (chain) {
+        // row chunks (gru_layer_fwd_plan), one launch each; backward saves keep the full batch's time stride; even / odd chunks
+        // count on different sync areas (the caller's and the one behind it)
+        const int CH = pl.rows;
         const long pkc = (long)pk_floats(CH, H);
-        // (the second-generation kernel keeps its W slice in 144 KB of LDS: one workgroup per CU, nothing to gain from two
-        // streams; every chunk gets its own contiguous ring of three-piece slots)
-        const bool v2 = gru_chain2_ok(H, CH, T, nd);
-        const bool emits = v2 && B % 32 == 0 && CH % 32 == 0;
-        hipStream_t s2 = !v2 ? twin_fork(s) : s;
-        for (int c = 0; c < B / CH; ++c) {
+        const bool v2 = pl.route == GRU_ROUTE_CHAIN2;
+        const bool emits = v2 && pl.b.EMR;
+        hipStream_t s2 = pl.two_at_a_time ? twin_fork(s) : s;
+        for (int c = 0; c < pl.launches; ++c) {
             const long r0 = (long)c * CH;
             GruChainFwd a{};
             a.H = H; a.B = CH; a.T = T; a.nprob = nd;
@@ -146,7 +184,7 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
                 GruChainFwdProb& P = a.p[i];
                 P = fwd_prob(D, r0, H);
                 if (P.sv) P.sv_ts = BH;
-                if (v2) P.hx = D.hpk + (long)c * 3 * pkc;
+                if (pl.ring == GRU_RING_OWN) P.hx = D.hpk + (long)c * 3 * pkc;
                 else { P.hx = D.hpk + (long)c * pkc; P.hx_slot_bytes = (int)(pkh * sizeof(float)); }
                 if (emits) { P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 3; }
             }
@@ -224,6 +262,37 @@ static GruChainBwdProb bwd_prob(const DirBwd& D, long r0, int H, int B) {
     return P;
 }
 
+// What gru_layer_bwd runs for a layer: the function branches on this plan and on nothing else, and inet_gru_chain_plan reports it.
+// pk: the fragment-major buffers (Wpk_hhT, dghpk) are given for every direction; chain_args: what a chain launch needs besides (the
+// counters, W_hh row-major, dh0 for every direction or for none); step_args: the step kernels' (W^T pieces, W_hh, dhz, no dgi_sum).
+GruLayerPlan gru_layer_bwd_plan(int H, int B, int T, int nd, bool pk, bool chain_args, bool step_args) {
+    GruLayerPlan p{};
+    const long pkg = (long)pk_floats(B, 3 * H);
+    pk = pk && pk_ok(H);
+    const int CHB = chain_chunk_rows_bwd(H, B, T, nd);
+    if (pk && chain_args && CHB > 0) {
+        // one persistent launch -- or, for a batch beyond one resident launch, one launch per chunk of CHB rows (the rows
+        // are independent; saves / dgh keep the full batch's time stride; bias gradients accumulate with atomics)
+        const long pkc = (long)pk_floats(CHB, 3 * H);
+        const int n = B / CHB;
+        const ChainLaunchPlan lp = gru_chain_bwd_plan(H, CHB, T, nd, B % 32 == 0 && CHB % 32 == 0);
+        p.route = GRU_ROUTE_CHAIN1; p.rows = CHB; p.launches = n; p.b = lp.b; p.groups = lp.groups; p.members = lp.members;
+        // (the rings sit as the forward chains' do: a contiguous ring per chunk, chain_ring_floats apart, where the forward launch of
+        // this shape is second-generation; otherwise chunk c works on its rows of the two slots of the full-batch ring)
+        p.ring = n == 1 ? GRU_RING_FULL : gru_chain2_ok(H, CHB, T, nd) ? GRU_RING_OWN : GRU_RING_ROWS;
+        p.ring_floats = p.ring == GRU_RING_OWN ? (long)(n - 1) * 3 * pkc + 2 * pkc : (long)(n - 1) * pkc + pkg + pkc;
+        return p;
+    }
+    // More rows than the chain launches take (chunks stop at INET_CHAIN_CHUNK_MAX rows): one bf16-pipe product per time step with
+    // the gate derivatives as its epilogue (gru_step_bf3.hip) instead of the f32-input per-step kernels
+    if (pk && step_args && nd <= 2 && gru_step_bf3_bwd_ok(H, B, T, nd)) {
+        p.route = GRU_ROUTE_STEP_BF3; p.rows = B; p.launches = T; p.ring = GRU_RING_FULL; p.ring_floats = (long)chain_ring_floats(B, 3 * H);
+        return p;
+    }
+    p.route = GRU_ROUTE_STEP; p.rows = B; p.launches = T; p.ring = GRU_RING_FULL; p.ring_floats = pk ? 2 * pkg : 0;
+    return p;
+}
+
 // The BPTT chain, steps T - 1 .. 0; the gradient wrt the initial hidden follows step 0.
 int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s) {
     for (int i = 0; i < nd; ++i) d[i].emitted = 0;
@@ -231,61 +300,50 @@ int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s) {
     const long pkg = (long)pk_floats(B, 3 * H);
     bool pk = pk_ok(H);
     for (int i = 0; i < nd; ++i) if (!d[i].Wpk_hhT || !d[i].dghpk) pk = false;
-    {
-        bool any0 = false, all0 = true, wok = true;
-        for (int i = 0; i < nd; ++i) { if (d[i].dh0) any0 = true; else all0 = false; if (!d[i].W_hh) wok = false; }
-        const int CHB = chain_chunk_rows_bwd(H, B, T, nd);
-        if (pk && wok && d[0].sync && (!any0 || all0) && CHB > 0) {
-            // one persistent launch -- or, for a batch beyond one resident launch, one launch per chunk of CHB rows (the rows
-            // are independent; saves / dgh keep the full batch's time stride; bias gradients accumulate with atomics)
-            const long pkc = (long)pk_floats(CHB, 3 * H);
-            // (the rings sit as the forward chains' do: a contiguous ring per chunk, chain_ring_floats apart, where the forward launch of
-            // this shape is second-generation; otherwise chunk c works on its rows of the two slots of the full-batch ring)
-            const bool own_rings = gru_chain2_ok(H, CHB, T, nd);
-            const bool emits_rows = B % 32 == 0 && CHB % 32 == 0 && gru_chain_bwd_emits_rows(H, CHB, T, nd);
-            for (int c = 0; c < B / CHB; ++c) {
-                const long r0 = (long)c * CHB;
-                GruChainBwd a{};
-                a.H = H; a.B = CHB; a.T = T; a.nprob = nd;
-                for (int i = 0; i < nd; ++i) {
-                    const DirBwd& D = d[i];
-                    GruChainBwdProb& P = a.p[i];
-                    P = bwd_prob(D, r0, H, B);
-                    if (own_rings) P.gx = D.dghpk + (long)c * 3 * pkc;
-                    else { P.gx = D.dghpk + (long)c * pkc; P.gx_slot_bytes = (int)(pkg * sizeof(float)); }
-                    if (emits_rows && D.em.rows) { P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 1; }   // (row pieces only)
-                }
-                a.counters = d[0].sync; a.prezeroed = (c == 0 && CHB == B) ? d[0].sync_prezeroed : 0;
-                INET_TRY(launch_gru_chain_bwd(a, s));
-            }
-            for (int i = 0; i < nd; ++i)
-                if (d[i].dgi_sum && d[i].dgi_sum_done) *d[i].dgi_sum_done = 1;
-            return 0;
-        }
+    bool any0 = false, all0 = true, wok = true, stepb = true;
+    for (int i = 0; i < nd; ++i) {
+        if (d[i].dh0) any0 = true; else all0 = false;
+        if (!d[i].W_hh) wok = false;
+        stepb = stepb && d[i].wp3T && d[i].W_hh && d[i].dhz && !d[i].dgi_sum;
     }
-    {
-        // More rows than the chain launches take (chunks stop at INET_CHAIN_CHUNK_MAX rows): one bf16-pipe product per time step with
-        // the gate derivatives as its epilogue (gru_step_bf3.hip) instead of the f32-input per-step kernels
-        bool any0 = false, all0 = true, stepb = pk && nd <= 2 && gru_step_bf3_bwd_ok(H, B, T, nd);
-        for (int i = 0; i < nd; ++i) {
-            if (d[i].dh0) any0 = true; else all0 = false;
-            stepb = stepb && d[i].wp3T && d[i].W_hh && d[i].dhz && !d[i].dgi_sum;
-        }
-        if (stepb && (!any0 || all0)) {
-            GruStepsBf3Bwd L{};
-            L.H = H; L.B = B; L.T = T; L.nprob = nd;
+    const bool dh0_ok = !any0 || all0;
+    const GruLayerPlan pl = gru_layer_bwd_plan(H, B, T, nd, pk, wok && d[0].sync && dh0_ok, stepb && dh0_ok);
+    if (pl.route == GRU_ROUTE_CHAIN1) {
+        const int CHB = pl.rows;
+        const long pkc = (long)pk_floats(CHB, 3 * H);
+        for (int c = 0; c < pl.launches; ++c) {
+            const long r0 = (long)c * CHB;
+            GruChainBwd a{};
+            a.H = H; a.B = CHB; a.T = T; a.nprob = nd;
             for (int i = 0; i < nd; ++i) {
                 const DirBwd& D = d[i];
-                GruChainBwdProb& P = L.p[i];
-                P = bwd_prob(D, 0, H, B);
-                P.gx = D.dghpk;
-                if (D.em.rows && B % 32 == 0) { P.em.rows = D.em.rows; P.em.rows_piece = D.em.rows_piece; P.em.rows_kb = D.em.rows_kb;
-                                                P.em.rows_kb0 = D.em.rows_kb0; P.em.B_full = B; P.em.r0 = 0; D.emitted = 1; }
-                INET_TRY(gru_step_bf3_split_wT(H, D.W_hh, D.wp3T, s));
-                L.WpT[i] = D.wp3T; L.dhz[i] = D.dhz;
+                GruChainBwdProb& P = a.p[i];
+                P = bwd_prob(D, r0, H, B);
+                if (pl.ring == GRU_RING_OWN) P.gx = D.dghpk + (long)c * 3 * pkc;
+                else { P.gx = D.dghpk + (long)c * pkc; P.gx_slot_bytes = (int)(pkg * sizeof(float)); }
+                if (pl.b.EMR && D.em.rows) { P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 1; }   // (row pieces only)
             }
-            return launch_gru_steps_bf3_bwd(L, s);
+            a.counters = d[0].sync; a.prezeroed = (c == 0 && CHB == B) ? d[0].sync_prezeroed : 0;
+            INET_TRY(launch_gru_chain_bwd(a, s));
         }
+        for (int i = 0; i < nd; ++i)
+            if (d[i].dgi_sum && d[i].dgi_sum_done) *d[i].dgi_sum_done = 1;
+        return 0;
+    }
+    if (pl.route == GRU_ROUTE_STEP_BF3) {
+        GruStepsBf3Bwd L{};
+        L.H = H; L.B = B; L.T = T; L.nprob = nd;
+        for (int i = 0; i < nd; ++i) {
+            const DirBwd& D = d[i];
+            GruChainBwdProb& P = L.p[i];
+            P = bwd_prob(D, 0, H, B);
+            P.gx = D.dghpk;
+            if (D.em.rows && B % 32 == 0) { P.em.rows = D.em.rows; P.em.rows_piece = D.em.rows_piece; P.em.rows_kb = D.em.rows_kb;
+                                            P.em.rows_kb0 = D.em.rows_kb0; P.em.B_full = B; P.em.r0 = 0; D.emitted = 1; }
+            INET_TRY(gru_step_bf3_split_wT(H, D.W_hh, D.wp3T, s));
+            L.WpT[i] = D.wp3T; L.dhz[i] = D.dhz;
+        }
+        return launch_gru_steps_bf3_bwd(L, s);
     }
     for (int step = T - 1; step >= 0; --step) {
         GruBwdBatch bt{};

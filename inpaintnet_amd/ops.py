@@ -506,6 +506,29 @@ def gemm_plan(M, N, K, a_kmajor=False, b_kmajor=False, lda=None, ldb=None, bias=
     return dict(zip(GEMM_PLAN_KEYS, list(out)), flops=work[0], bytes=work[1], label=label.value.decode())
 
 
+GRU_PLAN_KEYS = ("route", "rows", "launches", "gen", "MS", "SQ", "OCC", "EMR", "two_at_a_time", "ring", "groups", "members", "ring_floats",
+                 "ring_capacity", "chain_capacity", "max_groups")
+GRU_ROUTES = ("step", "chain1", "chain2", "step_bf3")
+GRU_RINGS = ("full", "own", "rows")
+
+
+def gru_chain_plan(H, B, T, nprob=2, save=True):
+    """What one GRU layer of nprob directions launches for (H, B, T) under the options set now, without a GPU (inet_gru_chain_plan):
+    (forward, backward), each a dict of GRU_PLAN_KEYS with "route" and "ring" as names (GRU_ROUTES, GRU_RINGS); backward is None
+    without save."""
+    out = (C.c_int64 * 32)()
+    check(_lib.lib().inet_gru_chain_plan(H, B, T, nprob, int(bool(save)), out), "inet_gru_chain_plan")
+    plans = []
+    for o in (out[:16], out[16:]):
+        p = dict(zip(GRU_PLAN_KEYS, o))
+        if p["route"] < 0:
+            plans.append(None)
+            continue
+        p["route"], p["ring"] = GRU_ROUTES[p["route"]], GRU_RINGS[p["ring"]]
+        plans.append(p)
+    return tuple(plans)
+
+
 def gemm_group(products):
     """Up to four INDEPENDENT products in one launch where a grouped kernel applies (inet_gemm_group; gemm_group_plan tells), one after
     the other otherwise.  products: dicts of gemm()'s arguments -- A, B, M, N, K, out (required here), and optionally a_kmajor,

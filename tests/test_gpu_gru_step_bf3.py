@@ -20,13 +20,12 @@ Measured on an MI355X: MEASURED below holds the worst tensor of every case; the 
 float64, a factor of 13 under the cap.  Under INET_TEST_POISON=1 (NaN-filled allocator pool) every case passes with the same step-path figures:
 no ring slot, save or piece buffer is read before it is written.
 """
-import csv
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import torch_ref as O
+from tests import bigru2_ref as R
 from tests import golden_util as G
 
 if torch.cuda.is_available():
@@ -45,28 +44,12 @@ MEASURED = {
 }
 
 
-def _labels(tmp_path, name):
-    path = str(tmp_path / name)
-    ops.prof_dump(path)
-    return [r["label"] for r in csv.DictReader(open(path))]
-
-
-def _rel(got, ref):
-    """max |got - ref| / max |ref|; against an all-zero reference (dW_hh at T = 1 from a zero state) the absolute error."""
-    ref = torch.as_tensor(ref).detach().double().cpu()
-    scale = float(ref.abs().max())
-    return float((got.detach().double().cpu() - ref).abs().max()) / (scale if scale > 0.0 else 1.0)
+_labels, _rel = R.labels, R.rel
 
 
 def _check(tag, errs):
     """errs: {tensor: (err_step, err_base)}.  Prints every pair, then applies the rule of the module docstring."""
-    for k, (es, eb) in errs.items():
-        print(f"{tag} {k}: step {es:.2e} base {eb:.2e}")
-    ws = max(errs, key=lambda k: errs[k][0])
-    print(f"{tag} WORST step {errs[ws][0]:.2e} ({ws}); worst base {max(e[1] for e in errs.values()):.2e}")
-    bad = [(k, es, eb) for k, (es, eb) in errs.items()
-           if not (es <= 2.0 * eb + FLOOR and es < CAP and eb < 0.5 * CAP)]
-    assert not bad, (tag, bad)
+    R.check(tag, errs, "step", CAP, FLOOR)
 
 
 # ------------------------------------------------------------------------------------------------ 1. inet_bigru2_fwd / _bwd
@@ -98,73 +81,14 @@ CASES = {
 
 def _bigru2_case(name):
     """Parameters, inputs and the float64 reference of one case (computed once per test)."""
-    from inpaintnet_amd import layout
     B, T, K, H, scalar, chains, with_h0, want_dh0, with_mask = CASES[name]
-    g = torch.Generator().manual_seed(1000 + sorted(CASES).index(name))
-    shapes = layout._gru("g", K, H, 2, True)
-    offs, total = layout.arena_offsets(dict(shapes))
-    # weights ~ N(0, 1/H), biases ~ 0.1: the recurrence stays contractive at every T
-    P = {k: torch.randn(*s, generator=g) * ((1.0 / np.sqrt(H)) if "weight" in k else 0.1) for k, s in shapes}
-    flat = torch.zeros(total)
-    for k, (off, s) in offs.items():
-        flat[off:off + P[k].numel()] = P[k].reshape(-1)
-    h0 = torch.tanh(torch.randn(4, B, H, generator=g)) if with_h0 else None
-    mask = (torch.rand(T, B, 2 * H, generator=g) > 0.5).float() * 2.0 if with_mask else None
-    xs = torch.randn(1, generator=g) if scalar else None
-    x = None if scalar else torch.randn(B, T, K, generator=g)
-    wo = torch.randn(B, T, 2 * H, generator=g)
-    wh = torch.randn(4, B, H, generator=g)
-    # float64 reference
-    P64 = {k: v.double().requires_grad_(True) for k, v in P.items()}
-    h64 = (h0.double() if with_h0 else torch.zeros(4, B, H, dtype=torch.float64)).requires_grad_(True)
-    if scalar:
-        xs64 = xs.double().requires_grad_(True)
-        x64 = xs64.view(1, 1, 1).expand(B, T, 1)
-    else:
-        x64 = x.double().requires_grad_(True)
-    out, hn = O.gru_stack(x64, h64, P64, "g", 2, True, [mask.double().permute(1, 0, 2)] if with_mask else None)
-    ((out * wo.double()).sum() + (hn * wh.double()).sum()).backward()
-    ref = {"out": out.detach(), "hn": hn.detach(), "dx": (xs64 if scalar else x64).grad}
-    if want_dh0:
-        ref["dh0"] = h64.grad
-    for k in P:
-        ref["d" + k] = P64[k].grad
-    dev = lambda t: None if t is None else t.to(DEV)
-    return dict(P=P, offs=offs, flat=flat.to(DEV), x=dev(x), xs=dev(xs), h0=dev(h0), mask=dev(mask), wo=dev(wo), wh=dev(wh),
-                ref=ref, fwd_ref={"out": ref["out"], "hn": ref["hn"]})
+    return R.make_case(B, T, K, H, scalar, with_h0, want_dh0, with_mask, 1000 + sorted(CASES).index(name))
 
 
 def _bigru2_run(name, c, key12, tmp_path, save=True):
     """One forward (+ backward) call under (key 4, key 12) = (the case's, key12): {tensor: error vs float64}, profile labels."""
-    B, T, K, H, scalar, chains, with_h0, want_dh0, with_mask = CASES[name]
-    try:
-        ops.set_option(4, chains)
-        ops.set_option(12, key12)
-        ops.prof_enable(True)
-        o, h, ws = ops.bigru2_fwd(c["x"], c["xs"], c["flat"], H, B, T, K, h0=c["h0"], mask=c["mask"], save=save)
-        got = {"out": o, "hn": h}
-        if save:
-            grads = torch.zeros_like(c["flat"])
-            dxs = torch.zeros(1, device=DEV) if scalar else None
-            dx, dh0 = ops.bigru2_bwd(c["x"], c["xs"], c["flat"], grads, H, B, T, K, c["mask"], c["wo"], c["wh"], ws,
-                                     want_dx=not scalar, dx_scalar=dxs, want_dh0=want_dh0)
-            ops.side_join()
-            got["dx"] = dxs if scalar else dx
-            if want_dh0:
-                got["dh0"] = dh0
-            for k, (off, sh) in c["offs"].items():
-                got["d" + k] = grads[off:off + c["P"][k].numel()].reshape(sh)
-        torch.cuda.synchronize()
-        labels = _labels(tmp_path, f"{name}_{key12}_{int(save)}.csv")
-    finally:
-        ops.prof_enable(False)
-        ops.set_option(4, 1)
-        ops.set_option(12, 256)
-    ref = c["ref"] if save else c["fwd_ref"]
-    assert set(got) == set(ref)
-    for k, v in got.items():
-        assert bool(torch.isfinite(v).all()), (name, key12, k)
-    return {k: _rel(got[k], ref[k]) for k in ref}, labels
+    chains = CASES[name][5]
+    return R.run(c, {4: chains, 12: key12}, tmp_path, f"{name}_{key12}_{int(save)}.csv", save)
 
 
 @pytest.mark.gpu
