@@ -126,6 +126,33 @@ int inet_vae_decoder_sample(const inet_vae_config* cfg, int batch, const float* 
 int inet_vae_decoder_sample_ex(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
                                const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
                                float temperature, const double* uniforms, int top_k, double top_p, float* logp, void* stream);
+/* The same behind PER-TICK TOKEN CONSTRAINTS: a mask of allowed tokens per (row, tick), applied in front of the truncated rule inside the
+ * launch (the token of tick t is fed back into tick t + 1 there; csrc/sample.h).
+ * Mask layout.  `allow` is an array of 64-bit words [rows][T][NW], with NW = ceil(V / 64).  Token v is allowed iff bit v % 64 of word
+ * v / 64 is set.  Bits at or above V are ignored.  A null `allow` means no constraint.
+ * For one (row, tick), with logits x[0..V), temperature T, uniform u, top_k and top_p:
+ *  0. Empty mask.  A mask with no bit set in [0, V) counts as all ones for that tick.  The Python surfaces refuse such a tick with
+ *     ValueError before any launch.
+ *  1. Scores.  s_v = T x_v in f32.  The NaN test of section 10 runs over all V values of s, as today.  The mask therefore does not
+ *     change which ticks fall back.  Then s_v = -inf for every banned v, and m = the maximum over the allowed tokens.
+ *  2. Truncation and draw.  Steps 2-7 of section 11 run unchanged on these s, with V and K = top_k unchanged.  Banned tokens tie at
+ *     -inf and rank last.  Their e = expf(-inf - m) is 0, so they add no mass and cannot be the first prefix above u S.  A top_k above
+ *     the number of allowed tokens keeps all of them.  logp is taken under the masked and truncated distribution.
+ *  3. Fallback.  Where the rule does not apply (a NaN among s, m or S not finite, u outside [0, 1) or NaN), the tick takes today's
+ *     argmax rule on the logits with every banned entry replaced by -inf.  The decode kernel may use its padding value -1 instead,
+ *     which lies below every post-ReLU logit.  logp is NaN there.  The token is still an allowed one.
+ * (Sections 10 and 11 of DESIGN.md: the sampling rule of inet_vae_decoder_sample and the truncated rule of inet_vae_decoder_sample_ex.)
+ * Consequences: a null mask or a mask of all ones gives inet_vae_decoder_sample_ex bit for bit (tokens, logits, logp); a one-bit mask
+ * returns that token for every u and every finite T, with logp exactly 0 (NaN on a fallback tick); no banned token is ever returned;
+ * for T > 0 the masked draw on x equals the unmasked draw on x with -inf written at the banned places.
+ * allow: [B][T][NW] words on the device, or null -- then this IS inet_vae_decoder_sample_ex.  A constrained call runs the masked build
+ * of the register-resident launch (the truncated call's plan: inet_decode_b1_plan_trunc) or, for every other shape,
+ * inet_sample_constrained's kernel tick by tick: its launch labels start with "cons_" (cons_decode_b1..., cons_sample ...).
+ * -1 where inet_vae_decoder_sample_ex returns it, and for a mask with more than 64 ticks. */
+int inet_vae_decoder_sample_cx(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
+                               const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
+                               float temperature, const double* uniforms, int top_k, double top_p, float* logp,
+                               const uint64_t* allow, void* stream);
 /* dweights [B,T,V] = dLoss/dweights; weights = the forward output; grads may be null (frozen decoder:
  * LatentRNN/latent_rnn.py:42-43) in which case only dz [B,Z] is produced.  `tokens_in` are the tokens that
  * were fed back (= samples of the forward call). */
@@ -184,6 +211,13 @@ int inet_sample_temperature(const float* weights, int64_t ld_w, int rows, int V,
 int inet_sample_truncated(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                           int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
                           void* stream);
+/* The constrained rule of inet_vae_decoder_sample_cx on rows of V logits, one wavefront per row: allow + row*allow_stride (the stride
+ * counted in words) = the row's ceil(V / 64) words of allowed tokens, up to 8; a null allow: inet_sample_truncated.  A row where the
+ * sampling rule does not apply takes inet_argmax's rule over its allowed tokens (a banned entry counts as -inf and is never returned)
+ * and a NaN logp.  -1 where inet_sample_truncated returns it. */
+int inet_sample_constrained(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
+                            int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
+                            const uint64_t* allow, int64_t allow_stride, void* stream);
 
 /* ---- optimizer: torch.optim.Adam as built at utils/trainer.py:32-35, stepped at :172-177 -------- */
 /* p,g,m,v: arenas of n floats; step is 1-based; grads are multiplied by gscale first (1/world_size for DP) */
@@ -509,6 +543,7 @@ int inet_decode_b1_plan(int B, int V, int Z, int* out8);
 int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8);
 /* ... and for a truncated call (inet_vae_decoder_sample_ex with truncation on or a logp): the truncating build has a merged build
  * for one row with V <= 32 alone (the others would spill registers), so more of its plans place workgroup C. */
+/* (A constrained call -- inet_vae_decoder_sample_cx with a mask -- has the truncated call's plan: every masked build fits.) */
 int inet_decode_b1_plan_trunc(int B, int V, int Z, int* out8);
 /* What inet_gemm (nbatch = 1) / inet_gemm_batched (nbatch 2..8: no bias, epi 0, acc 1) launch for a call, under the options set now
  * (inet_set_option keys 2, 3, 5), without a GPU: the dispatcher's planner (csrc/gemm.hip gemm_plan) behind the C-ABI.  out16 = {family

@@ -155,6 +155,7 @@ struct B1Args {
     chain::Status status;
     const double* uniforms; float temperature;   // the sampling build: one uniform per (row, tick) [B, T], the logits' factor
     int top_k; double top_p; float* logp;        // the truncating build: sample.h's truncation in front of the draw; logp [B, T] or null
+    const unsigned long long* allow;             // the masked build: the allowed tokens' words [B, T, ceil(V / 64)] (sample.h's layout)
 };
 
 #define B1_STAMP(who, t, i) do { if (stamps && tid == 0) stamps[((who) * 32 + (t)) * 8 + (i)] = wall_clock64(); } while (0)
@@ -533,6 +534,29 @@ __device__ __forceinline__ int sample_token_trunc(const float (&lg)[NVL], float 
     else S = 1.0;
     return tok;
 }
+// CONSTRAINED SAMPLING (MASK = true, the masked build of the truncating build; sample.h has the rule): the tick's mask words `aw` (from
+// sample::mask_words: bits at or above V cleared, an empty mask all ones) ban tokens behind the NaN test and in front of the truncation.
+// The words arrive through a wave-uniform address like `ut`, so the token is a pure function of `lgs`, u, the mask words and kernel arguments.
+template <int NVL>
+__device__ __forceinline__ int sample_token_cons(const float (&lg)[NVL], float temp, double u, int V, int lane, int top_k, double top_p,
+                                                 const unsigned long long (&aw)[NVL], float& gap, double& S) {
+    float sv[NVL];
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < NVL; ++j) {
+        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
+        nan |= sv[j] != sv[j];
+    }
+    gap = __builtin_nanf("");
+    S = 1.0;
+    if (__ballot(nan)) return -1;
+    const float ms = wave_max_dpp(sample::mask_scores<NVL>(sv, aw, lane));
+    sample::truncate<NVL>(sv, ms, top_k, top_p, V, lane);
+    const int tok = sample::pick<NVL>(sv, ms, u, V, lane, S);
+    if (tok >= 0) gap = sample::logp_gap<NVL>(sv, ms, tok);
+    else S = 1.0;
+    return tok;
+}
 // ... behind the last tick: logp[row, t] of the team's rows, one (row, tick) per thread (the picking waves' LDS writes are ordered by the
 // barrier the caller's loop ends with or by this one)
 template <int NB>
@@ -553,9 +577,10 @@ constexpr int kSharedRowsSmall = 3;              // ... and for four to six meas
 // self-check all ask here.  The SAMPLING build of two-row teams beside groups of six rows (V <= 32, eleven to sixteen measures) does
 // not fit: 256 VGPRs and two spilled (the argmax build: 253) -- it is not built, such a call runs workgroup C.  The TRUNCATING build
 // (sample == 2) has a merged build for one row with V <= 32 alone: with two logit blocks per thread (one row, 32 < V <= 64; two rows, V <=
-// 32) it comes out at 255 / 256 VGPRs with 12 bytes of scratch -- not built either, workgroup C.
+// 32) it comes out at 255 / 256 VGPRs with 12 bytes of scratch -- not built either, workgroup C.  The MASKED build (sample == 3) has the
+// truncating build's merged builds: a constrained call has the truncated call's plan.
 __host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, int sample) {
-    return nb * nj <= 2 && !(sample && nb == 2 && nbr == kSharedRows) && !(sample == 2 && nb * nj == 2);
+    return nb * nj <= 2 && !(sample && nb == 2 && nbr == kSharedRows) && !(sample >= 2 && nb * nj == 2);
 }
 
 // Shared recurrent groups (round 6, NBR > NB): seven to sixteen measures used to run as teams of FOUR rows (49 workgroups each: four
@@ -564,10 +589,12 @@ __host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, int sam
 // tick.  So they are shared: two-row critical teams (17 workgroups each, on one XCD) for every pair of rows, and recurrent groups
 // of 32 workgroups that serve NBR = 6 rows -- three teams -- each: 8 x 17 + 3 x 32 = 232 workgroups for sixteen measures, every
 // row on a two-row tick.  A group's rows without a team (the last group of a call) are skipped (Ctx.nact).
-// (TRUNC, the truncating build of the sampling build: behind SAMPLE, so that every build without it keeps its parameters)
-template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB, bool SAMPLE = false, bool TRUNC = false>
+// (TRUNC, the truncating build of the sampling build: behind SAMPLE, so that every build without it keeps its parameters; MASK, the
+//  masked build of the truncating build, behind TRUNC likewise)
+template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB, bool SAMPLE = false, bool TRUNC = false, bool MASK = false>
 __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     static_assert(SAMPLE || !TRUNC, "the truncating build is a sampling build");
+    static_assert(TRUNC || !MASK, "the masked build is a truncating build");
     constexpr int XROWS = NB > NBB ? (NB > NBR ? NB : NBR) : (NBB > NBR ? NBB : NBR);
     __shared__ __attribute__((aligned(16))) float xs[XROWS][2][XS];
     __shared__ float lgs[NB][32 * NJ];
@@ -596,7 +623,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     const int nb = a.T / a.G;
     const DecodeB1Beat& bp = a.bp;
     // MG, the merged build: workgroup C does not exist, every TBi_k does C's work for itself next to its own (CB below)
-    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE + TRUNC);
+    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE + TRUNC + MASK);
 
     if (role == R_C) {
         if (MG) return;
@@ -628,10 +655,19 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             for (int g = 0; g < 3; ++g) tb[r][g] = a.table[(long)tok[r] * D3 + g * DH + u];
         if (!get_2d<NB, 3>(ex + G_GH0 + u, G_END, DH, 1u, a.status, gh, hw)) *bad = 1;
         [[maybe_unused]] int done = 0;                         // (the truncating build: ticks finished)
+        constexpr int NVL = (32 * NJ + 63) / 64;
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
             double ut = 0.0;                                   // the sampling build: this tick's uniform, requested here and read behind the head
             if constexpr (SAMPLE) { if (picks) ut = a.uniforms[urow_at + t]; }
+            // the masked build: this (row, tick)'s mask words, requested next to `ut` through the same wave-uniform address
+            [[maybe_unused]] unsigned long long aw[MASK ? NVL : 1] = {};
+            if constexpr (MASK) {
+                if (picks) {
+#pragma unroll
+                    for (int j = 0; j < NVL; ++j) aw[j] = a.allow[(urow_at + t) * NVL + j];
+                }
+            }
             if (t % a.G == 0) {
                 const long beat = t / a.G;
                 if (FUSED) {
@@ -697,7 +733,6 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             // maximum by DPP, its lowest index by ballot
             if (NB == 1 || wave < NB) {
                 const int arow = NB == 1 ? 0 : wave;
-                constexpr int NVL = (32 * NJ + 63) / 64;
                 float lg[NVL], m = -1.f;
 #pragma unroll
                 for (int j = 0; j < NVL; ++j) {
@@ -707,10 +742,12 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 }
                 m = wave_max_dpp(m);
                 int bi = 0;
+                if constexpr (MASK) sample::mask_words<NVL>(aw, a.V);
                 if constexpr (TRUNC) {
                     float gap;
                     double tot;
-                    bi = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
+                    if constexpr (MASK) bi = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
+                    else bi = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
                     if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
                 }
                 else if constexpr (SAMPLE) bi = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
@@ -722,6 +759,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                         for (int j = 0; j < NVL; ++j) {
                             const int v = lane + 64 * j;
                             lg[j] = v < a.V ? lgs[arow][v] : -1.f;
+                            if constexpr (MASK) { if (!sample::allowed(aw[j], lane)) lg[j] = -1.f; }   // (a banned token: the padding value)
                             m = fmaxf(m, lg[j]);
                         }
                         m = wave_max_dpp(m);
@@ -774,7 +812,9 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         // travels -- of the two hand-offs of a tick (C -> TBi -> C) only the all-gather of h1_t among the 16 workgroups is left.
         // All of them run the same instructions on the same values, so they agree on every token bit for bit -- the sampling build too:
         // sample::pick is a pure function of the row's logits `lgs`, which every copy computes from the same gathered h1_t with the same
-        // instructions, and of the uniform u[row, t], which every copy reads from the same address; nothing else may enter a token.  CB_0 alone
+        // instructions, and of the uniform u[row, t], which every copy reads from the same address; the masked build adds the mask words
+        // of (row, t), which all sixteen copies likewise read from the same address, and top_k / top_p are kernel arguments: the token is a pure
+        // function of `lgs`, u, the mask words and kernel arguments, and nothing else may enter it.  CB_0 alone
         // publishes h0_t (for TA) and writes the outputs.  h0, h1 and gh0 alternate between two granule slots by tag parity: a CB
         // workgroup does not wait for its 15 peers to have READ a value before it writes the next one (a peer's read of h1_t is
         // ordered before its own h1_t+1, which the writer of h1_t+2 has to have seen: two slots are enough; likewise gh0, h0).
@@ -816,11 +856,20 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             for (int g = 0; g < 3; ++g) tb[r][g] = a.table[(long)tok[r] * D3 + g * DH + u];
         if (!get_2d<NB, 3>(ex + (gh0_near ? G_GH0N + D3 : G_GH0X) + u, G_END, DH, 1u, a.status, gh, hw)) *bad = 1;
         [[maybe_unused]] int done = 0;                         // (the truncating build: ticks finished)
+        constexpr int NVL = (32 * NJ + 63) / 64;
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
             const unsigned tag = (unsigned)t + 1u;
             double ut = 0.0;                                   // the sampling build: this tick's uniform, requested here and read behind the head
             if constexpr (SAMPLE) { if (picks) ut = a.uniforms[urow_at + t]; }
+            // the masked build: this (row, tick)'s mask words, requested next to `ut` through the same wave-uniform address
+            [[maybe_unused]] unsigned long long aw[MASK ? NVL : 1] = {};
+            if constexpr (MASK) {
+                if (picks) {
+#pragma unroll
+                    for (int j = 0; j < NVL; ++j) aw[j] = a.allow[(urow_at + t) * NVL + j];
+                }
+            }
             const int g_h1 = slot_h1(tag);
             float gh1[NB][3];
             unsigned long long hw1[NB][3];
@@ -917,7 +966,6 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             if (out) B1_STAMP(0, t, 4);
             if (NB == 1 || wave < NB) {
                 const int arow = NB == 1 ? 0 : wave;
-                constexpr int NVL = (32 * NJ + 63) / 64;
                 float lg[NVL], m = -1.f;
 #pragma unroll
                 for (int j = 0; j < NVL; ++j) {
@@ -927,10 +975,12 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 }
                 m = wave_max_dpp(m);
                 int best = 0;
+                if constexpr (MASK) sample::mask_words<NVL>(aw, a.V);
                 if constexpr (TRUNC) {
                     float gap;
                     double tot;
-                    best = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
+                    if constexpr (MASK) best = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
+                    else best = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
                     if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
                 }
                 else if constexpr (SAMPLE) best = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
@@ -942,6 +992,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                         for (int j = 0; j < NVL; ++j) {
                             const int v = lane + 64 * j;
                             lg[j] = v < a.V ? lgs[arow][v] : -1.f;
+                            if constexpr (MASK) { if (!sample::allowed(aw[j], lane)) lg[j] = -1.f; }   // (a banned token: the padding value)
                             m = fmaxf(m, lg[j]);
                         }
                         m = wave_max_dpp(m);
@@ -1094,6 +1145,8 @@ int placed_grid(int teams, int rteams, int beat_wgs, int crit = kCrit) {
 // shapes have a merged sampling build; under the other modes it has no plan here, and vae_decoder_fwd samples tick by tick.
 // A TRUNCATED call (DecodeChainArgs.trunc: top-k / nucleus truncation, or the draws' log-probabilities wanted) likewise, with the
 // truncating builds (decode_b1_kernel<..., true, true>) and their merged_build(); at most kTruncTicks ticks.
+// A CONSTRAINED call (DecodeChainArgs.allow: a mask of allowed tokens per (row, tick)) has the truncated call's plan with the masked builds
+// (decode_b1_kernel<..., true, true, true>): every one of them fits without a spill.
 
 // What launch_decode_b1 launches for a call, as a value (also behind inet_decode_b1_plan: the planner is tested without a GPU).  The
 // plan names its instantiation decode_b1_kernel<nj, fused, nb, nbb, nbr> itself (dispatch_b1).
@@ -1106,7 +1159,7 @@ struct B1Plan {
     int crit;                                    // critical workgroups per team under place_role: kCritTA, NU (merged build) or kCrit
     int place, stride, grid, live, beat_wgs;
     int rows;                                    // granule rows the launch addresses
-    int sample;                                  // 1: the sampling build, 2: the truncating build
+    int sample;                                  // 1: the sampling build, 2: the truncating build, 3: the masked build
     bool ok;                                     // the plan fits the chip
 };
 // a candidate plan's rows: teams of nb rows, the folded beat path's nbb, shared groups (ta_crit: the TA stay critical beside the
@@ -1196,10 +1249,10 @@ template <int NJ, int S>
 static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 #define B1_INST(F, NB, NBB, NBR)                                                                                             \
     if (p.fused == (F) && p.nb == (NB) && p.nbb == (NBB) && p.nbr == (NBR)) {                                               \
-        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR, S != 0, S == 2>), dim3(p.grid), dim3(NT), 0, s, *a);  \
+        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR, S != 0, S >= 2, S == 3>), dim3(p.grid), dim3(NT), 0, s, *a);  \
         return true;                                                                                                        \
     }
-    // (S = 1 / 2, the sampling and the truncating builds: the default mode's plans only -- candidates())
+    // (S = 1 / 2 / 3, the sampling, the truncating and the masked builds: the default mode's plans only -- candidates())
     B1_INST(true, 1, 1, 1)                       // one team, one row, beat path folded in
     if constexpr (!S) { B1_INST(true, 2, 2, 2) } // ... two rows (modes 3, 5)
     B1_INST(true, 1, kDecodeB1OneRowTeamsMax, 1) // two / three one-row teams
@@ -1213,12 +1266,25 @@ static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 #undef B1_INST
     return false;
 }
+// (the masked builds are named in a function of their own BEHIND this one: the instantiations are emitted in the order their first use is
+//  met, so the builds that existed before keep their places at the front of the code object)
+static bool dispatch_b1_masked(const B1Plan& p, const B1Args* a, hipStream_t s);
 static bool dispatch_b1(const B1Plan& p, const B1Args* a, hipStream_t s) {
+    if (p.sample == 3) return dispatch_b1_masked(p, a, s);
     switch (p.nj) {
         case 1: return p.sample == 2 ? dispatch_b1_nj<1, 2>(p, a, s) : p.sample ? dispatch_b1_nj<1, 1>(p, a, s) : dispatch_b1_nj<1, 0>(p, a, s);
         case 2: return p.sample == 2 ? dispatch_b1_nj<2, 2>(p, a, s) : p.sample ? dispatch_b1_nj<2, 1>(p, a, s) : dispatch_b1_nj<2, 0>(p, a, s);
         case 3: return p.sample == 2 ? dispatch_b1_nj<3, 2>(p, a, s) : p.sample ? dispatch_b1_nj<3, 1>(p, a, s) : dispatch_b1_nj<3, 0>(p, a, s);
         case 4: return p.sample == 2 ? dispatch_b1_nj<4, 2>(p, a, s) : p.sample ? dispatch_b1_nj<4, 1>(p, a, s) : dispatch_b1_nj<4, 0>(p, a, s);
+        default: return false;
+    }
+}
+static bool dispatch_b1_masked(const B1Plan& p, const B1Args* a, hipStream_t s) {
+    switch (p.nj) {
+        case 1: return dispatch_b1_nj<1, 3>(p, a, s);
+        case 2: return dispatch_b1_nj<2, 3>(p, a, s);
+        case 3: return dispatch_b1_nj<3, 3>(p, a, s);
+        case 4: return dispatch_b1_nj<4, 3>(p, a, s);
         default: return false;
     }
 }
@@ -1237,14 +1303,15 @@ int decode_b1_rows(int B) {
 void decode_b1_set_mode(int m) { g_mode = (m < 0 || m > 5) ? 4 : m; }
 
 bool decode_b1_shape_ok(int B, int H, int V, int T, int G, int sample) {
-    if (sample == 2 && T > kTruncTicks) return false;           // (the truncating build files one (gap, total) per tick in LDS)
+    if (sample >= 2 && T > kTruncTicks) return false;           // (the truncating build files one (gap, total) per tick in LDS)
     return mode() != 0 && chain_enabled() && B >= 1 && B <= kDecodeB1MaxRows && H == DH && V >= 1 && V <= 128 && T % G == 0 && T / G <= 4 &&
            kFusedRoles <= chain_capacity() && make_plan(B, V, false, sample).ok;
 }
 bool decode_b1_fused(int Z, int B, int V, int sample) { return Z == DZ && make_plan(B, V, true, sample).ok; }
 bool decode_b1_ok(const DecodeChainArgs& a) {
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;
-    const int sample = a.uniforms ? (a.trunc ? 2 : 1) : 0;
+    const int sample = a.uniforms ? (a.allow ? 3 : a.trunc ? 2 : 1) : 0;
+    if (a.allow && !a.uniforms) return false;
     return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G, sample) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr, sample).ok;
 }
 
@@ -1306,7 +1373,7 @@ int decode_b1_plan_check(int B, int V, int Z, int* out, int sample) {
 }
 
 int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
-    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms ? (d.trunc ? 2 : 1) : 0);
+    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms ? (d.allow ? 3 : d.trunc ? 2 : 1) : 0);
     if (!pl.ok || pl.rows > decode_b1_rows(d.B)) return -1;   // (decode_b1_ok has accepted the call: not reached)
     B1Args a{};
     a.fused = pl.fused; a.teams = pl.teams; a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place; a.stride = pl.stride;
@@ -1319,11 +1386,11 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     a.stamps = d.b1stamps;
     a.status = d.status;
     a.uniforms = d.uniforms; a.temperature = d.temperature;
-    a.top_k = d.top_k; a.top_p = d.top_p; a.logp = d.logp;
+    a.top_k = d.top_k; a.top_p = d.top_p; a.logp = d.logp; a.allow = d.allow;
     if (!dispatch_b1(pl, nullptr, nullptr)) return -1;        // (a plan without an instantiation launches nothing)
     char label[64];
-    // (a sampled and a truncated call's launch have label prefixes of their own: the profile tells the kinds of call apart)
-    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample == 2 ? "trunc_" : pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
+    // (a sampled, a truncated and a constrained call's launch have label prefixes of their own: the profile tells the kinds of call apart)
+    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample == 3 ? "cons_" : pl.sample == 2 ? "trunc_" : pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
     // algorithmic work: the tick GRU + head per tick and row; fused: + the beat path (z2b, two beat layers, three projections per beat)
     const double nbt = (double)d.T / d.G;
     const double beat_mac = a.fused ? 2.0 * DH * DZ + nbt * (3.0 * 3 * DH * DH + 2.0 * DH * DH + 1.0 * DH * DH + 3.0 * DH * DH) : 0.0;

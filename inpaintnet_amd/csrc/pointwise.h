@@ -28,6 +28,11 @@ int pw_sample_temperature(const float* W, long ld_w, int rows, int V, float temp
 // logp[row*lp_stride] (nullable) = the drawn token's log-probability under the truncated distribution, NaN where the row took argmax_first.
 int pw_sample_truncated(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
                         double top_p, long long* out, long stride, float* logp, long lp_stride, hipStream_t s);
+// The same behind sample.h's token constraints: allow + row*allow_stride = the row's ceil(V / 64) words of allowed tokens (null: the call
+// above).  A row outside the rule takes argmax_first over its allowed tokens.
+int pw_sample_constrained(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
+                          double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
+                          long allow_stride, hipStream_t s);
 // step_flag (optional device float): non-zero = skip (the ranks' summed chain status); report (optional, 4 host-mapped words
 // zeroed by the caller): [0] = 1 executed, [1] = 1 skipped, [2] = 1 a parameter became non-finite
 int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,

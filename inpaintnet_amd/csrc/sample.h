@@ -153,6 +153,57 @@ __device__ __forceinline__ void truncate(float (&s)[NV], float m, int top_k, dou
         if (!((keep[j] >> lane) & 1)) s[j] = -INFINITY;
 }
 
+// PER-TICK TOKEN CONSTRAINTS in front of truncate() / pick() (DESIGN.md section 13 has the same text).
+//
+// Mask layout.  `allow` is an array of 64-bit words [rows][T][NW], with NW = ceil(V / 64).  Token v is allowed iff bit v % 64 of word
+// v / 64 is set.  Bits at or above V are ignored.  A null `allow` means no constraint.
+//
+// For one (row, tick), with logits x[0..V), temperature T, uniform u, top_k and top_p:
+//  0. Empty mask.  A mask with no bit set in [0, V) counts as all ones for that tick.  The Python surfaces refuse such a tick with
+//     ValueError before any launch.
+//  1. Scores.  s_v = T x_v in f32.  The NaN test of section 10 runs over all V values of s, as today.  The mask therefore does not change
+//     which ticks fall back.  Then s_v = -inf for every banned v, and m = the maximum over the allowed tokens.
+//  2. Truncation and draw.  Steps 2-7 of section 11 run unchanged on these s, with V and K = top_k unchanged.  Banned tokens tie at -inf
+//     and rank last.  Their e = expf(-inf - m) is 0, so they add no mass and cannot be the first prefix above u S.  A top_k above the
+//     number of allowed tokens keeps all of them.  logp is taken under the masked and truncated distribution.
+//  3. Fallback.  Where the rule does not apply (a NaN among s, m or S not finite, u outside [0, 1) or NaN), the tick takes today's argmax
+//     rule on the logits with every banned entry replaced by -inf.  The decode kernel may use its padding value -1 instead, which lies
+//     below every post-ReLU logit.  logp is NaN there.  The token is still an allowed one.
+//
+// The mask words of one (row, tick) are wave-uniform (every lane holds all NV of them; scalar registers where the address is uniform).
+// mask_words(): step 0 -- the words with the bits at or above V cleared, or the words of the full vocabulary where none is left.
+template <int NV>
+__device__ __forceinline__ void mask_words(unsigned long long (&aw)[NV], int V) {
+    unsigned long long any = 0ull;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int n = V - 64 * j;                                           // tokens of this word
+        const unsigned long long valid = n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1ull;
+        aw[j] &= valid;
+        any |= aw[j];
+    }
+    if (!any) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int n = V - 64 * j;
+            aw[j] = n >= 64 ? ~0ull : n <= 0 ? 0ull : (1ull << n) - 1ull;
+        }
+    }
+}
+__device__ __forceinline__ bool allowed(unsigned long long word, int lane) { return (word >> lane) & 1ull; }
+// mask_scores(): step 1 behind the NaN test -- s = -inf for the banned lanes (aw from mask_words()); returns THIS LANE's maximum over
+// its allowed tokens (-inf without one): the caller reduces it over the wave with the reduction it has, and that is m.
+template <int NV>
+__device__ __forceinline__ float mask_scores(float (&s)[NV], const unsigned long long (&aw)[NV], int lane) {
+    float ms = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        if (!allowed(aw[j], lane)) s[j] = -INFINITY;
+        ms = fmaxf(ms, s[j]);
+    }
+    return ms;
+}
+
 // The log-probability of the drawn token under the (truncated) distribution pick() drew from is (s_tok - m) - log(S), stored as f32, in
 // two halves: logp_gap() = s_tok - m (f32; tok in [0, V) from pick(); wave-uniform) where the draw is made, logp_of() where there are
 // registers for an f64 logarithm -- decode_b1.hip's pick has none to spare and takes the logarithms behind its last tick.

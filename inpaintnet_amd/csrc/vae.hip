@@ -284,7 +284,7 @@ size_t vae_decoder_ws_bytes(const inet_vae_config& c, int B, int save) {
 int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long long* target, int teacher_forced,
                     const float* p, const float* mask_beat, const float* mask_tick, float* weights,
                     long long* samples, void* ws, int save, hipStream_t s, uint64_t multinomial_seed, const double* uniforms,
-                    float temperature, int top_k, double top_p, float* logp) {
+                    float temperature, int top_k, double top_p, float* logp, const unsigned long long* allow) {
     const int nb = c.beats, G = c.ticks_per_beat, T = nb * G, H = c.dec_hidden, V = c.num_notes, E = c.emb_dim, Z = c.z_dim;
     const long BH = (long)B * H;
     if (nb > 4) return -1;
@@ -292,8 +292,10 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     const bool sampled = uniforms != nullptr;                  // temperature sampling (sample.h): a free-running inference call
     if (sampled && (teacher_forced || multinomial_seed || V > 512)) return -1;
     // top-k / nucleus truncation in front of every draw, or the draws' log-probabilities wanted: the truncating kernels
-    const bool trunc = sampled && ((top_k >= 1 && top_k < V) || top_p < 1.0 || logp);
-    if (!sampled && (logp || top_k > 0 || top_p < 1.0)) return -1;
+    // ... a mask of allowed tokens: the masked kernels, which are truncating ones
+    const bool cons = sampled && allow;
+    const bool trunc = sampled && ((top_k >= 1 && top_k < V) || top_p < 1.0 || logp || cons);
+    if (!sampled && (logp || top_k > 0 || top_p < 1.0 || allow)) return -1;
     if (!(top_p > 0.0 && top_p <= 1.0)) return -1;
     VaeLayout L(c);
     DecWs w{};
@@ -310,8 +312,8 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     const bool chain_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
     // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
     const bool b1_decode = chain_whole && !save && !mask_tick && w.b1ex && w.b1ex + decode_b1_words(B) == w.sync &&
-                           decode_b1_shape_ok(B, H, V, T, G, sampled + trunc);
-    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, sampled + trunc);   // ... with the beat path inside the same launch
+                           decode_b1_shape_ok(B, H, V, T, G, sampled + trunc + cons);
+    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, sampled + trunc + cons);   // ... with the beat path inside the same launch
     // (a sampled call: the one fused launch that knows the rule is decode_b1.hip's; every other shape samples tick by tick below)
     const bool fused_whole = chain_whole && (!sampled || b1_decode);
     const bool fused_chunked = fused_shape && !sampled && !fused_whole && B > kDecodeChunk && B % kDecodeChunk == 0 &&
@@ -525,7 +527,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
             a.weights = weights + (long)r0 * T * V; a.samples = samples + (long)r0 * T;
             a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0;   // (later chunks: the launcher zeroes the area)
             a.uniforms = uniforms; a.temperature = temperature;                 // (sampled: one whole launch, never chunks)
-            a.trunc = trunc; a.top_k = top_k; a.top_p = top_p; a.logp = logp;
+            a.trunc = trunc; a.top_k = top_k; a.top_p = top_p; a.logp = logp; a.allow = cons ? allow : nullptr;
             if (mask_tick) { a.mask = mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
             if (save) {
                 a.sv0 = w.svt0 + (long)r0 * H; a.sv1 = w.svt1 + (long)r0 * H; a.sv_stride = (long)T * BH;
@@ -583,6 +585,9 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
                                 (long)T * V, B, V, H, EPI_RELU, s));
             if (draw) INET_TRY(pw_sample_multinomial(weights + (long)t * V, (long)T * V, B, V, samples + t, T,
                                                      multinomial_seed, (uint64_t)t * B, s));
+            else if (cons) INET_TRY(pw_sample_constrained(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
+                                                         samples + t, T, logp ? logp + t : nullptr, T, allow + (long)t * ((V + 63) / 64),
+                                                         (long)T * ((V + 63) / 64), s));
             else if (trunc) INET_TRY(pw_sample_truncated(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
                                                         samples + t, T, logp ? logp + t : nullptr, T, s));
             else if (sampled) INET_TRY(pw_sample_temperature(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T,

@@ -199,13 +199,14 @@ class LatentRNN(Model):
         return torch.zeros(self.num_rnn_layers * self.rnn_num_direction, batch_size, self.rnn_hidden_size,
                            device=self.flat.device)
 
-    def _decode(self, z2d, temperature=None, uniforms=None, top_k=None, top_p=None):
+    def _decode(self, z2d, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
         """frozen decoder, train=False (latent_rnn.py:238): dropout still follows module.training (the quirk)."""
         dummy = torch.zeros(z2d.shape[0], self.vae_model.num_ticks_per_measure, device=z2d.device)
-        return self.vae_model.decoder(z2d, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p)
+        return self.vae_model.decoder(z2d, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
+                                      allowed=allowed)
 
     def forward(self, past_context, future_context, target, measures_to_generate, train=True, eps=None,
-                teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None):
+                teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
         """-> weights (B,nt,24,V), samples (B,1,24*nt), gen_z (B,nt,Z)   (latent_rnn.py:110-159).
         eps: optional (eps_past (B,np,Z), eps_future, eps_target) injection; eps_ar: list of (B,Z) for the
         free-running auto-regressive path.
@@ -215,8 +216,19 @@ class LatentRNN(Model):
         np.random.random_sample call).
         top_k / top_p (with a temperature only: ValueError without): every draw behind top-k / nucleus truncation
         (HierarchicalDecoder.forward); such a call leaves self.last_logp (B, n_target, 24), the drawn tokens' log-probabilities under
-        the truncated distribution (NaN where a tick took the argmax), every other call leaves it None."""
+        the truncated distribution (NaN where a tick took the argmax), every other call leaves it None.
+        allowed (bool (B, n_target, 24, V); inference only): the tokens each generated tick may return (HierarchicalDecoder.forward),
+        with or without a temperature; the auto-regressive path hands each measure's slice to its decoder call."""
         batch_size, _, measure_seq_len = past_context.size()
+        if allowed is not None:
+            if train:
+                raise ValueError("token constraints are an inference call (train=False)")
+            allowed = torch.as_tensor(allowed)
+            if allowed.dtype != torch.bool or allowed.dim() != 4 or tuple(allowed.shape[:3]) != (batch_size, measures_to_generate, measure_seq_len):
+                raise ValueError(f"allowed must be bool of shape {(batch_size, measures_to_generate, measure_seq_len)} + (V,), got "
+                                 f"{allowed.dtype} {tuple(allowed.shape)}")
+            if not bool(allowed.any(-1).all()):
+                raise ValueError("allowed: a tick with nothing allowed")
         if temperature is None and (top_k is not None or top_p is not None):
             raise ValueError("top_k / top_p without a temperature")
         if top_p is not None and not (0.0 < float(top_p) <= 1.0):
@@ -273,11 +285,13 @@ class LatentRNN(Model):
         else:
             seed = zp[:, -1, :].unsqueeze(1)
         return self.forward_generation(comb_context, measures_to_generate, seed, measure_seq_len, teacher_forcing,
-                                       eps_ar=eps_ar, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p)
+                                       eps_ar=eps_ar, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
+                                       allowed=allowed)
 
     def forward_generation(self, context_vector, measures_to_gen, seed, measure_seq_len, teacher_forcing=False,
-                           eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None):
-        """latent_rnn.py:211-263; temperature / uniforms (B, measures_to_gen, 24) / top_k / top_p / self.last_logp: see forward"""
+                           eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
+        """latent_rnn.py:211-263; temperature / uniforms (B, measures_to_gen, 24) / top_k / top_p / self.last_logp / allowed (B,
+        measures_to_gen, 24, V): see forward"""
         if temperature is None and (top_k is not None or top_p is not None):
             raise ValueError("top_k / top_p without a temperature")
         batch_size = context_vector.size(1)
@@ -294,7 +308,8 @@ class LatentRNN(Model):
             z_out = z2d.view(batch_size, measures_to_gen, -1)
             # rows ordered (b, measure): all measures in one call
             w, s = self._decode(z2d, temperature, uniforms.reshape(batch_size * measures_to_gen, -1) if uniforms is not None else None,
-                                top_k, top_p)
+                                top_k, top_p, allowed.reshape((batch_size * measures_to_gen,) + tuple(allowed.shape[2:]))
+                                if allowed is not None else None)
             lp = self.vae_model.decoder.last_logp
             self.last_logp = lp.view(batch_size, measures_to_gen, measure_seq_len) if lp is not None else None
             weights = w.view(batch_size, measures_to_gen, measure_seq_len, -1)
@@ -308,7 +323,8 @@ class LatentRNN(Model):
             gen_z = _LinearFn.apply(rnn_out.reshape(batch_size, -1), self.flat_for_autograd(), self,
                                     "generation_linear.weight", "generation_linear.bias")
             z_out.append(gen_z.view(batch_size, 1, -1))
-            w, s = self._decode(gen_z, temperature, uniforms[:, i] if uniforms is not None else None, top_k, top_p)
+            w, s = self._decode(gen_z, temperature, uniforms[:, i] if uniforms is not None else None, top_k, top_p,
+                                allowed[:, i] if allowed is not None else None)
             logps.append(self.vae_model.decoder.last_logp)
             samples.append(s)
             weights.append(w.unsqueeze(1))

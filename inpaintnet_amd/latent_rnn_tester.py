@@ -35,7 +35,7 @@ class LatentRNNTester(object):
         return fn(tensor.cpu()) if fn is not None else None
 
     def generate(self, tensor_past, tensor_future, tensor_target, num_target_measures, eval=False, temperature=None,
-                 num_variations=1, top_k=None, top_p=None):
+                 num_variations=1, top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None):
         """-> (gen_score | None, gen_score_tensor (B, n_past + n_target + n_future, 24), original_score | None)
         (latent_rnn_tester.py:197-266)
         temperature (a finite float): `num_variations` fillings of the same gap -- the (one-row) contexts are expanded to that many
@@ -47,7 +47,13 @@ class LatentRNNTester(object):
         truncation (HierarchicalDecoder.forward) -- the remedy for the mass the many zero logits of a post-ReLU head carry.  Such a call
         leaves self.last_logp (num_variations, n_target): per generated measure the sum of its 24 drawn tokens' log-probabilities
         under the truncated distribution, NaN where a tick fell back to the argmax -- the score to rank the variations by (top_p=1.0
-        scores them without truncating); every other call leaves it None.  The return tuple is the same."""
+        scores them without truncating); every other call leaves it None.  The return tuple is the same.
+        banned_tokens (a list of token indices): never returned at any generated tick -- START, END or a padding symbol in the middle
+        of a piece.  fixed_tokens (an int tensor (n_target, 24), -1 = a free tick): the notes to keep; applied to every variation, and a
+        fixed tick wins over a ban.  Both are applied inside the decode launch (HierarchicalDecoder.forward's `allowed`), so the notes
+        behind a constrained tick are generated from it.  ValueError for an index outside [0, V) (fixed: other than -1) or a ban of
+        the whole vocabulary.  With a temperature last_logp is as above (a fixed tick adds exactly 0); without one the single filling
+        is the argmax over the allowed tokens and last_logp stays None."""
         if temperature is None and (top_k is not None or top_p is not None):
             raise ValueError("top_k / top_p need a temperature")
         if top_p is not None and not (0.0 < float(top_p) <= 1.0):
@@ -59,6 +65,7 @@ class LatentRNNTester(object):
             num_target_measures = tensor_target.size(1)
         elif num_target_measures is None:
             raise ValueError
+        allowed = self._allowed(banned_tokens, fixed_tokens, num_target_measures)      # (the argument errors, before any work)
         if tensor_past is None:
             tensor_past = self.create_empty_context('start')
         if tensor_future is None:
@@ -75,10 +82,12 @@ class LatentRNNTester(object):
             tensor_future = tensor_future.expand(num_variations, -1, -1).contiguous()
             if tensor_target is not None:
                 tensor_target = tensor_target.expand(num_variations, -1, -1).contiguous()
+        if allowed is not None:                                     # every row -- every variation -- under the same constraints
+            allowed = allowed.unsqueeze(0).expand(tensor_past.size(0), -1, -1, -1).contiguous()
         with torch.no_grad():
             weights, gen_target, _ = self.model(past_context=tensor_past, future_context=tensor_future, target=None,
                                                 measures_to_generate=num_target_measures, train=False, temperature=temperature,
-                                                top_k=top_k, top_p=top_p)
+                                                top_k=top_k, top_p=top_p, **({} if allowed is None else {"allowed": allowed}))
         self.last_weights = weights
         lp = getattr(self.model, "last_logp", None)
         self.last_logp = lp.sum(-1) if lp is not None else None
@@ -96,6 +105,32 @@ class LatentRNNTester(object):
         if tensor_target is not None:
             original = self._to_score(torch.cat((tensor_past, tensor_target, tensor_future), 1))
         return self._to_score(gen_score_tensor), gen_score_tensor, original
+
+    def _allowed(self, banned_tokens, fixed_tokens, n_target):
+        """generate()'s constraints as one row of the model's mask: bool (n_target, 24, V) on the host, or None without constraints"""
+        if banned_tokens is None and fixed_tokens is None:
+            return None
+        V, L = int(self.model.vae_model.decoder.cfg.num_notes), self.measure_seq_len
+        allow = torch.ones(n_target, L, V, dtype=torch.bool)
+        if banned_tokens is not None:
+            banned = [int(b) for b in banned_tokens]
+            if any(b != b0 for b, b0 in zip(banned, banned_tokens)) or any(not 0 <= b < V for b in banned):
+                raise ValueError(f"banned_tokens {list(banned_tokens)!r}: token indices in [0, {V})")
+            allow[:, :, banned] = False
+            if banned and not bool(allow.any(-1).all()):
+                raise ValueError("banned_tokens bans the whole vocabulary")
+        if fixed_tokens is not None:
+            fixed = torch.as_tensor(fixed_tokens).cpu()
+            if fixed.is_floating_point() or fixed.dtype == torch.bool or tuple(fixed.shape) != (n_target, L):
+                raise ValueError(f"fixed_tokens must be an int tensor of shape {(n_target, L)}, got {fixed.dtype} {tuple(fixed.shape)}")
+            fixed = fixed.long()
+            if bool(((fixed < -1) | (fixed >= V)).any()):
+                raise ValueError(f"fixed_tokens: token indices in [0, {V}), or -1 for a free tick")
+            keep = fixed >= 0
+            one = torch.zeros(n_target, L, V, dtype=torch.bool)
+            one.scatter_(2, fixed.clamp(min=0).unsqueeze(-1), True)
+            allow = torch.where(keep.unsqueeze(-1), one, allow)
+        return allow
 
     def create_empty_context(self, type):
         """(1, num_measures, 24) of one symbol: 3 START measures, 1 END measure or 1 rest measure (:268-296)."""

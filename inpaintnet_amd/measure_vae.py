@@ -68,11 +68,12 @@ class _EncoderFn(ops.TrackedFunction):
 class _DecoderFn(ops.TrackedFunction):
     @staticmethod
     def forward(ctx, z, flat, dec, target, teacher_forced, mask_beat, mask_tick, multinomial_seed=0, temperature=None,
-                uniforms=None, top_k=None, top_p=None, logp=None):
+                uniforms=None, top_k=None, top_p=None, logp=None, allowed=None):
         need = ops.outer_grad() and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         weights, samples, ws = ops.decoder_fwd(dec.cfg, z.contiguous(), target, teacher_forced, flat, mask_beat,
                                                mask_tick, save=need, multinomial_seed=multinomial_seed,
-                                               temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, logp=logp)
+                                               temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, logp=logp,
+                                               allowed=allowed)
         ctx.dec, ctx.ws, ctx.mb, ctx.mt = dec, ws, mask_beat, mask_tick
         if getattr(dec, "keep_ws", False):         # test hook: lets a parity test read intermediates (ops.ws_field)
             dec.last_ws = ws
@@ -88,7 +89,7 @@ class _DecoderFn(ops.TrackedFunction):
         dec = ctx.dec
         if dweights is None:                            # nothing downstream depends on the weights
             ctx.ws = None
-            return (None,) * 13
+            return (None,) * 14
         weights, samples = ctx.saved_tensors
         grads = dec.owner.grad if dec.owner.trainable else None
         dz = ops.decoder_bwd(dec.cfg, dweights.contiguous(), weights, samples, dec.owner.flat, grads, ctx.mb, ctx.mt,
@@ -99,7 +100,7 @@ class _DecoderFn(ops.TrackedFunction):
             if dp.world_size() > 1:
                 # behind the decoder's leaf GEMMs on the side streams, without holding up the encoder's backward
                 dp.start_bucket(grads, dec.owner.decoder_arena_start, grads.numel(), join_side=True)
-        return (dz,) + (None,) * 12
+        return (dz,) + (None,) * 13
 
 
 class _ReparamFn(torch.autograd.Function):
@@ -259,7 +260,7 @@ class HierarchicalDecoder(torch.nn.Module):
                f')'
 
     def forward(self, z, score_tensor, train, masks=None, teacher_forced=None, temperature=None, uniforms=None, top_k=None,
-                top_p=None):
+                top_p=None, allowed=None):
         """z (B,Z), score_tensor (B,24) -> weights (B,24,V), samples (B,1,24)   (decoder.py:412-453).
         One Bernoulli(0.5) teacher-forcing coin per call when train=True (decoder.py:431-434); it can be
         injected with `teacher_forced=`.
@@ -272,8 +273,21 @@ class HierarchicalDecoder(torch.nn.Module):
         every draw is taken from the top_k highest-ranked tokens, and among those from the shortest prefix of the ranking that
         holds top_p of their mass (csrc/sample.h: ranked by temperature * weight descending, lowest index first among equals).  Such a
         call leaves self.last_logp (B,24): the drawn tokens' log-probabilities under the truncated distribution, NaN where a tick
-        took the argmax; every other call leaves it None."""
+        took the argmax; every other call leaves it None.
+        allowed (bool (B,24,V), host or device; inference only, ignored by a call whose `teacher_forced=True` was injected): the tokens
+        each (row, tick) may return -- a ban clears entries, a note to keep is a tick with one entry set.  The mask is applied inside
+        the launch, in front of the truncation (csrc/sample.h): the token fed back into tick t + 1 is the
+        constrained one, a fixed tick's logp is exactly 0.  ValueError for a tick with nothing allowed.  Without a temperature the call
+        runs as temperature 1, top_k = 1 with zero uniforms -- the argmax over the allowed tokens -- and leaves last_logp None."""
         T = self.cfg.beats * self.cfg.ticks_per_beat
+        if allowed is not None:
+            if train:
+                raise ValueError("token constraints are an inference call (train=False)")
+            allowed = torch.as_tensor(allowed)
+            if allowed.dtype != torch.bool or tuple(allowed.shape) != (z.size(0), T, self.cfg.num_notes):
+                raise ValueError(f"allowed must be bool of shape {(z.size(0), T, self.cfg.num_notes)}, got {allowed.dtype} "
+                                 f"{tuple(allowed.shape)}")
+            allowed = ops.pack_allowed(allowed)                    # (ValueError for a tick with nothing allowed)
         if temperature is None and (top_k is not None or top_p is not None):
             raise ValueError("top_k / top_p without a temperature")
         if top_p is not None and not (0.0 < float(top_p) <= 1.0):
@@ -318,14 +332,20 @@ class HierarchicalDecoder(torch.nn.Module):
                                   _next_mask_offset(self.cfg.beats * batch_size * H), dev)
             mt = ops.dropout_mask((T, batch_size, H), self.dropout, _DropState.seed,
                                   _next_mask_offset(T * batch_size * H), dev)
+        if allowed is not None and temperature is None and not teacher_forced:
+            # constraints without a temperature: top_k = 1 keeps the top-ranked allowed token whatever the uniform (DESIGN.md section 11's
+            # top_k = 1 equality, over the allowed tokens)
+            u = torch.zeros(batch_size, T, dtype=torch.float64, device=z.device)
+            return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, 1.0, u, 1, None, None,
+                                   allowed.to(z.device).contiguous())
         if temperature is not None and not teacher_forced:
             if uniforms is None:
                 uniforms = torch.from_numpy(np.random.random_sample((batch_size, T)))
             u = uniforms.to(z.device).contiguous()
-            if top_k is not None or top_p is not None:
+            if top_k is not None or top_p is not None or allowed is not None:
                 logp = torch.empty(batch_size, T, dtype=torch.float32, device=z.device)
                 out = _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u,
-                                      top_k, top_p, logp)
+                                      top_k, top_p, logp, allowed.to(z.device).contiguous() if allowed is not None else None)
                 self.last_logp = logp
                 return out
             return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u)
@@ -432,12 +452,13 @@ class MeasureVAE(Model):
                                         teacher_forced=teacher_forced, masks=dec_masks)
         return weights, samples, z_dist, prior_dist, z_tilde, z_prior
 
-    def decode(self, z, temperature=None, uniforms=None, top_k=None, top_p=None):
+    def decode(self, z, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
         """z (B,Z) -> (weights (B,24,V), samples (B,1,24)): the free-running decoder alone (what VAETester.decode_mid_point does with
         a latent), by the argmax or -- temperature set -- drawn from softmax(temperature * weights), behind top-k / nucleus truncation
-        with top_k / top_p (HierarchicalDecoder.forward; the draws' log-probabilities: self.decoder.last_logp)."""
+        with top_k / top_p (HierarchicalDecoder.forward; the draws' log-probabilities: self.decoder.last_logp); allowed (bool
+        (B,24,V)): the tokens each tick may return, with or without a temperature (HierarchicalDecoder.forward)."""
         dummy = torch.zeros(z.shape[0], self.num_ticks_per_measure, device=z.device)
-        return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p)
+        return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, allowed=allowed)
 
     def _standard_normal(self, like):
         """N(0, 1) of the latent's shape (measure_vae.py:122-125): the constant loc / scale tensors are built once."""

@@ -248,17 +248,19 @@ def decoder_ws(cfg, B, save, device):
 
 
 def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tick=None, save=False, ws=None,
-                multinomial_seed=0, temperature=None, uniforms=None, top_k=None, top_p=None, logp=None):
+                multinomial_seed=0, temperature=None, uniforms=None, top_k=None, top_p=None, logp=None, allowed=None):
     """z [B,Z] -> weights [B,T,V], samples [B,1,T] int64, ws.  multinomial_seed != 0: the fed-back tokens are drawn from
     softmax(weights) (decoder.py:506-509) instead of the argmax.  temperature + uniforms ([B,T] float64 on the device, one uniform
     per row and tick): inet_vae_decoder_sample -- a free-running call whose tokens are drawn from softmax(temperature * weights) by
     csrc/sample.h's rule.  top_k / top_p / logp (with a temperature only): inet_vae_decoder_sample_ex -- the draw behind sample.h's
     top-k / nucleus truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off, else in (0, 1)), and logp, a contiguous float32
-    [B,T] device tensor, receives the drawn tokens' log-probabilities under the truncated distribution (NaN where a tick took the argmax)."""
+    [B,T] device tensor, receives the drawn tokens' log-probabilities under the truncated distribution (NaN where a tick took the argmax).
+    allowed (with a temperature only): inet_vae_decoder_sample_cx -- pack_allowed()'s words [B,T,ceil(V/64)], int64, contiguous, on the
+    device: the tokens every (row, tick) may return, applied in front of the truncation inside the launch (csrc/sample.h's rule)."""
     if (temperature is None) != (uniforms is None):
         raise ValueError("decoder_fwd: temperature and uniforms go together")
-    if temperature is None and (top_k is not None or top_p is not None or logp is not None):
-        raise ValueError("decoder_fwd: top_k / top_p / logp without a temperature")
+    if temperature is None and (top_k is not None or top_p is not None or logp is not None or allowed is not None):
+        raise ValueError("decoder_fwd: top_k / top_p / logp / allowed without a temperature")
     if top_p is not None and not (0.0 < float(top_p) <= 1.0):
         raise ValueError(f"decoder_fwd: top_p {top_p!r} outside (0, 1]")
     _f32c(z); _f32c(params)
@@ -273,12 +275,24 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
             raise ValueError(f"decoder_fwd: uniforms must be a contiguous float64 device tensor of shape {(B, T)}")
         if logp is not None and not (logp.is_cuda and logp.dtype == torch.float32 and logp.is_contiguous() and tuple(logp.shape) == (B, T)):
             raise ValueError(f"decoder_fwd: logp must be a contiguous float32 device tensor of shape {(B, T)}")
+        if allowed is not None:
+            nw = (cfg.num_notes + 63) // 64
+            if not (allowed.is_cuda and allowed.dtype == torch.int64 and allowed.is_contiguous() and tuple(allowed.shape) == (B, T, nw)):
+                raise ValueError(f"decoder_fwd: allowed must be pack_allowed()'s contiguous int64 device tensor of shape {(B, T, nw)}")
     if target is not None:
         _i64c(target)
     if ws is None:
         ws = decoder_ws(cfg, B, save, z.device)
     weights = torch.empty(B, T, cfg.num_notes, dtype=torch.float32, device=z.device)
     samples = torch.empty(B, 1, T, dtype=torch.int64, device=z.device)
+    if temperature is not None and allowed is not None:
+        check(_lib.lib().inet_vae_decoder_sample_cx(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
+                                                    ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
+                                                    _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(logp), ptr(allowed),
+                                                    stream_ptr()),
+              "inet_vae_decoder_sample_cx")
+        _hold(uniforms, logp, allowed)
+        return weights, samples, ws
     if temperature is not None and (top_k is not None or top_p is not None or logp is not None):
         check(_lib.lib().inet_vae_decoder_sample_ex(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
                                                     ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
@@ -366,15 +380,44 @@ def _top_k(top_k):
     return max(0, min(int(top_k), 2 ** 31 - 1))
 
 
-def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, want_logp=True):
+def pack_allowed(allowed):
+    """bool [..., V] (a tensor or an array: token v may be returned) -> int64 [..., ceil(V / 64)] with the bit patterns of csrc/sample.h's
+    mask words: token v is bit v % 64 of word v // 64, the bits at or above V are zero.  Packed on the host; the result lies on the
+    input's device (the CPU for an array).  ValueError for a (row, tick) with nothing allowed, or for what is no boolean mask."""
+    import numpy as np
+    dev = allowed.device if isinstance(allowed, torch.Tensor) else torch.device("cpu")
+    a = allowed.detach().cpu().numpy() if isinstance(allowed, torch.Tensor) else np.asarray(allowed)
+    if a.dtype != np.bool_ or a.ndim < 1 or a.shape[-1] < 1:
+        raise ValueError("pack_allowed: a boolean mask [..., V] with V >= 1")
+    if not a.any(-1).all():
+        where = np.argwhere(~a.any(-1))[0].tolist()
+        raise ValueError(f"pack_allowed: nothing is allowed at {where}")
+    V = a.shape[-1]
+    nw = (V + 63) // 64
+    bits = np.zeros(a.shape[:-1] + (nw * 64,), dtype=np.uint8)
+    bits[..., :V] = a
+    words = np.packbits(bits.reshape(a.shape[:-1] + (nw, 64)), axis=-1, bitorder="little")     # 8 bytes per word, the lowest first
+    words = np.ascontiguousarray(words).view("<u8").reshape(a.shape[:-1] + (nw,)).astype(np.int64)
+    return torch.from_numpy(words).to(dev)
+
+
+def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, want_logp=True, allowed=None):
     """inet_sample_truncated: sample_temperature() behind csrc/sample.h's top-k / nucleus truncation (top_k None, <= 0 or >= V: off;
     top_p None or 1: off, else in (0, 1)) -> (tokens [rows] int64, logp [rows] float32: the drawn tokens' log-probabilities under
-    the truncated distribution, NaN where a row took the argmax rule; None with want_logp=False)."""
+    the truncated distribution, NaN where a row took the argmax rule; None with want_logp=False).  allowed: inet_sample_constrained --
+    pack_allowed()'s words [rows, ceil(V / 64)] (int64 on the device, any row stride): the tokens each row may return."""
     rows, V = weights2d.shape
     assert weights2d.stride(1) == 1 and weights2d.dtype == torch.float32
     assert uniforms.is_cuda and uniforms.dtype == torch.float64 and tuple(uniforms.shape) == (rows,)
     out = torch.empty(rows, dtype=torch.int64, device=weights2d.device)
     logp = torch.empty(rows, dtype=torch.float32, device=weights2d.device) if want_logp else None
+    if allowed is not None:
+        if not (allowed.is_cuda and allowed.dtype == torch.int64 and tuple(allowed.shape) == (rows, (V + 63) // 64) and allowed.stride(1) == 1):
+            raise ValueError(f"sample_truncated: allowed must be pack_allowed()'s int64 device tensor of shape {(rows, (V + 63) // 64)}")
+        check(_lib.lib().inet_sample_constrained(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
+                                                 uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
+                                                 ptr(logp), 1, ptr(allowed), allowed.stride(0), stream_ptr()), "inet_sample_constrained")
+        return out, logp
     check(_lib.lib().inet_sample_truncated(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
                                            uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
                                            ptr(logp), 1, stream_ptr()), "inet_sample_truncated")

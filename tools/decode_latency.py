@@ -2,7 +2,10 @@
 --temperature T: only the sampled decode (temperature T, uniforms on the device) beside the argmax decode of the same build, b = 1, 4
 and 16, five rounds of 300 calls each (median and range per call).
 --top-k K / --top-p P (with --temperature): a third column, the truncated decode (top-k / nucleus truncation in front of every draw, and
-the draws' log-probabilities), and its cost per tick over the sampled decode."""
+the draws' log-probabilities), and its cost per tick over the sampled decode.
+--mask (with --temperature and --top-k / --top-p): a second line per batch size, the constrained decode under the every-plan mask of
+tests/decoder_constraint_ref.py (every fourth tick fixed, a fifth of the tokens banned elsewhere) next to the truncated decode of the
+same build, both at the ops level with the mask words packed once."""
 import os, sys
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -43,6 +46,17 @@ if "--temperature" in sys.argv:
             trunc, text = rounds(lambda: vae.decoder(z, dummy, train=False, temperature=temperature, uniforms=u, top_k=top_k, top_p=top_p))
             line += f", top_k {top_k} top_p {top_p} {text} (+{1e3 * (trunc - sampled) / 24:.2f} us per tick)"
         print(line + f", chain status {ops.chain_status()}")
+        if "--mask" in sys.argv and (top_k is not None or top_p is not None):
+            V = vae.num_notes
+            r, t, v = torch.meshgrid(torch.arange(b), torch.arange(24), torch.arange(V), indexing="ij")
+            allow = torch.where((r + t) % 4 == 0, v == (7 * r + 3 * t + 1) % V, (v + t + r) % 5 != 0)
+            words = ops.pack_allowed(allow).cuda()
+            lp = torch.empty(b, 24, dtype=torch.float32, device="cuda")
+            kw = dict(temperature=temperature, uniforms=u, top_k=top_k, top_p=top_p, logp=lp)
+            trunc, text = rounds(lambda: ops.decoder_fwd(vae.cfg, z, None, False, vae.flat, **kw))
+            cons, ctext = rounds(lambda: ops.decoder_fwd(vae.cfg, z, None, False, vae.flat, allowed=words, **kw))
+            print(f"b = {b}: ops level, truncated {text}, constrained {ctext} ({1e3 * (cons - trunc) / 24:+.2f} us per tick), "
+                  f"chain status {ops.chain_status()}")
     sys.exit(0)
 r = bench.decode_latency_extra(wl.model, iters=200)["decoder_eval"]
 print({k: v["ms_per_call"] for k, v in r.items() if isinstance(v, dict)})
