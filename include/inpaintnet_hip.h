@@ -404,6 +404,22 @@ int inet_arnn_sample_ex(int R, int L, int E, int Hc, int H, int U, int V, const 
                         const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
                         int64_t* tokens, float* ws, int64_t ws_floats, int top_k, double top_p, float* logp, float* logits,
                         void* stream);
+/* The same behind PER-TICK TOKEN CONSTRAINTS: a mask of allowed tokens per (row, tick), applied in front of the truncated rule inside the
+ * launch (the token of tick t is fed back into tick t + 1 there).  The rule is the one stated for inet_vae_decoder_sample_cx (DESIGN.md
+ * section 13: steps 0 to 3, the mask layout [rows][L][NW] with NW = ceil(V / 64), and its consequences), applied to s = temperature *
+ * logits of the note head.  The note head is not ReLU'd: a fallback tick replaces the banned logits by -inf (there is no padding value
+ * below every logit), and takes its NaN ballots and its maximum over the ALLOWED entries alone -- a NaN at a banned place does not win
+ * (inet_sample_constrained's reading of "still an allowed one").  logits receives the unmasked note-head output.
+ * allow: [R][L][NW] words on the device, or null -- then this IS inet_arnn_sample_ex.  A constrained call is a truncating call: it runs
+ * the masked build of the persistent token pass (V <= 64) or, for the other shapes, the masked head of the per-tick launches, and never a
+ * kernel that ignores the mask: its launch labels start with "cons_" (cons_arnn_token_sample R.. L.. V.., cons_arnn_ticks L.. V..).
+ * -1 where inet_arnn_sample_ex returns it. */
+int inet_arnn_sample_cx(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
+                        int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,
+                        const float* W_ih1, const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
+                        const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
+                        int64_t* tokens, float* ws, int64_t ws_floats, int top_k, double top_p, float* logp, float* logits,
+                        const uint64_t* allow, void* stream);
 /* nn.Embedding forward / backward (rows of E floats gathered by int64 index; backward accumulates with atomics).
  * row_scale (nullable, [rows]) multiplies each gathered row: the Dropout2d on the shifted note embeddings
  * (drop_input, anticipation_rnn_gauss_reg_model.py:437-442) and the all-zero first time step (:373-376). */

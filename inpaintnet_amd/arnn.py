@@ -397,7 +397,8 @@ class ConstraintModelGaussianReg(Model):
         return [torch.stack(ws, 1)], gen
 
     @torch.no_grad()
-    def generate(self, tensor_score, tensor_metadata, constraints_location, temperature=1., top_k=None, top_p=None, keep_weights=False):
+    def generate(self, tensor_score, tensor_metadata, constraints_location, temperature=1., top_k=None, top_p=None, keep_weights=False,
+                 allowed=None):
         """Temperature-sampled generation (anticipation_rnn_gauss_reg_model.py:570-679).  Shapes (1, L), (1, L, M), (1, L) as the
         reference takes them, or a batch (B, 1, L), (B, 1, L, M), (B, 1, L) of independent rows.  Leaves the model in eval().
 
@@ -414,10 +415,23 @@ class ConstraintModelGaussianReg(Model):
         <= 0 or >= V: off; top_p in (0, 1], None or 1: off).  With one of them given the call leaves self.last_logp, float32 of
         gen_chorale's shape: every drawn token's log-probability under the distribution it was drawn from, NaN where a tick took the
         argmax rule (top_p=1.0 scores without truncating); else None.  keep_weights: self.last_weights (B, L, V) = the note head's
-        logits of every tick; else None.  A call without the three runs the kernels it always ran."""
+        logits of every tick; else None.  A call without the three runs the kernels it always ran.
+
+        allowed (bool (L, V) for the one row, (B, L, V) for a batch; host or device): the tokens each tick may return, applied inside
+        the launch in front of the truncation (ops.arnn_sample's `allowed`) -- a tick with one token allowed
+        feeds THAT token back, so what follows is generated from it.  ValueError for a tick with nothing allowed.  It does not change
+        when last_logp is left: with top_k or top_p given, and then a one-token tick scores exactly 0.  None: the call as it was."""
         k = ops._top_k(top_k)
         if top_p is not None and not (0.0 < float(top_p) <= 1.0):
             raise ValueError(f"generate: top_p {top_p!r} outside (0, 1]")
+        if allowed is not None:
+            allowed = torch.as_tensor(allowed)
+            want = tuple(tensor_score.shape[:1] + tensor_score.shape[2:] if tensor_score.dim() == 3 else tensor_score.shape[1:])
+            if allowed.dtype != torch.bool or allowed.dim() != len(want) + 1 or tuple(allowed.shape[:-1]) != want or \
+                    allowed.size(-1) != self.num_notes_per_voice[0]:
+                raise ValueError(f"generate: allowed must be bool of shape {want + (self.num_notes_per_voice[0],)}, got {allowed.dtype} "
+                                 f"{tuple(allowed.shape)}")
+            allowed = ops.pack_allowed(allowed)                    # (ValueError for a tick with nothing allowed)
         self.last_logp = self.last_weights = None
         self.eval()
         batched = tensor_score.dim() == 3
@@ -450,9 +464,10 @@ class ConstraintModelGaussianReg(Model):
         emb, *net = self._generation_weights()
         score_it = top_k is not None or top_p is not None
         logp = weights = None
-        if score_it or keep_weights:
+        if score_it or keep_weights or allowed is not None:
             toks, logp, weights = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc, top_k=k, top_p=top_p,
-                                                  want_logp=score_it, want_logits=bool(keep_weights))
+                                                  want_logp=score_it, want_logits=bool(keep_weights),
+                                                  **({} if allowed is None else {"allowed": allowed.view(B, L, -1).to(dev).contiguous()}))
         else:
             toks = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc)
         torch.cuda.synchronize()

@@ -101,7 +101,7 @@ class AnticipationRNNTester(object):
                                      tensor_metadata.view(num_voices, seq_len, num_metadata), start_measure=8, num_measures_gen=2)
 
     def generation(self, tensor_score, start_measure, num_measures_gen, tensor_metadata=None, temperature=1.5, num_variations=1,
-                   top_k=None, top_p=None):
+                   top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None, clamp_context=False):
         """Generates measures start_measure .. start_measure + num_measures_gen - 1 (1-based) of a score with temperature 1.5
         (:185-243) -> (gen_score | None, gen_score_tensor (1, L): past | generated | future, original_score | None).
 
@@ -109,6 +109,15 @@ class AnticipationRNNTester(object):
         metadata and its constraints: gen_score_tensor is (num_variations, L), past and future the input's in every row.  top_k /
         top_p: generate()'s truncation; with one of them self.last_logp is (num_variations, num_measures_gen) float32, the sum of the
         window's log-probabilities per measure (NaN where a tick took the argmax rule) -- what to rank the fillings by; else None.
+
+        banned_tokens (a list of token indices): never returned at any tick of the window -- START, END or a padding symbol in the
+        middle of a piece.  fixed_tokens (an int tensor (num_measures_gen, measure_seq_len) or flat, -1 = a free tick): the notes to
+        keep; a fixed tick wins over a ban.  clamp_context=True fixes every tick OUTSIDE the window to the score's own token: generate()
+        draws every tick, so without it the generation LSTMs reach the gap behind their own drawn version of the past; with it they
+        reach it behind the true past.  All three act inside the launch (generate()'s `allowed`): the token fed into tick t + 1 is the
+        constrained one.  Every variation gets the same mask, and with one of the three given the batched call is taken for
+        num_variations=1 too.  ValueError for an index outside [0, V) (fixed: other than -1), a ban of the whole vocabulary, or -- with
+        clamp_context -- a score token outside [0, V).  A fixed tick adds exactly 0 to last_logp.
 
         tensor_score (1, L) tokens (None: a random score of dataset.iterator_gen()); its metadata come from
         dataset.transposed_score_and_metadata_tensors where the dataset has it and a score can be built, else from
@@ -137,16 +146,54 @@ class AnticipationRNNTester(object):
         tensor_score = tensor_score[:, :num_measures * self.measure_seq_len]
         tensor_metadata = tensor_metadata[:, :num_measures * self.measure_seq_len]
         return self._generate_window(tensor_score, tensor_metadata, start_measure, num_measures_gen, temperature, num_variations,
-                                     top_k, top_p)
+                                     top_k, top_p, banned_tokens, fixed_tokens, clamp_context)
+
+    def _allowed(self, tensor_score, start_tick, end_tick, measure_seq_len, banned_tokens, fixed_tokens, clamp_context):
+        """generation()'s constraints as one row of generate()'s mask: bool (L, V) on the host, or None without constraints.  The bans
+        and the fixed tokens act on the window [start_tick, end_tick); clamp_context fixes every tick outside it to the score's token."""
+        if banned_tokens is None and fixed_tokens is None and not clamp_context:
+            return None
+        V, L, W = int(self.model.num_notes_per_voice[0]), int(tensor_score.shape[1]), end_tick - start_tick
+        allow = torch.ones(L, V, dtype=torch.bool)
+        if banned_tokens is not None:
+            banned = [int(b) for b in banned_tokens]
+            if any(b != b0 for b, b0 in zip(banned, banned_tokens)) or any(not 0 <= b < V for b in banned):
+                raise ValueError(f"banned_tokens {list(banned_tokens)!r}: token indices in [0, {V})")
+            if len(set(banned)) == V:
+                raise ValueError("banned_tokens bans the whole vocabulary")
+            allow[start_tick:end_tick, banned] = False
+        if fixed_tokens is not None:
+            fixed = torch.as_tensor(fixed_tokens).cpu()
+            if fixed.is_floating_point() or fixed.dtype == torch.bool or fixed.numel() != W or \
+                    (fixed.dim() != 1 and tuple(fixed.shape) != (W // measure_seq_len, measure_seq_len)):
+                raise ValueError(f"fixed_tokens must be an int tensor of shape {(W // measure_seq_len, measure_seq_len)} or "
+                                 f"{(W,)}, got {fixed.dtype} {tuple(fixed.shape)}")
+            fixed = fixed.long().reshape(W)
+            if bool(((fixed < -1) | (fixed >= V)).any()):
+                raise ValueError(f"fixed_tokens: token indices in [0, {V}), or -1 for a free tick")
+            one = torch.zeros(W, V, dtype=torch.bool)
+            one.scatter_(1, fixed.clamp(min=0).unsqueeze(-1), True)
+            allow[start_tick:end_tick] = torch.where((fixed >= 0).unsqueeze(-1), one, allow[start_tick:end_tick])
+        if clamp_context:
+            own = torch.as_tensor(tensor_score)[0].cpu().long()
+            outside = torch.ones(L, dtype=torch.bool)
+            outside[start_tick:end_tick] = False
+            if bool(((own < 0) | (own >= V))[outside].any()):
+                raise ValueError(f"clamp_context: the score has tokens outside [0, {V}) outside the window")
+            one = torch.zeros(L, V, dtype=torch.bool)
+            one.scatter_(1, own.clamp(0, V - 1).unsqueeze(-1), True)
+            allow = torch.where(outside.unsqueeze(-1), one, allow)
+        return allow
 
     def _generate_window(self, tensor_score, tensor_metadata, start_measure, num_measures_gen, temperature=1.5, num_variations=1,
-                         top_k=None, top_p=None):
+                         top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None, clamp_context=False):
         num_variations = _num_variations(num_variations)
         self.last_logp = None
-        constraints_location = torch.zeros_like(tensor_score)
         measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
         start_tick = (start_measure - 1) * measure_seq_len
         end_tick = start_tick + num_measures_gen * measure_seq_len
+        allowed = self._allowed(tensor_score, start_tick, end_tick, measure_seq_len, banned_tokens, fixed_tokens, clamp_context)   # (the argument errors first)
+        constraints_location = torch.zeros_like(tensor_score)
         if start_tick > 0:
             constraints_location[:, :start_tick] = 1
         if end_tick < constraints_location.size(1) - 1:
@@ -155,7 +202,7 @@ class AnticipationRNNTester(object):
         tensor_future = tensor_score[:, end_tick:]
         tensor_target = tensor_score[:, start_tick:end_tick]
         original_tensor = torch.cat((tensor_past, tensor_target, tensor_future), 1)
-        if num_variations == 1 and top_k is None and top_p is None:
+        if num_variations == 1 and top_k is None and top_p is None and allowed is None:
             _, gen_target, _ = self.model.generate(tensor_score=tensor_score, tensor_metadata=tensor_metadata,
                                                    constraints_location=constraints_location, temperature=temperature)
             gen_target = gen_target[:, start_tick:end_tick]
@@ -166,7 +213,8 @@ class AnticipationRNNTester(object):
         _, gen, _ = self.model.generate(tensor_score=tensor_score[:1].unsqueeze(0).expand(n, 1, L).contiguous(),
                                         tensor_metadata=tensor_metadata[:1].unsqueeze(0).expand(n, 1, L, -1).contiguous(),
                                         constraints_location=constraints_location[:1].unsqueeze(0).expand(n, 1, L).contiguous(),
-                                        temperature=temperature, top_k=top_k, top_p=top_p)
+                                        temperature=temperature, top_k=top_k, top_p=top_p,
+                                        **({} if allowed is None else {"allowed": allowed.unsqueeze(0).expand(n, -1, -1)}))
         gen_target = gen[:, 0, start_tick:end_tick].to(tensor_score.dtype)
         gen_score_tensor = torch.cat((tensor_past.expand(n, -1), gen_target, tensor_future.expand(n, -1)), 1)
         if self.model.last_logp is not None:

@@ -21,6 +21,8 @@ size_t arnn_sample_ws_floats(const ArnnGenNet& net, int R, int L);
 // top_k / top_p: sample.h's truncation in front of the draw (0 / 1.0: off); logp [R][L] (nullable): the drawn tokens' log-probabilities
 // under the truncated distribution, NaN where a tick took the argmax rule; logits [R][L][V] (nullable): what each tick drew from.
 // Truncation on or one of the two pointers given: the truncating kernels (labels trunc_...); otherwise the kernels of the sampling build.
+// allow [R][L][ceil(V / 64)] (nullable): sample.h's words of allowed tokens per (row, tick), applied in front of the truncation inside the
+// launch -- the masked kernels (labels cons_...), which are truncating ones; null: the call above.
 int arnn_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
                 const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k = 0,
-                double top_p = 1.0, float* logp = nullptr, float* logits = nullptr);
+                double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr);

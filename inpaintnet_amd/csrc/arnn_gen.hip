@@ -38,6 +38,8 @@
 // The truncating build (TRUNC = true, V <= 64: inet_arnn_sample_ex) puts sample.h's top-k / nucleus truncation in front of that draw,
 // reports the drawn tokens' log-probabilities (the logarithms are taken behind the last tick) and, where asked, every tick's logits;
 // head_trunc_b1_kernel does the same for the per-tick launches.  A call without truncation, logp or logits runs the sampling build.
+// The masked build (MASK = true, V <= 64: inet_arnn_sample_cx) puts sample.h's per-tick token constraints in front of the truncation;
+// head_cons_b1_kernel does the same for the per-tick launches.  A call without a mask runs the kernels it ran before.
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -72,6 +74,8 @@ struct GenArgs {
     int rows; float temp; const double* uniforms;
     // truncating build (TRUNC: sample.h's truncation in front of the draw): logp [rows][L] or null, logits [rows][L][V] or null
     int top_k; double top_p; float* logp; float* logits;
+    // masked build (MASK: sample.h's token constraints in front of the truncation): the allowed tokens' words [rows][L][ceil(V / 64)]
+    const unsigned long long* allow;
 };
 #define GEN_STAMP(who, t, i) do { if (a.stamps && tid == 0) a.stamps[((long)(who) * a.L + (t)) * 8 + (i)] = wall_clock64(); } while (0)
 
@@ -155,9 +159,18 @@ __device__ __forceinline__ void recurrent_role(const GenArgs& a, int k, const fl
 // spilled next to the 160 weight registers), as it did in decode_b1.hip: the workgroup takes all logarithms behind the last tick, one
 // tick per thread, where the weights' registers are free.  The terms are filed in the first three floats of the tick's own row of
 // `pre`: the row's 256 readers are this workgroup's unit threads, which consumed it in front of the tick's first barrier.
-template <int NV, bool SAMPLE, bool TRUNC = false>
+// MASK (the masked build of the truncating build: inet_arnn_sample_cx; sample.h has the rule): the tick's word of allowed tokens bans
+// tokens behind the NaN test and in front of the truncation.  The word arrives like the tick's uniform: requested a tick early through a
+// wave-uniform address, so every wave of C holds it in scalar registers and the token stays a function of the logits, u, the word and
+// kernel arguments -- the same in all eight waves.  The note head is not ReLU'd: a tick outside the rule takes the argmax rule over its
+// ALLOWED logits alone (the banned ones count as -inf and are no candidates, a NaN at a banned place is no NaN), so its token is an
+// allowed one whatever the logits hold.  The logits the call returns stay the unmasked ones.  One word per tick: V <= 64, as the
+// truncating build.
+template <int NV, bool SAMPLE, bool TRUNC = false, bool MASK = false>
 __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
     static_assert(SAMPLE || !TRUNC, "the truncating build is a sampling build");
+    static_assert(TRUNC || !MASK, "the masked build is a truncating build");
+    static_assert(!MASK || NV == 1, "the masked build reads ONE word per tick: NW = ceil(V / 64) = NV = 1");
     __shared__ __attribute__((aligned(16))) float xs[2][XS];
     __shared__ __attribute__((aligned(16))) float us[GH];
     __shared__ float ps[8][64 * NV];
@@ -253,6 +266,12 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
         unsigned long long hw[4];
         const double* const urow = SAMPLE ? a.uniforms + (long)team * a.L : nullptr;
         double u = 0.0, u_next = SAMPLE ? urow[0] : 0.0;       // (the next tick's uniform is requested a tick early)
+        [[maybe_unused]] const unsigned long long* const arow = MASK ? a.allow + (long)team * a.L * NV : nullptr;
+        [[maybe_unused]] unsigned long long aw[NV] = {}, aw_next[NV] = {};   // (masked build: ... and its words of allowed tokens)
+        if constexpr (MASK) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) aw_next[j] = arow[j];
+        }
         if (unit) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) pr[g] = pre[g * GH + tid];
@@ -266,6 +285,13 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
             if constexpr (SAMPLE) {
                 u = u_next;
                 if (more) u_next = urow[t + 1];
+            }
+            if constexpr (MASK) {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    aw[j] = aw_next[j];
+                    if (more) aw_next[j] = arow[(long)(t + 1) * NV + j];
+                }
             }
             GEN_STAMP(0, t, 0);
             if (unit) {
@@ -357,7 +383,9 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                         }
                         float gap = 0.f;
                         double tot = 0.0;
+                        if constexpr (MASK) sample::mask_words<NV>(aw, a.V);
                         if (!__ballot(nan)) {
+                            if constexpr (MASK) ms = sample::mask_scores<NV>(sv, aw, lane);
                             const float mw = wave_max_dpp(ms);
                             sample::truncate<NV>(sv, mw, a.top_k, a.top_p, a.V, lane);
                             bi = sample::pick<NV>(sv, mw, u, a.V, lane, tot);
@@ -374,9 +402,19 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                     }
                 }
                 if (bi < 0) {
+                    if constexpr (MASK) {                       // the argmax rule over the allowed logits alone (the logits are stored by now)
+                        m = -INFINITY;
+#pragma unroll
+                        for (int j = 0; j < NV; ++j) {
+                            if (!sample::allowed(aw[j], lane)) lg[j] = -INFINITY;
+                            nanm[j] = __ballot(lg[j] != lg[j]);
+                            m = fmaxf(m, lg[j]);
+                        }
+                        m = wave_max_dpp(m);
+                    }
 #pragma unroll
                     for (int j = NV - 1; j >= 0; --j) {
-                        const unsigned long long eq = __ballot(lg[j] == m);
+                        const unsigned long long eq = __ballot(lg[j] == m) & (MASK ? aw[j] : ~0ull);   // (allowed logits all -inf: the lowest allowed)
                         if (eq) bi = 64 * j + __builtin_ctzll(eq);
                     }
 #pragma unroll
@@ -493,6 +531,8 @@ bool arnn_token_pass_ok(const ArnnGenNet& n) {
 // with spills (256 VGPRs, 40 spilled, 148 bytes of scratch -- the argmax and sampling builds of that shape spill 36 and 41), so it is
 // not built and a truncated call with V > 64 takes the per-tick launches.
 bool arnn_token_trunc_ok(const ArnnGenNet& n) { return arnn_token_pass_ok(n) && n.V <= 64; }
+// The masked build (<1, true, true, true>) fits where the truncating build does: one word of allowed tokens per tick.
+bool arnn_token_cons_ok(const ArnnGenNet& n) { return arnn_token_trunc_ok(n); }
 
 // tables | exchange + status | stamps (2 x L x 8 64-bit words, written only under INET_ARNN_GEN_STAMPS=1: tools/arnn_token_pass.py)
 size_t arnn_token_pass_ws_floats(int L, int V) { return (size_t)L * G4 + (size_t)V * G4 + (size_t)kExFloats + 64 + (size_t)32 * L; }
@@ -559,16 +599,17 @@ size_t arnn_token_sample_ws_floats(int R, int L, int V) {
 }
 
 // trunc: the truncating build (truncation on, or a logp / logits pointer given); its labels start with trunc_
+// allow (with trunc; V <= 64: arnn_token_cons_ok): the masked build, [R][L][1] words of allowed tokens; its labels start with cons_
 int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
                       const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, bool trunc, int top_k,
-                      double top_p, float* logp, float* logits) {
+                      double top_p, float* logp, float* logits, const unsigned long long* allow) {
     const int V = net.V, n = sample_teams(R);
     float* pre = ws;
     float* T0 = pre + (size_t)n * L * G4;
     unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
     const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
     char label[64];
-    std::snprintf(label, sizeof label, "%sarnn_token_sample R%d L%d V%d", trunc ? "trunc_" : "", R, L, V);
+    std::snprintf(label, sizeof label, "%sarnn_token_sample R%d L%d V%d", allow ? "cons_" : trunc ? "trunc_" : "", R, L, V);
     for (int r0 = 0; r0 < R; r0 += n) {                          // R > teams: successive launches of up to `n` rows
         const int rows = std::min(n, R - r0);
         unsigned* status = reinterpret_cast<unsigned*>(ex + rows * kExGranules);
@@ -580,10 +621,12 @@ int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, lon
         a.rows = rows; a.temp = temp; a.uniforms = uniforms + (long)r0 * L;
         a.top_k = top_k; a.top_p = top_p;
         a.logp = logp ? logp + (long)r0 * L : nullptr; a.logits = logits ? logits + (long)r0 * L * V : nullptr;
+        a.allow = allow ? allow + (long)r0 * L * ((V + 63) / 64) : nullptr;     // (this launch's rows, like uniforms, logp and logits)
         ProfScope prof(PROF_GRU_FWD, 2.0 * rows * L * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH), s, label,
                        4.0 * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH + (double)(rows * L + V) * G4));
         const dim3 grid(a.stride == 8 ? 13 * 8 : 13 * rows);
-        if (trunc) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true>), grid, dim3(NT), 0, s, a);    // (V <= 64: arnn_token_trunc_ok)
+        if (allow) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true>), grid, dim3(NT), 0, s, a);   // (V <= 64: arnn_token_cons_ok)
+        else if (trunc) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true>), grid, dim3(NT), 0, s, a);    // (V <= 64: arnn_token_trunc_ok)
         else if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true>), grid, dim3(NT), 0, s, a);
         else hipLaunchKernelGGL((arnn_token_pass_kernel<2, true>), grid, dim3(NT), 0, s, a);
         if (hipGetLastError() != hipSuccess) return -2;
@@ -825,21 +868,102 @@ __global__ __launch_bounds__(1024) void head_trunc_b1_kernel(const float* __rest
     }
 }
 
+// np.argmax order over the ALLOWED entries of lg[0 .. V) by one wave (aw: the words of sample::mask_words, at least one bit set): a
+// banned entry is no candidate whatever it holds -- a NaN there does not win --, so the token is an allowed one
+__device__ __forceinline__ int argmax_wave_allowed(const float* lg, const unsigned long long (&aw)[4], int V, int lane) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int v = lane + 64 * j;
+        if (v < V && sample::allowed(aw[j], lane) && argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float b2 = __shfl_xor(best, o, 64);
+        const int i2 = __shfl_xor(bi, o, 64);
+        if (argmax_better(b2, i2, best, bi)) { best = b2; bi = i2; }
+    }
+    return bi;
+}
+
+// head_trunc_b1_kernel behind sample.h's token constraints: allow = the tick's ceil(V / 64) words of allowed tokens (<= 4: V <= 256),
+// read by wave 0 through a wave-uniform address.  The mask acts behind the NaN test and in front of the truncation; a tick outside the
+// rule takes the argmax over its allowed logits (argmax_wave_allowed) with a NaN logp.  The logits stored are the unmasked ones.
+template <int NI>
+__global__ __launch_bounds__(1024) void head_cons_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                            const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
+                                                            float temp, const double* __restrict__ u, int top_k, double top_p,
+                                                            float* __restrict__ logp, float* __restrict__ logits,
+                                                            const unsigned long long* __restrict__ allow) {
+    __shared__ float lg[256];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float xv[NI];
+    load_x<NI>(xv, x, K, nullptr, K, lane);
+    float part[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int v = w + 16 * r;
+        if (v < V) {
+            const float a = wave_sum(part[r]);
+            if (lane == 0) lg[v] = a + b[v];
+        }
+    }
+    __syncthreads();
+    if (w == 1 && logits)
+        for (int v = lane; v < V; v += 64) logits[v] = lg[v];
+    if (w == 0) {
+        const int nw = (V + 63) / 64;
+        unsigned long long aw[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) aw[j] = j < nw ? allow[j] : 0ull;
+        sample::mask_words<4>(aw, V);
+        float sv[4];
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int v = lane + 64 * j;
+            sv[j] = v < V ? lg[v] * temp : -INFINITY;
+            nan |= sv[j] != sv[j];
+        }
+        int bi = -1;
+        float gap = 0.f;
+        double tot = 0.0;
+        if (!__ballot(nan)) {
+            float ms = sample::mask_scores<4>(sv, aw, lane);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
+            sample::truncate<4>(sv, ms, top_k, top_p, V, lane);
+            bi = sample::pick<4>(sv, ms, *u, V, lane, tot);
+            if (bi >= 0) gap = sample::logp_gap<4>(sv, ms, bi);
+        }
+        if (logp && lane == 0) *logp = bi >= 0 ? sample::logp_of(gap, tot) : __builtin_nanf("");
+        if (bi < 0) bi = argmax_wave_allowed(lg, aw, V, lane);
+        if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
+    }
+}
+
 // the template bounds of the one-row kernels (ops.arnn_generate_ok in Python)
 bool arnn_ticks_ok(const ArnnGenNet& n) { return n.E + n.Hc <= 320 && n.H <= 256 && n.U <= 256 && n.V <= 256; }
 size_t arnn_ticks_ws_floats(const ArnnGenNet& n) { return (size_t)(n.E + n.Hc) + 4 * (size_t)n.H + 8 * (size_t)n.H + n.U + n.V + 64; }
 
 // L ticks of one row from the state hc_init [layer][h | c][H] (null: zeros; inpainting: the state after the prefix) and the token
 // *first_tok (null: 0); `uniforms` [L]: the sampling head, null: the argmax head; trunc (with uniforms): the truncating head, logp [L]
-// and logits [L][V] nullable, one label (trunc_arnn_ticks ...) around the row's launches
+// and logits [L][V] nullable, one label (trunc_arnn_ticks ...) around the row's launches; allow (with trunc): the row's [L][ceil(V / 64)]
+// words of allowed tokens -- the masked head, label cons_arnn_ticks ...
 int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, const float* hc_init, const long long* first_tok,
                float temp, const double* uniforms, long long* tokens, float* ws, hipStream_t s, bool trunc = false, int top_k = 0,
-               double top_p = 1.0, float* logp = nullptr, float* logits = nullptr) {
+               double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr) {
     const int H = n.H;
     std::optional<ProfScope> prof;                             // (an untruncated call files nothing, as before)
     if (trunc) {
         char label[64];
-        std::snprintf(label, sizeof label, "trunc_arnn_ticks L%d V%d", L, n.V);
+        std::snprintf(label, sizeof label, "%sarnn_ticks L%d V%d", allow ? "cons_" : "trunc_", L, n.V);
         prof.emplace(PROF_GRU_FWD, 2.0 * L * ((double)4 * H * (n.E + n.Hc + 3.0 * H) + (double)n.U * H + (double)n.V * n.U), s, label);
     }
     float* hc = ws;                                            // [layer][h|c][ping-pong][H]
@@ -860,7 +984,11 @@ int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, cons
                            (const float*)C_(1, p), n.W_hh1, n.b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
         hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((n.U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), n.W1, n.b1, u,
                            n.U, H);
-        if (uniforms && trunc)
+        if (uniforms && trunc && allow)
+            hipLaunchKernelGGL((head_cons_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
+                               temp, uniforms + t, top_k, top_p, logp ? logp + t : nullptr, logits ? logits + (long)t * n.V : nullptr,
+                               allow + (long)t * ((n.V + 63) / 64));
+        else if (uniforms && trunc)
             hipLaunchKernelGGL((head_trunc_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
                                temp, uniforms + t, top_k, top_p, logp ? logp + t : nullptr, logits ? logits + (long)t * n.V : nullptr);
         else if (uniforms)
@@ -890,17 +1018,18 @@ int arnn_generate(const ArnnGenNet& n, int L, const float* oc0, long oc_stride, 
 
 int arnn_sample(const ArnnGenNet& n, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
                 const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k, double top_p,
-                float* logp, float* logits) {
-    // truncation on, or an output only the truncating kernels write: never a kernel that ignores them
-    const bool trunc = (top_k >= 1 && top_k < n.V) || top_p < 1.0 || logp || logits;
-    if (trunc ? arnn_token_trunc_ok(n) : arnn_token_pass_ok(n))    // up to 8 rows per launch
+                float* logp, float* logits, const unsigned long long* allow) {
+    // truncation on, or an output only the truncating kernels write: never a kernel that ignores them; a mask of allowed tokens: the
+    // masked kernels, which are truncating ones
+    const bool trunc = (top_k >= 1 && top_k < n.V) || top_p < 1.0 || logp || logits || allow;
+    if (allow ? arnn_token_cons_ok(n) : trunc ? arnn_token_trunc_ok(n) : arnn_token_pass_ok(n))    // up to 8 rows per launch
         return arnn_token_sample(n, R, L, oc0, oc_stride, oc_bstride, temp, uniforms, hc_init, tokens, ws, s, trunc, top_k, top_p, logp,
-                                 logits);
+                                 logits, allow);
     if (!arnn_ticks_ok(n)) return -1;
     int rc = 0;
     for (int r = 0; r < R && rc == 0; ++r)                     // the rows one after the other
         rc = arnn_ticks(n, L, oc0 + (long)r * oc_bstride, oc_stride, hc_init ? hc_init + (long)r * 4 * n.H : nullptr, nullptr, temp,
                         uniforms + (long)r * L, tokens + (long)r * L, ws, s, trunc, top_k, top_p, logp ? logp + (long)r * L : nullptr,
-                        logits ? logits + (long)r * L * n.V : nullptr);
+                        logits ? logits + (long)r * L * n.V : nullptr, allow ? allow + (long)r * L * ((n.V + 63) / 64) : nullptr);
     return rc;
 }
