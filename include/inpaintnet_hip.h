@@ -153,6 +153,45 @@ int inet_vae_decoder_sample_cx(const inet_vae_config* cfg, int batch, const floa
                                const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
                                float temperature, const double* uniforms, int top_k, double top_p, float* logp,
                                const uint64_t* allow, void* stream);
+/* The same with FORCED TOKENS: a per-(row, tick) token that is fed back like a drawn one and whose log-probability is taken under the same
+ * masked and truncated distribution a draw would have used (csrc/sample.h).  Every tick forced: the call scores a given
+ * filling (a teacher-forced evaluation pass inside the one launch); the first ticks forced: it continues a prefix.
+ * Layout.
+ *  - `forced` is an array of `int32` `[rows][T]`.
+ *  - A value `f` with `0 <= f < V` forces that tick.
+ *  - Every other value makes the tick free.  The Python surfaces write -1 for a free tick.
+ *  - A null `forced` means no tick is forced.
+ * At a free tick nothing changes.  Section 13's rule runs as it does today.
+ * At a forced tick with token `f`:
+ *  1. Scores and truncation.
+ *     - Steps 0-2 of section 13 run unchanged on the tick's logits: s = T x in f32, the NaN test, the mask, m, and the top-k / nucleus
+ *       truncation.
+ *     - S is the kept total.
+ *     - The tick's uniform is not used.  The rule is evaluated as with u = 0, so a uniform outside [0, 1) or NaN at a forced tick
+ *       causes no fallback.
+ *  2. Token.
+ *     - The token is `f`.  It is reported in `samples` and fed back into tick t + 1.
+ *     - This holds whether or not `f` is allowed or kept, and it holds on a fallback tick too.
+ *  3. Log-probability.  logp = (s_f - m) - log S as f32.
+ *     - It is exactly -inf when `f` is banned or truncated away (s_f = -inf).
+ *     - It is NaN where the rule does not apply: a NaN among s, or m or S not finite.
+ * Consequences.  The tests hold each of these exactly.
+ *  (a) No forced tick.  A null `forced`, or one with no value in [0, V), gives inet_vae_decoder_sample_cx bit for bit in tokens, logits
+ *      and logp.
+ *  (b) Replay.  Force, at every tick, the tokens that a sampled, truncated or constrained call returned.  The replay uses the same
+ *      temperature, top_k, top_p and mask, and any uniforms at all.  It returns that call's logits and logp bit for bit, with NaN where
+ *      that call had NaN.
+ *  (c) A banned forced token is still returned and fed back.  Its logp is -inf.
+ *  (d) One-bit mask.  A forced tick whose mask has the single bit `f` set has logp exactly 0.0f.
+ *  (e) Free ticks of a partly forced call follow section 13's rule on the trajectory behind the forced tokens.
+ * forced: [B][T] int32 on the device, or null -- then this IS inet_vae_decoder_sample_cx.  allow may be null beside it (a mask of all
+ * ones).  A forced call runs the forced build of the register-resident launch (the constrained call's plan: inet_decode_b1_plan_trunc) or,
+ * for every other shape, inet_sample_forced's kernel tick by tick: its launch labels start with "force_" (force_decode_b1...,
+ * force_sample ...).  -1 where inet_vae_decoder_sample_cx returns it. */
+int inet_vae_decoder_sample_fx(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
+                               const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
+                               float temperature, const double* uniforms, int top_k, double top_p, float* logp,
+                               const uint64_t* allow, const int32_t* forced, void* stream);
 /* dweights [B,T,V] = dLoss/dweights; weights = the forward output; grads may be null (frozen decoder:
  * LatentRNN/latent_rnn.py:42-43) in which case only dz [B,Z] is produced.  `tokens_in` are the tokens that
  * were fed back (= samples of the forward call). */
@@ -218,6 +257,14 @@ int inet_sample_truncated(const float* weights, int64_t ld_w, int rows, int V, f
 int inet_sample_constrained(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                             int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
                             const uint64_t* allow, int64_t allow_stride, void* stream);
+/* The forced rule of inet_vae_decoder_sample_fx on rows of V logits, one wavefront per row: forced[row*forced_stride] = the row's forced
+ * token, a value outside [0, V) = a free row, which is inet_sample_constrained's row; a null forced: inet_sample_constrained.  A forced row
+ * returns its token whatever the mask, the truncation and the logits hold, ignores its uniform, and reports logp = (s_f - m) - log S: -inf
+ * where the token is banned or truncated away, NaN where the rule does not apply.  allow may be null beside forced (all ones).  -1 where
+ * inet_sample_constrained returns it. */
+int inet_sample_forced(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
+                       int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
+                       const uint64_t* allow, int64_t allow_stride, const int32_t* forced, int64_t forced_stride, void* stream);
 
 /* ---- optimizer: torch.optim.Adam as built at utils/trainer.py:32-35, stepped at :172-177 -------- */
 /* p,g,m,v: arenas of n floats; step is 1-based; grads are multiplied by gscale first (1/world_size for DP) */
@@ -559,7 +606,8 @@ int inet_decode_b1_plan(int B, int V, int Z, int* out8);
 int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8);
 /* ... and for a truncated call (inet_vae_decoder_sample_ex with truncation on or a logp): the truncating build has a merged build
  * for one row with V <= 32 alone (the others would spill registers), so more of its plans place workgroup C. */
-/* (A constrained call -- inet_vae_decoder_sample_cx with a mask -- has the truncated call's plan: every masked build fits.) */
+/* (A constrained call -- inet_vae_decoder_sample_cx with a mask -- has the truncated call's plan: every masked build fits.  A forced call
+ *  -- inet_vae_decoder_sample_fx with forced tokens -- has it too: every forced build fits.) */
 int inet_decode_b1_plan_trunc(int B, int V, int Z, int* out8);
 /* What inet_gemm (nbatch = 1) / inet_gemm_batched (nbatch 2..8: no bias, epi 0, acc 1) launch for a call, under the options set now
  * (inet_set_option keys 2, 3, 5), without a GPU: the dispatcher's planner (csrc/gemm.hip gemm_plan) behind the C-ABI.  out16 = {family

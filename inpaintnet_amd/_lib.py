@@ -97,6 +97,7 @@ _SIGNATURES = {
     "inet_vae_decoder_sample": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P]),
     "inet_vae_decoder_sample_ex": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _I, C.c_double, _P, _P]),
     "inet_vae_decoder_sample_cx": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _I, C.c_double, _P, _P, _P]),
+    "inet_vae_decoder_sample_fx": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _I, C.c_double, _P, _P, _P, _P]),
     "inet_vae_decoder_bwd": (C.c_int, [_CFG, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "inet_vae_ws_field": (C.c_int, [_CFG, _I, _I, C.c_char_p, C.POINTER(_L), C.POINTER(_L)]),
     "inet_cross_entropy": (C.c_int, [_P, _L, _I, _I, _P, _P, _L, _F, _F, _P, _P, _P]),
@@ -106,6 +107,7 @@ _SIGNATURES = {
     "inet_sample_temperature": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _P, _L, _P]),
     "inet_sample_truncated": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _I, C.c_double, _P, _L, _P, _L, _P]),
     "inet_sample_constrained": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _I, C.c_double, _P, _L, _P, _L, _P, _L, _P]),
+    "inet_sample_forced": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _I, C.c_double, _P, _L, _P, _L, _P, _L, _P, _L, _P]),
     "inet_latent_bwd": (C.c_int, [_P, _P, _P, _P, _F, _P, _P, _P, _L, _P]),
     "inet_adam_step": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),
     "inet_adam_step_ex": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P, _P]),

@@ -131,17 +131,25 @@ int inet_vae_decoder_fwd(const inet_vae_config* cfg, int batch, const float* z, 
     return vae_decoder_fwd(*cfg, batch, z, (const long long*)target, teacher_forced, params, mask_beat, mask_tick,
                            weights, (long long*)samples, ws, save, (hipStream_t)stream, multinomial_seed);
 }
-int inet_vae_decoder_sample_cx(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
+int inet_vae_decoder_sample_fx(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
                                const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
                                float temperature, const double* uniforms, int top_k, double top_p, float* logp,
-                               const uint64_t* allow, void* stream) {
+                               const uint64_t* allow, const int32_t* forced, void* stream) {
     if (!cfg_ok(cfg) || batch <= 0 || !z || !params || !weights || !samples || !ws || !uniforms) return -1;
     if (allow && (int64_t)cfg->beats * cfg->ticks_per_beat > 64) return -1;    // (a constrained call: at most 64 ticks)
     if (!std::isfinite(temperature) || cfg->num_notes > 512) return -1;
     if (!(top_p > 0.0 && top_p <= 1.0)) return -1;             // (a NaN too)
     if (ws_bytes < (int64_t)vae_decoder_ws_bytes(*cfg, batch, save)) return -1;
     return vae_decoder_fwd(*cfg, batch, z, nullptr, 0, params, mask_beat, mask_tick, weights, (long long*)samples, ws, save,
-                           (hipStream_t)stream, 0, uniforms, temperature, top_k, top_p, logp, (const unsigned long long*)allow);
+                           (hipStream_t)stream, 0, uniforms, temperature, top_k, top_p, logp, (const unsigned long long*)allow,
+                           (const int*)forced);
+}
+int inet_vae_decoder_sample_cx(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
+                               const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
+                               float temperature, const double* uniforms, int top_k, double top_p, float* logp,
+                               const uint64_t* allow, void* stream) {
+    return inet_vae_decoder_sample_fx(cfg, batch, z, params, mask_beat, mask_tick, weights, samples, ws, ws_bytes, save, temperature,
+                                      uniforms, top_k, top_p, logp, allow, nullptr, stream);
 }
 int inet_vae_decoder_sample_ex(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
                                const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
@@ -197,13 +205,20 @@ int inet_sample_temperature(const float* weights, int64_t ld_w, int rows, int V,
     if (!weights || !uniforms || !out || rows <= 0 || V <= 0 || V > 512 || !std::isfinite(temperature)) return -1;
     return pw_sample_temperature(weights, ld_w, rows, V, temperature, uniforms, u_stride, (long long*)out, stride, (hipStream_t)stream);
 }
+int inet_sample_forced(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
+                       int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
+                       const uint64_t* allow, int64_t allow_stride, const int32_t* forced, int64_t forced_stride, void* stream) {
+    if (!weights || !uniforms || !out || rows <= 0 || V <= 0 || V > 512 || !std::isfinite(temperature)) return -1;
+    if (!(top_p > 0.0 && top_p <= 1.0)) return -1;             // (a NaN too)
+    return pw_sample_forced(weights, ld_w, rows, V, temperature, uniforms, u_stride, top_k, top_p, (long long*)out, stride, logp,
+                            logp_stride, (const unsigned long long*)allow, allow_stride, (const int*)forced, forced_stride,
+                            (hipStream_t)stream);
+}
 int inet_sample_constrained(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                             int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
                             const uint64_t* allow, int64_t allow_stride, void* stream) {
-    if (!weights || !uniforms || !out || rows <= 0 || V <= 0 || V > 512 || !std::isfinite(temperature)) return -1;
-    if (!(top_p > 0.0 && top_p <= 1.0)) return -1;             // (a NaN too)
-    return pw_sample_constrained(weights, ld_w, rows, V, temperature, uniforms, u_stride, top_k, top_p, (long long*)out, stride, logp,
-                                 logp_stride, (const unsigned long long*)allow, allow_stride, (hipStream_t)stream);
+    return inet_sample_forced(weights, ld_w, rows, V, temperature, uniforms, u_stride, top_k, top_p, out, stride, logp, logp_stride,
+                              allow, allow_stride, nullptr, 0, stream);
 }
 int inet_sample_truncated(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                           int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,

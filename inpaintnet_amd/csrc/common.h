@@ -78,6 +78,9 @@ struct GemmArgs {
     // nbatch > 1: that many products of one shape in one launch, problem i on A + i*batchA, B + i*batchB, C + i*batchC
     // (element strides of either sign; no bias / epilogue).  launch_gemm runs them one by one where no batched kernel applies.
     int nbatch; long batchA, batchB, batchC;
+    // 1: one k range per output tile -- the planner does not split K over the grid, so no f32 atomics accumulate in an order that changes
+    // from launch to launch and the product reproduces itself bit for bit (the beat path of a sampled decoder call: sample.h's replay)
+    int one_range;
 };
 
 // ---------------------------------------------------------------------------

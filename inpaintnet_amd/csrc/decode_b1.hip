@@ -156,6 +156,7 @@ struct B1Args {
     const double* uniforms; float temperature;   // the sampling build: one uniform per (row, tick) [B, T], the logits' factor
     int top_k; double top_p; float* logp;        // the truncating build: sample.h's truncation in front of the draw; logp [B, T] or null
     const unsigned long long* allow;             // the masked build: the allowed tokens' words [B, T, ceil(V / 64)] (sample.h's layout)
+    const int* forced;                           // the forced build: the forced tokens [B, T], a value outside [0, V) = a free tick
 };
 
 #define B1_STAMP(who, t, i) do { if (stamps && tid == 0) stamps[((who) * 32 + (t)) * 8 + (i)] = wall_clock64(); } while (0)
@@ -557,6 +558,33 @@ __device__ __forceinline__ int sample_token_cons(const float (&lg)[NVL], float t
     else S = 1.0;
     return tok;
 }
+// FORCED TOKENS (FORCE = true, the forced build of the masked build; sample.h has the rule): `f` is the tick's forced word, read through the
+// same wave-uniform address as `ut` and the mask words.  A free tick (f outside [0, V)) IS sample_token_cons.  A forced tick runs the same
+// mask, truncation and pick -- with u = 0.0, for the kept total S alone -- and then returns f with gap = s_f - m: -inf where f is banned or
+// truncated away, NaN (and S = 1) where the rule does not apply.  It never returns -1: the caller's argmax re-read is skipped.
+template <int NVL>
+__device__ __forceinline__ int sample_token_force(const float (&lg)[NVL], float temp, double u, int V, int lane, int top_k, double top_p,
+                                                  const unsigned long long (&aw)[NVL], int f, float& gap, double& S) {
+    const bool forced = sample::is_forced(f, V);
+    float sv[NVL];
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < NVL; ++j) {
+        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
+        nan |= sv[j] != sv[j];
+    }
+    gap = __builtin_nanf("");
+    S = 1.0;
+    if (__ballot(nan)) return forced ? f : -1;
+    const float ms = wave_max_dpp(sample::mask_scores<NVL>(sv, aw, lane));
+    sample::truncate<NVL>(sv, ms, top_k, top_p, V, lane);
+    int tok = sample::pick<NVL>(sv, ms, forced ? 0.0 : u, V, lane, S);
+    if (tok >= 0) {
+        if (forced) tok = f;
+        gap = sample::logp_gap<NVL>(sv, ms, tok);
+    } else S = 1.0;
+    return forced ? f : tok;
+}
 // ... behind the last tick: logp[row, t] of the team's rows, one (row, tick) per thread (the picking waves' LDS writes are ordered by the
 // barrier the caller's loop ends with or by this one)
 template <int NB>
@@ -578,7 +606,8 @@ constexpr int kSharedRowsSmall = 3;              // ... and for four to six meas
 // not fit: 256 VGPRs and two spilled (the argmax build: 253) -- it is not built, such a call runs workgroup C.  The TRUNCATING build
 // (sample == 2) has a merged build for one row with V <= 32 alone: with two logit blocks per thread (one row, 32 < V <= 64; two rows, V <=
 // 32) it comes out at 255 / 256 VGPRs with 12 bytes of scratch -- not built either, workgroup C.  The MASKED build (sample == 3) has the
-// truncating build's merged builds: a constrained call has the truncated call's plan.
+// truncating build's merged builds: a constrained call has the truncated call's plan.  The FORCED build (sample == 4) likewise: every one
+// of its builds fits without a spilled VGPR or scratch, so a forced call has the constrained call's plan.
 __host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, int sample) {
     return nb * nj <= 2 && !(sample && nb == 2 && nbr == kSharedRows) && !(sample >= 2 && nb * nj == 2);
 }
@@ -590,11 +619,12 @@ __host__ __device__ constexpr bool merged_build(int nb, int nj, int nbr, int sam
 // of 32 workgroups that serve NBR = 6 rows -- three teams -- each: 8 x 17 + 3 x 32 = 232 workgroups for sixteen measures, every
 // row on a two-row tick.  A group's rows without a team (the last group of a call) are skipped (Ctx.nact).
 // (TRUNC, the truncating build of the sampling build: behind SAMPLE, so that every build without it keeps its parameters; MASK, the
-//  masked build of the truncating build, behind TRUNC likewise)
-template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB, bool SAMPLE = false, bool TRUNC = false, bool MASK = false>
+//  masked build of the truncating build, behind TRUNC likewise; FORCE, the forced build of the masked build, behind MASK likewise)
+template <int NJ, bool FUSED, int NB, int NBB, int NBR = NB, bool SAMPLE = false, bool TRUNC = false, bool MASK = false, bool FORCE = false>
 __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     static_assert(SAMPLE || !TRUNC, "the truncating build is a sampling build");
     static_assert(TRUNC || !MASK, "the masked build is a truncating build");
+    static_assert(MASK || !FORCE, "the forced build is a masked build");
     constexpr int XROWS = NB > NBB ? (NB > NBR ? NB : NBR) : (NBB > NBR ? NBB : NBR);
     __shared__ __attribute__((aligned(16))) float xs[XROWS][2][XS];
     __shared__ float lgs[NB][32 * NJ];
@@ -623,7 +653,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     const int nb = a.T / a.G;
     const DecodeB1Beat& bp = a.bp;
     // MG, the merged build: workgroup C does not exist, every TBi_k does C's work for itself next to its own (CB below)
-    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE + TRUNC + MASK);
+    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE + TRUNC + MASK + FORCE);
 
     if (role == R_C) {
         if (MG) return;
@@ -663,9 +693,20 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             // the masked build: this (row, tick)'s mask words, requested next to `ut` through the same wave-uniform address
             [[maybe_unused]] unsigned long long aw[MASK ? NVL : 1] = {};
             if constexpr (MASK) {
-                if (picks) {
+                if (picks && (!FORCE || a.allow)) {
 #pragma unroll
                     for (int j = 0; j < NVL; ++j) aw[j] = a.allow[(urow_at + t) * NVL + j];
+                }
+            }
+            // the forced build: this (row, tick)'s forced word, likewise; without a mask (a kernel argument: wave-uniform) all ones
+            [[maybe_unused]] int fw = -1;
+            if constexpr (FORCE) {
+                if (picks) {
+                    fw = a.forced[urow_at + t];
+                    if (!a.allow) {
+#pragma unroll
+                        for (int j = 0; j < NVL; ++j) aw[j] = ~0ull;
+                    }
                 }
             }
             if (t % a.G == 0) {
@@ -746,7 +787,8 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 if constexpr (TRUNC) {
                     float gap;
                     double tot;
-                    if constexpr (MASK) bi = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
+                    if constexpr (FORCE) bi = sample_token_force<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, fw, gap, tot);
+                    else if constexpr (MASK) bi = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
                     else bi = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
                     if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
                 }
@@ -813,8 +855,9 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         // All of them run the same instructions on the same values, so they agree on every token bit for bit -- the sampling build too:
         // sample::pick is a pure function of the row's logits `lgs`, which every copy computes from the same gathered h1_t with the same
         // instructions, and of the uniform u[row, t], which every copy reads from the same address; the masked build adds the mask words
-        // of (row, t), which all sixteen copies likewise read from the same address, and top_k / top_p are kernel arguments: the token is a pure
-        // function of `lgs`, u, the mask words and kernel arguments, and nothing else may enter it.  CB_0 alone
+        // of (row, t), which all sixteen copies likewise read from the same address, and top_k / top_p are kernel arguments; the forced build adds
+        // the forced word of (row, t), again one address for all sixteen copies: the token is a pure function of `lgs`, u, the mask words, the
+        // forced word and kernel arguments, and nothing else may enter it.  CB_0 alone
         // publishes h0_t (for TA) and writes the outputs.  h0, h1 and gh0 alternate between two granule slots by tag parity: a CB
         // workgroup does not wait for its 15 peers to have READ a value before it writes the next one (a peer's read of h1_t is
         // ordered before its own h1_t+1, which the writer of h1_t+2 has to have seen: two slots are enough; likewise gh0, h0).
@@ -865,9 +908,20 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             // the masked build: this (row, tick)'s mask words, requested next to `ut` through the same wave-uniform address
             [[maybe_unused]] unsigned long long aw[MASK ? NVL : 1] = {};
             if constexpr (MASK) {
-                if (picks) {
+                if (picks && (!FORCE || a.allow)) {
 #pragma unroll
                     for (int j = 0; j < NVL; ++j) aw[j] = a.allow[(urow_at + t) * NVL + j];
+                }
+            }
+            // the forced build: this (row, tick)'s forced word, likewise; without a mask (a kernel argument: wave-uniform) all ones
+            [[maybe_unused]] int fw = -1;
+            if constexpr (FORCE) {
+                if (picks) {
+                    fw = a.forced[urow_at + t];
+                    if (!a.allow) {
+#pragma unroll
+                        for (int j = 0; j < NVL; ++j) aw[j] = ~0ull;
+                    }
                 }
             }
             const int g_h1 = slot_h1(tag);
@@ -979,7 +1033,8 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 if constexpr (TRUNC) {
                     float gap;
                     double tot;
-                    if constexpr (MASK) best = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
+                    if constexpr (FORCE) best = sample_token_force<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, fw, gap, tot);
+                    else if constexpr (MASK) best = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
                     else best = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
                     if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
                 }
@@ -1147,6 +1202,8 @@ int placed_grid(int teams, int rteams, int beat_wgs, int crit = kCrit) {
 // truncating builds (decode_b1_kernel<..., true, true>) and their merged_build(); at most kTruncTicks ticks.
 // A CONSTRAINED call (DecodeChainArgs.allow: a mask of allowed tokens per (row, tick)) has the truncated call's plan with the masked builds
 // (decode_b1_kernel<..., true, true, true>): every one of them fits without a spill.
+// A FORCED call (DecodeChainArgs.forced: a forced token per (row, tick), with or without a mask) has the constrained call's plan with the
+// forced builds (decode_b1_kernel<..., true, true, true, true>): every one of them fits likewise.
 
 // What launch_decode_b1 launches for a call, as a value (also behind inet_decode_b1_plan: the planner is tested without a GPU).  The
 // plan names its instantiation decode_b1_kernel<nj, fused, nb, nbb, nbr> itself (dispatch_b1).
@@ -1159,7 +1216,7 @@ struct B1Plan {
     int crit;                                    // critical workgroups per team under place_role: kCritTA, NU (merged build) or kCrit
     int place, stride, grid, live, beat_wgs;
     int rows;                                    // granule rows the launch addresses
-    int sample;                                  // 1: the sampling build, 2: the truncating build, 3: the masked build
+    int sample;                                  // 1: the sampling build, 2: the truncating build, 3: the masked build, 4: the forced build
     bool ok;                                     // the plan fits the chip
 };
 // a candidate plan's rows: teams of nb rows, the folded beat path's nbb, shared groups (ta_crit: the TA stay critical beside the
@@ -1249,10 +1306,10 @@ template <int NJ, int S>
 static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 #define B1_INST(F, NB, NBB, NBR)                                                                                             \
     if (p.fused == (F) && p.nb == (NB) && p.nbb == (NBB) && p.nbr == (NBR)) {                                               \
-        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR, S != 0, S >= 2, S == 3>), dim3(p.grid), dim3(NT), 0, s, *a);  \
+        if (a) hipLaunchKernelGGL((decode_b1_kernel<NJ, F, NB, NBB, NBR, S != 0, S >= 2, S >= 3, S == 4>), dim3(p.grid), dim3(NT), 0, s, *a);  \
         return true;                                                                                                        \
     }
-    // (S = 1 / 2 / 3, the sampling, the truncating and the masked builds: the default mode's plans only -- candidates())
+    // (S = 1 / 2 / 3 / 4, the sampling, the truncating, the masked and the forced builds: the default mode's plans only -- candidates())
     B1_INST(true, 1, 1, 1)                       // one team, one row, beat path folded in
     if constexpr (!S) { B1_INST(true, 2, 2, 2) } // ... two rows (modes 3, 5)
     B1_INST(true, 1, kDecodeB1OneRowTeamsMax, 1) // two / three one-row teams
@@ -1269,8 +1326,10 @@ static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 // (the masked builds are named in a function of their own BEHIND this one: the instantiations are emitted in the order their first use is
 //  met, so the builds that existed before keep their places at the front of the code object)
 static bool dispatch_b1_masked(const B1Plan& p, const B1Args* a, hipStream_t s);
+static bool dispatch_b1_forced(const B1Plan& p, const B1Args* a, hipStream_t s);      // (... and the forced builds behind the masked ones)
 static bool dispatch_b1(const B1Plan& p, const B1Args* a, hipStream_t s) {
     if (p.sample == 3) return dispatch_b1_masked(p, a, s);
+    if (p.sample == 4) return dispatch_b1_forced(p, a, s);
     switch (p.nj) {
         case 1: return p.sample == 2 ? dispatch_b1_nj<1, 2>(p, a, s) : p.sample ? dispatch_b1_nj<1, 1>(p, a, s) : dispatch_b1_nj<1, 0>(p, a, s);
         case 2: return p.sample == 2 ? dispatch_b1_nj<2, 2>(p, a, s) : p.sample ? dispatch_b1_nj<2, 1>(p, a, s) : dispatch_b1_nj<2, 0>(p, a, s);
@@ -1285,6 +1344,15 @@ static bool dispatch_b1_masked(const B1Plan& p, const B1Args* a, hipStream_t s) 
         case 2: return dispatch_b1_nj<2, 3>(p, a, s);
         case 3: return dispatch_b1_nj<3, 3>(p, a, s);
         case 4: return dispatch_b1_nj<4, 3>(p, a, s);
+        default: return false;
+    }
+}
+static bool dispatch_b1_forced(const B1Plan& p, const B1Args* a, hipStream_t s) {
+    switch (p.nj) {
+        case 1: return dispatch_b1_nj<1, 4>(p, a, s);
+        case 2: return dispatch_b1_nj<2, 4>(p, a, s);
+        case 3: return dispatch_b1_nj<3, 4>(p, a, s);
+        case 4: return dispatch_b1_nj<4, 4>(p, a, s);
         default: return false;
     }
 }
@@ -1310,8 +1378,8 @@ bool decode_b1_shape_ok(int B, int H, int V, int T, int G, int sample) {
 bool decode_b1_fused(int Z, int B, int V, int sample) { return Z == DZ && make_plan(B, V, true, sample).ok; }
 bool decode_b1_ok(const DecodeChainArgs& a) {
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;
-    const int sample = a.uniforms ? (a.allow ? 3 : a.trunc ? 2 : 1) : 0;
-    if (a.allow && !a.uniforms) return false;
+    const int sample = a.uniforms ? (a.forced ? 4 : a.allow ? 3 : a.trunc ? 2 : 1) : 0;
+    if ((a.allow || a.forced) && !a.uniforms) return false;
     return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G, sample) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr, sample).ok;
 }
 
@@ -1373,7 +1441,7 @@ int decode_b1_plan_check(int B, int V, int Z, int* out, int sample) {
 }
 
 int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
-    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms ? (d.allow ? 3 : d.trunc ? 2 : 1) : 0);
+    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms ? (d.forced ? 4 : d.allow ? 3 : d.trunc ? 2 : 1) : 0);
     if (!pl.ok || pl.rows > decode_b1_rows(d.B)) return -1;   // (decode_b1_ok has accepted the call: not reached)
     B1Args a{};
     a.fused = pl.fused; a.teams = pl.teams; a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place; a.stride = pl.stride;
@@ -1386,11 +1454,11 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     a.stamps = d.b1stamps;
     a.status = d.status;
     a.uniforms = d.uniforms; a.temperature = d.temperature;
-    a.top_k = d.top_k; a.top_p = d.top_p; a.logp = d.logp; a.allow = d.allow;
+    a.top_k = d.top_k; a.top_p = d.top_p; a.logp = d.logp; a.allow = d.allow; a.forced = d.forced;
     if (!dispatch_b1(pl, nullptr, nullptr)) return -1;        // (a plan without an instantiation launches nothing)
     char label[64];
-    // (a sampled, a truncated and a constrained call's launch have label prefixes of their own: the profile tells the kinds of call apart)
-    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample == 3 ? "cons_" : pl.sample == 2 ? "trunc_" : pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
+    // (a sampled, a truncated, a constrained and a forced call's launch have label prefixes of their own: the profile tells the kinds of call apart)
+    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample == 4 ? "force_" : pl.sample == 3 ? "cons_" : pl.sample == 2 ? "trunc_" : pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
     // algorithmic work: the tick GRU + head per tick and row; fused: + the beat path (z2b, two beat layers, three projections per beat)
     const double nbt = (double)d.T / d.G;
     const double beat_mac = a.fused ? 2.0 * DH * DZ + nbt * (3.0 * 3 * DH * DH + 2.0 * DH * DH + 1.0 * DH * DH + 3.0 * DH * DH) : 0.0;

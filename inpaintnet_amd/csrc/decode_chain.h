@@ -54,6 +54,8 @@ struct DecodeChainArgs {
     float* logp;                                  // [B,T] the drawn tokens' log-probabilities under the truncated distribution, or null
     // ... behind sample.h's per-tick token constraints (decode_b1.hip's masked build only, likewise; a constrained call is a truncated one)
     const unsigned long long* allow;              // [B,T,ceil(V/64)] the allowed tokens' words, or null: no constraint
+    // ... behind sample.h's forced tokens (decode_b1.hip's forced build only, likewise; a forced call is a constrained one, with or without a mask)
+    const int* forced;                            // [B,T] the forced tokens, a value outside [0, V) = a free tick, or null: no tick is forced
 };
 
 bool decode_chain_ok(int B, int H, int V, int T, int G);
@@ -73,8 +75,8 @@ constexpr int kDecodeB1OneRowTeamsMax = 3;        // ... with ONE-row teams (two
 // (the workspace is carved before the call knows whether its beat path is folded in; rows beyond B repeat row B - 1)
 int decode_b1_rows(int B);
 inline long decode_b1_words(int B) { return (long)decode_b1_rows(B) * kDecodeB1WordsPerRow; }
-// (sample: 1 = the plan of a temperature-sampled call, 2 = of a truncated one, 3 = of a constrained one -- the same planner decides, and
-//  may decide otherwise)
+// (sample: 1 = the plan of a temperature-sampled call, 2 = of a truncated one, 3 = of a constrained one, 4 = of a forced one -- the same
+//  planner decides, and may decide otherwise)
 bool decode_b1_shape_ok(int B, int H, int V, int T, int G, int sample = 0);   // a launchable plan with the beat path's own launches in front
 bool decode_b1_fused(int Z, int B, int V, int sample = 0);                         // ... and one with the beat path folded into the same launch
 bool decode_b1_ok(const DecodeChainArgs& a);                  // the plan of this call (beat.z != null: folded) is launchable

@@ -882,7 +882,7 @@ bool plan_ks(const GemmArgs& g, int force_split, GemmPlan& p) {
 // Big shapes (M or K = T*B = 6144) end up on 192-wide tiles with exactly 256 workgroups; small ones on 64x64
 // tiles split until every CU holds several workgroups.
 void plan_tiled(const GemmArgs& g, GemmPlan& p) {
-    const bool may_split = !(nonlinear(g) && g.acc != ACC_STORE);
+    const bool may_split = !(nonlinear(g) && g.acc != ACC_STORE) && !g.one_range;
     int bi = 0, bs = 1;
     if (g_force_cfg >= 0 && g_force_cfg < kNumCfgs) {
         bi = g_force_cfg;
@@ -932,7 +932,7 @@ void gemm_set_direct(int mode) { g_direct = mode; }
 GemmPlan gemm_plan(const GemmArgs& g) {
     GemmPlan p{};
     const bool direct = g_direct > 0 && g_force_cfg < 0;
-    const int fs = g_force_split;
+    const int fs = g.one_range ? 1 : g_force_split;          // (one_range: the direct kernels keep one k range too)
     if (g.nbatch > 1) {
         // several products of one shape: one launch of the shared-strip direct kernel when it applies (half the split-K
         // factor of a single product for the same 256 workgroups), else one product after the other

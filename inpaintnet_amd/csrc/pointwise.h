@@ -33,6 +33,11 @@ int pw_sample_truncated(const float* W, long ld_w, int rows, int V, float temp, 
 int pw_sample_constrained(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
                           double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
                           long allow_stride, hipStream_t s);
+// The same behind sample.h's forced tokens: forced[row*forced_stride] = the row's forced token, a value outside [0, V) = a free row (null:
+// the call above).  A forced row returns its token whatever the mask and the logits hold; allow may be null (all ones).
+int pw_sample_forced(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
+                     double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
+                     long allow_stride, const int* forced, long forced_stride, hipStream_t s);
 // step_flag (optional device float): non-zero = skip (the ranks' summed chain status); report (optional, 4 host-mapped words
 // zeroed by the caller): [0] = 1 executed, [1] = 1 skipped, [2] = 1 a parameter became non-finite
 int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,

@@ -790,6 +790,66 @@ __global__ void sample_constrained_kernel(const float* __restrict__ W, long ld_w
     }
 }
 
+// The constrained draw behind sample.h's forced tokens (the tick-by-tick path of a forced decoder call; the same rule): forced[row *
+// forced_stride] = the row's forced token, a value outside [0, V) = a free row, which is sample_constrained_kernel's row.  A forced row runs
+// the same mask, truncation and pick (u = 0.0, for the kept total S alone), returns f whatever the mask, the truncation or the logits hold,
+// and reports logp = (s_f - m) - log S: -inf where f is banned or truncated away, NaN where the rule does not apply.  A null `allow` counts
+// as all ones.  One wavefront per row, V <= 64 NV.
+template <int NV>
+__global__ void sample_forced_kernel(const float* __restrict__ W, long ld_w, int rows, int V, float temp,
+                                     const double* __restrict__ uniforms, long u_stride, int top_k, double top_p,
+                                     long long* __restrict__ out, long stride, float* __restrict__ logp, long lp_stride,
+                                     const unsigned long long* __restrict__ allow, long allow_stride,
+                                     const int* __restrict__ forced, long forced_stride) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    const int nw = (V + 63) / 64;
+    for (int row = wave; row < rows; row += nwaves) {
+        const float* w = W + (long)row * ld_w;
+        const int f = forced[(long)row * forced_stride];
+        const bool isf = sample::is_forced(f, V);
+        const double u = isf ? 0.0 : uniforms[(long)row * u_stride];
+        unsigned long long aw[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) aw[j] = j < nw ? (allow ? allow[(long)row * allow_stride + j] : ~0ull) : 0ull;
+        sample::mask_words<NV>(aw, V);
+        float x[NV], sv[NV], m = -INFINITY;
+        bool nan = false;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int v = lane + 64 * j;
+            x[j] = v < V ? w[v] : -INFINITY;
+            sv[j] = v < V ? x[j] * temp : -INFINITY;
+            nan |= sv[j] != sv[j];
+            if (!sample::allowed(aw[j], lane)) x[j] = -INFINITY;
+            m = fmaxf(m, x[j]);
+        }
+        int tok = -1;
+        float lp = __builtin_nanf("");
+        if (!__ballot(nan)) {
+            const float ms = wave_max(sample::mask_scores<NV>(sv, aw, lane));
+            double S;
+            sample::truncate<NV>(sv, ms, top_k, top_p, V, lane);
+            tok = sample::pick<NV>(sv, ms, u, V, lane, S);
+            if (tok >= 0) lp = sample::logp_of(sample::logp_gap<NV>(sv, ms, isf ? f : tok), S);
+        }
+        if (isf) tok = f;
+        if (tok < 0) {
+            m = wave_max(m);
+            int am = kAmNone;
+#pragma unroll
+            for (int j = 0; j < NV; ++j)
+                if (sample::allowed(aw[j], lane)) am = min(am, am_key(x[j], m, lane + 64 * j));
+            tok = am_index(wave_min_i(am));
+        }
+        if (lane == 0) {
+            out[(long)row * stride] = tok;
+            if (logp) logp[(long)row * lp_stride] = lp;
+        }
+    }
+}
+
 __global__ void scale_kernel(float* __restrict__ x, long n, float a) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] *= a;
 }
@@ -1095,6 +1155,21 @@ int pw_sample_constrained(const float* W, long ld_w, int rows, int V, float temp
     ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 20.0 + 8.0 * ((V + 63) / 64)));
     const dim3 grid(grid_for((long)rows * 64, 256, 1024));
 #define PW_ST(NV) hipLaunchKernelGGL(sample_constrained_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride, allow, allow_stride)
+    if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
+#undef PW_ST
+    return ok();
+}
+int pw_sample_forced(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
+                     double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
+                     long allow_stride, const int* forced, long forced_stride, hipStream_t s) {
+    if (!forced) return pw_sample_constrained(W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride, allow,
+                                              allow_stride, s);
+    if (V > 512 || !(top_p > 0.0 && top_p <= 1.0)) return -1;
+    char label[48];
+    std::snprintf(label, sizeof label, "force_sample B%d V%d", rows, V);
+    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 24.0 + (allow ? 8.0 * ((V + 63) / 64) : 0.0)));
+    const dim3 grid(grid_for((long)rows * 64, 256, 1024));
+#define PW_ST(NV) hipLaunchKernelGGL(sample_forced_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride, allow, allow_stride, forced, forced_stride)
     if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
 #undef PW_ST
     return ok();

@@ -204,6 +204,44 @@ __device__ __forceinline__ float mask_scores(float (&s)[NV], const unsigned long
     return ms;
 }
 
+// FORCED TOKENS behind the per-tick constraints (DESIGN.md section 15 has the same text).
+//
+// Layout.
+//  - `forced` is an array of `int32` `[rows][T]`.
+//  - A value `f` with `0 <= f < V` forces that tick.
+//  - Every other value makes the tick free.  The Python surfaces write -1 for a free tick.
+//  - A null `forced` means no tick is forced.
+//
+// At a free tick nothing changes.  Section 13's rule runs as it does today.
+//
+// At a forced tick with token `f`:
+//  1. Scores and truncation.
+//     - Steps 0-2 of section 13 run unchanged on the tick's logits: s = T x in f32, the NaN test, the mask, m, and the top-k / nucleus
+//       truncation.
+//     - S is the kept total.
+//     - The tick's uniform is not used.  The rule is evaluated as with u = 0, so a uniform outside [0, 1) or NaN at a forced tick causes
+//       no fallback.
+//  2. Token.
+//     - The token is `f`.  It is reported in `samples` and fed back into tick t + 1.
+//     - This holds whether or not `f` is allowed or kept, and it holds on a fallback tick too.
+//  3. Log-probability.  logp = (s_f - m) - log S as f32.
+//     - It is exactly -inf when `f` is banned or truncated away (s_f = -inf).
+//     - It is NaN where the rule does not apply: a NaN among s, or m or S not finite.
+//
+// Consequences.  The tests hold each of these exactly.
+//  (a) No forced tick.  A null `forced`, or one with no value in [0, V), gives inet_vae_decoder_sample_cx bit for bit in tokens, logits
+//      and logp.
+//  (b) Replay.  Force, at every tick, the tokens that a sampled, truncated or constrained call returned.  The replay uses the same
+//      temperature, top_k, top_p and mask, and any uniforms at all.  It returns that call's logits and logp bit for bit, with NaN where
+//      that call had NaN.
+//  (c) A banned forced token is still returned and fed back.  Its logp is -inf.
+//  (d) One-bit mask.  A forced tick whose mask has the single bit `f` set has logp exactly 0.0f.
+//  (e) Free ticks of a partly forced call follow section 13's rule on the trajectory behind the forced tokens.
+//
+// How: the callers run mask_scores(), truncate() and pick() (u = 0.0 at a forced tick, for S) as at a free tick, then take tok = f and
+// logp_gap(s, m, f).  The forced word of one (row, tick) is wave-uniform like the mask words.
+__device__ __forceinline__ bool is_forced(int f, int V) { return (unsigned)f < (unsigned)V; }
+
 // The log-probability of the drawn token under the (truncated) distribution pick() drew from is (s_tok - m) - log(S), stored as f32, in
 // two halves: logp_gap() = s_tok - m (f32; tok in [0, V) from pick(); wave-uniform) where the draw is made, logp_of() where there are
 // registers for an f64 logarithm -- decode_b1.hip's pick has none to spare and takes the logarithms behind its last tick.

@@ -284,7 +284,7 @@ size_t vae_decoder_ws_bytes(const inet_vae_config& c, int B, int save) {
 int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long long* target, int teacher_forced,
                     const float* p, const float* mask_beat, const float* mask_tick, float* weights,
                     long long* samples, void* ws, int save, hipStream_t s, uint64_t multinomial_seed, const double* uniforms,
-                    float temperature, int top_k, double top_p, float* logp, const unsigned long long* allow) {
+                    float temperature, int top_k, double top_p, float* logp, const unsigned long long* allow, const int* forced) {
     const int nb = c.beats, G = c.ticks_per_beat, T = nb * G, H = c.dec_hidden, V = c.num_notes, E = c.emb_dim, Z = c.z_dim;
     const long BH = (long)B * H;
     if (nb > 4) return -1;
@@ -293,9 +293,11 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     if (sampled && (teacher_forced || multinomial_seed || V > 512)) return -1;
     // top-k / nucleus truncation in front of every draw, or the draws' log-probabilities wanted: the truncating kernels
     // ... a mask of allowed tokens: the masked kernels, which are truncating ones
-    const bool cons = sampled && allow;
+    // ... forced tokens: the forced kernels, which are masked ones (with or without a mask)
+    const bool force = sampled && forced;
+    const bool cons = sampled && (allow || force);
     const bool trunc = sampled && ((top_k >= 1 && top_k < V) || top_p < 1.0 || logp || cons);
-    if (!sampled && (logp || top_k > 0 || top_p < 1.0 || allow)) return -1;
+    if (!sampled && (logp || top_k > 0 || top_p < 1.0 || allow || forced)) return -1;
     if (!(top_p > 0.0 && top_p <= 1.0)) return -1;
     VaeLayout L(c);
     DecWs w{};
@@ -312,8 +314,8 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     const bool chain_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
     // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
     const bool b1_decode = chain_whole && !save && !mask_tick && w.b1ex && w.b1ex + decode_b1_words(B) == w.sync &&
-                           decode_b1_shape_ok(B, H, V, T, G, sampled + trunc + cons);
-    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, sampled + trunc + cons);   // ... with the beat path inside the same launch
+                           decode_b1_shape_ok(B, H, V, T, G, sampled + trunc + cons + force);
+    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, sampled + trunc + cons + force);   // ... with the beat path inside the same launch
     // (a sampled call: the one fused launch that knows the rule is decode_b1.hip's; every other shape samples tick by tick below)
     const bool fused_whole = chain_whole && (!sampled || b1_decode);
     const bool fused_chunked = fused_shape && !sampled && !fused_whole && B > kDecodeChunk && B % kDecodeChunk == 0 &&
@@ -373,7 +375,15 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
 
     if (!b1_fused) {                                           // (one measure: these eight launches are roles of decode_b1.hip's launch)
         // ---- beat RNN (forward_beat_rnn, decoder.py:455-471) ----
-        INET_TRY(linear_fwd(z, Z, p + L.zb_w, Z, p + L.zb_b, w.hb0, 2L * H, B, 2 * H, Z, EPI_SELU, s));
+        // A sampled call reproduces itself bit for bit, so that forcing its tokens replays it (sample.h): its
+        // products keep one k range per tile.  (Without that the four-beat products of 9 to 63 rows other than 32 are split over K with
+        // f32 atomics, and two identical calls differ in the last bits of their logits.)
+        const int one_range = sampled ? 1 : 0;
+        {
+            GemmArgs g = linear_fwd_args(z, Z, p + L.zb_w, Z, p + L.zb_b, w.hb0, 2L * H, B, 2 * H, Z, EPI_SELU);
+            g.one_range = one_range;
+            INET_TRY(launch_gemm(g, s));
+        }
         DirFwd d{};
         d.W_hh = p + L.beat[0].w_hh; d.b_hh = p + L.beat[0].b_hh;
         d.gvec = w.gvec0;
@@ -385,7 +395,11 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
         if (beats_chained) { d.sync = w.sync; d.sync_prezeroed = 1; }   // 4 steps in one launch (8 groups of 32 rows at B = 256)
         INET_TRY(gru_layer_fwd(H, B, nb, 1, &d, s));
         const float* xb = mask_beat ? w.beat0m : w.beat0;
-        INET_TRY(linear_fwd(xb, H, p + L.beat[1].w_ih, H, p + L.beat[1].b_ih, w.gi1b, 3L * H, nb * B, 3 * H, H, EPI_NONE, s));
+        {
+            GemmArgs g = linear_fwd_args(xb, H, p + L.beat[1].w_ih, H, p + L.beat[1].b_ih, w.gi1b, 3L * H, nb * B, 3 * H, H, EPI_NONE);
+            g.one_range = one_range;
+            INET_TRY(launch_gemm(g, s));
+        }
         d = DirFwd{};
         d.W_hh = p + L.beat[1].w_hh; d.b_hh = p + L.beat[1].b_hh;
         d.gi = w.gi1b; d.gi_ld = 3L * H; d.gi_ts = 3 * BH;
@@ -398,14 +412,19 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
 
         // ---- per-beat constants for the tick RNN (decoder.py:494-495), all 4 beats at once ----
         {
-            const GemmArgs bt[2] = {linear_fwd_args(w.beat_out, H, p + L.bh_w, H, p + L.bh_b, w.ht0, 2L * H, nb * B, 2 * H, H, EPI_SELU),
-                                    linear_fwd_args(w.beat_out, H, p + L.bi_w, H, p + L.bi_b, w.c_all, H, nb * B, H, H, EPI_SELU)};
+            GemmArgs bt[2] = {linear_fwd_args(w.beat_out, H, p + L.bh_w, H, p + L.bh_b, w.ht0, 2L * H, nb * B, 2 * H, H, EPI_SELU),
+                              linear_fwd_args(w.beat_out, H, p + L.bi_w, H, p + L.bi_b, w.c_all, H, nb * B, H, H, EPI_SELU)};
+            bt[0].one_range = bt[1].one_range = one_range;
             INET_TRY(launch_gemm_group(bt, 2, s));
         }
         if (pk && !ticks_chained && !fused_chunked && !b1_decode)  // packed initial tick hiddens: [layer][beat]
             for (int l = 0; l < 2; ++l)
                 INET_TRY(pw_pack_frag(w.ht0 + (long)l * H, 2L * H, B, H, w.ht0pk + (long)l * nb * pkh, 0, nb, (long)B * 2 * H, pkh, s));
-        INET_TRY(linear_fwd(w.c_all, H, wih0 + E, ldw0, nullptr, w.cgi, 3L * H, nb * B, 3 * H, H, EPI_NONE, s));
+        {
+            GemmArgs g = linear_fwd_args(w.c_all, H, wih0 + E, ldw0, nullptr, w.cgi, 3L * H, nb * B, 3 * H, H, EPI_NONE);
+            g.one_range = one_range;
+            INET_TRY(launch_gemm(g, s));
+        }
     }
 
     // ---- tick RNN (forward_tick_rnn, decoder.py:473-529) ----
@@ -527,7 +546,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
             a.weights = weights + (long)r0 * T * V; a.samples = samples + (long)r0 * T;
             a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0;   // (later chunks: the launcher zeroes the area)
             a.uniforms = uniforms; a.temperature = temperature;                 // (sampled: one whole launch, never chunks)
-            a.trunc = trunc; a.top_k = top_k; a.top_p = top_p; a.logp = logp; a.allow = cons ? allow : nullptr;
+            a.trunc = trunc; a.top_k = top_k; a.top_p = top_p; a.logp = logp; a.allow = cons ? allow : nullptr; a.forced = force ? forced : nullptr;
             if (mask_tick) { a.mask = mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
             if (save) {
                 a.sv0 = w.svt0 + (long)r0 * H; a.sv1 = w.svt1 + (long)r0 * H; a.sv_stride = (long)T * BH;
@@ -585,6 +604,10 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
                                 (long)T * V, B, V, H, EPI_RELU, s));
             if (draw) INET_TRY(pw_sample_multinomial(weights + (long)t * V, (long)T * V, B, V, samples + t, T,
                                                      multinomial_seed, (uint64_t)t * B, s));
+            else if (force) INET_TRY(pw_sample_forced(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
+                                                      samples + t, T, logp ? logp + t : nullptr, T,
+                                                      allow ? allow + (long)t * ((V + 63) / 64) : nullptr, (long)T * ((V + 63) / 64),
+                                                      forced + t, T, s));
             else if (cons) INET_TRY(pw_sample_constrained(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
                                                          samples + t, T, logp ? logp + t : nullptr, T, allow + (long)t * ((V + 63) / 64),
                                                          (long)T * ((V + 63) / 64), s));

@@ -199,14 +199,15 @@ class LatentRNN(Model):
         return torch.zeros(self.num_rnn_layers * self.rnn_num_direction, batch_size, self.rnn_hidden_size,
                            device=self.flat.device)
 
-    def _decode(self, z2d, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
+    def _decode(self, z2d, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None, forced=None):
         """frozen decoder, train=False (latent_rnn.py:238): dropout still follows module.training (the quirk)."""
         dummy = torch.zeros(z2d.shape[0], self.vae_model.num_ticks_per_measure, device=z2d.device)
         return self.vae_model.decoder(z2d, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
-                                      allowed=allowed)
+                                      allowed=allowed, **({} if forced is None else {"forced": forced}))
 
     def forward(self, past_context, future_context, target, measures_to_generate, train=True, eps=None,
-                teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
+                teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None,
+                forced=None):
         """-> weights (B,nt,24,V), samples (B,1,24*nt), gen_z (B,nt,Z)   (latent_rnn.py:110-159).
         eps: optional (eps_past (B,np,Z), eps_future, eps_target) injection; eps_ar: list of (B,Z) for the
         free-running auto-regressive path.
@@ -218,8 +219,25 @@ class LatentRNN(Model):
         (HierarchicalDecoder.forward); such a call leaves self.last_logp (B, n_target, 24), the drawn tokens' log-probabilities under
         the truncated distribution (NaN where a tick took the argmax), every other call leaves it None.
         allowed (bool (B, n_target, 24, V); inference only): the tokens each generated tick may return (HierarchicalDecoder.forward),
-        with or without a temperature; the auto-regressive path hands each measure's slice to its decoder call."""
+        with or without a temperature; the auto-regressive path hands each measure's slice to its decoder call.
+        forced (an int tensor (B, n_target, 24), -1 = a free tick; inference with a temperature only): the tokens the generated ticks
+        return, feed back and score instead of drawing (HierarchicalDecoder.forward); the auto-regressive path
+        hands each measure's slice to its decoder call and re-encodes the forced tokens as it does the drawn ones.  Such a call
+        always leaves self.last_logp."""
         batch_size, _, measure_seq_len = past_context.size()
+        if forced is not None:
+            if train:
+                raise ValueError("forced tokens are an inference call (train=False)")
+            if temperature is None:
+                raise ValueError("forced tokens need a temperature")
+            forced = torch.as_tensor(forced)
+            if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool or \
+                    tuple(forced.shape) != (batch_size, measures_to_generate, measure_seq_len):
+                raise ValueError(f"forced must be an int tensor of shape {(batch_size, measures_to_generate, measure_seq_len)}, got "
+                                 f"{forced.dtype} {tuple(forced.shape)}")
+            V = int(self.vae_model.decoder.cfg.num_notes)
+            if forced.numel() and bool(((forced < -1) | (forced >= V)).any()):
+                raise ValueError(f"forced: token indices in [0, {V}), or -1 for a free tick")
         if allowed is not None:
             if train:
                 raise ValueError("token constraints are an inference call (train=False)")
@@ -286,12 +304,12 @@ class LatentRNN(Model):
             seed = zp[:, -1, :].unsqueeze(1)
         return self.forward_generation(comb_context, measures_to_generate, seed, measure_seq_len, teacher_forcing,
                                        eps_ar=eps_ar, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
-                                       allowed=allowed)
+                                       allowed=allowed, forced=forced)
 
     def forward_generation(self, context_vector, measures_to_gen, seed, measure_seq_len, teacher_forcing=False,
-                           eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
+                           eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None, forced=None):
         """latent_rnn.py:211-263; temperature / uniforms (B, measures_to_gen, 24) / top_k / top_p / self.last_logp / allowed (B,
-        measures_to_gen, 24, V): see forward"""
+        measures_to_gen, 24, V) / forced (B, measures_to_gen, 24): see forward"""
         if temperature is None and (top_k is not None or top_p is not None):
             raise ValueError("top_k / top_p without a temperature")
         batch_size = context_vector.size(1)
@@ -309,7 +327,8 @@ class LatentRNN(Model):
             # rows ordered (b, measure): all measures in one call
             w, s = self._decode(z2d, temperature, uniforms.reshape(batch_size * measures_to_gen, -1) if uniforms is not None else None,
                                 top_k, top_p, allowed.reshape((batch_size * measures_to_gen,) + tuple(allowed.shape[2:]))
-                                if allowed is not None else None)
+                                if allowed is not None else None,
+                                forced.reshape(batch_size * measures_to_gen, -1) if forced is not None else None)
             lp = self.vae_model.decoder.last_logp
             self.last_logp = lp.view(batch_size, measures_to_gen, measure_seq_len) if lp is not None else None
             weights = w.view(batch_size, measures_to_gen, measure_seq_len, -1)
@@ -324,7 +343,7 @@ class LatentRNN(Model):
                                     "generation_linear.weight", "generation_linear.bias")
             z_out.append(gen_z.view(batch_size, 1, -1))
             w, s = self._decode(gen_z, temperature, uniforms[:, i] if uniforms is not None else None, top_k, top_p,
-                                allowed[:, i] if allowed is not None else None)
+                                allowed[:, i] if allowed is not None else None, forced[:, i] if forced is not None else None)
             logps.append(self.vae_model.decoder.last_logp)
             samples.append(s)
             weights.append(w.unsqueeze(1))

@@ -7,6 +7,7 @@ the dataset offers it, otherwise the score slots of the return tuple are None.  
 argument of LatentRNN.forward (latent_rnn_tester.py:231-236, a TypeError as written); here forward() accepts
 target=None.
 """
+import math
 import os
 
 import torch
@@ -35,7 +36,7 @@ class LatentRNNTester(object):
         return fn(tensor.cpu()) if fn is not None else None
 
     def generate(self, tensor_past, tensor_future, tensor_target, num_target_measures, eval=False, temperature=None,
-                 num_variations=1, top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None):
+                 num_variations=1, top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None, score_fixed=False):
         """-> (gen_score | None, gen_score_tensor (B, n_past + n_target + n_future, 24), original_score | None)
         (latent_rnn_tester.py:197-266)
         temperature (a finite float): `num_variations` fillings of the same gap -- the (one-row) contexts are expanded to that many
@@ -53,7 +54,12 @@ class LatentRNNTester(object):
         fixed tick wins over a ban.  Both are applied inside the decode launch (HierarchicalDecoder.forward's `allowed`), so the notes
         behind a constrained tick are generated from it.  ValueError for an index outside [0, V) (fixed: other than -1) or a ban of
         the whole vocabulary.  With a temperature last_logp is as above (a fixed tick adds exactly 0); without one the single filling
-        is the argmax over the allowed tokens and last_logp stays None."""
+        is the argmax over the allowed tokens and last_logp stays None.
+        score_fixed=True (needs a temperature: ValueError without): the fixed ticks become FORCED ticks with an all-ones mask
+        (HierarchicalDecoder.forward's `forced`) -- a fixed tick still wins over a ban -- and last_logp then
+        includes what the model thinks of the kept notes instead of 0 for each of them.  The default is the behaviour above."""
+        if score_fixed and temperature is None:
+            raise ValueError("score_fixed needs a temperature")
         if temperature is None and (top_k is not None or top_p is not None):
             raise ValueError("top_k / top_p need a temperature")
         if top_p is not None and not (0.0 < float(top_p) <= 1.0):
@@ -66,6 +72,12 @@ class LatentRNNTester(object):
         elif num_target_measures is None:
             raise ValueError
         allowed = self._allowed(banned_tokens, fixed_tokens, num_target_measures)      # (the argument errors, before any work)
+        forced = None
+        if score_fixed and fixed_tokens is not None:
+            forced = torch.as_tensor(fixed_tokens).cpu().long()                        # (checked by _allowed above)
+            allowed = self._allowed(banned_tokens, None, num_target_measures)
+            if allowed is not None:                                                    # a fixed tick wins over a ban: its mask is all ones
+                allowed = allowed | (forced >= 0).unsqueeze(-1)
         if tensor_past is None:
             tensor_past = self.create_empty_context('start')
         if tensor_future is None:
@@ -84,10 +96,13 @@ class LatentRNNTester(object):
                 tensor_target = tensor_target.expand(num_variations, -1, -1).contiguous()
         if allowed is not None:                                     # every row -- every variation -- under the same constraints
             allowed = allowed.unsqueeze(0).expand(tensor_past.size(0), -1, -1, -1).contiguous()
+        extra = {} if allowed is None else {"allowed": allowed}
+        if forced is not None:
+            extra["forced"] = forced.unsqueeze(0).expand(tensor_past.size(0), -1, -1).contiguous()
         with torch.no_grad():
             weights, gen_target, _ = self.model(past_context=tensor_past, future_context=tensor_future, target=None,
                                                 measures_to_generate=num_target_measures, train=False, temperature=temperature,
-                                                top_k=top_k, top_p=top_p, **({} if allowed is None else {"allowed": allowed}))
+                                                top_k=top_k, top_p=top_p, **extra)
         self.last_weights = weights
         lp = getattr(self.model, "last_logp", None)
         self.last_logp = lp.sum(-1) if lp is not None else None
@@ -105,6 +120,52 @@ class LatentRNNTester(object):
         if tensor_target is not None:
             original = self._to_score(torch.cat((tensor_past, tensor_target, tensor_future), 1))
         return self._to_score(gen_score_tensor), gen_score_tensor, original
+
+    def score(self, tensor_past, tensor_future, fillings, temperature=1.0, top_k=None, top_p=None, banned_tokens=None):
+        """What the model thinks of given fillings of one gap -> (N, n_target): per measure the sum of its 24 tokens' log-probabilities
+        under softmax(temperature * weights) behind the same ban and top-k / nucleus truncation a generate() call with these
+        arguments draws from.  fillings: an int tensor (N, n_target, 24) of token indices in [0, V) -- the
+        user's own filling, the original measures, another model's, or generate()'s own gen_score_tensor slice -- for ONE context
+        (tensor_past / tensor_future of batch size 1, None: the empty contexts of generate()), which is expanded to N rows as generate
+        expands it for variations.  Every tick is forced: the tokens are fed back one by one inside the decode launch (up to
+        sixteen decoder rows are one register-resident launch), the uniforms are zeros and np.random is not touched.  -inf (a banned or
+        truncated token) and NaN (a tick outside the rule) propagate into the sums.  Scoring generate()'s fillings with its
+        temperature, top_k, top_p and bans returns its last_logp bit for bit.  Leaves self.last_tick_logp (N, n_target, 24) and
+        self.last_weights (N, n_target, 24, V)."""
+        if temperature is None or not math.isfinite(float(temperature)):
+            raise ValueError(f"score: temperature {temperature!r} must be a finite float")
+        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
+            raise ValueError(f"top_p {top_p!r} outside (0, 1]")
+        ops._top_k(top_k)                                          # (ValueError for a top_k that is no integer)
+        V, L = int(self.model.vae_model.decoder.cfg.num_notes), self.measure_seq_len
+        fillings = torch.as_tensor(fillings)
+        if fillings.is_floating_point() or fillings.is_complex() or fillings.dtype == torch.bool or fillings.dim() != 3 or \
+                fillings.size(0) < 1 or fillings.size(1) < 1 or fillings.size(2) != L:
+            raise ValueError(f"fillings must be an int tensor of shape (N, n_target, {L}), got {fillings.dtype} {tuple(fillings.shape)}")
+        fillings = fillings.cpu().long()
+        if bool(((fillings < 0) | (fillings >= V)).any()):
+            raise ValueError(f"fillings: token indices in [0, {V})")
+        n, n_target = fillings.size(0), fillings.size(1)
+        allowed = self._allowed(banned_tokens, None, n_target)
+        if tensor_past is None:
+            tensor_past = self.create_empty_context('start')
+        if tensor_future is None:
+            tensor_future = self.create_empty_context('end')
+        if tensor_past.size(0) != 1 or tensor_future.size(0) != 1:
+            raise ValueError("fillings are scored for one context (batch size 1)")
+        tensor_past = tensor_past.expand(n, -1, -1).contiguous()
+        tensor_future = tensor_future.expand(n, -1, -1).contiguous()
+        extra = {} if allowed is None else {"allowed": allowed.unsqueeze(0).expand(n, -1, -1, -1).contiguous()}
+        with torch.no_grad():
+            weights, _, _ = self.model(past_context=tensor_past, future_context=tensor_future, target=None,
+                                       measures_to_generate=n_target, train=False, temperature=float(temperature),
+                                       uniforms=torch.zeros(n, n_target, L, dtype=torch.float64), top_k=top_k, top_p=top_p,
+                                       forced=fillings, **extra)
+        self.last_weights = weights
+        self.last_tick_logp = self.model.last_logp
+        torch.cuda.synchronize()
+        ops.check_chains("LatentRNNTester.score")                      # persistent kernels: never hand back results of a failed launch
+        return self.last_tick_logp.sum(-1)
 
     def _allowed(self, banned_tokens, fixed_tokens, n_target):
         """generate()'s constraints as one row of the model's mask: bool (n_target, 24, V) on the host, or None without constraints"""

@@ -68,12 +68,12 @@ class _EncoderFn(ops.TrackedFunction):
 class _DecoderFn(ops.TrackedFunction):
     @staticmethod
     def forward(ctx, z, flat, dec, target, teacher_forced, mask_beat, mask_tick, multinomial_seed=0, temperature=None,
-                uniforms=None, top_k=None, top_p=None, logp=None, allowed=None):
+                uniforms=None, top_k=None, top_p=None, logp=None, allowed=None, forced=None):
         need = ops.outer_grad() and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         weights, samples, ws = ops.decoder_fwd(dec.cfg, z.contiguous(), target, teacher_forced, flat, mask_beat,
                                                mask_tick, save=need, multinomial_seed=multinomial_seed,
                                                temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, logp=logp,
-                                               allowed=allowed)
+                                               allowed=allowed, forced=forced)
         ctx.dec, ctx.ws, ctx.mb, ctx.mt = dec, ws, mask_beat, mask_tick
         if getattr(dec, "keep_ws", False):         # test hook: lets a parity test read intermediates (ops.ws_field)
             dec.last_ws = ws
@@ -89,7 +89,7 @@ class _DecoderFn(ops.TrackedFunction):
         dec = ctx.dec
         if dweights is None:                            # nothing downstream depends on the weights
             ctx.ws = None
-            return (None,) * 14
+            return (None,) * 15
         weights, samples = ctx.saved_tensors
         grads = dec.owner.grad if dec.owner.trainable else None
         dz = ops.decoder_bwd(dec.cfg, dweights.contiguous(), weights, samples, dec.owner.flat, grads, ctx.mb, ctx.mt,
@@ -100,7 +100,7 @@ class _DecoderFn(ops.TrackedFunction):
             if dp.world_size() > 1:
                 # behind the decoder's leaf GEMMs on the side streams, without holding up the encoder's backward
                 dp.start_bucket(grads, dec.owner.decoder_arena_start, grads.numel(), join_side=True)
-        return (dz,) + (None,) * 13
+        return (dz,) + (None,) * 14
 
 
 class _ReparamFn(torch.autograd.Function):
@@ -260,7 +260,7 @@ class HierarchicalDecoder(torch.nn.Module):
                f')'
 
     def forward(self, z, score_tensor, train, masks=None, teacher_forced=None, temperature=None, uniforms=None, top_k=None,
-                top_p=None, allowed=None):
+                top_p=None, allowed=None, forced=None):
         """z (B,Z), score_tensor (B,24) -> weights (B,24,V), samples (B,1,24)   (decoder.py:412-453).
         One Bernoulli(0.5) teacher-forcing coin per call when train=True (decoder.py:431-434); it can be
         injected with `teacher_forced=`.
@@ -278,8 +278,25 @@ class HierarchicalDecoder(torch.nn.Module):
         each (row, tick) may return -- a ban clears entries, a note to keep is a tick with one entry set.  The mask is applied inside
         the launch, in front of the truncation (csrc/sample.h): the token fed back into tick t + 1 is the
         constrained one, a fixed tick's logp is exactly 0.  ValueError for a tick with nothing allowed.  Without a temperature the call
-        runs as temperature 1, top_k = 1 with zero uniforms -- the argmax over the allowed tokens -- and leaves last_logp None."""
+        runs as temperature 1, top_k = 1 with zero uniforms -- the argmax over the allowed tokens -- and leaves last_logp None.
+        forced (an int tensor (B,24), host or device, -1 = a free tick; inference with a temperature only, ignored by a call whose
+        `teacher_forced=True` was injected): the token a tick returns and feeds back instead of drawing one -- whether or not it is
+        allowed or kept -- with its log-probability under the masked and truncated distribution a draw would have used (csrc/sample.h,
+        DESIGN.md section 15): -inf for a banned or truncated token, NaN where the rule does not apply.  A forced tick does not use its
+        uniform.  Every tick forced scores a given measure, the first ticks forced continue a prefix.  ValueError for a wrong shape or
+        dtype or a value outside [-1, V).  A forced call always leaves last_logp (B,24)."""
         T = self.cfg.beats * self.cfg.ticks_per_beat
+        if forced is not None:
+            if train:
+                raise ValueError("forced tokens are an inference call (train=False)")
+            if temperature is None:
+                raise ValueError("forced tokens need a temperature")
+            forced = torch.as_tensor(forced)
+            if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool or tuple(forced.shape) != (z.size(0), T):
+                raise ValueError(f"forced must be an int tensor of shape {(z.size(0), T)}, got {forced.dtype} {tuple(forced.shape)}")
+            if forced.numel() and bool(((forced < -1) | (forced >= self.cfg.num_notes)).any()):
+                raise ValueError(f"forced: token indices in [0, {self.cfg.num_notes}), or -1 for a free tick")
+            forced = forced.to(torch.int32)
         if allowed is not None:
             if train:
                 raise ValueError("token constraints are an inference call (train=False)")
@@ -342,10 +359,11 @@ class HierarchicalDecoder(torch.nn.Module):
             if uniforms is None:
                 uniforms = torch.from_numpy(np.random.random_sample((batch_size, T)))
             u = uniforms.to(z.device).contiguous()
-            if top_k is not None or top_p is not None or allowed is not None:
+            if top_k is not None or top_p is not None or allowed is not None or forced is not None:
                 logp = torch.empty(batch_size, T, dtype=torch.float32, device=z.device)
                 out = _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u,
-                                      top_k, top_p, logp, allowed.to(z.device).contiguous() if allowed is not None else None)
+                                      top_k, top_p, logp, allowed.to(z.device).contiguous() if allowed is not None else None,
+                                      *((forced.to(z.device).contiguous(),) if forced is not None else ()))
                 self.last_logp = logp
                 return out
             return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u)
@@ -452,13 +470,15 @@ class MeasureVAE(Model):
                                         teacher_forced=teacher_forced, masks=dec_masks)
         return weights, samples, z_dist, prior_dist, z_tilde, z_prior
 
-    def decode(self, z, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None):
+    def decode(self, z, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None, forced=None):
         """z (B,Z) -> (weights (B,24,V), samples (B,1,24)): the free-running decoder alone (what VAETester.decode_mid_point does with
         a latent), by the argmax or -- temperature set -- drawn from softmax(temperature * weights), behind top-k / nucleus truncation
         with top_k / top_p (HierarchicalDecoder.forward; the draws' log-probabilities: self.decoder.last_logp); allowed (bool
-        (B,24,V)): the tokens each tick may return, with or without a temperature (HierarchicalDecoder.forward)."""
+        (B,24,V)): the tokens each tick may return, with or without a temperature (HierarchicalDecoder.forward); forced (int (B,24), -1 = a
+        free tick; with a temperature): the tokens to return, feed back and score instead of drawing (HierarchicalDecoder.forward)."""
         dummy = torch.zeros(z.shape[0], self.num_ticks_per_measure, device=z.device)
-        return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, allowed=allowed)
+        return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, allowed=allowed,
+                            **({} if forced is None else {"forced": forced}))
 
     def _standard_normal(self, like):
         """N(0, 1) of the latent's shape (measure_vae.py:122-125): the constant loc / scale tensors are built once."""

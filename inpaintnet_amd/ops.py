@@ -258,7 +258,8 @@ def decoder_ws(cfg, B, save, device):
 
 
 def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tick=None, save=False, ws=None,
-                multinomial_seed=0, temperature=None, uniforms=None, top_k=None, top_p=None, logp=None, allowed=None):
+                multinomial_seed=0, temperature=None, uniforms=None, top_k=None, top_p=None, logp=None, allowed=None,
+                forced=None):
     """z [B,Z] -> weights [B,T,V], samples [B,1,T] int64, ws.  multinomial_seed != 0: the fed-back tokens are drawn from
     softmax(weights) (decoder.py:506-509) instead of the argmax.  temperature + uniforms ([B,T] float64 on the device, one uniform
     per row and tick): inet_vae_decoder_sample -- a free-running call whose tokens are drawn from softmax(temperature * weights) by
@@ -266,11 +267,14 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
     top-k / nucleus truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off, else in (0, 1)), and logp, a contiguous float32
     [B,T] device tensor, receives the drawn tokens' log-probabilities under the truncated distribution (NaN where a tick took the argmax).
     allowed (with a temperature only): inet_vae_decoder_sample_cx -- pack_allowed()'s words [B,T,ceil(V/64)], int64, contiguous, on the
-    device: the tokens every (row, tick) may return, applied in front of the truncation inside the launch (csrc/sample.h's rule)."""
+    device: the tokens every (row, tick) may return, applied in front of the truncation inside the launch (csrc/sample.h's rule).
+    forced (with a temperature only): inet_vae_decoder_sample_fx -- int32 [B,T], contiguous, on the device: the token every (row, tick)
+    returns and feeds back, -1 (any value outside [0, V)) for a free tick; its logp is taken under the masked and truncated
+    distribution (-inf for a banned or truncated token), with or without `allowed`."""
     if (temperature is None) != (uniforms is None):
         raise ValueError("decoder_fwd: temperature and uniforms go together")
-    if temperature is None and (top_k is not None or top_p is not None or logp is not None or allowed is not None):
-        raise ValueError("decoder_fwd: top_k / top_p / logp / allowed without a temperature")
+    if temperature is None and (top_k is not None or top_p is not None or logp is not None or allowed is not None or forced is not None):
+        raise ValueError("decoder_fwd: top_k / top_p / logp / allowed / forced without a temperature")
     if top_p is not None and not (0.0 < float(top_p) <= 1.0):
         raise ValueError(f"decoder_fwd: top_p {top_p!r} outside (0, 1]")
     _f32c(z); _f32c(params)
@@ -289,12 +293,22 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
             nw = (cfg.num_notes + 63) // 64
             if not (allowed.is_cuda and allowed.dtype == torch.int64 and allowed.is_contiguous() and tuple(allowed.shape) == (B, T, nw)):
                 raise ValueError(f"decoder_fwd: allowed must be pack_allowed()'s contiguous int64 device tensor of shape {(B, T, nw)}")
+        if forced is not None and not (forced.is_cuda and forced.dtype == torch.int32 and forced.is_contiguous() and tuple(forced.shape) == (B, T)):
+            raise ValueError(f"decoder_fwd: forced must be a contiguous int32 device tensor of shape {(B, T)}")
     if target is not None:
         _i64c(target)
     if ws is None:
         ws = decoder_ws(cfg, B, save, z.device)
     weights = torch.empty(B, T, cfg.num_notes, dtype=torch.float32, device=z.device)
     samples = torch.empty(B, 1, T, dtype=torch.int64, device=z.device)
+    if temperature is not None and forced is not None:
+        check(_lib.lib().inet_vae_decoder_sample_fx(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
+                                                    ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
+                                                    _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(logp), ptr(allowed),
+                                                    ptr(forced), stream_ptr()),
+              "inet_vae_decoder_sample_fx")
+        _hold(uniforms, logp, allowed, forced)
+        return weights, samples, ws
     if temperature is not None and allowed is not None:
         check(_lib.lib().inet_vae_decoder_sample_cx(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
                                                     ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
@@ -411,11 +425,13 @@ def pack_allowed(allowed):
     return torch.from_numpy(words).to(dev)
 
 
-def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, want_logp=True, allowed=None):
+def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, want_logp=True, allowed=None, forced=None):
     """inet_sample_truncated: sample_temperature() behind csrc/sample.h's top-k / nucleus truncation (top_k None, <= 0 or >= V: off;
     top_p None or 1: off, else in (0, 1)) -> (tokens [rows] int64, logp [rows] float32: the drawn tokens' log-probabilities under
     the truncated distribution, NaN where a row took the argmax rule; None with want_logp=False).  allowed: inet_sample_constrained --
-    pack_allowed()'s words [rows, ceil(V / 64)] (int64 on the device, any row stride): the tokens each row may return."""
+    pack_allowed()'s words [rows, ceil(V / 64)] (int64 on the device, any row stride): the tokens each row may return.  forced: inet_sample_forced -- int32 [rows] on the
+    device: the token each row returns whatever its mask and logits hold, -1 for a free row; its logp is taken under the masked and
+    truncated distribution."""
     rows, V = weights2d.shape
     assert weights2d.stride(1) == 1 and weights2d.dtype == torch.float32
     assert uniforms.is_cuda and uniforms.dtype == torch.float64 and tuple(uniforms.shape) == (rows,)
@@ -424,6 +440,15 @@ def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, w
     if allowed is not None:
         if not (allowed.is_cuda and allowed.dtype == torch.int64 and tuple(allowed.shape) == (rows, (V + 63) // 64) and allowed.stride(1) == 1):
             raise ValueError(f"sample_truncated: allowed must be pack_allowed()'s int64 device tensor of shape {(rows, (V + 63) // 64)}")
+    if forced is not None:
+        if not (forced.is_cuda and forced.dtype == torch.int32 and tuple(forced.shape) == (rows,)):
+            raise ValueError(f"sample_truncated: forced must be an int32 device tensor of shape {(rows,)}")
+        check(_lib.lib().inet_sample_forced(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
+                                            uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
+                                            ptr(logp), 1, ptr(allowed), allowed.stride(0) if allowed is not None else 0, ptr(forced),
+                                            forced.stride(0), stream_ptr()), "inet_sample_forced")
+        return out, logp
+    if allowed is not None:
         check(_lib.lib().inet_sample_constrained(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
                                                  uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
                                                  ptr(logp), 1, ptr(allowed), allowed.stride(0), stream_ptr()), "inet_sample_constrained")

@@ -5,7 +5,10 @@ and 16, five rounds of 300 calls each (median and range per call).
 the draws' log-probabilities), and its cost per tick over the sampled decode.
 --mask (with --temperature and --top-k / --top-p): a second line per batch size, the constrained decode under the every-plan mask of
 tests/decoder_constraint_ref.py (every fourth tick fixed, a fifth of the tokens banned elsewhere) next to the truncated decode of the
-same build, both at the ops level with the mask words packed once."""
+same build, both at the ops level with the mask words packed once.
+--forced (with --temperature and --top-k / --top-p): one more line per batch size, the all-forced call (every tick forced to a token
+drawn once on the host: a scoring call) next to the constrained call of the same build under the same every-plan mask, both at the ops
+level."""
 import os, sys
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -56,6 +59,18 @@ if "--temperature" in sys.argv:
             trunc, text = rounds(lambda: ops.decoder_fwd(vae.cfg, z, None, False, vae.flat, **kw))
             cons, ctext = rounds(lambda: ops.decoder_fwd(vae.cfg, z, None, False, vae.flat, allowed=words, **kw))
             print(f"b = {b}: ops level, truncated {text}, constrained {ctext} ({1e3 * (cons - trunc) / 24:+.2f} us per tick), "
+                  f"chain status {ops.chain_status()}")
+        if "--forced" in sys.argv and (top_k is not None or top_p is not None):
+            V = vae.num_notes
+            r, t, v = torch.meshgrid(torch.arange(b), torch.arange(24), torch.arange(V), indexing="ij")
+            allow = torch.where((r + t) % 4 == 0, v == (7 * r + 3 * t + 1) % V, (v + t + r) % 5 != 0)
+            words = ops.pack_allowed(allow).cuda()
+            forced = torch.randint(0, V, (b, 24), dtype=torch.int32).cuda()
+            lp = torch.empty(b, 24, dtype=torch.float32, device="cuda")
+            kw = dict(temperature=temperature, uniforms=u, top_k=top_k, top_p=top_p, logp=lp, allowed=words)
+            cons, ctext = rounds(lambda: ops.decoder_fwd(vae.cfg, z, None, False, vae.flat, **kw))
+            force, ftext = rounds(lambda: ops.decoder_fwd(vae.cfg, z, None, False, vae.flat, forced=forced, **kw))
+            print(f"b = {b}: ops level, constrained {ctext}, all forced {ftext} ({1e3 * (force - cons) / 24:+.2f} us per tick), "
                   f"chain status {ops.chain_status()}")
     sys.exit(0)
 r = bench.decode_latency_extra(wl.model, iters=200)["decoder_eval"]
