@@ -637,6 +637,18 @@ int inet_gemm_group_plan(int n, const int64_t* desc, int32_t* out, double* work,
  * capacity in workgroups (CUs, or INET_CHAIN_CUS), group counters of a sync area}.  0, or -1 for H, B, T <= 0, nprob outside 1..4 or a
  * null output -- nothing is written then. */
 int inet_gru_chain_plan(int H, int B, int T, int nprob, int save, int64_t* out32);
+/* What an LSTM layer of B rows, T steps and hidden size H launches under the options set now (inet_set_option key 4), without a GPU:
+ * the planner every launch site of csrc/lstm.hip reads.  pipeline = 0: inet_lstm_fwd / _bwd (one chain launch over all T steps);
+ * pipeline != 0: inet_lstm2_fwd / _bwd, which run two chain launches side by side -- both must be resident together, so the row
+ * tile is the smallest MS in {1, 2, 4} with 2 * groups * (H / 16) <= chain capacity, and no tile means the pipeline refuses the
+ * shape (inet_lstm2_ok = 0).  out16 = {ok (0: one launch per step; the pipeline: inet_lstm2_fwd returns 1), MS (16 * MS rows per
+ * group), groups, members per group (H / 16), workgroups of one launch that stay for all its steps (groups * members), blocks
+ * launched, forward launches on the tagged hand-off (label suffix " tag"), time steps per launch (pipeline: the chunk), launches per
+ * layer, one backward counter area per chunk (pipeline with at most 16 chunks), chain capacity in workgroups (CUs, or
+ * INET_CHAIN_CUS), launches side by side (1 or 2), group counters of a counter area, words between two group counters, words of a
+ * counter area, 0}; everything in front of the chain capacity is 0 when ok is.  0, or -1 for B, T, H < 1 or a null output -- nothing is
+ * written then. */
+int inet_lstm_chain_plan(int B, int T, int H, int pipeline, int64_t* out16);
 /* Loads every kernel of the library on the CURRENT device (code objects and function objects, which the HIP runtime otherwise
  * builds lazily on the launch path of each kernel's first launch: csrc/preload.hip) without launching anything.  Idempotent per
  * device; returns the number of kernels touched (0 when the device was done already), -2 without a device or on a runtime

@@ -157,6 +157,7 @@ _SIGNATURES = {
     "inet_gemm_plan": (C.c_int, [_I] * 5 + [_L, _L] + [_I] * 4 + [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, _I]),
     "inet_gemm_group_plan": (C.c_int, [_I, C.POINTER(_L), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, _I]),
     "inet_gru_chain_plan": (C.c_int, [_I] * 5 + [C.POINTER(_L)]),
+    "inet_lstm_chain_plan": (C.c_int, [_I] * 4 + [C.POINTER(_L)]),
     "inet_preload": (C.c_int, []),
     "inet_kernel_count": (C.c_int, []),
     "inet_prof_enable": (C.c_int, [_I]),

@@ -678,6 +678,15 @@ int inet_gru_chain_plan(int H, int B, int T, int nprob, int save, int64_t* out32
     return 0;
 }
 
+int inet_lstm_chain_plan(int B, int T, int H, int pipeline, int64_t* out) {
+    if (B < 1 || T < 1 || H < 1 || !out) return -1;
+    const LstmChainPlan p = lstm_chain_plan(B, T, H, pipeline ? 2 : 1);
+    const int64_t v[16] = {p.ok, p.ms, p.groups, p.members, p.workgroups, p.blocks, p.tagged, p.chunk, p.chunks, p.areas, p.capacity,
+                           p.side_by_side, p.max_groups, p.counter_stride, p.counter_words, 0};
+    for (int i = 0; i < 16; ++i) out[i] = v[i];
+    return 0;
+}
+
 int inet_preload(void) { return preload_kernels(); }
 int inet_kernel_count(void) { return preload_kernel_count(); }
 

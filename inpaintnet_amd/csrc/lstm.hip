@@ -17,7 +17,8 @@ namespace {
 
 // sync area: one 256-byte block per group counter (gru_chain.h): 32 forward counters, 32 backward counters, status word
 constexpr int kCounterStride = 64;
-constexpr int kBwdCounters = 32 * kCounterStride;
+constexpr int kMaxGroups = 32;
+constexpr int kBwdCounters = kMaxGroups * kCounterStride;
 constexpr int kStatusWord = 64 * kCounterStride;
 constexpr int kSyncWords = kStatusWord + 4;
 // chunked pipelines (lstm2_seq_*): one backward counter area per chunk behind the base area, zeroed by ONE memset per call
@@ -605,20 +606,10 @@ int launch_lstm_chain_bwd(const LstmChainBwdArgs& a, int ms, int groups, hipStre
                      : launch_chain(lstm_chain_bwd_kernel<4, 32>, a, groups, s);
 }
 
-// rows per group (16 * MS): the smallest tile that still fits the launch on the chip -- a step of these chains is mostly
-// hand-off latency plus the MFMAs of ONE workgroup (B = 32, H = 256: 1.9 of 4.1 us with 32 rows per workgroup), so more,
-// smaller groups shorten every step (AnticipationRNN: two 16-row groups instead of one 32-row group)
-inline int chain_ms(int B, int H) {
-    for (int ms = 1; ms <= 4; ms *= 2) {
-        const int groups = (B + 16 * ms - 1) / (16 * ms);
-        if (groups * (H / 16) <= chain_capacity() && groups <= 32) return ms;
-    }
-    return 4;
-}
-inline bool lstm_chain_ok(int B, int H) {
-    if (!chain_enabled() || (H != 256 && H != 512)) return false;
-    const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
-    return groups * (H / 16) <= chain_capacity() && groups <= 32;   // every workgroup of the launch must be resident at once
+// time steps per chunk of the two-layer pipeline
+int lstm_chunk_steps() {
+    static const int v = [] { const char* e = std::getenv("INET_LSTM_CHUNK"); return e ? std::atoi(e) : 32; }();
+    return v;
 }
 
 int launch_fwd(const LstmFwdArgs& a, hipStream_t s) {
@@ -654,25 +645,60 @@ size_t lstm_carve(int B, int T, int H, int save, void* base, LstmWs& w) {
 // counters and put the previous h into its slot of w.hx.  The kernel sees a sequence of nt steps whose buffers start at the chunk's
 // lowest time index; the saves keep the full sequence's array stride.  (The whole sequence: s_lo = 0, nt = T.)
 int lstm_chain_fwd_steps(int B, int T, int H, const float* gi, const float* W_hh, const float* b_hh, const float* cprev, int reverse,
-                         float* out, LstmWs& w, int save, int s_lo, int nt, bool tagged, int xrot, int phase, hipStream_t s) {
+                         float* out, LstmWs& w, int save, int s_lo, int nt, const LstmChainPlan& p, int xrot, int phase, hipStream_t s) {
     const long BH = (long)B * H, TBH = (long)T * BH;
-    const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
     const long t_lo = reverse ? T - (s_lo + nt) : s_lo;
     LstmChainFwdArgs a{};
-    a.B = B; a.H = H; a.T = nt; a.reverse = reverse; a.members = H / 16;
+    a.B = B; a.H = H; a.T = nt; a.reverse = reverse; a.members = p.members;
     a.gi = gi + t_lo * B * 4 * H; a.W_hh = W_hh; a.b_hh = b_hh; a.c0 = cprev;
     a.out = out + t_lo * BH; a.cseq = w.cseq + t_lo * BH;
     if (save) { a.sv = w.sv + t_lo * BH; a.sv_stride = TBH; }
     a.hx = w.hx; a.counters = w.sync; a.status = chain_status_for(w.sync + kStatusWord); a.xrot = xrot & 7;
     a.phase = phase;
     char label[64];
-    std::snprintf(label, sizeof label, "lstm_chain_fwd ms%d T%d B%d H%d", ms, nt, B, H);
+    std::snprintf(label, sizeof label, "lstm_chain_fwd ms%d T%d B%d H%d%s", p.ms, nt, B, H, p.tagged ? " tag" : "");
     ProfScope prof(PROF_GRU_FWD, 2.0 * nt * B * 4.0 * H * H, s, label,
                    4.0 * (4.0 * H * H + (double)nt * B * H * (4 + 2 + (save ? 6 : 0))));
-    return launch_lstm_chain_fwd(a, ms, groups, tagged, s);
+    return launch_lstm_chain_fwd(a, p.ms, p.groups, p.tagged != 0, s);
 }
 
 }  // namespace
+
+// The one place that decides what an LSTM layer launches (lstm.h).  A chain launch spins on its group's hand-off, so every workgroup
+// of it must be resident at once (chain.h chain_capacity(): one workgroup per CU); the two-layer pipeline runs TWO such launches
+// side by side on two streams, and both must fit together -- with only each of them fitting, two launches dispatched at the same
+// time can each be left without the last members of every group (block ids map to members in the order b >> 3) and spin on the CUs
+// the missing ones need.  Rows per group (16 * ms): the smallest tile with which the launches fit -- a step of these chains is
+// mostly hand-off latency plus the MFMAs of ONE workgroup (B = 32, H = 256: 1.9 of 4.1 us with 32 rows per workgroup), so more,
+// smaller groups shorten every step (AnticipationRNN: two 16-row groups instead of one 32-row group).
+LstmChainPlan lstm_chain_plan(int B, int T, int H, int side_by_side) {
+    LstmChainPlan p{};
+    p.side_by_side = side_by_side;
+    p.capacity = chain_capacity();
+    p.max_groups = kMaxGroups;
+    p.counter_stride = kCounterStride;
+    p.counter_words = kBwdCounters;
+    if (!chain_enabled() || (H != 256 && H != 512) || B < 1 || T < 1 || (side_by_side != 1 && side_by_side != 2)) return p;
+    const int members = H / 16;
+    for (int ms = 1; ms <= 4 && !p.ok; ms *= 2) {
+        const int groups = (B + 16 * ms - 1) / (16 * ms);
+        if (side_by_side * groups * members <= p.capacity && groups <= kMaxGroups) { p.ok = 1; p.ms = ms; p.groups = groups; }
+    }
+    const int CH = lstm_chunk_steps();
+    if (side_by_side == 2 && (CH < 2 || T < 2 * CH)) p.ok = 0;   // a pipeline of one chunk is the layers one after the other
+    if (!p.ok) { p.ms = p.groups = 0; return p; }
+    p.members = members;
+    p.workgroups = p.groups * members;
+    p.blocks = chain::blocks_for(p.groups, members);
+    // tagged hand-off (lstm_chain_fwd_tag_kernel) for the pipeline's forward chunks on the small tiles; the counter protocol
+    // otherwise.  (The same for the backward chain -- 16 fragments per lane to poll, four gate blocks per member to wait for --
+    // measured slower than its counter: 9.34 vs 9.23 ms per AnticipationRNN step with both, 8.87 with the forward chains only.)
+    p.tagged = side_by_side == 2 && H == 256 && p.ms <= 2;
+    p.chunk = side_by_side == 2 ? CH : T;
+    p.chunks = (T + p.chunk - 1) / p.chunk;
+    p.areas = side_by_side == 2 && p.chunks <= kMaxChunks;         // one pre-zeroed backward counter area per chunk (lstm2_seq_bwd)
+    return p;
+}
 
 size_t lstm_ws_bytes(int B, int T, int H, int save) {
     LstmWs w;
@@ -686,10 +712,11 @@ int lstm_seq_fwd(int B, int T, int H, const float* gi, const float* W_hh, const 
     lstm_carve(B, T, H, save, ws, w);
     const long BH = (long)B * H, TBH = (long)T * BH;
     if ((!h0 || !c0) && pw_zero(w.zeros, BH, s) != 0) return -2;
-    if (lstm_chain_ok(B, H)) {
+    const LstmChainPlan p = lstm_chain_plan(B, T, H, 1);
+    if (p.ok) {
         if (hipMemsetAsync(w.sync, 0, kSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
         INET_TRY(pw_pack_frag(h0 ? h0 : w.zeros, H, B, H, w.hx + pk_floats(B, H), 0, 1, 0, 0, s));   // slot 1 = h0
-        INET_TRY(lstm_chain_fwd_steps(B, T, H, gi, W_hh, b_hh, c0 ? c0 : w.zeros, reverse, out, w, save, 0, T, false, 0, 0, s));
+        INET_TRY(lstm_chain_fwd_steps(B, T, H, gi, W_hh, b_hh, c0 ? c0 : w.zeros, reverse, out, w, save, 0, T, p, 0, 0, s));
     } else
     for (int step = 0; step < T; ++step) {
         const int t = reverse ? T - 1 - step : step;
@@ -715,11 +742,9 @@ namespace {
 // lstm_chain_fwd_steps as a chunk of a pipeline: continues from (hprev, cprev) [B,H] (the state after step s_lo - 1: rows of `out` /
 // `cseq`, or zeros), one prologue launch in front.
 int lstm_chunk_fwd(int B, int T, int H, const float* gi, const float* W_hh, const float* b_hh, const float* hprev,
-                   const float* cprev, int reverse, float* out, LstmWs& w, int save, int s_lo, int nt, hipStream_t s, int xrot) {
-    // tagged hand-off (lstm_chain_fwd_tag_kernel) for the small tiles; the counter protocol otherwise.  (The same
-    // for the backward chain -- 16 fragments per lane to poll, four gate blocks per member to wait for -- measured slower
-    // than its counter: 9.34 vs 9.23 ms per AnticipationRNN step with both, 8.87 with the forward chains only.)
-    const bool tagged = H == 256 && chain_ms(B, H) <= 2;
+                   const float* cprev, int reverse, float* out, LstmWs& w, int save, int s_lo, int nt, const LstmChainPlan& p,
+                   hipStream_t s, int xrot) {
+    const bool tagged = p.tagged != 0;
     // counters zeroed; tagged: slots 0, 1 armed and slot 3 = the previous step's h; counter protocol: slot 1 = that h
     // (a tagged chunk behind another chunk of the same layer and call finds all of that in the ring)
     const bool cont = tagged && s_lo > 0;
@@ -729,7 +754,7 @@ int lstm_chunk_fwd(int B, int T, int H, const float* gi, const float* W_hh, cons
                            w.hx + (tagged ? 3 : 1) * pk_floats(B, H));
         if (hipGetLastError() != hipSuccess) return -2;
     }
-    return lstm_chain_fwd_steps(B, T, H, gi, W_hh, b_hh, cprev, reverse, out, w, save, s_lo, nt, tagged, xrot, cont ? s_lo : 0, s);
+    return lstm_chain_fwd_steps(B, T, H, gi, W_hh, b_hh, cprev, reverse, out, w, save, s_lo, nt, p, xrot, cont ? s_lo : 0, s);
 }
 
 // Backward through forward steps [s_lo, s_lo + nt) as one chain launch: (dhT, dcT) = the gradient into the state after
@@ -738,42 +763,34 @@ int lstm_chunk_fwd(int B, int T, int H, const float* gi, const float* W_hh, cons
 // `area` >= 0: the chunk's own pre-zeroed counter area (lstm2_seq_bwd zeroes all of them with one memset); < 0: the base area,
 // zeroed here.
 int lstm_chunk_bwd(int B, int T, int H, const float* dout, const float* dhT, const float* dcT, int reverse, float* dgi,
-                   float* db_ih, float* db_hh, float* dh0, float* dc0, LstmWs& w, int s_lo, int nt, hipStream_t s, int area = -1,
-                   int xrot = 0) {
+                   float* db_ih, float* db_hh, float* dh0, float* dc0, LstmWs& w, int s_lo, int nt, const LstmChainPlan& p,
+                   hipStream_t s, int area = -1, int xrot = 0) {
     const long BH = (long)B * H, TBH = (long)T * BH;
-    const int ms = chain_ms(B, H), groups = (B + 16 * ms - 1) / (16 * ms);
     const long t_lo = reverse ? T - (s_lo + nt) : s_lo;
     unsigned* const counters = area >= 0 ? w.sync + kSyncWords + 60 + (long)area * kBwdCounters : w.sync + kBwdCounters;
     if (area < 0 && hipMemsetAsync(counters, 0, kBwdCounters * sizeof(unsigned), s) != hipSuccess) return -2;
     LstmChainBwdArgs a{};
-    a.B = B; a.H = H; a.T = nt; a.reverse = reverse; a.members = H / 16;
+    a.B = B; a.H = H; a.T = nt; a.reverse = reverse; a.members = p.members;
     a.W_hhT = w.whhT; a.dout = dout ? dout + t_lo * BH : nullptr; a.dhT = dhT; a.dcT = dcT;
     a.sv = w.sv + t_lo * BH; a.sv_stride = TBH;
     a.dg = dgi + t_lo * B * 4 * H; a.dh0 = dh0; a.dc0 = dc0;
     a.db_ih = db_ih; a.db_hh = db_hh;
     a.gx = w.gx; a.counters = counters; a.status = chain_status_for(w.sync + kStatusWord); a.xrot = xrot & 7;
     char label[64];
-    std::snprintf(label, sizeof label, "lstm_chain_bwd ms%d T%d B%d H%d", ms, nt, B, H);
+    std::snprintf(label, sizeof label, "lstm_chain_bwd ms%d T%d B%d H%d", p.ms, nt, B, H);
     ProfScope prof(PROF_GRU_BWD, 2.0 * nt * B * 4.0 * H * H, s, label,
                    4.0 * (4.0 * H * H + (double)nt * B * H * (6 + 4 + 1)));
-    return launch_lstm_chain_bwd(a, ms, groups, s);
+    return launch_lstm_chain_bwd(a, p.ms, p.groups, s);
 }
 
 // XCD the second chain of a two-layer pipeline starts its groups on (the first starts on XCD 0)
 int lstm_pipe_xrot() {
     return 4;
 }
-int lstm_chunk_steps() {
-    static const int v = [] { const char* e = std::getenv("INET_LSTM_CHUNK"); return e ? std::atoi(e) : 32; }();
-    return v;
-}
 
 }  // namespace
 
-bool lstm2_ok(int B, int T, int H) {
-    const int CH = lstm_chunk_steps();
-    return lstm_chain_ok(B, H) && CH >= 2 && T >= 2 * CH;
-}
+bool lstm2_ok(int B, int T, int H) { return lstm_chain_plan(B, T, H, 2).ok != 0; }
 
 // Two stacked LSTM layers (zero initial states) as a pipeline over chunks of time steps: layer 1 needs layer 0's output of
 // step t only, so while layer 0's chain runs chunk c + 1 on the caller's stream, a second stream projects chunk c
@@ -784,8 +801,9 @@ bool lstm2_ok(int B, int T, int H) {
 int lstm2_seq_fwd(int B, int T, int H, const float* gi0, const float* W_hh0, const float* b_hh0, const float* W_ih1,
                   const float* b_ih1, const float* W_hh1, const float* b_hh1, int reverse, float* out0, float* gi1,
                   float* out1, void* ws0, void* ws1, int save, hipStream_t s) {
-    const int CH = lstm_chunk_steps();
-    if (!lstm2_ok(B, T, H)) return 1;
+    const LstmChainPlan p = lstm_chain_plan(B, T, H, 2);
+    if (!p.ok) return 1;
+    const int CH = p.chunk;
     LstmWs w0, w1;
     lstm_carve(B, T, H, save, ws0, w0);
     lstm_carve(B, T, H, save, ws1, w1);
@@ -796,7 +814,7 @@ int lstm2_seq_fwd(int B, int T, int H, const float* gi0, const float* W_hh0, con
         const int nt = T - s_lo < CH ? T - s_lo : CH;
         const long t_lo = reverse ? T - (s_lo + nt) : s_lo, tp = reverse ? t_lo + nt : t_lo - 1;
         INET_TRY(lstm_chunk_fwd(B, T, H, gi0, W_hh0, b_hh0, s_lo ? out0 + tp * BH : w0.zeros, s_lo ? w0.cseq + tp * BH : w0.zeros,
-                                reverse, out0, w0, save, s_lo, nt, s, 0));
+                                reverse, out0, w0, save, s_lo, nt, p, s, 0));
         // the chunk's projection gi1 = out0 W_ih1^T + b_ih1 on a THIRD stream (a side stream forked behind layer 0's chunk), so
         // that layer 1's queue holds nothing but its chain launches: the product (30 us) runs under layer 1's previous chunk
         hipStream_t s3 = side_fork(s);
@@ -804,7 +822,7 @@ int lstm2_seq_fwd(int B, int T, int H, const float* gi0, const float* W_hh0, con
         INET_TRY(linear_fwd(out0 + t_lo * BH, H, W_ih1, H, b_ih1, gi1 + t_lo * B * 4 * H, 4L * H, nt * B, 4 * H, H, EPI_NONE, s3));
         if (s3 != s2) INET_TRY(stream_wait(s2, s3));
         INET_TRY(lstm_chunk_fwd(B, T, H, gi1, W_hh1, b_hh1, s_lo ? out1 + tp * BH : w1.zeros, s_lo ? w1.cseq + tp * BH : w1.zeros,
-                                reverse, out1, w1, save, s_lo, nt, s2, lstm_pipe_xrot()));
+                                reverse, out1, w1, save, s_lo, nt, p, s2, lstm_pipe_xrot()));
     }
     return s2 != s ? twin_join(s) : 0;
 }
@@ -816,8 +834,9 @@ int lstm2_seq_bwd(int B, int T, int H, const float* W_hh0, const float* W_ih1, c
                   const float* out1, const float* dout1, int reverse, float* dgi0, float* dgi1, float* dout0, float* dW_hh0,
                   float* db_ih0, float* db_hh0, float* dW_ih1, float* dW_hh1, float* db_ih1, float* db_hh1, void* ws0,
                   void* ws1, hipStream_t s) {
-    const int CH = lstm_chunk_steps();
-    if (!lstm2_ok(B, T, H)) return 1;
+    const LstmChainPlan p = lstm_chain_plan(B, T, H, 2);
+    if (!p.ok) return 1;
+    const int CH = p.chunk;
     LstmWs w0, w1;
     lstm_carve(B, T, H, 1, ws0, w0);
     lstm_carve(B, T, H, 1, ws1, w1);
@@ -825,8 +844,7 @@ int lstm2_seq_bwd(int B, int T, int H, const float* W_hh0, const float* W_ih1, c
     INET_TRY(pw_transpose(W_hh0, H, w0.whhT, 4L * H, 4 * H, H, s));
     INET_TRY(pw_transpose(W_hh1, H, w1.whhT, 4L * H, 4 * H, H, s));
     hipStream_t s2 = twin_fork(s);
-    const int nchunks = (T + CH - 1) / CH;
-    const bool areas = nchunks <= kMaxChunks;            // one pre-zeroed counter area per chunk and layer
+    const bool areas = p.areas != 0;                     // one pre-zeroed counter area per chunk and layer
     if (areas && (hipMemsetAsync(w0.sync + kSyncWords, 0, (kSyncWordsAll - kSyncWords) * sizeof(unsigned), s) != hipSuccess ||
                   hipMemsetAsync(w1.sync + kSyncWords, 0, (kSyncWordsAll - kSyncWords) * sizeof(unsigned), s) != hipSuccess)) return -2;
     if (s2 != s) INET_TRY(stream_wait(s2, s));           // (the second stream's first launch must see those zeros)
@@ -839,14 +857,14 @@ int lstm2_seq_bwd(int B, int T, int H, const float* W_hh0, const float* W_ih1, c
         float* in0 = w0.carry + (long)((c + 1) & 1) * 2 * BH;
         float* ou0 = w0.carry + (long)(c & 1) * 2 * BH;
         INET_TRY(lstm_chunk_bwd(B, T, H, dout1, c ? in1 : nullptr, c ? in1 + BH : nullptr, reverse, dgi1, db_ih1, db_hh1,
-                                s_lo ? ou1 : nullptr, s_lo ? ou1 + BH : nullptr, w1, s_lo, nt, s, areas ? c : -1));
+                                s_lo ? ou1 : nullptr, s_lo ? ou1 + BH : nullptr, w1, s_lo, nt, p, s, areas ? c : -1));
         hipStream_t s3 = side_fork(s);                       // (as in the forward pipeline: the chunk's product on a third stream)
         if (s3 == s2 || s3 == s) { s3 = s2; INET_TRY(stream_wait(s2, s)); }
         INET_TRY(linear_dgrad(dgi1 + t_lo * B4H, 4L * H, W_ih1, H, dout0 + t_lo * BH, H, nt * B, 4 * H, H, EPI_NONE, nullptr, 0,
                               ACC_STORE, s3));
         if (s3 != s2) INET_TRY(stream_wait(s2, s3));
         INET_TRY(lstm_chunk_bwd(B, T, H, dout0, c ? in0 : nullptr, c ? in0 + BH : nullptr, reverse, dgi0, db_ih0, db_hh0,
-                                s_lo ? ou0 : nullptr, s_lo ? ou0 + BH : nullptr, w0, s_lo, nt, s2, areas ? c : -1, lstm_pipe_xrot()));
+                                s_lo ? ou0 : nullptr, s_lo ? ou0 + BH : nullptr, w0, s_lo, nt, p, s2, areas ? c : -1, lstm_pipe_xrot()));
     }
     // Weight gradients, once per layer (handing each chunk's products to an in-order stream as soon as its gate gradients exist
     // was slower -- 9.2 -> 10.5 ms per AnticipationRNN step: beside the chains they slow every hand-off):
@@ -875,9 +893,10 @@ int lstm_seq_bwd(int B, int T, int H, const float* W_hh, const float* h0, const 
     lstm_carve(B, T, H, 1, ws, w);
     const long BH = (long)B * H, TBH = (long)T * BH, B4H = 4 * BH;
     INET_TRY(pw_transpose(W_hh, H, w.whhT, 4L * H, 4 * H, H, s));
-    const bool use_chain = lstm_chain_ok(B, H);
+    const LstmChainPlan p = lstm_chain_plan(B, T, H, 1);
+    const bool use_chain = p.ok != 0;
     if (use_chain) {                                           // the whole sequence as one chunk on the base counter area
-        INET_TRY(lstm_chunk_bwd(B, T, H, dout, dhT, dcT, reverse, dgi, db_ih, db_hh, dh0, dc0, w, 0, T, s));
+        INET_TRY(lstm_chunk_bwd(B, T, H, dout, dhT, dcT, reverse, dgi, db_ih, db_hh, dh0, dc0, w, 0, T, p, s));
     } else
     for (int step = T - 1; step >= 0; --step) {
         const int t = reverse ? T - 1 - step : step;

@@ -732,6 +732,18 @@ def lstm_bwd(W_hh, out, dout, H, reverse, ws, dW_hh=None, db_ih=None, db_hh=None
     return dgi, dh0, dc0
 
 
+LSTM_PLAN_KEYS = ("ok", "MS", "groups", "members", "workgroups", "blocks", "tagged", "chunk_steps", "chunks", "areas", "chain_capacity",
+                  "side_by_side", "max_groups", "counter_stride", "counter_words")
+
+
+def lstm_chain_plan(B, T, H, pipeline=False):
+    """What one LSTM layer launches for (B, T, H) under the options set now, without a GPU (inet_lstm_chain_plan): a dict of
+    LSTM_PLAN_KEYS.  pipeline: the plan of lstm2_fwd / lstm2_bwd (two chain launches side by side) instead of lstm_fwd / lstm_bwd."""
+    out = (C.c_int64 * 16)()
+    check(_lib.lib().inet_lstm_chain_plan(int(B), int(T), int(H), int(bool(pipeline)), out), "inet_lstm_chain_plan")
+    return dict(zip(LSTM_PLAN_KEYS, out[:15]))
+
+
 def lstm2_ok(B, T, H):
     return bool(_lib.lib().inet_lstm2_ok(int(B), int(T), int(H)))
 

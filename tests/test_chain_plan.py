@@ -209,3 +209,138 @@ def test_other_chip_sizes(cus):
     env = dict(os.environ, INET_CHAIN_CUS=str(cus))
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "plans" in r.stdout, r.stdout + r.stderr
+
+
+# ---- the LSTM planner (csrc/lstm.hip lstm_chain_plan behind inet_lstm_chain_plan) ----------------------------------------------------
+LSTM_KEYS = ("ok", "MS", "groups", "members", "workgroups", "blocks", "tagged", "chunk", "chunks", "areas", "capacity", "side_by_side",
+             "max_groups", "counter_stride", "counter_words")
+LSTM_TS = (1, 63, 64, 65, 512, 513, 545)
+LSTM_CHUNK, LSTM_MAX_CHUNKS = 32, 16           # lstm_chunk_steps() without INET_LSTM_CHUNK; kMaxChunks
+
+
+def lstm_plan(L, B, T, H, pipeline):
+    out = (C.c_int64 * 16)()
+    assert L.inet_lstm_chain_plan(B, T, H, pipeline, out) == 0, (B, T, H, pipeline)
+    return dict(zip(LSTM_KEYS, out[:15]))
+
+
+def check_lstm_plan(p, B, T, H, pipeline, where):
+    """Every invariant of one LSTM plan, from the shape, the capacity the plan reports and the chunk length alone."""
+    side, cap = 2 if pipeline else 1, p["capacity"]
+    assert cap > 0 and p["side_by_side"] == side and p["max_groups"] == 32, (where, p)
+    assert p["max_groups"] * p["counter_stride"] <= p["counter_words"], (where, p)       # every group's counter inside the counter area
+    fits = lambda ms: side * ceil_div(B, 16 * ms) * (H // 16) <= cap and ceil_div(B, 16 * ms) <= 32
+    want_ms = next((ms for ms in (1, 2, 4) if fits(ms)), 0)
+    want_ok = want_ms != 0 and not (pipeline and T < 2 * LSTM_CHUNK)
+    assert p["ok"] == int(want_ok), (where, p)
+    if not p["ok"]:
+        assert all(p[k] == 0 for k in ("MS", "groups", "members", "workgroups", "blocks", "tagged", "chunk", "chunks", "areas")), (where, p)
+        return
+    assert p["MS"] == want_ms, (where, p)                                                # the smallest tile that fits
+    assert p["members"] == H // 16 and p["groups"] == ceil_div(B, 16 * p["MS"]), (where, p)
+    assert p["workgroups"] == p["groups"] * p["members"], (where, p)
+    assert side * p["groups"] * p["members"] <= cap and p["groups"] <= 32, (where, p)   # all launches that run together resident at once
+    assert p["groups"] * p["counter_stride"] <= p["counter_words"], (where, p)
+    assert p["blocks"] == 8 * p["members"] * ceil_div(p["groups"], 8), (where, p)       # chain::blocks_for, members <= 32
+    assert p["tagged"] == int(pipeline and H == 256 and p["MS"] <= 2), (where, p)
+    if pipeline:
+        assert T >= 2 * LSTM_CHUNK and p["chunk"] == LSTM_CHUNK and p["chunks"] == ceil_div(T, LSTM_CHUNK), (where, p)
+        assert p["areas"] == int(p["chunks"] <= LSTM_MAX_CHUNKS), (where, p)
+    else:
+        assert (p["chunk"], p["chunks"], p["areas"]) == (T, 1, 0), (where, p)
+
+
+def test_every_lstm_plan_of_the_grid_is_sound(L):
+    """H x B (every batch of 1..1100) x T x {layer, pipeline}: ok implies that the launches which run side by side are resident together
+    and every group has a counter, MS is the smallest tile with which they are, the tagged hand-off is the pipeline's at H = 256 and
+    MS <= 2, per-chunk counter areas are used iff there are at most 16 chunks, and a pipeline shorter than two chunks is refused."""
+    n = 0
+    for H in (256, 512):
+        for T in LSTM_TS:
+            for B in range(1, 1101):
+                for pipeline in (0, 1):
+                    check_lstm_plan(lstm_plan(L, B, T, H, pipeline), B, T, H, pipeline, (B, T, H, pipeline))
+                    n += 1
+    assert n == 2 * len(LSTM_TS) * 1100 * 2
+
+
+# (H, pipeline): ((last B of MS = 1, of MS = 2, of MS = 4); above the last one the plan is refused) on 256 CUs.  The single-layer rows
+# are what chain_ms() / lstm_chain_ok() gave before there was a planner: smallest MS with ceil(B / 16 MS) * H / 16 <= 256.
+LSTM_DOMAINS = {(256, 0): (256, 512, 1024), (512, 0): (128, 256, 512), (256, 1): (128, 256, 512), (512, 1): (64, 128, 256)}
+
+
+def test_lstm_tile_boundaries_on_256_cus(L):
+    """The single-layer plans are those of the parent commit at every B (boundaries 256 / 257, 512 / 513, 1024 / 1025 at H = 256 and
+    128 / 129, 256 / 257, 512 / 513 at H = 512); the pipeline's domains are half as wide, and it refuses what the layer alone takes."""
+    if lstm_plan(L, 1, 64, 256, 0)["capacity"] != 256:
+        pytest.skip("the table is written for a chain capacity of 256 workgroups (INET_CHAIN_CUS is set to another)")
+    for (H, pipeline), ends in LSTM_DOMAINS.items():
+        for B in range(1, 1101):
+            want = next((ms for ms, end in zip((1, 2, 4), ends) if B <= end), 0)
+            p = lstm_plan(L, B, 64, H, pipeline)
+            assert (p["ok"], p["MS"]) == (int(want != 0), want), (H, pipeline, B, p)
+    pins = {(256, 0): ((256, 1), (257, 2), (512, 2), (513, 4), (1024, 4), (1025, 0)),
+            (512, 0): ((128, 1), (129, 2), (256, 2), (257, 4), (512, 4), (513, 0)),
+            (256, 1): ((128, 1), (129, 2), (256, 2), (257, 4), (512, 4), (513, 0)),
+            (512, 1): ((64, 1), (65, 2), (128, 2), (129, 4), (256, 4), (257, 0))}
+    for (H, pipeline), rows in pins.items():
+        for B, ms in rows:
+            assert lstm_plan(L, B, 64, H, pipeline)["MS"] == ms, (H, pipeline, B)
+    # the benchmark's AnticipationRNN shape keeps its plan: two 16-row groups, tagged forward chunks of 32 steps, per-chunk areas
+    p = lstm_plan(L, 32, 384, 256, 1)
+    assert (p["ok"], p["MS"], p["groups"], p["tagged"], p["chunk"], p["chunks"], p["areas"]) == (1, 1, 2, 1, 32, 12, 1), p
+
+
+def test_lstm_plan_rejects_and_switch(L):
+    out = (C.c_int64 * 16)(*([7] * 16))
+    for args in ((0, 8, 256, 0), (8, 0, 256, 0), (8, 8, 0, 1), (-8, 8, 256, 1), (8, -1, 256, 0)):
+        assert L.inet_lstm_chain_plan(*args, out) == -1, args
+    assert L.inet_lstm_chain_plan(8, 8, 256, 0, None) == -1
+    assert list(out) == [7] * 16
+    assert lstm_plan(L, 8, 64, 768, 0)["ok"] == 0 and lstm_plan(L, 8, 64, 128, 1)["ok"] == 0     # widths no chain kernel is built for
+    assert L.inet_lstm2_ok(32, 64, 256) == 1 and L.inet_lstm2_ok(32, 63, 256) == 0
+    try:
+        assert L.inet_set_option(4, 0) == 0                                                      # chains off: nothing is ok
+        assert lstm_plan(L, 32, 384, 256, 0)["ok"] == 0 and lstm_plan(L, 32, 384, 256, 1)["ok"] == 0
+        assert L.inet_lstm2_ok(32, 384, 256) == 0
+    finally:
+        L.inet_set_option(4, 1)
+
+
+def test_lstm_routes_of_the_gpu_cases_on_256_cus(L):
+    """tests/test_gpu_lstm_chain_tiles.py ROUTES: the plan of every GPU case is the build the case was chosen for, no pipeline case sits
+    in what the residency rule refuses, and the shapes that file expects to be refused are."""
+    from inpaintnet_amd import ops
+    from tests import test_gpu_lstm_chain_tiles as G
+    if lstm_plan(L, 1, 64, 256, 0)["capacity"] != 256:
+        pytest.skip("ROUTES is written for a chain capacity of 256 workgroups (INET_CHAIN_CUS is set to another)")
+    assert set(G.ROUTES) == set(G.SINGLE) | set(G.PIPELINE) and not set(G.SINGLE) & set(G.PIPELINE)
+    for name, want in G.ROUTES.items():
+        pipeline = name in G.PIPELINE
+        H, B, T = (G.PIPELINE if pipeline else G.SINGLE)[name][:3]
+        p = ops.lstm_chain_plan(B, T, H, pipeline)
+        assert G.plan_key(p) == want and (p["ok"] or not pipeline), (name, p)
+    for B, T, H in G.REFUSED:
+        assert not ops.lstm2_ok(B, T, H) and ops.lstm_chain_plan(B, T, H, False)["ok"], (B, T, H)
+
+
+@pytest.mark.parametrize("cus", [64, 304])
+def test_lstm_plans_on_other_chip_sizes(cus):
+    """INET_CHAIN_CUS is read once per process: a fresh interpreter per capacity runs the LSTM sweep at a stride."""
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "from tests import test_chain_plan as P\n"
+            "from inpaintnet_amd import _lib\n"
+            "L = _lib.lib()\n"
+            "n = 0\n"
+            "for H in (256, 512):\n"
+            "    for T in (63, 64, 545):\n"
+            "        for B in P.batches():\n"
+            "            for pipeline in (0, 1):\n"
+            "                p = P.lstm_plan(L, B, T, H, pipeline)\n"
+            "                assert p['capacity'] == %d\n"
+            "                P.check_lstm_plan(p, B, T, H, pipeline, (B, T, H, pipeline))\n"
+            "                n += 1\n"
+            "print('plans', n)\n" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), cus))
+    env = dict(os.environ, INET_CHAIN_CUS=str(cus))
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "plans" in r.stdout, r.stdout + r.stderr
