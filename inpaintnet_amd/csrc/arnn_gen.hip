@@ -37,9 +37,9 @@
 // workgroups, each with its own exchange) in the workgroups that the argmax build leaves idle.
 // The truncating build (TRUNC = true, V <= 64: inet_arnn_sample_ex) puts sample.h's top-k / nucleus truncation in front of that draw,
 // reports the drawn tokens' log-probabilities (the logarithms are taken behind the last tick) and, where asked, every tick's logits;
-// head_trunc_b1_kernel does the same for the per-tick launches.  A call without truncation, logp or logits runs the sampling build.
+// head_b1_kernel<NI, 2> does the same for the per-tick launches.  A call without truncation, logp or logits runs the sampling build.
 // The masked build (MASK = true, V <= 64: inet_arnn_sample_cx) puts sample.h's per-tick token constraints in front of the truncation;
-// head_cons_b1_kernel does the same for the per-tick launches.  A call without a mask runs the kernels it ran before.
+// head_b1_kernel<NI, 3> does the same for the per-tick launches.  A call without a mask runs the kernels it ran before.
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -364,7 +364,9 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                 m = wave_max_dpp(m);
                 int bi = -1;
                 if constexpr (SAMPLE) {
-                    // the sampling head (sample.h): a NaN logit, a non-finite total or a uniform outside [0, 1) keep the argmax rule
+                    // the sampling head (sample.h): a NaN logit, a non-finite total or a uniform outside [0, 1) keep the argmax rule.
+                    // The steps of sample::draw stand here in the pass's own order, not as one call: through draw() the masked build
+                    // ran 3 % slower and the V > 64 sampling build 0.2 % -- a change to the rule is made here too
                     float sv[NV], ms = -INFINITY;
                     bool nan = false;
 #pragma unroll
@@ -373,6 +375,7 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                         nan |= sv[j] != sv[j];
                         ms = fmaxf(ms, sv[j]);
                     }
+                    double tot = 0.0;
                     if constexpr (TRUNC) {
                         // (one wave: plain vector stores of what every wave holds)
                         if (lrow && q == 6) {
@@ -382,7 +385,6 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                                 if (lane + 64 * j < a.V) row[lane + 64 * j] = lg[j];
                         }
                         float gap = 0.f;
-                        double tot = 0.0;
                         if constexpr (MASK) sample::mask_words<NV>(aw, a.V);
                         if (!__ballot(nan)) {
                             if constexpr (MASK) ms = sample::mask_scores<NV>(sv, aw, lane);
@@ -398,7 +400,7 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                             term[2] = gap;
                         }
                     } else {
-                        if (!__ballot(nan)) bi = sample::pick<NV>(sv, wave_max_dpp(ms), u, a.V, lane);
+                        if (!__ballot(nan)) bi = sample::pick<NV>(sv, wave_max_dpp(ms), u, a.V, lane, tot);
                     }
                 }
                 if (bi < 0) {
@@ -609,7 +611,8 @@ int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, lon
     unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
     const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
     char label[64];
-    std::snprintf(label, sizeof label, "%sarnn_token_sample R%d L%d V%d", allow ? "cons_" : trunc ? "trunc_" : "", R, L, V);
+    const int level = sample::level(uniforms, trunc, allow, nullptr);
+    std::snprintf(label, sizeof label, "%sarnn_token_sample R%d L%d V%d", level >= 2 ? sample::prefix(level) : "", R, L, V);
     for (int r0 = 0; r0 < R; r0 += n) {                          // R > teams: successive launches of up to `n` rows
         const int rows = std::min(n, R - r0);
         unsigned* status = reinterpret_cast<unsigned*>(ex + rows * kExGranules);
@@ -723,13 +726,18 @@ __device__ __forceinline__ bool argmax_better(float b2, int i2, float best, int 
     return b2 > best || (b2 == best && i2 < bi);
 }
 
-// np.argmax order over lg[0 .. V) (anticipation_rnn_gauss_reg_model.py:253) by one wave: a NaN is the maximum, the lowest index wins
-// among equals -- an all-NaN or all -inf row yields a token INSIDE the vocabulary (the next tick gathers the embedding row by it)
-__device__ __forceinline__ int argmax_wave(const float* lg, int V, int lane) {
-    float best = lane < V ? lg[lane] : -INFINITY;
-    int bi = lane < V ? lane : 0x7fffffff;
-    for (int v = lane + 64; v < V; v += 64)
-        if (argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
+// np.argmax order over the ALLOWED entries of lg[0 .. V) (anticipation_rnn_gauss_reg_model.py:253) by one wave: a NaN is the maximum, the
+// lowest index wins among equals -- an all-NaN or all -inf row yields a token INSIDE the vocabulary (the next tick gathers the embedding
+// row by it).  aw: the words of sample::mask_words (at least one bit set; no mask: all ones); a banned entry is no candidate whatever it
+// holds -- a NaN there does not win --, so the token is an allowed one
+__device__ __forceinline__ int argmax_wave(const float* lg, const unsigned long long (&aw)[4], int V, int lane) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int v = lane + 64 * j;
+        if (v < V && sample::allowed(aw[j], lane) && argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float b2 = __shfl_xor(best, o, 64);
@@ -739,11 +747,21 @@ __device__ __forceinline__ int argmax_wave(const float* lg, int V, int lane) {
     return bi;
 }
 
-// token = argmax_v (W[v,:] . x + b[v]), lowest index on ties, V <= 256: ONE workgroup of 16 waves; a wave's rows (V = 48: three) are all
-// requested before the first sum, the logits meet in LDS and the first wave takes the argmax with shuffles
-template <int NI>
-__global__ __launch_bounds__(1024) void head_argmax_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                              const float* __restrict__ b, long long* __restrict__ tok, int V, int K) {
+// The head of one tick, V <= 256: ONE workgroup of 16 waves; a wave's rows (V = 48: three) are all requested before the first sum, the
+// logits W[v,:] . x + b[v] meet in LDS and the first wave takes the token, in one build per LEVEL that reads its own level's arguments alone:
+//  0: token = the argmax, lowest index on ties.
+//  1: token = a draw from softmax(temp * logits) with the uniform *u (sample.h: numpy's np.random.choice order,
+//     anticipation_rnn_gauss_reg_model.py:655-667); a NaN logit, a non-finite total or a uniform outside [0, 1) keep the argmax rule.
+//  2: ... behind sample.h's top-k / nucleus truncation: *logp (nullable) receives the drawn token's log-probability under the truncated
+//     distribution (NaN where the tick takes the argmax rule) and logits [V] (nullable) the tick's logits, from the LDS array the draw reads.
+//  3: ... behind sample.h's token constraints: allow = the tick's ceil(V / 64) words of allowed tokens (<= 4), read by wave 0 through a
+//     wave-uniform address.  A tick outside the rule takes the argmax over its allowed logits.  The logits stored are the unmasked ones.
+template <int NI, int LEVEL>
+__global__ __launch_bounds__(1024) void head_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
+                                                       const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
+                                                       float temp, const double* __restrict__ u, int top_k, double top_p,
+                                                       float* __restrict__ logp, float* __restrict__ logits,
+                                                       const unsigned long long* __restrict__ allow) {
     __shared__ float lg[256];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float xv[NI];
@@ -763,187 +781,26 @@ __global__ __launch_bounds__(1024) void head_argmax_b1_kernel(const float* __res
         }
     }
     __syncthreads();
-    if (w == 0) {
-        const int bi = argmax_wave(lg, V, lane);
-        if (lane == 0) *tok = bi < V ? bi : 0;
+    if constexpr (LEVEL >= 2) {
+        if (w == 1 && logits)
+            for (int v = lane; v < V; v += 64) logits[v] = lg[v];
     }
-}
-
-// head_argmax_b1_kernel's products, then token = a draw from softmax(temp * logits) with the uniform *u (sample.h: numpy's
-// np.random.choice order, anticipation_rnn_gauss_reg_model.py:655-667); a NaN logit, a non-finite total or a uniform outside [0, 1)
-// keep the argmax rule.  V <= 256.
-template <int NI>
-__global__ __launch_bounds__(1024) void head_sample_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                              const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
-                                                              float temp, const double* __restrict__ u) {
-    __shared__ float lg[256];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float xv[NI];
-    load_x<NI>(xv, x, K, nullptr, K, lane);
-    float part[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        if (v < V) {
-            const float a = wave_sum(part[r]);
-            if (lane == 0) lg[v] = a + b[v];
-        }
-    }
-    __syncthreads();
-    if (w == 0) {
-        float sv[4], ms = -INFINITY;
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int v = lane + 64 * j;
-            sv[j] = v < V ? lg[v] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-            ms = fmaxf(ms, sv[j]);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
-        int bi = __ballot(nan) ? -1 : sample::pick<4>(sv, ms, *u, V, lane);
-        if (bi < 0) bi = argmax_wave(lg, V, lane);
-        if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
-    }
-}
-
-// head_sample_b1_kernel behind sample.h's top-k / nucleus truncation: the draw is made of the truncated distribution, *logp (nullable)
-// receives the drawn token's log-probability under it (NaN where the tick takes the argmax rule) and logits [V] (nullable) the tick's
-// logits, from the LDS array the draw reads.  V <= 256.
-template <int NI>
-__global__ __launch_bounds__(1024) void head_trunc_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                             const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
-                                                             float temp, const double* __restrict__ u, int top_k, double top_p,
-                                                             float* __restrict__ logp, float* __restrict__ logits) {
-    __shared__ float lg[256];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float xv[NI];
-    load_x<NI>(xv, x, K, nullptr, K, lane);
-    float part[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        if (v < V) {
-            const float a = wave_sum(part[r]);
-            if (lane == 0) lg[v] = a + b[v];
-        }
-    }
-    __syncthreads();
-    if (w == 1 && logits)
-        for (int v = lane; v < V; v += 64) logits[v] = lg[v];
-    if (w == 0) {
-        float sv[4], ms = -INFINITY;
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int v = lane + 64 * j;
-            sv[j] = v < V ? lg[v] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-            ms = fmaxf(ms, sv[j]);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
-        int bi = -1;
-        float gap = 0.f;
-        double tot = 0.0;
-        if (!__ballot(nan)) {
-            sample::truncate<4>(sv, ms, top_k, top_p, V, lane);
-            bi = sample::pick<4>(sv, ms, *u, V, lane, tot);
-            if (bi >= 0) gap = sample::logp_gap<4>(sv, ms, bi);
-        }
-        if (logp && lane == 0) *logp = bi >= 0 ? sample::logp_of(gap, tot) : __builtin_nanf("");
-        if (bi < 0) bi = argmax_wave(lg, V, lane);
-        if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
-    }
-}
-
-// np.argmax order over the ALLOWED entries of lg[0 .. V) by one wave (aw: the words of sample::mask_words, at least one bit set): a
-// banned entry is no candidate whatever it holds -- a NaN there does not win --, so the token is an allowed one
-__device__ __forceinline__ int argmax_wave_allowed(const float* lg, const unsigned long long (&aw)[4], int V, int lane) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int v = lane + 64 * j;
-        if (v < V && sample::allowed(aw[j], lane) && argmax_better(lg[v], v, best, bi)) { best = lg[v]; bi = v; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float b2 = __shfl_xor(best, o, 64);
-        const int i2 = __shfl_xor(bi, o, 64);
-        if (argmax_better(b2, i2, best, bi)) { best = b2; bi = i2; }
-    }
-    return bi;
-}
-
-// head_trunc_b1_kernel behind sample.h's token constraints: allow = the tick's ceil(V / 64) words of allowed tokens (<= 4: V <= 256),
-// read by wave 0 through a wave-uniform address.  The mask acts behind the NaN test and in front of the truncation; a tick outside the
-// rule takes the argmax over its allowed logits (argmax_wave_allowed) with a NaN logp.  The logits stored are the unmasked ones.
-template <int NI>
-__global__ __launch_bounds__(1024) void head_cons_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
-                                                            const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
-                                                            float temp, const double* __restrict__ u, int top_k, double top_p,
-                                                            float* __restrict__ logp, float* __restrict__ logits,
-                                                            const unsigned long long* __restrict__ allow) {
-    __shared__ float lg[256];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float xv[NI];
-    load_x<NI>(xv, x, K, nullptr, K, lane);
-    float part[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        part[r] = v < V ? dot_row<NI>(W + (long)v * K, xv, K, lane) : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int v = w + 16 * r;
-        if (v < V) {
-            const float a = wave_sum(part[r]);
-            if (lane == 0) lg[v] = a + b[v];
-        }
-    }
-    __syncthreads();
-    if (w == 1 && logits)
-        for (int v = lane; v < V; v += 64) logits[v] = lg[v];
     if (w == 0) {
         const int nw = (V + 63) / 64;
         unsigned long long aw[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) aw[j] = j < nw ? allow[j] : 0ull;
-        sample::mask_words<4>(aw, V);
-        float sv[4];
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int v = lane + 64 * j;
-            sv[j] = v < V ? lg[v] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-        }
+        for (int j = 0; j < 4; ++j) aw[j] = LEVEL < 3 ? ~0ull : j < nw ? allow[j] : 0ull;   // (below level 3: constants, and v < V bounds the argmax)
+        if constexpr (LEVEL >= 3) sample::mask_words<4>(aw, V);
         int bi = -1;
-        float gap = 0.f;
-        double tot = 0.0;
-        if (!__ballot(nan)) {
-            float ms = sample::mask_scores<4>(sv, aw, lane);
+        if constexpr (LEVEL >= 1) {
+            float xs[4], gap;
+            double tot;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ms = fmaxf(ms, __shfl_xor(ms, o, 64));
-            sample::truncate<4>(sv, ms, top_k, top_p, V, lane);
-            bi = sample::pick<4>(sv, ms, *u, V, lane, tot);
-            if (bi >= 0) gap = sample::logp_gap<4>(sv, ms, bi);
+            for (int j = 0; j < 4; ++j) xs[j] = lane + 64 * j < V ? lg[lane + 64 * j] : -INFINITY;
+            bi = sample::draw<4, LEVEL>(xs, temp, *u, V, lane, top_k, top_p, aw, -1, gap, tot);
+            if constexpr (LEVEL >= 2) { if (logp && lane == 0) *logp = bi >= 0 ? sample::logp_of(gap, tot) : gap; }
         }
-        if (logp && lane == 0) *logp = bi >= 0 ? sample::logp_of(gap, tot) : __builtin_nanf("");
-        if (bi < 0) bi = argmax_wave_allowed(lg, aw, V, lane);
+        if (bi < 0) bi = argmax_wave(lg, aw, V, lane);
         if (lane == 0) *tok = bi >= 0 && bi < V ? bi : 0;
     }
 }
@@ -960,10 +817,12 @@ int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, cons
                float temp, const double* uniforms, long long* tokens, float* ws, hipStream_t s, bool trunc = false, int top_k = 0,
                double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr) {
     const int H = n.H;
-    std::optional<ProfScope> prof;                             // (an untruncated call files nothing, as before)
-    if (trunc) {
+    const int level = sample::level(uniforms, trunc, allow, nullptr);
+    // (a call below level 2 files nothing.  `trunc` counts only with uniforms -- sample::level --, and no caller sets it without them)
+    std::optional<ProfScope> prof;
+    if (level >= 2) {
         char label[64];
-        std::snprintf(label, sizeof label, "%sarnn_ticks L%d V%d", allow ? "cons_" : "trunc_", L, n.V);
+        std::snprintf(label, sizeof label, "%sarnn_ticks L%d V%d", sample::prefix(level), L, n.V);
         prof.emplace(PROF_GRU_FWD, 2.0 * L * ((double)4 * H * (n.E + n.Hc + 3.0 * H) + (double)n.U * H + (double)n.V * n.U), s, label);
     }
     float* hc = ws;                                            // [layer][h|c][ping-pong][H]
@@ -984,18 +843,17 @@ int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, cons
                            (const float*)C_(1, p), n.W_hh1, n.b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
         hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((n.U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), n.W1, n.b1, u,
                            n.U, H);
-        if (uniforms && trunc && allow)
-            hipLaunchKernelGGL((head_cons_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
-                               temp, uniforms + t, top_k, top_p, logp ? logp + t : nullptr, logits ? logits + (long)t * n.V : nullptr,
-                               allow + (long)t * ((n.V + 63) / 64));
-        else if (uniforms && trunc)
-            hipLaunchKernelGGL((head_trunc_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
-                               temp, uniforms + t, top_k, top_p, logp ? logp + t : nullptr, logits ? logits + (long)t * n.V : nullptr);
-        else if (uniforms)
-            hipLaunchKernelGGL((head_sample_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,
-                               temp, uniforms + t);
-        else
-            hipLaunchKernelGGL((head_argmax_b1_kernel<4>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U);
+#define HEAD_B1(LEVEL)                                                                                                          \
+    hipLaunchKernelGGL((head_b1_kernel<4, LEVEL>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U, temp, \
+                       uniforms ? uniforms + t : nullptr, top_k, top_p, logp ? logp + t : nullptr,                                  \
+                       logits ? logits + (long)t * n.V : nullptr, allow ? allow + (long)t * ((n.V + 63) / 64) : nullptr)
+        switch (level) {
+            case 0: HEAD_B1(0); break;
+            case 1: HEAD_B1(1); break;
+            case 2: HEAD_B1(2); break;
+            default: HEAD_B1(3);
+        }
+#undef HEAD_B1
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

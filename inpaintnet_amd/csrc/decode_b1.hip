@@ -489,101 +489,43 @@ __device__ __forceinline__ void beat_path_role(const Ctx<NR>& c, int role, int n
     }
 }
 
-// TEMPERATURE SAMPLING (SAMPLE = true; sample.h has the rule): where the argmax wave of a row holds the row's post-ReLU logits
-// lg[j] of v = lane + 64 j, the token is the first v whose prefix of exp(T lg - max) exceeds u[row, tick] times the total.  Where the
-// rule does not apply (-1: a NaN among T lg -- an infinite logit times T = 0 --, a non-finite maximum or total, u outside [0, 1)) the
-// tick keeps the argmax rule.  The drawn token is the one fed back and stored.  The uniform of (row, tick) is requested at the start
-// of the tick through a wave-uniform address; rows beyond B read row B - 1's uniforms, as they repeat its logits.
-template <int NVL>
-__device__ __forceinline__ int sample_token(const float (&lg)[NVL], float temp, double u, int V, int lane) {
-    float sv[NVL], ms = -INFINITY;
-    bool nan = false;
-#pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
-        nan |= sv[j] != sv[j];
-        ms = fmaxf(ms, sv[j]);
-    }
-    if (__ballot(nan)) return -1;
-    return sample::pick<NVL>(sv, wave_max_dpp(ms), u, V, lane);
-}
-// TRUNCATED SAMPLING (TRUNC = true, the truncating build; sample.h has the rule): sample::truncate in front of the same pick -- top_k and
-// top_p are kernel arguments, so the token stays a pure function of `lgs`, u and two kernel arguments: the merged build's copies still agree
-// bit for bit.  The drawn token's log-probability under the truncated distribution is (s_tok - max s) - log(S): gap = its first half (NaN
-// where the tick keeps the argmax rule), S = the kept total (1 there); the wave that stores the token files both in LDS (lp_gap, lp_tot)
-// and takes the f64 logarithms of all ticks behind the last one, where the weights' registers are free (inside the tick the pick runs
-// with ~240 registers taken: an f64 log there spills).  Hence at most kTruncTicks ticks per call.
+// THE DRAW (DRAW = 1 .. 4 = SAMPLE + TRUNC + MASK + FORCE, sample.h's levels; sample::draw is the rule): where the argmax wave of a row
+// holds the row's post-ReLU logits lg[j] of v = lane + 64 j, the token is the first v whose prefix of exp(T lg - max) exceeds u[row, tick]
+// times the total.  Where the rule does not apply (-1: a NaN among T lg -- an infinite logit times T = 0 --, a non-finite maximum or
+// total, u outside [0, 1)) the tick keeps the argmax rule.  The drawn token is the one fed back and stored.
+//  2 up, the truncating build: sample.h's truncate() in front of the same pick -- top_k and top_p are kernel arguments, so the token stays a
+//   pure function of `lgs`, u and two kernel arguments: the merged build's copies still agree bit for bit.  The drawn token's
+//   log-probability under the truncated distribution is (s_tok - max s) - log(S): gap = its first half (NaN where the tick keeps the argmax
+//   rule), S = the kept total (1 there); the wave that stores the token files both in LDS (lp_gap, lp_tot) and takes the f64 logarithms of
+//   all ticks behind the last one, where the weights' registers are free (inside the tick the pick runs with ~240 registers taken: an f64
+//   log there spills).  Hence at most kTruncTicks ticks per call.
+//  3 up, the masked build: the tick's mask words `aw` (behind sample::mask_words: bits at or above V cleared, an empty mask all ones) ban
+//   tokens behind the NaN test and in front of the truncation.
+//  4, the forced build: `fw` is the tick's forced word.  A free tick (fw outside [0, V)) IS level 3's.  A forced tick runs the same mask,
+//   truncation and pick -- with u = 0.0, for the kept total S alone -- and then takes fw with gap = s_f - m: -inf where fw is banned or
+//   truncated away, NaN (and S = 1) where the rule does not apply.  It is never -1: the argmax re-read is skipped.
 constexpr int kTruncTicks = 64;
-template <int NVL>
-__device__ __forceinline__ int sample_token_trunc(const float (&lg)[NVL], float temp, double u, int V, int lane, int top_k, double top_p,
-                                                  float& gap, double& S) {
-    float sv[NVL], ms = -INFINITY;
-    bool nan = false;
+// The tick's words of the draw -- the uniform, the mask words (level 4 without a mask, a kernel argument: all ones) and the forced word of
+// (row, tick) at `at` = row * T + tick -- requested at the start of the tick and read behind the head.  The address is wave-uniform, so
+// the token is a pure function of `lgs`, these words and kernel arguments; rows beyond B read row B - 1's, as they repeat its logits.
+template <int DRAW, int NVL, int NA>
+__device__ __forceinline__ void request_draw(const B1Args& a, bool picks, long at, double& ut, unsigned long long (&aw)[NA], int& fw) {
+    if constexpr (DRAW >= 1) { if (picks) ut = a.uniforms[at]; }
+    if constexpr (DRAW >= 3) {
+        if (picks && (DRAW < 4 || a.allow)) {
 #pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
-        nan |= sv[j] != sv[j];
-        ms = fmaxf(ms, sv[j]);
+            for (int j = 0; j < NVL; ++j) aw[j] = a.allow[at * NVL + j];
+        }
     }
-    gap = __builtin_nanf("");
-    S = 1.0;
-    if (__ballot(nan)) return -1;
-    ms = wave_max_dpp(ms);
-    sample::truncate<NVL>(sv, ms, top_k, top_p, V, lane);
-    const int tok = sample::pick<NVL>(sv, ms, u, V, lane, S);
-    if (tok >= 0) gap = sample::logp_gap<NVL>(sv, ms, tok);
-    else S = 1.0;
-    return tok;
-}
-// CONSTRAINED SAMPLING (MASK = true, the masked build of the truncating build; sample.h has the rule): the tick's mask words `aw` (from
-// sample::mask_words: bits at or above V cleared, an empty mask all ones) ban tokens behind the NaN test and in front of the truncation.
-// The words arrive through a wave-uniform address like `ut`, so the token is a pure function of `lgs`, u, the mask words and kernel arguments.
-template <int NVL>
-__device__ __forceinline__ int sample_token_cons(const float (&lg)[NVL], float temp, double u, int V, int lane, int top_k, double top_p,
-                                                 const unsigned long long (&aw)[NVL], float& gap, double& S) {
-    float sv[NVL];
-    bool nan = false;
+    if constexpr (DRAW >= 4) {
+        if (picks) {
+            fw = a.forced[at];
+            if (!a.allow) {
 #pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
-        nan |= sv[j] != sv[j];
+                for (int j = 0; j < NVL; ++j) aw[j] = ~0ull;
+            }
+        }
     }
-    gap = __builtin_nanf("");
-    S = 1.0;
-    if (__ballot(nan)) return -1;
-    const float ms = wave_max_dpp(sample::mask_scores<NVL>(sv, aw, lane));
-    sample::truncate<NVL>(sv, ms, top_k, top_p, V, lane);
-    const int tok = sample::pick<NVL>(sv, ms, u, V, lane, S);
-    if (tok >= 0) gap = sample::logp_gap<NVL>(sv, ms, tok);
-    else S = 1.0;
-    return tok;
-}
-// FORCED TOKENS (FORCE = true, the forced build of the masked build; sample.h has the rule): `f` is the tick's forced word, read through the
-// same wave-uniform address as `ut` and the mask words.  A free tick (f outside [0, V)) IS sample_token_cons.  A forced tick runs the same
-// mask, truncation and pick -- with u = 0.0, for the kept total S alone -- and then returns f with gap = s_f - m: -inf where f is banned or
-// truncated away, NaN (and S = 1) where the rule does not apply.  It never returns -1: the caller's argmax re-read is skipped.
-template <int NVL>
-__device__ __forceinline__ int sample_token_force(const float (&lg)[NVL], float temp, double u, int V, int lane, int top_k, double top_p,
-                                                  const unsigned long long (&aw)[NVL], int f, float& gap, double& S) {
-    const bool forced = sample::is_forced(f, V);
-    float sv[NVL];
-    bool nan = false;
-#pragma unroll
-    for (int j = 0; j < NVL; ++j) {
-        sv[j] = lane + 64 * j < V ? lg[j] * temp : -INFINITY;
-        nan |= sv[j] != sv[j];
-    }
-    gap = __builtin_nanf("");
-    S = 1.0;
-    if (__ballot(nan)) return forced ? f : -1;
-    const float ms = wave_max_dpp(sample::mask_scores<NVL>(sv, aw, lane));
-    sample::truncate<NVL>(sv, ms, top_k, top_p, V, lane);
-    int tok = sample::pick<NVL>(sv, ms, forced ? 0.0 : u, V, lane, S);
-    if (tok >= 0) {
-        if (forced) tok = f;
-        gap = sample::logp_gap<NVL>(sv, ms, tok);
-    } else S = 1.0;
-    return forced ? f : tok;
 }
 // ... behind the last tick: logp[row, t] of the team's rows, one (row, tick) per thread (the picking waves' LDS writes are ordered by the
 // barrier the caller's loop ends with or by this one)
@@ -625,13 +567,14 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     static_assert(SAMPLE || !TRUNC, "the truncating build is a sampling build");
     static_assert(TRUNC || !MASK, "the masked build is a truncating build");
     static_assert(MASK || !FORCE, "the forced build is a masked build");
+    constexpr int DRAW = SAMPLE + TRUNC + MASK + FORCE;         // sample.h's level: 0 = argmax
     constexpr int XROWS = NB > NBB ? (NB > NBR ? NB : NBR) : (NBB > NBR ? NBB : NBR);
     __shared__ __attribute__((aligned(16))) float xs[XROWS][2][XS];
     __shared__ float lgs[NB][32 * NJ];
     __shared__ int toks[NB];
     // the truncating build: (s_tok - max s, kept total) of every (row, tick), filed by the wave that stores the token (lane 0; one row: wave 0's)
-    __shared__ float lp_gap[TRUNC ? NB : 1][TRUNC ? kTruncTicks : 1];
-    __shared__ double lp_tot[TRUNC ? NB : 1][TRUNC ? kTruncTicks : 1];
+    __shared__ float lp_gap[DRAW >= 2 ? NB : 1][DRAW >= 2 ? kTruncTicks : 1];
+    __shared__ double lp_tot[DRAW >= 2 ? NB : 1][DRAW >= 2 ? kTruncTicks : 1];
     __shared__ int bad_s;
     __shared__ int near_s;
     if (blockIdx.x % a.stride) return;
@@ -653,7 +596,7 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
     const int nb = a.T / a.G;
     const DecodeB1Beat& bp = a.bp;
     // MG, the merged build: workgroup C does not exist, every TBi_k does C's work for itself next to its own (CB below)
-    constexpr bool MG = merged_build(NB, NJ, NBR, SAMPLE + TRUNC + MASK + FORCE);
+    constexpr bool MG = merged_build(NB, NJ, NBR, DRAW);
 
     if (role == R_C) {
         if (MG) return;
@@ -688,27 +631,10 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         constexpr int NVL = (32 * NJ + 63) / 64;
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
-            double ut = 0.0;                                   // the sampling build: this tick's uniform, requested here and read behind the head
-            if constexpr (SAMPLE) { if (picks) ut = a.uniforms[urow_at + t]; }
-            // the masked build: this (row, tick)'s mask words, requested next to `ut` through the same wave-uniform address
-            [[maybe_unused]] unsigned long long aw[MASK ? NVL : 1] = {};
-            if constexpr (MASK) {
-                if (picks && (!FORCE || a.allow)) {
-#pragma unroll
-                    for (int j = 0; j < NVL; ++j) aw[j] = a.allow[(urow_at + t) * NVL + j];
-                }
-            }
-            // the forced build: this (row, tick)'s forced word, likewise; without a mask (a kernel argument: wave-uniform) all ones
+            double ut = 0.0;                                   // the draw's words of this tick, requested here and read behind the head
+            [[maybe_unused]] unsigned long long aw[DRAW >= 3 ? NVL : 1] = {};
             [[maybe_unused]] int fw = -1;
-            if constexpr (FORCE) {
-                if (picks) {
-                    fw = a.forced[urow_at + t];
-                    if (!a.allow) {
-#pragma unroll
-                        for (int j = 0; j < NVL; ++j) aw[j] = ~0ull;
-                    }
-                }
-            }
+            if constexpr (DRAW >= 1) request_draw<DRAW, NVL>(a, picks, urow_at + t, ut, aw, fw);
             if (t % a.G == 0) {
                 const long beat = t / a.G;
                 if (FUSED) {
@@ -770,8 +696,8 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             }
             lds_barrier();
             B1_STAMP(0, t, 4);
-            // wave r takes the argmax of row r (one row: every wave takes it for itself and the second barrier is not needed): the
-            // maximum by DPP, its lowest index by ballot
+            // wave r takes the token of row r (one row: every wave takes it for itself and the second barrier is not needed): the
+            // maximum by DPP, its lowest index by ballot -- or the draw, with that argmax where the rule does not apply
             if (NB == 1 || wave < NB) {
                 const int arow = NB == 1 ? 0 : wave;
                 float lg[NVL], m = -1.f;
@@ -783,25 +709,24 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
                 }
                 m = wave_max_dpp(m);
                 int bi = 0;
-                if constexpr (MASK) sample::mask_words<NVL>(aw, a.V);
-                if constexpr (TRUNC) {
+                if constexpr (DRAW >= 3) sample::mask_words<NVL>(aw, a.V);
+                if constexpr (DRAW >= 1) {
                     float gap;
                     double tot;
-                    if constexpr (FORCE) bi = sample_token_force<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, fw, gap, tot);
-                    else if constexpr (MASK) bi = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
-                    else bi = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
-                    if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
+                    bi = sample::draw<NVL, DRAW>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, fw, gap, tot);
+                    if constexpr (DRAW >= 2) {
+                        if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
+                    }
                 }
-                else if constexpr (SAMPLE) bi = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
-                if (!SAMPLE || bi < 0) {
-                    if (SAMPLE) bi = 0;
-                    if constexpr (TRUNC) {                      // (the truncating build does not keep the logits across the draw: read again)
+                if (!DRAW || bi < 0) {
+                    if (DRAW) bi = 0;
+                    if constexpr (DRAW >= 2) {                  // (the truncating build does not keep the logits across the draw: read again)
                         m = -1.f;
 #pragma unroll
                         for (int j = 0; j < NVL; ++j) {
                             const int v = lane + 64 * j;
                             lg[j] = v < a.V ? lgs[arow][v] : -1.f;
-                            if constexpr (MASK) { if (!sample::allowed(aw[j], lane)) lg[j] = -1.f; }   // (a banned token: the padding value)
+                            if constexpr (DRAW >= 3) { if (!sample::allowed(aw[j], lane)) lg[j] = -1.f; }   // (a banned token: the padding value)
                             m = fmaxf(m, lg[j]);
                         }
                         m = wave_max_dpp(m);
@@ -835,9 +760,9 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             }
             if (more && !get_2d<NB, 3>(ex + G_GH0 + u, G_END, DH, (unsigned)t + 2u, a.status, gh, hw, false)) *bad = 1;
             B1_STAMP(0, t, 6);
-            if constexpr (TRUNC) done = t + 1;
+            if constexpr (DRAW >= 2) done = t + 1;
         }
-        if constexpr (TRUNC) store_logp<NB>(a, lp_gap, lp_tot, rb, nrow, tid, done);
+        if constexpr (DRAW >= 2) store_logp<NB>(a, lp_gap, lp_tot, rb, nrow, tid, done);
     } else if (role < R_TBI) {
         if (NBR != NB && a.crit != kCritTA) {                  // a shared group: rows [NBR team, NBR team + NBR) of the call
             const int rbr = team * NBR;
@@ -903,27 +828,10 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
         for (int t = 0; t < a.T; ++t) {
             const bool more = t + 1 < a.T;
             const unsigned tag = (unsigned)t + 1u;
-            double ut = 0.0;                                   // the sampling build: this tick's uniform, requested here and read behind the head
-            if constexpr (SAMPLE) { if (picks) ut = a.uniforms[urow_at + t]; }
-            // the masked build: this (row, tick)'s mask words, requested next to `ut` through the same wave-uniform address
-            [[maybe_unused]] unsigned long long aw[MASK ? NVL : 1] = {};
-            if constexpr (MASK) {
-                if (picks && (!FORCE || a.allow)) {
-#pragma unroll
-                    for (int j = 0; j < NVL; ++j) aw[j] = a.allow[(urow_at + t) * NVL + j];
-                }
-            }
-            // the forced build: this (row, tick)'s forced word, likewise; without a mask (a kernel argument: wave-uniform) all ones
+            double ut = 0.0;                                   // the draw's words of this tick, requested here and read behind the head
+            [[maybe_unused]] unsigned long long aw[DRAW >= 3 ? NVL : 1] = {};
             [[maybe_unused]] int fw = -1;
-            if constexpr (FORCE) {
-                if (picks) {
-                    fw = a.forced[urow_at + t];
-                    if (!a.allow) {
-#pragma unroll
-                        for (int j = 0; j < NVL; ++j) aw[j] = ~0ull;
-                    }
-                }
-            }
+            if constexpr (DRAW >= 1) request_draw<DRAW, NVL>(a, picks, urow_at + t, ut, aw, fw);
             const int g_h1 = slot_h1(tag);
             float gh1[NB][3];
             unsigned long long hw1[NB][3];
@@ -1024,30 +932,29 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
 #pragma unroll
                 for (int j = 0; j < NVL; ++j) {
                     const int v = lane + 64 * j;
-                    lg[j] = v < a.V ? lgs[arow][v] : -1.f;
+                    lg[j] = v < a.V ? lgs[arow][v] : -1.f;      // (below every post-ReLU logit)
                     m = fmaxf(m, lg[j]);
                 }
                 m = wave_max_dpp(m);
                 int best = 0;
-                if constexpr (MASK) sample::mask_words<NVL>(aw, a.V);
-                if constexpr (TRUNC) {
+                if constexpr (DRAW >= 3) sample::mask_words<NVL>(aw, a.V);
+                if constexpr (DRAW >= 1) {
                     float gap;
                     double tot;
-                    if constexpr (FORCE) best = sample_token_force<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, fw, gap, tot);
-                    else if constexpr (MASK) best = sample_token_cons<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, gap, tot);
-                    else best = sample_token_trunc<NVL>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, gap, tot);
-                    if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
+                    best = sample::draw<NVL, DRAW>(lg, a.temperature, ut, a.V, lane, a.top_k, a.top_p, aw, fw, gap, tot);
+                    if constexpr (DRAW >= 2) {
+                        if (lane == 0 && t < kTruncTicks) { lp_gap[arow][t] = gap; lp_tot[arow][t] = tot; }
+                    }
                 }
-                else if constexpr (SAMPLE) best = sample_token<NVL>(lg, a.temperature, ut, a.V, lane);
-                if (!SAMPLE || best < 0) {
-                    if (SAMPLE) best = 0;
-                    if constexpr (TRUNC) {                      // (the truncating build does not keep the logits across the draw: read again)
+                if (!DRAW || best < 0) {
+                    if (DRAW) best = 0;
+                    if constexpr (DRAW >= 2) {                  // (the truncating build does not keep the logits across the draw: read again)
                         m = -1.f;
 #pragma unroll
                         for (int j = 0; j < NVL; ++j) {
                             const int v = lane + 64 * j;
                             lg[j] = v < a.V ? lgs[arow][v] : -1.f;
-                            if constexpr (MASK) { if (!sample::allowed(aw[j], lane)) lg[j] = -1.f; }   // (a banned token: the padding value)
+                            if constexpr (DRAW >= 3) { if (!sample::allowed(aw[j], lane)) lg[j] = -1.f; }   // (a banned token: the padding value)
                             m = fmaxf(m, lg[j]);
                         }
                         m = wave_max_dpp(m);
@@ -1082,9 +989,9 @@ __global__ __launch_bounds__(NT) void decode_b1_kernel(B1Args a) {
             if (more && !get_2d<NB, 3>(ex + (gh0_near ? G_GH0N + (int)((tag + 1u) & 1) * D3 : (((tag + 1u) & 1) ? G_GH0X : G_GH0)) + u, G_END, DH, tag + 1u,
                                        a.status, gh, hw, false)) *bad = 1;
             if (out) B1_STAMP(0, t, 6);
-            if constexpr (TRUNC) done = t + 1;
+            if constexpr (DRAW >= 2) done = t + 1;
         }
-        if constexpr (TRUNC) { if (out) store_logp<NB>(a, lp_gap, lp_tot, rb, nrow, tid, done); }
+        if constexpr (DRAW >= 2) { if (out) store_logp<NB>(a, lp_gap, lp_tot, rb, nrow, tid, done); }
     } else if (role < R_TBH) {
         // ---- TBi_k: tick layer 1's input-side product and its cell ----
         const int k = role - R_TBI, p = tid >> 4, s = tid & 15, u = UW * k + p;
@@ -1323,38 +1230,23 @@ static bool dispatch_b1_nj(const B1Plan& p, const B1Args* a, hipStream_t s) {
 #undef B1_INST
     return false;
 }
-// (the masked builds are named in a function of their own BEHIND this one: the instantiations are emitted in the order their first use is
-//  met, so the builds that existed before keep their places at the front of the code object)
-static bool dispatch_b1_masked(const B1Plan& p, const B1Args* a, hipStream_t s);
-static bool dispatch_b1_forced(const B1Plan& p, const B1Args* a, hipStream_t s);      // (... and the forced builds behind the masked ones)
+// One switch over (level S = p.sample in 0..4, nj in 1..4), both packed into one case value 8 * S + nj (nj < 8, so no two pairs meet).
+// The ORDER OF THE CASE LABELS is the order in which the compiler first meets, and so emits, the instantiations; it is kept as the
+// code object has had it, so that a comparison of the assembly against an earlier commit lines the kernels up:
+//     nj = 1: S = 2, 1, 0;  nj = 2: S = 2, 1, 0;  nj = 3: ...;  nj = 4: ...     (B1_LOW: per nj the truncating, the sampling, the argmax build)
+//     S = 3: nj = 1, 2, 3, 4;  S = 4: nj = 1, 2, 3, 4                           (B1_HIGH: the masked, then the forced builds)
+// The order has no meaning at run time: a new level or nj goes where it reads best.
 static bool dispatch_b1(const B1Plan& p, const B1Args* a, hipStream_t s) {
-    if (p.sample == 3) return dispatch_b1_masked(p, a, s);
-    if (p.sample == 4) return dispatch_b1_forced(p, a, s);
-    switch (p.nj) {
-        case 1: return p.sample == 2 ? dispatch_b1_nj<1, 2>(p, a, s) : p.sample ? dispatch_b1_nj<1, 1>(p, a, s) : dispatch_b1_nj<1, 0>(p, a, s);
-        case 2: return p.sample == 2 ? dispatch_b1_nj<2, 2>(p, a, s) : p.sample ? dispatch_b1_nj<2, 1>(p, a, s) : dispatch_b1_nj<2, 0>(p, a, s);
-        case 3: return p.sample == 2 ? dispatch_b1_nj<3, 2>(p, a, s) : p.sample ? dispatch_b1_nj<3, 1>(p, a, s) : dispatch_b1_nj<3, 0>(p, a, s);
-        case 4: return p.sample == 2 ? dispatch_b1_nj<4, 2>(p, a, s) : p.sample ? dispatch_b1_nj<4, 1>(p, a, s) : dispatch_b1_nj<4, 0>(p, a, s);
+#define B1_NJ(NJ, S) case 8 * (S) + NJ: return dispatch_b1_nj<NJ, S>(p, a, s);
+#define B1_LOW(NJ) B1_NJ(NJ, 2) B1_NJ(NJ, 1) B1_NJ(NJ, 0)
+#define B1_HIGH(S) B1_NJ(1, S) B1_NJ(2, S) B1_NJ(3, S) B1_NJ(4, S)
+    switch (8 * p.sample + p.nj) {
+        B1_LOW(1) B1_LOW(2) B1_LOW(3) B1_LOW(4) B1_HIGH(3) B1_HIGH(4)
         default: return false;
     }
-}
-static bool dispatch_b1_masked(const B1Plan& p, const B1Args* a, hipStream_t s) {
-    switch (p.nj) {
-        case 1: return dispatch_b1_nj<1, 3>(p, a, s);
-        case 2: return dispatch_b1_nj<2, 3>(p, a, s);
-        case 3: return dispatch_b1_nj<3, 3>(p, a, s);
-        case 4: return dispatch_b1_nj<4, 3>(p, a, s);
-        default: return false;
-    }
-}
-static bool dispatch_b1_forced(const B1Plan& p, const B1Args* a, hipStream_t s) {
-    switch (p.nj) {
-        case 1: return dispatch_b1_nj<1, 4>(p, a, s);
-        case 2: return dispatch_b1_nj<2, 4>(p, a, s);
-        case 3: return dispatch_b1_nj<3, 4>(p, a, s);
-        case 4: return dispatch_b1_nj<4, 4>(p, a, s);
-        default: return false;
-    }
+#undef B1_HIGH
+#undef B1_LOW
+#undef B1_NJ
 }
 
 int decode_b1_rows(int B) {
@@ -1378,7 +1270,7 @@ bool decode_b1_shape_ok(int B, int H, int V, int T, int G, int sample) {
 bool decode_b1_fused(int Z, int B, int V, int sample) { return Z == DZ && make_plan(B, V, true, sample).ok; }
 bool decode_b1_ok(const DecodeChainArgs& a) {
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;
-    const int sample = a.uniforms ? (a.forced ? 4 : a.allow ? 3 : a.trunc ? 2 : 1) : 0;
+    const int sample = sample::level(a.uniforms, a.trunc, a.allow, a.forced);
     if ((a.allow || a.forced) && !a.uniforms) return false;
     return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G, sample) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr, sample).ok;
 }
@@ -1441,7 +1333,7 @@ int decode_b1_plan_check(int B, int V, int Z, int* out, int sample) {
 }
 
 int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
-    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.uniforms ? (d.forced ? 4 : d.allow ? 3 : d.trunc ? 2 : 1) : 0);
+    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, sample::level(d.uniforms, d.trunc, d.allow, d.forced));
     if (!pl.ok || pl.rows > decode_b1_rows(d.B)) return -1;   // (decode_b1_ok has accepted the call: not reached)
     B1Args a{};
     a.fused = pl.fused; a.teams = pl.teams; a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place; a.stride = pl.stride;
@@ -1458,7 +1350,7 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     if (!dispatch_b1(pl, nullptr, nullptr)) return -1;        // (a plan without an instantiation launches nothing)
     char label[64];
     // (a sampled, a truncated, a constrained and a forced call's launch have label prefixes of their own: the profile tells the kinds of call apart)
-    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", pl.sample == 4 ? "force_" : pl.sample == 3 ? "cons_" : pl.sample == 2 ? "trunc_" : pl.sample ? "sample_" : "", a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
+    std::snprintf(label, sizeof label, "%sdecode_b1%s T%d B%d H%d V%d", sample::prefix(pl.sample), a.fused ? "_beats" : "", d.T, d.B, d.H, d.V);
     // algorithmic work: the tick GRU + head per tick and row; fused: + the beat path (z2b, two beat layers, three projections per beat)
     const double nbt = (double)d.T / d.G;
     const double beat_mac = a.fused ? 2.0 * DH * DZ + nbt * (3.0 * 3 * DH * DH + 2.0 * DH * DH + 1.0 * DH * DH + 3.0 * DH * DH) : 0.0;

@@ -102,15 +102,5 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // (plain v_fmac_f32 on purpose: left to itself hipcc SLP-packs the sums into v_pk_fma_f32 -- no faster on this part -- and pays two
 //  v_mov per pair to line the operands up)
 __device__ __forceinline__ void fmac(float& acc, float w, float x) { asm("v_fmac_f32_e32 %0, %1, %2" : "+v"(acc) : "v"(w), "v"(x)); }
-// maximum over the wave without LDS: two quad permutes, the two mirrors of a 16-lane row, then the four rows through SGPRs
-__device__ __forceinline__ float wave_max_dpp(float v) {
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0xB1, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x141, 0xF, 0xF, false)));  // row_half_mirror
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x140, 0xF, 0xF, false)));  // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
 
 }  // namespace granule

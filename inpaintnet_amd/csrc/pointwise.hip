@@ -674,7 +674,8 @@ __global__ void sample_temperature_kernel(const float* __restrict__ W, long ld_w
             m = fmaxf(m, x[j]);
             ms = fmaxf(ms, sv[j]);
         }
-        int tok = __ballot(nan) ? -1 : sample::pick<NV>(sv, wave_max(ms), u, V, lane);
+        double S;                                              // (not read: the temperature draw has no logp)
+        int tok = __ballot(nan) ? -1 : sample::pick<NV>(sv, wave_max(ms), u, V, lane, S);
         if (tok < 0) {
             m = wave_max(m);
             int am = kAmNone;

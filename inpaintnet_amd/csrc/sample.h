@@ -6,6 +6,7 @@
 // token = the first v with prefix_v > u * S, S = the total, by ballot and ctz.  The result is wave-uniform.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "common.h"
 
 namespace sample {
 
@@ -34,32 +35,8 @@ __device__ __forceinline__ double wave_scan(double x, int lane) {
 
 // s[j] = T x_v of v = lane + 64 j (-inf for v >= V), no NaN among them; m = max_v s_v (wave-uniform); u = the tick's uniform.
 // -> the first v with prefix_v > u S, or -1 where the rule does not apply (m or S not finite, u outside [0, 1)): the caller then
-// takes the argmax rule.  The result lies in [0, V) or is -1.
-template <int NV>
-__device__ __forceinline__ int pick(const float (&s)[NV], float m, double u, int V, int lane) {
-    if (!(m > -INFINITY && m < INFINITY) || !(u >= 0.0 && u < 1.0)) return -1;
-    double pre[NV];
-    double carry = 0.0;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const double e = lane + 64 * j < V ? (double)expf(s[j] - m) : 0.0;
-        const double x = wave_scan(e, lane);
-        pre[j] = carry + x;
-        carry += readlane_d(x, 63);
-    }
-    if (!(carry > 0.0 && carry < INFINITY)) return -1;
-    const double thr = u * carry;
-    int tok = -1;
-#pragma unroll
-    for (int j = NV - 1; j >= 0; --j) {
-        const unsigned long long b = __ballot(lane + 64 * j < V && pre[j] > thr);
-        if (b) tok = 64 * j + __builtin_ctzll(b);
-    }
-    return tok;
-}
-
-// The same, and S = the total the threshold was taken of (the kept total behind truncate()): what logp_of() needs.  Same instructions
-// on the same values as pick() above, which AnticipationRNN's kernels keep using: the token is the same bit for bit.
+// takes the argmax rule.  The result lies in [0, V) or is -1.  S = the total the threshold was taken of (the kept total behind
+// truncate(); 0 with -1): what logp_of() needs -- a caller that does not read it lets it die.
 template <int NV>
 __device__ __forceinline__ int pick(const float (&s)[NV], float m, double u, int V, int lane, double& S) {
     S = 0.0;
@@ -254,5 +231,48 @@ __device__ __forceinline__ float logp_gap(const float (&s)[NV], float m, int tok
     return st - m;
 }
 __device__ __forceinline__ float logp_of(float gap, double S) { return (float)((double)gap - log(S)); }
+
+// THE DRAW of one (row, tick): the rule above as one function, in builds of one LEVEL each -- 1 = temperature, 2 = truncated, 3 = masked,
+// 4 = forced; every step stands behind its level, so a lower build carries nothing of a higher one.
+//  x[j] = the logit of v = lane + 64 j (anything for v >= V); u = the tick's uniform; aw = the tick's mask words behind mask_words()
+//  (level 3 up; below it any array), f = the tick's forced word (level 4).
+//  -> the token; gap = s_tok - m (logp_gap()); S = the kept total.  Where the rule does not apply: -1, gap NaN and S = 1 -- the caller
+//  then takes ITS argmax rule (they differ: the decode kernel's padding -1, AnticipationRNN's NaN-aware order over the allowed entries,
+//  pointwise.hip's am_key).  A forced tick returns f, never -1, with gap NaN and S = 1 where the rule does not apply.
+// s_v = T x_v is ONE rounded f32 product that the NaN test and expf(s_v - m) both read.
+template <int NV, int LEVEL, int NA>
+__device__ __forceinline__ int draw(const float (&x)[NV], float temp, double u, int V, int lane, int top_k, double top_p,
+                                    const unsigned long long (&aw)[NA], int f, float& gap, double& S) {
+    static_assert(LEVEL >= 1 && LEVEL <= 4 && (LEVEL < 3 || NA == NV), "one mask word per 64 tokens from the masked build up");
+    const bool forced = LEVEL >= 4 && is_forced(f, V);
+    float s[NV], ms = -INFINITY;
+    bool nan = false;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        s[j] = lane + 64 * j < V ? x[j] * temp : -INFINITY;
+        nan |= s[j] != s[j];
+        if constexpr (LEVEL < 3) ms = fmaxf(ms, s[j]);
+    }
+    gap = __builtin_nanf("");
+    S = 1.0;
+    if (__ballot(nan)) return forced ? f : -1;
+    if constexpr (LEVEL >= 3) ms = mask_scores<NV>(s, aw, lane);
+    ms = wave_max_dpp(ms);
+    if constexpr (LEVEL >= 2) truncate<NV>(s, ms, top_k, top_p, V, lane);
+    int tok = pick<NV>(s, ms, forced ? 0.0 : u, V, lane, S);
+    if (tok >= 0) {
+        if (forced) tok = f;
+        gap = logp_gap<NV>(s, ms, tok);
+    } else S = 1.0;
+    return forced ? f : tok;
+}
+
+// The level of a call from what it passes (0 = argmax: no uniforms), and the prefix of its launch labels.
+constexpr int level(const void* uniforms, bool trunc, const void* allow, const void* forced) {
+    return !uniforms ? 0 : forced ? 4 : allow ? 3 : trunc ? 2 : 1;
+}
+constexpr const char* prefix(int level) {
+    return level == 4 ? "force_" : level == 3 ? "cons_" : level == 2 ? "trunc_" : level == 1 ? "sample_" : "";
+}
 
 }  // namespace sample

@@ -17,6 +17,7 @@
 #include "layout.h"
 #include "vae.h"
 #include "decode_chain.h"
+#include "sample.h"
 #include <cstdlib>
 #include <string>
 
@@ -294,9 +295,8 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     // top-k / nucleus truncation in front of every draw, or the draws' log-probabilities wanted: the truncating kernels
     // ... a mask of allowed tokens: the masked kernels, which are truncating ones
     // ... forced tokens: the forced kernels, which are masked ones (with or without a mask)
-    const bool force = sampled && forced;
-    const bool cons = sampled && (allow || force);
-    const bool trunc = sampled && ((top_k >= 1 && top_k < V) || top_p < 1.0 || logp || cons);
+    const bool trunc = sampled && ((top_k >= 1 && top_k < V) || top_p < 1.0 || logp || allow || forced);
+    const int level = sample::level(uniforms, trunc, allow, forced);       // (sample.h: 0 = argmax ... 4 = forced)
     if (!sampled && (logp || top_k > 0 || top_p < 1.0 || allow || forced)) return -1;
     if (!(top_p > 0.0 && top_p <= 1.0)) return -1;
     VaeLayout L(c);
@@ -314,8 +314,8 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     const bool chain_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
     // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
     const bool b1_decode = chain_whole && !save && !mask_tick && w.b1ex && w.b1ex + decode_b1_words(B) == w.sync &&
-                           decode_b1_shape_ok(B, H, V, T, G, sampled + trunc + cons + force);
-    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, sampled + trunc + cons + force);   // ... with the beat path inside the same launch
+                           decode_b1_shape_ok(B, H, V, T, G, level);
+    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, level);   // ... with the beat path inside the same launch
     // (a sampled call: the one fused launch that knows the rule is decode_b1.hip's; every other shape samples tick by tick below)
     const bool fused_whole = chain_whole && (!sampled || b1_decode);
     const bool fused_chunked = fused_shape && !sampled && !fused_whole && B > kDecodeChunk && B % kDecodeChunk == 0 &&
@@ -546,7 +546,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
             a.weights = weights + (long)r0 * T * V; a.samples = samples + (long)r0 * T;
             a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0;   // (later chunks: the launcher zeroes the area)
             a.uniforms = uniforms; a.temperature = temperature;                 // (sampled: one whole launch, never chunks)
-            a.trunc = trunc; a.top_k = top_k; a.top_p = top_p; a.logp = logp; a.allow = cons ? allow : nullptr; a.forced = force ? forced : nullptr;
+            a.trunc = trunc; a.top_k = top_k; a.top_p = top_p; a.logp = logp; a.allow = allow; a.forced = forced;   // (null without uniforms: refused above)
             if (mask_tick) { a.mask = mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
             if (save) {
                 a.sv0 = w.svt0 + (long)r0 * H; a.sv1 = w.svt1 + (long)r0 * H; a.sv_stride = (long)T * BH;
@@ -604,17 +604,13 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
                                 (long)T * V, B, V, H, EPI_RELU, s));
             if (draw) INET_TRY(pw_sample_multinomial(weights + (long)t * V, (long)T * V, B, V, samples + t, T,
                                                      multinomial_seed, (uint64_t)t * B, s));
-            else if (force) INET_TRY(pw_sample_forced(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
-                                                      samples + t, T, logp ? logp + t : nullptr, T,
-                                                      allow ? allow + (long)t * ((V + 63) / 64) : nullptr, (long)T * ((V + 63) / 64),
-                                                      forced + t, T, s));
-            else if (cons) INET_TRY(pw_sample_constrained(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
-                                                         samples + t, T, logp ? logp + t : nullptr, T, allow + (long)t * ((V + 63) / 64),
-                                                         (long)T * ((V + 63) / 64), s));
-            else if (trunc) INET_TRY(pw_sample_truncated(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
-                                                        samples + t, T, logp ? logp + t : nullptr, T, s));
-            else if (sampled) INET_TRY(pw_sample_temperature(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T,
-                                                            samples + t, T, s));
+            else if (level == 1) INET_TRY(pw_sample_temperature(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T,
+                                                                samples + t, T, s));
+            // (levels 2 to 4 behind one call: a null `forced` is the constrained call, a null `allow` behind it the truncated one)
+            else if (sampled) INET_TRY(pw_sample_forced(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
+                                                        samples + t, T, logp ? logp + t : nullptr, T,
+                                                        allow ? allow + (long)t * ((V + 63) / 64) : nullptr, (long)T * ((V + 63) / 64),
+                                                        forced ? forced + t : nullptr, T, s));
             else INET_TRY(pw_argmax(weights + (long)t * V, (long)T * V, B, V, samples + t, T, s));
         }
     }

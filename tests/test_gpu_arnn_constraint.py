@@ -1,5 +1,5 @@
 """AnticipationRNN's per-tick token constraints on the GPU (inet_arnn_sample_cx: the masked build of the persistent token pass and
-head_cons_b1_kernel of the per-tick launches, csrc/arnn_gen.hip) and the public surface down from
+head_b1_kernel<NI, 3> of the per-tick launches, csrc/arnn_gen.hip) and the public surface down from
 AnticipationRNNTester.generation(banned_tokens=, fixed_tokens=, clamp_context=).
 
 The reference for the rule is its float64 restatement (tests/decoder_constraint_ref.py) APPLIED TO THE f32 LOGITS THE CALL RETURNED, as
@@ -146,7 +146,7 @@ def test_the_rule_on_the_per_tick_path(R):
 
 
 def test_the_per_tick_path_of_the_token_pass_shape():
-    """option key 14 = 0: H = 256, V = 48 through head_cons_b1_kernel"""
+    """option key 14 = 0: H = 256, V = 48 through head_b1_kernel<NI, 3>"""
     try:
         ops.set_option(14, 0)
         run_case(48, 5, AR.FULL, persistent=False)

@@ -1,5 +1,5 @@
 """GPU: AnticipationRNN's temperature-sampled generation (ConstraintModelGaussianReg.generate, ops.arnn_sample: the sampling build
-of the token pass and head_sample_b1_kernel of the per-tick launches, both in csrc/arnn_gen.hip) and AnticipationRNNTester, against
+of the token pass and head_b1_kernel<NI, 1> of the per-tick launches, both in csrc/arnn_gen.hip) and AnticipationRNNTester, against
 tests/golden/arnn_generate.npz (the reference's generate under np.random.seed, its tester on the arnn_inpaint_small model).
 Every comparison of tokens is exact over all L ticks: the fixture's uniforms sit at least 2e-5 from every CDF step."""
 import types

@@ -1,5 +1,5 @@
 """AnticipationRNN's top-k / nucleus truncated sampling on the GPU (inet_arnn_sample_ex: the truncating build of the persistent token
-pass and head_trunc_b1_kernel of the per-tick launches, csrc/arnn_gen.hip), its log-probabilities and logits, and the public surface
+pass and head_b1_kernel<NI, 2> of the per-tick launches, csrc/arnn_gen.hip), its log-probabilities and logits, and the public surface
 down from AnticipationRNNTester.generation.
 
 The reference for the rule is its float64 restatement (tests/decoder_trunc_ref.py) APPLIED TO THE f32 LOGITS THE CALL RETURNED: those
@@ -126,7 +126,7 @@ def test_the_rule_on_the_per_tick_path(R):
 
 
 def test_the_per_tick_path_of_the_token_pass_shape():
-    """option key 14 = 0: H = 256, V = 48 through head_trunc_b1_kernel"""
+    """option key 14 = 0: H = 256, V = 48 through head_b1_kernel<NI, 2>"""
     try:
         ops.set_option(14, 0)
         run_case(48, 5, AR.FULL, persistent=False)

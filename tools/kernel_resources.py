@@ -42,7 +42,7 @@ def device_asm(src, incdir):
 
 
 def functions(lines):
-    """{symbol: its lines from `.globl SYM` to `.Lfunc_endN:`} without the function's index in its file (block labels, func_begin / end)"""
+    """{symbol: its lines from `.globl SYM` to `.Lfunc_endN:`} without the function's index in its file (block labels, func_begin / end) and the file's count of long branches (post_getpc)"""
     out, sym = {}, None
     for l in lines:
         m = re.match(r"\s*\.globl\s+(\S+).*-- Begin function", l)
@@ -50,7 +50,7 @@ def functions(lines):
             sym = m.group(1)
             out[sym] = []
         if sym is not None:
-            l = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", re.sub(r"BB\d+_", "BB_", l))
+            l = re.sub(r"\.L(func_begin|func_end|post_getpc)\d+", r".L\1", re.sub(r"BB\d+_", "BB_", l))
             out[sym].append(re.sub(r"\s+", " ", l))            # (the comment column behind a label moves with the index's width)
             if l.startswith(".Lfunc_end:"):
                 sym = None
