@@ -467,6 +467,37 @@ int inet_arnn_sample_cx(int R, int L, int E, int Hc, int H, int U, int V, const 
                         const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
                         int64_t* tokens, float* ws, int64_t ws_floats, int top_k, double top_p, float* logp, float* logits,
                         const uint64_t* allow, void* stream);
+/* The same behind FORCED TOKENS: the log-probability the model gives to a filling it did not draw.  The rule is the one stated for
+ * inet_vae_decoder_sample_fx (word for word: layout, free tick, forced tick and consequences (a) to (e)), applied
+ * to s = temperature * logits of the note head, with the two model-specific points of inet_arnn_sample_cx.
+ *
+ * Layout.
+ *  - `forced` is an array of `int32` `[rows][L]`.
+ *  - A value `f` with `0 <= f < V` forces that tick.
+ *  - Every other value makes the tick free.  The Python surfaces write -1 for a free tick.
+ *  - A null `forced` means no tick is forced: then this IS inet_arnn_sample_cx.
+ *
+ * At a forced tick with token `f`:
+ *  - Steps 0 to 2 of the rule run on the tick's logits: the NaN test, the mask, m, and the truncation.  The tick's uniform is not used.
+ *    The rule is evaluated as with u = 0, so a uniform of 1.0, 2.0 or NaN at a forced tick causes no fallback.
+ *  - The token is `f`.  It is stored in `tokens` and fed back into tick t + 1.  This holds whether or not `f` is allowed or kept, and on
+ *    a fallback tick too.
+ *  - logp = (s_f - m) - log S as f32.  It is exactly -inf when `f` is banned or truncated away.  It is NaN where the rule does not
+ *    apply: a NaN among s, or m or S not finite.
+ *  - The note head is not ReLU'd.  On a fallback tick a free tick takes inet_arnn_sample_cx's argmax over the allowed entries.  A forced
+ *    tick takes `f`.
+ *  - The returned logits stay the unmasked ones.
+ *
+ * A forced call is a truncating, masked call (allow nullable: no token banned).  It runs the forced build of the persistent token pass
+ * (V <= 64) or, for the other shapes, the forced head of the per-tick launches, and never a kernel that ignores the forced words: its
+ * launch labels start with "force_" (force_arnn_token_sample R.. L.. V.., force_arnn_ticks L.. V..).
+ * -1 where inet_arnn_sample_cx returns it (so for `forced` without uniforms). */
+int inet_arnn_sample_fx(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
+                        int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,
+                        const float* W_ih1, const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
+                        const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
+                        int64_t* tokens, float* ws, int64_t ws_floats, int top_k, double top_p, float* logp, float* logits,
+                        const uint64_t* allow, const int32_t* forced, void* stream);
 /* nn.Embedding forward / backward (rows of E floats gathered by int64 index; backward accumulates with atomics).
  * row_scale (nullable, [rows]) multiplies each gathered row: the Dropout2d on the shifted note embeddings
  * (drop_input, anticipation_rnn_gauss_reg_model.py:437-442) and the all-zero first time step (:373-376). */

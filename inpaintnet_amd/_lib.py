@@ -146,6 +146,7 @@ _SIGNATURES = {
     "inet_arnn_sample": (C.c_int, [_I] * 7 + [_P, _P, _L, _L] + [_P] * 12 + [_F, _P, _P, _P, _P, _L, _P]),
     "inet_arnn_sample_ex": (C.c_int, [_I] * 7 + [_P, _P, _L, _L] + [_P] * 12 + [_F, _P, _P, _P, _P, _L, _I, C.c_double, _P, _P, _P]),
     "inet_arnn_sample_cx": (C.c_int, [_I] * 7 + [_P, _P, _L, _L] + [_P] * 12 + [_F, _P, _P, _P, _P, _L, _I, C.c_double, _P, _P, _P, _P]),
+    "inet_arnn_sample_fx": (C.c_int, [_I] * 7 + [_P, _P, _L, _L] + [_P] * 12 + [_F, _P, _P, _P, _P, _L, _I, C.c_double, _P, _P, _P, _P, _P]),
     "inet_side_wait": (C.c_int, [_P]),
     "inet_twin_stream": (C.c_int, [C.POINTER(C.c_void_p)]),
     "inet_debug_read": (C.c_int, [_P, _L]),

@@ -398,7 +398,7 @@ class ConstraintModelGaussianReg(Model):
 
     @torch.no_grad()
     def generate(self, tensor_score, tensor_metadata, constraints_location, temperature=1., top_k=None, top_p=None, keep_weights=False,
-                 allowed=None):
+                 allowed=None, forced=None, uniforms=None):
         """Temperature-sampled generation (anticipation_rnn_gauss_reg_model.py:570-679).  Shapes (1, L), (1, L, M), (1, L) as the
         reference takes them, or a batch (B, 1, L), (B, 1, L, M), (B, 1, L) of independent rows.  Leaves the model in eval().
 
@@ -420,7 +420,14 @@ class ConstraintModelGaussianReg(Model):
         allowed (bool (L, V) for the one row, (B, L, V) for a batch; host or device): the tokens each tick may return, applied inside
         the launch in front of the truncation (ops.arnn_sample's `allowed`) -- a tick with one token allowed
         feeds THAT token back, so what follows is generated from it.  ValueError for a tick with nothing allowed.  It does not change
-        when last_logp is left: with top_k or top_p given, and then a one-token tick scores exactly 0.  None: the call as it was."""
+        when last_logp is left: with top_k or top_p given, and then a one-token tick scores exactly 0.  None: the call as it was.
+
+        forced (an int tensor (L,) for the one row, (B, L) for a batch, -1 for a free tick; host or device): the token of each forced
+        tick, returned and fed back whatever the mask, the truncation and the uniform hold, and scored under the masked and truncated
+        distribution a draw would have used (ops.arnn_sample's `forced`): -inf for a banned or truncated
+        token.  ValueError for a wrong shape or dtype or a value outside [-1, V), before np.random is touched.  A forced call always
+        leaves last_logp.  uniforms (float64 (B, L)): used instead of the np.random.random_sample((B, L)) draw, and np.random is not
+        touched; None: the stream is consumed exactly as before.  A call without the two runs the kernels it always ran."""
         k = ops._top_k(top_k)
         if top_p is not None and not (0.0 < float(top_p) <= 1.0):
             raise ValueError(f"generate: top_p {top_p!r} outside (0, 1]")
@@ -432,6 +439,19 @@ class ConstraintModelGaussianReg(Model):
                 raise ValueError(f"generate: allowed must be bool of shape {want + (self.num_notes_per_voice[0],)}, got {allowed.dtype} "
                                  f"{tuple(allowed.shape)}")
             allowed = ops.pack_allowed(allowed)                    # (ValueError for a tick with nothing allowed)
+        rows = tensor_score.shape[0] if tensor_score.dim() == 3 else 1
+        if forced is not None:
+            forced = torch.as_tensor(forced)
+            want = (rows, tensor_score.shape[-1]) if tensor_score.dim() == 3 else (tensor_score.shape[-1],)
+            if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool or tuple(forced.shape) != want:
+                raise ValueError(f"generate: forced must be an int tensor of shape {want}, got {forced.dtype} {tuple(forced.shape)}")
+            if bool(((forced < -1) | (forced >= self.num_notes_per_voice[0])).any()):
+                raise ValueError(f"generate: forced holds a value outside [-1, {self.num_notes_per_voice[0]})")
+        if uniforms is not None:
+            uniforms = np.asarray(uniforms)
+            if uniforms.dtype != np.float64 or uniforms.shape != (rows, tensor_score.shape[-1]):
+                raise ValueError(f"generate: uniforms must be float64 of shape {(rows, tensor_score.shape[-1])}, got {uniforms.dtype} "
+                                 f"{uniforms.shape}")
         self.last_logp = self.last_weights = None
         self.eval()
         batched = tensor_score.dim() == 3
@@ -460,14 +480,16 @@ class ConstraintModelGaussianReg(Model):
         for l in range(2):
             x, hT, cT = self._lstm(f"lstm_generation.{l}", x, False)
             hc[:, l, 0], hc[:, l, 1] = hT.reshape(B, H), cT.reshape(B, H)
-        u = np.random.random_sample((B, L))
+        u = np.random.random_sample((B, L)) if uniforms is None else uniforms
         emb, *net = self._generation_weights()
-        score_it = top_k is not None or top_p is not None
+        score_it = top_k is not None or top_p is not None or forced is not None
         logp = weights = None
         if score_it or keep_weights or allowed is not None:
+            kw = {} if allowed is None else {"allowed": allowed.view(B, L, -1).to(dev).contiguous()}
+            if forced is not None:
+                kw["forced"] = forced.to(dev).to(torch.int32).reshape(B, L).contiguous()
             toks, logp, weights = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc, top_k=k, top_p=top_p,
-                                                  want_logp=score_it, want_logits=bool(keep_weights),
-                                                  **({} if allowed is None else {"allowed": allowed.view(B, L, -1).to(dev).contiguous()}))
+                                                  want_logp=score_it, want_logits=bool(keep_weights), **kw)
         else:
             toks = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc)
         torch.cuda.synchronize()

@@ -22,6 +22,19 @@ def _num_variations(n):
     return int(n)
 
 
+def _fixed_ticks(fixed_tokens, W, measure_seq_len, V):
+    """generation()'s fixed_tokens as a flat int64 (W,) host tensor, -1 = a free tick; ValueError for a wrong shape, dtype or range"""
+    fixed = torch.as_tensor(fixed_tokens).cpu()
+    if fixed.is_floating_point() or fixed.dtype == torch.bool or fixed.numel() != W or \
+            (fixed.dim() != 1 and tuple(fixed.shape) != (W // measure_seq_len, measure_seq_len)):
+        raise ValueError(f"fixed_tokens must be an int tensor of shape {(W // measure_seq_len, measure_seq_len)} or "
+                         f"{(W,)}, got {fixed.dtype} {tuple(fixed.shape)}")
+    fixed = fixed.long().reshape(W)
+    if bool(((fixed < -1) | (fixed >= V)).any()):
+        raise ValueError(f"fixed_tokens: token indices in [0, {V}), or -1 for a free tick")
+    return fixed
+
+
 class AnticipationRNNTester(object):
     def __init__(self, dataset, model):
         self.dataset = dataset
@@ -33,6 +46,7 @@ class AnticipationRNNTester(object):
         self.batch_size = 1
         self.measure_seq_len = 24                    # (:16-18: set from the dataset, then fixed to 24)
         self.last_logp = None                        # generation(top_k= / top_p=): (num_variations, num_measures_gen)
+        self.last_tick_logp = None                   # score(): (N, num_measures_gen, measure_seq_len)
 
     def _to_score(self, tensor):
         fn = getattr(self.dataset, "tensor_to_score", None)
@@ -101,7 +115,7 @@ class AnticipationRNNTester(object):
                                      tensor_metadata.view(num_voices, seq_len, num_metadata), start_measure=8, num_measures_gen=2)
 
     def generation(self, tensor_score, start_measure, num_measures_gen, tensor_metadata=None, temperature=1.5, num_variations=1,
-                   top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None, clamp_context=False):
+                   top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None, clamp_context=False, score_fixed=False):
         """Generates measures start_measure .. start_measure + num_measures_gen - 1 (1-based) of a score with temperature 1.5
         (:185-243) -> (gen_score | None, gen_score_tensor (1, L): past | generated | future, original_score | None).
 
@@ -118,6 +132,10 @@ class AnticipationRNNTester(object):
         constrained one.  Every variation gets the same mask, and with one of the three given the batched call is taken for
         num_variations=1 too.  ValueError for an index outside [0, V) (fixed: other than -1), a ban of the whole vocabulary, or -- with
         clamp_context -- a score token outside [0, V).  A fixed tick adds exactly 0 to last_logp.
+
+        score_fixed=True: the fixed ticks become FORCED ticks under a mask of all ones (generate()'s `forced`): the
+        same notes are kept and fed back -- a fixed tick still wins over a ban --, and last_logp, which such a call always leaves,
+        includes what the model thinks of the kept notes instead of exactly 0.
 
         tensor_score (1, L) tokens (None: a random score of dataset.iterator_gen()); its metadata come from
         dataset.transposed_score_and_metadata_tensors where the dataset has it and a score can be built, else from
@@ -146,7 +164,80 @@ class AnticipationRNNTester(object):
         tensor_score = tensor_score[:, :num_measures * self.measure_seq_len]
         tensor_metadata = tensor_metadata[:, :num_measures * self.measure_seq_len]
         return self._generate_window(tensor_score, tensor_metadata, start_measure, num_measures_gen, temperature, num_variations,
-                                     top_k, top_p, banned_tokens, fixed_tokens, clamp_context)
+                                     top_k, top_p, banned_tokens, fixed_tokens, clamp_context, score_fixed)
+
+    def score(self, tensor_score, start_measure, num_measures_gen, fillings, tensor_metadata=None, temperature=1.0, top_k=None,
+              top_p=None, banned_tokens=None):
+        """The model's log-probability of GIVEN fillings of measures start_measure .. start_measure + num_measures_gen - 1 (1-based) --
+        the user's, the original measures, an InpaintNet filling -- on the scale of generation()'s last_logp: -> float32 (N,
+        num_measures_gen), the window's log-probabilities summed per measure under softmax(temperature * logits) behind the same top_k
+        / top_p truncation and bans a draw would have seen.  -inf where a note is banned or truncated away, NaN where the rule does not
+        apply; both propagate.
+
+        fillings: an int tensor (N, num_measures_gen, measure_seq_len) with every value in [0, V).  The score is expanded to N rows as
+        generation() expands it for variations; every tick of the window is forced to the filling and every tick outside it to the
+        score's own token, the true context (ValueError for a token outside [0, V) there, as under clamp_context) -- ONE forced
+        generate() call with uniforms of zeros: np.random is not touched.  banned_tokens act inside the window only, as in generation().
+        Leaves self.last_tick_logp (N, num_measures_gen, measure_seq_len) and model.last_weights (N, L, V).  tensor_score and
+        tensor_metadata as generation() takes them (tensor_score is required)."""
+        measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
+        V = int(self.model.num_notes_per_voice[0])
+        fill = torch.as_tensor(fillings)
+        if fill.is_floating_point() or fill.is_complex() or fill.dtype == torch.bool or fill.dim() != 3 or fill.size(0) < 1 or \
+                tuple(fill.shape[1:]) != (num_measures_gen, measure_seq_len):
+            raise ValueError(f"score: fillings must be an int tensor of shape (N, {num_measures_gen}, {measure_seq_len}), got {fill.dtype} "
+                             f"{tuple(fill.shape)}")
+        fill = fill.cpu().long()
+        if bool(((fill < 0) | (fill >= V)).any()):
+            raise ValueError(f"score: fillings hold a token outside [0, {V})")
+        if tensor_score is None:
+            raise ValueError("score: tensor_score is required")
+        original_score = self._to_score(tensor_score) if tensor_metadata is None else None
+        if original_score is not None and hasattr(self.dataset, "transposed_score_and_metadata_tensors"):
+            trans_interval = self.dataset.get_transpostion_interval_from_semitone(0)
+            tensor_score, tensor_metadata = self.dataset.transposed_score_and_metadata_tensors(original_score, trans_interval)
+        elif tensor_metadata is None:
+            raise ValueError("score: pass tensor_metadata= (the dataset cannot derive it: no tensor_to_score / "
+                             "transposed_score_and_metadata_tensors)")
+        tensor_score, tensor_metadata = torch.as_tensor(tensor_score), torch.as_tensor(tensor_metadata)
+        num_measures = min(16, tensor_score.size(1) // self.measure_seq_len)
+        tensor_score = tensor_score[:, :num_measures * self.measure_seq_len]
+        tensor_metadata = tensor_metadata[:, :num_measures * self.measure_seq_len]
+        n, L = fill.size(0), tensor_score.size(1)
+        start_tick = (start_measure - 1) * measure_seq_len
+        end_tick = start_tick + num_measures_gen * measure_seq_len
+        if start_tick < 0 or end_tick > L:
+            raise ValueError(f"score: measures {start_measure} .. {start_measure + num_measures_gen - 1} lie outside the score's {L} ticks")
+        allowed = self._allowed(tensor_score, start_tick, end_tick, measure_seq_len, banned_tokens, None, False)
+        own = tensor_score[0].cpu().long()
+        outside = torch.ones(L, dtype=torch.bool)
+        outside[start_tick:end_tick] = False
+        if bool(((own < 0) | (own >= V))[outside].any()):
+            raise ValueError(f"score: the score has tokens outside [0, {V}) outside the window")
+        forced = own.unsqueeze(0).repeat(n, 1)
+        forced[:, start_tick:end_tick] = fill.reshape(n, -1)
+        tensor_score = to_cuda_variable_long(tensor_score)
+        tensor_metadata = to_cuda_variable_long(tensor_metadata)
+        self.last_logp = self.last_tick_logp = None
+        self.model.generate(tensor_score=tensor_score[:1].unsqueeze(0).expand(n, 1, L).contiguous(),
+                            tensor_metadata=tensor_metadata[:1].unsqueeze(0).expand(n, 1, L, -1).contiguous(),
+                            constraints_location=self._window_location(tensor_score, start_tick, end_tick)[:1].unsqueeze(0)
+                            .expand(n, 1, L).contiguous(),
+                            temperature=temperature, top_k=top_k, top_p=top_p, keep_weights=True, forced=forced,
+                            uniforms=np.zeros((n, L), dtype=np.float64),
+                            **({} if allowed is None else {"allowed": allowed.unsqueeze(0).expand(n, -1, -1)}))
+        self.last_tick_logp = self.model.last_logp[:, 0, start_tick:end_tick].reshape(n, num_measures_gen, measure_seq_len)
+        return self.last_tick_logp.sum(-1)
+
+    @staticmethod
+    def _window_location(tensor_score, start_tick, end_tick):
+        """1 = constrained tick, 0 = to be generated: the window [start_tick, end_tick) of generation()"""
+        constraints_location = torch.zeros_like(tensor_score)
+        if start_tick > 0:
+            constraints_location[:, :start_tick] = 1
+        if end_tick < constraints_location.size(1) - 1:
+            constraints_location[:, end_tick:] = 1
+        return constraints_location
 
     def _allowed(self, tensor_score, start_tick, end_tick, measure_seq_len, banned_tokens, fixed_tokens, clamp_context):
         """generation()'s constraints as one row of generate()'s mask: bool (L, V) on the host, or None without constraints.  The bans
@@ -163,14 +254,7 @@ class AnticipationRNNTester(object):
                 raise ValueError("banned_tokens bans the whole vocabulary")
             allow[start_tick:end_tick, banned] = False
         if fixed_tokens is not None:
-            fixed = torch.as_tensor(fixed_tokens).cpu()
-            if fixed.is_floating_point() or fixed.dtype == torch.bool or fixed.numel() != W or \
-                    (fixed.dim() != 1 and tuple(fixed.shape) != (W // measure_seq_len, measure_seq_len)):
-                raise ValueError(f"fixed_tokens must be an int tensor of shape {(W // measure_seq_len, measure_seq_len)} or "
-                                 f"{(W,)}, got {fixed.dtype} {tuple(fixed.shape)}")
-            fixed = fixed.long().reshape(W)
-            if bool(((fixed < -1) | (fixed >= V)).any()):
-                raise ValueError(f"fixed_tokens: token indices in [0, {V}), or -1 for a free tick")
+            fixed = _fixed_ticks(fixed_tokens, W, measure_seq_len, V)
             one = torch.zeros(W, V, dtype=torch.bool)
             one.scatter_(1, fixed.clamp(min=0).unsqueeze(-1), True)
             allow[start_tick:end_tick] = torch.where((fixed >= 0).unsqueeze(-1), one, allow[start_tick:end_tick])
@@ -186,13 +270,24 @@ class AnticipationRNNTester(object):
         return allow
 
     def _generate_window(self, tensor_score, tensor_metadata, start_measure, num_measures_gen, temperature=1.5, num_variations=1,
-                         top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None, clamp_context=False):
+                         top_k=None, top_p=None, banned_tokens=None, fixed_tokens=None, clamp_context=False, score_fixed=False):
         num_variations = _num_variations(num_variations)
         self.last_logp = None
         measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
         start_tick = (start_measure - 1) * measure_seq_len
         end_tick = start_tick + num_measures_gen * measure_seq_len
-        allowed = self._allowed(tensor_score, start_tick, end_tick, measure_seq_len, banned_tokens, fixed_tokens, clamp_context)   # (the argument errors first)
+        forced = None
+        if score_fixed and fixed_tokens is not None:
+            # the fixed ticks as forced ticks under a mask of all ones: the bans and the clamp alone make the mask
+            V, L = int(self.model.num_notes_per_voice[0]), int(tensor_score.shape[1])
+            fixed = _fixed_ticks(fixed_tokens, end_tick - start_tick, measure_seq_len, V)
+            allowed = self._allowed(tensor_score, start_tick, end_tick, measure_seq_len, banned_tokens, None, clamp_context)
+            forced = torch.full((L,), -1, dtype=torch.int64)
+            forced[start_tick:end_tick] = fixed
+            if allowed is not None:
+                allowed[forced >= 0] = True
+        else:
+            allowed = self._allowed(tensor_score, start_tick, end_tick, measure_seq_len, banned_tokens, fixed_tokens, clamp_context)   # (the argument errors first)
         constraints_location = torch.zeros_like(tensor_score)
         if start_tick > 0:
             constraints_location[:, :start_tick] = 1
@@ -202,7 +297,7 @@ class AnticipationRNNTester(object):
         tensor_future = tensor_score[:, end_tick:]
         tensor_target = tensor_score[:, start_tick:end_tick]
         original_tensor = torch.cat((tensor_past, tensor_target, tensor_future), 1)
-        if num_variations == 1 and top_k is None and top_p is None and allowed is None:
+        if num_variations == 1 and top_k is None and top_p is None and allowed is None and forced is None:
             _, gen_target, _ = self.model.generate(tensor_score=tensor_score, tensor_metadata=tensor_metadata,
                                                    constraints_location=constraints_location, temperature=temperature)
             gen_target = gen_target[:, start_tick:end_tick]
@@ -214,7 +309,8 @@ class AnticipationRNNTester(object):
                                         tensor_metadata=tensor_metadata[:1].unsqueeze(0).expand(n, 1, L, -1).contiguous(),
                                         constraints_location=constraints_location[:1].unsqueeze(0).expand(n, 1, L).contiguous(),
                                         temperature=temperature, top_k=top_k, top_p=top_p,
-                                        **({} if allowed is None else {"allowed": allowed.unsqueeze(0).expand(n, -1, -1)}))
+                                        **({} if allowed is None else {"allowed": allowed.unsqueeze(0).expand(n, -1, -1)}),
+                                        **({} if forced is None else {"forced": forced.unsqueeze(0).expand(n, -1)}))
         gen_target = gen[:, 0, start_tick:end_tick].to(tensor_score.dtype)
         gen_score_tensor = torch.cat((tensor_past.expand(n, -1), gen_target, tensor_future.expand(n, -1)), 1)
         if self.model.last_logp is not None:

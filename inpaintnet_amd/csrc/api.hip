@@ -471,12 +471,12 @@ int64_t inet_arnn_sample_ws_floats(int R, int L, int E, int Hc, int H, int U, in
     if (R < 1 || L < 1 || E <= 0 || Hc < 0 || H <= 0 || H % 16 || U <= 0 || V <= 0) return -1;
     return (int64_t)arnn_sample_ws_floats(ArnnGenNet{E, Hc, H, U, V}, R, L);
 }
-int inet_arnn_sample_cx(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
+int inet_arnn_sample_fx(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
                         int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,
                         const float* W_ih1, const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
                         const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
                         int64_t* tokens, float* ws, int64_t ws_floats, int top_k, double top_p, float* logp, float* logits,
-                        const uint64_t* allow, void* stream) {
+                        const uint64_t* allow, const int32_t* forced, void* stream) {
     if (R < 1 || L < 1 || E <= 0 || Hc < 0 || H <= 0 || H % 16 || U <= 0 || V <= 0 || !emb || (Hc && !oc0) || !W_ih0 || !b_ih0 ||
         !W_hh0 || !b_hh0 || !W_ih1 || !b_ih1 || !W_hh1 || !b_hh1 || !W1 || !b1 || !W2 || !b2 || !uniforms || !tokens || !ws)
         return -1;
@@ -485,7 +485,17 @@ int inet_arnn_sample_cx(int R, int L, int E, int Hc, int H, int U, int V, const 
     const ArnnGenNet net{E, Hc, H, U, V, emb, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2};
     if (ws_floats < (int64_t)arnn_sample_ws_floats(net, R, L)) return -1;
     return arnn_sample(net, R, L, oc0, (long)oc_row_stride, (long)oc_batch_stride, temperature, uniforms, hc_init, (long long*)tokens, ws,
-                       (hipStream_t)stream, top_k, top_p, logp, logits, (const unsigned long long*)allow);
+                       (hipStream_t)stream, top_k, top_p, logp, logits, (const unsigned long long*)allow, (const int*)forced);
+}
+int inet_arnn_sample_cx(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
+                        int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,
+                        const float* W_ih1, const float* b_ih1, const float* W_hh1, const float* b_hh1, const float* W1, const float* b1,
+                        const float* W2, const float* b2, float temperature, const double* uniforms, const float* hc_init,
+                        int64_t* tokens, float* ws, int64_t ws_floats, int top_k, double top_p, float* logp, float* logits,
+                        const uint64_t* allow, void* stream) {
+    return inet_arnn_sample_fx(R, L, E, Hc, H, U, V, emb, oc0, oc_row_stride, oc_batch_stride, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1,
+                               W_hh1, b_hh1, W1, b1, W2, b2, temperature, uniforms, hc_init, tokens, ws, ws_floats, top_k, top_p, logp,
+                               logits, allow, nullptr, stream);
 }
 int inet_arnn_sample_ex(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
                         int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,

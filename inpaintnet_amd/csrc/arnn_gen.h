@@ -23,6 +23,9 @@ size_t arnn_sample_ws_floats(const ArnnGenNet& net, int R, int L);
 // Truncation on or one of the two pointers given: the truncating kernels (labels trunc_...); otherwise the kernels of the sampling build.
 // allow [R][L][ceil(V / 64)] (nullable): sample.h's words of allowed tokens per (row, tick), applied in front of the truncation inside the
 // launch -- the masked kernels (labels cons_...), which are truncating ones; null: the call above.
+// forced [R][L] (nullable): sample.h's forced words per (row, tick); a value in [0, V) is that tick's token, returned, fed back and scored
+// -- the forced kernels (labels force_...), which are masked ones (allow nullable); null: the call above.
 int arnn_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
                 const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k = 0,
-                double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr);
+                double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr,
+                const int* forced = nullptr);

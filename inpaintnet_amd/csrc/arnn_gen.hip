@@ -40,6 +40,8 @@
 // head_b1_kernel<NI, 2> does the same for the per-tick launches.  A call without truncation, logp or logits runs the sampling build.
 // The masked build (MASK = true, V <= 64: inet_arnn_sample_cx) puts sample.h's per-tick token constraints in front of the truncation;
 // head_b1_kernel<NI, 3> does the same for the per-tick launches.  A call without a mask runs the kernels it ran before.
+// The forced build (FORCE = true, V <= 64: inet_arnn_sample_fx) puts sample.h's forced tokens behind the constraints: a forced tick returns
+// and feeds back its token and reports that token's log-probability; head_b1_kernel<NI, 4> does the same for the per-tick launches.
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -76,6 +78,8 @@ struct GenArgs {
     int top_k; double top_p; float* logp; float* logits;
     // masked build (MASK: sample.h's token constraints in front of the truncation): the allowed tokens' words [rows][L][ceil(V / 64)]
     const unsigned long long* allow;
+    // forced build (FORCE: sample.h's forced tokens behind the constraints): the forced words [rows][L], a value in [0, V) forces its tick
+    const int* forced;
 };
 #define GEN_STAMP(who, t, i) do { if (a.stamps && tid == 0) a.stamps[((long)(who) * a.L + (t)) * 8 + (i)] = wall_clock64(); } while (0)
 
@@ -166,10 +170,16 @@ __device__ __forceinline__ void recurrent_role(const GenArgs& a, int k, const fl
 // ALLOWED logits alone (the banned ones count as -inf and are no candidates, a NaN at a banned place is no NaN), so its token is an
 // allowed one whatever the logits hold.  The logits the call returns stay the unmasked ones.  One word per tick: V <= 64, as the
 // truncating build.
-template <int NV, bool SAMPLE, bool TRUNC = false, bool MASK = false>
+// FORCE (the forced build of the masked build: inet_arnn_sample_fx; sample.h has the rule): the tick's forced word arrives like the mask
+// word -- requested a tick early through a wave-uniform address, held in scalar registers by every wave of C -- so the token stays a
+// function of the logits, u, the mask word, the forced word and kernel arguments.  A forced tick runs the tick's steps with u = 0.0 for S
+// alone, then takes tok = f and the gap of f: -inf where f is banned or truncated away.  On a fallback tick f skips the argmax block.  A
+// forced call without a mask (a null `allow`: a kernel argument, wave-uniform) takes a word of all ones, which mask_words() trims.
+template <int NV, bool SAMPLE, bool TRUNC = false, bool MASK = false, bool FORCE = false>
 __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
     static_assert(SAMPLE || !TRUNC, "the truncating build is a sampling build");
     static_assert(TRUNC || !MASK, "the masked build is a truncating build");
+    static_assert(MASK || !FORCE, "the forced build is a masked build");
     static_assert(!MASK || NV == 1, "the masked build reads ONE word per tick: NW = ceil(V / 64) = NV = 1");
     __shared__ __attribute__((aligned(16))) float xs[2][XS];
     __shared__ __attribute__((aligned(16))) float us[GH];
@@ -268,10 +278,14 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
         double u = 0.0, u_next = SAMPLE ? urow[0] : 0.0;       // (the next tick's uniform is requested a tick early)
         [[maybe_unused]] const unsigned long long* const arow = MASK ? a.allow + (long)team * a.L * NV : nullptr;
         [[maybe_unused]] unsigned long long aw[NV] = {}, aw_next[NV] = {};   // (masked build: ... and its words of allowed tokens)
+        [[maybe_unused]] const bool masked = !FORCE || a.allow;             // (forced build: a call without a mask has words of all ones)
         if constexpr (MASK) {
 #pragma unroll
-            for (int j = 0; j < NV; ++j) aw_next[j] = arow[j];
+            for (int j = 0; j < NV; ++j) aw_next[j] = masked ? arow[j] : ~0ull;
         }
+        [[maybe_unused]] const int* const frow = FORCE ? a.forced + (long)team * a.L : nullptr;
+        [[maybe_unused]] int fw = -1, fw_next = -1;           // (forced build: ... and its forced word)
+        if constexpr (FORCE) fw_next = frow[0];
         if (unit) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) pr[g] = pre[g * GH + tid];
@@ -290,8 +304,12 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
 #pragma unroll
                 for (int j = 0; j < NV; ++j) {
                     aw[j] = aw_next[j];
-                    if (more) aw_next[j] = arow[(long)(t + 1) * NV + j];
+                    if (more && masked) aw_next[j] = arow[(long)(t + 1) * NV + j];
                 }
+            }
+            if constexpr (FORCE) {
+                fw = fw_next;
+                if (more) fw_next = frow[t + 1];
             }
             GEN_STAMP(0, t, 0);
             if (unit) {
@@ -366,9 +384,11 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                 if constexpr (SAMPLE) {
                     // the sampling head (sample.h): a NaN logit, a non-finite total or a uniform outside [0, 1) keep the argmax rule.
                     // The steps of sample::draw stand here in the pass's own order, not as one call: through draw() the masked build
-                    // ran 3 % slower and the V > 64 sampling build 0.2 % -- a change to the rule is made here too
+                    // ran 3 % slower and the V > 64 sampling build 0.2 % -- a change to the rule is made here too,
+                    // and the forced step (u = 0.0 for S, then tok = f and the gap of f) exists in both places
                     float sv[NV], ms = -INFINITY;
                     bool nan = false;
+                    [[maybe_unused]] const bool forced = FORCE && sample::is_forced(fw, a.V);
 #pragma unroll
                     for (int j = 0; j < NV; ++j) {
                         sv[j] = lane + 64 * j < a.V ? lg[j] * a.temp : -INFINITY;
@@ -390,7 +410,8 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                             if constexpr (MASK) ms = sample::mask_scores<NV>(sv, aw, lane);
                             const float mw = wave_max_dpp(ms);
                             sample::truncate<NV>(sv, mw, a.top_k, a.top_p, a.V, lane);
-                            bi = sample::pick<NV>(sv, mw, u, a.V, lane, tot);
+                            bi = sample::pick<NV>(sv, mw, FORCE && forced ? 0.0 : u, a.V, lane, tot);
+                            if constexpr (FORCE) { if (forced && bi >= 0) bi = fw; }
                             if (bi >= 0) gap = sample::logp_gap<NV>(sv, mw, bi);
                         }
                         // (a tick that falls back to the argmax rule below files S = NaN: its logp comes out NaN)
@@ -399,6 +420,7 @@ __global__ __launch_bounds__(NT) void arnn_token_pass_kernel(GenArgs a) {
                             *reinterpret_cast<double*>(term) = bi >= 0 ? tot : (double)__builtin_nanf("");
                             term[2] = gap;
                         }
+                        if constexpr (FORCE) { if (forced) bi = fw; }    // (on a fallback tick too: f skips the argmax block)
                     } else {
                         if (!__ballot(nan)) bi = sample::pick<NV>(sv, wave_max_dpp(ms), u, a.V, lane, tot);
                     }
@@ -535,6 +557,8 @@ bool arnn_token_pass_ok(const ArnnGenNet& n) {
 bool arnn_token_trunc_ok(const ArnnGenNet& n) { return arnn_token_pass_ok(n) && n.V <= 64; }
 // The masked build (<1, true, true, true>) fits where the truncating build does: one word of allowed tokens per tick.
 bool arnn_token_cons_ok(const ArnnGenNet& n) { return arnn_token_trunc_ok(n); }
+// The forced build (<1, true, true, true, true>) fits where the masked build does: one forced word per tick in scalar registers.
+bool arnn_token_force_ok(const ArnnGenNet& n) { return arnn_token_cons_ok(n); }
 
 // tables | exchange + status | stamps (2 x L x 8 64-bit words, written only under INET_ARNN_GEN_STAMPS=1: tools/arnn_token_pass.py)
 size_t arnn_token_pass_ws_floats(int L, int V) { return (size_t)L * G4 + (size_t)V * G4 + (size_t)kExFloats + 64 + (size_t)32 * L; }
@@ -602,16 +626,17 @@ size_t arnn_token_sample_ws_floats(int R, int L, int V) {
 
 // trunc: the truncating build (truncation on, or a logp / logits pointer given); its labels start with trunc_
 // allow (with trunc; V <= 64: arnn_token_cons_ok): the masked build, [R][L][1] words of allowed tokens; its labels start with cons_
+// forced (with trunc; arnn_token_force_ok): the forced build, [R][L] forced words, allow nullable; its labels start with force_
 int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
                       const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, bool trunc, int top_k,
-                      double top_p, float* logp, float* logits, const unsigned long long* allow) {
+                      double top_p, float* logp, float* logits, const unsigned long long* allow, const int* forced) {
     const int V = net.V, n = sample_teams(R);
     float* pre = ws;
     float* T0 = pre + (size_t)n * L * G4;
     unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
     const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
     char label[64];
-    const int level = sample::level(uniforms, trunc, allow, nullptr);
+    const int level = sample::level(uniforms, trunc, allow, forced);
     std::snprintf(label, sizeof label, "%sarnn_token_sample R%d L%d V%d", level >= 2 ? sample::prefix(level) : "", R, L, V);
     for (int r0 = 0; r0 < R; r0 += n) {                          // R > teams: successive launches of up to `n` rows
         const int rows = std::min(n, R - r0);
@@ -625,10 +650,12 @@ int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, lon
         a.top_k = top_k; a.top_p = top_p;
         a.logp = logp ? logp + (long)r0 * L : nullptr; a.logits = logits ? logits + (long)r0 * L * V : nullptr;
         a.allow = allow ? allow + (long)r0 * L * ((V + 63) / 64) : nullptr;     // (this launch's rows, like uniforms, logp and logits)
+        a.forced = forced ? forced + (long)r0 * L : nullptr;
         ProfScope prof(PROF_GRU_FWD, 2.0 * rows * L * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH), s, label,
                        4.0 * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH + (double)(rows * L + V) * G4));
         const dim3 grid(a.stride == 8 ? 13 * 8 : 13 * rows);
-        if (allow) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true>), grid, dim3(NT), 0, s, a);   // (V <= 64: arnn_token_cons_ok)
+        if (forced) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true, true>), grid, dim3(NT), 0, s, a);   // (arnn_token_force_ok)
+        else if (allow) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true>), grid, dim3(NT), 0, s, a);   // (V <= 64: arnn_token_cons_ok)
         else if (trunc) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true>), grid, dim3(NT), 0, s, a);    // (V <= 64: arnn_token_trunc_ok)
         else if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true>), grid, dim3(NT), 0, s, a);
         else hipLaunchKernelGGL((arnn_token_pass_kernel<2, true>), grid, dim3(NT), 0, s, a);
@@ -756,12 +783,15 @@ __device__ __forceinline__ int argmax_wave(const float* lg, const unsigned long 
 //     distribution (NaN where the tick takes the argmax rule) and logits [V] (nullable) the tick's logits, from the LDS array the draw reads.
 //  3: ... behind sample.h's token constraints: allow = the tick's ceil(V / 64) words of allowed tokens (<= 4), read by wave 0 through a
 //     wave-uniform address.  A tick outside the rule takes the argmax over its allowed logits.  The logits stored are the unmasked ones.
+//  4: ... behind sample.h's forced tokens: *forced = the tick's forced word, read by wave 0 through a wave-uniform address; a value in
+//     [0, V) is the token whatever the logits, the mask and the uniform hold.  A null allow: words of all ones.
 template <int NI, int LEVEL>
 __global__ __launch_bounds__(1024) void head_b1_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                        const float* __restrict__ b, long long* __restrict__ tok, int V, int K,
                                                        float temp, const double* __restrict__ u, int top_k, double top_p,
                                                        float* __restrict__ logp, float* __restrict__ logits,
-                                                       const unsigned long long* __restrict__ allow) {
+                                                       const unsigned long long* __restrict__ allow,
+                                                       const int* __restrict__ forced) {
     __shared__ float lg[256];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float xv[NI];
@@ -789,7 +819,8 @@ __global__ __launch_bounds__(1024) void head_b1_kernel(const float* __restrict__
         const int nw = (V + 63) / 64;
         unsigned long long aw[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) aw[j] = LEVEL < 3 ? ~0ull : j < nw ? allow[j] : 0ull;   // (below level 3: constants, and v < V bounds the argmax)
+        for (int j = 0; j < 4; ++j)                            // (below level 3: constants, and v < V bounds the argmax)
+            aw[j] = LEVEL < 3 ? ~0ull : j < nw ? (LEVEL >= 4 && !allow ? ~0ull : allow[j]) : 0ull;
         if constexpr (LEVEL >= 3) sample::mask_words<4>(aw, V);
         int bi = -1;
         if constexpr (LEVEL >= 1) {
@@ -797,7 +828,8 @@ __global__ __launch_bounds__(1024) void head_b1_kernel(const float* __restrict__
             double tot;
 #pragma unroll
             for (int j = 0; j < 4; ++j) xs[j] = lane + 64 * j < V ? lg[lane + 64 * j] : -INFINITY;
-            bi = sample::draw<4, LEVEL>(xs, temp, *u, V, lane, top_k, top_p, aw, -1, gap, tot);
+            const int f = LEVEL >= 4 && forced ? *forced : -1;
+            bi = sample::draw<4, LEVEL>(xs, temp, *u, V, lane, top_k, top_p, aw, f, gap, tot);
             if constexpr (LEVEL >= 2) { if (logp && lane == 0) *logp = bi >= 0 ? sample::logp_of(gap, tot) : gap; }
         }
         if (bi < 0) bi = argmax_wave(lg, aw, V, lane);
@@ -812,12 +844,14 @@ size_t arnn_ticks_ws_floats(const ArnnGenNet& n) { return (size_t)(n.E + n.Hc) +
 // L ticks of one row from the state hc_init [layer][h | c][H] (null: zeros; inpainting: the state after the prefix) and the token
 // *first_tok (null: 0); `uniforms` [L]: the sampling head, null: the argmax head; trunc (with uniforms): the truncating head, logp [L]
 // and logits [L][V] nullable, one label (trunc_arnn_ticks ...) around the row's launches; allow (with trunc): the row's [L][ceil(V / 64)]
-// words of allowed tokens -- the masked head, label cons_arnn_ticks ...
+// words of allowed tokens -- the masked head, label cons_arnn_ticks ...; forced (with trunc): the row's [L] forced words -- the forced
+// head, label force_arnn_ticks ..., allow nullable
 int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, const float* hc_init, const long long* first_tok,
                float temp, const double* uniforms, long long* tokens, float* ws, hipStream_t s, bool trunc = false, int top_k = 0,
-               double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr) {
+               double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr,
+               const int* forced = nullptr) {
     const int H = n.H;
-    const int level = sample::level(uniforms, trunc, allow, nullptr);
+    const int level = sample::level(uniforms, trunc, allow, forced);
     // (a call below level 2 files nothing.  `trunc` counts only with uniforms -- sample::level --, and no caller sets it without them)
     std::optional<ProfScope> prof;
     if (level >= 2) {
@@ -846,12 +880,14 @@ int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, cons
 #define HEAD_B1(LEVEL)                                                                                                          \
     hipLaunchKernelGGL((head_b1_kernel<4, LEVEL>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U, temp, \
                        uniforms ? uniforms + t : nullptr, top_k, top_p, logp ? logp + t : nullptr,                                  \
-                       logits ? logits + (long)t * n.V : nullptr, allow ? allow + (long)t * ((n.V + 63) / 64) : nullptr)
+                       logits ? logits + (long)t * n.V : nullptr, allow ? allow + (long)t * ((n.V + 63) / 64) : nullptr,                \
+                       forced ? forced + t : nullptr)
         switch (level) {
             case 0: HEAD_B1(0); break;
             case 1: HEAD_B1(1); break;
             case 2: HEAD_B1(2); break;
-            default: HEAD_B1(3);
+            case 3: HEAD_B1(3); break;
+            default: HEAD_B1(4);
         }
 #undef HEAD_B1
     }
@@ -876,18 +912,19 @@ int arnn_generate(const ArnnGenNet& n, int L, const float* oc0, long oc_stride, 
 
 int arnn_sample(const ArnnGenNet& n, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
                 const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k, double top_p,
-                float* logp, float* logits, const unsigned long long* allow) {
+                float* logp, float* logits, const unsigned long long* allow, const int* forced) {
     // truncation on, or an output only the truncating kernels write: never a kernel that ignores them; a mask of allowed tokens: the
-    // masked kernels, which are truncating ones
-    const bool trunc = (top_k >= 1 && top_k < n.V) || top_p < 1.0 || logp || logits || allow;
-    if (allow ? arnn_token_cons_ok(n) : trunc ? arnn_token_trunc_ok(n) : arnn_token_pass_ok(n))    // up to 8 rows per launch
+    // masked kernels, which are truncating ones; forced words: the forced kernels, which are masked ones -- never a kernel that ignores them
+    const bool trunc = (top_k >= 1 && top_k < n.V) || top_p < 1.0 || logp || logits || allow || forced;
+    if (forced ? arnn_token_force_ok(n) : allow ? arnn_token_cons_ok(n) : trunc ? arnn_token_trunc_ok(n) : arnn_token_pass_ok(n))    // up to 8 rows per launch
         return arnn_token_sample(n, R, L, oc0, oc_stride, oc_bstride, temp, uniforms, hc_init, tokens, ws, s, trunc, top_k, top_p, logp,
-                                 logits, allow);
+                                 logits, allow, forced);
     if (!arnn_ticks_ok(n)) return -1;
     int rc = 0;
     for (int r = 0; r < R && rc == 0; ++r)                     // the rows one after the other
         rc = arnn_ticks(n, L, oc0 + (long)r * oc_bstride, oc_stride, hc_init ? hc_init + (long)r * 4 * n.H : nullptr, nullptr, temp,
                         uniforms + (long)r * L, tokens + (long)r * L, ws, s, trunc, top_k, top_p, logp ? logp + (long)r * L : nullptr,
-                        logits ? logits + (long)r * L * n.V : nullptr, allow ? allow + (long)r * L * ((n.V + 63) / 64) : nullptr);
+                        logits ? logits + (long)r * L * n.V : nullptr, allow ? allow + (long)r * L * ((n.V + 63) / 64) : nullptr,
+                        forced ? forced + (long)r * L : nullptr);
     return rc;
 }

@@ -164,7 +164,7 @@ _ARNN_KEEP_WS = []
 
 
 def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2, temperature, uniforms, hc_init=None,
-                top_k=None, top_p=None, want_logp=False, want_logits=False, allowed=None):
+                top_k=None, top_p=None, want_logp=False, want_logits=False, allowed=None, forced=None):
     """inet_arnn_sample: AnticipationRNN's temperature-sampled generation for R independent rows.  oc [R,L,Hc] (the rows' constraint
     outputs; strided rows and ticks allowed); uniforms [R,L] float64 (one np.random.random_sample() double per tick; a host array is
     copied to the device); hc_init [R,2,2,H] (layer, h|c) or None (zeros).  Token t of row r is the first v whose softmax(temperature *
@@ -175,8 +175,12 @@ def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
     the note head's output every tick drew from).
     allowed: inet_arnn_sample_cx -- pack_allowed()'s words [R,L,ceil(V/64)], int64, contiguous, on the device: the tokens each (row,
     tick) may return, applied inside the launch in front of the truncation (csrc/sample.h).  A constrained call is
-    a truncating one: allowed alone runs with (top_k, top_p) = (0, 1.0), and the return is the triple above."""
-    ex = top_k is not None or top_p is not None or want_logp or want_logits or allowed is not None
+    a truncating one: allowed alone runs with (top_k, top_p) = (0, 1.0), and the return is the triple above.
+    forced: inet_arnn_sample_fx -- int32 [R,L], contiguous, on the device, -1 for a free tick: a value in [0, V) is that tick's token,
+    returned and fed back whatever the mask, the truncation and the uniform hold, with its log-probability under the masked and
+    truncated distribution (-inf for a banned or truncated token; csrc/sample.h).  forced alone runs with (top_k,
+    top_p) = (0, 1.0) and returns logp."""
+    ex = top_k is not None or top_p is not None or want_logp or want_logits or allowed is not None or forced is not None
     k = _top_k(top_k)
     if top_p is not None and not (0.0 < float(top_p) <= 1.0):
         raise ValueError(f"arnn_sample: top_p {top_p!r} outside (0, 1]")
@@ -186,6 +190,11 @@ def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
         if not (isinstance(allowed, torch.Tensor) and allowed.is_cuda and allowed.dtype == torch.int64 and allowed.is_contiguous()
                 and tuple(allowed.shape) == (R, L, nw)):
             raise ValueError(f"arnn_sample: allowed must be pack_allowed()'s contiguous int64 device tensor of shape {(R, L, nw)}")
+    if forced is not None:
+        if not (isinstance(forced, torch.Tensor) and forced.is_cuda and forced.dtype == torch.int32 and forced.is_contiguous()
+                and tuple(forced.shape) == (R, L)):
+            raise ValueError(f"arnn_sample: forced must be a contiguous int32 device tensor of shape {(R, L)}")
+        want_logp = True
     assert oc.is_cuda and oc.dtype == torch.float32 and oc.stride(2) == 1
     E, H, U, V = emb.shape[1], W_hh0.shape[1], W1.shape[0], W2.shape[0]
     net = [ptr(_f32c(t)) for t in (W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2)]
@@ -205,11 +214,13 @@ def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
         args = (R, L, E, Hc, H, U, V, ptr(_f32c(emb)), ptr(oc), oc.stride(1), oc.stride(0), *net, float(temperature), ptr(u),
                 ptr(_f32c(hc_init) if hc_init is not None else None), ptr(tokens), ptr(ws), nws, k,
                 1.0 if top_p is None else float(top_p), ptr(logp), ptr(logits))
-        if allowed is not None:
+        if forced is not None:
+            check(_lib.lib().inet_arnn_sample_fx(*args, ptr(allowed), ptr(forced), stream_ptr()), "inet_arnn_sample_fx")
+        elif allowed is not None:
             check(_lib.lib().inet_arnn_sample_cx(*args, ptr(allowed), stream_ptr()), "inet_arnn_sample_cx")
         else:
             check(_lib.lib().inet_arnn_sample_ex(*args, stream_ptr()), "inet_arnn_sample_ex")
-        _hold(ws, oc, u, hc_init, allowed)
+        _hold(ws, oc, u, hc_init, allowed, forced)
         return tokens, logp, logits
     check(_lib.lib().inet_arnn_sample(R, L, E, Hc, H, U, V, ptr(_f32c(emb)), ptr(oc), oc.stride(1), oc.stride(0), *net,
                                       float(temperature), ptr(u),

@@ -3,13 +3,16 @@
 With INET_ARNN_GEN_STAMPS=1 the persistent kernel (csrc/arnn_gen.hip) also leaves wall-clock stamps of the phases of a tick in its
 workspace: the anatomy of a tick as workgroup C (layer-0 cell, linear_1, head, argmax) and workgroup Bi_0 (layer-1 product + cell)
 see it is printed below the timings.
-    python tools/arnn_token_pass.py [V] --sample [--rows 1,8] [--temperature 6.0] [--top-k 8] [--top-p 0.9] [--mask] [--rounds 5] [--iters 20]
+    python tools/arnn_token_pass.py [V] --sample [--rows 1,8] [--temperature 6.0] [--top-k 8] [--top-p 0.9] [--mask] [--forced] [--rounds 5] [--iters 20]
 times the SAMPLING build (ops.arnn_sample, L = 384, R independent rows) and the TRUNCATING build on the same inputs instead: the plain
 call, the call that only asks for logp (truncation off), and one call per truncation given -- top-k alone, top-p alone, both when both
 are given -- with device events, per round the median of --iters calls, over the rounds the median (range), and each truncating call's
 cost per tick over the sampling build.  --mask adds, behind every truncating call, the CONSTRAINED call of the same arguments
 (ops.arnn_sample's allowed=: the masked build) under tests/decoder_constraint_ref.plan_mask(V, R, T=L) -- every fourth tick fixed, a fifth
-of the tokens banned elsewhere, the words packed once -- with its cost per tick over that truncating call."""
+of the tokens banned elsewhere, the words packed once -- with its cost per tick over that truncating call.  --forced (with --mask) adds,
+behind every constrained call, two calls of the FORCED build (ops.arnn_sample's forced=) under the same mask: the constrained call through
+it (no tick forced: every word -1) and the ALL-FORCED call (tick t of row r forced to (5 r + 11 t + 2) % V), with the all-forced call's
+cost per tick over the constrained call of the same build."""
 import os, sys, time, types
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -50,10 +53,17 @@ def sample_builds():
         calls.append((f"top_k={top_k}, top_p={top_p}", dict(top_k=top_k, top_p=top_p, want_logp=True)))
     if "--mask" in sys.argv:
         from tests.decoder_constraint_ref import plan_mask
-        calls = [c for name, kw in calls for c in ([(name, kw)] + ([(name + ", mask", dict(kw, mask=name))] if kw else []))]
+        forced = "--forced" in sys.argv
+        calls = [c for name, kw in calls for c in ([(name, kw)] + ([(name + ", mask", dict(kw, mask=name))] if kw else []) +
+                                                   ([(name + ", mask, forced build, no tick forced", dict(kw, mask=name, forced=-1)),
+                                                     (name + ", mask, all forced", dict(kw, mask=name + ", mask, forced build, no tick forced",
+                                                                                        forced=1))] if kw and forced else []))]
     for R in rows:
         if "--mask" in sys.argv:
             words = ops.pack_allowed(torch.from_numpy(plan_mask(NOTES, R, L))).cuda().contiguous()
+            rr, tt = np.meshgrid(np.arange(R), np.arange(L), indexing="ij")
+            fwords = {-1: torch.full((R, L), -1, dtype=torch.int32, device="cuda"),
+                      1: torch.from_numpy(((5 * rr + 11 * tt + 2) % NOTES).astype(np.int32)).cuda().contiguous()}
         oc = torch.randn(R, L, H, device="cuda") * 0.5
         u = torch.from_numpy(np.random.RandomState(1).random_sample((R, L))).cuda()
         hc = torch.zeros(R, 2, 2, H, device="cuda")
@@ -63,6 +73,8 @@ def sample_builds():
             base = kw.pop("mask", None)                         # (the truncating call this constrained call is compared with)
             if base is not None:
                 kw["allowed"] = words
+            if "forced" in kw:
+                kw["forced"] = fwords[kw["forced"]]
             fn = lambda: ops.arnn_sample(args[0], oc, *args[2:], temp, u, hc_init=hc, **kw)
             for _ in range(3): fn()
             torch.cuda.synchronize()
@@ -77,7 +89,8 @@ def sample_builds():
             med[name] = sorted(per_round)[len(per_round) // 2]
             over = "" if not kw else f"  {1e3 * (med[name] - med['sampling build']) / L:+.2f} us per tick over the sampling build"
             if base is not None:
-                over = f"  {1e3 * (med[name] - med[base]) / L:+.2f} us per tick over the truncating call"
+                over = f"  {1e3 * (med[name] - med[base]) / L:+.2f} us per tick over " + \
+                    ("the constrained call of the same build" if name.endswith("all forced") else "the truncating call")
             print(f"V = {NOTES}, R = {R}, T = {temp}: {name}: {med[name]:.4f} ms ({min(per_round):.4f} .. {max(per_round):.4f}), "
                   f"{1e3 * med[name] / L:.2f} us per tick{over}  chain status {ops.chain_status()}")
 
