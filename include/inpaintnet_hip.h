@@ -287,6 +287,29 @@ int inet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, floa
  *    generous: a lag of 2 cost the B = 256 step 5 % (profiles/r04_b_report_lag.txt); Trainer.finish() reads what is outstanding. */
 int inet_adam_step_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                       float eps, int step, float gscale, const float* step_flag, uint32_t* report, void* stream);
+/* Clip the gradient by its global norm and skip a step whose gradient is not finite, on the device.  The rule,
+ * for the gradient arena g[0..n), gscale and 0 < max_norm <= +inf:
+ *   1. S = sum (double)g_i * (double)g_i -- every square exact in f64, the sum in f64 in a FIXED order that depends on n only;
+ *      norm = |gscale| * sqrt(S) in f64.
+ *   2. nonfinite = !isfinite(norm): true iff some element is inf or NaN (a finite f32 arena cannot overflow the f64 sum).
+ *   3. c = max_norm / (norm + 1e-6) in f64, torch's clip_grad_norm_ coefficient; scale = c < 1 ? (float)c : 1.0f; clipped = c < 1.
+ *      max_norm = +inf never clips; it still measures the norm and still skips non-finite steps.
+ *   4. The chain / step flag says skip (inet_adam_step_ex's rule, unchanged): the step is skipped, only report[1] is set, nonfinite
+ *      and clipped are reported as 0.
+ *   5. Otherwise, nonfinite: p, m, v are left bit for bit untouched, report[5] = 1, report[1] and report[2] stay 0 -- not a chain
+ *      failure.
+ *   6. Otherwise Adam runs exactly as inet_adam_step_ex with gscale replaced by the single f32 product gscale * scale: with
+ *      scale == 1.0f p, m, v are bit-identical to inet_adam_step_ex on the same inputs.
+ * Two launches on `stream`: inet_grad_sqnorm writes ALL inet_sqnorm_parts() doubles of `partials` (device memory the caller allocates
+ * once and reuses; nothing to zero), inet_adam_step_clip sums them in every workgroup in one fixed order and applies steps 2-6.
+ * g must be 16-byte aligned.  report (nullable): EIGHT 32-bit words of host-mapped memory zeroed by the caller: [0..3] as in
+ * inet_adam_step_ex, [4] = clipped, [5] = skipped for a non-finite gradient, [6] = the bits of (float)norm (written whenever the kernel
+ * ran, also on a skip), [7] = 0.  step_flag: as in inet_adam_step_ex.  -1 for a max_norm that is NaN or <= 0, before any launch. */
+int inet_sqnorm_parts(void);
+int inet_grad_sqnorm(const float* g, int64_t n, double* partials, void* stream);
+int inet_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                        float eps, int step, float gscale, float max_norm, const double* partials, const float* step_flag,
+                        uint32_t* report, void* stream);
 /* dst: the TWO floats described above (chain status, token status of this process) */
 int inet_step_flag_export(float* dst, void* stream);
 /* Number of prologue launches that met a token index outside [0, num_notes) since the last reset (encoder input tokens,

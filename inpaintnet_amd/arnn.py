@@ -564,8 +564,8 @@ class AnticipationRNNBaseline(ConstraintModelGaussianReg):
 class AnticipationRNNGaussianRegTrainer(Trainer):
     """AnticipationRNN/anticipation_rnn_trainer.py:8-182"""
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False):
-        super().__init__(dataset, model, lr, early_stopping)
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
+        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm)
         self.min_num_measures_target = 2
         self.max_num_measure_target = 6
         self.measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
@@ -622,8 +622,8 @@ class AnticipationRNNBaselineTrainer(AnticipationRNNGaussianRegTrainer):
     mask over the ticks (rate p ~ U(0, 0.5) per batch, the same mask for every sequence of the batch).  The draws use
     Python's `random` (p) and torch's CPU generator (the mask), in the reference's order."""
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False):
-        super().__init__(dataset, model, lr, early_stopping)
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
+        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm)
         self.constraint_prod = 0.5
 
     def process_batch_data(self, batch):

@@ -246,6 +246,18 @@ int inet_adam_step_ex(float* p, const float* g, float* m, float* v, int64_t n, f
     if (!p || !g || !m || !v || n <= 0 || step < 1) return -1;
     return pw_adam(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, (hipStream_t)stream, step_flag, report);
 }
+int inet_sqnorm_parts(void) { return pw_sqnorm_parts(); }
+int inet_grad_sqnorm(const float* g, int64_t n, double* partials, void* stream) {
+    if (!g || !partials || n <= 0 || ((uintptr_t)g & 15)) return -1;
+    return pw_grad_sqnorm(g, n, partials, (hipStream_t)stream);
+}
+int inet_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                        float eps, int step, float gscale, float max_norm, const double* partials, const float* step_flag,
+                        uint32_t* report, void* stream) {
+    if (!p || !g || !m || !v || !partials || n <= 0 || step < 1 || !(max_norm > 0.f)) return -1;       // (NaN fails the comparison)
+    return pw_adam_clip(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, max_norm, partials, (hipStream_t)stream, step_flag,
+                        report);
+}
 int inet_step_flag_export(float* dst, void* stream) {
     if (!dst) return -1;
     return pw_step_flag_export(dst, (hipStream_t)stream);

@@ -42,6 +42,15 @@ int pw_sample_forced(const float* W, long ld_w, int rows, int V, float temp, con
 // zeroed by the caller): [0] = 1 executed, [1] = 1 skipped, [2] = 1 a parameter became non-finite
 int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
             float gscale, hipStream_t s, const float* step_flag = nullptr, unsigned* report = nullptr);
+// Global-norm clipping (the rule: pointwise.hip), two launches: partials[pw_sqnorm_parts()] = the f64 sums of
+// squares of the fixed grid's shares of g (every entry written: nothing to zero in front); then pw_adam with the clip coefficient and
+// the non-finite skip derived from them.  report (optional): EIGHT host-mapped words zeroed by the caller -- [0..3] as pw_adam,
+// [4] = 1 clipped, [5] = 1 skipped for an inf / NaN gradient, [6] = the bits of (float)norm, [7] = 0
+int pw_sqnorm_parts();
+int pw_grad_sqnorm(const float* g, long n, double* partials, hipStream_t s);
+int pw_adam_clip(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
+                 float gscale, float max_norm, const double* partials, hipStream_t s, const float* step_flag = nullptr,
+                 unsigned* report = nullptr);
 int pw_step_flag_export(float* dst, hipStream_t s);
 int pw_epoch_stats_add(float* sums, const float* loss, const float* acc, hipStream_t s, const float* step_flag = nullptr);
 int pw_colsum(const float* X, long ld, int M, int N, float* out, hipStream_t s);

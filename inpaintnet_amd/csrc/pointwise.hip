@@ -200,6 +200,44 @@ __global__ void latent_bwd_kernel(const float* __restrict__ dz, const float* __r
 }
 
 // torch.optim.Adam (2.x single-tensor form): denom = sqrt(v)/sqrt(bc2) + eps; p -= lr/bc1 * m/denom
+// The update of the calling thread's grid-stride share (tid = its index in the grid, stride = the grid's threads: the kernels read
+// blockDim / gridDim themselves, which keeps adam_kernel's code what it was before the body was shared), the body adam_kernel and
+// adam_clip_kernel have in common; returns whether one of its parameters left the finite range.
+__device__ __forceinline__ bool adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, long n, float lr_over_bc1, float inv_sqrt_bc2, float b1,
+                                            float b2, float eps, float gscale, long tid, long stride) {
+    bool bad = false;
+    const long n4 = n >> 2;
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    for (long i = tid; i < n4; i += stride) {
+        f32x4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gr = gg[e] * gscale;
+            mm[e] = b1 * mm[e] + (1.f - b1) * gr;
+            vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
+            const float denom = sqrtf(vv[e]) * inv_sqrt_bc2 + eps;
+            pp[e] -= lr_over_bc1 * (mm[e] / denom);
+            bad |= !(fabsf(pp[e]) <= 3.402823466e38f);          // NaN or +-inf
+        }
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+    }
+    // tail (n is a multiple of 4 for arenas; kept for generality)
+    for (long i = (n4 << 2) + tid; i < n; i += stride) {
+        const float gr = g[i] * gscale;
+        const float mm = b1 * m[i] + (1.f - b1) * gr;
+        const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
+        m[i] = mm; v[i] = vv;
+        const float pn = p[i] - lr_over_bc1 * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
+        p[i] = pn;
+        bad |= !(fabsf(pn) <= 3.402823466e38f);
+    }
+    return bad;
+}
+
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long n, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
                             float eps, float gscale, const unsigned* __restrict__ abort_word,
@@ -219,35 +257,101 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
         if (step_flag && step_flag[1] != 0.f) __hip_atomic_store(report + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (skip) return;
-    bool bad = false;
-    const long n4 = n >> 2;
-    f32x4* p4 = reinterpret_cast<f32x4*>(p);
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
-    f32x4* m4 = reinterpret_cast<f32x4*>(m);
-    f32x4* v4 = reinterpret_cast<f32x4*>(v);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        f32x4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
+    const bool bad = adam_update(p, g, m, v, n, lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, gscale,
+                                 (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
+    if (bad && report) __hip_atomic_store(report + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- global-norm clipping in front of the step.  The rule, for the gradient arena g[0..n), gscale and
+// 0 < max_norm <= +inf:
+//   1. S = sum (double)g_i * (double)g_i: every square exact in f64, the sum in f64 in a FIXED order that depends on n only;
+//      norm = |gscale| * sqrt(S) in f64.
+//   2. nonfinite = !isfinite(norm)  (a finite f32 arena cannot overflow the f64 sum: true iff some element is inf or NaN).
+//   3. c = max_norm / (norm + 1e-6) in f64 (torch's clip_grad_norm_ coefficient); scale = c < 1 ? (float)c : 1.0f;
+//      clipped = c < 1.  max_norm = +inf never clips.
+//   4. the chain / step flag says skip: the step is skipped as adam_kernel skips it, nonfinite and clipped are reported as 0.
+//   5. else nonfinite: p, m, v stay untouched, report[5] = 1, report[1] and report[2] stay 0 (not a chain failure).
+//   6. else Adam exactly as adam_kernel with gscale replaced by the ONE f32 product gscale * scale.
+constexpr int kSqnormParts = 1024;               // workgroups of grad_sqnorm_kernel = doubles of its output
+constexpr int kSqnormBlock = 256;
+
+__device__ __forceinline__ double wave_sum_d(double v) {           // xor butterfly: every lane ends with the same bits
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gr = gg[e] * gscale;
-            mm[e] = b1 * mm[e] + (1.f - b1) * gr;
-            vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
-            const float denom = sqrtf(vv[e]) * inv_sqrt_bc2 + eps;
-            pp[e] -= lr_over_bc1 * (mm[e] / denom);
-            bad |= !(fabsf(pp[e]) <= 3.402823466e38f);          // NaN or +-inf
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// the sum of the workgroup's 256 values on every thread: the wave tree, then the four waves in wave order
+__device__ __forceinline__ double block_sum_d(double v, double* part) {
+    v = wave_sum_d(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+// partials[b] = the squares of workgroup b's grid-stride share of g, in f64.  EVERY workgroup stores (one without elements: 0.0), with a
+// plain store: nothing to zero in front, no atomics, no hand-off between workgroups -- the consumer is the next launch.
+__global__ void __launch_bounds__(kSqnormBlock) grad_sqnorm_kernel(const float* __restrict__ g, long n, double* __restrict__ partials) {
+    __shared__ double part[4];
+    const long n4 = n >> 2;
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    const long stride = (long)gridDim.x * blockDim.x;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;                   // one chain per element slot of the 16-byte load
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    // four loads in flight per lane: the grid holds 4 MB per pass, the HBM pipe wants more than that outstanding
+    for (; i + 3 * stride < n4; i += 4 * stride) {
+        const f32x4 x0 = g4[i], x1 = g4[i + stride], x2 = g4[i + 2 * stride], x3 = g4[i + 3 * stride];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f32x4 x = k == 0 ? x0 : k == 1 ? x1 : k == 2 ? x2 : x3;
+            a0 = fma((double)x[0], (double)x[0], a0);
+            a1 = fma((double)x[1], (double)x[1], a1);
+            a2 = fma((double)x[2], (double)x[2], a2);
+            a3 = fma((double)x[3], (double)x[3], a3);
         }
-        p4[i] = pp; m4[i] = mm; v4[i] = vv;
     }
-    // tail (n is a multiple of 4 for arenas; kept for generality)
-    for (long i = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gr = g[i] * gscale;
-        const float mm = b1 * m[i] + (1.f - b1) * gr;
-        const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        m[i] = mm; v[i] = vv;
-        const float pn = p[i] - lr_over_bc1 * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
-        p[i] = pn;
-        bad |= !(fabsf(pn) <= 3.402823466e38f);
+    for (; i < n4; i += stride) {
+        const f32x4 x = g4[i];
+        a0 = fma((double)x[0], (double)x[0], a0);
+        a1 = fma((double)x[1], (double)x[1], a1);
+        a2 = fma((double)x[2], (double)x[2], a2);
+        a3 = fma((double)x[3], (double)x[3], a3);
     }
+    // tail, as adam_kernel's
+    for (long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) a0 = fma((double)g[t], (double)g[t], a0);
+    const double s = block_sum_d((a0 + a1) + (a2 + a3), part);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// adam_kernel behind the rule above.  Every workgroup sums the kSqnormParts partials itself, in the SAME order (lane-strided reads, the
+// same tree), so that all of them derive norm, c, scale and the decision bit for bit alike; `report`: eight host-mapped words.
+__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, long n, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
+                                 float eps, float gscale, float max_norm, const double* __restrict__ partials,
+                                 const unsigned* __restrict__ abort_word, const float* __restrict__ step_flag,
+                                 unsigned* __restrict__ report) {
+    __shared__ double part[4];
+    double acc = 0.0;
+#pragma unroll
+    for (int k = 0; k < kSqnormParts / kSqnormBlock; ++k) acc += partials[threadIdx.x + k * kSqnormBlock];
+    const double S = block_sum_d(acc, part);
+    const double norm = fabs((double)gscale) * sqrt(S);
+    const bool skip = step_flag ? (*step_flag != 0.f)
+                                : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
+    const bool nonfinite = !skip && !(fabs(norm) <= 1.7976931348623157e308);          // NaN or +inf
+    const double c = (double)max_norm / (norm + 1e-6);
+    const bool clipped = !skip && !nonfinite && c < 1.0;
+    if (report && blockIdx.x == 0 && threadIdx.x == 0) {
+        __hip_atomic_store(report + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (skip) __hip_atomic_store(report + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (step_flag && step_flag[1] != 0.f) __hip_atomic_store(report + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (clipped) __hip_atomic_store(report + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (nonfinite) __hip_atomic_store(report + 5, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(report + 6, __float_as_uint((float)norm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (skip || nonfinite) return;
+    const float scale = clipped ? (float)c : 1.0f;
+    const bool bad = adam_update(p, g, m, v, n, lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, gscale * scale,
+                                 (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
     if (bad && report) __hip_atomic_store(report + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -960,6 +1064,21 @@ int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, floa
     ProfScope prof(PROF_HBM, 0.0, s, "adam", 28.0 * (double)n);      // read p,g,m,v; write p,m,v
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(256), 0, s, p, g, m, v, n,
                        (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, gscale,
+                       (const unsigned*)chain_dev_status(), step_flag, report);
+    return ok();
+}
+int pw_sqnorm_parts() { return kSqnormParts; }
+int pw_grad_sqnorm(const float* g, long n, double* partials, hipStream_t s) {
+    ProfScope prof(PROF_HBM, 0.0, s, "grad_sqnorm", 4.0 * (double)n);         // one read of the arena
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(kSqnormParts), dim3(kSqnormBlock), 0, s, g, n, partials);
+    return ok();
+}
+int pw_adam_clip(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
+                 float gscale, float max_norm, const double* partials, hipStream_t s, const float* step_flag, unsigned* report) {
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    ProfScope prof(PROF_HBM, 0.0, s, "adam_clip", 28.0 * (double)n + 8.0 * kSqnormParts);      // adam's traffic + the partials
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(kSqnormBlock), 0, s, p, g, m, v, n,
+                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, gscale, max_norm, partials,
                        (const unsigned*)chain_dev_status(), step_flag, report);
     return ok();
 }

@@ -16,8 +16,8 @@ from .trainer import Trainer
 class LatentRNNTrainer(Trainer):
     feed_fields = (0,)                     # the metadata tensor of a batch is never read (latent_rnn_trainer.py:31-33)
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False):
-        super().__init__(dataset, model, lr, early_stopping)
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
+        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm)
         # window sizes of the stochastic split (latent_rnn_trainer.py:17-22)
         self.min_num_measures_target, self.max_num_measure_target = 2, 6
         n_bars = self.dataset.n_bars

@@ -507,6 +507,37 @@ def adam_step(p, g, m, v, lr, step, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, step
               "inet_adam_step_ex")
 
 
+def sqnorm_parts():
+    """How many float64 partial sums grad_sqnorm writes (a constant of the library)."""
+    return int(_lib.lib().inet_sqnorm_parts())
+
+
+def grad_sqnorm(g, partials=None):
+    """partials[b] = the float64 sum of squares of workgroup b's share of g; sum(partials) = |g|^2 in a fixed order that depends on
+    g.numel() only.  Every entry is written.  `partials`: a device float64 tensor of sqnorm_parts() elements the caller allocates once
+    and reuses (None: a new one).  Returns it."""
+    _f32c(g)
+    if partials is None:
+        partials = torch.empty(sqnorm_parts(), dtype=torch.float64, device=g.device)
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= sqnorm_parts()
+    check(_lib.lib().inet_grad_sqnorm(ptr(g), g.numel(), ptr(partials), stream_ptr()), "inet_grad_sqnorm")
+    return partials
+
+
+def adam_step_clip(p, g, m, v, lr, step, max_norm, partials, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, step_flag=None, report=None):
+    """adam_step behind global-norm clipping and the non-finite skip (include/inpaintnet_hip.h inet_adam_step_clip states the rule):
+    `partials` is what grad_sqnorm(g) left, max_norm in (0, inf].  report: EIGHT int32 words of PINNED host memory, zeroed by the
+    caller: [0..3] as adam_step's, [4] clipped, [5] skipped for an inf / NaN gradient, [6] the bits of float32(norm), [7] 0."""
+    for t in (p, g, m, v):
+        _f32c(t)
+    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= sqnorm_parts()
+    if report is not None:
+        assert report.dtype == torch.int32 and report.numel() >= 8 and report.is_pinned() and report.is_contiguous()
+    check(_lib.lib().inet_adam_step_clip(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(b1), float(b2), float(eps),
+                                         int(step), float(gscale), float(max_norm), ptr(partials), ptr(step_flag), ptr(report),
+                                         stream_ptr()), "inet_adam_step_clip")
+
+
 def step_flag_export(dst):
     """dst[0] = 1.0 if a chain launch of this process has timed out since the last reset else 0.0 (on the current stream)."""
     check(_lib.lib().inet_step_flag_export(ptr(_f32c(dst)), stream_ptr()), "inet_step_flag_export")

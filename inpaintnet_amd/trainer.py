@@ -16,6 +16,7 @@ Plotting / tensorboard plumbing of the reference is out of scope.
 """
 import gc
 import os
+import struct
 import sys
 import time
 from abc import ABC, abstractmethod
@@ -140,7 +141,21 @@ class Trainer(ABC):
 
     feed_fields = (0, 1)       # which members of a (score, metadata) batch the trainer needs on the device
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False):
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
+        """max_grad_norm (None or 0 < value <= inf): clip the gradient arena by its global norm in front of every optimizer step, as
+        torch.nn.utils.clip_grad_norm_(..., error_if_nonfinite=False) around optimizer.step() would, and DROP a step whose gradient
+        holds an inf or a NaN instead of folding it into the weights -- both on the device (ops.grad_sqnorm +
+        ops.adam_step_clip in the place of ops.adam_step; inf = measure and drop only, never clip).  The step reports, read at the
+        usual lag (check_steps), keep last_grad_norm, clipped_steps and nonfinite_steps up to date.  None: nothing changes."""
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:              # (NaN fails the comparison too)
+                raise ValueError(f"max_grad_norm must be None or in (0, inf], got {max_grad_norm}")
+        self.max_grad_norm = max_grad_norm
+        self.last_grad_norm = None                   # the norm the newest report read so far holds (before clipping, gscale applied)
+        self.clipped_steps = 0
+        self.nonfinite_steps = 0                     # steps dropped for an inf / NaN gradient (not chain failures, not replayed)
+        self._sqnorm = None                          # the norm kernel's float64 partial sums, allocated at the first clipped step
         self.dataset = dataset
         self.model = model
         self.lr = lr
@@ -379,8 +394,16 @@ class Trainer(ABC):
         m = self.model
         rec = self._report_slot(tag)
         rec.zero_()                                  # host write: the launch that last wrote this record was waited for when it was read
-        ops.adam_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.betas[0], self.betas[1],
-                      self.eps, gscale, step_flag=flag, report=rec)
+        if self.max_grad_norm is None:
+            ops.adam_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.betas[0], self.betas[1],
+                          self.eps, gscale, step_flag=flag, report=rec)
+        else:
+            # m.grad is the arena alone (the 16-byte head of its store holds the ranks' flags, not gradients); both launches sit
+            # behind the gradient exchange, so every rank measures the same all-reduced arena in the same fixed order and all
+            # ranks clip and drop together: no collective of their own
+            self._sqnorm = ops.grad_sqnorm(m.grad, self._sqnorm)
+            ops.adam_step_clip(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.max_grad_norm, self._sqnorm,
+                               self.betas[0], self.betas[1], self.eps, gscale, step_flag=flag, report=rec)
         self._report_events[tag % self._NREP].record()
 
     def _device_sync(self):
@@ -396,30 +419,55 @@ class Trainer(ABC):
 
     def _report_slot(self, tag):
         if self._reports is None:
-            self._reports = torch.zeros(self._NREP, 4, dtype=torch.int32).pin_memory()
+            # four words per record (inet_adam_step_ex), eight with clipping (inet_adam_step_clip)
+            self._reports = torch.zeros(self._NREP, 4 if self.max_grad_norm is None else 8, dtype=torch.int32).pin_memory()
             self._report_events = [torch.cuda.Event() for _ in range(self._NREP)]
         return self._reports[tag % self._NREP]
 
     def _read_report(self, tag):
-        """(executed, skipped, nonfinite) of the optimizer launch issued under `tag`, after the event behind it."""
+        """(executed, skipped, nonfinite, bad token) of the optimizer launch issued under `tag`, after the event behind it; with
+        max_grad_norm set also (clipped, dropped for a non-finite gradient, the gradient norm)."""
         self._report_events[tag % self._NREP].synchronize()
         r = self._reports[tag % self._NREP].tolist()
         if not r[0]:
             raise RuntimeError(f"optimizer launch {tag} left no report (the kernel did not run?)")
-        return bool(r[0]), bool(r[1]), bool(r[2]), bool(r[3])
+        rep = bool(r[0]), bool(r[1]), bool(r[2]), bool(r[3])
+        if len(r) > 4:
+            rep += (bool(r[4]), bool(r[5]), struct.unpack("<f", struct.pack("<i", r[6]))[0])
+        return rep
+
+    def _note_clip(self, tag, rep):
+        """The clipping part of a step report (absent without max_grad_norm).  A step dropped for a non-finite gradient changed
+        nothing: its count comes back out of the bias-correction step number, as _fall_back_from_chains does for lost steps.  Nothing
+        is raised and nothing is run again -- the batch is gone, as under torch's GradScaler."""
+        if len(rep) <= 4 or rep[1]:                  # (a step the chain flag skipped reports no norm decision)
+            return
+        self.last_grad_norm = rep[6]
+        self.clipped_steps += int(rep[4])
+        if rep[5]:
+            self.nonfinite_steps += 1
+            self.adam_t = max(self.adam_t - 1, 0)
+            print(f"[inpaintnet_amd] rank {dp.rank()}: optimizer step {tag} was dropped on every rank: its gradient held an inf "
+                  f"or a NaN (norm {rep[6]}); weights and moments were left alone")
 
     def check_steps(self, wait_all=False):
         """Read the reports of the optimizer steps issued at least `report_lag` steps ago (all outstanding ones with
         wait_all).  Raises ops.ChainTimeoutError if one of them skipped itself -- a persistent kernel of SOME rank had timed out,
         see _run_batch --, ValueError if a parameter became NaN / inf in one of them (the reference's "... has become nan",
         MeasureVAE/encoder.py:111-116, decoder.py:424-429), ops.TokenRangeError for a token outside the vocabulary
-        (decoder.py:36-45).  Identical on every rank of a data-parallel job: same reports, read at the same step."""
+        (decoder.py:36-45).  Identical on every rank of a data-parallel job: same reports, read at the same step.
+
+        With max_grad_norm set a report also carries the gradient norm and what the kernel did about it: last_grad_norm,
+        clipped_steps and nonfinite_steps follow the reports read here.  A step dropped for an inf / NaN gradient raises nothing: one
+        line is printed and adam_t goes down by one.  The host learns of it `report_lag` steps late, so the up to `report_lag` steps
+        queued in between ran with a bias-correction step number one too high; from the next launch on it is right again."""
         newest = self._tag - 1
         skipped = nonfinite = badtok = False
         while self._inflight and (wait_all or self._inflight[0] <= newest - self.report_lag):
             tag = self._inflight.popleft()
             rep = self._read_report(tag)
             skip, bad, tok = rep[1], rep[2], (rep[3] if len(rep) > 3 else False)
+            self._note_clip(tag, rep)
             if skip:
                 self._lost.append(tag)
             skipped |= skip
@@ -473,7 +521,9 @@ class Trainer(ABC):
         self._device_sync()
         while self._inflight:
             tag = self._inflight.popleft()
-            if self._read_report(tag)[1]:
+            rep = self._read_report(tag)
+            self._note_clip(tag, rep)
+            if rep[1]:
                 self._lost.append(tag)
         lost, self._lost = sorted(set(self._lost)), []
         n = self._chains_off()

@@ -8,8 +8,8 @@ from .trainer import Trainer, _ElboFn, _KLFn
 class VAETrainer(Trainer):
     feed_fields = (0,)                     # the metadata tensor is never read (vae_trainer.py:42-55)
 
-    def __init__(self, dataset, model, lr=1e-4):
-        super().__init__(dataset, model, lr)
+    def __init__(self, dataset, model, lr=1e-4, max_grad_norm=None):
+        super().__init__(dataset, model, lr, max_grad_norm=max_grad_norm)
 
     def loss_and_acc_for_batch(self, batch, epoch_num=None, train=True):
         """loss = CE_mean + 1e-3 * mean_b KL ; accuracy   (vae_trainer.py:16-40)"""
