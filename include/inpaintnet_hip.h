@@ -310,6 +310,32 @@ int inet_grad_sqnorm(const float* g, int64_t n, double* partials, void* stream);
 int inet_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                         float eps, int step, float gscale, float max_norm, const double* partials, const float* step_flag,
                         uint32_t* report, void* stream);
+/* The optimizer step with decoupled weight decay (AdamW) and an exponential moving average of the weights, in one launch
+ * (DESIGN.md section 19).  Inputs: everything inet_adam_step_clip takes, with `partials` now nullable; weight_decay >= 0, finite;
+ * decay_mask, nullable device uint32 words, ceil(n / 32) of them -- bit i & 31 of word i >> 5 set means element i decays, null means
+ * every element decays (torch.optim.AdamW's default); ema, a nullable device arena of n floats; ema_decay in [0, 1).  The rule:
+ *   1. Skip and scale are exactly today's.  With partials: the rule of inet_adam_step_clip, steps 1-6, norm, clip coefficient,
+ *      non-finite drop and flag precedence included.  Without partials: inet_adam_step_ex's rule -- only the chain / step flag skips,
+ *      and max_norm is ignored.
+ *   2. A skipped or dropped step leaves p, m, v AND ema bit for bit untouched.
+ *   3. An applied step: the launcher computes decay = (float)(1.0 - (double)lr * (double)weight_decay) and
+ *      omd = (float)(1.0 - (double)ema_decay), once, on the host.  Per element: m, v as today; p1 = decays(i) ? p * decay : p (the
+ *      product rounded to f32 on its own); p_new = p1 - lr_over_bc1 * (m / denom) as today.  This is torch's _single_tensor_adamw
+ *      order, param.mul_(1 - lr * wd) before the update.  report[2] ("a parameter left the finite range") tests p_new.
+ *   4. After an applied step, if ema is given: e_new = fmaf(ema_decay, e, omd * p_new), the product rounded on its own.  ema_decay == 0
+ *      therefore gives e_new == p_new bit for bit.
+ *   5. With weight_decay == 0, decay is exactly 1.0f: with ema null as well, p, m, v and the report are bit-identical to
+ *      inet_adam_step_clip (with partials) or inet_adam_step_ex (without) on the same inputs.
+ * report (nullable): always EIGHT words of host-mapped memory zeroed by the caller.  [0..3] as inet_adam_step_ex; with partials
+ * [4..6] are inet_adam_step_clip's (clipped, dropped, norm bits), without partials they stay 0; [7] stays 0.
+ * p, g, m, v and ema must be 16-byte aligned.  Data parallel: decay and EMA are element-wise functions of values that are
+ * bit-identical on every rank behind the all-reduce, so replicas and their EMA arenas stay bit-identical with nothing to coordinate.
+ * -1, before any launch, for: null p, g, m or v; n <= 0; step < 1; weight_decay negative, NaN or inf; ema_decay outside [0, 1) or
+ * NaN; partials given with !(max_norm > 0). */
+int inet_adam_step_w(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                     int step, float gscale, float max_norm, const double* partials, float weight_decay,
+                     const uint32_t* decay_mask, float* ema, float ema_decay, const float* step_flag, uint32_t* report,
+                     void* stream);
 /* dst: the TWO floats described above (chain status, token status of this process) */
 int inet_step_flag_export(float* dst, void* stream);
 /* Number of prologue launches that met a token index outside [0, num_notes) since the last reset (encoder input tokens,

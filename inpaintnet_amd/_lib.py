@@ -114,6 +114,7 @@ _SIGNATURES = {
     "inet_sqnorm_parts": (C.c_int, []),
     "inet_grad_sqnorm": (C.c_int, [_P, _L, _P, _P]),
     "inet_adam_step_clip": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _F, _P, _P, _P, _P]),
+    "inet_adam_step_w": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _F, _P, _F, _P, _P, _F, _P, _P, _P]),
     "inet_step_flag_export": (C.c_int, [_P, _P]),
     "inet_token_status": (C.c_int, [_I]),
     "inet_epoch_stats_add_ex": (C.c_int, [_P, _P, _P, _P, _P]),

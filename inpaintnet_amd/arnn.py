@@ -564,8 +564,10 @@ class AnticipationRNNBaseline(ConstraintModelGaussianReg):
 class AnticipationRNNGaussianRegTrainer(Trainer):
     """AnticipationRNN/anticipation_rnn_trainer.py:8-182"""
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
-        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm)
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
+                 ema_decay=None, ema_warmup=False):
+        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
+                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.min_num_measures_target = 2
         self.max_num_measure_target = 6
         self.measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
@@ -622,8 +624,10 @@ class AnticipationRNNBaselineTrainer(AnticipationRNNGaussianRegTrainer):
     mask over the ticks (rate p ~ U(0, 0.5) per batch, the same mask for every sequence of the batch).  The draws use
     Python's `random` (p) and torch's CPU generator (the mask), in the reference's order."""
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
-        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm)
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
+                 ema_decay=None, ema_warmup=False):
+        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
+                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.constraint_prod = 0.5
 
     def process_batch_data(self, batch):

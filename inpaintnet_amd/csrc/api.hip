@@ -258,6 +258,17 @@ int inet_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n,
     return pw_adam_clip(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, max_norm, partials, (hipStream_t)stream, step_flag,
                         report);
 }
+int inet_adam_step_w(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                     int step, float gscale, float max_norm, const double* partials, float weight_decay,
+                     const uint32_t* decay_mask, float* ema, float ema_decay, const float* step_flag, uint32_t* report,
+                     void* stream) {
+    if (!p || !g || !m || !v || n <= 0 || step < 1) return -1;
+    if (!(weight_decay >= 0.f) || !(weight_decay <= 3.402823466e38f)) return -1;                // negative, NaN, inf
+    if (!(ema_decay >= 0.f) || !(ema_decay < 1.f)) return -1;                                   // outside [0, 1), NaN
+    if (partials && !(max_norm > 0.f)) return -1;                                               // (without partials max_norm is ignored)
+    return pw_adamw(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, max_norm, partials, weight_decay, decay_mask, ema,
+                    ema_decay, (hipStream_t)stream, step_flag, report);
+}
 int inet_step_flag_export(float* dst, void* stream) {
     if (!dst) return -1;
     return pw_step_flag_export(dst, (hipStream_t)stream);

@@ -51,6 +51,12 @@ int pw_grad_sqnorm(const float* g, long n, double* partials, hipStream_t s);
 int pw_adam_clip(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
                  float gscale, float max_norm, const double* partials, hipStream_t s, const float* step_flag = nullptr,
                  unsigned* report = nullptr);
+// The step with decoupled weight decay and EMA shadow weights (the rule: pointwise.hip): pw_adam (partials null)
+// or pw_adam_clip (partials given) with p scaled by (float)(1 - lr * weight_decay) in front of the update where `mask` says so (null:
+// everywhere) and ema = fmaf(ema_decay, ema, (float)(1 - ema_decay) * p_new) behind it (ema null: none).  report: EIGHT words
+int pw_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step, float gscale,
+             float max_norm, const double* partials, float weight_decay, const unsigned* mask, float* ema, float ema_decay,
+             hipStream_t s, const float* step_flag = nullptr, unsigned* report = nullptr);
 int pw_step_flag_export(float* dst, hipStream_t s);
 int pw_epoch_stats_add(float* sums, const float* loss, const float* acc, hipStream_t s, const float* step_flag = nullptr);
 int pw_colsum(const float* X, long ld, int M, int N, float* out, hipStream_t s);

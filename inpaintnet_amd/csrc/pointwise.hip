@@ -355,6 +355,106 @@ __global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict_
     if (bad && report) __hip_atomic_store(report + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ---- decoupled weight decay and EMA shadow weights inside the step.  The rule, for one optimizer step with
+// weight_decay >= 0, a nullable decay mask (bit i & 31 of word i >> 5 set: element i decays; null: every element decays), a nullable
+// arena ema[0..n) and ema_decay in [0, 1):
+//   1. skip and scale are today's: with partials steps 1-6 of the rule above (norm, clip coefficient, non-finite drop, flag
+//      precedence), without partials adam_kernel's -- only the chain / step flag skips.
+//   2. a skipped or dropped step leaves p, m, v AND ema bit for bit untouched.
+//   3. an applied step: the launcher computes decay = (float)(1.0 - (double)lr * (double)weight_decay) and
+//      omd = (float)(1.0 - (double)ema_decay) once; per element m, v as adam_kernel, p1 = decays(i) ? p * decay : p (one rounding),
+//      p_new = p1 - lr_over_bc1 * (m / denom) as adam_kernel (torch's _single_tensor_adamw order: param.mul_(1 - lr * wd) first);
+//      report[2] tests p_new.
+//   4. ema given: e_new = fmaf(ema_decay, e, omd * p_new) (the product rounded on its own); ema_decay == 0 gives e_new == p_new.
+//   5. weight_decay == 0 gives decay == 1.0f exactly: with ema null p, m, v and the report are bit-identical to adam_clip_kernel
+//      (with partials) or adam_kernel (without).
+// report: EIGHT words; [4..6] are adam_clip_kernel's with partials and stay 0 without, [7] stays 0.
+// Rule 5 is a statement about roundings, so this kernel leaves none of them to the compiler: contraction is OFF in its body and every
+// fused operation is written out, in the forms adam_kernel and adam_clip_kernel are compiled to (-ffp-contract=fast picks them per
+// expression and per loop; tools/kernel_resources.py --asm shows them): body and tail m = fma(1 - b1, gr, b1 * m),
+// denom = fma(sqrt(v), inv_sqrt_bc2, eps), p = fma(-lr_over_bc1, m / denom, p1); v = fma(b2, v, gr * ((1 - b2) * gr)) in the body but
+// b2 * v + gr * ((1 - b2) * gr), both products rounded, in the tail.  p * decay is never fused into what follows: p * 1.0f - x as one
+// fma would round once where adam_kernel rounds twice.  tests/test_gpu_adamw_ema.py holds the identity at every size class.
+// adam_kernel's grid, 16-byte body and scalar tail with its own copy of the body (adam_kernel and adam_clip_kernel keep theirs as it
+// was compiled); EMA / MASK: whether `ema` / `mask` are given -- compile-time, so that the plain form carries neither loads nor
+// registers of the other three.  Four consecutive elements never straddle a mask word: the body reads ONE word per 16 bytes.
+template <bool EMA, bool MASK>
+__global__ void __launch_bounds__(kSqnormBlock)
+adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
+             float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2, float eps, float gscale, float max_norm,
+             const double* __restrict__ partials, float decay, const unsigned* __restrict__ mask, float* __restrict__ ema,
+             float ema_decay, float omd, const unsigned* __restrict__ abort_word, const float* __restrict__ step_flag,
+             unsigned* __restrict__ report) {
+#pragma clang fp contract(off)
+    __shared__ double part[4];
+    const bool skip = step_flag ? (*step_flag != 0.f)
+                                : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
+    bool nonfinite = false, clipped = false;
+    double norm = 0.0, c = 1.0;
+    if (partials) {                                  // uniform over the grid: adam_clip_kernel's prologue and decisions, word for word
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < kSqnormParts / kSqnormBlock; ++k) acc += partials[threadIdx.x + k * kSqnormBlock];
+        const double S = block_sum_d(acc, part);
+        norm = fabs((double)gscale) * sqrt(S);
+        nonfinite = !skip && !(fabs(norm) <= 1.7976931348623157e308);          // NaN or +inf
+        c = (double)max_norm / (norm + 1e-6);
+        clipped = !skip && !nonfinite && c < 1.0;
+    }
+    if (report && blockIdx.x == 0 && threadIdx.x == 0) {
+        __hip_atomic_store(report + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (skip) __hip_atomic_store(report + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (step_flag && step_flag[1] != 0.f) __hip_atomic_store(report + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (partials) {
+            if (clipped) __hip_atomic_store(report + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (nonfinite) __hip_atomic_store(report + 5, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(report + 6, __float_as_uint((float)norm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    if (skip || nonfinite) return;
+    const float gs = partials ? gscale * (clipped ? (float)c : 1.0f) : gscale;
+    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
+    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+    bool bad = false;
+    const long n4 = n >> 2;
+    f32x4* p4 = reinterpret_cast<f32x4*>(p);
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    f32x4* m4 = reinterpret_cast<f32x4*>(m);
+    f32x4* v4 = reinterpret_cast<f32x4*>(v);
+    f32x4* e4 = reinterpret_cast<f32x4*>(ema);
+    for (long i = tid; i < n4; i += stride) {
+        f32x4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ee;
+        if (EMA) ee = e4[i];
+        unsigned bits = 0xfu;
+        if (MASK) bits = mask[i >> 3] >> (((unsigned)i & 7u) << 2);            // elements 4i .. 4i+3: word (4i) >> 5, bit (4i) & 31
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gr = gg[e] * gs;
+            mm[e] = fmaf(omb1, gr, b1 * mm[e]);
+            vv[e] = fmaf(b2, vv[e], gr * (omb2 * gr));
+            const float denom = fmaf(sqrtf(vv[e]), inv_sqrt_bc2, eps);
+            const float p1 = (!MASK || ((bits >> e) & 1u)) ? pp[e] * decay : pp[e];
+            pp[e] = fmaf(-lr_over_bc1, mm[e] / denom, p1);
+            bad |= !(fabsf(pp[e]) <= 3.402823466e38f);          // NaN or +-inf
+            if (EMA) ee[e] = fmaf(ema_decay, ee[e], omd * pp[e]);
+        }
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+        if (EMA) e4[i] = ee;
+    }
+    for (long i = (n4 << 2) + tid; i < n; i += stride) {          // tail: the mask per element; v's sum rounds both products
+        const float gr = g[i] * gs;
+        const float mm = fmaf(omb1, gr, b1 * m[i]);
+        const float vv = b2 * v[i] + gr * (omb2 * gr);
+        m[i] = mm; v[i] = vv;
+        const float p1 = (!MASK || ((mask[i >> 5] >> ((unsigned)i & 31u)) & 1u)) ? p[i] * decay : p[i];
+        const float pn = fmaf(-lr_over_bc1, mm / fmaf(sqrtf(vv), inv_sqrt_bc2, eps), p1);
+        p[i] = pn;
+        bad |= !(fabsf(pn) <= 3.402823466e38f);
+        if (EMA) ema[i] = fmaf(ema_decay, ema[i], omd * pn);
+    }
+    if (bad && report) __hip_atomic_store(report + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 // dst[0] = 1 if a chain launch of this process has timed out since the last reset, else 0: the word a data-parallel caller sums
 // over ranks together with the gradients (inet_step_flag_export)
 // dst[1] = 1 if a prologue kernel of this process has met a token outside the vocabulary since the last reset (the host-mapped
@@ -1080,6 +1180,31 @@ int pw_adam_clip(float* p, const float* g, float* m, float* v, long n, float lr,
     hipLaunchKernelGGL(adam_clip_kernel, dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(kSqnormBlock), 0, s, p, g, m, v, n,
                        (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, gscale, max_norm, partials,
                        (const unsigned*)chain_dev_status(), step_flag, report);
+    return ok();
+}
+template <bool EMA, bool MASK>
+static void launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, long n, float lr_over_bc1, float inv_sqrt_bc2,
+                         float b1, float b2, float eps, float gscale, float max_norm, const double* partials, float decay,
+                         const unsigned* mask, float* ema, float ema_decay, float omd, const float* step_flag, unsigned* report) {
+    hipLaunchKernelGGL((adamw_kernel<EMA, MASK>), dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(kSqnormBlock), 0, s, p, g, m, v, n,
+                       lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, gscale, max_norm, partials, decay, mask, ema, ema_decay, omd,
+                       (const unsigned*)chain_dev_status(), step_flag, report);
+}
+int pw_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step, float gscale,
+             float max_norm, const double* partials, float weight_decay, const unsigned* mask, float* ema, float ema_decay,
+             hipStream_t s, const float* step_flag, unsigned* report) {
+    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+    // the two factors of the rule, rounded ONCE here: what the kernel multiplies by does not depend on how it was compiled
+    const float decay = (float)(1.0 - (double)lr * (double)weight_decay), omd = (float)(1.0 - (double)ema_decay);
+    // adam's traffic + a bit per element of the mask + one read and one write of the EMA arena + the partials
+    ProfScope prof(PROF_HBM, 0.0, s, partials ? "adamw_clip" : "adamw",
+                   28.0 * (double)n + (mask ? (double)n / 8.0 : 0.0) + (ema ? 8.0 * (double)n : 0.0) + (partials ? 8.0 * kSqnormParts : 0.0));
+    const float l1 = (float)(lr / bc1), is2 = (float)(1.0 / sqrt(bc2));
+#define ADAMW_LAUNCH(E, M) launch_adamw<E, M>(s, p, g, m, v, n, l1, is2, b1, b2, eps, gscale, max_norm, partials, decay, mask, ema, \
+                                            ema_decay, omd, step_flag, report)
+    if (ema) { if (mask) ADAMW_LAUNCH(true, true); else ADAMW_LAUNCH(true, false); }
+    else     { if (mask) ADAMW_LAUNCH(false, true); else ADAMW_LAUNCH(false, false); }
+#undef ADAMW_LAUNCH
     return ok();
 }
 int pw_step_flag_export(float* dst, hipStream_t s) {

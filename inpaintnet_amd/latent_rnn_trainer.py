@@ -16,8 +16,10 @@ from .trainer import Trainer
 class LatentRNNTrainer(Trainer):
     feed_fields = (0,)                     # the metadata tensor of a batch is never read (latent_rnn_trainer.py:31-33)
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
-        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm)
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
+                 ema_decay=None, ema_warmup=False):
+        super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
+                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup)
         # window sizes of the stochastic split (latent_rnn_trainer.py:17-22)
         self.min_num_measures_target, self.max_num_measure_target = 2, 6
         n_bars = self.dataset.n_bars

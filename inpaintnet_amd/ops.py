@@ -538,6 +538,48 @@ def adam_step_clip(p, g, m, v, lr, step, max_norm, partials, b1=0.9, b2=0.999, e
                                          stream_ptr()), "inet_adam_step_clip")
 
 
+def pack_decay_mask(n, ranges, device="cuda"):
+    """The decay mask of inet_adam_step_w for an arena of n elements: ceil(n / 32) 32-bit words (an int32 tensor: the bits are what
+    counts), bit i & 31 of word i >> 5 set for every element i of one of `ranges`, a list of [start, stop) element ranges.  Built on
+    the host, copied to `device` once."""
+    import numpy as np
+    bits = np.zeros(((int(n) + 31) // 32) * 32, dtype=np.uint8)
+    for start, stop in ranges:
+        if not 0 <= start <= stop <= n:
+            raise ValueError(f"decay range [{start}, {stop}) outside the arena of {n} elements")
+        bits[start:stop] = 1
+    words = np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+    return torch.from_numpy(words.view(np.int32).copy()).to(device)
+
+
+def adamw_step(p, g, m, v, lr, step, weight_decay=0.0, decay_mask=None, ema=None, ema_decay=0.0, max_norm=None, partials=None,
+               b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, step_flag=None, report=None):
+    """adam_step (partials None) or adam_step_clip (partials = what grad_sqnorm(g) left, max_norm in (0, inf]) with decoupled weight
+    decay and an exponential moving average of the weights in the same launch (include/inpaintnet_hip.h inet_adam_step_w states the
+    rule): p is scaled by float32(1 - lr * weight_decay) in front of the update where decay_mask (pack_decay_mask; None: everywhere)
+    says so, and ema (None: none) becomes ema_decay * ema + float32(1 - ema_decay) * p behind it.  A skipped or dropped step leaves
+    ema alone as well.  report: EIGHT int32 words of PINNED host memory, zeroed by the caller: [0..3] as adam_step's, [4..6] as
+    adam_step_clip's with partials and 0 without, [7] 0."""
+    for t in (p, g, m, v):
+        _f32c(t)
+    n = p.numel()
+    assert g.numel() == n and m.numel() == n and v.numel() == n
+    if ema is not None:
+        assert _f32c(ema).numel() == n
+    if decay_mask is not None:
+        assert decay_mask.is_cuda and decay_mask.dtype == torch.int32 and decay_mask.is_contiguous() \
+            and decay_mask.numel() >= (n + 31) // 32
+    if partials is not None:
+        assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= sqnorm_parts()
+        assert max_norm is not None, "partials without max_norm"
+    if report is not None:
+        assert report.dtype == torch.int32 and report.numel() >= 8 and report.is_pinned() and report.is_contiguous()
+    check(_lib.lib().inet_adam_step_w(ptr(p), ptr(g), ptr(m), ptr(v), n, float(lr), float(b1), float(b2), float(eps), int(step),
+                                      float(gscale), 0.0 if max_norm is None else float(max_norm), ptr(partials),
+                                      float(weight_decay), ptr(decay_mask), ptr(ema), float(ema_decay), ptr(step_flag),
+                                      ptr(report), stream_ptr()), "inet_adam_step_w")
+
+
 def step_flag_export(dst):
     """dst[0] = 1.0 if a chain launch of this process has timed out since the last reset else 0.0 (on the current stream)."""
     check(_lib.lib().inet_step_flag_export(ptr(_f32c(dst)), stream_ptr()), "inet_step_flag_export")

@@ -14,13 +14,15 @@ the static loss helpers.  Differences that are the point of the build:
     (the reference syncs every batch: utils/trainer.py:154).
 Plotting / tensorboard plumbing of the reference is out of scope.
 """
+import contextlib
 import gc
+import math
 import os
 import struct
 import sys
 import time
 from abc import ABC, abstractmethod
-from collections import deque
+from collections import OrderedDict, deque
 
 import torch
 
@@ -141,12 +143,32 @@ class Trainer(ABC):
 
     feed_fields = (0, 1)       # which members of a (score, metadata) batch the trainer needs on the device
 
-    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None):
+    def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
+                 ema_decay=None, ema_warmup=False):
         """max_grad_norm (None or 0 < value <= inf): clip the gradient arena by its global norm in front of every optimizer step, as
         torch.nn.utils.clip_grad_norm_(..., error_if_nonfinite=False) around optimizer.step() would, and DROP a step whose gradient
         holds an inf or a NaN instead of folding it into the weights -- both on the device (ops.grad_sqnorm +
         ops.adam_step_clip in the place of ops.adam_step; inf = measure and drop only, never clip).  The step reports, read at the
-        usual lag (check_steps), keep last_grad_norm, clipped_steps and nonfinite_steps up to date.  None: nothing changes."""
+        usual lag (check_steps), keep last_grad_norm, clipped_steps and nonfinite_steps up to date.  None: nothing changes.
+
+        weight_decay (>= 0, finite): decoupled weight decay as torch.optim.AdamW applies it, p *= 1 - lr * weight_decay in front of
+        every update, inside the optimizer launch (ops.adamw_step).  The weight matrices decay -- the entries
+        of model._table with "weight" in the name and two dimensions, what Model.init_reference_style calls a weight matrix; biases,
+        b_0 and x_0 do not.  decay_all=True decays every element, torch's default.
+        ema_decay (None or in [0, 1)): keep `self.ema`, an exponential moving average of the weights, up to date inside the same
+        launch: ema = ema_decay * ema + (1 - ema_decay) * p behind every applied step; a skipped or dropped step leaves it alone.
+        ema_warmup: step t (t = adam_t of that launch) uses min(ema_decay, (1 + t) / (10 + t)), evaluated on the host per launch
+        like lr.  ema_state_dict() and `with trainer.ema_weights():` read it; train_model validates under it.
+        With weight_decay == 0 and ema_decay None the trainer launches what it launched before, under the same labels."""
+        weight_decay = float(weight_decay)
+        if not (weight_decay >= 0.0 and math.isfinite(weight_decay)):          # (NaN fails the comparison)
+            raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}")
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= ema_decay < 1.0:
+                raise ValueError(f"ema_decay must be None or in [0, 1), got {ema_decay}")
+        elif ema_warmup:
+            raise ValueError("ema_warmup needs ema_decay")
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if not max_grad_norm > 0.0:              # (NaN fails the comparison too)
@@ -164,6 +186,12 @@ class Trainer(ABC):
         self.adam_m = torch.zeros_like(model.flat)
         self.adam_v = torch.zeros_like(model.flat)
         self.adam_t = 0
+        self.weight_decay, self.decay_all = weight_decay, bool(decay_all)
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        # built once: the mask only when something decays and not everything does, the EMA arena from the weights as they are now
+        self._decay_mask = self._build_decay_mask() if weight_decay > 0.0 and not decay_all else None
+        self.ema = model.flat.clone() if ema_decay is not None else None
+        self._ema_swapped = None                     # model.flat's own values while ema_weights() holds the EMA in their place
         self.early_stopping = False
         if early_stopping:
             self.early_stopping = True
@@ -221,10 +249,14 @@ class Trainer(ABC):
                 stats = []
                 for loader, train in ((train_loader, True), (val_loader, False)):
                     self.model.train(train)
-                    stats += self.loss_and_acc_on_epoch(data_loader=loader, epoch_num=epoch, train=train)
+                    # with an EMA the validation pass -- and with it early stopping -- looks at the EMA weights
+                    with (self.ema_weights() if self.ema is not None and not train else contextlib.nullcontext()):
+                        stats += self.loss_and_acc_on_epoch(data_loader=loader, epoch_num=epoch, train=train)
                 self.print_epoch_stats(epoch, num_epochs, *stats)
                 if dp.rank() == 0:
                     self.model.save()
+                    if self.ema is not None:
+                        torch.save({k: v.cpu() for k, v in self.ema_state_dict().items()}, self.model.filepath + '_ema')
                     if epoch > 0 and epoch % 10 == 0:
                         self.model.save_checkpoint(epoch)
                         self.save_training_state(self.model.filepath + f'_{epoch}.trainer', epoch + 1)
@@ -359,6 +391,8 @@ class Trainer(ABC):
     def step(self):
         """utils/trainer.py:172-177 (+ the data-parallel gradient exchange).  May raise ops.ChainTimeoutError / ValueError
         for an EARLIER step (see check_steps)."""
+        if self._ema_swapped is not None:
+            raise RuntimeError("step() inside ema_weights(): model.flat holds the EMA weights, not the trained ones")
         self._join_side_work()
         m = self.model
         flag = self._flag()
@@ -375,9 +409,64 @@ class Trainer(ABC):
             self._launch_optimizer(tag, gscale, flag)
             self._inflight.append(tag)
             self.check_steps()
+        elif self._adamw_on():                       # (no reports: host arenas never get here, a device trainer always reports)
+            ops.adamw_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, **self._adamw_args(gscale, clip=False))
         else:
             ops.adam_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.betas[0], self.betas[1],
                           self.eps, gscale)
+
+    # ---- decoupled weight decay and the EMA shadow weights ----
+    def _adamw_on(self):
+        return self.weight_decay > 0.0 or self.ema_decay is not None
+
+    def _build_decay_mask(self):
+        """The elements that decay by default: the weight matrices, by the criterion Model.init_reference_style uses."""
+        ranges = [(off, off + shape[0] * shape[1]) for name, off, shape in self.model._table if "weight" in name and len(shape) == 2]
+        return ops.pack_decay_mask(self.model.flat.numel(), ranges, device=self.model.flat.device)
+
+    def ema_decay_at(self, t):
+        """The EMA decay of the launch whose bias-correction step number is t: ema_decay, behind min(., (1 + t) / (10 + t)) with
+        ema_warmup.  t is adam_t as the host knows it at the launch: after a dropped step it runs one too high for up to report_lag
+        launches, exactly as the bias correction does (check_steps)."""
+        if self.ema_warmup:
+            return min(self.ema_decay, (1.0 + t) / (10.0 + t))
+        return self.ema_decay
+
+    def _adamw_args(self, gscale, clip=True):
+        """What ops.adamw_step takes beyond the arenas, lr and the step number.  The partials only with max_grad_norm (and only
+        where grad_sqnorm ran in front: clip=False is the report-less branch of step(), which does not measure)."""
+        on = clip and self.max_grad_norm is not None
+        return dict(weight_decay=self.weight_decay, decay_mask=self._decay_mask, ema=self.ema,
+                    ema_decay=0.0 if self.ema is None else self.ema_decay_at(self.adam_t),
+                    max_norm=self.max_grad_norm if on else None, partials=self._sqnorm if on else None,
+                    b1=self.betas[0], b2=self.betas[1], eps=self.eps, gscale=gscale)
+
+    def ema_state_dict(self):
+        """The EMA weights under the keys and shapes of model.state_dict(): load them into a model to evaluate or sample from it."""
+        if self.ema is None:
+            raise RuntimeError("this trainer keeps no EMA (ema_decay=None)")
+        out = OrderedDict()
+        for name, off, shape in self.model._table:
+            out[name] = self.ema[off:off + math.prod(shape)].view(shape).detach().clone()
+        return out
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context model.flat holds the EMA weights: the model's own are copied aside and the EMA copied over them on the
+        current stream, behind everything queued; they come back on exit, also on an exception.  The parameter views alias
+        model.flat and nothing in the library keeps values derived from the weights across calls, so every forward pass inside sees
+        the EMA.  step() inside raises RuntimeError."""
+        if self.ema is None:
+            raise RuntimeError("this trainer keeps no EMA (ema_decay=None)")
+        if self._ema_swapped is not None:
+            raise RuntimeError("ema_weights() is not re-entrant")
+        self._ema_swapped = self.model.flat.clone()
+        self.model.flat.copy_(self.ema)
+        try:
+            yield self.model
+        finally:
+            self.model.flat.copy_(self._ema_swapped)
+            self._ema_swapped = None
 
     # ---- the device-touching pieces of the protocol, one method each: tests/test_dp_gloo.py drives step(), check_steps() and the
     # ---- fallback / replay logic with host stand-ins for them (world 2, gloo)
@@ -394,7 +483,14 @@ class Trainer(ABC):
         m = self.model
         rec = self._report_slot(tag)
         rec.zero_()                                  # host write: the launch that last wrote this record was waited for when it was read
-        if self.max_grad_norm is None:
+        if self._adamw_on():
+            # decay and EMA are element-wise functions of values that are bit-identical on every rank behind the exchange: the
+            # replicas and their EMA arenas stay bit-identical with nothing to coordinate
+            if self.max_grad_norm is not None:
+                self._sqnorm = ops.grad_sqnorm(m.grad, self._sqnorm)
+            ops.adamw_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, step_flag=flag, report=rec,
+                           **self._adamw_args(gscale))
+        elif self.max_grad_norm is None:
             ops.adam_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.betas[0], self.betas[1],
                           self.eps, gscale, step_flag=flag, report=rec)
         else:
@@ -419,8 +515,9 @@ class Trainer(ABC):
 
     def _report_slot(self, tag):
         if self._reports is None:
-            # four words per record (inet_adam_step_ex), eight with clipping (inet_adam_step_clip)
-            self._reports = torch.zeros(self._NREP, 4 if self.max_grad_norm is None else 8, dtype=torch.int32).pin_memory()
+            # four words per record (inet_adam_step_ex), eight with clipping (inet_adam_step_clip) or decay / EMA (inet_adam_step_w)
+            words = 4 if self.max_grad_norm is None and not self._adamw_on() else 8
+            self._reports = torch.zeros(self._NREP, words, dtype=torch.int32).pin_memory()
             self._report_events = [torch.cuda.Event() for _ in range(self._NREP)]
         return self._reports[tag % self._NREP]
 
@@ -432,7 +529,7 @@ class Trainer(ABC):
         if not r[0]:
             raise RuntimeError(f"optimizer launch {tag} left no report (the kernel did not run?)")
         rep = bool(r[0]), bool(r[1]), bool(r[2]), bool(r[3])
-        if len(r) > 4:
+        if self.max_grad_norm is not None:           # (an eight-word record of inet_adam_step_w without partials carries no norm)
             rep += (bool(r[4]), bool(r[5]), struct.unpack("<f", struct.pack("<i", r[6]))[0])
         return rep
 
@@ -460,7 +557,8 @@ class Trainer(ABC):
         With max_grad_norm set a report also carries the gradient norm and what the kernel did about it: last_grad_norm,
         clipped_steps and nonfinite_steps follow the reports read here.  A step dropped for an inf / NaN gradient raises nothing: one
         line is printed and adam_t goes down by one.  The host learns of it `report_lag` steps late, so the up to `report_lag` steps
-        queued in between ran with a bias-correction step number one too high; from the next launch on it is right again."""
+        queued in between ran with a bias-correction step number one too high; from the next launch on it is right again.  The
+        warm-up of the EMA decay (ema_warmup, ema_decay_at) is evaluated at the same step number and lags in the same way."""
         newest = self._tag - 1
         skipped = nonfinite = badtok = False
         while self._inflight and (wait_all or self._inflight[0] <= newest - self.report_lag):
@@ -539,7 +637,9 @@ class Trainer(ABC):
     def training_state(self, next_epoch=0):
         return {"adam_m": self.adam_m.cpu(), "adam_v": self.adam_v.cpu(), "adam_t": self.adam_t, "lr": self.lr,
                 "betas": self.betas, "eps": self.eps, "next_epoch": int(next_epoch),
-                "num_parameters": int(self.model.flat.numel())}
+                "num_parameters": int(self.model.flat.numel()),
+                "weight_decay": self.weight_decay, "decay_all": self.decay_all, "ema_decay": self.ema_decay,
+                "ema_warmup": self.ema_warmup, "ema": None if self.ema is None else self.ema.cpu()}
 
     def save_training_state(self, path, next_epoch=0):
         torch.save(self.training_state(next_epoch), path)
@@ -555,6 +655,25 @@ class Trainer(ABC):
         self.adam_t = int(st["adam_t"])
         self.lr, self.betas, self.eps = float(st["lr"]), tuple(st["betas"]), float(st["eps"])
         self.start_epoch = int(st["next_epoch"])
+        if "weight_decay" in st:
+            self.weight_decay, self.decay_all = float(st["weight_decay"]), bool(st["decay_all"])
+            self.ema_decay, self.ema_warmup = st["ema_decay"], bool(st["ema_warmup"])
+            masked = self.weight_decay > 0.0 and not self.decay_all
+            self._decay_mask = (self._decay_mask if self._decay_mask is not None else self._build_decay_mask()) if masked else None
+            if self.ema_decay is None:
+                self.ema = None
+            elif st["ema"] is not None:
+                self.ema = self.model.flat.clone() if self.ema is None else self.ema
+                self.ema.copy_(st["ema"])
+        elif self.ema is not None:
+            # a state written before weight decay and EMA existed: the settings stay this trainer's, the EMA starts at the weights
+            self.ema.copy_(self.model.flat)
+            print("[inpaintnet_amd] training state without an EMA: the EMA arena was seeded from the model's weights as loaded")
+        if self._reports is not None and self._reports.shape[1] < 8 and self._adamw_on():
+            # the loaded settings need eight-word records: read what the four-word ones still hold (waits for those launches and
+            # raises what they report), then replace the ring -- its events stay, none is pending any more
+            self.check_steps(wait_all=True)
+            self._reports = torch.zeros(self._NREP, 8, dtype=torch.int32).pin_memory()
         return self.start_epoch
 
     @abstractmethod

@@ -8,8 +8,10 @@ from .trainer import Trainer, _ElboFn, _KLFn
 class VAETrainer(Trainer):
     feed_fields = (0,)                     # the metadata tensor is never read (vae_trainer.py:42-55)
 
-    def __init__(self, dataset, model, lr=1e-4, max_grad_norm=None):
-        super().__init__(dataset, model, lr, max_grad_norm=max_grad_norm)
+    def __init__(self, dataset, model, lr=1e-4, max_grad_norm=None, weight_decay=0.0, decay_all=False, ema_decay=None,
+                 ema_warmup=False):
+        super().__init__(dataset, model, lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay, decay_all=decay_all,
+                         ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     def loss_and_acc_for_batch(self, batch, epoch_num=None, train=True):
         """loss = CE_mean + 1e-3 * mean_b KL ; accuracy   (vae_trainer.py:16-40)"""
