@@ -267,7 +267,9 @@ int inet_sample_forced(const float* weights, int64_t ld_w, int rows, int V, floa
                        const uint64_t* allow, int64_t allow_stride, const int32_t* forced, int64_t forced_stride, void* stream);
 
 /* ---- optimizer: torch.optim.Adam as built at utils/trainer.py:32-35, stepped at :172-177 -------- */
-/* p,g,m,v: arenas of n floats; step is 1-based; grads are multiplied by gscale first (1/world_size for DP) */
+/* p,g,m,v: arenas of n floats; step is 1-based; grads are multiplied by gscale first (1/world_size for DP).
+ * The four entry points below are ONE kernel: inet_adam_step_w with everything it adds switched off IS
+ * inet_adam_step_clip, and that without partials IS inet_adam_step_ex -- the same launch, not a bit-identical twin. */
 int inet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                    float eps, int step, float gscale, void* stream);
 /* The same step for a caller that must know, without stalling the queue, what the kernel decided (round 4):
@@ -326,8 +328,9 @@ int inet_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n,
  *      therefore gives e_new == p_new bit for bit.
  *   5. With weight_decay == 0, decay is exactly 1.0f: with ema null as well, p, m, v and the report are bit-identical to
  *      inet_adam_step_clip (with partials) or inet_adam_step_ex (without) on the same inputs.
- * report (nullable): always EIGHT words of host-mapped memory zeroed by the caller.  [0..3] as inet_adam_step_ex; with partials
- * [4..6] are inet_adam_step_clip's (clipped, dropped, norm bits), without partials they stay 0; [7] stays 0.
+ * report (nullable): host-mapped words zeroed by the caller, [0..3] as inet_adam_step_ex.  With partials EIGHT words: [4..6] are
+ * inet_adam_step_clip's (clipped, dropped, norm bits), [7] stays 0.  Without partials the kernel stores to [0..3] only: FOUR words
+ * are enough, and a longer record keeps whatever its other words held.
  * p, g, m, v and ema must be 16-byte aligned.  Data parallel: decay and EMA are element-wise functions of values that are
  * bit-identical on every rank behind the all-reduce, so replicas and their EMA arenas stay bit-identical with nothing to coordinate.
  * -1, before any launch, for: null p, g, m or v; n <= 0; step < 1; weight_decay negative, NaN or inf; ema_decay outside [0, 1) or

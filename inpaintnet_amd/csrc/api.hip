@@ -236,15 +236,23 @@ int inet_latent_bwd(const float* dz, const float* mu, const float* logsigma, con
     if (!mu || !logsigma || !dmu || !dlogsigma || n <= 0) return -1;
     return pw_latent_bwd(dz, mu, logsigma, eps, kscale, kscale_dev, dmu, dlogsigma, n, (hipStream_t)stream);
 }
+// the four entry points of the optimizer step: one check, one launcher (pw_adam_step)
+static int adam_step_checked(const PwAdamStep& a, void* stream) {
+    if (!a.p || !a.g || !a.m || !a.v || a.n <= 0 || a.step < 1) return -1;
+    if (!(a.weight_decay >= 0.f) || !(a.weight_decay <= 3.402823466e38f)) return -1;            // negative, NaN, inf
+    if (!(a.ema_decay >= 0.f) || !(a.ema_decay < 1.f)) return -1;                               // outside [0, 1), NaN
+    if (a.partials && !(a.max_norm > 0.f)) return -1;                                           // NaN fails the comparison; without partials max_norm is ignored
+    return pw_adam_step(a, (hipStream_t)stream);
+}
 int inet_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                    float eps, int step, float gscale, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || step < 1) return -1;
-    return pw_adam(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, (hipStream_t)stream);
+    return adam_step_checked({p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, 0.f, nullptr, 0.f, nullptr, nullptr, 0.f, nullptr, nullptr},
+                             stream);
 }
 int inet_adam_step_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                       float eps, int step, float gscale, const float* step_flag, uint32_t* report, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || step < 1) return -1;
-    return pw_adam(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, (hipStream_t)stream, step_flag, report);
+    return adam_step_checked({p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, 0.f, nullptr, 0.f, nullptr, nullptr, 0.f, step_flag, report},
+                             stream);
 }
 int inet_sqnorm_parts(void) { return pw_sqnorm_parts(); }
 int inet_grad_sqnorm(const float* g, int64_t n, double* partials, void* stream) {
@@ -254,20 +262,16 @@ int inet_grad_sqnorm(const float* g, int64_t n, double* partials, void* stream) 
 int inet_adam_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                         float eps, int step, float gscale, float max_norm, const double* partials, const float* step_flag,
                         uint32_t* report, void* stream) {
-    if (!p || !g || !m || !v || !partials || n <= 0 || step < 1 || !(max_norm > 0.f)) return -1;       // (NaN fails the comparison)
-    return pw_adam_clip(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, max_norm, partials, (hipStream_t)stream, step_flag,
-                        report);
+    if (!partials) return -1;
+    return adam_step_checked({p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, max_norm, partials, 0.f, nullptr, nullptr, 0.f, step_flag,
+                              report}, stream);
 }
 int inet_adam_step_w(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                      int step, float gscale, float max_norm, const double* partials, float weight_decay,
                      const uint32_t* decay_mask, float* ema, float ema_decay, const float* step_flag, uint32_t* report,
                      void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || step < 1) return -1;
-    if (!(weight_decay >= 0.f) || !(weight_decay <= 3.402823466e38f)) return -1;                // negative, NaN, inf
-    if (!(ema_decay >= 0.f) || !(ema_decay < 1.f)) return -1;                                   // outside [0, 1), NaN
-    if (partials && !(max_norm > 0.f)) return -1;                                               // (without partials max_norm is ignored)
-    return pw_adamw(p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, max_norm, partials, weight_decay, decay_mask, ema,
-                    ema_decay, (hipStream_t)stream, step_flag, report);
+    return adam_step_checked({p, g, m, v, n, lr, beta1, beta2, eps, step, gscale, max_norm, partials, weight_decay, decay_mask, ema,
+                              ema_decay, step_flag, report}, stream);
 }
 int inet_step_flag_export(float* dst, void* stream) {
     if (!dst) return -1;

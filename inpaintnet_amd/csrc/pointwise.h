@@ -38,25 +38,21 @@ int pw_sample_constrained(const float* W, long ld_w, int rows, int V, float temp
 int pw_sample_forced(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
                      double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
                      long allow_stride, const int* forced, long forced_stride, hipStream_t s);
-// step_flag (optional device float): non-zero = skip (the ranks' summed chain status); report (optional, 4 host-mapped words
-// zeroed by the caller): [0] = 1 executed, [1] = 1 skipped, [2] = 1 a parameter became non-finite
-int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
-            float gscale, hipStream_t s, const float* step_flag = nullptr, unsigned* report = nullptr);
-// Global-norm clipping (the rule: pointwise.hip), two launches: partials[pw_sqnorm_parts()] = the f64 sums of
-// squares of the fixed grid's shares of g (every entry written: nothing to zero in front); then pw_adam with the clip coefficient and
-// the non-finite skip derived from them.  report (optional): EIGHT host-mapped words zeroed by the caller -- [0..3] as pw_adam,
-// [4] = 1 clipped, [5] = 1 skipped for an inf / NaN gradient, [6] = the bits of (float)norm, [7] = 0
+// The norm of the gradient arena: partials[pw_sqnorm_parts()] = the f64 sums of squares of the fixed grid's shares of g (every entry
+// written: nothing to zero in front), what the optimizer step takes as `partials`.
 int pw_sqnorm_parts();
 int pw_grad_sqnorm(const float* g, long n, double* partials, hipStream_t s);
-int pw_adam_clip(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
-                 float gscale, float max_norm, const double* partials, hipStream_t s, const float* step_flag = nullptr,
-                 unsigned* report = nullptr);
-// The step with decoupled weight decay and EMA shadow weights (the rule: pointwise.hip): pw_adam (partials null)
-// or pw_adam_clip (partials given) with p scaled by (float)(1 - lr * weight_decay) in front of the update where `mask` says so (null:
-// everywhere) and ema = fmaf(ema_decay, ema, (float)(1 - ema_decay) * p_new) behind it (ema null: none).  report: EIGHT words
-int pw_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step, float gscale,
-             float max_norm, const double* partials, float weight_decay, const unsigned* mask, float* ema, float ema_decay,
-             hipStream_t s, const float* step_flag = nullptr, unsigned* report = nullptr);
+// The optimizer step, one launch (the rule: pointwise.hip).  Nullable members switch a part off.
+struct PwAdamStep {
+    float* p; const float* g; float* m; float* v; long n;
+    float lr, b1, b2, eps; int step; float gscale;
+    float max_norm; const double* partials;      // global-norm clipping and the non-finite drop; null: neither, max_norm is ignored
+    float weight_decay; const unsigned* mask;    // p *= (float)(1 - lr * weight_decay) where the mask says so; null: everywhere
+    float* ema; float ema_decay;                 // ema = fmaf(ema_decay, ema, (float)(1 - ema_decay) * p_new); null: none
+    const float* step_flag;                      // device float, non-zero = skip (the ranks' summed chain status); null: this process's word
+    unsigned* report;                            // host-mapped words zeroed by the caller: four, eight with partials; null: none
+};
+int pw_adam_step(const PwAdamStep& a, hipStream_t s);
 int pw_step_flag_export(float* dst, hipStream_t s);
 int pw_epoch_stats_add(float* sums, const float* loss, const float* acc, hipStream_t s, const float* step_flag = nullptr);
 int pw_colsum(const float* X, long ld, int M, int N, float* out, hipStream_t s);

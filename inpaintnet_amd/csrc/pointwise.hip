@@ -199,79 +199,8 @@ __global__ void latent_bwd_kernel(const float* __restrict__ dz, const float* __r
     }
 }
 
-// torch.optim.Adam (2.x single-tensor form): denom = sqrt(v)/sqrt(bc2) + eps; p -= lr/bc1 * m/denom
-// The update of the calling thread's grid-stride share (tid = its index in the grid, stride = the grid's threads: the kernels read
-// blockDim / gridDim themselves, which keeps adam_kernel's code what it was before the body was shared), the body adam_kernel and
-// adam_clip_kernel have in common; returns whether one of its parameters left the finite range.
-__device__ __forceinline__ bool adam_update(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                            float* __restrict__ v, long n, float lr_over_bc1, float inv_sqrt_bc2, float b1,
-                                            float b2, float eps, float gscale, long tid, long stride) {
-    bool bad = false;
-    const long n4 = n >> 2;
-    f32x4* p4 = reinterpret_cast<f32x4*>(p);
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
-    f32x4* m4 = reinterpret_cast<f32x4*>(m);
-    f32x4* v4 = reinterpret_cast<f32x4*>(v);
-    for (long i = tid; i < n4; i += stride) {
-        f32x4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gr = gg[e] * gscale;
-            mm[e] = b1 * mm[e] + (1.f - b1) * gr;
-            vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
-            const float denom = sqrtf(vv[e]) * inv_sqrt_bc2 + eps;
-            pp[e] -= lr_over_bc1 * (mm[e] / denom);
-            bad |= !(fabsf(pp[e]) <= 3.402823466e38f);          // NaN or +-inf
-        }
-        p4[i] = pp; m4[i] = mm; v4[i] = vv;
-    }
-    // tail (n is a multiple of 4 for arenas; kept for generality)
-    for (long i = (n4 << 2) + tid; i < n; i += stride) {
-        const float gr = g[i] * gscale;
-        const float mm = b1 * m[i] + (1.f - b1) * gr;
-        const float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        m[i] = mm; v[i] = vv;
-        const float pn = p[i] - lr_over_bc1 * (mm / (sqrtf(vv) * inv_sqrt_bc2 + eps));
-        p[i] = pn;
-        bad |= !(fabsf(pn) <= 3.402823466e38f);
-    }
-    return bad;
-}
-
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
-                            float eps, float gscale, const unsigned* __restrict__ abort_word,
-                            const float* __restrict__ step_flag, unsigned* __restrict__ report) {
-    // A chain kernel gave up waiting for its group (chain.h): the gradients of the step are not valid, so the step leaves
-    // parameters and moments as they are.  Which word decides: `step_flag` when the caller passes one -- the flags of ALL
-    // ranks summed with the gradients (inet_step_flag_export + the all-reduce), so that every rank of a data-parallel job
-    // takes the same decision --, else this process's own device word.  `report` (four host-mapped words owned by the caller) tells
-    // the host what was decided and whether a parameter left the finite range (encoder.py:111-116, decoder.py:424-429).
-    const bool skip = step_flag ? (*step_flag != 0.f)
-                                : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
-    if (report && blockIdx.x == 0 && threadIdx.x == 0) {
-        __hip_atomic_store(report + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (skip) __hip_atomic_store(report + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        // word 3: SOME rank's prologue kernels met a token outside the vocabulary (step_flag[1] = the ranks' exported token words,
-        // summed with the gradients): every rank raises the reference's check_index ValueError at the same step
-        if (step_flag && step_flag[1] != 0.f) __hip_atomic_store(report + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (skip) return;
-    const bool bad = adam_update(p, g, m, v, n, lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, gscale,
-                                 (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-    if (bad && report) __hip_atomic_store(report + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// ---- global-norm clipping in front of the step.  The rule, for the gradient arena g[0..n), gscale and
-// 0 < max_norm <= +inf:
-//   1. S = sum (double)g_i * (double)g_i: every square exact in f64, the sum in f64 in a FIXED order that depends on n only;
-//      norm = |gscale| * sqrt(S) in f64.
-//   2. nonfinite = !isfinite(norm)  (a finite f32 arena cannot overflow the f64 sum: true iff some element is inf or NaN).
-//   3. c = max_norm / (norm + 1e-6) in f64 (torch's clip_grad_norm_ coefficient); scale = c < 1 ? (float)c : 1.0f;
-//      clipped = c < 1.  max_norm = +inf never clips.
-//   4. the chain / step flag says skip: the step is skipped as adam_kernel skips it, nonfinite and clipped are reported as 0.
-//   5. else nonfinite: p, m, v stay untouched, report[5] = 1, report[1] and report[2] stay 0 (not a chain failure).
-//   6. else Adam exactly as adam_kernel with gscale replaced by the ONE f32 product gscale * scale.
+// ---- the optimizer step and, in front of it, the norm of the gradient arena.  grad_sqnorm_kernel leaves kSqnormParts f64 partial sums
+// of squares; adamw_kernel, the ONE step kernel behind every inet_adam_step* entry point, adds them up itself (clip rule, below).
 constexpr int kSqnormParts = 1024;               // workgroups of grad_sqnorm_kernel = doubles of its output
 constexpr int kSqnormBlock = 256;
 
@@ -316,67 +245,59 @@ __global__ void __launch_bounds__(kSqnormBlock) grad_sqnorm_kernel(const float* 
         a2 = fma((double)x[2], (double)x[2], a2);
         a3 = fma((double)x[3], (double)x[3], a3);
     }
-    // tail, as adam_kernel's
+    // tail, as the step kernel's
     for (long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) a0 = fma((double)g[t], (double)g[t], a0);
     const double s = block_sum_d((a0 + a1) + (a2 + a3), part);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
-// adam_kernel behind the rule above.  Every workgroup sums the kSqnormParts partials itself, in the SAME order (lane-strided reads, the
-// same tree), so that all of them derive norm, c, scale and the decision bit for bit alike; `report`: eight host-mapped words.
-__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, long n, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2,
-                                 float eps, float gscale, float max_norm, const double* __restrict__ partials,
-                                 const unsigned* __restrict__ abort_word, const float* __restrict__ step_flag,
-                                 unsigned* __restrict__ report) {
-    __shared__ double part[4];
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < kSqnormParts / kSqnormBlock; ++k) acc += partials[threadIdx.x + k * kSqnormBlock];
-    const double S = block_sum_d(acc, part);
-    const double norm = fabs((double)gscale) * sqrt(S);
-    const bool skip = step_flag ? (*step_flag != 0.f)
-                                : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
-    const bool nonfinite = !skip && !(fabs(norm) <= 1.7976931348623157e308);          // NaN or +inf
-    const double c = (double)max_norm / (norm + 1e-6);
-    const bool clipped = !skip && !nonfinite && c < 1.0;
-    if (report && blockIdx.x == 0 && threadIdx.x == 0) {
-        __hip_atomic_store(report + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (skip) __hip_atomic_store(report + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (step_flag && step_flag[1] != 0.f) __hip_atomic_store(report + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (clipped) __hip_atomic_store(report + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (nonfinite) __hip_atomic_store(report + 5, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(report + 6, __float_as_uint((float)norm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (skip || nonfinite) return;
-    const float scale = clipped ? (float)c : 1.0f;
-    const bool bad = adam_update(p, g, m, v, n, lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, gscale * scale,
-                                 (long)blockIdx.x * blockDim.x + threadIdx.x, (long)gridDim.x * blockDim.x);
-    if (bad && report) __hip_atomic_store(report + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// ---- decoupled weight decay and EMA shadow weights inside the step.  The rule, for one optimizer step with
-// weight_decay >= 0, a nullable decay mask (bit i & 31 of word i >> 5 set: element i decays; null: every element decays), a nullable
-// arena ema[0..n) and ema_decay in [0, 1):
-//   1. skip and scale are today's: with partials steps 1-6 of the rule above (norm, clip coefficient, non-finite drop, flag
-//      precedence), without partials adam_kernel's -- only the chain / step flag skips.
-//   2. a skipped or dropped step leaves p, m, v AND ema bit for bit untouched.
-//   3. an applied step: the launcher computes decay = (float)(1.0 - (double)lr * (double)weight_decay) and
-//      omd = (float)(1.0 - (double)ema_decay) once; per element m, v as adam_kernel, p1 = decays(i) ? p * decay : p (one rounding),
-//      p_new = p1 - lr_over_bc1 * (m / denom) as adam_kernel (torch's _single_tensor_adamw order: param.mul_(1 - lr * wd) first);
-//      report[2] tests p_new.
-//   4. ema given: e_new = fmaf(ema_decay, e, omd * p_new) (the product rounded on its own); ema_decay == 0 gives e_new == p_new.
-//   5. weight_decay == 0 gives decay == 1.0f exactly: with ema null p, m, v and the report are bit-identical to adam_clip_kernel
-//      (with partials) or adam_kernel (without).
-// report: EIGHT words; [4..6] are adam_clip_kernel's with partials and stay 0 without, [7] stays 0.
-// Rule 5 is a statement about roundings, so this kernel leaves none of them to the compiler: contraction is OFF in its body and every
-// fused operation is written out, in the forms adam_kernel and adam_clip_kernel are compiled to (-ffp-contract=fast picks them per
-// expression and per loop; tools/kernel_resources.py --asm shows them): body and tail m = fma(1 - b1, gr, b1 * m),
-// denom = fma(sqrt(v), inv_sqrt_bc2, eps), p = fma(-lr_over_bc1, m / denom, p1); v = fma(b2, v, gr * ((1 - b2) * gr)) in the body but
-// b2 * v + gr * ((1 - b2) * gr), both products rounded, in the tail.  p * decay is never fused into what follows: p * 1.0f - x as one
-// fma would round once where adam_kernel rounds twice.  tests/test_gpu_adamw_ema.py holds the identity at every size class.
-// adam_kernel's grid, 16-byte body and scalar tail with its own copy of the body (adam_kernel and adam_clip_kernel keep theirs as it
-// was compiled); EMA / MASK: whether `ema` / `mask` are given -- compile-time, so that the plain form carries neither loads nor
+// ---- the optimizer step: torch.optim.Adam / AdamW (2.x single-tensor form) over the flat arena, optionally
+// behind global-norm clipping, with decoupled weight decay and with EMA shadow weights.  One kernel; the rule, stated once.
+//
+// Skip and report.  A chain kernel gave up waiting for its group (chain.h): the gradients of the step are not valid, so the step leaves
+// every arena as it is.  Which word decides: `step_flag` when the caller passes one -- the flags of ALL ranks summed with the gradients
+// (inet_step_flag_export + the all-reduce), so that every rank of a data-parallel job takes the same decision --, else this process's own
+// device word.  `report` (nullable; host-mapped words the caller owns and zeroed) tells the host what was decided (encoder.py:111-116,
+// decoder.py:424-429): [0] = 1 the kernel ran, [1] = 1 the flag skipped the step, [2] = 1 a parameter left the finite range, [3] = 1
+// SOME rank's prologue kernels met a token outside the vocabulary (step_flag[1] = the ranks' exported token words: every rank raises the
+// reference's check_index ValueError at the same step).  WITHOUT partials only these four words are ever stored to: a record of four
+// words is enough.  With partials the record has eight: [4] = 1 clipped, [5] = 1 dropped for a non-finite gradient, [6] = the bits of
+// (float)norm (also on a skip), [7] stays 0.
+//
+// Clipping (partials given: what grad_sqnorm_kernel left for the gradient arena g[0..n); 0 < max_norm <= +inf; section 18):
+//   1. S = sum (double)g_i * (double)g_i: every square exact in f64, the sum in f64 in a FIXED order that depends on n only.  Every
+//      workgroup sums the kSqnormParts partials itself, in the SAME order (lane-strided reads, the same tree), so that all of them derive
+//      norm, c, scale and the decision bit for bit alike.  norm = |gscale| * sqrt(S) in f64.
+//   2. nonfinite = !isfinite(norm)  (a finite f32 arena cannot overflow the f64 sum: true iff some element is inf or NaN).
+//   3. c = max_norm / (norm + 1e-6) in f64 (torch's clip_grad_norm_ coefficient); scale = c < 1 ? (float)c : 1.0f;
+//      clipped = c < 1.  max_norm = +inf never clips.
+//   4. the chain / step flag says skip: the step is skipped, nonfinite and clipped are reported as 0.
+//   5. else nonfinite: every arena stays untouched, report[5] = 1, report[1] and report[2] stay 0 (not a chain failure).
+//   6. else the step below with gs = the ONE f32 product gscale * scale.
+// Without partials gs = gscale, max_norm is ignored and only the flag skips.
+//
+// Decay and EMA (section 19).  weight_decay >= 0; a nullable decay mask (bit i & 31 of word i >> 5 set: element i decays; null: every
+// element decays); a nullable arena ema[0..n) and ema_decay in [0, 1).  The launcher rounds the factors ONCE, on the host:
+// lr_over_bc1 = (float)(lr / (1 - b1^step)), inv_sqrt_bc2 = (float)(1 / sqrt(1 - b2^step)), decay = (float)(1.0 - (double)lr *
+// (double)weight_decay) -- exactly 1.0f for weight_decay == 0 --, omd = (float)(1.0 - (double)ema_decay).  A skipped or dropped step
+// leaves p, m, v AND ema bit for bit untouched.
+//
+// The applied step, per element, every operation in f32 and every rounding spelled out -- contraction is OFF in the kernel and each fused
+// operation is written as an fmaf, so the bits do not depend on what a compiler would contract (tests/test_gpu_adam_bits.py holds them to
+// a recording):
+//   gr    = g * gs
+//   m     = fmaf(1 - b1, gr, b1 * m)
+//   v     = fmaf(b2, v, gr * ((1 - b2) * gr))        in the 16-byte body;
+//           b2 * v + gr * ((1 - b2) * gr)            in the scalar tail: BOTH products rounded, then the sum.  An oddity, and part of the
+//                                                    recorded bits: the last n & 3 elements round v once more than the rest
+//   denom = fmaf(sqrtf(v), inv_sqrt_bc2, eps)        (torch: sqrt(v) / sqrt(bc2) + eps)
+//   p1    = decays(i) ? p * decay : p                (torch's _single_tensor_adamw order, param.mul_(1 - lr * wd) first; the product is
+//                                                    rounded on its own, never fused into what follows: p * 1.0f is p)
+//   p     = fmaf(-lr_over_bc1, m / denom, p1);       report[2] tests this p
+//   ema   = fmaf(ema_decay, ema, omd * p)            (ema given; the product rounded on its own: ema_decay == 0 gives ema == p)
+//
+// The grid is grid_for(n / 4 + 1, 256, 4096) workgroups of kSqnormBlock threads, grid-stride over 16-byte groups, then the n & 3 elements
+// of the tail.  EMA / MASK: whether `ema` / `mask` are given -- compile-time, so that the plain form carries neither loads nor
 // registers of the other three.  Four consecutive elements never straddle a mask word: the body reads ONE word per 16 bytes.
 template <bool EMA, bool MASK>
 __global__ void __launch_bounds__(kSqnormBlock)
@@ -391,7 +312,7 @@ adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restri
                                 : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
     bool nonfinite = false, clipped = false;
     double norm = 0.0, c = 1.0;
-    if (partials) {                                  // uniform over the grid: adam_clip_kernel's prologue and decisions, word for word
+    if (partials) {                                  // uniform over the grid: steps 1-3 of the clip rule
         double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < kSqnormParts / kSqnormBlock; ++k) acc += partials[threadIdx.x + k * kSqnormBlock];
@@ -1158,53 +1079,31 @@ int pw_latent_bwd(const float* dz, const float* mu, const float* ls, const float
                        dls, n);
     return ok();
 }
-int pw_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
-            float gscale, hipStream_t s, const float* step_flag, unsigned* report) {
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    ProfScope prof(PROF_HBM, 0.0, s, "adam", 28.0 * (double)n);      // read p,g,m,v; write p,m,v
-    hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(256), 0, s, p, g, m, v, n,
-                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, gscale,
-                       (const unsigned*)chain_dev_status(), step_flag, report);
-    return ok();
-}
 int pw_sqnorm_parts() { return kSqnormParts; }
 int pw_grad_sqnorm(const float* g, long n, double* partials, hipStream_t s) {
     ProfScope prof(PROF_HBM, 0.0, s, "grad_sqnorm", 4.0 * (double)n);         // one read of the arena
     hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(kSqnormParts), dim3(kSqnormBlock), 0, s, g, n, partials);
     return ok();
 }
-int pw_adam_clip(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
-                 float gscale, float max_norm, const double* partials, hipStream_t s, const float* step_flag, unsigned* report) {
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    ProfScope prof(PROF_HBM, 0.0, s, "adam_clip", 28.0 * (double)n + 8.0 * kSqnormParts);      // adam's traffic + the partials
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(kSqnormBlock), 0, s, p, g, m, v, n,
-                       (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), b1, b2, eps, gscale, max_norm, partials,
-                       (const unsigned*)chain_dev_status(), step_flag, report);
-    return ok();
-}
 template <bool EMA, bool MASK>
-static void launch_adamw(hipStream_t s, float* p, const float* g, float* m, float* v, long n, float lr_over_bc1, float inv_sqrt_bc2,
-                         float b1, float b2, float eps, float gscale, float max_norm, const double* partials, float decay,
-                         const unsigned* mask, float* ema, float ema_decay, float omd, const float* step_flag, unsigned* report) {
-    hipLaunchKernelGGL((adamw_kernel<EMA, MASK>), dim3(grid_for(n / 4 + 1, 256, 4096)), dim3(kSqnormBlock), 0, s, p, g, m, v, n,
-                       lr_over_bc1, inv_sqrt_bc2, b1, b2, eps, gscale, max_norm, partials, decay, mask, ema, ema_decay, omd,
-                       (const unsigned*)chain_dev_status(), step_flag, report);
+static void launch_adam_step(const PwAdamStep& a, float lr_over_bc1, float inv_sqrt_bc2, float decay, float omd, hipStream_t s) {
+    hipLaunchKernelGGL((adamw_kernel<EMA, MASK>), dim3(grid_for(a.n / 4 + 1, 256, 4096)), dim3(kSqnormBlock), 0, s, a.p, a.g, a.m, a.v,
+                       a.n, lr_over_bc1, inv_sqrt_bc2, a.b1, a.b2, a.eps, a.gscale, a.max_norm, a.partials, decay, a.mask, a.ema,
+                       a.ema_decay, omd, (const unsigned*)chain_dev_status(), a.step_flag, a.report);
 }
-int pw_adamw(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step, float gscale,
-             float max_norm, const double* partials, float weight_decay, const unsigned* mask, float* ema, float ema_decay,
-             hipStream_t s, const float* step_flag, unsigned* report) {
-    const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
-    // the two factors of the rule, rounded ONCE here: what the kernel multiplies by does not depend on how it was compiled
-    const float decay = (float)(1.0 - (double)lr * (double)weight_decay), omd = (float)(1.0 - (double)ema_decay);
-    // adam's traffic + a bit per element of the mask + one read and one write of the EMA arena + the partials
-    ProfScope prof(PROF_HBM, 0.0, s, partials ? "adamw_clip" : "adamw",
-                   28.0 * (double)n + (mask ? (double)n / 8.0 : 0.0) + (ema ? 8.0 * (double)n : 0.0) + (partials ? 8.0 * kSqnormParts : 0.0));
-    const float l1 = (float)(lr / bc1), is2 = (float)(1.0 / sqrt(bc2));
-#define ADAMW_LAUNCH(E, M) launch_adamw<E, M>(s, p, g, m, v, n, l1, is2, b1, b2, eps, gscale, max_norm, partials, decay, mask, ema, \
-                                            ema_decay, omd, step_flag, report)
-    if (ema) { if (mask) ADAMW_LAUNCH(true, true); else ADAMW_LAUNCH(true, false); }
-    else     { if (mask) ADAMW_LAUNCH(false, true); else ADAMW_LAUNCH(false, false); }
-#undef ADAMW_LAUNCH
+int pw_adam_step(const PwAdamStep& a, hipStream_t s) {
+    const double bc1 = 1.0 - pow((double)a.b1, a.step), bc2 = 1.0 - pow((double)a.b2, a.step);
+    // the factors of the rule, rounded ONCE here: what the kernel multiplies by does not depend on how it was compiled
+    const float l1 = (float)(a.lr / bc1), is2 = (float)(1.0 / sqrt(bc2));
+    const float decay = (float)(1.0 - (double)a.lr * (double)a.weight_decay), omd = (float)(1.0 - (double)a.ema_decay);
+    // the label says what the launch does: "w" with decay or an EMA, "_clip" behind the partials
+    const bool w = a.weight_decay > 0.f || a.ema;
+    // read p,g,m,v; write p,m,v + a bit per element of the mask + one read and one write of the EMA arena + the partials
+    ProfScope prof(PROF_HBM, 0.0, s, w ? (a.partials ? "adamw_clip" : "adamw") : (a.partials ? "adam_clip" : "adam"),
+                   28.0 * (double)a.n + (a.mask ? (double)a.n / 8.0 : 0.0) + (a.ema ? 8.0 * (double)a.n : 0.0) +
+                       (a.partials ? 8.0 * kSqnormParts : 0.0));
+    if (a.ema) { if (a.mask) launch_adam_step<true, true>(a, l1, is2, decay, omd, s); else launch_adam_step<true, false>(a, l1, is2, decay, omd, s); }
+    else       { if (a.mask) launch_adam_step<false, true>(a, l1, is2, decay, omd, s); else launch_adam_step<false, false>(a, l1, is2, decay, omd, s); }
     return ok();
 }
 int pw_step_flag_export(float* dst, hipStream_t s) {
@@ -1218,7 +1117,7 @@ int pw_step_flag_export(float* dst, hipStream_t s) {
 __global__ void epoch_stats_add_kernel(float* sums, const float* loss, const float* acc, const unsigned* abort_word,
                                        const float* step_flag) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    // the same decision as the optimizer kernel of the step (adam_kernel): the ranks' summed flag if the caller has one
+    // the same decision as the optimizer kernel of the step (adamw_kernel): the ranks' summed flag if the caller has one
     if (step_flag ? (*step_flag != 0.f)
                   : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) return;
     sums[0] += loss[0];

@@ -490,19 +490,30 @@ def latent_bwd(dz, mu, ls, eps, kscale, kscale_dev=None):
     return dmu, dls
 
 
+def _adam_arenas(p, g, m, v, partials, report):
+    """What every optimizer entry point asks of its tensors: four float32 arenas of one size; `partials` (where given) what
+    grad_sqnorm left; `report` (where given) pinned int32 words, four of them, eight with partials.  Returns the size."""
+    n = p.numel()
+    for t in (p, g, m, v):
+        assert _f32c(t).numel() == n
+    if partials is not None:
+        assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= sqnorm_parts()
+    if report is not None:
+        assert report.dtype == torch.int32 and report.numel() >= (4 if partials is None else 8) and report.is_pinned() \
+            and report.is_contiguous()
+    return n
+
+
 def adam_step(p, g, m, v, lr, step, b1=0.9, b2=0.999, eps=1e-8, gscale=1.0, step_flag=None, report=None):
     """report: 4 int32 words of PINNED host memory, zeroed by the caller; the kernel sets [0] executed, [1] skipped, [2] a
     parameter became non-finite.  step_flag: 1-element device tensor that alone decides whether the step is applied (the ranks'
     summed chain status, include/inpaintnet_hip.h inet_adam_step_ex)."""
-    for t in (p, g, m, v):
-        _f32c(t)
+    n = _adam_arenas(p, g, m, v, None, report)
     if report is None and step_flag is None:
-        check(_lib.lib().inet_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(b1), float(b2),
+        check(_lib.lib().inet_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), n, float(lr), float(b1), float(b2),
                                         float(eps), int(step), float(gscale), stream_ptr()), "inet_adam_step")
     else:
-        if report is not None:
-            assert report.dtype == torch.int32 and report.numel() >= 4 and report.is_pinned() and report.is_contiguous()
-        check(_lib.lib().inet_adam_step_ex(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(b1), float(b2),
+        check(_lib.lib().inet_adam_step_ex(ptr(p), ptr(g), ptr(m), ptr(v), n, float(lr), float(b1), float(b2),
                                            float(eps), int(step), float(gscale), ptr(step_flag), ptr(report), stream_ptr()),
               "inet_adam_step_ex")
 
@@ -528,12 +539,9 @@ def adam_step_clip(p, g, m, v, lr, step, max_norm, partials, b1=0.9, b2=0.999, e
     """adam_step behind global-norm clipping and the non-finite skip (include/inpaintnet_hip.h inet_adam_step_clip states the rule):
     `partials` is what grad_sqnorm(g) left, max_norm in (0, inf].  report: EIGHT int32 words of PINNED host memory, zeroed by the
     caller: [0..3] as adam_step's, [4] clipped, [5] skipped for an inf / NaN gradient, [6] the bits of float32(norm), [7] 0."""
-    for t in (p, g, m, v):
-        _f32c(t)
-    assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= sqnorm_parts()
-    if report is not None:
-        assert report.dtype == torch.int32 and report.numel() >= 8 and report.is_pinned() and report.is_contiguous()
-    check(_lib.lib().inet_adam_step_clip(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), float(lr), float(b1), float(b2), float(eps),
+    assert partials is not None
+    n = _adam_arenas(p, g, m, v, partials, report)
+    check(_lib.lib().inet_adam_step_clip(ptr(p), ptr(g), ptr(m), ptr(v), n, float(lr), float(b1), float(b2), float(eps),
                                          int(step), float(gscale), float(max_norm), ptr(partials), ptr(step_flag), ptr(report),
                                          stream_ptr()), "inet_adam_step_clip")
 
@@ -558,22 +566,15 @@ def adamw_step(p, g, m, v, lr, step, weight_decay=0.0, decay_mask=None, ema=None
     decay and an exponential moving average of the weights in the same launch (include/inpaintnet_hip.h inet_adam_step_w states the
     rule): p is scaled by float32(1 - lr * weight_decay) in front of the update where decay_mask (pack_decay_mask; None: everywhere)
     says so, and ema (None: none) becomes ema_decay * ema + float32(1 - ema_decay) * p behind it.  A skipped or dropped step leaves
-    ema alone as well.  report: EIGHT int32 words of PINNED host memory, zeroed by the caller: [0..3] as adam_step's, [4..6] as
-    adam_step_clip's with partials and 0 without, [7] 0."""
-    for t in (p, g, m, v):
-        _f32c(t)
-    n = p.numel()
-    assert g.numel() == n and m.numel() == n and v.numel() == n
+    ema alone as well.  report: int32 words of PINNED host memory, zeroed by the caller: [0..3] as adam_step's; with partials EIGHT
+    words, [4..6] as adam_step_clip's and [7] 0; without partials four are enough and words beyond them are left alone."""
+    n = _adam_arenas(p, g, m, v, partials, report)
     if ema is not None:
         assert _f32c(ema).numel() == n
     if decay_mask is not None:
         assert decay_mask.is_cuda and decay_mask.dtype == torch.int32 and decay_mask.is_contiguous() \
             and decay_mask.numel() >= (n + 31) // 32
-    if partials is not None:
-        assert partials.is_cuda and partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= sqnorm_parts()
-        assert max_norm is not None, "partials without max_norm"
-    if report is not None:
-        assert report.dtype == torch.int32 and report.numel() >= 8 and report.is_pinned() and report.is_contiguous()
+    assert partials is None or max_norm is not None, "partials without max_norm"
     check(_lib.lib().inet_adam_step_w(ptr(p), ptr(g), ptr(m), ptr(v), n, float(lr), float(b1), float(b2), float(eps), int(step),
                                       float(gscale), 0.0 if max_norm is None else float(max_norm), ptr(partials),
                                       float(weight_decay), ptr(decay_mask), ptr(ema), float(ema_decay), ptr(step_flag),

@@ -147,9 +147,9 @@ class Trainer(ABC):
                  ema_decay=None, ema_warmup=False):
         """max_grad_norm (None or 0 < value <= inf): clip the gradient arena by its global norm in front of every optimizer step, as
         torch.nn.utils.clip_grad_norm_(..., error_if_nonfinite=False) around optimizer.step() would, and DROP a step whose gradient
-        holds an inf or a NaN instead of folding it into the weights -- both on the device (ops.grad_sqnorm +
-        ops.adam_step_clip in the place of ops.adam_step; inf = measure and drop only, never clip).  The step reports, read at the
-        usual lag (check_steps), keep last_grad_norm, clipped_steps and nonfinite_steps up to date.  None: nothing changes.
+        holds an inf or a NaN instead of folding it into the weights -- both on the device (ops.grad_sqnorm in
+        front of the optimizer launch, which takes its partial sums; inf = measure and drop only, never clip).  The step reports,
+        read at the usual lag (check_steps), keep last_grad_norm, clipped_steps and nonfinite_steps up to date.  None: nothing changes.
 
         weight_decay (>= 0, finite): decoupled weight decay as torch.optim.AdamW applies it, p *= 1 - lr * weight_decay in front of
         every update, inside the optimizer launch (ops.adamw_step).  The weight matrices decay -- the entries
@@ -203,7 +203,7 @@ class Trainer(ABC):
         self.lost_steps = 0                          # optimizer steps the device skipped (their batches were run again)
         # deferred side-stream joins for zero_grad() -> forward -> backward -> step() sequences (see zero_grad)
         self.overlap_backward = False
-        # Step reports (inet_adam_step_ex): every optimizer launch leaves a record of what it decided; the host reads the
+        # Step reports (inet_adam_step_w): every optimizer launch leaves a record of what it decided; the host reads the
         # record of step k when it has queued step k + report_lag -- by then that kernel has normally run, so the read costs
         # nothing, and it happens at the SAME step on every rank of a data-parallel job (the decision itself is the ranks'
         # summed flag), so all ranks fall back and repeat the same batches together.
@@ -409,16 +409,10 @@ class Trainer(ABC):
             self._launch_optimizer(tag, gscale, flag)
             self._inflight.append(tag)
             self.check_steps()
-        elif self._adamw_on():                       # (no reports: host arenas never get here, a device trainer always reports)
-            ops.adamw_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, **self._adamw_args(gscale, clip=False))
-        else:
-            ops.adam_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.betas[0], self.betas[1],
-                          self.eps, gscale)
+        else:                                        # (no reports: host arenas never get here, a device trainer always reports)
+            ops.adamw_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, **self._adamw_args(gscale))
 
     # ---- decoupled weight decay and the EMA shadow weights ----
-    def _adamw_on(self):
-        return self.weight_decay > 0.0 or self.ema_decay is not None
-
     def _build_decay_mask(self):
         """The elements that decay by default: the weight matrices, by the criterion Model.init_reference_style uses."""
         ranges = [(off, off + shape[0] * shape[1]) for name, off, shape in self.model._table if "weight" in name and len(shape) == 2]
@@ -432,14 +426,15 @@ class Trainer(ABC):
             return min(self.ema_decay, (1.0 + t) / (10.0 + t))
         return self.ema_decay
 
-    def _adamw_args(self, gscale, clip=True):
-        """What ops.adamw_step takes beyond the arenas, lr and the step number.  The partials only with max_grad_norm (and only
-        where grad_sqnorm ran in front: clip=False is the report-less branch of step(), which does not measure)."""
-        on = clip and self.max_grad_norm is not None
+    def _adamw_args(self, gscale, step_flag=None, report=None):
+        """What ops.adamw_step takes beyond the arenas, lr and the step number: the one optimizer launch of the trainer, whatever is
+        switched on.  The partials only with max_grad_norm and a report, which is where grad_sqnorm ran in front (_launch_optimizer;
+        the report-less branch of step() does not measure)."""
+        on = report is not None and self.max_grad_norm is not None
         return dict(weight_decay=self.weight_decay, decay_mask=self._decay_mask, ema=self.ema,
                     ema_decay=0.0 if self.ema is None else self.ema_decay_at(self.adam_t),
                     max_norm=self.max_grad_norm if on else None, partials=self._sqnorm if on else None,
-                    b1=self.betas[0], b2=self.betas[1], eps=self.eps, gscale=gscale)
+                    b1=self.betas[0], b2=self.betas[1], eps=self.eps, gscale=gscale, step_flag=step_flag, report=report)
 
     def ema_state_dict(self):
         """The EMA weights under the keys and shapes of model.state_dict(): load them into a model to evaluate or sample from it."""
@@ -483,23 +478,14 @@ class Trainer(ABC):
         m = self.model
         rec = self._report_slot(tag)
         rec.zero_()                                  # host write: the launch that last wrote this record was waited for when it was read
-        if self._adamw_on():
-            # decay and EMA are element-wise functions of values that are bit-identical on every rank behind the exchange: the
-            # replicas and their EMA arenas stay bit-identical with nothing to coordinate
-            if self.max_grad_norm is not None:
-                self._sqnorm = ops.grad_sqnorm(m.grad, self._sqnorm)
-            ops.adamw_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, step_flag=flag, report=rec,
-                           **self._adamw_args(gscale))
-        elif self.max_grad_norm is None:
-            ops.adam_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.betas[0], self.betas[1],
-                          self.eps, gscale, step_flag=flag, report=rec)
-        else:
+        if self.max_grad_norm is not None:
             # m.grad is the arena alone (the 16-byte head of its store holds the ranks' flags, not gradients); both launches sit
             # behind the gradient exchange, so every rank measures the same all-reduced arena in the same fixed order and all
             # ranks clip and drop together: no collective of their own
             self._sqnorm = ops.grad_sqnorm(m.grad, self._sqnorm)
-            ops.adam_step_clip(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, self.max_grad_norm, self._sqnorm,
-                               self.betas[0], self.betas[1], self.eps, gscale, step_flag=flag, report=rec)
+        # decay and EMA are element-wise functions of values that are bit-identical on every rank behind the exchange: the
+        # replicas and their EMA arenas stay bit-identical with nothing to coordinate
+        ops.adamw_step(m.flat, m.grad, self.adam_m, self.adam_v, self.lr, self.adam_t, **self._adamw_args(gscale, flag, rec))
         self._report_events[tag % self._NREP].record()
 
     def _device_sync(self):
@@ -515,9 +501,8 @@ class Trainer(ABC):
 
     def _report_slot(self, tag):
         if self._reports is None:
-            # four words per record (inet_adam_step_ex), eight with clipping (inet_adam_step_clip) or decay / EMA (inet_adam_step_w)
-            words = 4 if self.max_grad_norm is None and not self._adamw_on() else 8
-            self._reports = torch.zeros(self._NREP, words, dtype=torch.int32).pin_memory()
+            # eight words per record, whatever is switched on now or by a later load_training_state (inet_adam_step_w)
+            self._reports = torch.zeros(self._NREP, 8, dtype=torch.int32).pin_memory()
             self._report_events = [torch.cuda.Event() for _ in range(self._NREP)]
         return self._reports[tag % self._NREP]
 
@@ -650,6 +635,10 @@ class Trainer(ABC):
             else path_or_state
         if int(st["num_parameters"]) != self.model.flat.numel():
             raise RuntimeError("training state belongs to a model with a different parameter arena")
+        if self._inflight:
+            # before adam_t is overwritten: a report read afterwards would take ITS dropped step off the loaded step count
+            # (waits for those launches and raises what they report)
+            self.check_steps(wait_all=True)
         self.adam_m.copy_(st["adam_m"])
         self.adam_v.copy_(st["adam_v"])
         self.adam_t = int(st["adam_t"])
@@ -669,11 +658,6 @@ class Trainer(ABC):
             # a state written before weight decay and EMA existed: the settings stay this trainer's, the EMA starts at the weights
             self.ema.copy_(self.model.flat)
             print("[inpaintnet_amd] training state without an EMA: the EMA arena was seeded from the model's weights as loaded")
-        if self._reports is not None and self._reports.shape[1] < 8 and self._adamw_on():
-            # the loaded settings need eight-word records: read what the four-word ones still hold (waits for those launches and
-            # raises what they report), then replace the ring -- its events stay, none is pending any more
-            self.check_steps(wait_all=True)
-            self._reports = torch.zeros(self._NREP, 8, dtype=torch.int32).pin_memory()
         return self.start_epoch
 
     @abstractmethod

@@ -1,6 +1,7 @@
 """Decoupled weight decay and EMA shadow weights inside the optimizer step: adamw_kernel alone through
 ops.adamw_step / inet_adam_step_w, then through Trainer(weight_decay=, ema_decay=).  The reference is the float64 restatement of the
-rule, tests/adamw_ref.py; without decay and EMA the step must EQUAL ops.adam_step / ops.adam_step_clip bit for bit.
+rule, tests/adamw_ref.py; without decay and EMA the step must EQUAL ops.adam_step / ops.adam_step_clip bit for bit -- three entry points
+of one kernel: what holds the arithmetic itself in place is tests/test_gpu_adam_bits.py, against recorded bits.
 
 Sizes: tail only (1, 3, 4, 5), around a mask word's edge (31 .. 65), the 16-byte body plus a tail of 0..3, and one size past a full
 pass of the grid (its grid-stride loop runs twice, with a ragged end and a tail)."""
@@ -79,6 +80,8 @@ def assert_within(got, ref, bound, what):
 
 
 # =============================================================================== 1. no decay, no EMA, no partials: adam_step
+# (sections 1 and 2 are entry-point checks: both calls reach one kernel, so they hold the argument plumbing and the reports; that the
+# arithmetic is what it was is tests/test_gpu_adam_bits.py's to prove, against the recorded fixture)
 @pytest.mark.parametrize("gscale", [1.0, 0.125])
 def test_plain_form_is_bit_identical_to_adam_step(gscale):
     for n in ALL_N:
@@ -427,7 +430,7 @@ def test_trainer_follows_the_restatement_over_three_steps():
 
 def test_trainer_biases_do_not_decay_and_the_default_trainer_launches_what_it_launched():
     """The same three gradients through a trainer built with the defaults: its biases (and b_0 / x_0) EQUAL the decaying run's bit
-    for bit, its weight matrices do not; its launches carry today's labels and its reports four words."""
+    for bit, its weight matrices do not; its launches carry today's labels (its records have eight words like everybody's)."""
     from tests.test_gpu_decode_plans import labels_of
     model_w, trainer_w, tok, start, grads, _ = trained()
     model, trainer, _ = _vae()
@@ -441,7 +444,7 @@ def test_trainer_biases_do_not_decay_and_the_default_trainer_launches_what_it_la
             trainer.step()
     trainer.finish()
     assert labels.count("adam") == 1 and "adamw" not in labels and "grad_sqnorm" not in labels
-    assert trainer._reports.shape == (trainer._NREP, 4)
+    assert trainer._reports.shape == (trainer._NREP, 8)
     decayed = 0
     for name, t in model.state_dict().items():
         same = same_bits(t, model_w.state_dict()[name])
@@ -551,9 +554,9 @@ def test_training_state_round_trip(capsys):
     assert st["weight_decay"] == 0.01 and st["decay_all"] is False and st["ema_decay"] == 0.9 and st["ema_warmup"] is False
     assert not st["ema"].is_cuda and same_bits(st["ema"], trainer.ema)
     model2, trainer2, _ = _vae()
-    _backward(trainer2, tok)                                                    # a four-word record is in flight when the state arrives:
-    trainer2.step()                                                             # loading drains it and replaces the ring
-    assert trainer2._reports.shape[1] == 4 and len(trainer2._inflight) == 1
+    _backward(trainer2, tok)                                                    # a record is in flight when the state arrives:
+    trainer2.step()                                                             # loading drains it before it touches adam_t
+    assert trainer2._reports.shape[1] == 8 and len(trainer2._inflight) == 1
     trainer2.load_training_state(st)
     assert not trainer2._inflight and trainer2._reports.shape[1] == 8
     assert (trainer2.weight_decay, trainer2.decay_all, trainer2.ema_decay, trainer2.ema_warmup) == (0.01, False, 0.9, False)

@@ -1,6 +1,7 @@
-"""Global-norm clipping and the non-finite skip of the optimizer step: grad_sqnorm_kernel and adam_clip_kernel
+"""Global-norm clipping and the non-finite skip of the optimizer step: grad_sqnorm_kernel and the step kernel
 alone through ops.grad_sqnorm / ops.adam_step_clip, then through Trainer(max_grad_norm=...).  The reference is the float64
-restatement of the rule, tests/clip_ref.py; the unclipped step must EQUAL ops.adam_step bit for bit.
+restatement of the rule, tests/clip_ref.py; the unclipped step must EQUAL ops.adam_step bit for bit -- two entry points of one kernel:
+what holds the arithmetic itself in place is tests/test_gpu_adam_bits.py, against recorded bits.
 
 Sizes: the optimizer tests' own (tail only, body + tail of 0..3), one just above one full pass of the norm kernel's grid (its
 grid-stride loop runs twice, with a ragged end), one at which every workgroup of the Adam grid has work and the norm kernel's
@@ -122,6 +123,8 @@ def test_clip_entry_points_refuse_bad_arguments():
 
 
 # =============================================================================== 2. not clipped: bit-identical to inet_adam_step_ex
+# (an entry-point check: both calls reach one kernel, so this holds scale == 1.0f and the argument plumbing; that the arithmetic is
+# what it was is tests/test_gpu_adam_bits.py's to prove, against the recorded fixture)
 @pytest.mark.parametrize("gscale", [1.0, 0.125])
 @pytest.mark.parametrize("how", ["ten_times", "inf"])
 def test_unclipped_step_is_bit_identical_to_adam_step(how, gscale):
@@ -300,7 +303,7 @@ def test_trainer_without_max_grad_norm_launches_what_it_launched():
     _, labels = labels_of(lambda: _one_step(trainer, tok))
     trainer.finish()
     assert "adam" in labels and "grad_sqnorm" not in labels and "adam_clip" not in labels
-    assert trainer._reports.shape == (trainer._NREP, 4)
+    assert trainer._reports.shape == (trainer._NREP, 8)
     assert trainer.last_grad_norm is None and trainer.clipped_steps == 0 and trainer.nonfinite_steps == 0
 
 

@@ -18,7 +18,8 @@ def short(n):
 def main(path, which=5, gap_us=12.0, full=False):
     rows = list(csv.DictReader(open(path)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    adam = [i for i, r in enumerate(rows) if "adam_kernel" in r["Kernel_Name"]]
+    # the optimizer launch ends a step ("adam_kernel": traces recorded before the step kernels were folded into adamw_kernel)
+    adam = [i for i, r in enumerate(rows) if "adamw_kernel" in r["Kernel_Name"] or "adam_kernel" in r["Kernel_Name"]]
     i0, i1 = adam[which] + 1, adam[which + 1] + 1
     step = rows[i0:i1]
     T0 = int(step[0]["Start_Timestamp"])
