@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import layout, ops
+from .draw import GENERATE, Draw
 from .helpers import to_cuda_variable_long
 from .latent_rnn_trainer import LatentRNNTrainer
 from .measure_vae import _DropState, _next_mask_offset
@@ -428,30 +429,9 @@ class ConstraintModelGaussianReg(Model):
         token.  ValueError for a wrong shape or dtype or a value outside [-1, V), before np.random is touched.  A forced call always
         leaves last_logp.  uniforms (float64 (B, L)): used instead of the np.random.random_sample((B, L)) draw, and np.random is not
         touched; None: the stream is consumed exactly as before.  A call without the two runs the kernels it always ran."""
-        k = ops._top_k(top_k)
-        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
-            raise ValueError(f"generate: top_p {top_p!r} outside (0, 1]")
-        if allowed is not None:
-            allowed = torch.as_tensor(allowed)
-            want = tuple(tensor_score.shape[:1] + tensor_score.shape[2:] if tensor_score.dim() == 3 else tensor_score.shape[1:])
-            if allowed.dtype != torch.bool or allowed.dim() != len(want) + 1 or tuple(allowed.shape[:-1]) != want or \
-                    allowed.size(-1) != self.num_notes_per_voice[0]:
-                raise ValueError(f"generate: allowed must be bool of shape {want + (self.num_notes_per_voice[0],)}, got {allowed.dtype} "
-                                 f"{tuple(allowed.shape)}")
-            allowed = ops.pack_allowed(allowed)                    # (ValueError for a tick with nothing allowed)
-        rows = tensor_score.shape[0] if tensor_score.dim() == 3 else 1
-        if forced is not None:
-            forced = torch.as_tensor(forced)
-            want = (rows, tensor_score.shape[-1]) if tensor_score.dim() == 3 else (tensor_score.shape[-1],)
-            if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool or tuple(forced.shape) != want:
-                raise ValueError(f"generate: forced must be an int tensor of shape {want}, got {forced.dtype} {tuple(forced.shape)}")
-            if bool(((forced < -1) | (forced >= self.num_notes_per_voice[0])).any()):
-                raise ValueError(f"generate: forced holds a value outside [-1, {self.num_notes_per_voice[0]})")
-        if uniforms is not None:
-            uniforms = np.asarray(uniforms)
-            if uniforms.dtype != np.float64 or uniforms.shape != (rows, tensor_score.shape[-1]):
-                raise ValueError(f"generate: uniforms must be float64 of shape {(rows, tensor_score.shape[-1])}, got {uniforms.dtype} "
-                                 f"{uniforms.shape}")
+        # (L,) for the one row, (B, L) for a batch
+        want = lambda: tensor_score.shape[:1] + tensor_score.shape[2:] if tensor_score.dim() == 3 else tensor_score.shape[1:]
+        d = Draw(temperature, uniforms, top_k, top_p, allowed, forced).check(want, lambda: self.num_notes_per_voice[0], False, GENERATE)
         self.last_logp = self.last_weights = None
         self.eval()
         batched = tensor_score.dim() == 3
@@ -480,16 +460,17 @@ class ConstraintModelGaussianReg(Model):
         for l in range(2):
             x, hT, cT = self._lstm(f"lstm_generation.{l}", x, False)
             hc[:, l, 0], hc[:, l, 1] = hT.reshape(B, H), cT.reshape(B, H)
-        u = np.random.random_sample((B, L)) if uniforms is None else uniforms
+        u = np.random.random_sample((B, L)) if d.uniforms is None else d.uniforms
         emb, *net = self._generation_weights()
         score_it = top_k is not None or top_p is not None or forced is not None
         logp = weights = None
-        if score_it or keep_weights or allowed is not None:
-            kw = {} if allowed is None else {"allowed": allowed.view(B, L, -1).to(dev).contiguous()}
-            if forced is not None:
-                kw["forced"] = forced.to(dev).to(torch.int32).reshape(B, L).contiguous()
-            toks, logp, weights = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc, top_k=k, top_p=top_p,
-                                                  want_logp=score_it, want_logits=bool(keep_weights), **kw)
+        if d.scored() or keep_weights:
+            kw = d.device(dev)
+            for name, n in (("allowed", (B, L, -1)), ("forced", (B, L))):     # (the one row's (L, ...) forms as a batch of one)
+                if name in kw:
+                    kw[name] = kw[name].view(n)
+            toks, logp, weights = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc, want_logp=score_it,
+                                                  want_logits=bool(keep_weights), **kw)
         else:
             toks = ops.arnn_sample(emb, oc.permute(1, 0, 2), *net, temperature, u, hc_init=hc)
         torch.cuda.synchronize()

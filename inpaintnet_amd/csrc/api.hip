@@ -129,7 +129,7 @@ int inet_vae_decoder_fwd(const inet_vae_config* cfg, int batch, const float* z, 
     if (!cfg_ok(cfg) || batch <= 0 || !z || !params || !weights || !samples || !ws) return -1;
     if (ws_bytes < (int64_t)vae_decoder_ws_bytes(*cfg, batch, save)) return -1;
     return vae_decoder_fwd(*cfg, batch, z, (const long long*)target, teacher_forced, params, mask_beat, mask_tick,
-                           weights, (long long*)samples, ws, save, (hipStream_t)stream, multinomial_seed);
+                           weights, (long long*)samples, ws, save, (hipStream_t)stream, multinomial_seed, sample::Request{});
 }
 int inet_vae_decoder_sample_fx(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
                                const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
@@ -137,12 +137,12 @@ int inet_vae_decoder_sample_fx(const inet_vae_config* cfg, int batch, const floa
                                const uint64_t* allow, const int32_t* forced, void* stream) {
     if (!cfg_ok(cfg) || batch <= 0 || !z || !params || !weights || !samples || !ws || !uniforms) return -1;
     if (allow && (int64_t)cfg->beats * cfg->ticks_per_beat > 64) return -1;    // (a constrained call: at most 64 ticks)
-    if (!std::isfinite(temperature) || cfg->num_notes > 512) return -1;
-    if (!(top_p > 0.0 && top_p <= 1.0)) return -1;             // (a NaN too)
+    sample::Request rq{uniforms, temperature, top_k, top_p, logp, nullptr, (const unsigned long long*)allow, (const int*)forced};
+    rq.dense(cfg->beats * cfg->ticks_per_beat, cfg->num_notes);
+    if (!rq.ok(cfg->num_notes)) return -1;
     if (ws_bytes < (int64_t)vae_decoder_ws_bytes(*cfg, batch, save)) return -1;
     return vae_decoder_fwd(*cfg, batch, z, nullptr, 0, params, mask_beat, mask_tick, weights, (long long*)samples, ws, save,
-                           (hipStream_t)stream, 0, uniforms, temperature, top_k, top_p, logp, (const unsigned long long*)allow,
-                           (const int*)forced);
+                           (hipStream_t)stream, 0, rq);
 }
 int inet_vae_decoder_sample_cx(const inet_vae_config* cfg, int batch, const float* z, const float* params, const float* mask_beat,
                                const float* mask_tick, float* weights, int64_t* samples, void* ws, int64_t ws_bytes, int save,
@@ -202,17 +202,19 @@ int inet_sample_multinomial(const float* weights, int64_t ld_w, int rows, int V,
 }
 int inet_sample_temperature(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                             int64_t u_stride, int64_t* out, int64_t stride, void* stream) {
-    if (!weights || !uniforms || !out || rows <= 0 || V <= 0 || V > 512 || !std::isfinite(temperature)) return -1;
-    return pw_sample_temperature(weights, ld_w, rows, V, temperature, uniforms, u_stride, (long long*)out, stride, (hipStream_t)stream);
+    if (!weights || !uniforms || !out || rows <= 0 || V <= 0) return -1;
+    sample::Request rq{uniforms, temperature};
+    rq.ld_u = u_stride;
+    return pw_sample(weights, ld_w, rows, V, (long long*)out, stride, rq, 1, (hipStream_t)stream);
 }
 int inet_sample_forced(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                        int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
                        const uint64_t* allow, int64_t allow_stride, const int32_t* forced, int64_t forced_stride, void* stream) {
-    if (!weights || !uniforms || !out || rows <= 0 || V <= 0 || V > 512 || !std::isfinite(temperature)) return -1;
-    if (!(top_p > 0.0 && top_p <= 1.0)) return -1;             // (a NaN too)
-    return pw_sample_forced(weights, ld_w, rows, V, temperature, uniforms, u_stride, top_k, top_p, (long long*)out, stride, logp,
-                            logp_stride, (const unsigned long long*)allow, allow_stride, (const int*)forced, forced_stride,
-                            (hipStream_t)stream);
+    if (!weights || !uniforms || !out || rows <= 0 || V <= 0) return -1;
+    sample::Request rq{uniforms, temperature, top_k, top_p, logp, nullptr, (const unsigned long long*)allow, (const int*)forced};
+    rq.ld_u = u_stride; rq.ld_logp = logp_stride; rq.ld_allow = allow_stride; rq.ld_forced = forced_stride;
+    // (the truncating kernel at the least, whatever the values: the three entries of this family promise it; pw_sample asks rq.ok())
+    return pw_sample(weights, ld_w, rows, V, (long long*)out, stride, rq, 2, (hipStream_t)stream);
 }
 int inet_sample_constrained(const float* weights, int64_t ld_w, int rows, int V, float temperature, const double* uniforms,
                             int64_t u_stride, int top_k, double top_p, int64_t* out, int64_t stride, float* logp, int64_t logp_stride,
@@ -507,12 +509,13 @@ int inet_arnn_sample_fx(int R, int L, int E, int Hc, int H, int U, int V, const 
     if (R < 1 || L < 1 || E <= 0 || Hc < 0 || H <= 0 || H % 16 || U <= 0 || V <= 0 || !emb || (Hc && !oc0) || !W_ih0 || !b_ih0 ||
         !W_hh0 || !b_hh0 || !W_ih1 || !b_ih1 || !W_hh1 || !b_hh1 || !W1 || !b1 || !W2 || !b2 || !uniforms || !tokens || !ws)
         return -1;
-    if (!std::isfinite(temperature) || oc_row_stride < 0 || oc_batch_stride < 0) return -1;
-    if (!(top_p > 0.0 && top_p <= 1.0)) return -1;             // (a NaN too)
+    if (oc_row_stride < 0 || oc_batch_stride < 0) return -1;
+    sample::Request rq{uniforms, temperature, top_k, top_p, logp, logits, (const unsigned long long*)allow, (const int*)forced};
+    rq.dense(L, V);
+    if (!rq.ok(V)) return -1;
     const ArnnGenNet net{E, Hc, H, U, V, emb, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1, W1, b1, W2, b2};
     if (ws_floats < (int64_t)arnn_sample_ws_floats(net, R, L)) return -1;
-    return arnn_sample(net, R, L, oc0, (long)oc_row_stride, (long)oc_batch_stride, temperature, uniforms, hc_init, (long long*)tokens, ws,
-                       (hipStream_t)stream, top_k, top_p, logp, logits, (const unsigned long long*)allow, (const int*)forced);
+    return arnn_sample(net, R, L, oc0, (long)oc_row_stride, (long)oc_batch_stride, hc_init, (long long*)tokens, ws, (hipStream_t)stream, rq);
 }
 int inet_arnn_sample_cx(int R, int L, int E, int Hc, int H, int U, int V, const float* emb, const float* oc0, int64_t oc_row_stride,
                         int64_t oc_batch_stride, const float* W_ih0, const float* b_ih0, const float* W_hh0, const float* b_hh0,

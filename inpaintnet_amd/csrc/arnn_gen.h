@@ -1,6 +1,7 @@
 // AnticipationRNN's token generation (arnn_gen.hip): the generation network's weights and the two entry points.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "sample.h"
 
 // emb [V', E]; W_ih0 [4H, E + Hc], W_hh0 [4H, H], W_ih1 / W_hh1 [4H, H], b_* [4H]; W1 [U, H], b1 [U]; W2 [V, U], b2 [V]
 struct ArnnGenNet {
@@ -18,14 +19,10 @@ int arnn_generate(const ArnnGenNet& net, int L, const float* oc0, long oc_stride
 // AnticipationRNN's generate (anticipation_rnn_gauss_reg_model.py:570-679): R independent rows, each L ticks with the token DRAWN from
 // softmax(temp * logits) by the uniform uniforms[r][t] (sample.h).  oc row r at oc0 + r * oc_bstride, hc_init [R][2][2][H] or null.
 size_t arnn_sample_ws_floats(const ArnnGenNet& net, int R, int L);
-// top_k / top_p: sample.h's truncation in front of the draw (0 / 1.0: off); logp [R][L] (nullable): the drawn tokens' log-probabilities
-// under the truncated distribution, NaN where a tick took the argmax rule; logits [R][L][V] (nullable): what each tick drew from.
-// Truncation on or one of the two pointers given: the truncating kernels (labels trunc_...); otherwise the kernels of the sampling build.
-// allow [R][L][ceil(V / 64)] (nullable): sample.h's words of allowed tokens per (row, tick), applied in front of the truncation inside the
-// launch -- the masked kernels (labels cons_...), which are truncating ones; null: the call above.
-// forced [R][L] (nullable): sample.h's forced words per (row, tick); a value in [0, V) is that tick's token, returned, fed back and scored
-// -- the forced kernels (labels force_...), which are masked ones (allow nullable); null: the call above.
-int arnn_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
-                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k = 0,
-                double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr,
-                const int* forced = nullptr);
+// rq: sample.h's Request with [R][L] arrays (logits [R][L][V]: what each tick drew from; allow [R][L][ceil(V / 64)]), uniforms required.
+// The request's level picks the kernels: 1 = the sampling build; 2 = the truncating kernels (labels trunc_...: truncation on, or logp /
+// logits wanted; logp is NaN where a tick took the argmax rule); 3 = the masked kernels (cons_...), which are truncating ones; 4 = the
+// forced kernels (force_...), which are masked ones (allow nullable): a forced value in [0, V) is that tick's token, returned, fed back
+// and scored.  -1: a shape out of range, or what rq.ok(V) refuses.
+int arnn_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, const float* hc_init,
+                long long* tokens, float* ws, hipStream_t s, const sample::Request& rq);

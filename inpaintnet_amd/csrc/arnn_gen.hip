@@ -624,19 +624,18 @@ size_t arnn_token_sample_ws_floats(int R, int L, int V) {
     return n * L * G4 + (size_t)V * G4 + n * 2 * kExGranules + 64 + 64;
 }
 
-// trunc: the truncating build (truncation on, or a logp / logits pointer given); its labels start with trunc_
-// allow (with trunc; V <= 64: arnn_token_cons_ok): the masked build, [R][L][1] words of allowed tokens; its labels start with cons_
-// forced (with trunc; arnn_token_force_ok): the forced build, [R][L] forced words, allow nullable; its labels start with force_
-int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
-                      const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, bool trunc, int top_k,
-                      double top_p, float* logp, float* logits, const unsigned long long* allow, const int* forced) {
+// rq ([R][L] arrays, uniforms given), one build per level of the request, the labels of a level from 2 up with its prefix:
+// 2 = the truncating build (V <= 64: arnn_token_trunc_ok); 3 = the masked build (arnn_token_cons_ok), [R][L][1] words of allowed tokens;
+// 4 = the forced build (arnn_token_force_ok), [R][L] forced words, allow nullable
+int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, long oc_stride, long oc_bstride, const float* hc_init,
+                      long long* tokens, float* ws, hipStream_t s, const sample::Request& rq) {
     const int V = net.V, n = sample_teams(R);
     float* pre = ws;
     float* T0 = pre + (size_t)n * L * G4;
     unsigned long long* ex = reinterpret_cast<unsigned long long*>(T0 + (size_t)V * G4);
     const int nb_t0 = (int)(((long)V * G4 + 255) / 256);
     char label[64];
-    const int level = sample::level(uniforms, trunc, allow, forced);
+    const int level = rq.level(V);
     std::snprintf(label, sizeof label, "%sarnn_token_sample R%d L%d V%d", level >= 2 ? sample::prefix(level) : "", R, L, V);
     for (int r0 = 0; r0 < R; r0 += n) {                          // R > teams: successive launches of up to `n` rows
         const int rows = std::min(n, R - r0);
@@ -646,17 +645,16 @@ int arnn_token_sample(const ArnnGenNet& net, int R, int L, const float* oc0, lon
         hipLaunchKernelGGL(arnn_gen_prep_kernel, dim3(p.nb_pre * rows + (r0 == 0 ? nb_t0 : 0)), dim3(256), 0, s, p);
         GenArgs a = gen_args(net, L, pre, T0, ex, status);
         a.hc_init = hc_init ? hc_init + (long)r0 * 4 * GH : nullptr; a.tokens = tokens + (long)r0 * L;
-        a.rows = rows; a.temp = temp; a.uniforms = uniforms + (long)r0 * L;
-        a.top_k = top_k; a.top_p = top_p;
-        a.logp = logp ? logp + (long)r0 * L : nullptr; a.logits = logits ? logits + (long)r0 * L * V : nullptr;
-        a.allow = allow ? allow + (long)r0 * L * ((V + 63) / 64) : nullptr;     // (this launch's rows, like uniforms, logp and logits)
-        a.forced = forced ? forced + (long)r0 * L : nullptr;
+        const sample::Request q = rq.rows(r0);                   // (this launch's rows)
+        a.rows = rows; a.temp = q.temperature; a.uniforms = q.uniforms;
+        a.top_k = q.top_k; a.top_p = q.top_p;
+        a.logp = q.logp; a.logits = q.logits; a.allow = q.allow; a.forced = q.forced;
         ProfScope prof(PROF_GRU_FWD, 2.0 * rows * L * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH), s, label,
                        4.0 * (3.0 * G4 * GH + (double)GH * GH + (double)V * GH + (double)(rows * L + V) * G4));
         const dim3 grid(a.stride == 8 ? 13 * 8 : 13 * rows);
-        if (forced) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true, true>), grid, dim3(NT), 0, s, a);   // (arnn_token_force_ok)
-        else if (allow) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true>), grid, dim3(NT), 0, s, a);   // (V <= 64: arnn_token_cons_ok)
-        else if (trunc) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true>), grid, dim3(NT), 0, s, a);    // (V <= 64: arnn_token_trunc_ok)
+        if (level == 4) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true, true>), grid, dim3(NT), 0, s, a);   // (arnn_token_force_ok)
+        else if (level == 3) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true, true>), grid, dim3(NT), 0, s, a);   // (V <= 64: arnn_token_cons_ok)
+        else if (level == 2) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true, true>), grid, dim3(NT), 0, s, a);    // (V <= 64: arnn_token_trunc_ok)
         else if (V <= 64) hipLaunchKernelGGL((arnn_token_pass_kernel<1, true>), grid, dim3(NT), 0, s, a);
         else hipLaunchKernelGGL((arnn_token_pass_kernel<2, true>), grid, dim3(NT), 0, s, a);
         if (hipGetLastError() != hipSuccess) return -2;
@@ -842,17 +840,12 @@ bool arnn_ticks_ok(const ArnnGenNet& n) { return n.E + n.Hc <= 320 && n.H <= 256
 size_t arnn_ticks_ws_floats(const ArnnGenNet& n) { return (size_t)(n.E + n.Hc) + 4 * (size_t)n.H + 8 * (size_t)n.H + n.U + n.V + 64; }
 
 // L ticks of one row from the state hc_init [layer][h | c][H] (null: zeros; inpainting: the state after the prefix) and the token
-// *first_tok (null: 0); `uniforms` [L]: the sampling head, null: the argmax head; trunc (with uniforms): the truncating head, logp [L]
-// and logits [L][V] nullable, one label (trunc_arnn_ticks ...) around the row's launches; allow (with trunc): the row's [L][ceil(V / 64)]
-// words of allowed tokens -- the masked head, label cons_arnn_ticks ...; forced (with trunc): the row's [L] forced words -- the forced
-// head, label force_arnn_ticks ..., allow nullable
+// *first_tok (null: 0), the head of the request's level: rq = the ROW's request ([L] arrays; no uniforms: the argmax head).  From level 2
+// up one label (trunc_ / cons_ / force_arnn_ticks ...) goes around the row's launches; a call below files nothing.
 int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, const float* hc_init, const long long* first_tok,
-               float temp, const double* uniforms, long long* tokens, float* ws, hipStream_t s, bool trunc = false, int top_k = 0,
-               double top_p = 1.0, float* logp = nullptr, float* logits = nullptr, const unsigned long long* allow = nullptr,
-               const int* forced = nullptr) {
+               long long* tokens, float* ws, hipStream_t s, const sample::Request& rq) {
     const int H = n.H;
-    const int level = sample::level(uniforms, trunc, allow, forced);
-    // (a call below level 2 files nothing.  `trunc` counts only with uniforms -- sample::level --, and no caller sets it without them)
+    const int level = rq.level(n.V);
     std::optional<ProfScope> prof;
     if (level >= 2) {
         char label[64];
@@ -877,11 +870,10 @@ int arnn_ticks(const ArnnGenNet& n, int L, const float* oc, long oc_stride, cons
                            (const float*)C_(1, p), n.W_hh1, n.b_hh1, H_(1, p ^ 1), C_(1, p ^ 1), H);
         hipLaunchKernelGGL((relu_linear_b1_kernel<4>), dim3((n.U + 3) / 4), dim3(256), 0, s, (const float*)H_(1, p ^ 1), n.W1, n.b1, u,
                            n.U, H);
+        const sample::Request q = rq.tick(t, n.V);
 #define HEAD_B1(LEVEL)                                                                                                          \
-    hipLaunchKernelGGL((head_b1_kernel<4, LEVEL>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U, temp, \
-                       uniforms ? uniforms + t : nullptr, top_k, top_p, logp ? logp + t : nullptr,                                  \
-                       logits ? logits + (long)t * n.V : nullptr, allow ? allow + (long)t * ((n.V + 63) / 64) : nullptr,                \
-                       forced ? forced + t : nullptr)
+    hipLaunchKernelGGL((head_b1_kernel<4, LEVEL>), dim3(1), dim3(1024), 0, s, (const float*)u, n.W2, n.b2, tokens + t, n.V, n.U,       \
+                       q.temperature, q.uniforms, q.top_k, q.top_p, q.logp, q.logits, q.allow, q.forced)
         switch (level) {
             case 0: HEAD_B1(0); break;
             case 1: HEAD_B1(1); break;
@@ -907,24 +899,21 @@ int arnn_generate(const ArnnGenNet& n, int L, const float* oc0, long oc_stride, 
                   long long* tokens, float* ws, hipStream_t s) {
     if (arnn_token_pass_ok(n)) return arnn_token_pass(n, L, oc0, oc_stride, hc_init, first_tok, tokens, ws, s);   // 14.3 -> ~3.5 us per tick
     if (!arnn_ticks_ok(n)) return -1;
-    return arnn_ticks(n, L, oc0, oc_stride, hc_init, first_tok, 0.f, nullptr, tokens, ws, s);
+    return arnn_ticks(n, L, oc0, oc_stride, hc_init, first_tok, tokens, ws, s, sample::Request{});
 }
 
-int arnn_sample(const ArnnGenNet& n, int R, int L, const float* oc0, long oc_stride, long oc_bstride, float temp,
-                const double* uniforms, const float* hc_init, long long* tokens, float* ws, hipStream_t s, int top_k, double top_p,
-                float* logp, float* logits, const unsigned long long* allow, const int* forced) {
-    // truncation on, or an output only the truncating kernels write: never a kernel that ignores them; a mask of allowed tokens: the
-    // masked kernels, which are truncating ones; forced words: the forced kernels, which are masked ones -- never a kernel that ignores them
-    const bool trunc = (top_k >= 1 && top_k < n.V) || top_p < 1.0 || logp || logits || allow || forced;
-    if (forced ? arnn_token_force_ok(n) : allow ? arnn_token_cons_ok(n) : trunc ? arnn_token_trunc_ok(n) : arnn_token_pass_ok(n))    // up to 8 rows per launch
-        return arnn_token_sample(n, R, L, oc0, oc_stride, oc_bstride, temp, uniforms, hc_init, tokens, ws, s, trunc, top_k, top_p, logp,
-                                 logits, allow, forced);
+int arnn_sample(const ArnnGenNet& n, int R, int L, const float* oc0, long oc_stride, long oc_bstride, const float* hc_init,
+                long long* tokens, float* ws, hipStream_t s, const sample::Request& rq) {
+    // each level has its build of the token pass, and the builds have bounds of their own (V <= 64 from level 2 up): never a kernel that
+    // ignores what the request asks for
+    const int level = rq.level(n.V);
+    if (level < 1 || !rq.ok(n.V)) return -1;
+    if (level == 4 ? arnn_token_force_ok(n) : level == 3 ? arnn_token_cons_ok(n) : level == 2 ? arnn_token_trunc_ok(n) : arnn_token_pass_ok(n))
+        return arnn_token_sample(n, R, L, oc0, oc_stride, oc_bstride, hc_init, tokens, ws, s, rq);    // up to 8 rows per launch
     if (!arnn_ticks_ok(n)) return -1;
     int rc = 0;
     for (int r = 0; r < R && rc == 0; ++r)                     // the rows one after the other
-        rc = arnn_ticks(n, L, oc0 + (long)r * oc_bstride, oc_stride, hc_init ? hc_init + (long)r * 4 * n.H : nullptr, nullptr, temp,
-                        uniforms + (long)r * L, tokens + (long)r * L, ws, s, trunc, top_k, top_p, logp ? logp + (long)r * L : nullptr,
-                        logits ? logits + (long)r * L * n.V : nullptr, allow ? allow + (long)r * L * ((n.V + 63) / 64) : nullptr,
-                        forced ? forced + (long)r * L : nullptr);
+        rc = arnn_ticks(n, L, oc0 + (long)r * oc_bstride, oc_stride, hc_init ? hc_init + (long)r * 4 * n.H : nullptr, nullptr,
+                        tokens + (long)r * L, ws, s, rq.rows(r));
     return rc;
 }

@@ -1105,11 +1105,11 @@ int placed_grid(int teams, int rteams, int beat_wgs, int crit = kCrit) {
 // own launches (folded beat path) or decode_chain.hip's exchange kernel.
 // A SAMPLED call (temperature + uniforms) gets the same plans from the same planner under mode 4, with merged_build() deciding which
 // shapes have a merged sampling build; under the other modes it has no plan here, and vae_decoder_fwd samples tick by tick.
-// A TRUNCATED call (DecodeChainArgs.trunc: top-k / nucleus truncation, or the draws' log-probabilities wanted) likewise, with the
+// A TRUNCATED call (DecodeChainArgs.draw at level 2: top-k / nucleus truncation, or the draws' log-probabilities wanted) likewise, with the
 // truncating builds (decode_b1_kernel<..., true, true>) and their merged_build(); at most kTruncTicks ticks.
-// A CONSTRAINED call (DecodeChainArgs.allow: a mask of allowed tokens per (row, tick)) has the truncated call's plan with the masked builds
+// A CONSTRAINED call (draw.allow: a mask of allowed tokens per (row, tick)) has the truncated call's plan with the masked builds
 // (decode_b1_kernel<..., true, true, true>): every one of them fits without a spill.
-// A FORCED call (DecodeChainArgs.forced: a forced token per (row, tick), with or without a mask) has the constrained call's plan with the
+// A FORCED call (draw.forced: a forced token per (row, tick), with or without a mask) has the constrained call's plan with the
 // forced builds (decode_b1_kernel<..., true, true, true, true>): every one of them fits likewise.
 
 // What launch_decode_b1 launches for a call, as a value (also behind inet_decode_b1_plan: the planner is tested without a GPU).  The
@@ -1270,8 +1270,8 @@ bool decode_b1_shape_ok(int B, int H, int V, int T, int G, int sample) {
 bool decode_b1_fused(int Z, int B, int V, int sample) { return Z == DZ && make_plan(B, V, true, sample).ok; }
 bool decode_b1_ok(const DecodeChainArgs& a) {
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;
-    const int sample = sample::level(a.uniforms, a.trunc, a.allow, a.forced);
-    if ((a.allow || a.forced) && !a.uniforms) return false;
+    const int sample = a.draw.level(a.V);
+    if (!a.draw.ok(a.V)) return false;
     return decode_b1_shape_ok(a.B, a.H, a.V, a.T, a.G, sample) && !train && a.b1ex && make_plan(a.B, a.V, a.beat.z != nullptr, sample).ok;
 }
 
@@ -1333,7 +1333,7 @@ int decode_b1_plan_check(int B, int V, int Z, int* out, int sample) {
 }
 
 int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
-    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, sample::level(d.uniforms, d.trunc, d.allow, d.forced));
+    const B1Plan pl = make_plan(d.B, d.V, d.beat.z != nullptr, d.draw.level(d.V));
     if (!pl.ok || pl.rows > decode_b1_rows(d.B)) return -1;   // (decode_b1_ok has accepted the call: not reached)
     B1Args a{};
     a.fused = pl.fused; a.teams = pl.teams; a.rgroups = pl.rgroups; a.crit = pl.crit; a.place = pl.place; a.stride = pl.stride;
@@ -1345,8 +1345,9 @@ int launch_decode_b1(const DecodeChainArgs& d, hipStream_t s) {
     a.bp = d.beat;
     a.stamps = d.b1stamps;
     a.status = d.status;
-    a.uniforms = d.uniforms; a.temperature = d.temperature;
-    a.top_k = d.top_k; a.top_p = d.top_p; a.logp = d.logp; a.allow = d.allow; a.forced = d.forced;
+    const sample::Request& q = d.draw;
+    a.uniforms = q.uniforms; a.temperature = q.temperature;
+    a.top_k = q.top_k; a.top_p = q.top_p; a.logp = q.logp; a.allow = q.allow; a.forced = q.forced;
     if (!dispatch_b1(pl, nullptr, nullptr)) return -1;        // (a plan without an instantiation launches nothing)
     char label[64];
     // (a sampled, a truncated, a constrained and a forced call's launch have label prefixes of their own: the profile tells the kinds of call apart)

@@ -1,6 +1,7 @@
 // Fused free-running decode kernel (decode_chain.hip; protocol in chain.h).
 #pragma once
 #include "chain.h"
+#include "sample.h"
 
 constexpr int kDecodeMaxGroups = 8;               // row tiles of 16*MS rows: B <= 256 at MS = 2
 constexpr int kDecodeCounterStride = 64;          // one 256-byte block per group counter (see gru_chain.h)
@@ -45,17 +46,9 @@ struct DecodeChainArgs {
     float* sv0; float* sv1; long sv_stride;       // saves r,z,n,W_hn h + b_hn,h_prev of layer 0 / 1: [5][T,B,H], stride
     float* h0out;                                 // [T,B,H] layer-0 output as layer 1 saw it (masked if mask)
     float* h1seq;                                 // [T,B,H] layer-1 output (input of the output projection's gradients)
-    // temperature sampling (decode_b1.hip's sampling build only: launch_decode_chain refuses a sampled call it cannot hand there)
-    const double* uniforms;                       // [B,T] one uniform per (row, tick), or null: the argmax rule
-    float temperature;                            // the logits' factor in front of the softmax
-    // ... behind sample.h's top-k / nucleus truncation (decode_b1.hip's truncating build only, likewise)
-    int trunc;                                    // 1: truncation is on or logp is wanted -- the truncating build's plan and kernels
-    int top_k; double top_p;                      // top_k <= 0 or >= V: off; top_p in (0, 1], 1: off
-    float* logp;                                  // [B,T] the drawn tokens' log-probabilities under the truncated distribution, or null
-    // ... behind sample.h's per-tick token constraints (decode_b1.hip's masked build only, likewise; a constrained call is a truncated one)
-    const unsigned long long* allow;              // [B,T,ceil(V/64)] the allowed tokens' words, or null: no constraint
-    // ... behind sample.h's forced tokens (decode_b1.hip's forced build only, likewise; a forced call is a constrained one, with or without a mask)
-    const int* forced;                            // [B,T] the forced tokens, a value outside [0, V) = a free tick, or null: no tick is forced
+    // the draw (sample.h: uniforms null = the argmax rule).  decode_b1.hip's builds alone know it: launch_decode_chain refuses a sampled
+    // call it cannot hand there.  [B,T] arrays (allow: [B,T,ceil(V/64)]); launch_decode_b1 unpacks it into the kernel's arguments.
+    sample::Request draw;
 };
 
 bool decode_chain_ok(int B, int H, int V, int T, int G);

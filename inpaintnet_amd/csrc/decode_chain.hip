@@ -477,7 +477,7 @@ int launch_decode_chain(DecodeChainArgs a, hipStream_t s) {
     a.status = chain_status_for(a.counters + kDecodeStatusWord);
     if (decode_b1_ok(a)) return launch_decode_b1(a, s);        // one measure: weights in registers, two hand-offs per tick
     if (a.beat.z) return -1;                                   // (the beat path was left to decode_b1's launch: cgi / ht0 are not there)
-    if (a.uniforms) return -1;                                 // (a sampled call: the exchange kernel below knows the argmax rule alone)
+    if (a.draw.uniforms) return -1;                            // (a sampled call: the exchange kernel below knows the argmax rule alone)
     const size_t lds = decode_chain_lds_bytes(a.B, a.H);
     char label[72];
     const bool train = a.sv0 || a.sv1 || a.mask || a.h0out || a.h1seq;

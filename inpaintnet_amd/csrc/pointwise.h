@@ -20,24 +20,15 @@ int pw_latent_bwd(const float* dz, const float* mu, const float* ls, const float
                   float* dmu, float* dls, long n, hipStream_t s);
 int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long* out, long stride, uint64_t seed,
                           uint64_t offset, hipStream_t s);
-// out[row*stride] = sample.h's token for softmax(temp * W[row,:]) and the uniform uniforms[row*u_stride]; argmax_first where the rule
-// does not apply.  V <= 512, else -1.
-int pw_sample_temperature(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride,
-                          long long* out, long stride, hipStream_t s);
-// The same behind sample.h's top-k / nucleus truncation (top_k <= 0 or >= V: off; top_p in (0, 1], 1 = off, else -1), and
-// logp[row*lp_stride] (nullable) = the drawn token's log-probability under the truncated distribution, NaN where the row took argmax_first.
-int pw_sample_truncated(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
-                        double top_p, long long* out, long stride, float* logp, long lp_stride, hipStream_t s);
-// The same behind sample.h's token constraints: allow + row*allow_stride = the row's ceil(V / 64) words of allowed tokens (null: the call
-// above).  A row outside the rule takes argmax_first over its allowed tokens.
-int pw_sample_constrained(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
-                          double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
-                          long allow_stride, hipStream_t s);
-// The same behind sample.h's forced tokens: forced[row*forced_stride] = the row's forced token, a value outside [0, V) = a free row (null:
-// the call above).  A forced row returns its token whatever the mask and the logits hold; allow may be null (all ones).
-int pw_sample_forced(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
-                     double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
-                     long allow_stride, const int* forced, long forced_stride, hipStream_t s);
+// out[row*stride] = sample.h's token of the row W[row,:] for the request r: a row here is what r calls a row, so r's strides step from
+// row to row (uniforms required, logits not written).  ONE of the four row kernels runs -- temperature, truncated, constrained, forced --:
+// the one of level max(floor_level, r.level(V)).  floor_level is 1 or 2: an entry that promises the truncating kernel passes 2, so that
+// inet_sample_truncated with truncation off and no logp still runs it under its trunc_ label; vae.hip's tick loop passes the call's level.
+// Levels 3 and 4 come from r's mask and forced array alone (level 4 without a mask: words of all ones).  A row outside the rule takes
+// argmax_first over its allowed tokens, logp NaN.  -1: what r.ok(V) refuses.
+namespace sample { struct Request; }
+int pw_sample(const float* W, long ld_w, int rows, int V, long long* out, long stride, const sample::Request& r, int floor_level,
+              hipStream_t s);
 // The norm of the gradient arena: partials[pw_sqnorm_parts()] = the f64 sums of squares of the fixed grid's shares of g (every entry
 // written: nothing to zero in front), what the optimizer step takes as `partials`.
 int pw_sqnorm_parts();

@@ -5,6 +5,7 @@
 // atomics), transposes, dropout-mask generation.  All are grid-stride,
 // coalesced along the contiguous dimension, 64-lane wave reductions via DPP
 // shuffles.
+#include <algorithm>
 #include <cstdio>
 #include "common.h"
 #include "pointwise.h"
@@ -1265,55 +1266,29 @@ int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long*
                        out, stride, seed, offset);
     return ok();
 }
-int pw_sample_temperature(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride,
-                          long long* out, long stride, hipStream_t s) {
-    if (V > 512) return -1;
+int pw_sample(const float* W, long ld_w, int rows, int V, long long* out, long stride, const sample::Request& r, int floor_level,
+              hipStream_t s) {
+    if (!r.uniforms || r.logits || !r.ok(V)) return -1;
+    const int level = std::max(std::min(floor_level, 2), r.level(V));      // (a floor above 2 would read a null mask or forced array)
     char label[48];
-    std::snprintf(label, sizeof label, "sample_temperature B%d V%d", rows, V);
-    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 16.0));
+    if (level == 1) std::snprintf(label, sizeof label, "sample_temperature B%d V%d", rows, V);
+    else std::snprintf(label, sizeof label, "%ssample B%d V%d", sample::prefix(level), rows, V);
+    // per row: the logits, the uniform and the token; from level 2 the log-probability, the mask words where given, at level 4 the forced word
+    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 16.0 + (level >= 2 ? 4.0 : 0.0) + (level >= 4 ? 4.0 : 0.0) +
+                                                            (r.allow ? 8.0 * sample::Request::words(V) : 0.0)));
     const dim3 grid(grid_for((long)rows * 64, 256, 1024));
-#define PW_ST(NV) hipLaunchKernelGGL(sample_temperature_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, out, stride)
-    if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
-#undef PW_ST
-    return ok();
-}
-int pw_sample_truncated(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
-                        double top_p, long long* out, long stride, float* logp, long lp_stride, hipStream_t s) {
-    if (V > 512 || !(top_p > 0.0 && top_p <= 1.0)) return -1;
-    char label[48];
-    std::snprintf(label, sizeof label, "trunc_sample B%d V%d", rows, V);
-    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 20.0));
-    const dim3 grid(grid_for((long)rows * 64, 256, 1024));
-#define PW_ST(NV) hipLaunchKernelGGL(sample_truncated_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride)
-    if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
-#undef PW_ST
-    return ok();
-}
-int pw_sample_constrained(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
-                          double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
-                          long allow_stride, hipStream_t s) {
-    if (!allow) return pw_sample_truncated(W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride, s);
-    if (V > 512 || !(top_p > 0.0 && top_p <= 1.0)) return -1;
-    char label[48];
-    std::snprintf(label, sizeof label, "cons_sample B%d V%d", rows, V);
-    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 20.0 + 8.0 * ((V + 63) / 64)));
-    const dim3 grid(grid_for((long)rows * 64, 256, 1024));
-#define PW_ST(NV) hipLaunchKernelGGL(sample_constrained_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride, allow, allow_stride)
-    if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
-#undef PW_ST
-    return ok();
-}
-int pw_sample_forced(const float* W, long ld_w, int rows, int V, float temp, const double* uniforms, long u_stride, int top_k,
-                     double top_p, long long* out, long stride, float* logp, long lp_stride, const unsigned long long* allow,
-                     long allow_stride, const int* forced, long forced_stride, hipStream_t s) {
-    if (!forced) return pw_sample_constrained(W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride, allow,
-                                              allow_stride, s);
-    if (V > 512 || !(top_p > 0.0 && top_p <= 1.0)) return -1;
-    char label[48];
-    std::snprintf(label, sizeof label, "force_sample B%d V%d", rows, V);
-    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 24.0 + (allow ? 8.0 * ((V + 63) / 64) : 0.0)));
-    const dim3 grid(grid_for((long)rows * 64, 256, 1024));
-#define PW_ST(NV) hipLaunchKernelGGL(sample_forced_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, uniforms, u_stride, top_k, top_p, out, stride, logp, lp_stride, allow, allow_stride, forced, forced_stride)
+    const float temp = r.temperature;
+#define PW_ST(NV)                                                                                                                         \
+    do { switch (level) {                                                                                                                 \
+        case 1: hipLaunchKernelGGL(sample_temperature_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u, out,   \
+                                   stride); break;                                                                                        \
+        case 2: hipLaunchKernelGGL(sample_truncated_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u, r.top_k, \
+                                   r.top_p, out, stride, r.logp, r.ld_logp); break;                                                       \
+        case 3: hipLaunchKernelGGL(sample_constrained_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u,       \
+                                   r.top_k, r.top_p, out, stride, r.logp, r.ld_logp, r.allow, r.ld_allow); break;                         \
+        default: hipLaunchKernelGGL(sample_forced_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u, r.top_k,  \
+                                    r.top_p, out, stride, r.logp, r.ld_logp, r.allow, r.ld_allow, r.forced, r.ld_forced);                 \
+    } } while (0)
     if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
 #undef PW_ST
     return ok();

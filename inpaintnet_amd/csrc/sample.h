@@ -4,8 +4,12 @@
 // v whose inclusive prefix exceeds u.  Here e_v = exp(s_v - max s) in f32 (s = T x, the reference's f32 softmax numerator), the
 // prefix over v in f64 (a wave scan over 64 lanes x NV chunks: DPP shifts inside the 16-lane rows, the row totals by readlane), and
 // token = the first v with prefix_v > u * S, S = the total, by ballot and ctz.  The result is wave-uniform.
+// Below, in this order: pick(), truncate(), the mask and forced-token helpers, draw() -- the device rule of one (row, tick), one build per
+// level -- and, host side, Request: what a CALL asks of the draw, carried as one value from the C-ABI entries to the launch sites of
+// vae.hip, decode_b1.hip, arnn_gen.hip and pointwise.hip.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include "common.h"
 
 namespace sample {
@@ -267,12 +271,55 @@ __device__ __forceinline__ int draw(const float (&x)[NV], float temp, double u, 
     return forced ? f : tok;
 }
 
-// The level of a call from what it passes (0 = argmax: no uniforms), and the prefix of its launch labels.
-constexpr int level(const void* uniforms, bool trunc, const void* allow, const void* forced) {
-    return !uniforms ? 0 : forced ? 4 : allow ? 3 : trunc ? 2 : 1;
-}
+// The prefix of a level's launch labels.
 constexpr const char* prefix(int level) {
     return level == 4 ? "force_" : level == 3 ? "cons_" : level == 2 ? "trunc_" : level == 1 ? "sample_" : "";
 }
+
+// THE REQUEST of a call, host side: everything a caller may ask of the draw, as ONE value from the C-ABI entry (api.hip builds it and asks
+// ok()) to the place a kernel-argument struct is filled, which reads it field by field.  The default value is the argmax call.  Arrays are
+// per (row, tick): row r of `x` starts at x + r * ld_x, tick t behind it (logits: t * V floats, allow: t * ceil(V / 64) words).
+struct Request {
+    const double* uniforms = nullptr;            // one uniform per (row, tick); null: the argmax rule, and nothing below may be set
+    float temperature = 1.f;                     // the logits' factor in front of the softmax
+    int top_k = 0; double top_p = 1.0;           // truncate(): top_k <= 0 or >= V: off; top_p in (0, 1], 1: off
+    float* logp = nullptr;                       // the drawn tokens' log-probabilities, or null
+    float* logits = nullptr;                     // [.., V] what each tick drew from (AnticipationRNN alone), or null
+    const unsigned long long* allow = nullptr;   // [.., ceil(V / 64)] the allowed tokens' words, or null: no constraint
+    const int* forced = nullptr;                 // the forced tokens, or null: no tick is forced
+    long ld_u = 0, ld_logp = 0, ld_logits = 0, ld_allow = 0, ld_forced = 0;   // the row strides, in elements
+
+    // the strides of contiguous [rows][T] arrays
+    Request& dense(int T, int V) {
+        ld_u = ld_logp = ld_forced = T; ld_logits = (long)T * V; ld_allow = (long)T * words(V);
+        return *this;
+    }
+    static constexpr int words(int V) { return (V + 63) / 64; }
+    template <class P> static P* at(P* p, long off) { return p ? p + off : nullptr; }
+    // the request of the rows from r0 on / of the ticks from t on: every array moved, null stays null
+    Request rows(long r0) const {
+        Request q = *this;
+        q.uniforms = at(uniforms, r0 * ld_u); q.logp = at(logp, r0 * ld_logp); q.logits = at(logits, r0 * ld_logits);
+        q.allow = at(allow, r0 * ld_allow); q.forced = at(forced, r0 * ld_forced);
+        return q;
+    }
+    Request tick(long t, int V) const {
+        Request q = *this;
+        q.uniforms = at(uniforms, t); q.logp = at(logp, t); q.logits = at(logits, t * V);
+        q.allow = at(allow, t * words(V)); q.forced = at(forced, t);
+        return q;
+    }
+    // a truncating call: truncation on, or something only the truncating kernels read or write
+    bool truncating(int V) const { return (top_k >= 1 && top_k < V) || top_p < 1.0 || logp || logits || allow || forced; }
+    // 0 = argmax (no uniforms), 1 = temperature, 2 = truncated, 3 = masked, 4 = forced: draw()'s LEVEL
+    int level(int V) const { return !uniforms ? 0 : forced ? 4 : allow ? 3 : truncating(V) ? 2 : 1; }
+    // what every entry refuses: a top_p outside (0, 1] (a NaN too), anything asked of an argmax call, a temperature that is not finite,
+    // more tokens than the widest build holds
+    bool ok(int V) const {
+        if (!(top_p > 0.0 && top_p <= 1.0)) return false;
+        if (!uniforms) return top_k <= 0 && top_p == 1.0 && !logp && !logits && !allow && !forced;
+        return std::isfinite(temperature) && V <= 512;
+    }
+};
 
 }  // namespace sample

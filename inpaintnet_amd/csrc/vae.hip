@@ -284,21 +284,18 @@ size_t vae_decoder_ws_bytes(const inet_vae_config& c, int B, int save) {
 
 int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long long* target, int teacher_forced,
                     const float* p, const float* mask_beat, const float* mask_tick, float* weights,
-                    long long* samples, void* ws, int save, hipStream_t s, uint64_t multinomial_seed, const double* uniforms,
-                    float temperature, int top_k, double top_p, float* logp, const unsigned long long* allow, const int* forced) {
+                    long long* samples, void* ws, int save, hipStream_t s, uint64_t multinomial_seed, const sample::Request& rq) {
     const int nb = c.beats, G = c.ticks_per_beat, T = nb * G, H = c.dec_hidden, V = c.num_notes, E = c.emb_dim, Z = c.z_dim;
     const long BH = (long)B * H;
     if (nb > 4) return -1;
     if (teacher_forced && !target) return -1;
-    const bool sampled = uniforms != nullptr;                  // temperature sampling (sample.h): a free-running inference call
-    if (sampled && (teacher_forced || multinomial_seed || V > 512)) return -1;
-    // top-k / nucleus truncation in front of every draw, or the draws' log-probabilities wanted: the truncating kernels
-    // ... a mask of allowed tokens: the masked kernels, which are truncating ones
-    // ... forced tokens: the forced kernels, which are masked ones (with or without a mask)
-    const bool trunc = sampled && ((top_k >= 1 && top_k < V) || top_p < 1.0 || logp || allow || forced);
-    const int level = sample::level(uniforms, trunc, allow, forced);       // (sample.h: 0 = argmax ... 4 = forced)
-    if (!sampled && (logp || top_k > 0 || top_p < 1.0 || allow || forced)) return -1;
-    if (!(top_p > 0.0 && top_p <= 1.0)) return -1;
+    const bool sampled = rq.uniforms != nullptr;               // temperature sampling (sample.h): a free-running inference call
+    if (sampled && (teacher_forced || multinomial_seed)) return -1;
+    if (!rq.ok(V) || rq.logits) return -1;
+    // 0 = argmax; 1 = temperature; 2 = top-k / nucleus truncation in front of every draw, or the draws' log-probabilities wanted: the
+    // truncating kernels; 3 = a mask of allowed tokens: the masked kernels, which are truncating ones; 4 = forced tokens: the forced
+    // kernels, which are masked ones (with or without a mask)
+    const int level = rq.level(V);
     VaeLayout L(c);
     DecWs w{};
     dec_carve(c, B, save, ws, w);
@@ -545,8 +542,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
             }
             a.weights = weights + (long)r0 * T * V; a.samples = samples + (long)r0 * T;
             a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0;   // (later chunks: the launcher zeroes the area)
-            a.uniforms = uniforms; a.temperature = temperature;                 // (sampled: one whole launch, never chunks)
-            a.trunc = trunc; a.top_k = top_k; a.top_p = top_p; a.logp = logp; a.allow = allow; a.forced = forced;   // (null without uniforms: refused above)
+            a.draw = rq;                                       // (sampled: one whole launch, never chunks)
             if (mask_tick) { a.mask = mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
             if (save) {
                 a.sv0 = w.svt0 + (long)r0 * H; a.sv1 = w.svt1 + (long)r0 * H; a.sv_stride = (long)T * BH;
@@ -604,13 +600,7 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
                                 (long)T * V, B, V, H, EPI_RELU, s));
             if (draw) INET_TRY(pw_sample_multinomial(weights + (long)t * V, (long)T * V, B, V, samples + t, T,
                                                      multinomial_seed, (uint64_t)t * B, s));
-            else if (level == 1) INET_TRY(pw_sample_temperature(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T,
-                                                                samples + t, T, s));
-            // (levels 2 to 4 behind one call: a null `forced` is the constrained call, a null `allow` behind it the truncated one)
-            else if (sampled) INET_TRY(pw_sample_forced(weights + (long)t * V, (long)T * V, B, V, temperature, uniforms + t, T, top_k, top_p,
-                                                        samples + t, T, logp ? logp + t : nullptr, T,
-                                                        allow ? allow + (long)t * ((V + 63) / 64) : nullptr, (long)T * ((V + 63) / 64),
-                                                        forced ? forced + t : nullptr, T, s));
+            else if (sampled) INET_TRY(pw_sample(weights + (long)t * V, (long)T * V, B, V, samples + t, T, rq.tick(t, V), level, s));
             else INET_TRY(pw_argmax(weights + (long)t * V, (long)T * V, B, V, samples + t, T, s));
         }
     }

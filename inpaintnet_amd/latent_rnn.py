@@ -10,7 +10,6 @@ decoded by the frozen VAE decoder.  Differences that are the point of the build:
   * every GRU / Linear is a single autograd Function over the C-ABI (inet_bigru2_*, inet_linear_*);
     the decoder runs dgrad-only (frozen parameters, latent_rnn.py:42-43).
 """
-import math
 import os
 import random
 
@@ -19,6 +18,7 @@ import torch
 
 from . import dp, layout, ops
 from ._lib import LatentConfig
+from .draw import LATENT, Draw
 from .measure_vae import MeasureVAE, _DropState, _next_mask_offset
 from .model import Model
 
@@ -199,11 +199,11 @@ class LatentRNN(Model):
         return torch.zeros(self.num_rnn_layers * self.rnn_num_direction, batch_size, self.rnn_hidden_size,
                            device=self.flat.device)
 
-    def _decode(self, z2d, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None, forced=None):
-        """frozen decoder, train=False (latent_rnn.py:238): dropout still follows module.training (the quirk)."""
+    def _decode(self, z2d, d):
+        """frozen decoder, train=False (latent_rnn.py:238): dropout still follows module.training (the quirk).  d: the Draw of these rows"""
         dummy = torch.zeros(z2d.shape[0], self.vae_model.num_ticks_per_measure, device=z2d.device)
-        return self.vae_model.decoder(z2d, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
-                                      allowed=allowed, **({} if forced is None else {"forced": forced}))
+        return self.vae_model.decoder(z2d, dummy, train=False, temperature=d.temperature, uniforms=d.uniforms, top_k=d.top_k,
+                                      top_p=d.top_p, allowed=d.allowed, **({} if d.forced is None else {"forced": d.forced}))
 
     def forward(self, past_context, future_context, target, measures_to_generate, train=True, eps=None,
                 teacher_forcing=None, eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None,
@@ -225,46 +225,11 @@ class LatentRNN(Model):
         hands each measure's slice to its decoder call and re-encodes the forced tokens as it does the drawn ones.  Such a call
         always leaves self.last_logp."""
         batch_size, _, measure_seq_len = past_context.size()
-        if forced is not None:
-            if train:
-                raise ValueError("forced tokens are an inference call (train=False)")
-            if temperature is None:
-                raise ValueError("forced tokens need a temperature")
-            forced = torch.as_tensor(forced)
-            if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool or \
-                    tuple(forced.shape) != (batch_size, measures_to_generate, measure_seq_len):
-                raise ValueError(f"forced must be an int tensor of shape {(batch_size, measures_to_generate, measure_seq_len)}, got "
-                                 f"{forced.dtype} {tuple(forced.shape)}")
-            V = int(self.vae_model.decoder.cfg.num_notes)
-            if forced.numel() and bool(((forced < -1) | (forced >= V)).any()):
-                raise ValueError(f"forced: token indices in [0, {V}), or -1 for a free tick")
-        if allowed is not None:
-            if train:
-                raise ValueError("token constraints are an inference call (train=False)")
-            allowed = torch.as_tensor(allowed)
-            if allowed.dtype != torch.bool or allowed.dim() != 4 or tuple(allowed.shape[:3]) != (batch_size, measures_to_generate, measure_seq_len):
-                raise ValueError(f"allowed must be bool of shape {(batch_size, measures_to_generate, measure_seq_len)} + (V,), got "
-                                 f"{allowed.dtype} {tuple(allowed.shape)}")
-            if not bool(allowed.any(-1).all()):
-                raise ValueError("allowed: a tick with nothing allowed")
-        if temperature is None and (top_k is not None or top_p is not None):
-            raise ValueError("top_k / top_p without a temperature")
-        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
-            raise ValueError(f"top_p {top_p!r} outside (0, 1]")
-        ops._top_k(top_k)                                          # (ValueError for a top_k that is no integer)
-        if temperature is None and uniforms is not None:
-            raise ValueError("uniforms without a temperature")
-        if temperature is not None:
-            if train:
-                raise ValueError("temperature sampling is an inference call (train=False)")
-            if not math.isfinite(float(temperature)):
-                raise ValueError(f"temperature {temperature!r} is not finite")
-            shape = (batch_size, measures_to_generate, measure_seq_len)
-            if uniforms is None:
-                uniforms = np.random.random_sample(shape)
-            uniforms = torch.as_tensor(uniforms, dtype=torch.float64).to(self.flat.device)
-            if tuple(uniforms.shape) != shape:
-                raise ValueError(f"uniforms of shape {tuple(uniforms.shape)}, expected {shape}")
+        shape = (batch_size, measures_to_generate, measure_seq_len)
+        d = Draw(temperature, uniforms, top_k, top_p, allowed, forced).check(shape, int(self.vae_model.decoder.cfg.num_notes), train, LATENT)
+        if d.temperature is not None:                              # (behind the checks: a rejected call leaves every stream alone)
+            u = np.random.random_sample(shape) if d.uniforms is None else d.uniforms
+            d.uniforms = torch.as_tensor(u, dtype=torch.float64).to(self.flat.device)
         n_past, n_future = past_context.size(1), future_context.size(1)
         n_target = target.size(1) if target is not None else 0        # inference: no target (latent_rnn_tester.py:231-236)
         # the teacher-forcing coin first (the reference draws it behind the context GRUs, :142-145: nothing else reads `random` in
@@ -303,8 +268,8 @@ class LatentRNN(Model):
         else:
             seed = zp[:, -1, :].unsqueeze(1)
         return self.forward_generation(comb_context, measures_to_generate, seed, measure_seq_len, teacher_forcing,
-                                       eps_ar=eps_ar, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p,
-                                       allowed=allowed, forced=forced)
+                                       eps_ar=eps_ar, temperature=d.temperature, uniforms=d.uniforms, top_k=d.top_k, top_p=d.top_p,
+                                       allowed=d.allowed, forced=d.forced)
 
     def forward_generation(self, context_vector, measures_to_gen, seed, measure_seq_len, teacher_forcing=False,
                            eps_ar=None, temperature=None, uniforms=None, top_k=None, top_p=None, allowed=None, forced=None):
@@ -312,6 +277,7 @@ class LatentRNN(Model):
         measures_to_gen, 24, V) / forced (B, measures_to_gen, 24): see forward"""
         if temperature is None and (top_k is not None or top_p is not None):
             raise ValueError("top_k / top_p without a temperature")
+        d = Draw(temperature, uniforms, top_k, top_p, allowed, forced)
         batch_size = context_vector.size(1)
         self.last_logp = None
         Hg = self.gen_hidden
@@ -325,10 +291,7 @@ class LatentRNN(Model):
                                   "generation_linear.weight", "generation_linear.bias")
             z_out = z2d.view(batch_size, measures_to_gen, -1)
             # rows ordered (b, measure): all measures in one call
-            w, s = self._decode(z2d, temperature, uniforms.reshape(batch_size * measures_to_gen, -1) if uniforms is not None else None,
-                                top_k, top_p, allowed.reshape((batch_size * measures_to_gen,) + tuple(allowed.shape[2:]))
-                                if allowed is not None else None,
-                                forced.reshape(batch_size * measures_to_gen, -1) if forced is not None else None)
+            w, s = self._decode(z2d, d.flat())
             lp = self.vae_model.decoder.last_logp
             self.last_logp = lp.view(batch_size, measures_to_gen, measure_seq_len) if lp is not None else None
             weights = w.view(batch_size, measures_to_gen, measure_seq_len, -1)
@@ -342,8 +305,7 @@ class LatentRNN(Model):
             gen_z = _LinearFn.apply(rnn_out.reshape(batch_size, -1), self.flat_for_autograd(), self,
                                     "generation_linear.weight", "generation_linear.bias")
             z_out.append(gen_z.view(batch_size, 1, -1))
-            w, s = self._decode(gen_z, temperature, uniforms[:, i] if uniforms is not None else None, top_k, top_p,
-                                allowed[:, i] if allowed is not None else None, forced[:, i] if forced is not None else None)
+            w, s = self._decode(gen_z, d.measure(i))
             logps.append(self.vae_model.decoder.last_logp)
             samples.append(s)
             weights.append(w.unsqueeze(1))

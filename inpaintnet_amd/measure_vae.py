@@ -7,7 +7,6 @@ torch.autograd.Function whose forward/backward are single calls into the C-ABI
 (include/inpaintnet_hip.h); parameter gradients are accumulated straight into
 the model's flat gradient arena (`model.grad`) by the backward kernels.
 """
-import math
 import os
 import random
 
@@ -17,6 +16,7 @@ import torch
 from torch import distributions
 
 from . import dp, ops
+from .draw import DECODER, Draw
 from .model import Model, default_device
 
 _mask_counter = [0]
@@ -67,13 +67,15 @@ class _EncoderFn(ops.TrackedFunction):
 
 class _DecoderFn(ops.TrackedFunction):
     @staticmethod
-    def forward(ctx, z, flat, dec, target, teacher_forced, mask_beat, mask_tick, multinomial_seed=0, temperature=None,
-                uniforms=None, top_k=None, top_p=None, logp=None, allowed=None, forced=None):
+    def forward(ctx, z, flat, dec, target, teacher_forced, mask_beat, mask_tick, multinomial_seed=0, draw=None, logp=None):
+        """draw: the sampled call's Draw (None: the argmax / teacher-forced / multinomial call); logp: its output, or None"""
         need = ops.outer_grad() and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        kw = {}
+        if draw is not None:
+            kw = draw.device(z.device)
+            kw.update(temperature=float(draw.temperature), uniforms=draw.uniforms.to(z.device).contiguous())
         weights, samples, ws = ops.decoder_fwd(dec.cfg, z.contiguous(), target, teacher_forced, flat, mask_beat,
-                                               mask_tick, save=need, multinomial_seed=multinomial_seed,
-                                               temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, logp=logp,
-                                               allowed=allowed, forced=forced)
+                                               mask_tick, save=need, multinomial_seed=multinomial_seed, logp=logp, **kw)
         ctx.dec, ctx.ws, ctx.mb, ctx.mt = dec, ws, mask_beat, mask_tick
         if getattr(dec, "keep_ws", False):         # test hook: lets a parity test read intermediates (ops.ws_field)
             dec.last_ws = ws
@@ -89,7 +91,7 @@ class _DecoderFn(ops.TrackedFunction):
         dec = ctx.dec
         if dweights is None:                            # nothing downstream depends on the weights
             ctx.ws = None
-            return (None,) * 15
+            return (None,) * 10
         weights, samples = ctx.saved_tensors
         grads = dec.owner.grad if dec.owner.trainable else None
         dz = ops.decoder_bwd(dec.cfg, dweights.contiguous(), weights, samples, dec.owner.flat, grads, ctx.mb, ctx.mt,
@@ -100,7 +102,7 @@ class _DecoderFn(ops.TrackedFunction):
             if dp.world_size() > 1:
                 # behind the decoder's leaf GEMMs on the side streams, without holding up the encoder's backward
                 dp.start_bucket(grads, dec.owner.decoder_arena_start, grads.numel(), join_side=True)
-        return (dz,) + (None,) * 14
+        return (dz,) + (None,) * 9
 
 
 class _ReparamFn(torch.autograd.Function):
@@ -286,41 +288,7 @@ class HierarchicalDecoder(torch.nn.Module):
         uniform.  Every tick forced scores a given measure, the first ticks forced continue a prefix.  ValueError for a wrong shape or
         dtype or a value outside [-1, V).  A forced call always leaves last_logp (B,24)."""
         T = self.cfg.beats * self.cfg.ticks_per_beat
-        if forced is not None:
-            if train:
-                raise ValueError("forced tokens are an inference call (train=False)")
-            if temperature is None:
-                raise ValueError("forced tokens need a temperature")
-            forced = torch.as_tensor(forced)
-            if forced.is_floating_point() or forced.is_complex() or forced.dtype == torch.bool or tuple(forced.shape) != (z.size(0), T):
-                raise ValueError(f"forced must be an int tensor of shape {(z.size(0), T)}, got {forced.dtype} {tuple(forced.shape)}")
-            if forced.numel() and bool(((forced < -1) | (forced >= self.cfg.num_notes)).any()):
-                raise ValueError(f"forced: token indices in [0, {self.cfg.num_notes}), or -1 for a free tick")
-            forced = forced.to(torch.int32)
-        if allowed is not None:
-            if train:
-                raise ValueError("token constraints are an inference call (train=False)")
-            allowed = torch.as_tensor(allowed)
-            if allowed.dtype != torch.bool or tuple(allowed.shape) != (z.size(0), T, self.cfg.num_notes):
-                raise ValueError(f"allowed must be bool of shape {(z.size(0), T, self.cfg.num_notes)}, got {allowed.dtype} "
-                                 f"{tuple(allowed.shape)}")
-            allowed = ops.pack_allowed(allowed)                    # (ValueError for a tick with nothing allowed)
-        if temperature is None and (top_k is not None or top_p is not None):
-            raise ValueError("top_k / top_p without a temperature")
-        if top_p is not None and not (0.0 < float(top_p) <= 1.0):
-            raise ValueError(f"top_p {top_p!r} outside (0, 1]")
-        ops._top_k(top_k)                                          # (ValueError for a top_k that is no integer)
-        if uniforms is not None and temperature is None:
-            raise ValueError("uniforms without a temperature")
-        if temperature is not None:
-            if train:
-                raise ValueError("temperature sampling is an inference call (train=False)")
-            if not math.isfinite(float(temperature)):
-                raise ValueError(f"temperature {temperature!r} is not finite")
-            if uniforms is not None:
-                uniforms = torch.as_tensor(uniforms, dtype=torch.float64)
-                if tuple(uniforms.shape) != (z.size(0), T):
-                    raise ValueError(f"uniforms of shape {tuple(uniforms.shape)}, expected {(z.size(0), T)}")
+        d = Draw(temperature, uniforms, top_k, top_p, allowed, forced).check((z.size(0), T), int(self.cfg.num_notes), train, DECODER)
         self.last_logp = None
         if teacher_forced is None:
             if self.use_teacher_forcing and train:
@@ -349,24 +317,19 @@ class HierarchicalDecoder(torch.nn.Module):
                                   _next_mask_offset(self.cfg.beats * batch_size * H), dev)
             mt = ops.dropout_mask((T, batch_size, H), self.dropout, _DropState.seed,
                                   _next_mask_offset(T * batch_size * H), dev)
-        if allowed is not None and temperature is None and not teacher_forced:
+        if d.allowed is not None and d.temperature is None and not teacher_forced:
             # constraints without a temperature: top_k = 1 keeps the top-ranked allowed token whatever the uniform (DESIGN.md section 11's
             # top_k = 1 equality, over the allowed tokens)
             u = torch.zeros(batch_size, T, dtype=torch.float64, device=z.device)
-            return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, 1.0, u, 1, None, None,
-                                   allowed.to(z.device).contiguous())
-        if temperature is not None and not teacher_forced:
-            if uniforms is None:
-                uniforms = torch.from_numpy(np.random.random_sample((batch_size, T)))
-            u = uniforms.to(z.device).contiguous()
-            if top_k is not None or top_p is not None or allowed is not None or forced is not None:
-                logp = torch.empty(batch_size, T, dtype=torch.float32, device=z.device)
-                out = _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u,
-                                      top_k, top_p, logp, allowed.to(z.device).contiguous() if allowed is not None else None,
-                                      *((forced.to(z.device).contiguous(),) if forced is not None else ()))
-                self.last_logp = logp
-                return out
-            return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, float(temperature), u)
+            return _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0,
+                                   Draw(1.0, u, 1, None, d.allowed, None, d.words))
+        if d.temperature is not None and not teacher_forced:
+            if d.uniforms is None:
+                d.uniforms = torch.from_numpy(np.random.random_sample((batch_size, T)))
+            logp = torch.empty(batch_size, T, dtype=torch.float32, device=z.device) if d.scored() else None
+            out = _DecoderFn.call(z, self.owner.flat_for_autograd(), self, None, False, mb, mt, 0, d, logp)
+            self.last_logp = logp
+            return out
         seed = 0
         if self.sampling == 'multinomial' and not teacher_forced:
             # one counter-based stream per call, derived from the dropout seed (set_dropout_seed) and the call counter

@@ -167,19 +167,21 @@ def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
                 top_k=None, top_p=None, want_logp=False, want_logits=False, allowed=None, forced=None):
     """inet_arnn_sample: AnticipationRNN's temperature-sampled generation for R independent rows.  oc [R,L,Hc] (the rows' constraint
     outputs; strided rows and ticks allowed); uniforms [R,L] float64 (one np.random.random_sample() double per tick; a host array is
-    copied to the device); hc_init [R,2,2,H] (layer, h|c) or None (zeros).  Token t of row r is the first v whose softmax(temperature *
-    logits) prefix exceeds uniforms[r, t] (np.random.choice's rule) -> tokens [R,L] int64 on the device, no host round trip.
-    With one of top_k / top_p / want_logp / want_logits: inet_arnn_sample_ex -- the draw behind csrc/sample.h's top-k / nucleus
-    truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off, else in (0, 1)) -> (tokens, logp [R,L] float32 or None: the drawn
-    tokens' log-probabilities under the truncated distribution, NaN where a tick took the argmax rule; logits [R,L,V] float32 or None:
-    the note head's output every tick drew from).
-    allowed: inet_arnn_sample_cx -- pack_allowed()'s words [R,L,ceil(V/64)], int64, contiguous, on the device: the tokens each (row,
-    tick) may return, applied inside the launch in front of the truncation (csrc/sample.h).  A constrained call is
-    a truncating one: allowed alone runs with (top_k, top_p) = (0, 1.0), and the return is the triple above.
-    forced: inet_arnn_sample_fx -- int32 [R,L], contiguous, on the device, -1 for a free tick: a value in [0, V) is that tick's token,
-    returned and fed back whatever the mask, the truncation and the uniform hold, with its log-probability under the masked and
-    truncated distribution (-inf for a banned or truncated token; csrc/sample.h).  forced alone runs with (top_k,
-    top_p) = (0, 1.0) and returns logp."""
+    copied to the device); hc_init [R,2,2,H] (layer, h|c) or None (zeros).  Token t of row r is the first v whose
+    softmax(temperature * logits) prefix exceeds uniforms[r, t] (np.random.choice's rule) -> tokens [R,L] int64 on the device, no
+    host round trip.
+    Every call goes through inet_arnn_sample_fx, the widest entry, with nulls for what it does not ask (the library picks the
+    kernels by what it is handed: a plain call runs the kernels of inet_arnn_sample).  With one of top_k / top_p / want_logp /
+    want_logits: the draw behind csrc/sample.h's top-k / nucleus truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off,
+    else in (0, 1)) -> (tokens, logp [R,L] float32 or None: the drawn tokens' log-probabilities under the truncated distribution,
+    NaN where a tick took the argmax rule; logits [R,L,V] float32 or None: the note head's output every tick drew from).
+    allowed: pack_allowed()'s words [R,L,ceil(V/64)], int64, contiguous, on the device: the tokens each (row, tick) may return,
+    applied inside the launch in front of the truncation (csrc/sample.h).  A constrained call is a truncating
+    one: allowed alone runs with (top_k, top_p) = (0, 1.0), and the return is the triple above.
+    forced: int32 [R,L], contiguous, on the device, -1 for a free tick: a value in [0, V) is that tick's token, returned and fed
+    back whatever the mask, the truncation and the uniform hold, with its log-probability under the masked and truncated
+    distribution (-inf for a banned or truncated token; csrc/sample.h).  forced alone runs with (top_k, top_p)
+    = (0, 1.0) and returns logp."""
     ex = top_k is not None or top_p is not None or want_logp or want_logits or allowed is not None or forced is not None
     k = _top_k(top_k)
     if top_p is not None and not (0.0 < float(top_p) <= 1.0):
@@ -208,26 +210,15 @@ def arnn_sample(emb, oc, W_ih0, b_ih0, W_hh0, b_hh0, W_ih1, b_ih1, W_hh1, b_hh1,
         raise ValueError("inet_arnn_sample_ws_floats: invalid arguments")
     ws = torch.empty(nws, dtype=torch.float32, device=emb.device)
     tokens = torch.empty(R, L, dtype=torch.int64, device=emb.device)
-    if ex:
-        logp = torch.empty(R, L, dtype=torch.float32, device=emb.device) if want_logp else None
-        logits = torch.empty(R, L, V, dtype=torch.float32, device=emb.device) if want_logits else None
-        args = (R, L, E, Hc, H, U, V, ptr(_f32c(emb)), ptr(oc), oc.stride(1), oc.stride(0), *net, float(temperature), ptr(u),
-                ptr(_f32c(hc_init) if hc_init is not None else None), ptr(tokens), ptr(ws), nws, k,
-                1.0 if top_p is None else float(top_p), ptr(logp), ptr(logits))
-        if forced is not None:
-            check(_lib.lib().inet_arnn_sample_fx(*args, ptr(allowed), ptr(forced), stream_ptr()), "inet_arnn_sample_fx")
-        elif allowed is not None:
-            check(_lib.lib().inet_arnn_sample_cx(*args, ptr(allowed), stream_ptr()), "inet_arnn_sample_cx")
-        else:
-            check(_lib.lib().inet_arnn_sample_ex(*args, stream_ptr()), "inet_arnn_sample_ex")
-        _hold(ws, oc, u, hc_init, allowed, forced)
-        return tokens, logp, logits
-    check(_lib.lib().inet_arnn_sample(R, L, E, Hc, H, U, V, ptr(_f32c(emb)), ptr(oc), oc.stride(1), oc.stride(0), *net,
-                                      float(temperature), ptr(u),
-                                      ptr(_f32c(hc_init) if hc_init is not None else None), ptr(tokens), ptr(ws), nws,
-                                      stream_ptr()), "inet_arnn_sample")
-    _hold(ws, oc, u, hc_init)
-    return tokens
+    logp = torch.empty(R, L, dtype=torch.float32, device=emb.device) if want_logp else None
+    logits = torch.empty(R, L, V, dtype=torch.float32, device=emb.device) if want_logits else None
+    # one entry, the widest, with nulls for what the call does not ask: the library picks the kernels by what it is handed
+    check(_lib.lib().inet_arnn_sample_fx(R, L, E, Hc, H, U, V, ptr(_f32c(emb)), ptr(oc), oc.stride(1), oc.stride(0), *net,
+                                         float(temperature), ptr(u), ptr(_f32c(hc_init) if hc_init is not None else None), ptr(tokens),
+                                         ptr(ws), nws, k, 1.0 if top_p is None else float(top_p), ptr(logp), ptr(logits), ptr(allowed),
+                                         ptr(forced), stream_ptr()), "inet_arnn_sample_fx")
+    _hold(ws, oc, u, hc_init, allowed, forced)
+    return (tokens, logp, logits) if ex else tokens
 
 
 _twin = {}
@@ -273,15 +264,16 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
                 forced=None):
     """z [B,Z] -> weights [B,T,V], samples [B,1,T] int64, ws.  multinomial_seed != 0: the fed-back tokens are drawn from
     softmax(weights) (decoder.py:506-509) instead of the argmax.  temperature + uniforms ([B,T] float64 on the device, one uniform
-    per row and tick): inet_vae_decoder_sample -- a free-running call whose tokens are drawn from softmax(temperature * weights) by
-    csrc/sample.h's rule.  top_k / top_p / logp (with a temperature only): inet_vae_decoder_sample_ex -- the draw behind sample.h's
-    top-k / nucleus truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off, else in (0, 1)), and logp, a contiguous float32
-    [B,T] device tensor, receives the drawn tokens' log-probabilities under the truncated distribution (NaN where a tick took the argmax).
-    allowed (with a temperature only): inet_vae_decoder_sample_cx -- pack_allowed()'s words [B,T,ceil(V/64)], int64, contiguous, on the
-    device: the tokens every (row, tick) may return, applied in front of the truncation inside the launch (csrc/sample.h's rule).
-    forced (with a temperature only): inet_vae_decoder_sample_fx -- int32 [B,T], contiguous, on the device: the token every (row, tick)
-    returns and feeds back, -1 (any value outside [0, V)) for a free tick; its logp is taken under the masked and truncated
-    distribution (-inf for a banned or truncated token), with or without `allowed`."""
+    per row and tick): inet_vae_decoder_sample_fx, the widest entry, with nulls for what the call does not ask -- a free-running
+    call whose tokens are drawn from softmax(temperature * weights) by csrc/sample.h's rule.  top_k / top_p / logp (with a
+    temperature only): the draw behind sample.h's top-k / nucleus truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off,
+    else in (0, 1)), and logp, a contiguous float32 [B,T] device tensor, receives the drawn tokens' log-probabilities under the
+    truncated distribution (NaN where a tick took the argmax).
+    allowed (with a temperature only): pack_allowed()'s words [B,T,ceil(V/64)], int64, contiguous, on the device: the tokens every
+    (row, tick) may return, applied in front of the truncation inside the launch (csrc/sample.h's rule).
+    forced (with a temperature only): int32 [B,T], contiguous, on the device: the token every (row, tick) returns and feeds back, -1
+    (any value outside [0, V)) for a free tick; its logp is taken under the masked and truncated distribution (-inf for a banned or
+    truncated token), with or without `allowed`."""
     if (temperature is None) != (uniforms is None):
         raise ValueError("decoder_fwd: temperature and uniforms go together")
     if temperature is None and (top_k is not None or top_p is not None or logp is not None or allowed is not None or forced is not None):
@@ -312,34 +304,13 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
         ws = decoder_ws(cfg, B, save, z.device)
     weights = torch.empty(B, T, cfg.num_notes, dtype=torch.float32, device=z.device)
     samples = torch.empty(B, 1, T, dtype=torch.int64, device=z.device)
-    if temperature is not None and forced is not None:
+    if temperature is not None:                      # one entry, the widest, with nulls for what the call does not ask
         check(_lib.lib().inet_vae_decoder_sample_fx(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
                                                     ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
                                                     _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(logp), ptr(allowed),
                                                     ptr(forced), stream_ptr()),
               "inet_vae_decoder_sample_fx")
         _hold(uniforms, logp, allowed, forced)
-        return weights, samples, ws
-    if temperature is not None and allowed is not None:
-        check(_lib.lib().inet_vae_decoder_sample_cx(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
-                                                    ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
-                                                    _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(logp), ptr(allowed),
-                                                    stream_ptr()),
-              "inet_vae_decoder_sample_cx")
-        _hold(uniforms, logp, allowed)
-        return weights, samples, ws
-    if temperature is not None and (top_k is not None or top_p is not None or logp is not None):
-        check(_lib.lib().inet_vae_decoder_sample_ex(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
-                                                    ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
-                                                    _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(logp), stream_ptr()),
-              "inet_vae_decoder_sample_ex")
-        _hold(uniforms, logp)
-        return weights, samples, ws
-    if temperature is not None:
-        check(_lib.lib().inet_vae_decoder_sample(C.byref(cfg), B, ptr(z), ptr(params), ptr(mask_beat), ptr(mask_tick), ptr(weights),
-                                                 ptr(samples), ptr(ws), ws.numel() * 4, int(save), float(temperature), ptr(uniforms),
-                                                 stream_ptr()), "inet_vae_decoder_sample")
-        _hold(uniforms)
         return weights, samples, ws
     check(_lib.lib().inet_vae_decoder_fwd(C.byref(cfg), B, ptr(z), ptr(target), int(bool(teacher_forced)), ptr(params),
                                           ptr(mask_beat), ptr(mask_tick), ptr(weights), ptr(samples), ptr(ws),
@@ -437,12 +408,12 @@ def pack_allowed(allowed):
 
 
 def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, want_logp=True, allowed=None, forced=None):
-    """inet_sample_truncated: sample_temperature() behind csrc/sample.h's top-k / nucleus truncation (top_k None, <= 0 or >= V: off;
-    top_p None or 1: off, else in (0, 1)) -> (tokens [rows] int64, logp [rows] float32: the drawn tokens' log-probabilities under
-    the truncated distribution, NaN where a row took the argmax rule; None with want_logp=False).  allowed: inet_sample_constrained --
-    pack_allowed()'s words [rows, ceil(V / 64)] (int64 on the device, any row stride): the tokens each row may return.  forced: inet_sample_forced -- int32 [rows] on the
-    device: the token each row returns whatever its mask and logits hold, -1 for a free row; its logp is taken under the masked and
-    truncated distribution."""
+    """inet_sample_forced with nulls for what is not given (inet_sample_truncated's kernel at the least): sample_temperature() behind
+    csrc/sample.h's top-k / nucleus truncation (top_k None, <= 0 or >= V: off; top_p None or 1: off, else in (0, 1)) -> (tokens
+    [rows] int64, logp [rows] float32: the drawn tokens' log-probabilities under the truncated distribution, NaN where a row took
+    the argmax rule; None with want_logp=False).  allowed: pack_allowed()'s words [rows, ceil(V / 64)] (int64 on the device, any row
+    stride): the tokens each row may return.  forced: int32 [rows] on the device: the token each row returns whatever its mask and
+    logits hold, -1 for a free row; its logp is taken under the masked and truncated distribution."""
     rows, V = weights2d.shape
     assert weights2d.stride(1) == 1 and weights2d.dtype == torch.float32
     assert uniforms.is_cuda and uniforms.dtype == torch.float64 and tuple(uniforms.shape) == (rows,)
@@ -451,22 +422,12 @@ def sample_truncated(weights2d, temperature, uniforms, top_k=None, top_p=None, w
     if allowed is not None:
         if not (allowed.is_cuda and allowed.dtype == torch.int64 and tuple(allowed.shape) == (rows, (V + 63) // 64) and allowed.stride(1) == 1):
             raise ValueError(f"sample_truncated: allowed must be pack_allowed()'s int64 device tensor of shape {(rows, (V + 63) // 64)}")
-    if forced is not None:
-        if not (forced.is_cuda and forced.dtype == torch.int32 and tuple(forced.shape) == (rows,)):
-            raise ValueError(f"sample_truncated: forced must be an int32 device tensor of shape {(rows,)}")
-        check(_lib.lib().inet_sample_forced(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
-                                            uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
-                                            ptr(logp), 1, ptr(allowed), allowed.stride(0) if allowed is not None else 0, ptr(forced),
-                                            forced.stride(0), stream_ptr()), "inet_sample_forced")
-        return out, logp
-    if allowed is not None:
-        check(_lib.lib().inet_sample_constrained(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
-                                                 uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
-                                                 ptr(logp), 1, ptr(allowed), allowed.stride(0), stream_ptr()), "inet_sample_constrained")
-        return out, logp
-    check(_lib.lib().inet_sample_truncated(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
-                                           uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
-                                           ptr(logp), 1, stream_ptr()), "inet_sample_truncated")
+    if forced is not None and not (forced.is_cuda and forced.dtype == torch.int32 and tuple(forced.shape) == (rows,)):
+        raise ValueError(f"sample_truncated: forced must be an int32 device tensor of shape {(rows,)}")
+    check(_lib.lib().inet_sample_forced(ptr(weights2d), weights2d.stride(0), rows, V, float(temperature), ptr(uniforms),
+                                        uniforms.stride(0), _top_k(top_k), 1.0 if top_p is None else float(top_p), ptr(out), 1,
+                                        ptr(logp), 1, ptr(allowed), allowed.stride(0) if allowed is not None else 0, ptr(forced),
+                                        forced.stride(0) if forced is not None else 0, stream_ptr()), "inet_sample_forced")
     return out, logp
 
 
