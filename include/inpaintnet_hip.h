@@ -230,6 +230,26 @@ int inet_reparam_kl(const float* mu, const float* logsigma, const float* eps, fl
 int inet_latent_bwd(const float* dz, const float* mu, const float* logsigma, const float* eps, float kscale,
                     const float* kscale_dev, float* dmu, float* dlogsigma, int64_t n, void* stream);
 
+/* The KL term with a floor ("free bits").  mu, logsigma [rows, Z] contiguous; KL[b,d] = 0.5(s^2 + mu^2 - 1) - ls.
+ * per = 0 ('measure'): part[b] = sum_d KL[b,d], rows parts, thr = free_nats.  per = 1 ('dim'): part[d] = sum_b KL[b,d], Z parts,
+ * thr = (float)(rows * free_nats).  kept = !(part <= thr): a tie is floored, a NaN part is kept.  Writes z = mu + eps*exp(logsigma)
+ * (z nullable; eps nullable, read as 0), parts[] and keep[] (1.0f / 0.0f); *kl_sum += sum(kept ? part : thr); *kl_raw += sum(part).
+ * Every sum -- the parts and the two scalars -- is added in a fixed order, without float atomics: the same inputs give the same parts,
+ * keep bits and scalars in every run, and with every part kept the amounts added onto kl_sum and kl_raw are the same bits.  Two
+ * launches: the elementwise pass, then one finishing workgroup (the floor and the scalars; for per = 1 also the column sums, from the
+ * first launch's per-workgroup partials in `ws`: inet_reparam_kl_fb_ws_bytes(rows, Z, per) bytes of device memory, nothing to zero;
+ * 0 for per = 0, when ws may be null).  16-byte loads when Z % 4 == 0 and mu, logsigma, eps and z are 16-byte aligned.  -1: a null required pointer, rows <= 0, Z <= 0, free_nats negative, NaN or inf, per outside {0, 1},
+ * ws_bytes too small -- before any launch. */
+int64_t inet_reparam_kl_fb_ws_bytes(int64_t rows, int Z, int per);
+int inet_reparam_kl_fb(const float* mu, const float* logsigma, const float* eps, float* z, int64_t rows, int Z, float free_nats,
+                       int per, float* parts, float* keep, float* kl_sum, float* kl_raw, void* ws, int64_t ws_bytes, void* stream);
+/* inet_latent_bwd with the keep vector inet_reparam_kl_fb left: the KL gradient reaches an element only where its part (row for
+ * per = 0, column for per = 1) is kept -- k or 0 is SELECTED per element: dmu = dz + kk*mu; dlogsigma = dz*eps*sigma + kk*(sigma^2-1).
+ * With every part kept the results are inet_latent_bwd's bit for bit; a floored part hands dz on bit for bit. */
+int inet_latent_bwd_fb(const float* dz, const float* mu, const float* logsigma, const float* eps, float kscale,
+                       const float* kscale_dev, const float* keep, int per, float* dmu, float* dlogsigma, int64_t rows, int Z,
+                       void* stream);
+
 /* rows of V (post-ReLU) logits -> out[row*stride] ~ Multinomial(softmax(row))  (decoder.py:506-509): inverse-CDF draw with
  * one counter-based uniform per row keyed (seed, offset + row): row r of a call at `offset` is row 0 of a call at offset + r.
  * The token drawn always has mass (exp(w - max) > 0 in float32): where rounding leaves every prefix sum at or below

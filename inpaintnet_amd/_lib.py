@@ -109,6 +109,9 @@ _SIGNATURES = {
     "inet_sample_constrained": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _I, C.c_double, _P, _L, _P, _L, _P, _L, _P]),
     "inet_sample_forced": (C.c_int, [_P, _L, _I, _I, _F, _P, _L, _I, C.c_double, _P, _L, _P, _L, _P, _L, _P, _L, _P]),
     "inet_latent_bwd": (C.c_int, [_P, _P, _P, _P, _F, _P, _P, _P, _L, _P]),
+    "inet_reparam_kl_fb_ws_bytes": (_L, [_L, _I, _I]),
+    "inet_reparam_kl_fb": (C.c_int, [_P, _P, _P, _P, _L, _I, _F, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "inet_latent_bwd_fb": (C.c_int, [_P, _P, _P, _P, _F, _P, _P, _I, _P, _P, _L, _I, _P]),
     "inet_adam_step": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P]),
     "inet_adam_step_ex": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _I, _F, _P, _P, _P]),
     "inet_sqnorm_parts": (C.c_int, []),

@@ -238,6 +238,19 @@ int inet_latent_bwd(const float* dz, const float* mu, const float* logsigma, con
     if (!mu || !logsigma || !dmu || !dlogsigma || n <= 0) return -1;
     return pw_latent_bwd(dz, mu, logsigma, eps, kscale, kscale_dev, dmu, dlogsigma, n, (hipStream_t)stream);
 }
+int64_t inet_reparam_kl_fb_ws_bytes(int64_t rows, int Z, int per) { return pw_reparam_kl_fb_ws_bytes(rows, Z, per); }
+int inet_reparam_kl_fb(const float* mu, const float* logsigma, const float* eps, float* z, int64_t rows, int Z, float free_nats,
+                       int per, float* parts, float* keep, float* kl_sum, float* kl_raw, void* ws, int64_t ws_bytes, void* stream) {
+    if (!mu || !logsigma || !parts || !keep || !kl_sum || !kl_raw || rows <= 0 || Z <= 0) return -1;
+    if (!(free_nats >= 0.f) || !(free_nats <= 3.402823466e38f) || (per != 0 && per != 1)) return -1;       // negative, NaN, inf
+    return pw_reparam_kl_fb(mu, logsigma, eps, z, rows, Z, free_nats, per, parts, keep, kl_sum, kl_raw, ws, ws_bytes, (hipStream_t)stream);
+}
+int inet_latent_bwd_fb(const float* dz, const float* mu, const float* logsigma, const float* eps, float kscale,
+                       const float* kscale_dev, const float* keep, int per, float* dmu, float* dlogsigma, int64_t rows, int Z,
+                       void* stream) {
+    if (!mu || !logsigma || !keep || !dmu || !dlogsigma || rows <= 0 || Z <= 0 || (per != 0 && per != 1)) return -1;
+    return pw_latent_bwd_fb(dz, mu, logsigma, eps, kscale, kscale_dev, keep, per, dmu, dlogsigma, rows, Z, (hipStream_t)stream);
+}
 // the four entry points of the optimizer step: one check, one launcher (pw_adam_step)
 static int adam_step_checked(const PwAdamStep& a, void* stream) {
     if (!a.p || !a.g || !a.m || !a.v || a.n <= 0 || a.step < 1) return -1;

@@ -29,6 +29,14 @@ int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long*
 namespace sample { struct Request; }
 int pw_sample(const float* W, long ld_w, int rows, int V, long long* out, long stride, const sample::Request& r, int floor_level,
               hipStream_t s);
+// The KL term with a floor (free bits; the rule: pointwise.hip).  per 0 = 'measure' (a part per row, threshold
+// free_nats), 1 = 'dim' (a part per column, threshold rows * free_nats; through a workspace of pw_reparam_kl_fb_ws_bytes).  Two launches.
+// parts / keep: rows or Z floats; kl_sum (floored) and kl_raw (plain) are added onto.  z and eps nullable.
+long pw_reparam_kl_fb_ws_bytes(long rows, int Z, int per);
+int pw_reparam_kl_fb(const float* mu, const float* ls, const float* eps, float* z, long rows, int Z, float free_nats, int per,
+                     float* parts, float* keep, float* kl_sum, float* kl_raw, void* ws, long ws_bytes, hipStream_t s);
+int pw_latent_bwd_fb(const float* dz, const float* mu, const float* ls, const float* eps, float kscale, const float* kdev,
+                     const float* keep, int per, float* dmu, float* dls, long rows, int Z, hipStream_t s);
 // The norm of the gradient arena: partials[pw_sqnorm_parts()] = the f64 sums of squares of the fixed grid's shares of g (every entry
 // written: nothing to zero in front), what the optimizer step takes as `partials`.
 int pw_sqnorm_parts();

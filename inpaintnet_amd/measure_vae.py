@@ -129,17 +129,51 @@ class _ReparamFn(torch.autograd.Function):
         return dmu, dls, None, None
 
 
+class _ReparamFbFn(torch.autograd.Function):
+    """_ReparamFn with the KL term summed into parts and floored ("free bits"): the forward kernel leaves the
+    floored sum, the plain sum, the parts and their keep vector; the backward hands the KL gradient to the elements of kept parts
+    only (ops.latent_bwd_fb with the saved keep vector)."""
+
+    @staticmethod
+    def forward(ctx, mu, ls, eps, free_nats, per, stats=None):
+        if stats is None:
+            stats = torch.zeros(2, dtype=torch.float32, device=mu.device)
+        z, parts, keep, _, _ = ops.reparam_kl_fb(mu, ls, eps, free_nats, per, kl_sum=stats[0:1], kl_raw=stats[1:2])
+        ctx.save_for_backward(mu, ls, eps, keep)
+        ctx.per = per
+        kl, raw = stats[0], stats[1]
+        ctx.mark_non_differentiable(raw, parts, keep)
+        ctx.set_materialize_grads(False)
+        return z, kl, raw, parts, keep
+
+    @staticmethod
+    def backward(ctx, dz, dkl, _draw, _dparts, _dkeep):
+        mu, ls, eps, keep = ctx.saved_tensors
+        if dz is not None:
+            dz = dz.contiguous()
+        if dkl is not None:
+            dkl = dkl.reshape(1).contiguous()
+        dmu, dls = ops.latent_bwd_fb(dz, mu, ls, eps, 1.0 if dkl is not None else 0.0, keep, ctx.per, kscale_dev=dkl)
+        return dmu, dls, None, None, None, None
+
+
 class NormalLogScale(distributions.Normal):
     """torch Normal whose log-scale (the encoder's actual output) is kept alongside, so the KL kernel needs no log()
     round trip.  `scale` (= exp(log_scale), encoder.py:133) is computed the first time something reads it: the training
     step never does.  rsample()/sample() draw eps with torch's device generator and combine on the GPU with the
-    reparameterisation kernel, which also leaves the KL sum in `kl_sum`."""
+    reparameterisation kernel, which also leaves the KL sum in `kl_sum`.
+
+    rsample(free_bits=(free_nats, per)) floors the KL term: per 'measure' sums KL[b, d] over d and floors
+    every measure's sum at free_nats; per 'dim' sums over the rows of THIS call -- under data parallelism the rank's own shard, as
+    batch statistics would be, no collective -- and floors every latent dimension's sum at rows * free_nats.  It leaves `kl_sum` (the
+    floored sum), `kl_raw` (the plain sum), `kl_parts` and `kl_keep` (1.0 = the part is above its floor and passes its gradient)."""
 
     def __init__(self, loc, log_scale, owner=None):
         self.loc = loc
         self.log_scale = log_scale
         self._scale = None
         self.kl_sum = None
+        self.kl_raw = self.kl_parts = self.kl_keep = None      # only rsample(free_bits=...) fills these
         self._owner = owner                      # the model whose arena tail holds the per-step accumulators (or None)
         distributions.Distribution.__init__(self, loc.size(), validate_args=False)
 
@@ -153,11 +187,18 @@ class NormalLogScale(distributions.Normal):
     def scale(self, value):
         self._scale = value
 
-    def rsample(self, sample_shape=torch.Size(), eps=None):
+    def rsample(self, sample_shape=torch.Size(), eps=None, free_bits=None):
         if len(sample_shape) != 0:
             return super().rsample(sample_shape)
         if eps is None:
             eps = torch.randn_like(self.loc)
+        if free_bits is not None:
+            free_nats, per = free_bits
+            stats = self._owner.take_stats(2) if self._owner is not None else None
+            z, self.kl_sum, self.kl_raw, self.kl_parts, self.kl_keep = _ReparamFbFn.apply(self.loc, self.log_scale, eps,
+                                                                                          float(free_nats), per, stats)
+            self.last_eps = eps
+            return z
         kl = self._owner.take_stats(1) if self._owner is not None else None
         z, self.kl_sum = _ReparamFn.apply(self.loc, self.log_scale, eps, kl)
         self.last_eps = eps
@@ -361,6 +402,7 @@ class MeasureVAE(Model):
         self.has_metadata = has_metadata
         self.num_notes = len(dataset.note2index_dicts[0])
         self.trainable = True
+        self.free_bits = None                    # (free_nats, 'measure' | 'dim'): the KL floor of TRAINING passes (VAETrainer sets it)
         self.cfg = ops.vae_config(self.num_notes, note_embedding_dim, encoder_hidden_size, latent_space_dim,
                                   decoder_hidden_size, self.num_beats_per_measure, self.num_ticks_per_beat)
         table, total = ops.vae_param_table(self.cfg)
@@ -427,7 +469,12 @@ class MeasureVAE(Model):
             eps, z_prior = draws[0], draws[1]
         else:
             z_prior = torch.randn_like(z_dist.loc)
-        z_tilde = z_dist.rsample(eps=eps)
+        # the KL floor is a training device: validation, the testers and forward_test always take the plain KL, so that their
+        # losses stay comparable across epochs and with the reference
+        if train and self.free_bits is not None:
+            z_tilde = z_dist.rsample(eps=eps, free_bits=self.free_bits)
+        else:
+            z_tilde = z_dist.rsample(eps=eps)
         prior_dist = self._standard_normal(z_dist.loc)
         weights, samples = self.decoder(z=z_tilde, score_tensor=measure_score_tensor, train=train,
                                         teacher_forced=teacher_forced, masks=dec_masks)

@@ -451,6 +451,58 @@ def latent_bwd(dz, mu, ls, eps, kscale, kscale_dev=None):
     return dmu, dls
 
 
+FB_PER = {"measure": 0, "dim": 1}
+
+
+def _fb_per(per):
+    if per not in FB_PER:
+        raise ValueError(f"free_nats_per must be 'measure' or 'dim', got {per!r}")
+    return FB_PER[per]
+
+
+def reparam_kl_fb(mu, ls, eps, free_nats, per, kl_sum=None, kl_raw=None, want_z=True):
+    """The reparameterisation with the KL term summed into parts and floored at free_nats (include/inpaintnet_hip.h
+    inet_reparam_kl_fb).  mu, ls [rows, Z]; eps the same shape or None (reads as 0); per 'measure' (a part per
+    row, threshold free_nats) or 'dim' (a part per column, threshold rows * free_nats).  kl_sum / kl_raw: one-element device tensors
+    the floored / the plain sum is ADDED onto (None: new zeroed ones).  -> (z or None, parts, keep, kl_sum, kl_raw); keep holds 1.0
+    where a part is kept, !(part <= threshold), else 0.0."""
+    _f32c(mu); _f32c(ls)
+    if mu.dim() != 2 or ls.shape != mu.shape or (eps is not None and _f32c(eps).shape != mu.shape):
+        raise ValueError("reparam_kl_fb: mu, logsigma (and eps) must be [rows, Z] tensors of one shape")
+    rows, Z = mu.shape
+    p = _fb_per(per)
+    dev = mu.device
+    z = torch.empty_like(mu) if want_z else None
+    parts = torch.empty(Z if p else rows, dtype=torch.float32, device=dev)
+    keep = torch.empty_like(parts)
+    if kl_sum is None:
+        kl_sum = torch.zeros(1, dtype=torch.float32, device=dev)
+    if kl_raw is None:
+        kl_raw = torch.zeros(1, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    nbytes = L.inet_reparam_kl_fb_ws_bytes(rows, Z, p)
+    ws = _ws(nbytes, dev) if nbytes > 0 else None
+    check(L.inet_reparam_kl_fb(ptr(mu), ptr(ls), ptr(eps), ptr(z), rows, Z, float(free_nats), p, ptr(parts), ptr(keep),
+                               ptr(_f32c(kl_sum)), ptr(_f32c(kl_raw)), ptr(ws), 0 if ws is None else ws.numel() * 4, stream_ptr()),
+          "inet_reparam_kl_fb")
+    return z, parts, keep, kl_sum, kl_raw
+
+
+def latent_bwd_fb(dz, mu, ls, eps, kscale, keep, per, kscale_dev=None):
+    """latent_bwd with reparam_kl_fb's keep vector: the KL gradient, kscale * kscale_dev[0], reaches the elements of kept parts only."""
+    _f32c(mu); _f32c(ls); _f32c(keep)
+    rows, Z = mu.shape
+    p = _fb_per(per)
+    if keep.numel() != (Z if p else rows):
+        raise ValueError(f"latent_bwd_fb: keep must hold {Z if p else rows} elements for per={per!r}")
+    dmu = torch.empty_like(mu)
+    dls = torch.empty_like(mu)
+    _hold(kscale_dev)
+    check(_lib.lib().inet_latent_bwd_fb(ptr(dz), ptr(mu), ptr(ls), ptr(eps), float(kscale), ptr(kscale_dev), ptr(keep), p, ptr(dmu),
+                                        ptr(dls), rows, Z, stream_ptr()), "inet_latent_bwd_fb")
+    return dmu, dls
+
+
 def _adam_arenas(p, g, m, v, partials, report):
     """What every optimizer entry point asks of its tensors: four float32 arenas of one size; `partials` (where given) what
     grad_sqnorm left; `report` (where given) pinned int32 words, four of them, eight with partials.  Returns the size."""

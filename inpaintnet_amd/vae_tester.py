@@ -51,6 +51,31 @@ class VAETester(object):
         fn = getattr(self.dataset, "tensor_to_score", None)
         return (fn(tensor_score.cpu()) if fn is not None else None), tensor_score
 
+    def kl_per_dim(self, data_loader):
+        """(Z,) float64 on the device: the mean over all measures of the loader of KL[., d] = 0.5(sigma^2 + mu^2 - 1) - log sigma, the
+        plain KL of the encoder's posterior against N(0, 1) per latent dimension -- which dimensions the model uses (DESIGN.md section
+        22).  The column sums come from the 'dim' forward kernel with free_nats = 0, accumulated over the batches in float64."""
+        total, count = None, 0
+        n_bars = getattr(self.dataset, "n_bars", None)
+        for score_tensor, _ in data_loader:
+            if n_bars is not None and score_tensor.dim() == 3:
+                score_tensor = score_tensor.reshape(score_tensor.size(0) * n_bars, -1)
+            score = to_cuda_variable_long(score_tensor)
+            with torch.no_grad():
+                z_dist = self.model.encoder(score)
+                parts = ops.reparam_kl_fb(z_dist.loc.contiguous(), z_dist.log_scale.contiguous(), None, 0.0, 'dim', want_z=False)[1]
+            total = parts.double() if total is None else total + parts.double()
+            count += int(score.shape[0])
+            ops.check_chains("VAETester.kl_per_dim")
+        if total is None:
+            raise ValueError("kl_per_dim: the loader is empty")
+        return total / count
+
+    def active_units(self, data_loader, threshold=0.01):
+        """How many latent dimensions carry more than `threshold` nats of KL per measure on average (Burda et al. 2016 count active
+        units by a threshold of 0.01 on a posterior statistic; this is the KL form of that count)."""
+        return int((self.kl_per_dim(data_loader) > threshold).sum())
+
     def loss_and_acc_test(self, data_loader):
         """vae_tester.py:113-160: mean reconstruction CE / accuracy over a loader (eval mode, no teacher forcing)."""
         tot = torch.zeros(3)

@@ -1,4 +1,7 @@
 """VAETrainer: MeasureVAE/vae_trainer.py:10-139 of the reference on the HIP kernels."""
+import math
+import os
+
 import torch
 
 from .helpers import to_cuda_variable_long
@@ -8,15 +11,68 @@ from .trainer import Trainer, _ElboFn, _KLFn
 class VAETrainer(Trainer):
     feed_fields = (0,)                     # the metadata tensor is never read (vae_trainer.py:42-55)
 
+    KL_SETTINGS = ("kl_beta", "kl_warmup_steps", "kl_cycle_steps", "kl_ramp", "free_nats", "free_nats_per")
+
     def __init__(self, dataset, model, lr=1e-4, max_grad_norm=None, weight_decay=0.0, decay_all=False, ema_decay=None,
-                 ema_warmup=False):
+                 ema_warmup=False, kl_beta=0.001, kl_warmup_steps=0, kl_cycle_steps=0, kl_ramp=0.5, free_nats=0.0,
+                 free_nats_per='measure'):
+        """The loss of a training step is CE + beta_t / B * kl_sum.
+
+        kl_beta (finite, >= 0): the KL weight; the reference's 0.001.  kl_warmup_steps (an int >= 0): beta rises linearly from 0 to
+        kl_beta over that many optimizer steps, then holds.  kl_cycle_steps = M > 0: cyclical annealing (Fu et al. 2019) -- within
+        every period of M steps beta rises linearly over the first kl_ramp * M steps (0 < kl_ramp <= 1), then holds at kl_beta.
+        Warm-up and cycle exclude each other.  beta_at(t) is evaluated on the host, per step, at adam_t as the host knows it when the
+        loss is built: the first step sees t = 0, and after a dropped step t runs one too high for up to report_lag steps -- the
+        convention and the lag of ema_decay_at.  Validation (train=False) always uses kl_beta.
+
+        free_nats (finite, >= 0) with free_nats_per 'measure' or 'dim': the KL floor ("free bits").  'measure': every measure's KL,
+        summed over the latent dimensions, counts with max(KL_b, free_nats) -- MusicVAE's hinge plus the constant.  'dim' (Kingma
+        et al. 2016): every latent dimension's KL, summed over the batch, counts with max(KL_d, B * free_nats), i.e. its batch mean
+        is floored at free_nats.  The batch is the one this process sees: under data parallelism the rank's own shard, as batch
+        statistics would be; there is no collective for it.  A floored part passes no KL gradient; a part equal to its floor is
+        floored; a NaN part is kept, so that a NaN reaches loss and gradient as on the plain path.  free_nats > 0 sets
+        model.free_bits, which MeasureVAE.forward applies to training passes only; after such a step `last_kl` holds the device
+        tensors {'raw': (), 'floored': (), 'parts': (B,) or (Z,), 'keep': the same shape, 1.0 = kept} -- reading them is the
+        caller's synchronisation.  With the defaults the trainer launches what it launched before and last_kl stays None."""
+        kl_beta, kl_ramp, free_nats = float(kl_beta), float(kl_ramp), float(free_nats)
+        if not (kl_beta >= 0.0 and math.isfinite(kl_beta)):                     # (NaN fails the comparison)
+            raise ValueError(f"kl_beta must be finite and >= 0, got {kl_beta}")
+        for name, v in (("kl_warmup_steps", kl_warmup_steps), ("kl_cycle_steps", kl_cycle_steps)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
+        if kl_warmup_steps > 0 and kl_cycle_steps > 0:
+            raise ValueError("kl_warmup_steps and kl_cycle_steps exclude each other")
+        if not 0.0 < kl_ramp <= 1.0:
+            raise ValueError(f"kl_ramp must lie in (0, 1], got {kl_ramp}")
+        if not (free_nats >= 0.0 and math.isfinite(free_nats)):
+            raise ValueError(f"free_nats must be finite and >= 0, got {free_nats}")
+        if free_nats_per not in ('measure', 'dim'):
+            raise ValueError(f"free_nats_per must be 'measure' or 'dim', got {free_nats_per!r}")
         super().__init__(dataset, model, lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay, decay_all=decay_all,
                          ema_decay=ema_decay, ema_warmup=ema_warmup)
+        self.kl_beta, self.kl_warmup_steps, self.kl_cycle_steps, self.kl_ramp = kl_beta, kl_warmup_steps, kl_cycle_steps, kl_ramp
+        self.free_nats, self.free_nats_per = free_nats, free_nats_per
+        self.last_kl = None
+        if free_nats > 0.0:
+            model.free_bits = (free_nats, free_nats_per)
+
+    def beta_at(self, t):
+        """The KL weight of the step whose loss is built while adam_t == t (a pure function of the settings)."""
+        if self.kl_cycle_steps > 0:
+            return self.kl_beta * min(1.0, (t % self.kl_cycle_steps) / (self.kl_ramp * self.kl_cycle_steps))
+        if self.kl_warmup_steps > 0:
+            return self.kl_beta * min(1.0, t / self.kl_warmup_steps)
+        return self.kl_beta
 
     def loss_and_acc_for_batch(self, batch, epoch_num=None, train=True):
-        """loss = CE_mean + 1e-3 * mean_b KL ; accuracy   (vae_trainer.py:16-40)"""
+        """loss = CE_mean + beta * mean_b KL ; accuracy   (vae_trainer.py:16-40; beta = 1e-3 there)"""
         score = batch
         weights, samples, z_dist, prior_dist, z_tilde, z_prior = self.model(measure_score_tensor=score, train=train)
+        beta = self.beta_at(self.adam_t) if train else self.kl_beta
+        if train:
+            parts = getattr(z_dist, "kl_parts", None)
+            self.last_kl = None if parts is None else {"raw": z_dist.kl_raw.detach(), "floored": z_dist.kl_sum.detach(),
+                                                       "parts": parts, "keep": z_dist.kl_keep}
         kl_sum = getattr(z_dist, "kl_sum", None)
         if kl_sum is not None and type(self).compute_kld_loss is VAETrainer.compute_kld_loss and \
                 type(self).mean_crossentropy_loss_and_accuracy is Trainer.mean_crossentropy_loss_and_accuracy:
@@ -25,10 +81,11 @@ class VAETrainer(Trainer):
             t1 = score.contiguous().view(-1)
             if t1.dtype != torch.int64:
                 t1 = t1.long()
-            return _ElboFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, 0.001 / z_dist.loc.shape[0],
+            return _ElboFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, beta / z_dist.loc.shape[0],
                                  self.model.take_stats(2))
         recons_loss, accuracy = self.mean_crossentropy_loss_and_accuracy(weights, score)
-        dist_loss = self.compute_kld_loss(z_dist, prior_dist)
+        # (an override written against the reference's two-argument call keeps working while beta is the reference's)
+        dist_loss = self.compute_kld_loss(z_dist, prior_dist, **({} if beta == 0.001 else {"beta": beta}))
         loss = recons_loss + dist_loss
         return loss, accuracy
 
@@ -44,6 +101,22 @@ class VAETrainer(Trainer):
 
     def update_scheduler(self, epoch_num):
         return
+
+    def training_state(self, next_epoch=0):
+        st = super().training_state(next_epoch)
+        st.update({k: getattr(self, k) for k in self.KL_SETTINGS})
+        return st
+
+    def load_training_state(self, path_or_state):
+        """... and the six KL settings; a state written before they existed leaves this trainer's own."""
+        st = torch.load(path_or_state, map_location="cpu") if isinstance(path_or_state, (str, bytes, os.PathLike)) \
+            else path_or_state
+        out = super().load_training_state(st)
+        if "kl_beta" in st:
+            for k in self.KL_SETTINGS:
+                setattr(self, k, st[k])
+            self.model.free_bits = (self.free_nats, self.free_nats_per) if self.free_nats > 0.0 else None
+        return out
 
     @staticmethod
     def compute_kld_loss(z_dist, prior_dist, beta=0.001):

@@ -1,0 +1,166 @@
+"""The float64 restatement of the KL term with a floor ("free bits": include/inpaintnet_hip.h inet_reparam_kl_fb / inet_latent_bwd_fb,
+DESIGN.md section 22), forward and backward, both modes -- and the error bounds of the float32 kernels, derived here.  Shared by
+tests/test_kl_fb_host.py (CPU) and tests/test_gpu_kl_fb.py / tests/test_gpu_kl_schedule.py (GPU).
+
+Nothing here imports the library: a reference that called the code under test would prove nothing.
+
+The rule.  KL[b,d] = 0.5 (sigma^2 + mu^2 - 1) - log sigma over [rows, Z].
+  'measure': part[b] = sum_d KL[b,d], thr = free_nats;          'dim': part[d] = sum_b KL[b,d], thr = rows * free_nats.
+  keep = !(part <= thr) (a tie is floored, a NaN part is kept);  floored = sum keep ? part : thr;  raw = sum part.
+  dmu = dz + kk mu;  dls = dz eps sigma + kk (sigma^2 - 1),  kk = k where the element's part is kept, else 0.
+
+The bounds, with u = 2^-24 (the unit roundoff of float32: every correctly rounded operation has a relative error of at most u).
+
+One element.  Let T = 0.5 sigma^2 + 0.5 mu^2 + 0.5 + |log sigma|, the sum of the magnitudes of the element's terms.
+  s = expf(l): the device's expf is specified to 1 ulp; EXP_U = 4 allows 2 ulp = 4 u relative.
+  s*s: (1 + 4u)^2 (1 + u) - 1 < 9.1 u relative to sigma^2          -> at most ~9 u * 0.5 sigma^2 in the element (after the 0.5)
+  m*m: u relative                                                   -> u * 0.5 mu^2
+  a = s*s + m*m, b = a - 1: one rounding each, of at most u (sigma^2 + mu^2 + 1) <= 2 u T, halved by the exact 0.5 -> u T each
+  c = 0.5 b - l: one rounding, at most u T
+  Sum: the two squares err by at most 9 u (0.5 sigma^2 + 0.5 mu^2) <= 9 u T, the three roundings by u T each: ELEM_U = 12, an
+  element's float32 KL lies within 12 u T of the float64 one.  (A fused multiply-add only removes roundings.)
+
+A part.  The kernels add a part's n terms in a fixed tree; a float32 sum in ANY fixed order errs by at most depth * u * sum|terms|
+  to first order (Higham, Accuracy and Stability of Numerical Algorithms, section 4.2), depth = the most additions a term passes
+  through.  The issue states the bound as n * u * sum|terms| with n the number of terms; depth <= n, and the kernels' trees are
+  much shallower than n, which matters: at n of a thousand the n-bound would be wider than the gaps between neighbouring parts.
+  depth() below restates the trees from the launchers' constants.  With sum|terms| <= sum T:
+      part_bound = (ELEM_U + depth) * u * sum_{elements of the part} T.
+The two scalars add the (floored) parts, again in float32 in a fixed order of the finishing workgroup; any order of N terms errs by
+  at most N u sum|terms|:   scalar_bound = sum part_bound + nparts * u * sum|values added|.
+
+z = m + e*s:     4u |e s| (expf) + u |e s| (product) + u |z| (sum)                     <= 6 u (|m| + |e| sigma)
+dmu = g + kk*m:  u |kk m| + u |dmu|                                                      <= 2 u (|g| + |kk m|)
+dls = g*e*s + kk*(s*s - 1):  first term (g e rounded, expf, the product) 6 u |g e s|; second: 9 u sigma^2 for the square, u for the
+  subtraction, u for the product, each relative to at most sigma^2 + 1: 11 u |kk| (sigma^2 + 1); the sum u (|t1| + |t2|)
+                                                                                         <= 7 u |g e sigma| + 12 u |kk| (sigma^2 + 1)
+k itself is the float32 product kscale * kdev, formed the same way here: no error of its own."""
+import numpy as np
+
+U = 2.0 ** -24
+EXP_U = 4                      # expf: 2 ulp allowed = 4 u
+ELEM_U = 12
+PER = ("measure", "dim")
+
+# the launchers' constants (csrc/pointwise.hip): the 'measure' forward caps its grid at MEASURE_GRID workgroups of 4 waves, one wave per
+# row: MEASURE_PASS rows per pass of the grid; the 'dim' forward at DIM_GRID workgroups of 4 row-lanes: DIM_PASS rows per pass
+MEASURE_GRID, DIM_GRID = 256, 128
+MEASURE_PASS, DIM_PASS = 4 * MEASURE_GRID, 4 * DIM_GRID
+
+
+def f32(x):
+    return float(np.float32(x))
+
+
+def vec4(Z):
+    """Whether the kernels take their 16-byte path (every test tensor is 16-byte aligned)."""
+    return Z % 4 == 0
+
+
+def depth(rows, Z, per):
+    """The most float32 additions one term of a part passes through, from the kernels' summation order."""
+    cdiv = lambda a, b: -(-a // b)
+    if per == "measure":
+        # a lane's chain over its elements (one chain per slot of the 16-byte load, then 2 levels), then the 6 levels of the xor tree
+        chain = cdiv(Z, 256) + 2 if vec4(Z) else cdiv(Z, 64)
+        return chain + 6
+    G = min(cdiv(rows, 4), DIM_GRID)
+    # a row-lane's chain over its rows, the 4 row-lanes in order (3), a finishing thread's chain over G / 4 workspace rows, the 4 in order (3)
+    return cdiv(rows, 4 * G) + 3 + cdiv(G, 4) + 3
+
+
+def threshold(rows, free_nats, per):
+    """What the kernel compares a part with: free_nats as the ABI's float; 'dim': (float)(rows * free_nats)."""
+    lam = f32(free_nats)
+    return lam if per == "measure" else f32(rows * lam)
+
+
+def forward(mu, ls, eps, free_nats, per):
+    """-> dict(z, kl [rows, Z], parts, keep (bool), thr, floored, raw) in float64; eps None reads as 0."""
+    mu, ls = np.asarray(mu, np.float64), np.asarray(ls, np.float64)
+    rows, Z = mu.shape
+    s = np.exp(ls)
+    kl = 0.5 * (s * s + mu * mu - 1.0) - ls
+    parts = kl.sum(1 if per == "measure" else 0)
+    thr = threshold(rows, free_nats, per)
+    keep = ~(parts <= thr)
+    z = mu + (0.0 if eps is None else np.asarray(eps, np.float64)) * s
+    return dict(z=z, kl=kl, parts=parts, keep=keep, thr=thr, floored=np.where(keep, parts, thr).sum(), raw=parts.sum())
+
+
+def keep_of_elements(keep, shape, per):
+    keep = np.asarray(keep, bool)
+    return np.broadcast_to(keep[:, None] if per == "measure" else keep[None, :], shape)
+
+
+def backward(dz, mu, ls, eps, kscale, kdev, keep, per):
+    """-> (dmu, dls) in float64; dz / eps None read as 0; k = (float)kscale * (float)kdev as the kernel forms it."""
+    mu, ls = np.asarray(mu, np.float64), np.asarray(ls, np.float64)
+    k = f32(kscale) if kdev is None else float(np.float32(kscale) * np.float32(kdev))
+    kk = np.where(keep_of_elements(keep, mu.shape, per), k, 0.0)
+    g = 0.0 if dz is None else np.asarray(dz, np.float64)
+    e = 0.0 if eps is None else np.asarray(eps, np.float64)
+    s = np.exp(ls)
+    return g + kk * mu, g * e * s + kk * (s * s - 1.0)
+
+
+def bounds(mu, ls, eps, free_nats, per):
+    """-> dict(parts (per part), floored, raw, z (per element)): the forward kernels' error bounds derived in the module docstring."""
+    mu, ls = np.asarray(mu, np.float64), np.asarray(ls, np.float64)
+    rows, Z = mu.shape
+    s = np.exp(ls)
+    T = 0.5 * s * s + 0.5 * mu * mu + 0.5 + np.abs(ls)
+    pb = (ELEM_U + depth(rows, Z, per)) * U * T.sum(1 if per == "measure" else 0)
+    f = forward(mu, ls, eps, free_nats, per)
+    n = f["parts"].size
+    e = 0.0 if eps is None else np.abs(np.asarray(eps, np.float64))
+    return dict(parts=pb,
+                floored=float(pb.sum() + n * U * np.abs(np.where(f["keep"], f["parts"], f["thr"])).sum()),
+                raw=float(pb.sum() + n * U * np.abs(f["parts"]).sum()),
+                z=6.0 * U * (np.abs(mu) + e * s))
+
+
+def backward_bounds(dz, mu, ls, eps, kscale, kdev, keep, per):
+    mu, ls = np.asarray(mu, np.float64), np.asarray(ls, np.float64)
+    k = f32(kscale) if kdev is None else float(np.float32(kscale) * np.float32(kdev))
+    kk = np.abs(np.where(keep_of_elements(keep, mu.shape, per), k, 0.0))
+    g = 0.0 if dz is None else np.abs(np.asarray(dz, np.float64))
+    e = 0.0 if eps is None else np.abs(np.asarray(eps, np.float64))
+    s = np.exp(ls)
+    return 2.0 * U * (g + kk * np.abs(mu)), 7.0 * U * g * e * s + 12.0 * U * kk * (s * s + 1.0)
+
+
+def gap_threshold(parts):
+    """free-nats threshold in part units: the midpoint of the widest gap between neighbouring sorted parts in their middle half, so
+    that some parts are kept and some floored; a single part: half of it (kept).  -> (thr, the half width of that gap)."""
+    p = np.sort(np.asarray(parts, np.float64))
+    n = p.size
+    if n == 1:
+        return 0.5 * float(p[0]), 0.5 * float(p[0])
+    lo, hi = n // 4, max(n // 4 + 2, n - n // 4)
+    mid = p[lo:min(hi, n)]
+    i = int(np.argmax(np.diff(mid)))
+    return 0.5 * float(mid[i] + mid[i + 1]), 0.5 * float(mid[i + 1] - mid[i])
+
+
+# ---- the cases of tests/test_gpu_kl_fb.py, checked on the CPU by tests/test_kl_fb_host.py
+SHAPES = [(1, 1), (1, 256), (3, 5), (37, 64), (64, 63), (65, 257), (300, 256),
+          (MEASURE_PASS + 13, 260)]       # 1037 rows: past one full pass of both grids (1024 / 512 rows), the loops run again, ragged
+
+
+def case(rows, Z, per):
+    """The deterministic inputs of a shape and the free_nats whose threshold sits in the widest middle gap of the reference's parts.
+    -> dict(mu, ls, eps, dz (float32), free_nats, margin: the least |part - thr| minus that part's bound, which must be > 0)."""
+    from inpaintnet_amd import synthetic
+    tag = f"kl_fb/{rows}x{Z}"
+    mu = (0.3 * synthetic.det_normal(tag + "/mu", (rows, Z))).astype(np.float32)
+    ls = (-0.5 + 0.3 * synthetic.det_normal(tag + "/ls", (rows, Z))).astype(np.float32)
+    eps = synthetic.det_normal(tag + "/eps", (rows, Z)).astype(np.float32)
+    dz = synthetic.det_normal(tag + "/dz", (rows, Z)).astype(np.float32)
+    f0 = forward(mu, ls, eps, 0.0, per)
+    thr, _ = gap_threshold(f0["parts"])
+    free_nats = f32(thr if per == "measure" else thr / rows)
+    f = forward(mu, ls, eps, free_nats, per)
+    b = bounds(mu, ls, eps, free_nats, per)
+    margin = float((np.abs(f["parts"] - f["thr"]) - b["parts"]).min())
+    return dict(mu=mu, ls=ls, eps=eps, dz=dz, free_nats=free_nats, margin=margin)
