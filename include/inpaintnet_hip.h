@@ -712,6 +712,20 @@ int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8);
 /* (A constrained call -- inet_vae_decoder_sample_cx with a mask -- has the truncated call's plan: every masked build fits.  A forced call
  *  -- inet_vae_decoder_sample_fx with forced tokens -- has it too: every forced build fits.) */
 int inet_decode_b1_plan_trunc(int B, int V, int Z, int* out8);
+/* What a decoder forward call launches, under the options set now (inet_set_option keys 4, 15) and on this chip (CUs, or
+ * INET_CHAIN_CUS), without a GPU or a workspace: the route function that inet_vae_decoder_fwd and the inet_vae_decoder_sample entries
+ * ask themselves (csrc/vae.hip dec_route).  flags: bit 0 = a multinomial seed, bit 1 = mask_beat given, bit 2 = mask_tick given; level:
+ * 0 = argmax, 1 = temperature, 2 = truncated or logp, 3 = a mask of allowed tokens, 4 = forced tokens.  out (n_out >= 13) = {beat path
+ * (0 = one launch per step, 1 = chain launches, 2 = folded into the register-resident launch), tick path (0 = teacher-forced chains,
+ * 1 = teacher-forced steps, 2 = one fused launch, 3 = fused launches over row chunks, 4 = tick by tick), beats per teacher-forced chain
+ * launch, rows per chunk (512 / 256), the fused launch is the register-resident one, ... with the beat path inside it, words the
+ * prologue zeroes (0 = none, 1 = the sync areas, 2 = the register-resident launch's granules and the sync areas), fragment-major twins
+ * packed: the beat layers' W_hh, the tick layers' three, the output projection's, the initial tick hiddens (0 = no, 1 = once for all
+ * rows, 2 = per chunk), the workspace carries twins at all, the first fused launch finds its counters zeroed by the prologue (0 where
+ * row-chunked beat chains counted on them: it zeroes them itself)}.  0, or -1 for a call the entries refuse (more than 4 beats, a level above
+ * 0 with teacher forcing or a seed), a level outside 0..4, flags outside 0..7, a null or short output -- nothing is written then. */
+int inet_vae_decoder_route(const inet_vae_config* cfg, int batch, int save, int teacher_forced, int flags, int level, int32_t* out,
+                           int n_out);
 /* What inet_gemm (nbatch = 1) / inet_gemm_batched (nbatch 2..8: no bias, epi 0, acc 1) launch for a call, under the options set now
  * (inet_set_option keys 2, 3, 5), without a GPU: the dispatcher's planner (csrc/gemm.hip gemm_plan) behind the C-ABI.  out16 = {family
  * (0 = few-row gemv, 1 = TN-direct, 2 = kc-direct, 3 = workgroup split-K, 4 = LDS-tiled), tile configuration, tile rows, tile columns,

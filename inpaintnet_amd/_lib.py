@@ -162,6 +162,7 @@ _SIGNATURES = {
     "inet_decode_b1_plan": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int)]),
     "inet_decode_b1_plan_sample": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int)]),
     "inet_decode_b1_plan_trunc": (C.c_int, [_I, _I, _I, C.POINTER(C.c_int)]),
+    "inet_vae_decoder_route": (C.c_int, [_CFG] + [_I] * 5 + [C.POINTER(C.c_int32), _I]),
     "inet_gemm_plan": (C.c_int, [_I] * 5 + [_L, _L] + [_I] * 4 + [C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, _I]),
     "inet_gemm_group_plan": (C.c_int, [_I, C.POINTER(_L), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, _I]),
     "inet_gru_chain_plan": (C.c_int, [_I] * 5 + [C.POINTER(_L)]),

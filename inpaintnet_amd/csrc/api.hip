@@ -670,6 +670,10 @@ int inet_slow_waits(unsigned* dst, int max_entries, int reset, int64_t* noted) {
 int inet_decode_b1_plan(int B, int V, int Z, int* out8) { return decode_b1_plan_check(B, V, Z, out8); }
 int inet_decode_b1_plan_sample(int B, int V, int Z, int* out8) { return decode_b1_plan_check(B, V, Z, out8, 1); }
 int inet_decode_b1_plan_trunc(int B, int V, int Z, int* out8) { return decode_b1_plan_check(B, V, Z, out8, 2); }
+int inet_vae_decoder_route(const inet_vae_config* cfg, int batch, int save, int teacher_forced, int flags, int level, int32_t* out, int n_out) {
+    if (!cfg_ok(cfg) || batch <= 0 || flags < 0 || flags > 7) return -1;
+    return vae_decoder_route(*cfg, batch, save, teacher_forced, flags, level, out, n_out);
+}
 
 namespace {
 // the arguments of a product as the planners read them (shape, layout, leading dimensions, modes; no operand is touched)

@@ -62,6 +62,7 @@ constexpr int kDecodeB1MaxRows = 16;              // rows (measures) per call th
                                                   // workgroups, up to five teams (tick path only beyond one team)
 // How a call of B rows is split into teams of the tick path's workgroups, whether the beat path goes into the same launch and
 // which kernel instantiation runs it is ONE decision: decode_b1.hip's make_plan (the plans per call size are listed above it).
+// Whether a decoder call takes this launch at all, and with which beat path, is vae.hip's dec_route, which asks the two tests below.
 constexpr int kDecodeB1BeatRowsMax = 6;           // rows the beat path's workgroups serve when they share the launch with several teams
 constexpr int kDecodeB1OneRowTeamsMax = 3;        // ... with ONE-row teams (two or three measures under mode 4): the beat path serves three rows
 // granule areas of a call: the most rows any plan of B measures addresses under the current mode -- fused or not, any V, any capacity

@@ -18,6 +18,9 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
 // rq (sample.h's Request, [B, T] arrays; the default value: the argmax call).  With uniforms (a free-running call: no target, no seed) the
 // tokens are drawn by sample.h's rule at the request's level -- temperature, truncated, constrained, forced: each level's builds of
 // decode_b1.hip's launch where its planner has a plan of that level, else tick by tick with pw_sample at the call's level.
+// What vae_decoder_fwd launches for such a call (flags: 1 = a multinomial seed, 2 = mask_beat, 4 = mask_tick; level: the request's, 0 =
+// argmax): the thirteen integers of vae.hip's DecRoute, from the function the launch itself asks.  No GPU, no workspace.
+int vae_decoder_route(const inet_vae_config& c, int B, int save, int teacher_forced, int flags, int level, int32_t* out, int n_out);
 int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, const float* weights,
                     const long long* tokens_in, const float* p, float* g, const float* mask_beat,
                     const float* mask_tick, float* dz, void* ws, hipStream_t s);

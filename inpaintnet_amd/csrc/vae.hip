@@ -275,6 +275,349 @@ void tick_pk(const DecWs& w, int i, int j, int nb, long pkh, bool masked, GruFwd
     P1.hpk_new = r1 + (long)(j & 1) * pkh;
 }
 
+// ---- the route of a forward call: decided once, by dec_route(); every pass below reads it and no condition stands anywhere else
+// (inet_vae_decoder_route reports it without a GPU; DESIGN.md section 23 has the table) ----
+enum DecBeats { kBeatsSteps, kBeatsChained, kBeatsFolded };  // per step / chain launches / roles of decode_b1.hip's launch
+enum DecTicks { kTfChained, kTfSteps, kFused, kFusedChunked, kPerTick };
+enum DecZero { kZeroNone, kZeroSync, kZeroB1Sync };          // the prologue zeroes nothing / w.sync / w.b1ex .. w.sync (adjacent: one range)
+enum DecHt0 { kHt0No, kHt0Once, kHt0PerChunk };              // fragment-major initial tick hiddens: all rows behind the beat path / per chunk
+
+struct DecRoute {
+    int beats, ticks;                                // DecBeats, DecTicks
+    int npl;                                         // kTfChained: beats per chain launch
+    int chunk_rows;                                  // kFusedChunked: rows per launch, 512 or 256
+    int b1, b1_fused;                                // kFused: decode_b1.hip's register-resident launch; ... with the beat path inside it
+    int zero, pack_beat, pack_tick, pack_out, ht0;   // what follows from the two paths: DecZero, the twins to pack, DecHt0
+    int pk;                                          // the workspace carries fragment-major twins (pk_ok(H))
+    int fused_prezeroed;                             // kFused / kFusedChunked: the first launch finds its counters zeroed by the prologue
+};
+
+DecRoute dec_route(const inet_vae_config& c, int B, int save, bool teacher_forced, bool seeded, bool mask_beat, bool mask_tick, int level,
+                   bool sampled, const DecWs& w) {
+    const int nb = c.beats, G = c.ticks_per_beat, T = nb * G, H = c.dec_hidden, V = c.num_notes;
+    DecRoute r{};
+    r.pk = w.wpk_t0 != nullptr;
+    const int beat_rows = r.pk ? chain_chunk_rows(H, B, nb, 1, save) : 0;          // (one launch, or one per row chunk)
+    const bool beats_chained = beat_rows > 0;
+    const bool fused_shape = r.pk && !teacher_forced && !seeded;
+    const bool chain_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
+    // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
+    r.b1 = chain_whole && !save && !mask_tick && w.b1ex && w.b1ex + decode_b1_words(B) == w.sync && decode_b1_shape_ok(B, H, V, T, G, level);
+    r.b1_fused = r.b1 && !mask_beat && decode_b1_fused(c.z_dim, B, V, level);   // ... with the beat path inside the same launch
+    // (a sampled call: the one fused launch that knows the rule is decode_b1.hip's; every other shape samples tick by tick)
+    const bool fused_whole = chain_whole && (!sampled || r.b1);
+    // batches beyond one resident launch (LatentRNN decodes 512 measures per step): the rows are independent, so the fused
+    // kernel runs over chunks of 512 rows (the 64-row build: 27 us per tick instead of 2 x 20) or 256, one launch after the other
+    const int chunk = B % 512 == 0 ? 512 : 256;
+    const bool fused_chunked = fused_shape && !sampled && !fused_whole && B > chunk && B % chunk == 0 && decode_chain_ok(chunk, H, V, T, G);
+    // teacher-forced ticks: every input token is known and the 4 beats are independent, so each tick layer is a chain of
+    // G steps over the beats as problems -- `npl` beats per launch, as many as fit the chip at once (2 at B = 256)
+    if (r.pk && teacher_forced) {
+        for (int n = nb; n >= 1 && !r.npl; --n)              // whole batch in one launch per `n` beats ...
+            if (nb % n == 0 && 3 + 2 * (nb / n) <= kSyncAreas && gru_chain_ok(H, B, G, n)) r.npl = n;
+        for (int n = nb; n >= 1 && !r.npl; --n)              // ... else row chunks
+            if (nb % n == 0 && 3 + 2 * (nb / n) <= kSyncAreas && chain_chunk_rows(H, B, G, n, save) > 0) r.npl = n;
+    }
+    r.beats = r.b1_fused ? kBeatsFolded : beats_chained ? kBeatsChained : kBeatsSteps;
+    r.ticks = r.npl ? kTfChained : teacher_forced ? kTfSteps : fused_whole ? kFused : fused_chunked ? kFusedChunked : kPerTick;
+    r.chunk_rows = r.ticks == kFusedChunked ? chunk : 0;
+    const bool fused = r.ticks == kFused || r.ticks == kFusedChunked, steps = r.ticks == kTfSteps || r.ticks == kPerTick;
+    // the sync areas for every chain or fused launch, and the b = 1 kernel's granules in front of them
+    r.zero = r.b1 ? kZeroB1Sync : (beats_chained || fused || r.npl) ? kZeroSync : kZeroNone;
+    // Row-chunked beat chains count on two areas per layer (seq.hip gru_layer_fwd: odd chunks on the area behind the layer's), so layer 1
+    // leaves area 2 -- the fused launches' counters -- counted up: their first launch then zeroes it itself, like the later ones
+    r.fused_prezeroed = fused && !(r.beats == kBeatsChained && beat_rows < B);
+    // Which kernels will run: the chain kernels read W_hh / W_ih as stored, only the per-step kernels want the
+    // fragment-major twins -- each is packed only if its consumer runs.
+    r.pack_beat = r.pk && r.beats == kBeatsSteps;
+    r.pack_tick = r.pk && steps;
+    r.pack_out = r.pk && w.wpk_out && r.ticks == kPerTick;
+    // packed initial tick hiddens: the per-step kernels and decode_chain.hip's launch read them, the chains and the b = 1 launch do not
+    r.ht0 = !r.pk ? kHt0No : r.ticks == kFusedChunked ? kHt0PerChunk : (steps || (r.ticks == kFused && !r.b1)) ? kHt0Once : kHt0No;
+    return r;
+}
+
+// One forward call: what the passes below read, filled once per call by vae_decoder_fwd.
+struct DecCall {
+    explicit DecCall(const inet_vae_config& c) : L(c) {}
+    VaeLayout L;
+    DecWs w{};
+    DecRoute r{};
+    int B, nb, G, T, H, V, E, Z, save, teacher_forced, level;
+    long BH, pkh;
+    bool sampled;
+    const float *z, *p, *mask_beat, *mask_tick, *wih0;       // wih0: tick layer 0's W_ih [3H, E+H], row stride ldw0
+    long ldw0;
+    const long long* target;
+    float* weights; long long* samples;
+    uint64_t seed; sample::Request rq;
+    hipStream_t s;
+};
+
+int dec_prologue(const DecCall& d) {
+    const DecWs& w = d.w; const VaeLayout& L = d.L; const float* p = d.p;
+    const int B = d.B, H = d.H, V = d.V, E = d.E;
+    // One launch for the scattered little jobs (each used to be its own ~5 us launch): z saved for the backward pass, the
+    // chain kernels' sync areas zeroed, the beat GRU's constant input gates gvec0 = b_0 W_ih[:,0] + b_ih, the tick
+    // GRU's gather table (rows 0..V-1 = E_dec . W_ih[:, :E]^T + b_ih; row V = x_0 . W_ih[:, :E]^T + b_ih), the start
+    // token index, and the teacher-forced token copy / shift.
+    PwPrologue pr{};
+    pr.tab[0] = PwTableJob{p + L.dec_emb, E, V, d.wih0, d.ldw0, p + L.tick[0].b_ih, w.table, 3L * H, 3 * H, E};
+    pr.tab[1] = PwTableJob{p + L.x_0, E, 1, d.wih0, d.ldw0, p + L.tick[0].b_ih, w.table + (long)V * 3 * H, 3L * H, 3 * H, E};
+    pr.ntab = 2;
+    if (d.r.zero != kZeroNone) { pr.zero_words = w.sync; pr.nzero = (long)kSyncAreas * kChainSyncWords; }
+    if (d.r.zero == kZeroB1Sync) { pr.zero_words = w.b1ex; pr.nzero = decode_b1_words(B) + (long)kSyncAreas * kChainSyncWords; }
+    if (d.save) { pr.copy_src = reinterpret_cast<const unsigned*>(d.z); pr.copy_dst = reinterpret_cast<unsigned*>(w.zsave); pr.ncopy = (long)B * d.Z; }
+    pr.axpb_a = p + L.b_0; pr.axpb_x = p + L.beat[0].w_ih; pr.axpb_incx = 1; pr.axpb_b = p + L.beat[0].b_ih;
+    pr.axpb_y = w.gvec0; pr.axpb_n = 3 * H;
+    pr.fill_ptr = w.idxV; pr.nfill = B; pr.fill_val = V;
+    if (d.teacher_forced) {
+        pr.tok_src = d.target; pr.tok_copy = d.samples; pr.tok_B = B; pr.tok_T = d.T; pr.tok_first = V; pr.tok_V = V;
+        if (d.r.ticks == kTfChained) pr.tok_shift = w.tokin;
+    }
+    return pw_prologue(pr, d.s);
+}
+
+int dec_pack_weights(const DecCall& d) {
+    const DecWs& w = d.w; const VaeLayout& L = d.L; const float* p = d.p;
+    const float* ins[5]; float* outs[5];
+    int n = 0;
+    if (d.r.pack_beat) {
+        ins[n] = p + L.beat[0].w_hh; outs[n++] = w.wpk_b[0];
+        ins[n] = p + L.beat[1].w_hh; outs[n++] = w.wpk_b[1];
+    }
+    if (d.r.pack_tick) {
+        ins[n] = p + L.tick[0].w_hh; outs[n++] = w.wpk_t0;
+        ins[n] = p + L.tick[1].w_hh; outs[n++] = w.wpk_t1hh;
+        ins[n] = p + L.tick[1].w_ih; outs[n++] = w.wpk_t1ih;
+    }
+    if (n) INET_TRY(pw_pack_frag_multi(ins, outs, n, d.H, 3 * d.H, d.H, 0, d.s));
+    if (d.r.pack_out) INET_TRY(pw_pack_frag(p + L.out_w, d.H, d.V, d.H, w.wpk_out, 0, 1, 0, 0, d.s));
+    return 0;
+}
+
+// ---- beat RNN (forward_beat_rnn, decoder.py:455-471) and the per-beat constants for the tick RNN: eight launches, or roles of
+// decode_b1.hip's launch (kBeatsFolded: not called) ----
+int dec_beat_path(const DecCall& d) {
+    const DecWs& w = d.w; const VaeLayout& L = d.L; const float* p = d.p; hipStream_t s = d.s;
+    const int B = d.B, nb = d.nb, H = d.H, Z = d.Z;
+    const long BH = d.BH;
+    const bool chained = d.r.beats == kBeatsChained;
+    // A sampled call reproduces itself bit for bit, so that forcing its tokens replays it (sample.h): its
+    // products keep one k range per tile.  (Without that the four-beat products of 9 to 63 rows other than 32 are split over K with
+    // f32 atomics, and two identical calls differ in the last bits of their logits.)
+    const int one_range = d.sampled ? 1 : 0;
+    {
+        GemmArgs g = linear_fwd_args(d.z, Z, p + L.zb_w, Z, p + L.zb_b, w.hb0, 2L * H, B, 2 * H, Z, EPI_SELU);
+        g.one_range = one_range;
+        INET_TRY(launch_gemm(g, s));
+    }
+    DirFwd f{};
+    f.W_hh = p + L.beat[0].w_hh; f.b_hh = p + L.beat[0].b_hh;
+    f.gvec = w.gvec0;
+    f.h0 = w.hb0; f.h0_ld = 2L * H;
+    f.out = w.beat0; f.out_ld = H; f.out_ts = BH;
+    if (d.mask_beat) { f.outm = w.beat0m; f.outm_ld = H; f.outm_ts = BH; f.mask = d.mask_beat; f.mask_ld = H; f.mask_ts = BH; }
+    if (d.save) { f.sv = w.svb0; f.sv_astride = nb * BH; }
+    f.Wpk_hh = w.wpk_b[0]; f.hpk = w.hpk_b;
+    if (chained) { f.sync = w.sync; f.sync_prezeroed = 1; }  // 4 steps in one launch (8 groups of 32 rows at B = 256)
+    INET_TRY(gru_layer_fwd(H, B, nb, 1, &f, s));
+    const float* xb = d.mask_beat ? w.beat0m : w.beat0;
+    {
+        GemmArgs g = linear_fwd_args(xb, H, p + L.beat[1].w_ih, H, p + L.beat[1].b_ih, w.gi1b, 3L * H, nb * B, 3 * H, H, EPI_NONE);
+        g.one_range = one_range;
+        INET_TRY(launch_gemm(g, s));
+    }
+    f = DirFwd{};
+    f.W_hh = p + L.beat[1].w_hh; f.b_hh = p + L.beat[1].b_hh;
+    f.gi = w.gi1b; f.gi_ld = 3L * H; f.gi_ts = 3 * BH;
+    f.h0 = w.hb0 + H; f.h0_ld = 2L * H;
+    f.out = w.beat_out; f.out_ld = H; f.out_ts = BH;
+    if (d.save) { f.sv = w.svb1; f.sv_astride = nb * BH; }
+    f.Wpk_hh = w.wpk_b[1]; f.hpk = w.hpk_b;
+    if (chained) { f.sync = w.sync + kChainSyncWords; f.sync_prezeroed = 1; }
+    INET_TRY(gru_layer_fwd(H, B, nb, 1, &f, s));
+
+    // ---- per-beat constants for the tick RNN (decoder.py:494-495), all 4 beats at once ----
+    {
+        GemmArgs bt[2] = {linear_fwd_args(w.beat_out, H, p + L.bh_w, H, p + L.bh_b, w.ht0, 2L * H, nb * B, 2 * H, H, EPI_SELU),
+                          linear_fwd_args(w.beat_out, H, p + L.bi_w, H, p + L.bi_b, w.c_all, H, nb * B, H, H, EPI_SELU)};
+        bt[0].one_range = bt[1].one_range = one_range;
+        INET_TRY(launch_gemm_group(bt, 2, s));
+    }
+    if (d.r.ht0 == kHt0Once)                                 // packed initial tick hiddens: [layer][beat]
+        for (int l = 0; l < 2; ++l)
+            INET_TRY(pw_pack_frag(w.ht0 + (long)l * H, 2L * H, B, H, w.ht0pk + (long)l * nb * d.pkh, 0, nb, (long)B * 2 * H, d.pkh, s));
+    GemmArgs g = linear_fwd_args(w.c_all, H, d.wih0 + d.E, d.ldw0, nullptr, w.cgi, 3L * H, nb * B, 3 * H, H, EPI_NONE);
+    g.one_range = one_range;
+    return launch_gemm(g, s);
+}
+
+// the shared tail of the teacher-forced tick paths: ONE output projection over all ticks
+int dec_project_tf(const DecCall& d) {
+    const DecWs& w = d.w;
+    INET_TRY(linear_fwd(w.h1seq, d.H, d.p + d.L.out_w, d.H, d.p + d.L.out_b, w.wtm, d.V, d.T * d.B, d.V, d.H, EPI_RELU, d.s));
+    return pw_swap01(w.wtm, d.T, d.B, d.V, d.weights, d.s);  // [T,B,V] -> [B,T,V]
+}
+
+// each tick layer as chains of G steps over the beats as problems, d.r.npl beats per launch
+int dec_ticks_tf_chained(const DecCall& d) {
+    const DecWs& w = d.w; const VaeLayout& L = d.L; const float* p = d.p; hipStream_t s = d.s;
+    const int B = d.B, nb = d.nb, G = d.G, T = d.T, H = d.H, npl = d.r.npl;
+    const long BH = d.BH, pkh = d.pkh;
+    const float* x1 = d.mask_tick ? w.h0m : w.h0seq;
+    for (int layer = 0; layer < 2; ++layer) {
+        if (layer == 1)                                      // layer 1's input-side pre-activations for all 24 ticks at once
+            INET_TRY(linear_fwd(x1, H, p + L.tick[1].w_ih, H, p + L.tick[1].b_ih, w.gi1t, 3L * H, T * B, 3 * H, H, EPI_NONE, s));
+        for (int i0 = 0; i0 < nb; i0 += npl) {
+            DirFwd dd[4];
+            for (int k = 0; k < npl; ++k) {
+                const int i = i0 + k;
+                DirFwd& D = dd[k];
+                D = DirFwd{};
+                D.W_hh = p + L.tick[layer].w_hh; D.b_hh = p + L.tick[layer].b_hh;
+                D.h0 = w.ht0 + (long)i * B * 2 * H + layer * H; D.h0_ld = 2L * H;
+                D.out_ld = H; D.out_ts = BH;
+                if (layer == 0) {
+                    D.gi = w.cgi + (long)i * B * 3 * H; D.gi_ld = 3L * H; D.gi_ts = 0;   // the beat's constant half
+                    D.table = w.table; D.table_ld = 3L * H;                              // the token half
+                    D.idx = w.tokin + (long)i * G; D.idx_bs = T; D.idx_ts = 1;
+                    D.out = w.h0seq + (long)i * G * BH;
+                    if (d.mask_tick) {
+                        D.outm = w.h0m + (long)i * G * BH; D.outm_ld = H; D.outm_ts = BH;
+                        D.mask = d.mask_tick + (long)i * G * BH; D.mask_ld = H; D.mask_ts = BH;
+                    }
+                    if (d.save) { D.sv = w.svt0 + (long)i * G * BH; D.sv_astride = (long)T * BH; }
+                    D.Wpk_hh = w.wpk_t0; D.hpk = w.hpk_t0 + (long)i * 3 * pkh;
+                } else {
+                    D.gi = w.gi1t + (long)i * G * 3 * BH; D.gi_ld = 3L * H; D.gi_ts = 3 * BH;
+                    D.out = w.h1seq + (long)i * G * BH;
+                    if (d.save) { D.sv = w.svt1 + (long)i * G * BH; D.sv_astride = (long)T * BH; }
+                    D.Wpk_hh = w.wpk_t1hh; D.hpk = w.hpk_t1 + (long)i * 3 * pkh;
+                }
+            }
+            dd[0].sync = w.sync + (long)(2 + layer * (nb / npl) + i0 / npl) * kChainSyncWords;
+            dd[0].sync_prezeroed = 1;
+            INET_TRY(gru_layer_fwd(H, B, G, npl, dd, s));
+        }
+    }
+    return dec_project_tf(d);
+}
+
+// The two step problems of tick t = i * G + j, layer 0 = P0 and layer 1 = P1, into zeroed problems: operands, saves and -- with the
+// twins -- tick_pk's fragment-major ones (tick_pk writes no field written here).
+void dec_tick_probs(const DecCall& d, int i, int j, GruFwdProb& P0, GruFwdProb& P1) {
+    const DecWs& w = d.w; const VaeLayout& L = d.L; const float* p = d.p;
+    const int B = d.B, H = d.H, T = d.T, t = i * d.G + j;
+    const long BH = d.BH, as = (long)T * BH;
+    P0.B = B;
+    if (j == 0) { P0.h_prev = w.ht0 + (long)i * B * 2 * H; P0.ld_hprev = 2L * H; }
+    else { P0.h_prev = w.h0seq + (long)(t - 1) * BH; P0.ld_hprev = H; }
+    P0.W_hh = p + L.tick[0].w_hh; P0.b_hh = p + L.tick[0].b_hh;
+    P0.gi_dense = w.cgi + (long)i * B * 3 * H; P0.ld_gi = 3L * H;
+    P0.gi_table = w.table; P0.ld_table = 3L * H;
+    if (t == 0) { P0.idx = w.idxV; P0.idx_stride = 1; }
+    else { P0.idx = d.samples + (t - 1); P0.idx_stride = T; }
+    P0.h_new = w.h0seq + (long)t * BH; P0.ld_hnew = H;
+    if (d.mask_tick) { P0.h_masked = w.h0m + (long)t * BH; P0.ld_hm = H; P0.mask = d.mask_tick + (long)t * BH; P0.ld_mask = H; }
+    P1.B = B;
+    if (j == 0) { P1.h_prev = w.ht0 + (long)i * B * 2 * H + H; P1.ld_hprev = 2L * H; }
+    else { P1.h_prev = w.h1seq + (long)(t - 1) * BH; P1.ld_hprev = H; }
+    P1.W_hh = p + L.tick[1].w_hh; P1.b_hh = p + L.tick[1].b_hh;
+    P1.x = (d.mask_tick ? w.h0m : w.h0seq) + (long)t * BH; P1.ldx = H; P1.K2 = H;
+    P1.W_ih = p + L.tick[1].w_ih; P1.ld_wih = H; P1.b_ih = p + L.tick[1].b_ih;
+    P1.h_new = w.h1seq + (long)t * BH; P1.ld_hnew = H;
+    const auto saves = [&](GruFwdProb& P, float* q) { P.sv_r = q; P.sv_z = q + as; P.sv_n = q + 2 * as; P.sv_ghn = q + 3 * as; P.sv_hprev = q + 4 * as; };
+    if (d.save) { saves(P0, w.svt0 + (long)t * BH); saves(P1, w.svt1 + (long)t * BH); }
+    if (d.r.pk) tick_pk(w, i, j, d.nb, d.pkh, d.mask_tick != nullptr, P0, P1);
+}
+
+// Every input token is known, and the tick GRU's hidden state is re-initialised per beat, so the 4 beats are
+// independent: 6 steps x 4 problems per layer instead of 24 dependent steps, and ONE output projection.
+int dec_ticks_tf_steps(const DecCall& d) {
+    for (int j = 0; j < d.G; ++j) {
+        GruFwdBatch b0{}, b1{};
+        b0.H = b1.H = d.H; b0.nprob = b1.nprob = d.nb;
+        for (int i = 0; i < d.nb; ++i) dec_tick_probs(d, i, j, b0.p[i], b1.p[i]);
+        INET_TRY(launch_gru_fwd(b0, d.s));
+        INET_TRY(launch_gru_fwd(b1, d.s));
+    }
+    return dec_project_tf(d);
+}
+
+// all 24 free-running ticks (layer 0, layer 1, projection, argmax, token feedback) in ONE launch: inference, and
+// the free-running half of the training steps (dropout mask between the layers, backward saves written on the way) --
+// over all rows (kFused) or one launch per chunk of d.r.chunk_rows rows (kFusedChunked)
+int dec_ticks_fused(const DecCall& d) {
+    const DecWs& w = d.w; const VaeLayout& L = d.L; const float* p = d.p; hipStream_t s = d.s;
+    const int B = d.B, nb = d.nb, T = d.T, H = d.H, V = d.V;
+    const bool chunked = d.r.ticks == kFusedChunked;
+    const int Bc = chunked ? d.r.chunk_rows : B;
+    const long pkc = (long)pk_floats(Bc, H);
+    for (int r0 = 0; r0 < B; r0 += Bc) {
+        if (d.r.ht0 == kHt0PerChunk)                         // the chunk's initial tick hiddens, fragment-major [layer][beat]
+            for (int l = 0; l < 2; ++l)
+                INET_TRY(pw_pack_frag(w.ht0 + (long)r0 * 2 * H + (long)l * H, 2L * H, Bc, H, w.ht0pk + (long)l * nb * pkc, 0, nb,
+                                      (long)B * 2 * H, pkc, s));
+        DecodeChainArgs a{};
+        a.B = Bc; a.Bs = B; a.H = H; a.T = T; a.G = d.G; a.V = V;
+        a.W_hh0 = p + L.tick[0].w_hh; a.b_hh0 = p + L.tick[0].b_hh;
+        a.cgi = w.cgi + (long)r0 * 3 * H; a.table = w.table;
+        a.W_ih1 = p + L.tick[1].w_ih; a.b_ih1 = p + L.tick[1].b_ih; a.W_hh1 = p + L.tick[1].w_hh; a.b_hh1 = p + L.tick[1].b_hh;
+        a.W_out = p + L.out_w; a.b_out = p + L.out_b;
+        a.ht0 = w.ht0 + (long)r0 * 2 * H; a.ht0pk = w.ht0pk;
+        a.hx0 = w.hpk_t0; a.hx1 = w.hpk_t1; a.amax = w.amax;
+        a.b1ex = d.r.b1 ? reinterpret_cast<unsigned long long*>(w.b1ex) : nullptr;
+        static const bool b1st = [] { const char* v = std::getenv("INET_DECODE_B1_STAMPS"); return v && v[0] == '1'; }();
+        a.b1stamps = (d.r.b1 && b1st && T <= 32) ? reinterpret_cast<unsigned long long*>(w.b1stamps) : nullptr;
+        if (d.r.b1_fused) {
+            DecodeB1Beat& bt = a.beat;
+            bt.z = d.z; bt.zb_w = p + L.zb_w; bt.zb_b = p + L.zb_b; bt.gvec0 = w.gvec0;
+            bt.W_hh0 = p + L.beat[0].w_hh; bt.b_hh0 = p + L.beat[0].b_hh;
+            bt.W_ih1 = p + L.beat[1].w_ih; bt.b_ih1 = p + L.beat[1].b_ih; bt.W_hh1 = p + L.beat[1].w_hh; bt.b_hh1 = p + L.beat[1].b_hh;
+            bt.bh_w = p + L.bh_w; bt.bh_b = p + L.bh_b; bt.bi_w = p + L.bi_w; bt.bi_b = p + L.bi_b;
+            bt.wih0_c = d.wih0 + d.E; bt.wih0_ld = d.ldw0;
+        }
+        a.weights = d.weights + (long)r0 * T * V; a.samples = d.samples + (long)r0 * T;
+        a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0 && d.r.fused_prezeroed;   // (else the launcher zeroes the area)
+        a.draw = d.rq;                                       // (sampled: one whole launch, never chunks)
+        if (d.mask_tick) { a.mask = d.mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
+        if (d.save) {
+            a.sv0 = w.svt0 + (long)r0 * H; a.sv1 = w.svt1 + (long)r0 * H; a.sv_stride = (long)T * d.BH;
+            a.h0out = (d.mask_tick ? w.h0m : w.h0seq) + (long)r0 * H; a.h1seq = w.h1seq + (long)r0 * H;
+        }
+        INET_TRY(launch_decode_chain(a, s));
+    }
+    return 0;
+}
+
+// free-running ticks, one launch per layer and tick
+int dec_ticks_per_tick(const DecCall& d) {
+    const DecWs& w = d.w; const VaeLayout& L = d.L; const float* p = d.p; hipStream_t s = d.s;
+    const int B = d.B, T = d.T, H = d.H, V = d.V;
+    const bool draw = d.seed != 0;                           // decoder.py:506-509: sample the fed-back token
+    for (int t = 0; t < T; ++t) {
+        GruFwdBatch b0{}, b1{};
+        b0.H = b1.H = H; b0.nprob = b1.nprob = 1;
+        dec_tick_probs(d, t / d.G, t % d.G, b0.p[0], b1.p[0]);
+        INET_TRY(launch_gru_fwd(b0, s));
+        INET_TRY(launch_gru_fwd(b1, s));
+        // logits = ReLU(h_top . Wo^T + bo) straight into weights[:, t, :], fused with the argmax that feeds tick t+1
+        const float* h1 = w.h1seq + (long)t * d.BH;
+        float* wt = d.weights + (long)t * V;
+        int rc = draw || d.sampled ? 1 : launch_logits_argmax(h1, H, B, H, p + L.out_w, p + L.out_b, V, wt, (long)T * V, d.samples + t, T, s,
+                                                               d.r.pk ? b1.p[0].hpk_new : nullptr, w.wpk_out);
+        if (rc < 0) return rc;
+        if (rc == 1) {                                       // V not a multiple of 16 (or > 64), or sampling: two kernels
+            INET_TRY(linear_fwd(h1, H, p + L.out_w, H, p + L.out_b, wt, (long)T * V, B, V, H, EPI_RELU, s));
+            if (draw) INET_TRY(pw_sample_multinomial(wt, (long)T * V, B, V, d.samples + t, T, d.seed, (uint64_t)t * B, s));
+            else if (d.sampled) INET_TRY(pw_sample(wt, (long)T * V, B, V, d.samples + t, T, d.rq.tick(t, V), d.level, s));
+            else INET_TRY(pw_argmax(wt, (long)T * V, B, V, d.samples + t, T, s));
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 size_t vae_decoder_ws_bytes(const inet_vae_config& c, int B, int save) {
@@ -285,327 +628,50 @@ size_t vae_decoder_ws_bytes(const inet_vae_config& c, int B, int save) {
 int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long long* target, int teacher_forced,
                     const float* p, const float* mask_beat, const float* mask_tick, float* weights,
                     long long* samples, void* ws, int save, hipStream_t s, uint64_t multinomial_seed, const sample::Request& rq) {
-    const int nb = c.beats, G = c.ticks_per_beat, T = nb * G, H = c.dec_hidden, V = c.num_notes, E = c.emb_dim, Z = c.z_dim;
-    const long BH = (long)B * H;
-    if (nb > 4) return -1;
+    if (c.beats > 4) return -1;
     if (teacher_forced && !target) return -1;
     const bool sampled = rq.uniforms != nullptr;               // temperature sampling (sample.h): a free-running inference call
     if (sampled && (teacher_forced || multinomial_seed)) return -1;
-    if (!rq.ok(V) || rq.logits) return -1;
+    if (!rq.ok(c.num_notes) || rq.logits) return -1;
+    DecCall d(c);
+    d.B = B; d.nb = c.beats; d.G = c.ticks_per_beat; d.T = d.nb * d.G; d.H = c.dec_hidden; d.V = c.num_notes; d.E = c.emb_dim; d.Z = c.z_dim;
+    d.BH = (long)B * d.H; d.pkh = (long)pk_floats(B, d.H);
+    d.save = save; d.teacher_forced = teacher_forced; d.sampled = sampled;
     // 0 = argmax; 1 = temperature; 2 = top-k / nucleus truncation in front of every draw, or the draws' log-probabilities wanted: the
     // truncating kernels; 3 = a mask of allowed tokens: the masked kernels, which are truncating ones; 4 = forced tokens: the forced
     // kernels, which are masked ones (with or without a mask)
-    const int level = rq.level(V);
-    VaeLayout L(c);
-    DecWs w{};
-    dec_carve(c, B, save, ws, w);
-    const bool pk = w.wpk_t0 != nullptr;
-    const long pkh = (long)pk_floats(B, H);
-    // Which kernels will run: the chain kernels read W_hh / W_ih as stored, only the per-step kernels want the
-    // fragment-major twins -- each is packed only if its consumer runs.
-    const bool beats_chained = pk && chain_chunk_rows(H, B, nb, 1, save) > 0;   // (one launch, or one per row chunk)
-    const bool fused_shape = pk && !teacher_forced && !multinomial_seed;
-    // batches beyond one resident launch (LatentRNN decodes 512 measures per step): the rows are independent, so the fused
-    // kernel runs over chunks of 512 rows (the 64-row build: 27 us per tick instead of 2 x 20) or 256, one launch after the other
-    const int kDecodeChunk = B % 512 == 0 ? 512 : 256;
-    const bool chain_whole = fused_shape && decode_chain_ok(B, H, V, T, G);
-    // one measure, inference: decode_b1.hip's register-resident launch (reads the row-major initial hiddens: no packed twins)
-    const bool b1_decode = chain_whole && !save && !mask_tick && w.b1ex && w.b1ex + decode_b1_words(B) == w.sync &&
-                           decode_b1_shape_ok(B, H, V, T, G, level);
-    const bool b1_fused = b1_decode && !mask_beat && decode_b1_fused((int)Z, B, V, level);   // ... with the beat path inside the same launch
-    // (a sampled call: the one fused launch that knows the rule is decode_b1.hip's; every other shape samples tick by tick below)
-    const bool fused_whole = chain_whole && (!sampled || b1_decode);
-    const bool fused_chunked = fused_shape && !sampled && !fused_whole && B > kDecodeChunk && B % kDecodeChunk == 0 &&
-                               decode_chain_ok(kDecodeChunk, H, V, T, G);
-    const bool fused_decode = fused_whole || fused_chunked;
-    // teacher-forced ticks: every input token is known and the 4 beats are independent, so each tick layer is a chain of
-    // G steps over the beats as problems -- `npl` beats per launch, as many as fit the chip at once (2 at B = 256)
-    int npl = 0;
-    if (pk && teacher_forced) {
-        for (int n = nb; n >= 1 && !npl; --n)                  // whole batch in one launch per `n` beats ...
-            if (nb % n == 0 && 3 + 2 * (nb / n) <= kSyncAreas && gru_chain_ok(H, B, G, n)) npl = n;
-        for (int n = nb; n >= 1 && !npl; --n)                  // ... else row chunks
-            if (nb % n == 0 && 3 + 2 * (nb / n) <= kSyncAreas && chain_chunk_rows(H, B, G, n, save) > 0) npl = n;
-    }
-    const bool ticks_chained = npl > 0;
-    const float* wih0 = p + L.tick[0].w_ih;                   // [3H, E+H]
-    const long ldw0 = E + H;
-    {
-        // One launch for the scattered little jobs (each used to be its own ~5 us launch): z saved for the backward pass, the
-        // chain kernels' sync areas zeroed, the beat GRU's constant input gates gvec0 = b_0 W_ih[:,0] + b_ih, the tick
-        // GRU's gather table (rows 0..V-1 = E_dec . W_ih[:, :E]^T + b_ih; row V = x_0 . W_ih[:, :E]^T + b_ih), the start
-        // token index, and the teacher-forced token copy / shift.
-        PwPrologue pr{};
-        pr.tab[0] = PwTableJob{p + L.dec_emb, E, V, wih0, ldw0, p + L.tick[0].b_ih, w.table, 3L * H, 3 * H, E};
-        pr.tab[1] = PwTableJob{p + L.x_0, E, 1, wih0, ldw0, p + L.tick[0].b_ih, w.table + (long)V * 3 * H, 3L * H, 3 * H, E};
-        pr.ntab = 2;
-        if (beats_chained || fused_decode || ticks_chained) { pr.zero_words = w.sync; pr.nzero = (long)kSyncAreas * kChainSyncWords; }
-        if (b1_decode) {                                       // ... and the b = 1 kernel's granules in front of them
-            pr.zero_words = w.b1ex; pr.nzero = decode_b1_words(B) + (long)kSyncAreas * kChainSyncWords;
-        }
-        if (save) { pr.copy_src = reinterpret_cast<const unsigned*>(z); pr.copy_dst = reinterpret_cast<unsigned*>(w.zsave); pr.ncopy = (long)B * Z; }
-        pr.axpb_a = p + L.b_0; pr.axpb_x = p + L.beat[0].w_ih; pr.axpb_incx = 1; pr.axpb_b = p + L.beat[0].b_ih;
-        pr.axpb_y = w.gvec0; pr.axpb_n = 3 * H;
-        pr.fill_ptr = w.idxV; pr.nfill = B; pr.fill_val = V;
-        if (teacher_forced) {
-            pr.tok_src = target; pr.tok_copy = samples; pr.tok_B = B; pr.tok_T = T; pr.tok_first = V; pr.tok_V = V;
-            if (ticks_chained) pr.tok_shift = w.tokin;
-        }
-        INET_TRY(pw_prologue(pr, s));
-    }
-    if (pk) {
-        const float* ins[5]; float* outs[5];
-        int n = 0;
-        if (!beats_chained && !b1_fused) {
-            ins[n] = p + L.beat[0].w_hh; outs[n++] = w.wpk_b[0];
-            ins[n] = p + L.beat[1].w_hh; outs[n++] = w.wpk_b[1];
-        }
-        if (!fused_decode && !ticks_chained) {
-            ins[n] = p + L.tick[0].w_hh; outs[n++] = w.wpk_t0;
-            ins[n] = p + L.tick[1].w_hh; outs[n++] = w.wpk_t1hh;
-            ins[n] = p + L.tick[1].w_ih; outs[n++] = w.wpk_t1ih;
-        }
-        if (n) INET_TRY(pw_pack_frag_multi(ins, outs, n, H, 3 * H, H, 0, s));
-        if (w.wpk_out && !fused_decode && !teacher_forced)
-            INET_TRY(pw_pack_frag(p + L.out_w, H, V, H, w.wpk_out, 0, 1, 0, 0, s));
-    }
-
-    if (!b1_fused) {                                           // (one measure: these eight launches are roles of decode_b1.hip's launch)
-        // ---- beat RNN (forward_beat_rnn, decoder.py:455-471) ----
-        // A sampled call reproduces itself bit for bit, so that forcing its tokens replays it (sample.h): its
-        // products keep one k range per tile.  (Without that the four-beat products of 9 to 63 rows other than 32 are split over K with
-        // f32 atomics, and two identical calls differ in the last bits of their logits.)
-        const int one_range = sampled ? 1 : 0;
-        {
-            GemmArgs g = linear_fwd_args(z, Z, p + L.zb_w, Z, p + L.zb_b, w.hb0, 2L * H, B, 2 * H, Z, EPI_SELU);
-            g.one_range = one_range;
-            INET_TRY(launch_gemm(g, s));
-        }
-        DirFwd d{};
-        d.W_hh = p + L.beat[0].w_hh; d.b_hh = p + L.beat[0].b_hh;
-        d.gvec = w.gvec0;
-        d.h0 = w.hb0; d.h0_ld = 2L * H;
-        d.out = w.beat0; d.out_ld = H; d.out_ts = BH;
-        if (mask_beat) { d.outm = w.beat0m; d.outm_ld = H; d.outm_ts = BH; d.mask = mask_beat; d.mask_ld = H; d.mask_ts = BH; }
-        if (save) { d.sv = w.svb0; d.sv_astride = nb * BH; }
-        d.Wpk_hh = w.wpk_b[0]; d.hpk = w.hpk_b;
-        if (beats_chained) { d.sync = w.sync; d.sync_prezeroed = 1; }   // 4 steps in one launch (8 groups of 32 rows at B = 256)
-        INET_TRY(gru_layer_fwd(H, B, nb, 1, &d, s));
-        const float* xb = mask_beat ? w.beat0m : w.beat0;
-        {
-            GemmArgs g = linear_fwd_args(xb, H, p + L.beat[1].w_ih, H, p + L.beat[1].b_ih, w.gi1b, 3L * H, nb * B, 3 * H, H, EPI_NONE);
-            g.one_range = one_range;
-            INET_TRY(launch_gemm(g, s));
-        }
-        d = DirFwd{};
-        d.W_hh = p + L.beat[1].w_hh; d.b_hh = p + L.beat[1].b_hh;
-        d.gi = w.gi1b; d.gi_ld = 3L * H; d.gi_ts = 3 * BH;
-        d.h0 = w.hb0 + H; d.h0_ld = 2L * H;
-        d.out = w.beat_out; d.out_ld = H; d.out_ts = BH;
-        if (save) { d.sv = w.svb1; d.sv_astride = nb * BH; }
-        d.Wpk_hh = w.wpk_b[1]; d.hpk = w.hpk_b;
-        if (beats_chained) { d.sync = w.sync + kChainSyncWords; d.sync_prezeroed = 1; }
-        INET_TRY(gru_layer_fwd(H, B, nb, 1, &d, s));
-
-        // ---- per-beat constants for the tick RNN (decoder.py:494-495), all 4 beats at once ----
-        {
-            GemmArgs bt[2] = {linear_fwd_args(w.beat_out, H, p + L.bh_w, H, p + L.bh_b, w.ht0, 2L * H, nb * B, 2 * H, H, EPI_SELU),
-                              linear_fwd_args(w.beat_out, H, p + L.bi_w, H, p + L.bi_b, w.c_all, H, nb * B, H, H, EPI_SELU)};
-            bt[0].one_range = bt[1].one_range = one_range;
-            INET_TRY(launch_gemm_group(bt, 2, s));
-        }
-        if (pk && !ticks_chained && !fused_chunked && !b1_decode)  // packed initial tick hiddens: [layer][beat]
-            for (int l = 0; l < 2; ++l)
-                INET_TRY(pw_pack_frag(w.ht0 + (long)l * H, 2L * H, B, H, w.ht0pk + (long)l * nb * pkh, 0, nb, (long)B * 2 * H, pkh, s));
-        {
-            GemmArgs g = linear_fwd_args(w.c_all, H, wih0 + E, ldw0, nullptr, w.cgi, 3L * H, nb * B, 3 * H, H, EPI_NONE);
-            g.one_range = one_range;
-            INET_TRY(launch_gemm(g, s));
-        }
-    }
-
+    d.level = rq.level(d.V);
+    d.z = z; d.p = p; d.mask_beat = mask_beat; d.mask_tick = mask_tick; d.target = target; d.weights = weights; d.samples = samples;
+    d.wih0 = p + d.L.tick[0].w_ih; d.ldw0 = d.E + d.H;
+    d.seed = multinomial_seed; d.rq = rq; d.s = s;
+    dec_carve(c, B, save, ws, d.w);
+    d.r = dec_route(c, B, save, teacher_forced != 0, multinomial_seed != 0, mask_beat != nullptr, mask_tick != nullptr, d.level, sampled, d.w);
+    INET_TRY(dec_prologue(d));
+    INET_TRY(dec_pack_weights(d));
+    if (d.r.beats != kBeatsFolded) INET_TRY(dec_beat_path(d));   // (one measure: these eight launches are roles of decode_b1.hip's launch)
     // ---- tick RNN (forward_tick_rnn, decoder.py:473-529) ----
-    if (ticks_chained) {
-        const float* x1 = mask_tick ? w.h0m : w.h0seq;
-        for (int layer = 0; layer < 2; ++layer) {
-            if (layer == 1)                                    // layer 1's input-side pre-activations for all 24 ticks at once
-                INET_TRY(linear_fwd(x1, H, p + L.tick[1].w_ih, H, p + L.tick[1].b_ih, w.gi1t, 3L * H, T * B, 3 * H, H, EPI_NONE, s));
-            for (int i0 = 0; i0 < nb; i0 += npl) {
-                DirFwd dd[4];
-                for (int k = 0; k < npl; ++k) {
-                    const int i = i0 + k;
-                    DirFwd& D = dd[k];
-                    D = DirFwd{};
-                    D.W_hh = p + L.tick[layer].w_hh; D.b_hh = p + L.tick[layer].b_hh;
-                    D.h0 = w.ht0 + (long)i * B * 2 * H + layer * H; D.h0_ld = 2L * H;
-                    D.out_ld = H; D.out_ts = BH;
-                    if (layer == 0) {
-                        D.gi = w.cgi + (long)i * B * 3 * H; D.gi_ld = 3L * H; D.gi_ts = 0;   // the beat's constant half
-                        D.table = w.table; D.table_ld = 3L * H;                              // the token half
-                        D.idx = w.tokin + (long)i * G; D.idx_bs = T; D.idx_ts = 1;
-                        D.out = w.h0seq + (long)i * G * BH;
-                        if (mask_tick) {
-                            D.outm = w.h0m + (long)i * G * BH; D.outm_ld = H; D.outm_ts = BH;
-                            D.mask = mask_tick + (long)i * G * BH; D.mask_ld = H; D.mask_ts = BH;
-                        }
-                        if (save) { D.sv = w.svt0 + (long)i * G * BH; D.sv_astride = (long)T * BH; }
-                        D.Wpk_hh = w.wpk_t0; D.hpk = w.hpk_t0 + (long)i * 3 * pkh;
-                    } else {
-                        D.gi = w.gi1t + (long)i * G * 3 * BH; D.gi_ld = 3L * H; D.gi_ts = 3 * BH;
-                        D.out = w.h1seq + (long)i * G * BH;
-                        if (save) { D.sv = w.svt1 + (long)i * G * BH; D.sv_astride = (long)T * BH; }
-                        D.Wpk_hh = w.wpk_t1hh; D.hpk = w.hpk_t1 + (long)i * 3 * pkh;
-                    }
-                }
-                dd[0].sync = w.sync + (long)(2 + layer * (nb / npl) + i0 / npl) * kChainSyncWords;
-                dd[0].sync_prezeroed = 1;
-                INET_TRY(gru_layer_fwd(H, B, G, npl, dd, s));
-            }
-        }
-        INET_TRY(linear_fwd(w.h1seq, H, p + L.out_w, H, p + L.out_b, w.wtm, V, T * B, V, H, EPI_RELU, s));
-        INET_TRY(pw_swap01(w.wtm, T, B, V, weights, s));             // [T,B,V] -> [B,T,V]
-        return 0;
+    switch (d.r.ticks) {
+        case kTfChained: return dec_ticks_tf_chained(d);
+        case kTfSteps: return dec_ticks_tf_steps(d);
+        case kFused: case kFusedChunked: return dec_ticks_fused(d);
+        default: return dec_ticks_per_tick(d);
     }
-    if (teacher_forced) {
-        // Every input token is known, and the tick GRU's hidden state is re-initialised per beat, so the 4 beats are
-        // independent: 6 steps x 4 problems per layer instead of 24 dependent steps, and ONE output projection.
-        const long as = (long)T * BH;
-        for (int j = 0; j < G; ++j) {
-            GruFwdBatch b0{}, b1{};
-            b0.H = b1.H = H; b0.nprob = b1.nprob = nb;
-            for (int i = 0; i < nb; ++i) {
-                const int t = i * G + j;
-                GruFwdProb& P0 = b0.p[i];
-                P0.B = B;
-                if (j == 0) { P0.h_prev = w.ht0 + (long)i * B * 2 * H; P0.ld_hprev = 2L * H; }
-                else { P0.h_prev = w.h0seq + (long)(t - 1) * BH; P0.ld_hprev = H; }
-                P0.W_hh = p + L.tick[0].w_hh; P0.b_hh = p + L.tick[0].b_hh;
-                P0.gi_dense = w.cgi + (long)i * B * 3 * H; P0.ld_gi = 3L * H;
-                P0.gi_table = w.table; P0.ld_table = 3L * H;
-                if (t == 0) { P0.idx = w.idxV; P0.idx_stride = 1; }
-                else { P0.idx = samples + (t - 1); P0.idx_stride = T; }
-                P0.h_new = w.h0seq + (long)t * BH; P0.ld_hnew = H;
-                if (mask_tick) { P0.h_masked = w.h0m + (long)t * BH; P0.ld_hm = H; P0.mask = mask_tick + (long)t * BH; P0.ld_mask = H; }
-                if (save) {
-                    float* q = w.svt0 + (long)t * BH;
-                    P0.sv_r = q; P0.sv_z = q + as; P0.sv_n = q + 2 * as; P0.sv_ghn = q + 3 * as; P0.sv_hprev = q + 4 * as;
-                }
-                GruFwdProb& P1 = b1.p[i];
-                if (pk) tick_pk(w, i, j, nb, pkh, mask_tick != nullptr, P0, P1);
-                P1.B = B;
-                if (j == 0) { P1.h_prev = w.ht0 + (long)i * B * 2 * H + H; P1.ld_hprev = 2L * H; }
-                else { P1.h_prev = w.h1seq + (long)(t - 1) * BH; P1.ld_hprev = H; }
-                P1.W_hh = p + L.tick[1].w_hh; P1.b_hh = p + L.tick[1].b_hh;
-                P1.x = (mask_tick ? w.h0m : w.h0seq) + (long)t * BH; P1.ldx = H; P1.K2 = H;
-                P1.W_ih = p + L.tick[1].w_ih; P1.ld_wih = H; P1.b_ih = p + L.tick[1].b_ih;
-                P1.h_new = w.h1seq + (long)t * BH; P1.ld_hnew = H;
-                if (save) {
-                    float* q = w.svt1 + (long)t * BH;
-                    P1.sv_r = q; P1.sv_z = q + as; P1.sv_n = q + 2 * as; P1.sv_ghn = q + 3 * as; P1.sv_hprev = q + 4 * as;
-                }
-            }
-            INET_TRY(launch_gru_fwd(b0, s));
-            INET_TRY(launch_gru_fwd(b1, s));
-        }
-        INET_TRY(linear_fwd(w.h1seq, H, p + L.out_w, H, p + L.out_b, w.wtm, V, T * B, V, H, EPI_RELU, s));
-        INET_TRY(pw_swap01(w.wtm, T, B, V, weights, s));             // [T,B,V] -> [B,T,V]
-        return 0;
-    }
-    if (fused_decode) {
-        // all 24 free-running ticks (layer 0, layer 1, projection, argmax, token feedback) in ONE launch: inference, and
-        // the free-running half of the training steps (dropout mask between the layers, backward saves written on the way)
-        const int Bc = fused_whole ? B : kDecodeChunk;
-        const long pkc = (long)pk_floats(Bc, H);
-        for (int r0 = 0; r0 < B; r0 += Bc) {
-            if (fused_chunked)                                 // the chunk's initial tick hiddens, fragment-major [layer][beat]
-                for (int l = 0; l < 2; ++l)
-                    INET_TRY(pw_pack_frag(w.ht0 + (long)r0 * 2 * H + (long)l * H, 2L * H, Bc, H, w.ht0pk + (long)l * nb * pkc, 0, nb,
-                                          (long)B * 2 * H, pkc, s));
-            DecodeChainArgs a{};
-            a.B = Bc; a.Bs = B; a.H = H; a.T = T; a.G = G; a.V = V;
-            a.W_hh0 = p + L.tick[0].w_hh; a.b_hh0 = p + L.tick[0].b_hh;
-            a.cgi = w.cgi + (long)r0 * 3 * H; a.table = w.table;
-            a.W_ih1 = p + L.tick[1].w_ih; a.b_ih1 = p + L.tick[1].b_ih; a.W_hh1 = p + L.tick[1].w_hh; a.b_hh1 = p + L.tick[1].b_hh;
-            a.W_out = p + L.out_w; a.b_out = p + L.out_b;
-            a.ht0 = w.ht0 + (long)r0 * 2 * H; a.ht0pk = w.ht0pk;
-            a.hx0 = w.hpk_t0; a.hx1 = w.hpk_t1; a.amax = w.amax;
-            a.b1ex = b1_decode ? reinterpret_cast<unsigned long long*>(w.b1ex) : nullptr;
-            static const bool b1st = [] { const char* v = std::getenv("INET_DECODE_B1_STAMPS"); return v && v[0] == '1'; }();
-            a.b1stamps = (b1_decode && b1st && T <= 32) ? reinterpret_cast<unsigned long long*>(w.b1stamps) : nullptr;
-            if (b1_fused) {
-                DecodeB1Beat& bt = a.beat;
-                bt.z = z; bt.zb_w = p + L.zb_w; bt.zb_b = p + L.zb_b; bt.gvec0 = w.gvec0;
-                bt.W_hh0 = p + L.beat[0].w_hh; bt.b_hh0 = p + L.beat[0].b_hh;
-                bt.W_ih1 = p + L.beat[1].w_ih; bt.b_ih1 = p + L.beat[1].b_ih; bt.W_hh1 = p + L.beat[1].w_hh; bt.b_hh1 = p + L.beat[1].b_hh;
-                bt.bh_w = p + L.bh_w; bt.bh_b = p + L.bh_b; bt.bi_w = p + L.bi_w; bt.bi_b = p + L.bi_b;
-                bt.wih0_c = wih0 + E; bt.wih0_ld = ldw0;
-            }
-            a.weights = weights + (long)r0 * T * V; a.samples = samples + (long)r0 * T;
-            a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0;   // (later chunks: the launcher zeroes the area)
-            a.draw = rq;                                       // (sampled: one whole launch, never chunks)
-            if (mask_tick) { a.mask = mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
-            if (save) {
-                a.sv0 = w.svt0 + (long)r0 * H; a.sv1 = w.svt1 + (long)r0 * H; a.sv_stride = (long)T * BH;
-                a.h0out = (mask_tick ? w.h0m : w.h0seq) + (long)r0 * H; a.h1seq = w.h1seq + (long)r0 * H;
-            }
-            INET_TRY(launch_decode_chain(a, s));
-        }
-        return 0;
-    }
-    for (int t = 0; t < T; ++t) {                              // free-running ticks, one launch per layer and tick
-        const int i = t / G, j = t % G;
-        GruFwdBatch b0{};
-        b0.H = H; b0.nprob = 1;
-        GruFwdProb& P0 = b0.p[0];
-        P0.B = B;
-        if (j == 0) { P0.h_prev = w.ht0 + (long)i * B * 2 * H; P0.ld_hprev = 2L * H; }
-        else { P0.h_prev = w.h0seq + (long)(t - 1) * BH; P0.ld_hprev = H; }
-        P0.W_hh = p + L.tick[0].w_hh; P0.b_hh = p + L.tick[0].b_hh;
-        P0.gi_dense = w.cgi + (long)i * B * 3 * H; P0.ld_gi = 3L * H;
-        P0.gi_table = w.table; P0.ld_table = 3L * H;
-        if (t == 0) { P0.idx = w.idxV; P0.idx_stride = 1; }
-        else { P0.idx = samples + (t - 1); P0.idx_stride = T; }
-        P0.h_new = w.h0seq + (long)t * BH; P0.ld_hnew = H;
-        if (mask_tick) { P0.h_masked = w.h0m + (long)t * BH; P0.ld_hm = H; P0.mask = mask_tick + (long)t * BH; P0.ld_mask = H; }
-        if (save) {
-            float* q = w.svt0 + (long)t * BH; const long as = (long)T * BH;
-            P0.sv_r = q; P0.sv_z = q + as; P0.sv_n = q + 2 * as; P0.sv_ghn = q + 3 * as; P0.sv_hprev = q + 4 * as;
-        }
-        GruFwdBatch b1{};
-        b1.H = H; b1.nprob = 1;
-        GruFwdProb& P1 = b1.p[0];
-        P1.B = B;
-        if (j == 0) { P1.h_prev = w.ht0 + (long)i * B * 2 * H + H; P1.ld_hprev = 2L * H; }
-        else { P1.h_prev = w.h1seq + (long)(t - 1) * BH; P1.ld_hprev = H; }
-        P1.W_hh = p + L.tick[1].w_hh; P1.b_hh = p + L.tick[1].b_hh;
-        P1.x = (mask_tick ? w.h0m : w.h0seq) + (long)t * BH; P1.ldx = H; P1.K2 = H;
-        P1.W_ih = p + L.tick[1].w_ih; P1.ld_wih = H; P1.b_ih = p + L.tick[1].b_ih;
-        P1.h_new = w.h1seq + (long)t * BH; P1.ld_hnew = H;
-        if (save) {
-            float* q = w.svt1 + (long)t * BH; const long as = (long)T * BH;
-            P1.sv_r = q; P1.sv_z = q + as; P1.sv_n = q + 2 * as; P1.sv_ghn = q + 3 * as; P1.sv_hprev = q + 4 * as;
-        }
-        if (pk) tick_pk(w, i, j, nb, pkh, mask_tick != nullptr, P0, P1);
-        INET_TRY(launch_gru_fwd(b0, s));
-        INET_TRY(launch_gru_fwd(b1, s));
+}
 
-        // logits = ReLU(h_top . Wo^T + bo) straight into weights[:, t, :], fused with the argmax that feeds tick t+1
-        const bool draw = multinomial_seed != 0;               // decoder.py:506-509: sample the fed-back token
-        int rc = draw || sampled ? 1 : launch_logits_argmax(w.h1seq + (long)t * BH, H, B, H, p + L.out_w, p + L.out_b, V,
-                                                 weights + (long)t * V, (long)T * V, samples + t,
-                                                 T, s, pk ? P1.hpk_new : nullptr, w.wpk_out);
-        if (rc < 0) return rc;
-        if (rc == 1) {                                         // V not a multiple of 16 (or > 64), or sampling: two kernels
-            INET_TRY(linear_fwd(w.h1seq + (long)t * BH, H, p + L.out_w, H, p + L.out_b, weights + (long)t * V,
-                                (long)T * V, B, V, H, EPI_RELU, s));
-            if (draw) INET_TRY(pw_sample_multinomial(weights + (long)t * V, (long)T * V, B, V, samples + t, T,
-                                                     multinomial_seed, (uint64_t)t * B, s));
-            else if (sampled) INET_TRY(pw_sample(weights + (long)t * V, (long)T * V, B, V, samples + t, T, rq.tick(t, V), level, s));
-            else INET_TRY(pw_argmax(weights + (long)t * V, (long)T * V, B, V, samples + t, T, s));
-        }
-    }
+// inet_vae_decoder_route: the route of the call with these arguments, from dec_route() on a carve that is never dereferenced
+int vae_decoder_route(const inet_vae_config& c, int B, int save, int teacher_forced, int flags, int level, int32_t* out, int n_out) {
+    const bool sampled = level > 0;
+    if (c.beats > 4 || level < 0 || level > 4 || !out || n_out < 13) return -1;
+    if (sampled && (teacher_forced || (flags & 1))) return -1;
+    DecWs w{};
+    dec_carve(c, B, save, reinterpret_cast<char*>(static_cast<uintptr_t>(1) << 30), w);
+    const DecRoute r = dec_route(c, B, save, teacher_forced != 0, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, level, sampled, w);
+    const int32_t v[13] = {r.beats, r.ticks, r.npl, r.chunk_rows, r.b1, r.b1_fused, r.zero, r.pack_beat, r.pack_tick, r.pack_out, r.ht0, r.pk,
+                           r.fused_prezeroed};
+    for (int i = 0; i < 13; ++i) out[i] = v[i];
     return 0;
 }
+
 
 int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, const float* weights,
                     const long long* tokens_in, const float* p, float* g, const float* mask_beat,
@@ -641,21 +707,25 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
     INET_TRY(linear_dgrad(w.dlg, V, p + L.out_w, H, w.dh1top, H, T * B, V, H, EPI_NONE, nullptr, 0, ACC_STORE, s));
 
     // ---- tick RNN layer 1: 6 steps x 4 beats ----
-    DirBwd d[4];
-    for (int i = 0; i < nb; ++i) {
-        DirBwd& D = d[i];
-        D = DirBwd{};
-        D.W_hhT = w.whhT[3];
-        D.dout = w.dh1top + (long)i * G * BH; D.dout_ld = H; D.dout_ts = BH;
-        D.sv = w.svt1 + (long)i * G * BH; D.sv_astride = TBH;
-        D.dgi = w.dgi1t + (long)i * G * 3 * BH; D.dgi_ld = 3L * H; D.dgi_ts = 3 * BH;
-        D.dgh = w.dgh1t + (long)i * G * 3 * BH;
+    int dcgi_done = 0;
+    // beat i of tick layer `layer` as one problem of the layer's launch (4 beats = 4 problems, 2 row tiles per workgroup)
+    const auto tick_dir_bwd = [&](int layer, int i) {
+        DirBwd D{};
+        D.W_hhT = w.whhT[2 + layer];
+        D.dout = (layer ? w.dh1top : w.dx1t) + (long)i * G * BH; D.dout_ld = H; D.dout_ts = BH;
+        D.sv = (layer ? w.svt1 : w.svt0) + (long)i * G * BH; D.sv_astride = TBH;
+        D.dgi = (layer ? w.dgi1t : w.dgi0t) + (long)i * G * 3 * BH; D.dgi_ld = 3L * H; D.dgi_ts = 3 * BH;
+        D.dgh = (layer ? w.dgh1t : w.dgh0t) + (long)i * G * 3 * BH;
         D.dhz = w.dhz + (long)i * 2 * BH;
-        if (g) { D.db_ih = g + L.tick[1].b_ih; D.db_hh = g + L.tick[1].b_hh; }
-        D.dh0 = w.dht0 + (long)i * B * 2 * H + H; D.dh0_ld = 2L * H; D.dh0_acc = 0;
-        D.Wpk_hhT = w.wpkT[3]; D.dghpk = w.dghpk ? w.dghpk + (long)i * 3 * pkg : nullptr;
-        if (ticks_chained) { D.W_hh = p + L.tick[1].w_hh; D.sync = w.sync; D.sync_prezeroed = 1; }   // 4 beats = 4 problems, 2 row tiles per workgroup
-    }
+        if (g) { D.db_ih = g + L.tick[layer].b_ih; D.db_hh = g + L.tick[layer].b_hh; }
+        D.dh0 = w.dht0 + (long)i * B * 2 * H + layer * H; D.dh0_ld = 2L * H; D.dh0_acc = 0;
+        D.Wpk_hhT = w.wpkT[2 + layer]; D.dghpk = w.dghpk ? w.dghpk + (long)i * 3 * pkg : nullptr;
+        if (ticks_chained) { D.W_hh = p + L.tick[layer].w_hh; D.sync = w.sync + (1 - layer) * kChainSyncWords; D.sync_prezeroed = 1; }
+        if (layer == 0) { D.dgi_sum = w.dcgi + (long)i * 3 * BH; D.dgi_sum_done = &dcgi_done; }   // beat-constant input half, see below
+        return D;
+    };
+    DirBwd d[4];
+    for (int i = 0; i < nb; ++i) d[i] = tick_dir_bwd(1, i);
     INET_TRY(gru_layer_bwd(H, B, G, nb, d, s));
     const float* x1 = mask_tick ? w.h0m : w.h0seq;
     // Layer 1's leaf work is issued BEHIND the layer-0 chain, not beside it (round 5, profiles/r05_s_leaf_schedule.txt): beside the
@@ -666,22 +736,7 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
                           mask_tick ? EPI_MUL_AUX : EPI_NONE, mask_tick, H, ACC_STORE, s));
 
     // ---- tick RNN layer 0 ----
-    int dcgi_done = 0;
-    for (int i = 0; i < nb; ++i) {
-        DirBwd& D = d[i];
-        D = DirBwd{};
-        D.W_hhT = w.whhT[2];
-        D.dout = w.dx1t + (long)i * G * BH; D.dout_ld = H; D.dout_ts = BH;
-        D.sv = w.svt0 + (long)i * G * BH; D.sv_astride = TBH;
-        D.dgi = w.dgi0t + (long)i * G * 3 * BH; D.dgi_ld = 3L * H; D.dgi_ts = 3 * BH;
-        D.dgh = w.dgh0t + (long)i * G * 3 * BH;
-        D.dhz = w.dhz + (long)i * 2 * BH;
-        if (g) { D.db_ih = g + L.tick[0].b_ih; D.db_hh = g + L.tick[0].b_hh; }
-        D.dh0 = w.dht0 + (long)i * B * 2 * H; D.dh0_ld = 2L * H; D.dh0_acc = 0;
-        D.Wpk_hhT = w.wpkT[2]; D.dghpk = w.dghpk ? w.dghpk + (long)i * 3 * pkg : nullptr;
-        if (ticks_chained) { D.W_hh = p + L.tick[0].w_hh; D.sync = w.sync + kChainSyncWords; D.sync_prezeroed = 1; }
-        D.dgi_sum = w.dcgi + (long)i * 3 * BH; D.dgi_sum_done = &dcgi_done;     // beat-constant input half, see below
-    }
+    for (int i = 0; i < nb; ++i) d[i] = tick_dir_bwd(0, i);
     INET_TRY(gru_layer_bwd(H, B, G, nb, d, s));
     const float* wih0 = p + L.tick[0].w_ih;
     const long ldw0 = E + H;
@@ -725,30 +780,25 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
     INET_TRY(linear_dgrad(w.dc_all, H, p + L.bi_w, H, w.dbeat_out, H, nb * B, H, H, EPI_NONE, nullptr, 0, ACC_ADD, s));
 
     // ---- beat RNN ----
-    DirBwd b{};
-    b.W_hhT = w.whhT[1];
-    b.dout = w.dbeat_out; b.dout_ld = H; b.dout_ts = BH;
-    b.sv = w.svb1; b.sv_astride = nb * BH;
-    b.dgi = w.dgi1b; b.dgi_ld = 3L * H; b.dgi_ts = 3 * BH;
-    b.dgh = w.dgh1b; b.dhz = w.dhz;
-    if (g) { b.db_ih = g + L.beat[1].b_ih; b.db_hh = g + L.beat[1].b_hh; }
-    b.dh0 = w.dhb0 + H; b.dh0_ld = 2L * H;
-    b.Wpk_hhT = w.wpkT[1]; b.dghpk = w.dghpk;
-    if (beats_chained) { b.W_hh = p + L.beat[1].w_hh; b.sync = w.sync + 2 * kChainSyncWords; b.sync_prezeroed = 1; }
+    const auto beat_dir_bwd = [&](int layer) {
+        DirBwd b{};
+        b.W_hhT = w.whhT[layer];
+        b.dout = layer ? w.dbeat_out : w.dxb; b.dout_ld = H; b.dout_ts = BH;
+        b.sv = layer ? w.svb1 : w.svb0; b.sv_astride = nb * BH;
+        b.dgi = layer ? w.dgi1b : w.dgi0b; b.dgi_ld = 3L * H; b.dgi_ts = 3 * BH;
+        b.dgh = layer ? w.dgh1b : w.dgh0b; b.dhz = w.dhz;
+        if (g) { b.db_ih = g + L.beat[layer].b_ih; b.db_hh = g + L.beat[layer].b_hh; }
+        b.dh0 = w.dhb0 + layer * H; b.dh0_ld = 2L * H;
+        b.Wpk_hhT = w.wpkT[layer]; b.dghpk = w.dghpk;
+        if (beats_chained) { b.W_hh = p + L.beat[layer].w_hh; b.sync = w.sync + (3 - layer) * kChainSyncWords; b.sync_prezeroed = 1; }
+        return b;
+    };
+    DirBwd b = beat_dir_bwd(1);
     INET_TRY(gru_layer_bwd(H, B, nb, 1, &b, s));
     const float* xb = mask_beat ? w.beat0m : w.beat0;
     INET_TRY(linear_dgrad(w.dgi1b, 3L * H, p + L.beat[1].w_ih, H, w.dxb, H, nb * B, 3 * H, H,
                           mask_beat ? EPI_MUL_AUX : EPI_NONE, mask_beat, H, ACC_STORE, s));
-    b = DirBwd{};
-    b.W_hhT = w.whhT[0];
-    b.dout = w.dxb; b.dout_ld = H; b.dout_ts = BH;
-    b.sv = w.svb0; b.sv_astride = nb * BH;
-    b.dgi = w.dgi0b; b.dgi_ld = 3L * H; b.dgi_ts = 3 * BH;
-    b.dgh = w.dgh0b; b.dhz = w.dhz;
-    if (g) { b.db_ih = g + L.beat[0].b_ih; b.db_hh = g + L.beat[0].b_hh; }
-    b.dh0 = w.dhb0; b.dh0_ld = 2L * H;
-    b.Wpk_hhT = w.wpkT[0]; b.dghpk = w.dghpk;
-    if (beats_chained) { b.W_hh = p + L.beat[0].w_hh; b.sync = w.sync + 3 * kChainSyncWords; b.sync_prezeroed = 1; }
+    b = beat_dir_bwd(0);
     INET_TRY(gru_layer_bwd(H, B, nb, 1, &b, s));
 
     // ---- z -> beat hidden ----

@@ -319,6 +319,31 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
     return weights, samples, ws
 
 
+DECODER_ROUTE_KEYS = ("beats", "ticks", "npl", "chunk_rows", "b1", "b1_fused", "zero", "pack_beat_twins", "pack_tick_twins", "pack_out_w",
+                      "pack_ht0", "pk", "fused_prezeroed")
+DECODER_BEATS = ("steps", "chained", "folded")
+DECODER_TICKS = ("TfChained", "TfSteps", "Fused", "FusedChunked", "PerTick")
+DECODER_ZERO = ("none", "sync", "b1ex+sync")
+DECODER_HT0 = ("no", "once", "per_chunk")
+
+
+def decoder_route(cfg, B, save=False, teacher_forced=False, multinomial_seed=False, mask_beat=False, mask_tick=False, level=0):
+    """What decoder_fwd launches for such a call under the options set now, without a GPU (inet_vae_decoder_route, the function the
+    launch itself asks): a dict of DECODER_ROUTE_KEYS with "beats", "ticks", "zero" and "pack_ht0" as names (DECODER_BEATS,
+    DECODER_TICKS, DECODER_ZERO, DECODER_HT0) and the flags as bools.  level: 0 argmax, 1 temperature, 2 truncated, 3 masked, 4 forced."""
+    out = (C.c_int32 * 13)()
+    flags = int(bool(multinomial_seed)) | 2 * int(mask_beat is not None and mask_beat is not False) | \
+        4 * int(mask_tick is not None and mask_tick is not False)
+    check(_lib.lib().inet_vae_decoder_route(C.byref(cfg), int(B), int(bool(save)), int(bool(teacher_forced)), flags, int(level), out, 13),
+          "inet_vae_decoder_route")
+    r = dict(zip(DECODER_ROUTE_KEYS, out))
+    r["beats"], r["ticks"] = DECODER_BEATS[r["beats"]], DECODER_TICKS[r["ticks"]]
+    r["zero"], r["pack_ht0"] = DECODER_ZERO[r["zero"]], DECODER_HT0[r["pack_ht0"]]
+    for k in ("b1", "b1_fused", "pack_beat_twins", "pack_tick_twins", "pack_out_w", "pk", "fused_prezeroed"):
+        r[k] = bool(r[k])
+    return r
+
+
 def decoder_bwd(cfg, dweights, weights, samples, params, grads, mask_beat, mask_tick, ws, need_dz=True):
     B = weights.shape[0]
     _f32c(dweights); _f32c(weights); _i64c(samples)
