@@ -715,14 +715,18 @@ int inet_decode_b1_plan_trunc(int B, int V, int Z, int* out8);
 /* What a decoder forward call launches, under the options set now (inet_set_option keys 4, 15) and on this chip (CUs, or
  * INET_CHAIN_CUS), without a GPU or a workspace: the route function that inet_vae_decoder_fwd and the inet_vae_decoder_sample entries
  * ask themselves (csrc/vae.hip dec_route).  flags: bit 0 = a multinomial seed, bit 1 = mask_beat given, bit 2 = mask_tick given; level:
- * 0 = argmax, 1 = temperature, 2 = truncated or logp, 3 = a mask of allowed tokens, 4 = forced tokens.  out (n_out >= 13) = {beat path
+ * 0 = argmax, 1 = temperature, 2 = truncated or logp, 3 = a mask of allowed tokens, 4 = forced tokens.  out (n_out >= 13; 13 values are
+ * written, 16 where n_out >= 16) = {beat path
  * (0 = one launch per step, 1 = chain launches, 2 = folded into the register-resident launch), tick path (0 = teacher-forced chains,
  * 1 = teacher-forced steps, 2 = one fused launch, 3 = fused launches over row chunks, 4 = tick by tick), beats per teacher-forced chain
  * launch, rows per chunk (512 / 256), the fused launch is the register-resident one, ... with the beat path inside it, words the
  * prologue zeroes (0 = none, 1 = the sync areas, 2 = the register-resident launch's granules and the sync areas), fragment-major twins
  * packed: the beat layers' W_hh, the tick layers' three, the output projection's, the initial tick hiddens (0 = no, 1 = once for all
  * rows, 2 = per chunk), the workspace carries twins at all, the first fused launch finds its counters zeroed by the prologue (0 where
- * row-chunked beat chains counted on them: it zeroes them itself)}.  0, or -1 for a call the entries refuse (more than 4 beats, a level above
+ * row-chunked beat chains counted on them: it zeroes them itself); [13] bit a = the beat path's launches count on sync area a of the
+ * workspace, [14] the same for the tick path's, [15] how many chain or fused launches of the call zero their own counters (their area
+ * was counted on since the prologue zeroed it)}: [12] .. [15] are what a dry run of the call's ledger of sync areas (csrc/sync_areas.h)
+ * over the route's launches gives, the ledger the call itself takes its areas from.  0, or -1 for a call the entries refuse (more than 4 beats, a level above
  * 0 with teacher forcing or a seed), a level outside 0..4, flags outside 0..7, a null or short output -- nothing is written then. */
 int inet_vae_decoder_route(const inet_vae_config* cfg, int batch, int save, int teacher_forced, int flags, int level, int32_t* out,
                            int n_out);

@@ -344,7 +344,8 @@ int inet_bigru2_fwd(int B, int T, int K, int H, const float* x, const float* x_s
     const long BH = (long)B * H;
     float* hn[4] = {nullptr, nullptr, nullptr, nullptr};
     if (h_n) for (int i = 0; i < 4; ++i) hn[i] = h_n + i * BH;
-    INET_TRY(bigru2_core_fwd(B, T, H, P, in, h0, mask, h_n ? hn : nullptr, H, w.g, save, s));
+    SyncLedger areas(w.g.sync);                                      // (nothing zeroed yet: the core does where it pays)
+    INET_TRY(bigru2_core_fwd(B, T, H, P, in, h0, mask, h_n ? hn : nullptr, H, w.g, save, s, areas));
     if (out) INET_TRY(pw_swap01(w.g.h1, T, B, 2 * H, out, s));       // [T,B,2H] -> [B,T,2H]
     return 0;
 }

@@ -10,8 +10,10 @@ constexpr int kChainCounterStride = 64;           // words between two group cou
 constexpr int kChainStatusWord = kChainMaxGroups * kChainCounterStride;   // the launch's status word (abort flag)
 constexpr int kChainZeroWord = kChainStatusWord + 64; // words [+0, +1] stay zero: the target of absent operand pointers
 constexpr int kChainSyncWords = kChainZeroWord + 4;
-// A workspace holds kSyncAreas such areas: a library call zeroes all of them with ONE memset and gives each of its chain
-// launches its own (`prezeroed`), instead of one 5 us fill kernel in front of every launch (11 per training step).
+// A workspace holds kSyncAreas such areas: a library call zeroes all of them at once (one memset, or its prologue launch) instead of
+// one 5 us fill kernel in front of every launch (11 per training step), and its ledger (sync_areas.h SyncLedger) hands them to the
+// chain launches.  A launch is told `prezeroed` only while nobody has counted on its area since; launches share areas -- the row
+// chunks of a layer, odd forward chunks on the area behind their layer's -- and whoever comes second has its launcher zero the area.
 constexpr int kSyncAreas = 8;
 
 // Piece outputs of a second-generation chain kernel (gemm_bf3.h layouts) for the bf16-matrix-core products that consume the

@@ -9,6 +9,7 @@
 #include "pointwise.h"
 #include "side.h"
 #include "gru_chain.h"
+#include "sync_areas.h"
 
 #define INET_TRY(expr) do { int _rc = (expr); if (_rc != 0) return _rc; } while (0)
 
@@ -39,9 +40,9 @@ struct DirFwd {
     int reverse;
     // fragment-major fast path (both or neither; H % 256 == 0): packed W_hh and a 2 x pk_floats(B,H) ping-pong buffer
     const float* Wpk_hh; float* hpk;
-    // chain kernel (gru_chain.h): kChainSyncWords words for the launch's group counters, given for direction 0 (or null)
-    unsigned* sync;
-    int sync_prezeroed;                                       // those words are zero already (one memset per library call)
+    // chain kernels (gru_chain.h): the call's ledger of sync areas and the layer's base area in it, given for direction 0 (or null);
+    // gru_layer_fwd_areas says which areas the layer's launches take from there
+    SyncLedger* areas; int area;
     // piece outputs for the bf16-matrix-core products (gru_chain.h ChainEmit; B_full / r0 are filled in by gru_layer_fwd);
     // `emitted` is set by gru_layer_fwd / gru_layer_bwd to what the kernels they launched wrote (bit 0: rows, bit 1: the transposed
     // pieces; 0: nothing) -- the caller splits the rest from the f32 arrays with bf3_split
@@ -65,8 +66,7 @@ struct DirBwd {
     // fragment-major fast path (both or neither; H % 256 == 0): packed W_hh^T and a 2 x pk_floats(B,3H) ping-pong buffer
     const float* Wpk_hhT; float* dghpk;
     const float* W_hh;                                        // [3H,H] row-major (chain kernel reads it transposed once)
-    unsigned* sync;                                           // as in DirFwd
-    int sync_prezeroed;
+    SyncLedger* areas; int area;                              // as in DirFwd (gru_layer_bwd_areas)
     unsigned char* wp3T;                                      // big batches (gru_step_bf3.h): scratch for the pieces of W_hh^T, or null
     float* dgi_sum;                                           // optional [B,3H] sum_t dgi(t); `*dgi_sum_done` is set to 1 when the
     int* dgi_sum_done;                                        // layer's launch produced it (chain kernel), else left alone
@@ -102,6 +102,26 @@ struct GruLayerPlan {
 GruLayerPlan gru_layer_fwd_plan(int H, int B, int T, int nd, bool save, bool pk, bool sync, bool wp3);
 GruLayerPlan gru_layer_bwd_plan(int H, int B, int T, int nd, bool pk, bool chain_args, bool step_args);
 void bf3_set_emit_mask(int m);      // which piece outputs the chain kernels write themselves (inet_set_option key 9)
+// The sync areas of a chain layer's launches, in launch order: launch(c, area) for c = 0 .. pl.launches - 1.  A forward layer counts on
+// its base area; row chunks alternate between it and the one BEHIND it (two chunks may run side by side on two streams).  A backward
+// layer's chunks run one after the other on its base area.  These two are the only functions that take a layer's areas from a ledger:
+// gru_layer_fwd / gru_layer_bwd launch through them, and a dry run (vae.hip dec_route_areas) passes a `launch` that launches nothing.
+template <class F> int gru_layer_fwd_areas(const GruLayerPlan& pl, SyncLedger& L, int base, F&& launch) {
+    for (int c = 0; c < pl.launches; ++c) {
+        SyncArea a;
+        if (L.take(base + (c & 1), &a) != 0) return -1;
+        INET_TRY(launch(c, a));
+    }
+    return 0;
+}
+template <class F> int gru_layer_bwd_areas(const GruLayerPlan& pl, SyncLedger& L, int base, F&& launch) {
+    for (int c = 0; c < pl.launches; ++c) {
+        SyncArea a;
+        if (L.take(base, &a) != 0) return -1;
+        INET_TRY(launch(c, a));
+    }
+    return 0;
+}
 int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s);
 int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s);
 // dW_hh += dgh^T hprev       (rows = T*B, contiguous in t then b; the bias gradients come from the step kernel)
@@ -181,10 +201,9 @@ struct BiGru2In {
     const float* gvec[2];
 };
 // h0: [4][B][H] or null.  mask: [T][B][2H] or null.  hn4: 4 destinations (ld given) for final hiddens or null.
-// sync_prezeroed: the caller has zeroed w.sync (all kSyncAreas areas) on `s` already (the encoder's prologue launch does)
+// areas: the call's ledger over w.sync; a caller that has zeroed the block on `s` already (the encoder's prologue launch does) has told it so
 int bigru2_core_fwd(int B, int T, int H, const GruDirPtr* P /*[4]*/, const BiGru2In& in, const float* h0,
-                    const float* mask, float* const* hn, long hn_ld, BiGru2Ws& w, int save, hipStream_t s,
-                    int sync_prezeroed = 0);
+                    const float* mask, float* const* hn, long hn_ld, BiGru2Ws& w, int save, hipStream_t s, SyncLedger& areas);
 // dout1: gradient wrt the top layer outputs [T][B][2H] (or null); dhn[4] (ld) gradients wrt final hiddens (or null each).
 // Produces w.dgi0 [T][B][6H] (layer-0 input-side gate gradients, fwd dir cols 0..3H, reverse 3H..6H), accumulates the
 // recurrent / layer-1 weight gradients into P[*].d* (skipped when P[0].dw_hh is null), dh0 [4][B][H] (or null).

@@ -127,7 +127,7 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
         wp3 = wp3 && d[i].wp3;
         any_sv = any_sv || d[i].sv;
     }
-    const GruLayerPlan pl = gru_layer_fwd_plan(H, B, T, nd, any_sv, pk, d[0].sync != nullptr, wp3);
+    const GruLayerPlan pl = gru_layer_fwd_plan(H, B, T, nd, any_sv, pk, d[0].areas && d[0].areas->base, wp3);
     const bool chain = pl.route == GRU_ROUTE_CHAIN1 || pl.route == GRU_ROUTE_CHAIN2;
     if (chain && pl.launches == 1) {
         // one persistent launch for all T steps (gru_chain.hip); the exchange buffer is the hpk ring, slot 1 = h0 (published
@@ -142,8 +142,10 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
             P.hx = D.hpk;
             if (emits) { P.em = D.em; P.em.B_full = B; P.em.r0 = 0; D.emitted = 3; }
         }
-        a.counters = d[0].sync; a.prezeroed = d[0].sync_prezeroed;
-        return launch_gru_chain_fwd(a, s);
+        return gru_layer_fwd_areas(pl, *d[0].areas, d[0].area, [&](int, SyncArea sa) {
+            a.counters = sa.counters; a.prezeroed = sa.prezeroed;
+            return launch_gru_chain_fwd(a, s);
+        });
     }
     if (pl.route == GRU_ROUTE_STEP_BF3) {
         GruStepsBf3 L{};
@@ -168,13 +170,13 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
     }
     if (chain) {
         // row chunks (gru_layer_fwd_plan), one launch each; backward saves keep the full batch's time stride; even / odd chunks
-        // count on different sync areas (the caller's and the one behind it)
+        // count on different sync areas (gru_layer_fwd_areas)
         const int CH = pl.rows;
         const long pkc = (long)pk_floats(CH, H);
         const bool v2 = pl.route == GRU_ROUTE_CHAIN2;
         const bool emits = v2 && pl.b.EMR;
         hipStream_t s2 = pl.two_at_a_time ? twin_fork(s) : s;
-        for (int c = 0; c < pl.launches; ++c) {
+        INET_TRY(gru_layer_fwd_areas(pl, *d[0].areas, d[0].area, [&](int c, SyncArea sa) {
             const long r0 = (long)c * CH;
             GruChainFwd a{};
             a.H = H; a.B = CH; a.T = T; a.nprob = nd;
@@ -188,9 +190,9 @@ int gru_layer_fwd(int H, int B, int T, int nd, const DirFwd* d, hipStream_t s) {
                 else { P.hx = D.hpk + (long)c * pkc; P.hx_slot_bytes = (int)(pkh * sizeof(float)); }
                 if (emits) { P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 3; }
             }
-            a.counters = d[0].sync + (c & 1) * kChainSyncWords;
-            INET_TRY(launch_gru_chain_fwd(a, (c & 1) ? s2 : s));
-        }
+            a.counters = sa.counters; a.prezeroed = sa.prezeroed;
+            return launch_gru_chain_fwd(a, (c & 1) ? s2 : s);
+        }));
         return s2 != s ? twin_join(s) : 0;
     }
     // one launch per step (gru.hip): the fragment-major ring's slot 1 is packed from h0 here (step 0 reads it)
@@ -307,11 +309,11 @@ int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s) {
         stepb = stepb && d[i].wp3T && d[i].W_hh && d[i].dhz && !d[i].dgi_sum;
     }
     const bool dh0_ok = !any0 || all0;
-    const GruLayerPlan pl = gru_layer_bwd_plan(H, B, T, nd, pk, wok && d[0].sync && dh0_ok, stepb && dh0_ok);
+    const GruLayerPlan pl = gru_layer_bwd_plan(H, B, T, nd, pk, wok && d[0].areas && d[0].areas->base && dh0_ok, stepb && dh0_ok);
     if (pl.route == GRU_ROUTE_CHAIN1) {
         const int CHB = pl.rows;
         const long pkc = (long)pk_floats(CHB, 3 * H);
-        for (int c = 0; c < pl.launches; ++c) {
+        INET_TRY(gru_layer_bwd_areas(pl, *d[0].areas, d[0].area, [&](int c, SyncArea sa) {
             const long r0 = (long)c * CHB;
             GruChainBwd a{};
             a.H = H; a.B = CHB; a.T = T; a.nprob = nd;
@@ -323,9 +325,9 @@ int gru_layer_bwd(int H, int B, int T, int nd, const DirBwd* d, hipStream_t s) {
                 else { P.gx = D.dghpk + (long)c * pkc; P.gx_slot_bytes = (int)(pkg * sizeof(float)); }
                 if (pl.b.EMR && D.em.rows) { P.em = D.em; P.em.B_full = B; P.em.r0 = (int)r0; D.emitted = 1; }   // (row pieces only)
             }
-            a.counters = d[0].sync; a.prezeroed = (c == 0 && CHB == B) ? d[0].sync_prezeroed : 0;
-            INET_TRY(launch_gru_chain_bwd(a, s));
-        }
+            a.counters = sa.counters; a.prezeroed = sa.prezeroed;
+            return launch_gru_chain_bwd(a, s);
+        }));
         for (int i = 0; i < nd; ++i)
             if (d[i].dgi_sum && d[i].dgi_sum_done) *d[i].dgi_sum_done = 1;
         return 0;
@@ -400,6 +402,12 @@ int gru_dir_wgrad(int H, int B, int T, const float* dgh, const float* sv_hprev, 
     return linear_wgrad(dgh, 3L * H, sv_hprev, H, dW_hh, H, T * B, 3 * H, H, s);
 }
 
+// The sync areas of the stack's calls (w.sync; sync_areas.h): the base area of layer l.  A row-chunked forward layer also counts on the one
+// behind its base (gru_layer_fwd_areas), so layer 1's first chunk finds area 1 counted up by layer 0 and zeroes it itself; backward chunks
+// reuse their base.  Stage 2 of a staged backward call runs layer 0 on the area that stage 1's zeroing left untouched.
+constexpr int kBiGru2FwdArea[2] = {0, 1};
+constexpr int kBiGru2BwdArea[2] = {1, 0};
+
 size_t bigru2_carve(Carver& c, int B, int T, int H, int save, BiGru2Ws& w) {
     const size_t BH = (size_t)B * H, TBH = (size_t)T * BH;
     w.zeros = c.take<float>(BH);
@@ -428,7 +436,7 @@ size_t bigru2_carve(Carver& c, int B, int T, int H, int save, BiGru2Ws& w) {
         w.wp3[i] = pk && !gru_chain_ok(H, B, T, 2) && gru_step_bf3_ok(H, B, T, 2) ? c.take<unsigned char>(gru_step_bf3_w_bytes(H)) : nullptr;
         w.wp3T[i] = pk && save && chain_chunk_rows_bwd(H, B, T, 2) == 0 && gru_step_bf3_bwd_ok(H, B, T, 2) ? c.take<unsigned char>(gru_step_bf3_w_bytes(H)) : nullptr;
     }
-    w.sync = c.take<unsigned>(kSyncAreas * kChainSyncWords);
+    w.sync = c.take<unsigned>(kSyncBlockWords);
     // The bf16-pipe products (gemm_bf3.hip) tile 192 rows x 192 / 128 columns: below ~3072 rows (T*B) a launch leaves most CUs idle
     // (LatentRNN's context GRUs, T*B = 768: 27-52 TFLOP/s against 65-105 on the f32-input kernels) -- those stay on gemm.hip.
     const bool bf3 = gemm_bf3_ok(T * B, 6 * H, 2 * H) && (long)T * B >= 3072;
@@ -485,7 +493,7 @@ int bigru2_ws_opts_peek(const BiGru2Ws& w) {
 }
 
 int bigru2_core_fwd(int B, int T, int H, const GruDirPtr* P, const BiGru2In& in, const float* h0, const float* mask,
-                    float* const* hn, long hn_ld, BiGru2Ws& w, int save, hipStream_t s, int sync_prezeroed) {
+                    float* const* hn, long hn_ld, BiGru2Ws& w, int save, hipStream_t s, SyncLedger& areas) {
     const long BH = (long)B * H, TBH = (long)T * BH;
     if (save) ws_opts_note(w.zeros, opts_snapshot());           // (keyed by the first field: its offset does not move with the options)
     // fragment-major W_hh twins: only the per-step kernels read them (the chain kernels take W_hh as stored)
@@ -495,11 +503,17 @@ int bigru2_core_fwd(int B, int T, int H, const GruDirPtr* P, const BiGru2In& in,
     // zero initial state: the chain kernels take a null pointer (and skip step 0's contraction), the per-step kernels a buffer
     const float* const hzero = chained ? nullptr : w.zeros;
     if (!h0 && !chained && pw_zero(w.zeros, BH, s) != 0) return -2;
-    const bool one_launch = chained && gru_chain_ok(H, B, T, 2);      // (not the chunked form: it reuses one area per launch)
     const long TBl = (long)T * B;
     const bool bf3f = w.x1pk && w.wih1pk && bf3_mode() != 0 && gemm_bf3_ok(T * B, 6 * H, 2 * H);
-    if (one_launch && !sync_prezeroed &&
-        hipMemsetAsync(w.sync, 0, (size_t)kSyncAreas * kChainSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
+    // A caller that has not zeroed the block: one memset for both layers' launches where a layer is one launch (row chunks, several per
+    // area, have their launchers zero what they find counted up; the step kernels count on nothing)
+    if (!areas.clean && w.sync) {
+        const GruLayerPlan pl = gru_layer_fwd_plan(H, B, T, 2, save != 0, w.wpk[0] && w.hpk[0], true, w.wp3[0] != nullptr);
+        if ((pl.route == GRU_ROUTE_CHAIN1 || pl.route == GRU_ROUTE_CHAIN2) && pl.launches == 1) {
+            if (hipMemsetAsync(w.sync, 0, (size_t)kSyncBlockWords * sizeof(unsigned), s) != hipSuccess) return -2;
+            areas.zeroed_all();
+        }
+    }
     if (w.wpk[0] && !chained)
     {
         const float* ins[4] = {P[0].w_hh, P[1].w_hh, P[2].w_hh, P[3].w_hh};
@@ -540,7 +554,7 @@ int bigru2_core_fwd(int B, int T, int H, const GruDirPtr* P, const BiGru2In& in,
         if (save) { D.sv = w.sv[dir]; D.sv_astride = TBH; }
         D.reverse = dir;
         D.Wpk_hh = w.wpk[dir]; D.hpk = w.hpk[dir]; D.wp3 = w.wp3[dir];
-        D.sync = w.sync; D.sync_prezeroed = one_launch;
+        D.areas = &areas; D.area = kBiGru2FwdArea[0];
         if (bf3f && (emit_mask() & 1)) {                       // the layer-1 input products' A operand, written by the chain
             D.em.rows = w.x1pk; D.em.rows_piece = (long)bf3_piece_bytes(TBl, 2 * H); D.em.rows_kb = 2 * H / 32; D.em.rows_kb0 = dir * H / 32;
         }
@@ -581,7 +595,7 @@ int bigru2_core_fwd(int B, int T, int H, const GruDirPtr* P, const BiGru2In& in,
         if (save) { D.sv = w.sv[2 + dir]; D.sv_astride = TBH; }
         D.reverse = dir;
         D.Wpk_hh = w.wpk[2 + dir]; D.hpk = w.hpk[2 + dir]; D.wp3 = w.wp3[2 + dir];
-        D.sync = one_launch ? w.sync + kChainSyncWords : w.sync; D.sync_prezeroed = one_launch;
+        D.areas = &areas; D.area = kBiGru2FwdArea[1];
         if (bf3f && save && w.hpT[2 + dir] && (emit_mask() & 2)) {
             D.em.colsB = w.hpT[2 + dir]; D.em.colsB_piece = (long)bf3_piece_bytes(H, TBl); D.em.colsB_rb0 = 0;
         }
@@ -630,9 +644,13 @@ int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, 
     const bool bf3w_pre = bf3_mode() != 0 && w.gT[0] && w.hpT[0] && P[0].dw_hh != nullptr;
     // what the forward call's chains wrote (the same predicate it checked itself against)
     const bool fwd_emitted = bf3w_pre && w.x1pk && gemm_bf3_ok(T * B, 6 * H, 2 * H) && gru_layer_fwd_emits(H, B, T, 2, true) && (emit_mask() & 2);
-    // (stage 2 continues on what stage 1 left in the workspace: zeroed sync areas, packed / transposed weights, dx1)
-    if (stage != 2 && chained &&
-        hipMemsetAsync(w.sync, 0, (size_t)kSyncAreas * kChainSyncWords * sizeof(unsigned), s) != hipSuccess) return -2;
+    // (stage 2 continues on what stage 1 left in the workspace: layer 0's sync area still zero, packed / transposed weights, dx1)
+    SyncLedger areas(w.sync);
+    if (stage != 2 && chained) {
+        if (hipMemsetAsync(w.sync, 0, (size_t)kSyncBlockWords * sizeof(unsigned), s) != hipSuccess) return -2;
+        areas.zeroed_all();
+    }
+    if (stage == 2 && chained) areas.carried_over(kBiGru2BwdArea[0]);
     if (stage == 2 || (w.wpkT[0] && chained)) {
     } else if (w.wpkT[0]) {
         const float* ins[4] = {P[0].w_hh, P[1].w_hh, P[2].w_hh, P[3].w_hh};
@@ -656,7 +674,7 @@ int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, 
         if (dh0) { D.dh0 = dh0 + (2 + dir) * BH; D.dh0_ld = H; D.dh0_acc = 0; }
         D.reverse = dir;
         D.Wpk_hhT = w.wpkT[2 + dir]; D.dghpk = w.dghpk[2 + dir];
-        D.W_hh = P[2 + dir].w_hh; D.sync = w.sync; D.sync_prezeroed = chained; D.wp3T = w.wp3T[2 + dir];
+        D.W_hh = P[2 + dir].w_hh; D.areas = &areas; D.area = kBiGru2BwdArea[1]; D.wp3T = w.wp3T[2 + dir];
         if (bf3d_pre && (emit_mask() & 4)) {
             D.em.rows = w.dgi1pk; D.em.rows_piece = (long)bf3_piece_bytes((long)T * B, 6 * H); D.em.rows_kb = 6 * H / 32;
             D.em.rows_kb0 = dir * 3 * H / 32;
@@ -735,7 +753,7 @@ int bigru2_core_bwd(int B, int T, int H, const GruDirPtr* P, const float* mask, 
         if (dh0) { D.dh0 = dh0 + dir * BH; D.dh0_ld = H; D.dh0_acc = 0; }
         D.reverse = dir;
         D.Wpk_hhT = w.wpkT[dir]; D.dghpk = w.dghpk[dir];
-        D.W_hh = P[dir].w_hh; D.sync = chained ? w.sync + kChainSyncWords : w.sync; D.sync_prezeroed = chained; D.wp3T = w.wp3T[dir];
+        D.W_hh = P[dir].w_hh; D.areas = &areas; D.area = kBiGru2BwdArea[0]; D.wp3T = w.wp3T[dir];
     }
     INET_TRY(gru_layer_bwd(H, B, T, 2, d, s));
     if (wg)

@@ -82,16 +82,18 @@ int vae_encoder_fwd(const inet_vae_config& c, int B, const long long* tokens, co
         for (int dir = 0; dir < 2; ++dir)
             pr.tab[dir] = PwTableJob{p + L.enc_emb, E, V, P[dir].w_ih, E, P[dir].b_ih, dir ? w.tabR : w.tabF, 3L * H, 3 * H, E};
         pr.ntab = 2;
-        pr.zero_words = w.g.sync; pr.nzero = (long)kSyncAreas * kChainSyncWords;
+        pr.zero_words = w.g.sync; pr.nzero = kSyncBlockWords;
         pr.tok_src = tokens; pr.tok_B = B; pr.tok_T = T; pr.tok_V = V;     // range check only (encoder.py:118 embeds them)
         INET_TRY(pw_prologue(pr, s));
     }
+    SyncLedger areas(w.g.sync);
+    areas.zeroed_all();                                      // (the prologue launch did)
     BiGru2In in{};
     in.tab[0] = w.tabF; in.tab[1] = w.tabR; in.tab_ld = 3L * H;
     in.idx = tokens; in.idx_bs = T; in.idx_ts = 1;
     // final hiddens land directly in hcat = [l0f | l0b | l1f | l1b]   (encoder.py:126-127)
     float* hn[4] = {w.hcat, w.hcat + H, w.hcat + 2 * H, w.hcat + 3 * H};
-    INET_TRY(bigru2_core_fwd(B, T, H, P, in, nullptr, mask, hn, 4L * H, w.g, save, s, 1));
+    INET_TRY(bigru2_core_fwd(B, T, H, P, in, nullptr, mask, hn, 4L * H, w.g, save, s, areas));
     // the two heads (encoder.py:130-133) side by side: two launches of two products instead of four launches
     const GemmArgs l1[2] = {linear_fwd_args(w.hcat, 4L * H, p + L.mean_w0, 4L * H, p + L.mean_b0, w.a_mu, 2L * H, B, 2 * H, 4 * H, EPI_SELU),
                             linear_fwd_args(w.hcat, 4L * H, p + L.ls_w0, 4L * H, p + L.ls_b0, w.a_ls, 2L * H, B, 2 * H, 4 * H, EPI_SELU)};
@@ -255,11 +257,24 @@ size_t dec_carve(const inet_vae_config& c, int B, int save, void* base, DecWs& w
     static_assert(kDecodeSyncWords <= kChainSyncWords, "one sync area serves either kind of chain launch");
     w.b1stamps = (B <= kDecodeB1MaxRows && H == 512 && !save) ? cv.take<unsigned>(kDecodeB1StampWords) : nullptr;
     w.b1ex = (B <= kDecodeB1MaxRows && H == 512 && !save) ? cv.take<unsigned>(decode_b1_words(B)) : nullptr;
-    w.sync = cv.take<unsigned>(kSyncAreas * kChainSyncWords);
+    w.sync = cv.take<unsigned>(kSyncBlockWords);
     w.tmp3h = save ? cv.take<float>(3 * H) : nullptr;          // right behind the sync areas: one memset zeroes both
     w.b0part = save ? cv.take<float>(64) : nullptr;            // fixed-order partial sums of the b_0 gradient (pw_beat_input_grad)
     return cv.bytes();
 }
+
+// ---- the sync areas of the decoder's calls (w.sync: kSyncAreas areas; the calls' ledgers, sync_areas.h, hand them out) ----
+// forward: beat layer l counts on area l; the fused / register-resident launches on area 2; launch i of the nl = nb / npl teacher-forced
+// chains of tick layer l on area 2 + l * nl + i.  A row-chunked layer also counts on the area BEHIND its base (gru_layer_fwd_areas): beat
+// layer 1's on the fused launches', a teacher-forced chain's on its successor's -- whoever comes second finds the area counted up and zeroes it.
+constexpr int kDecAreaFused = 2;
+constexpr int dec_area_beat(int layer) { return layer; }
+constexpr int dec_area_tf(int layer, int nl, int i) { return 2 + layer * nl + i; }
+// nl launches per tick layer fit the block: the last one's area and the one behind it exist (3 + 2 nl <= kSyncAreas)
+constexpr bool dec_tf_areas_fit(int nl) { return dec_area_tf(1, nl, nl - 1) + 1 < kSyncAreas; }
+// backward: tick layer 1 / 0 on areas 0 / 1, beat layer 1 / 0 on 2 / 3; row chunks reuse their layer's
+constexpr int dec_area_bwd_tick(int layer) { return 1 - layer; }
+constexpr int dec_area_bwd_beat(int layer) { return 3 - layer; }
 
 // fragment-major operands of tick j of beat i: layer 0 = P0, layer 1 = P1 (whose x is layer 0's masked output)
 void tick_pk(const DecWs& w, int i, int j, int nb, long pkh, bool masked, GruFwdProb& P0, GruFwdProb& P1) {
@@ -289,8 +304,45 @@ struct DecRoute {
     int b1, b1_fused;                                // kFused: decode_b1.hip's register-resident launch; ... with the beat path inside it
     int zero, pack_beat, pack_tick, pack_out, ht0;   // what follows from the two paths: DecZero, the twins to pack, DecHt0
     int pk;                                          // the workspace carries fragment-major twins (pk_ok(H))
+    // what dec_route_areas' dry run of the call's ledger saw:
     int fused_prezeroed;                             // kFused / kFusedChunked: the first launch finds its counters zeroed by the prologue
+    unsigned beat_areas, tick_areas;                 // bit a: the beat / tick path counts on sync area a
+    int self_zeroed;                                 // chain and fused launches whose area was not clean when handed out (their launcher zeroes it)
 };
+
+// The ledger a forward call starts its launches with: clean behind the prologue's zeroing
+SyncLedger dec_ledger(const DecRoute& r, const DecWs& w) {
+    SyncLedger L(w.sync);
+    if (r.zero != kZeroNone) L.zeroed_all();
+    return L;
+}
+// beat layer l's / a teacher-forced tick chain's plan: what gru_layer_fwd makes of the descriptors dec_beat_path / dec_ticks_tf_chained fill
+// (twins and a ledger given, no step-kernel pieces)
+GruLayerPlan dec_beat_plan(int H, int B, int nb, int save) { return gru_layer_fwd_plan(H, B, nb, 1, save != 0, true, true, false); }
+GruLayerPlan dec_tf_plan(int H, int B, int G, int npl, int save) { return gru_layer_fwd_plan(H, B, G, npl, save != 0, true, true, false); }
+
+// The areas of the route's launches in the order the passes below make them, on a ledger of its own and without a launch: the layers'
+// through gru_layer_fwd_areas, as gru_layer_fwd takes them; the fused launches' as dec_ticks_fused takes them.
+int dec_route_areas(DecRoute& r, int H, int B, int nb, int G, int save, const DecWs& w) {
+    SyncLedger L = dec_ledger(r, w);
+    const auto dry = [](int, SyncArea) { return 0; };
+    if (r.beats == kBeatsChained)
+        for (int layer = 0; layer < 2; ++layer) INET_TRY(gru_layer_fwd_areas(dec_beat_plan(H, B, nb, save), L, dec_area_beat(layer), dry));
+    r.beat_areas = L.used; L.used = 0;
+    if (r.ticks == kTfChained)
+        for (int layer = 0; layer < 2; ++layer)
+            for (int i = 0; i < nb / r.npl; ++i)
+                INET_TRY(gru_layer_fwd_areas(dec_tf_plan(H, B, G, r.npl, save), L, dec_area_tf(layer, nb / r.npl, i), dry));
+    if (r.ticks == kFused || r.ticks == kFusedChunked)
+        for (int r0 = 0; r0 < B; r0 += r.chunk_rows ? r.chunk_rows : B) {
+            SyncArea a;
+            INET_TRY(L.take(kDecAreaFused, &a));
+            if (r0 == 0) r.fused_prezeroed = a.prezeroed;
+        }
+    r.tick_areas = L.used;
+    r.self_zeroed = L.self_zeroed;
+    return 0;
+}
 
 DecRoute dec_route(const inet_vae_config& c, int B, int save, bool teacher_forced, bool seeded, bool mask_beat, bool mask_tick, int level,
                    bool sampled, const DecWs& w) {
@@ -314,9 +366,9 @@ DecRoute dec_route(const inet_vae_config& c, int B, int save, bool teacher_force
     // G steps over the beats as problems -- `npl` beats per launch, as many as fit the chip at once (2 at B = 256)
     if (r.pk && teacher_forced) {
         for (int n = nb; n >= 1 && !r.npl; --n)              // whole batch in one launch per `n` beats ...
-            if (nb % n == 0 && 3 + 2 * (nb / n) <= kSyncAreas && gru_chain_ok(H, B, G, n)) r.npl = n;
+            if (nb % n == 0 && dec_tf_areas_fit(nb / n) && gru_chain_ok(H, B, G, n)) r.npl = n;
         for (int n = nb; n >= 1 && !r.npl; --n)              // ... else row chunks
-            if (nb % n == 0 && 3 + 2 * (nb / n) <= kSyncAreas && chain_chunk_rows(H, B, G, n, save) > 0) r.npl = n;
+            if (nb % n == 0 && dec_tf_areas_fit(nb / n) && chain_chunk_rows(H, B, G, n, save) > 0) r.npl = n;
     }
     r.beats = r.b1_fused ? kBeatsFolded : beats_chained ? kBeatsChained : kBeatsSteps;
     r.ticks = r.npl ? kTfChained : teacher_forced ? kTfSteps : fused_whole ? kFused : fused_chunked ? kFusedChunked : kPerTick;
@@ -324,9 +376,6 @@ DecRoute dec_route(const inet_vae_config& c, int B, int save, bool teacher_force
     const bool fused = r.ticks == kFused || r.ticks == kFusedChunked, steps = r.ticks == kTfSteps || r.ticks == kPerTick;
     // the sync areas for every chain or fused launch, and the b = 1 kernel's granules in front of them
     r.zero = r.b1 ? kZeroB1Sync : (beats_chained || fused || r.npl) ? kZeroSync : kZeroNone;
-    // Row-chunked beat chains count on two areas per layer (seq.hip gru_layer_fwd: odd chunks on the area behind the layer's), so layer 1
-    // leaves area 2 -- the fused launches' counters -- counted up: their first launch then zeroes it itself, like the later ones
-    r.fused_prezeroed = fused && !(r.beats == kBeatsChained && beat_rows < B);
     // Which kernels will run: the chain kernels read W_hh / W_ih as stored, only the per-step kernels want the
     // fragment-major twins -- each is packed only if its consumer runs.
     r.pack_beat = r.pk && r.beats == kBeatsSteps;
@@ -334,6 +383,9 @@ DecRoute dec_route(const inet_vae_config& c, int B, int save, bool teacher_force
     r.pack_out = r.pk && w.wpk_out && r.ticks == kPerTick;
     // packed initial tick hiddens: the per-step kernels and decode_chain.hip's launch read them, the chains and the b = 1 launch do not
     r.ht0 = !r.pk ? kHt0No : r.ticks == kFusedChunked ? kHt0PerChunk : (steps || (r.ticks == kFused && !r.b1)) ? kHt0Once : kHt0No;
+    // which sync areas the launches count on and which of them they find zeroed (cannot fail: every area of the map is inside the block,
+    // the teacher-forced chains' by dec_tf_areas_fit)
+    (void)dec_route_areas(r, H, B, nb, G, save, w);
     return r;
 }
 
@@ -352,6 +404,7 @@ struct DecCall {
     float* weights; long long* samples;
     uint64_t seed; sample::Request rq;
     hipStream_t s;
+    SyncLedger* areas;                               // the call's ledger over w.sync (dec_ledger)
 };
 
 int dec_prologue(const DecCall& d) {
@@ -365,8 +418,8 @@ int dec_prologue(const DecCall& d) {
     pr.tab[0] = PwTableJob{p + L.dec_emb, E, V, d.wih0, d.ldw0, p + L.tick[0].b_ih, w.table, 3L * H, 3 * H, E};
     pr.tab[1] = PwTableJob{p + L.x_0, E, 1, d.wih0, d.ldw0, p + L.tick[0].b_ih, w.table + (long)V * 3 * H, 3L * H, 3 * H, E};
     pr.ntab = 2;
-    if (d.r.zero != kZeroNone) { pr.zero_words = w.sync; pr.nzero = (long)kSyncAreas * kChainSyncWords; }
-    if (d.r.zero == kZeroB1Sync) { pr.zero_words = w.b1ex; pr.nzero = decode_b1_words(B) + (long)kSyncAreas * kChainSyncWords; }
+    if (d.r.zero != kZeroNone) { pr.zero_words = w.sync; pr.nzero = kSyncBlockWords; }
+    if (d.r.zero == kZeroB1Sync) { pr.zero_words = w.b1ex; pr.nzero = decode_b1_words(B) + kSyncBlockWords; }
     if (d.save) { pr.copy_src = reinterpret_cast<const unsigned*>(d.z); pr.copy_dst = reinterpret_cast<unsigned*>(w.zsave); pr.ncopy = (long)B * d.Z; }
     pr.axpb_a = p + L.b_0; pr.axpb_x = p + L.beat[0].w_ih; pr.axpb_incx = 1; pr.axpb_b = p + L.beat[0].b_ih;
     pr.axpb_y = w.gvec0; pr.axpb_n = 3 * H;
@@ -420,7 +473,7 @@ int dec_beat_path(const DecCall& d) {
     if (d.mask_beat) { f.outm = w.beat0m; f.outm_ld = H; f.outm_ts = BH; f.mask = d.mask_beat; f.mask_ld = H; f.mask_ts = BH; }
     if (d.save) { f.sv = w.svb0; f.sv_astride = nb * BH; }
     f.Wpk_hh = w.wpk_b[0]; f.hpk = w.hpk_b;
-    if (chained) { f.sync = w.sync; f.sync_prezeroed = 1; }  // 4 steps in one launch (8 groups of 32 rows at B = 256)
+    if (chained) { f.areas = d.areas; f.area = dec_area_beat(0); }   // 4 steps in one launch (8 groups of 32 rows at B = 256)
     INET_TRY(gru_layer_fwd(H, B, nb, 1, &f, s));
     const float* xb = d.mask_beat ? w.beat0m : w.beat0;
     {
@@ -435,7 +488,7 @@ int dec_beat_path(const DecCall& d) {
     f.out = w.beat_out; f.out_ld = H; f.out_ts = BH;
     if (d.save) { f.sv = w.svb1; f.sv_astride = nb * BH; }
     f.Wpk_hh = w.wpk_b[1]; f.hpk = w.hpk_b;
-    if (chained) { f.sync = w.sync + kChainSyncWords; f.sync_prezeroed = 1; }
+    if (chained) { f.areas = d.areas; f.area = dec_area_beat(1); }
     INET_TRY(gru_layer_fwd(H, B, nb, 1, &f, s));
 
     // ---- per-beat constants for the tick RNN (decoder.py:494-495), all 4 beats at once ----
@@ -496,8 +549,7 @@ int dec_ticks_tf_chained(const DecCall& d) {
                     D.Wpk_hh = w.wpk_t1hh; D.hpk = w.hpk_t1 + (long)i * 3 * pkh;
                 }
             }
-            dd[0].sync = w.sync + (long)(2 + layer * (nb / npl) + i0 / npl) * kChainSyncWords;
-            dd[0].sync_prezeroed = 1;
+            dd[0].areas = d.areas; dd[0].area = dec_area_tf(layer, nb / npl, i0 / npl);
             INET_TRY(gru_layer_fwd(H, B, G, npl, dd, s));
         }
     }
@@ -579,7 +631,9 @@ int dec_ticks_fused(const DecCall& d) {
             bt.wih0_c = d.wih0 + d.E; bt.wih0_ld = d.ldw0;
         }
         a.weights = d.weights + (long)r0 * T * V; a.samples = d.samples + (long)r0 * T;
-        a.counters = w.sync + 2 * kChainSyncWords; a.prezeroed = r0 == 0 && d.r.fused_prezeroed;   // (else the launcher zeroes the area)
+        SyncArea sa;
+        INET_TRY(d.areas->take(kDecAreaFused, &sa));
+        a.counters = sa.counters; a.prezeroed = sa.prezeroed;   // (counted up by a launch in front: the launcher zeroes the area)
         a.draw = d.rq;                                       // (sampled: one whole launch, never chunks)
         if (d.mask_tick) { a.mask = d.mask_tick + (long)r0 * H; a.hx0m = w.hm0pk; }
         if (d.save) {
@@ -647,6 +701,8 @@ int vae_decoder_fwd(const inet_vae_config& c, int B, const float* z, const long 
     dec_carve(c, B, save, ws, d.w);
     d.r = dec_route(c, B, save, teacher_forced != 0, multinomial_seed != 0, mask_beat != nullptr, mask_tick != nullptr, d.level, sampled, d.w);
     INET_TRY(dec_prologue(d));
+    SyncLedger areas = dec_ledger(d.r, d.w);
+    d.areas = &areas;
     INET_TRY(dec_pack_weights(d));
     if (d.r.beats != kBeatsFolded) INET_TRY(dec_beat_path(d));   // (one measure: these eight launches are roles of decode_b1.hip's launch)
     // ---- tick RNN (forward_tick_rnn, decoder.py:473-529) ----
@@ -666,9 +722,9 @@ int vae_decoder_route(const inet_vae_config& c, int B, int save, int teacher_for
     DecWs w{};
     dec_carve(c, B, save, reinterpret_cast<char*>(static_cast<uintptr_t>(1) << 30), w);
     const DecRoute r = dec_route(c, B, save, teacher_forced != 0, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, level, sampled, w);
-    const int32_t v[13] = {r.beats, r.ticks, r.npl, r.chunk_rows, r.b1, r.b1_fused, r.zero, r.pack_beat, r.pack_tick, r.pack_out, r.ht0, r.pk,
-                           r.fused_prezeroed};
-    for (int i = 0; i < 13; ++i) out[i] = v[i];
+    const int32_t v[16] = {r.beats, r.ticks, r.npl, r.chunk_rows, r.b1, r.b1_fused, r.zero, r.pack_beat, r.pack_tick, r.pack_out, r.ht0, r.pk,
+                           r.fused_prezeroed, (int32_t)r.beat_areas, (int32_t)r.tick_areas, r.self_zeroed};
+    for (int i = 0; i < (n_out >= 16 ? 16 : 13); ++i) out[i] = v[i];
     return 0;
 }
 
@@ -688,6 +744,8 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
     const bool ticks_chained = w.wpkT[0] && w.dghpk && chain_chunk_rows_bwd(H, B, G, nb) > 0;
     // one memset: the chain kernels' sync areas and, right behind them, the accumulator of the beat GRU's input-gate column sum
     if (hipMemsetAsync(w.sync, 0, (size_t)((char*)(w.tmp3h + 3 * H) - (char*)w.sync), s) != hipSuccess) return -2;
+    SyncLedger areas(w.sync);
+    areas.zeroed_all();
     if (w.wpkT[0]) {
         const float* ins[4]; float* outs[4];
         int n = 0;
@@ -720,7 +778,7 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
         if (g) { D.db_ih = g + L.tick[layer].b_ih; D.db_hh = g + L.tick[layer].b_hh; }
         D.dh0 = w.dht0 + (long)i * B * 2 * H + layer * H; D.dh0_ld = 2L * H; D.dh0_acc = 0;
         D.Wpk_hhT = w.wpkT[2 + layer]; D.dghpk = w.dghpk ? w.dghpk + (long)i * 3 * pkg : nullptr;
-        if (ticks_chained) { D.W_hh = p + L.tick[layer].w_hh; D.sync = w.sync + (1 - layer) * kChainSyncWords; D.sync_prezeroed = 1; }
+        if (ticks_chained) { D.W_hh = p + L.tick[layer].w_hh; D.areas = &areas; D.area = dec_area_bwd_tick(layer); }
         if (layer == 0) { D.dgi_sum = w.dcgi + (long)i * 3 * BH; D.dgi_sum_done = &dcgi_done; }   // beat-constant input half, see below
         return D;
     };
@@ -790,7 +848,7 @@ int vae_decoder_bwd(const inet_vae_config& c, int B, const float* dweights, cons
         if (g) { b.db_ih = g + L.beat[layer].b_ih; b.db_hh = g + L.beat[layer].b_hh; }
         b.dh0 = w.dhb0 + layer * H; b.dh0_ld = 2L * H;
         b.Wpk_hhT = w.wpkT[layer]; b.dghpk = w.dghpk;
-        if (beats_chained) { b.W_hh = p + L.beat[layer].w_hh; b.sync = w.sync + (3 - layer) * kChainSyncWords; b.sync_prezeroed = 1; }
+        if (beats_chained) { b.W_hh = p + L.beat[layer].w_hh; b.areas = &areas; b.area = dec_area_bwd_beat(layer); }
         return b;
     };
     DirBwd b = beat_dir_bwd(1);

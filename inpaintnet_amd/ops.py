@@ -320,7 +320,7 @@ def decoder_fwd(cfg, z, target, teacher_forced, params, mask_beat=None, mask_tic
 
 
 DECODER_ROUTE_KEYS = ("beats", "ticks", "npl", "chunk_rows", "b1", "b1_fused", "zero", "pack_beat_twins", "pack_tick_twins", "pack_out_w",
-                      "pack_ht0", "pk", "fused_prezeroed")
+                      "pack_ht0", "pk", "fused_prezeroed", "beat_areas", "tick_areas", "self_zeroed")
 DECODER_BEATS = ("steps", "chained", "folded")
 DECODER_TICKS = ("TfChained", "TfSteps", "Fused", "FusedChunked", "PerTick")
 DECODER_ZERO = ("none", "sync", "b1ex+sync")
@@ -330,11 +330,12 @@ DECODER_HT0 = ("no", "once", "per_chunk")
 def decoder_route(cfg, B, save=False, teacher_forced=False, multinomial_seed=False, mask_beat=False, mask_tick=False, level=0):
     """What decoder_fwd launches for such a call under the options set now, without a GPU (inet_vae_decoder_route, the function the
     launch itself asks): a dict of DECODER_ROUTE_KEYS with "beats", "ticks", "zero" and "pack_ht0" as names (DECODER_BEATS,
-    DECODER_TICKS, DECODER_ZERO, DECODER_HT0) and the flags as bools.  level: 0 argmax, 1 temperature, 2 truncated, 3 masked, 4 forced."""
-    out = (C.c_int32 * 13)()
+    DECODER_TICKS, DECODER_ZERO, DECODER_HT0) and the flags as bools; "beat_areas" / "tick_areas": bit a = the path's launches count on sync
+    area a; "self_zeroed": how many launches zero their own counters.  level: 0 argmax, 1 temperature, 2 truncated, 3 masked, 4 forced."""
+    out = (C.c_int32 * 16)()
     flags = int(bool(multinomial_seed)) | 2 * int(mask_beat is not None and mask_beat is not False) | \
         4 * int(mask_tick is not None and mask_tick is not False)
-    check(_lib.lib().inet_vae_decoder_route(C.byref(cfg), int(B), int(bool(save)), int(bool(teacher_forced)), flags, int(level), out, 13),
+    check(_lib.lib().inet_vae_decoder_route(C.byref(cfg), int(B), int(bool(save)), int(bool(teacher_forced)), flags, int(level), out, 16),
           "inet_vae_decoder_route")
     r = dict(zip(DECODER_ROUTE_KEYS, out))
     r["beats"], r["ticks"] = DECODER_BEATS[r["beats"]], DECODER_TICKS[r["ticks"]]

@@ -38,6 +38,8 @@ CASES = (
     ("13 B32 free-running train", dict(B=32, save=True, masks="both")),
     ("14 B1024 teacher-forced train", dict(B=1024, tf=True, save=True)),
     ("15 B32 teacher-forced train chains off", dict(B=32, tf=True, save=True, chains=0)),
+    # (recorded from the revision in front of the sync-area ledger, DESIGN.md section 24: the odd-chunk form of case 05 in training)
+    ("16 B768 free-running train", dict(B=768, save=True, masks="both")),
 )
 
 

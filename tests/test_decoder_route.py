@@ -2,16 +2,30 @@
 which beat path and tick path a call shape takes, and that what follows from the two -- the words the prologue zeroes, the twins that
 are packed -- fits them for every call shape, option and chip size.  The launch asks the same function, and
 tests/test_gpu_decoder_launches.py holds its launches to the ones recorded in front of the refactor; a route whose parts disagree
-shows up on a GPU as a chain launch on counters nobody zeroed or a step kernel reading twins nobody packed."""
+shows up on a GPU as a chain launch on counters nobody zeroed or a step kernel reading twins nobody packed.
+tests/golden/decoder_routes.json (tools/record_decoder_routes.py) pins the routes of the whole sweep to the revision in front of the
+sync-area ledger."""
+import ctypes
+import functools
+import hashlib
 import itertools
+import json
+import os
+import subprocess
+import sys
 
 import pytest
 
 from inpaintnet_amd import _lib, ops
 
-BS = tuple(range(1, 18)) + (32, 256, 512, 600, 768, 1024)
+# (320 / 576 / 768: the smallest batches whose beat chains run in row chunks on 128 / 256 chips and in front of fused chunks; on 64 and 40 CUs
+# -- INET_CHAIN_CUS is at least 100 here -- that would be 192 and 128)
+BS = tuple(range(1, 18)) + (32, 256, 320, 512, 576, 600, 768, 1024)
 CALLS = (("inference", False, False), ("TF + save", True, True), ("free + save", True, False))      # name, save, teacher_forced
 CAPACITIES = (256, 252, 250, 248, 245, 240, 230, 212, 200, 180, 160, 140, 129, 128, 100)           # tests/test_decode_plan.py's
+CONFIGS = ((48, 256, 512), (48, 128, 512), (50, 256, 512), (48, 256, 64))                          # V, Z, H
+SYNC_AREAS = 8                                                                                      # csrc/gru_chain.h kSyncAreas
+ROUTES_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "decoder_routes.json")
 
 
 @pytest.fixture(scope="module")
@@ -65,6 +79,13 @@ def test_the_route_of_every_recorded_case(L, call, want):
     assert {k: got[k] for k in want} == want, got
 
 
+@functools.lru_cache(maxsize=None)
+def row_chunks(H, B, T, nprob, save, chains):
+    """launches of a forward chain layer that runs in row chunks under option 4 = `chains` (which the caller has set), else 0"""
+    p = ops.gru_chain_plan(H, B, T, nprob=nprob, save=save)[0]
+    return p["launches"] if p["route"] in ("chain1", "chain2") and p["launches"] > 1 else 0
+
+
 def violations(r, B, Z, H, save, tf, seed, mb, mt, level, chains):
     """The invariants that hold for every route, as a list of the ones this route breaks."""
     bad = []
@@ -99,76 +120,123 @@ def violations(r, B, Z, H, save, tf, seed, mb, mt, level, chains):
         bad.append("no twins: step kernels only")
     if not chains and (r["beats"] != "steps" or not steps):
         bad.append("chains off: step kernels only")
-    # Row-chunked beat chains count on the area behind their layer's (csrc/seq.hip gru_layer_fwd), layer 1's on the fused launches'
-    # counters: the first fused launch may call them zeroed only where the beat layers ran as one launch each (or not as chains).
-    # (Found with case 05 of tests/decoder_launches.py: stale counters let a workgroup read tokens nobody had written yet.)
-    beat_plan = ops.gru_chain_plan(H, B, 4, nprob=1, save=save)[0]
-    chunked = chain_beats and beat_plan["launches"] > 1
-    if r["fused_prezeroed"] != (fused and not chunked):
-        bad.append("the first fused launch zeroes its counters behind row-chunked beat chains")
+    # The sync areas, as the dry run of the call's ledger reports them (csrc/sync_areas.h, csrc/vae.hip dec_route_areas).  The fused launches
+    # count on area 2, and so does a row-chunked beat layer 1 (the area behind its own): the first fused launch may call the area zeroed
+    # exactly where the beat path left it alone.  (Found with case 05 of tests/decoder_launches.py: stale counters let a workgroup read
+    # tokens nobody had written yet.)
+    if (r["beat_areas"] | r["tick_areas"]) >> SYNC_AREAS:
+        bad.append("every area is inside the block")
+    if r["fused_prezeroed"] != (fused and not r["beat_areas"] >> 2 & 1):
+        bad.append("the first fused launch zeroes its counters exactly where the beat path counted on them")
+    # launches that zero their own counters: never more than the rule in front of the ledger gave -- every launch of a row-chunked forward
+    # layer, the first fused launch behind row-chunked beat chains, fused chunks after the first -- and none where every layer is one launch
+    beat_chunks = row_chunks(H, B, 4, 1, save, chains) if chain_beats else 0
+    tick_chunks = row_chunks(H, B, 6, r["npl"], save, chains) if r["ticks"] == "TfChained" else 0
+    fused_launches = B // r["chunk_rows"] if r["chunk_rows"] else int(fused)
+    before = 2 * beat_chunks + 2 * (4 // r["npl"]) * tick_chunks if r["npl"] else 2 * beat_chunks
+    before += (fused_launches - 1) + int(bool(beat_chunks)) if fused else 0
+    if r["self_zeroed"] > before or r["self_zeroed"] < 0:
+        bad.append("no launch zeroes its counters that did not before the ledger")
+    if not beat_chunks and not tick_chunks and fused_launches <= 1 and r["self_zeroed"] != 0:
+        bad.append("one launch per layer: nobody zeroes its own counters")
     return bad
 
 
-def sweep_violations(L):
-    """Every call shape under chains on / off on this process's chip.  Restores the options."""
-    bad, seen = [], set()
+def sweep(L, check=True):
+    """Every call shape under chains on / off on this process's chip -> (the violations, the (beat path, tick path) pairs seen, per
+    "V Z H chains" the SHA-256 over the 13 integers of every route in sweep order and their count).  check=False: the digests alone (the
+    recorder's, on a library in front of the ledger).  Restores the options."""
+    bad, seen, digests = [], set(), {}
+    out = (ctypes.c_int32 * 13)()
     try:
         for chains in (1, 0):
             assert L.inet_set_option(4, chains) == 0 and L.inet_set_option(15, 4) == 0
-            for (V, Z, H), B, (_, save, tf), level, seed, mb, mt in itertools.product(
-                    ((48, 256, 512), (48, 128, 512), (50, 256, 512), (48, 256, 64)), BS, CALLS, range(5), (False, True), (False, True),
-                    (False, True)):
-                kw = dict(save=save, teacher_forced=tf, multinomial_seed=seed, mask_beat=mb, mask_tick=mt, level=level)
-                if level > 0 and (tf or seed):                       # the entries refuse it, and so does the query
-                    try:
-                        route(B, V, Z, H, **kw)
-                        bad.append(("accepted", V, Z, H, B, kw))
-                    except ValueError:
-                        pass
-                    continue
-                r = route(B, V, Z, H, **kw)
-                seen.add((r["beats"], r["ticks"]))
-                for what in violations(r, B, Z, H, save, tf, seed, mb, mt, level, chains):
-                    bad.append((what, chains, V, Z, H, B, kw, r))
+            for V, Z, H in CONFIGS:
+                h, n, cfg = hashlib.sha256(), 0, cfg_of(V, Z, H)
+                for B, (_, save, tf), level, seed, mb, mt in itertools.product(BS, CALLS, range(5), (False, True), (False, True), (False, True)):
+                    kw = dict(save=save, teacher_forced=tf, multinomial_seed=seed, mask_beat=mb, mask_tick=mt, level=level)
+                    rc = L.inet_vae_decoder_route(ctypes.byref(cfg), B, int(save), int(tf), int(seed) | 2 * int(mb) | 4 * int(mt), level, out, 13)
+                    if level > 0 and (tf or seed):                   # the entries refuse it, and so does the query
+                        if rc != -1:
+                            bad.append(("accepted", V, Z, H, B, kw))
+                        continue
+                    assert rc == 0, (rc, V, Z, H, B, kw)
+                    h.update(b"".join(int(v).to_bytes(4, "little", signed=True) for v in out))
+                    n += 1
+                    if not check:
+                        continue
+                    r = route(B, V, Z, H, **kw)
+                    seen.add((r["beats"], r["ticks"]))
+                    for what in violations(r, B, Z, H, save, tf, seed, mb, mt, level, chains):
+                        bad.append((what, chains, V, Z, H, B, kw, r))
+                digests[f"V{V} Z{Z} H{H} chains{chains}"] = [h.hexdigest(), n]
     finally:
         L.inet_set_option(4, 1)
         L.inet_set_option(15, 4)
-    return bad, sorted(seen)
+    return bad, sorted(seen), digests
+
+
+def sweep_in_child(cap, tree=None, check=True):
+    """sweep() on a chip of `cap` CUs: INET_CHAIN_CUS is read once per process, so a child process, with a time limit.  tree: a built
+    checkout whose library to ask (this one's by default).  -> (the first violations, the digests)"""
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, %r)\n"
+            "from inpaintnet_amd import _lib, ops\n"
+            "sys.path.insert(0, %r)\n"
+            "from tests.test_decoder_route import sweep\n"
+            "bad, _, digests = sweep(_lib.lib(), %r)\n"
+            "print('SWEEP ' + json.dumps([bad[:4], digests]))\n") % (os.path.abspath(tree or repo), repo, check)
+    env = dict(os.environ, INET_CHAIN_CUS=str(cap))
+    env.pop("INET_DECODE_B1", None)
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=repo, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (cap, r.returncode, r.stderr[-2000:])
+    return tuple(json.loads(r.stdout.split("SWEEP ", 1)[1]))
+
+
+child = functools.lru_cache(maxsize=None)(sweep_in_child)        # one child per capacity for the tests below
 
 
 def test_every_route_is_consistent_on_the_full_chip(L):
-    bad, seen = sweep_violations(L)
+    bad, seen, _ = sweep(L)
     assert not bad, (len(bad), bad[:6])
     # every tick path and every beat path is taken somewhere in the sweep
     assert {t for _, t in seen} == set(ops.DECODER_TICKS) and {b for b, _ in seen} == set(ops.DECODER_BEATS), seen
 
 
 def test_every_route_is_consistent_below_the_full_chip():
-    """The same sweep on partitions of the chip: INET_CHAIN_CUS is read once per process, so one child process per capacity, one after
-    the other, each with a time limit."""
-    import json
-    import os
-    import subprocess
-    import sys
-    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import json, sys; sys.path.insert(0, %r)\n"
-            "from inpaintnet_amd import _lib\n"
-            "from tests.test_decoder_route import sweep_violations\n"
-            "print('VIOLATIONS ' + json.dumps(sweep_violations(_lib.lib())[0][:4]))\n") % repo
-    failed = {}
-    for cap in CAPACITIES[1:]:
-        env = dict(os.environ, INET_CHAIN_CUS=str(cap))
-        env.pop("INET_DECODE_B1", None)
-        r = subprocess.run([sys.executable, "-c", code], env=env, cwd=repo, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, (cap, r.returncode, r.stderr[-2000:])
-        bad = json.loads(r.stdout.split("VIOLATIONS ", 1)[1])
-        if bad:
-            failed[cap] = bad
+    """The same sweep on partitions of the chip, one child process per capacity, one after the other."""
+    failed = {cap: child(cap)[0] for cap in CAPACITIES[1:] if child(cap)[0]}
     assert not failed, failed
 
 
+def test_every_route_is_the_one_recorded_in_front_of_the_ledger():
+    """Per capacity, configuration and chains on / off: the digest over the 13 integers of every route of the sweep, and their count, as
+    tools/record_decoder_routes.py took them from the revision the fixture names."""
+    with open(ROUTES_FIXTURE) as f:
+        fx = json.load(f)
+    assert fx["BS"] == list(BS) and [int(c) for c in fx["capacities"]] == list(CAPACITIES)
+    differ = {(cap, k): (v, fx["capacities"][str(cap)].get(k)) for cap in CAPACITIES for k, v in child(cap)[1].items()
+              if v != fx["capacities"][str(cap)].get(k)}
+    assert not differ, differ
+    assert all(len(fx["capacities"][str(cap)]) == 2 * len(CONFIGS) for cap in CAPACITIES)
+
+
+def test_the_rows_the_ledger_checks_are_there(L):
+    """The routes the new assertions of violations() are for: row-chunked beat chains in front of fused chunks (256 CUs: 3 x 256 at B = 768)
+    and in front of chunked teacher-forced chains (9 x 64 at B = 576); on 128 CUs 5 x 64 at B = 320."""
+    r = route(768, **TRAIN)
+    assert (r["ticks"], r["chunk_rows"], r["fused_prezeroed"], r["beat_areas"], r["tick_areas"]) == ("FusedChunked", 256, False, 0b111, 0b100)
+    assert r["self_zeroed"] == 3 + 3          # of each beat layer's three launches the first two / the second find a clean area; no fused launch
+    r = route(576, teacher_forced=True, **TRAIN)
+    tick_chunks = ops.gru_chain_plan(512, 576, 6, nprob=r["npl"])[0]["launches"]
+    assert (r["ticks"], ops.gru_chain_plan(512, 576, 4, nprob=1)[0]["launches"], r["beat_areas"]) == ("TfChained", 9, 0b111) and tick_chunks > 1
+    assert r["fused_prezeroed"] is False and 0 < r["self_zeroed"] < 2 * 9 + 2 * (4 // r["npl"]) * tick_chunks
+    r = route(256, teacher_forced=True, **TRAIN)
+    assert (r["npl"], r["beat_areas"], r["tick_areas"], r["self_zeroed"]) == (2, 0b11, 0b111100, 0)
+
+
 def test_calls_the_query_refuses(L):
-    import ctypes as C
+    C = ctypes
     cfg, out = cfg_of(), (C.c_int32 * 13)()
     ok = lambda *a: L.inet_vae_decoder_route(*a)                                      # noqa: E731
     assert ok(C.byref(cfg), 1, 0, 0, 0, 0, out, 13) == 0
@@ -178,3 +246,7 @@ def test_calls_the_query_refuses(L):
     assert ok(None, 1, 0, 0, 0, 0, out, 13) == -1
     five = ops.vae_config(48, 10, 512, 256, 512, beats=5)
     assert ok(C.byref(five), 1, 0, 0, 0, 0, out, 13) == -1
+    # n_out 13 .. 15 writes the 13 values of old, 16 the areas behind them
+    wide = (C.c_int32 * 16)(*([77] * 16))
+    assert ok(C.byref(cfg), 768, 0, 0, 0, 0, wide, 15) == 0 and list(wide[13:]) == [77] * 3
+    assert ok(C.byref(cfg), 768, 0, 0, 0, 0, wide, 16) == 0 and list(wide[12:]) == [0, 0b111, 0b100, 6]

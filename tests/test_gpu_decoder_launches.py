@@ -43,6 +43,8 @@ ROUTE = {
     "14 B1024 teacher-forced train": lambda l: sum(" np1 T4 B512 " in x for x in l) == 4 and sum(" np4 T6 B128 " in x for x in l) == 16 and
     count(l, "gru_fwd") == 0,
     "15 B32 teacher-forced train chains off": lambda l: count(l, "gru_chain") == 0 and sum(" pk1 np4 B32 " in x for x in l) == 2 * 6,
+    "16 B768 free-running train": lambda l: [x.split(" ms")[0] for x in l if x.startswith("decode_")] == ["decode_chain_train"] * 3 and
+    sum(x.startswith("decode_chain_train ") and " B256 " in x for x in l) == 3 and sum(" np1 T4 B256 " in x for x in l) == 6,
 }
 # The cases that reproduce themselves by design and must carry a digest: the register-resident launch alone (01) or behind a beat path
 # whose products are single-range gemv launches (03).  Two more were expected to and did not in the recorded revision's own two runs:
@@ -76,8 +78,11 @@ def test_fused_chunks_behind_row_chunked_beat_chains_reproduce_themselves():
     """Case 05 (three fused launches of 256 rows behind beat chains in three row chunks): in the recorded revision layer 1's second beat
     chunk left the fused launches' counters counted up and the first fused launch took them for zeroed, so workgroups read hand-offs
     nobody had written yet -- its two recorded runs differ, and on recycled memory a stale token index reads outside the gather table.
-    The route now has that launch zero its counters: every kernel of the call is deterministic, so two calls agree bit for bit."""
-    run = dict(CASES)["05 B768 inference"]
-    (l1, _, d1), (l2, _, d2) = run(ops, synthetic), run(ops, synthetic)
-    assert l1 == l2 == DL.fixture()["cases"]["05 B768 inference"]["labels"]
-    assert d1 == d2
+    The route now has that launch zero its counters: every kernel of the call is deterministic, so two calls agree bit for bit.
+    Case 16 is the same odd-chunk form in training (decode_chain_train, with saves and both masks, and the backward call behind it): the
+    fused launches take area 2 from the call's ledger (csrc/sync_areas.h), which knows that beat layer 1 counted on it."""
+    for name in ("05 B768 inference", "16 B768 free-running train"):
+        run, want = dict(CASES)[name], DL.fixture()["cases"][name]
+        (l1, b1, d1), (l2, b2, d2) = run(ops, synthetic), run(ops, synthetic)
+        assert l1 == l2 == want["labels"] and b1 == b2 == want["bwd_labels"], name
+        assert d1 == d2, name
