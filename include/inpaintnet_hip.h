@@ -250,6 +250,19 @@ int inet_latent_bwd_fb(const float* dz, const float* mu, const float* logsigma, 
                        const float* kscale_dev, const float* keep, int per, float* dmu, float* dlogsigma, int64_t rows, int Z,
                        void* stream);
 
+/* The MMD (InfoVAE / WAE-MMD) latent loss between two samples.  x (z_tilde), y (z_prior) [B, Z] contiguous;
+ * d(u,v) = sum_z (u_z - v_z)^2; kind 0 'gaussian': k = exp(-d / var), 1 'imq': k = var / (var + d); S_xx, S_yy, S_xy = the sums of k
+ * over all B^2 pairs, diagonals included.  out4 = {coeff (a (S_xx - diag B) + a (S_yy - diag B) - c S_xy), S_xx, S_yy, S_xy};
+ * grad (nullable: the value only) [B, Z] = d out4[0] / d x.  The estimator is the caller's (a, c, diag): unbiased (1/(B(B-1)), 2/B^2,
+ * 1), biased (1/B^2, 2/B^2, 0), the reference's (1/(B(B-1))/2, 2/B^2, 0).  A distance is a sum of squared differences in a fixed
+ * order, so a diagonal kernel value is exactly 1; no float atomics: the same inputs give the same bits in out4 and grad.  Two
+ * launches (pair, finish) through `ws`: inet_mmd_ws_bytes(B, Z) bytes of device memory, nothing to zero.  x and y may be the same
+ * memory; 4-byte alignment suffices.  -1: a null x, y or out4, B < 1, B > 2^24, Z < 1, var not finite or <= 0, a, c, diag or coeff not
+ * finite, kind outside {0, 1}, ws null or ws_bytes too small -- before any launch. */
+int64_t inet_mmd_ws_bytes(int64_t B, int Z);
+int inet_mmd(const float* x, const float* y, int64_t B, int Z, int kind, float var, double a, double c, double diag, double coeff,
+             float* out4, float* grad, void* ws, int64_t ws_bytes, void* stream);
+
 /* rows of V (post-ReLU) logits -> out[row*stride] ~ Multinomial(softmax(row))  (decoder.py:506-509): inverse-CDF draw with
  * one counter-based uniform per row keyed (seed, offset + row): row r of a call at `offset` is row 0 of a call at offset + r.
  * The token drawn always has mass (exp(w - max) > 0 in float32): where rounding leaves every prefix sum at or below

@@ -12,6 +12,7 @@
 #include "gemm_bf3.h"
 #include "gru_step_bf3.h"
 #include "side.h"
+#include "mmd.h"
 
 namespace {
 
@@ -250,6 +251,13 @@ int inet_latent_bwd_fb(const float* dz, const float* mu, const float* logsigma, 
                        void* stream) {
     if (!mu || !logsigma || !keep || !dmu || !dlogsigma || rows <= 0 || Z <= 0 || (per != 0 && per != 1)) return -1;
     return pw_latent_bwd_fb(dz, mu, logsigma, eps, kscale, kscale_dev, keep, per, dmu, dlogsigma, rows, Z, (hipStream_t)stream);
+}
+int64_t inet_mmd_ws_bytes(int64_t B, int Z) { return B > (1 << 24) ? -1 : mmd_ws_bytes(B, Z); }
+int inet_mmd(const float* x, const float* y, int64_t B, int Z, int kind, float var, double a, double c, double diag, double coeff,
+             float* out4, float* grad, void* ws, int64_t ws_bytes, void* stream) {
+    if (!x || !y || !out4 || B < 1 || B > (1 << 24) || Z < 1 || (kind != MMD_GAUSSIAN && kind != MMD_IMQ)) return -1;
+    if (!(var > 0.f) || !std::isfinite(var) || !std::isfinite(a) || !std::isfinite(c) || !std::isfinite(diag) || !std::isfinite(coeff)) return -1;
+    return mmd_launch(x, y, B, Z, kind, var, a, c, diag, coeff, out4, grad, ws, ws_bytes, (hipStream_t)stream);
 }
 // the four entry points of the optimizer step: one check, one launcher (pw_adam_step)
 static int adam_step_checked(const PwAdamStep& a, void* stream) {

@@ -129,6 +129,29 @@ class _ReparamFn(torch.autograd.Function):
         return dmu, dls, None, None
 
 
+class _MmdFn(torch.autograd.Function):
+    """The MMD between z_tilde and z_prior (ops.mmd) as a loss term: where z_tilde takes a gradient the pair
+    launch of the forward also leaves G = d value / d z_tilde, and the backward is the device product G * gloss -- autograd adds it
+    to the decoder's dz in front of the reparameterisation's backward.  z_prior is a constant.  -> value, S_xx, S_yy, S_xy."""
+
+    @staticmethod
+    def forward(ctx, z_tilde, z_prior, kernel, bandwidth, estimator, coeff):
+        out4, G = ops.mmd(z_tilde.contiguous(), z_prior.detach().contiguous(), kernel, bandwidth, estimator, coeff,
+                          want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(G)
+        value, sxx, syy, sxy = out4[0], out4[1], out4[2], out4[3]
+        ctx.mark_non_differentiable(sxx, syy, sxy)
+        ctx.set_materialize_grads(False)
+        return value, sxx, syy, sxy
+
+    @staticmethod
+    def backward(ctx, gloss, _gxx, _gyy, _gxy):
+        G, = ctx.saved_tensors
+        if gloss is None or G is None:
+            return None, None, None, None, None, None
+        return G * gloss, None, None, None, None, None
+
+
 class _ReparamFbFn(torch.autograd.Function):
     """_ReparamFn with the KL term summed into parts and floored ("free bits"): the forward kernel leaves the
     floored sum, the plain sum, the parts and their keep vector; the backward hands the KL gradient to the elements of kept parts

@@ -529,6 +529,58 @@ def latent_bwd_fb(dz, mu, ls, eps, kscale, keep, per, kscale_dev=None):
     return dmu, dls
 
 
+MMD_KERNEL = {"gaussian": 0, "imq": 1}
+MMD_ESTIMATORS = ("unbiased", "biased", "reference")
+
+
+def mmd_weights(B, estimator):
+    """(a, c, diag) of value = coeff (a (S_xx - diag B) + a (S_yy - diag B) - c S_xy) for B samples a side:
+    'unbiased' (B >= 2) drops the self terms' diagonals and divides by B (B - 1); 'biased' is the V-statistic; 'reference' is
+    VAETrainer.compute_mmd_loss of the reference as written, diagonals in, 1 / (B (B - 1)) / 2 on the self terms (1 at B = 1)."""
+    if estimator not in MMD_ESTIMATORS:
+        raise ValueError(f"mmd estimator must be one of {MMD_ESTIMATORS}, got {estimator!r}")
+    B = int(B)
+    if B < 1:
+        raise ValueError("mmd: B must be >= 1")
+    c = 2.0 / (B * B)
+    if estimator == "unbiased":
+        if B < 2:
+            raise ValueError("the 'unbiased' MMD estimator needs B >= 2")
+        return 1.0 / (B * (B - 1)), c, 1.0
+    if estimator == "biased":
+        return 1.0 / (B * B), c, 0.0
+    return (1.0 / (B * (B - 1)) / 2 if B > 1 else 1.0), c, 0.0
+
+
+def mmd(z, z_prior, kernel="gaussian", bandwidth=None, estimator="unbiased", coeff=1.0, want_grad=False):
+    """The MMD between the samples z and z_prior, both [B, Z] (include/inpaintnet_hip.h inet_mmd).  kernel
+    'gaussian' exp(-d / bandwidth) or 'imq' bandwidth / (bandwidth + d) on the squared distance d; bandwidth None: 2 Z, the expected
+    squared distance of two prior draws.  -> (out4, grad): out4 = {value, S_xx, S_yy, S_xy} on the device; grad = d value / d z
+    [B, Z] with want_grad, else None (the value launches only).  Two calls on the same inputs give the same bits."""
+    _f32c(z); _f32c(z_prior)
+    if z.dim() != 2 or z_prior.shape != z.shape:
+        raise ValueError(f"mmd: z and z_prior must be [B, Z] tensors of one shape, got {tuple(z.shape)} and {tuple(z_prior.shape)}")
+    if kernel not in MMD_KERNEL:
+        raise ValueError(f"mmd kernel must be 'gaussian' or 'imq', got {kernel!r}")
+    B, Z = z.shape
+    a, c, diag = mmd_weights(B, estimator)
+    var = 2.0 * Z if bandwidth is None else float(bandwidth)
+    if not (var > 0.0 and math.isfinite(var)):
+        raise ValueError(f"mmd bandwidth must be finite and > 0, got {var}")
+    coeff = float(coeff)
+    if not math.isfinite(coeff):
+        raise ValueError(f"mmd coeff must be finite, got {coeff}")
+    dev = z.device
+    out4 = torch.empty(4, dtype=torch.float32, device=dev)
+    grad = torch.empty_like(z) if want_grad else None
+    L = _lib.lib()
+    ws = _ws(L.inet_mmd_ws_bytes(B, Z), dev)
+    _hold(z, z_prior, ws)
+    check(L.inet_mmd(ptr(z), ptr(z_prior), B, Z, MMD_KERNEL[kernel], var, a, c, diag, coeff, ptr(out4), ptr(grad), ptr(ws),
+                     ws.numel() * 4, stream_ptr()), "inet_mmd")
+    return out4, grad
+
+
 def _adam_arenas(p, g, m, v, partials, report):
     """What every optimizer entry point asks of its tensors: four float32 arenas of one size; `partials` (where given) what
     grad_sqnorm left; `report` (where given) pinned int32 words, four of them, eight with partials.  Returns the size."""

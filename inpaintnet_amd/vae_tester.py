@@ -76,6 +76,31 @@ class VAETester(object):
         units by a threshold of 0.01 on a posterior statistic; this is the KL form of that count)."""
         return int((self.kl_per_dim(data_loader) > threshold).sum())
 
+    def mmd(self, data_loader, kernel='gaussian', bandwidth=None, estimator='unbiased', generator=None):
+        """The mean over the loader's batches of the MMD (ops.mmd, DESIGN.md section 25: coeff = 1) between a draw rsample() of the
+        encoder's posterior for every measure of the batch and as many draws of the prior N(0, 1) -- whether the AGGREGATE posterior
+        matches the prior, which the per-measure KL of kl_per_dim / active_units cannot say.  bandwidth None: 2 * z_dim.  A 0-dim
+        float64 tensor on the device.  generator: the device torch.Generator of the 2 B Z normal draws per batch (eps first, then
+        the prior's), None: the default one.  Only the value launches run."""
+        total, count = None, 0
+        n_bars = getattr(self.dataset, "n_bars", None)
+        for score_tensor, _ in data_loader:
+            if n_bars is not None and score_tensor.dim() == 3:
+                score_tensor = score_tensor.reshape(score_tensor.size(0) * n_bars, -1)
+            score = to_cuda_variable_long(score_tensor)
+            with torch.no_grad():
+                z_dist = self.model.encoder(score)
+                draws = torch.randn((2,) + tuple(z_dist.loc.shape), dtype=z_dist.loc.dtype, device=z_dist.loc.device,
+                                    generator=generator)
+                z = z_dist.rsample(eps=draws[0])
+                value = ops.mmd(z.contiguous(), draws[1], kernel, bandwidth, estimator)[0][0].double()
+            total = value if total is None else total + value
+            count += 1
+            ops.check_chains("VAETester.mmd")
+        if total is None:
+            raise ValueError("mmd: the loader is empty")
+        return total / count
+
     def loss_and_acc_test(self, data_loader):
         """vae_tester.py:113-160: mean reconstruction CE / accuracy over a loader (eval mode, no teacher forcing)."""
         tot = torch.zeros(3)

@@ -4,7 +4,9 @@ import os
 
 import torch
 
+from . import ops
 from .helpers import to_cuda_variable_long
+from .measure_vae import _MmdFn
 from .trainer import Trainer, _ElboFn, _KLFn
 
 
@@ -12,11 +14,12 @@ class VAETrainer(Trainer):
     feed_fields = (0,)                     # the metadata tensor is never read (vae_trainer.py:42-55)
 
     KL_SETTINGS = ("kl_beta", "kl_warmup_steps", "kl_cycle_steps", "kl_ramp", "free_nats", "free_nats_per")
+    MMD_SETTINGS = ("mmd_coeff", "mmd_kernel", "mmd_bandwidth", "mmd_estimator")
 
     def __init__(self, dataset, model, lr=1e-4, max_grad_norm=None, weight_decay=0.0, decay_all=False, ema_decay=None,
                  ema_warmup=False, kl_beta=0.001, kl_warmup_steps=0, kl_cycle_steps=0, kl_ramp=0.5, free_nats=0.0,
-                 free_nats_per='measure'):
-        """The loss of a training step is CE + beta_t / B * kl_sum.
+                 free_nats_per='measure', mmd_coeff=0.0, mmd_kernel='gaussian', mmd_bandwidth=None, mmd_estimator='unbiased'):
+        """The loss of a training step is CE + beta_t / B * kl_sum [+ mmd_coeff * MMD(z_tilde, z_prior)].
 
         kl_beta (finite, >= 0): the KL weight; the reference's 0.001.  kl_warmup_steps (an int >= 0): beta rises linearly from 0 to
         kl_beta over that many optimizer steps, then holds.  kl_cycle_steps = M > 0: cyclical annealing (Fu et al. 2019) -- within
@@ -33,7 +36,18 @@ class VAETrainer(Trainer):
         floored; a NaN part is kept, so that a NaN reaches loss and gradient as on the plain path.  free_nats > 0 sets
         model.free_bits, which MeasureVAE.forward applies to training passes only; after such a step `last_kl` holds the device
         tensors {'raw': (), 'floored': (), 'parts': (B,) or (Z,), 'keep': the same shape, 1.0 = kept} -- reading them is the
-        caller's synchronisation.  With the defaults the trainer launches what it launched before and last_kl stays None."""
+        caller's synchronisation.  With the defaults the trainer launches what it launched before and last_kl stays None.
+
+        mmd_coeff (finite, >= 0) > 0 adds the InfoVAE / WAE-MMD term: mmd_coeff times the MMD between the
+        step's z_tilde and its prior draws z_prior, with mmd_kernel 'gaussian' (exp(-d / bandwidth)) or 'imq' (bandwidth / (bandwidth
+        + d)) on the squared distance d, mmd_bandwidth (finite, > 0; None: 2 * z_dim, the expected squared distance of two prior
+        draws) and mmd_estimator 'unbiased' (the U-statistic: needs a batch of 2 or more), 'biased' (the V-statistic) or 'reference'
+        (the reference's compute_mmd_loss as written, which is negative for two samples of one distribution).  The term matches the
+        aggregate posterior to the prior; it is independent of the KL settings and combines with them.  It is part of the objective,
+        so validation (train=False) adds its value too, without the gradient phase.  Under data parallelism it is the MMD of the
+        rank's own shard, as for free_nats_per='dim': no collective.  After a step `last_mmd` holds the device tensors {'value' (the
+        term as added), 'S_xx', 'S_yy', 'S_xy' (the kernel sums, diagonals included)}.  With mmd_coeff == 0 nothing is launched
+        and last_mmd stays None."""
         kl_beta, kl_ramp, free_nats = float(kl_beta), float(kl_ramp), float(free_nats)
         if not (kl_beta >= 0.0 and math.isfinite(kl_beta)):                     # (NaN fails the comparison)
             raise ValueError(f"kl_beta must be finite and >= 0, got {kl_beta}")
@@ -48,11 +62,25 @@ class VAETrainer(Trainer):
             raise ValueError(f"free_nats must be finite and >= 0, got {free_nats}")
         if free_nats_per not in ('measure', 'dim'):
             raise ValueError(f"free_nats_per must be 'measure' or 'dim', got {free_nats_per!r}")
+        mmd_coeff = float(mmd_coeff)
+        if not (mmd_coeff >= 0.0 and math.isfinite(mmd_coeff)):
+            raise ValueError(f"mmd_coeff must be finite and >= 0, got {mmd_coeff}")
+        if not isinstance(mmd_kernel, str) or mmd_kernel not in ops.MMD_KERNEL:
+            raise ValueError(f"mmd_kernel must be 'gaussian' or 'imq', got {mmd_kernel!r}")
+        if mmd_bandwidth is not None:
+            if isinstance(mmd_bandwidth, bool) or not isinstance(mmd_bandwidth, (int, float)) or \
+                    not (mmd_bandwidth > 0.0 and math.isfinite(mmd_bandwidth)):
+                raise ValueError(f"mmd_bandwidth must be None or finite and > 0, got {mmd_bandwidth!r}")
+            mmd_bandwidth = float(mmd_bandwidth)
+        if not isinstance(mmd_estimator, str) or mmd_estimator not in ops.MMD_ESTIMATORS:
+            raise ValueError(f"mmd_estimator must be one of {ops.MMD_ESTIMATORS}, got {mmd_estimator!r}")
         super().__init__(dataset, model, lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay, decay_all=decay_all,
                          ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.kl_beta, self.kl_warmup_steps, self.kl_cycle_steps, self.kl_ramp = kl_beta, kl_warmup_steps, kl_cycle_steps, kl_ramp
         self.free_nats, self.free_nats_per = free_nats, free_nats_per
         self.last_kl = None
+        self.mmd_coeff, self.mmd_kernel, self.mmd_bandwidth, self.mmd_estimator = mmd_coeff, mmd_kernel, mmd_bandwidth, mmd_estimator
+        self.last_mmd = None
         if free_nats > 0.0:
             model.free_bits = (free_nats, free_nats_per)
 
@@ -81,13 +109,26 @@ class VAETrainer(Trainer):
             t1 = score.contiguous().view(-1)
             if t1.dtype != torch.int64:
                 t1 = t1.long()
-            return _ElboFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, beta / z_dist.loc.shape[0],
-                                 self.model.take_stats(2))
+            loss, accuracy = _ElboFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, beta / z_dist.loc.shape[0],
+                                           self.model.take_stats(2))
+            return self._add_mmd(loss, z_tilde, z_prior, train), accuracy
         recons_loss, accuracy = self.mean_crossentropy_loss_and_accuracy(weights, score)
         # (an override written against the reference's two-argument call keeps working while beta is the reference's)
         dist_loss = self.compute_kld_loss(z_dist, prior_dist, **({} if beta == 0.001 else {"beta": beta}))
         loss = recons_loss + dist_loss
-        return loss, accuracy
+        return self._add_mmd(loss, z_tilde, z_prior, train), accuracy
+
+    def _add_mmd(self, loss, z_tilde, z_prior, train):
+        """loss + mmd_coeff * MMD(z_tilde, z_prior); a training pass takes the gradient phase along, validation the value alone."""
+        if not self.mmd_coeff > 0.0:
+            return loss
+        args = (self.mmd_kernel, self.mmd_bandwidth, self.mmd_estimator, self.mmd_coeff)
+        if train and torch.is_grad_enabled() and z_tilde.requires_grad:
+            value, sxx, syy, sxy = _MmdFn.apply(z_tilde, z_prior, *args)
+        else:
+            value, sxx, syy, sxy = ops.mmd(z_tilde.detach().contiguous(), z_prior.detach().contiguous(), *args)[0].unbind(0)
+        self.last_mmd = {"value": value.detach(), "S_xx": sxx, "S_yy": syy, "S_xy": sxy}
+        return loss + value
 
     def process_batch_data(self, batch):
         """(B,1,384) int32 -> (B*16, 24) int64 on the device   (vae_trainer.py:42-55)"""
@@ -104,11 +145,11 @@ class VAETrainer(Trainer):
 
     def training_state(self, next_epoch=0):
         st = super().training_state(next_epoch)
-        st.update({k: getattr(self, k) for k in self.KL_SETTINGS})
+        st.update({k: getattr(self, k) for k in self.KL_SETTINGS + self.MMD_SETTINGS})
         return st
 
     def load_training_state(self, path_or_state):
-        """... and the six KL settings; a state written before they existed leaves this trainer's own."""
+        """... and the six KL and four MMD settings; a state written before they existed leaves this trainer's own."""
         st = torch.load(path_or_state, map_location="cpu") if isinstance(path_or_state, (str, bytes, os.PathLike)) \
             else path_or_state
         out = super().load_training_state(st)
@@ -116,7 +157,22 @@ class VAETrainer(Trainer):
             for k in self.KL_SETTINGS:
                 setattr(self, k, st[k])
             self.model.free_bits = (self.free_nats, self.free_nats_per) if self.free_nats > 0.0 else None
+        if "mmd_coeff" in st:
+            for k in self.MMD_SETTINGS:
+                setattr(self, k, st[k])
         return out
+
+    @staticmethod
+    def compute_mmd_loss(z_tilde, z_prior, coeff=10, kernel='gaussian', bandwidth=16.0, estimator='reference'):
+        """vae_trainer.py:93-126 on the MMD kernels: with the defaults the reference's rule as written -- the
+        Gaussian kernel exp(-d / 16), 1 / (B (B - 1)) / 2 on both self terms with their diagonals in, 2 / B^2 on the cross term --
+        which is negative for two samples of one distribution and whose bandwidth leaves no gradient at z_dim 256; kernel, bandwidth
+        and estimator select the textbook forms (ops.mmd).  z_tilde takes a gradient where it requires one, z_prior is a constant.
+        The reference's helper compute_kernel, which materialises the B x B x Z differences, is not offered."""
+        args = (kernel, bandwidth, estimator, float(coeff))
+        if torch.is_grad_enabled() and z_tilde.requires_grad:
+            return _MmdFn.apply(z_tilde, z_prior, *args)[0]
+        return ops.mmd(z_tilde.detach().contiguous(), z_prior.detach().contiguous(), *args)[0][0]
 
     @staticmethod
     def compute_kld_loss(z_dist, prior_dist, beta=0.001):
