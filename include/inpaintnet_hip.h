@@ -263,6 +263,46 @@ int64_t inet_mmd_ws_bytes(int64_t B, int Z);
 int inet_mmd(const float* x, const float* y, int64_t B, int Z, int kind, float var, double a, double c, double diag, double coeff,
              float* out4, float* grad, void* ws, int64_t ws_bytes, void* stream);
 
+/* The importance-weighted log-likelihood of a measure: the IWAE bound of Burda et al. 2016.  For a measure x_b
+ * (T = 24 tokens) the encoder gives mu_b, ls_b (log sigma), both [Z].  For k = 0..K-1 and eps[b,k,:] standard normal:
+ *   z[b,k,d]   = mu[b,d] + eps[b,k,d] * exp(ls[b,d])
+ *   logr[b,k]  = log p(z) - log q(z|x) = sum_d ( 0.5 eps^2 - 0.5 z^2 + ls[b,d] )     (the 2*pi terms cancel)
+ *   nll[b,k]   = - sum_t log softmax(weights[b,k,t,:])[ x[b,t] ]
+ *                (weights come from the decoder run on z[b,k] with x_b's own tokens fed back: teacher-forced, eval mode, no dropout)
+ *   logw[b,k]  = logr[b,k] - nll[b,k]
+ *   m = max_k logw;  s1 = sum_k exp(logw - m);  s2 = sum_k exp(2 (logw - m))
+ *   iwae[b] = m + log(s1 / K)         lower bound on log p(x_b), tight as K grows
+ *   elbo[b] = (sum_k logw) / K        the single-sample bound, averaged
+ *   ess[b]  = s1^2 / s2               effective sample size, in [1, K]
+ *   rec[b]  = (sum_k nll) / K
+ *   kl[b]   = -(sum_k logr) / K, the Monte-Carlo KL, formed as -(sum_k logw + sum_k nll) / K: rec + kl = -elbo
+ * A NaN anywhere in a measure's logw row: iwae, elbo and ess are all NaN.  m == -inf (every sample has zero weight): iwae = elbo =
+ * -inf and ess = 0.  A +inf in the row: whatever IEEE gives (NaN).  No float atomics, every sum in a fixed order: two calls on the
+ * same inputs give the same bits.  Every entry returns -1 for a bad argument before any launch, -2 for a failed launch.
+ *
+ * inet_iw_draw: one wavefront per row r = b * Kc + j of a chunk of Kc samples: reads mu + b Z, logsigma + b Z and eps + b *
+ * eps_stride_b + j * Z (a chunk of a larger (B, K, Z) tensor needs no copy), writes z[r,:] ([B*Kc, Z] contiguous) and logr[r].  The
+ * element is inet_reparam_kl's: expf, mu + eps * s.  16-byte loads and stores where Z % 4 == 0, eps_stride_b % 4 == 0 and mu,
+ * logsigma, eps, z are 16-byte aligned (a lane adds the terms of d = 4 lane .. 4 lane + 3, then 256 further on), else a scalar path
+ * (d = lane, lane + 64, ...); in both a lane adds in ascending d and a xor tree adds the lanes.  -1: a null pointer, B, Kc or Z < 1,
+ * B * Kc > 2^24, eps_stride_b < Kc * Z. */
+int inet_iw_draw(const float* mu, const float* logsigma, const float* eps, int64_t eps_stride_b, float* z, float* logr, int64_t B, int Kc,
+                 int Z, void* stream);
+/* One workgroup of four waves per measure row r < R: weights [R*T, V] with row stride ld_w >= V, targets int64 [R, T], logr (nullable:
+ * reads as 0) [R].  Wave w takes ticks w, w + 4, ...; per tick inet_cross_entropy's arithmetic (the maximum, expf(x - m) added per lane
+ * in ascending v, the xor tree, lse = m + logf(se), the term lse - x[target]); lane 0 adds its ticks in ascending order, the four
+ * partial sums meet as (p0 + p1) + (p2 + p3).  nll and logw = logr - nll (each nullable, not both) are written at [(r / group) * ld_out
+ * + r % group]: a chunk of `group` samples per measure lands in its columns of a (B, K) array with ld_out = K.  A target outside [0, V)
+ * writes NaN for that row and reads nothing through it; a -inf logit at the target gives nll = +inf, logw = -inf.  -1: weights or
+ * targets null, nll and logw both null, R, group, T or V < 1, R > 2^24, ld_w < V, R % group != 0, ld_out < group. */
+int inet_nll_rows(const float* weights, int64_t ld_w, const int64_t* targets, const float* logr, float* nll, float* logw, int64_t ld_out,
+                  int64_t R, int group, int T, int V, void* stream);
+/* One wavefront per measure b < B over logw, nll [B, K] (float32, row stride ld >= K); all arithmetic in double on the widened values:
+ * the maximum, then s1, s2, sum logw, sum nll per lane in ascending k and a xor tree.  out [B, 5] float64 = {iwae, elbo, ess, rec, kl};
+ * iwae is formed as m + log(s1 / K), in this order (K = 1 and K equal weights are exact).  -1: a null pointer, B or K < 1, B > 2^24,
+ * ld < K. */
+int inet_iw_finish(const float* logw, const float* nll, int64_t ld, int64_t B, int K, double* out, void* stream);
+
 /* rows of V (post-ReLU) logits -> out[row*stride] ~ Multinomial(softmax(row))  (decoder.py:506-509): inverse-CDF draw with
  * one counter-based uniform per row keyed (seed, offset + row): row r of a call at `offset` is row 0 of a call at offset + r.
  * The token drawn always has mass (exp(w - max) > 0 in float32): where rounding leaves every prefix sum at or below

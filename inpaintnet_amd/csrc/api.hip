@@ -13,6 +13,7 @@
 #include "gru_step_bf3.h"
 #include "side.h"
 #include "mmd.h"
+#include "iw.h"
 
 namespace {
 
@@ -258,6 +259,18 @@ int inet_mmd(const float* x, const float* y, int64_t B, int Z, int kind, float v
     if (!x || !y || !out4 || B < 1 || B > (1 << 24) || Z < 1 || (kind != MMD_GAUSSIAN && kind != MMD_IMQ)) return -1;
     if (!(var > 0.f) || !std::isfinite(var) || !std::isfinite(a) || !std::isfinite(c) || !std::isfinite(diag) || !std::isfinite(coeff)) return -1;
     return mmd_launch(x, y, B, Z, kind, var, a, c, diag, coeff, out4, grad, ws, ws_bytes, (hipStream_t)stream);
+}
+// the importance-weighted log-likelihood (iw.hip): the launchers refuse a bad argument themselves, before anything is launched
+int inet_iw_draw(const float* mu, const float* logsigma, const float* eps, int64_t eps_stride_b, float* z, float* logr, int64_t B, int Kc,
+                 int Z, void* stream) {
+    return iw_draw_launch(mu, logsigma, eps, eps_stride_b, z, logr, B, Kc, Z, (hipStream_t)stream);
+}
+int inet_nll_rows(const float* weights, int64_t ld_w, const int64_t* targets, const float* logr, float* nll, float* logw, int64_t ld_out,
+                  int64_t R, int group, int T, int V, void* stream) {
+    return nll_rows_launch(weights, ld_w, (const long long*)targets, logr, nll, logw, ld_out, R, group, T, V, (hipStream_t)stream);
+}
+int inet_iw_finish(const float* logw, const float* nll, int64_t ld, int64_t B, int K, double* out, void* stream) {
+    return iw_finish_launch(logw, nll, ld, B, K, out, (hipStream_t)stream);
 }
 // the four entry points of the optimizer step: one check, one launcher (pw_adam_step)
 static int adam_step_checked(const PwAdamStep& a, void* stream) {

@@ -7,6 +7,7 @@ torch.autograd.Function whose forward/backward are single calls into the C-ABI
 (include/inpaintnet_hip.h); parameter gradients are accumulated straight into
 the model's flat gradient arena (`model.grad`) by the backward kernels.
 """
+import contextlib
 import os
 import random
 
@@ -512,6 +513,54 @@ class MeasureVAE(Model):
         dummy = torch.zeros(z.shape[0], self.num_ticks_per_measure, device=z.device)
         return self.decoder(z, dummy, train=False, temperature=temperature, uniforms=uniforms, top_k=top_k, top_p=top_p, allowed=allowed,
                             **({} if forced is None else {"forced": forced}))
+
+    def log_weights(self, score, num_samples, eps=None, generator=None, max_rows=4096, reproducible=True):
+        """The log importance weights of the IWAE bound: score (B, 24) int64 -> (logw, nll), both float32
+        (B, K) on the device, K = num_samples.  logw[b, k] = log p(z) - log q(z | x_b) - nll[b, k] for z = mu_b + eps[b, k] * sigma_b,
+        nll[b, k] the negative log-likelihood of x_b's 24 tokens under the decoder run on z with x_b's own tokens fed back
+        (teacher-forced, eval mode).  ops.iw_finish turns them into (iwae, elbo, ess, rec, kl).  Runs under torch.no_grad(); ValueError
+        in training mode: a likelihood under dropout is not the model's.  The encoder runs once; the decoder sees blocks of Bc = min(B,
+        max_rows) measures and chunks of Kc = max(1, max_rows // Bc) samples, Bc * Kc rows a call.  eps: float32 (B, K, Z), the
+        draws to use; None: drawn per (block, chunk), in that order, from `generator` (the device's default one if None) -- another
+        max_rows then means other draws for the same seed.  reproducible: the encoder's and the decoder's products run with one k range
+        each (ops.one_k_range: no f32 atomics), so that the same draws give the same bits from call to call -- 7 % slower at 256
+        measures x 16 samples; False leaves the planner's choice, and two calls then agree to about 1e-7 of a weight only.  The call
+        ends with a synchronisation and the chain / token checks."""
+        if self.training:
+            raise ValueError("log_weights: the model is in training mode; a likelihood under dropout is not the model's -- call eval()")
+        K, max_rows = int(num_samples), int(max_rows)
+        if K < 1 or max_rows < 1:
+            raise ValueError(f"log_weights: num_samples and max_rows must be >= 1, got {num_samples} and {max_rows}")
+        if score.dim() != 2 or score.size(1) != self.num_ticks_per_measure or score.size(0) < 1:
+            raise ValueError(f"log_weights: score must be (B, {self.num_ticks_per_measure}), got {tuple(score.shape)}")
+        B, Z = score.size(0), self.latent_space_dim
+        score = score.long().contiguous()
+        if eps is not None and not (isinstance(eps, torch.Tensor) and eps.dtype == torch.float32 and tuple(eps.shape) == (B, K, Z)
+                                    and eps.device == score.device and eps.is_contiguous()):
+            raise ValueError(f"log_weights: eps must be a contiguous float32 ({B}, {K}, {Z}) tensor on the score's device")
+        with torch.no_grad(), (ops.one_k_range() if reproducible else contextlib.nullcontext()):
+            z_dist = self.encoder(score)
+            mu, ls = z_dist.loc.contiguous(), z_dist.log_scale.contiguous()
+            logw = torch.empty(B, K, dtype=torch.float32, device=mu.device)
+            nll = torch.empty_like(logw)
+            Bc = min(B, max_rows)
+            Kc = max(1, max_rows // Bc)
+            for b0 in range(0, B, Bc):
+                b1 = min(B, b0 + Bc)
+                block = score[b0:b1]
+                for k0 in range(0, K, Kc):
+                    k1 = min(K, k0 + Kc)
+                    if eps is None:
+                        e = torch.randn(b1 - b0, k1 - k0, Z, dtype=torch.float32, device=mu.device, generator=generator)
+                    else:
+                        e = eps[b0:b1, k0:k1]
+                    z, logr = ops.iw_draw(mu[b0:b1], ls[b0:b1], e)
+                    rows = block.repeat_interleave(k1 - k0, 0)       # row b * Kc + j: measure b, as iw_draw orders z
+                    weights, _ = self.decoder(z, rows, train=False, teacher_forced=True)
+                    ops.nll_rows(weights, rows, logr, group=k1 - k0, out_nll=nll[b0:b1, k0:k1], out_logw=logw[b0:b1, k0:k1], ld_out=K)
+        torch.cuda.synchronize()
+        ops.check_chains("MeasureVAE.log_weights")
+        return logw, nll
 
     def _standard_normal(self, like):
         """N(0, 1) of the latent's shape (measure_vae.py:122-125): the constant loc / scale tensors are built once."""

@@ -4,6 +4,7 @@ torch is used here only for device memory and the current stream; every number
 is produced by the HIP kernels behind include/inpaintnet_hip.h.  All functions
 are asynchronous on torch's current stream.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -581,6 +582,112 @@ def mmd(z, z_prior, kernel="gaussian", bandwidth=None, estimator="unbiased", coe
     return out4, grad
 
 
+def _iw_f32(name, t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+        raise ValueError(f"{name}: {what} must be a float32 device tensor")
+    return t
+
+
+def iw_draw(mu, ls, eps):
+    """K-sample reparameterisation with each draw's density ratio (include/inpaintnet_hip.h inet_iw_draw).
+    mu, ls [B, Z] contiguous; eps [B, Kc, Z] standard normal draws, rows contiguous -- a chunk eps_all[:, k0:k1] of a larger (B, K, Z)
+    tensor is taken as it is, without a copy.  -> (z [B * Kc, Z], logr [B * Kc]), row b * Kc + j: z = mu[b] + eps[b, j] * exp(ls[b]),
+    logr = log p(z) - log q(z | x) = sum_d (0.5 eps^2 - 0.5 z^2 + ls).  Two calls on the same inputs give the same bits."""
+    for name, t in (("mu", mu), ("ls", ls), ("eps", eps)):
+        _iw_f32("iw_draw", t, name)
+    if mu.dim() != 2 or ls.shape != mu.shape or not (mu.is_contiguous() and ls.is_contiguous()):
+        raise ValueError(f"iw_draw: mu and ls must be contiguous [B, Z] tensors of one shape, got {tuple(mu.shape)} and {tuple(ls.shape)}")
+    B, Z = mu.shape
+    if eps.dim() != 3 or eps.shape[0] != B or eps.shape[2] != Z or B < 1 or Z < 1 or eps.shape[1] < 1:
+        raise ValueError(f"iw_draw: eps must be [B, Kc, Z] = [{B}, Kc >= 1, {Z}], got {tuple(eps.shape)}")
+    Kc = eps.shape[1]
+    if eps.stride(2) != 1 or eps.stride(1) != Z or (B > 1 and eps.stride(0) < Kc * Z):
+        raise ValueError(f"iw_draw: the rows eps[b, j, :] must be contiguous and a measure's Kc rows adjacent, got strides {eps.stride()}")
+    if ls.device != mu.device or eps.device != mu.device:
+        raise ValueError("iw_draw: mu, ls and eps must lie on one device")
+    if B * Kc > 1 << 24:
+        raise ValueError(f"iw_draw: B * Kc = {B * Kc} rows exceed 2^24; draw in chunks")
+    z = torch.empty(B * Kc, Z, dtype=torch.float32, device=mu.device)
+    logr = torch.empty(B * Kc, dtype=torch.float32, device=mu.device)
+    _hold(mu, ls, eps, z, logr)
+    check(_lib.lib().inet_iw_draw(ptr(mu), ptr(ls), ptr(eps), max(eps.stride(0), Kc * Z), ptr(z), ptr(logr), B, Kc, Z, stream_ptr()),
+          "inet_iw_draw")
+    return z, logr
+
+
+def nll_rows(weights, targets, logr=None, group=None, out_nll=None, out_logw=None, ld_out=None):
+    """The negative log-likelihood of every measure row under its own logits (include/inpaintnet_hip.h inet_nll_rows, DESIGN.md
+    section 26).  weights [R, T, V] float32 (the decoder's output; the last dimension contiguous, the rows [R * T] evenly strided),
+    targets [R, T] int64 contiguous, logr [R] float32 contiguous or None (reads as 0).  nll[r] = -sum_t log softmax(weights[r, t])[
+    targets[r, t]] and logw[r] = logr[r] - nll[r] are written at [r // group, r % group] of their outputs (group None: 1).  out_nll /
+    out_logw: float32 [R / group, group] views with contiguous rows of one row stride -- the columns of a chunk in a (B, K) array; when
+    only one is given the other is not computed (None comes back); when neither is given both are allocated with row stride ld_out
+    (None: group).  ld_out with outputs given must be their row stride.  A target outside [0, V) leaves NaN in that row.
+    -> (nll, logw)."""
+    _iw_f32("nll_rows", weights, "weights")
+    if weights.dim() != 3 or min(weights.shape) < 1:
+        raise ValueError(f"nll_rows: weights must be [R, T, V], got {tuple(weights.shape)}")
+    R, T, V = weights.shape
+    ld_w = weights.stride(1)
+    if weights.stride(2) != 1 or ld_w < V or (R > 1 and weights.stride(0) != T * ld_w):
+        raise ValueError(f"nll_rows: weights must have a contiguous last dimension and evenly strided rows, got strides {weights.stride()}")
+    if not (isinstance(targets, torch.Tensor) and targets.dtype == torch.int64 and tuple(targets.shape) == (R, T)
+            and targets.is_contiguous() and targets.device == weights.device):
+        raise ValueError(f"nll_rows: targets must be a contiguous int64 [{R}, {T}] tensor on the weights' device")
+    if logr is not None:
+        _iw_f32("nll_rows", logr, "logr")
+        if tuple(logr.shape) != (R,) or not logr.is_contiguous() or logr.device != weights.device:
+            raise ValueError(f"nll_rows: logr must be a contiguous [{R}] tensor on the weights' device")
+    group = 1 if group is None else int(group)
+    if group < 1 or R % group != 0:
+        raise ValueError(f"nll_rows: group must be >= 1 and divide R = {R}, got {group}")
+    if R > 1 << 24:
+        raise ValueError(f"nll_rows: R = {R} rows exceed 2^24; score in chunks")
+    rows_out = R // group
+    given = [o for o in (out_nll, out_logw) if o is not None]
+    if given:
+        for o in given:
+            _iw_f32("nll_rows", o, "an output")
+            if tuple(o.shape) != (rows_out, group) or o.stride(1) != 1 or o.device != weights.device \
+                    or (rows_out > 1 and o.stride(0) < group):
+                raise ValueError(f"nll_rows: an output must be a [{rows_out}, {group}] view with contiguous rows on the weights' device")
+        ld = given[0].stride(0) if rows_out > 1 else (group if ld_out is None else int(ld_out))
+        if any(rows_out > 1 and o.stride(0) != ld for o in given) or (ld_out is not None and int(ld_out) != ld):
+            raise ValueError("nll_rows: the outputs and ld_out must agree on one row stride")
+    else:
+        ld = group if ld_out is None else int(ld_out)
+        if ld < group:
+            raise ValueError(f"nll_rows: ld_out must be >= group = {group}, got {ld}")
+        out_nll = torch.empty(rows_out, ld, dtype=torch.float32, device=weights.device)[:, :group]
+        out_logw = torch.empty(rows_out, ld, dtype=torch.float32, device=weights.device)[:, :group]
+    _hold(weights, targets, logr, out_nll, out_logw)
+    check(_lib.lib().inet_nll_rows(ptr(weights), ld_w, ptr(targets), ptr(logr), ptr(out_nll), ptr(out_logw), ld, R, group, T, V,
+                                   stream_ptr()), "inet_nll_rows")
+    return out_nll, out_logw
+
+
+IW_COLUMNS = ("iwae", "elbo", "ess", "rec", "kl")
+
+
+def iw_finish(logw, nll):
+    """The log-mean-exp over the samples and what comes out of the same pass (include/inpaintnet_hip.h inet_iw_finish, DESIGN.md
+    section 26).  logw, nll [B, K] float32 of one shape and row stride, rows contiguous -> float64 [B, 5], the columns IW_COLUMNS =
+    (iwae, elbo, ess, rec, kl): iwae = m + log(s1 / K), elbo = mean logw, ess = s1^2 / s2, rec = mean nll, kl = -mean (logw + nll),
+    all in double.  A NaN in a row of logw: iwae, elbo, ess NaN; every weight -inf: (-inf, -inf, 0)."""
+    _iw_f32("iw_finish", logw, "logw"); _iw_f32("iw_finish", nll, "nll")
+    if logw.dim() != 2 or nll.shape != logw.shape or min(logw.shape) < 1:
+        raise ValueError(f"iw_finish: logw and nll must be [B, K] tensors of one shape, got {tuple(logw.shape)} and {tuple(nll.shape)}")
+    B, K = logw.shape
+    if nll.device != logw.device or logw.stride(1) != 1 or nll.stride(1) != 1 or (B > 1 and (logw.stride(0) < K or nll.stride(0) != logw.stride(0))):
+        raise ValueError("iw_finish: logw and nll must lie on one device with contiguous rows of one row stride")
+    if B > 1 << 24:
+        raise ValueError(f"iw_finish: B = {B} exceeds 2^24")
+    out = torch.empty(B, 5, dtype=torch.float64, device=logw.device)
+    _hold(logw, nll, out)
+    check(_lib.lib().inet_iw_finish(ptr(logw), ptr(nll), logw.stride(0) if B > 1 else K, B, K, ptr(out), stream_ptr()), "inet_iw_finish")
+    return out
+
+
 def _adam_arenas(p, g, m, v, partials, report):
     """What every optimizer entry point asks of its tensors: four float32 arenas of one size; `partials` (where given) what
     grad_sqnorm left; `report` (where given) pinned int32 words, four of them, eight with partials.  Returns the size."""
@@ -713,6 +820,22 @@ def set_option(key, value):
     5 LDS-free GEMM kernels (0 never / 1 by shape / 2 whenever the shape qualifies / 3 direct kernels only, no workgroup split-K / 4
     workgroup split-K first)."""
     check(_lib.lib().inet_set_option(int(key), int(value)), "inet_set_option")
+
+
+@contextlib.contextmanager
+def one_k_range():
+    """Inside the block every f32 product the planner would hand to a split-K kernel runs the LDS-tiled kernel in tile configuration 0
+    with ONE k range per output tile (inet_set_option keys 2 and 3, the settings tests/test_gpu_bench_sizes.py forces): no zero fill
+    and no f32 atomics, whose order of accumulation changes from launch to launch -- two identical calls of the encoder or the decoder
+    then return the same bits.  Leaving the block hands the choice back to the planner (-1, 0): the options are
+    process-wide and have no getter, so a caller that had forced them itself finds them reset."""
+    set_option(2, 0)
+    set_option(3, 1)
+    try:
+        yield
+    finally:
+        set_option(2, -1)
+        set_option(3, 0)
 
 
 def prof_dump(path):

@@ -101,6 +101,37 @@ class VAETester(object):
             raise ValueError("mmd: the loader is empty")
         return total / count
 
+    LL_COLUMNS = ops.IW_COLUMNS                      # ('iwae', 'elbo', 'ess', 'rec', 'kl')
+
+    def measure_log_likelihood(self, score_tensor, num_samples=64, eps=None, generator=None, max_rows=4096):
+        """score_tensor (N, 24) -> float64 (N, 5) on the device, the columns LL_COLUMNS per measure: iwae, the
+        importance-weighted bound on log p(x) from num_samples draws of the encoder's posterior (Burda et al. 2016; tight as
+        num_samples grows); elbo, the single-sample bound averaged over the same draws; ess, the effective sample size in [1,
+        num_samples]; rec and kl, the Monte-Carlo reconstruction and KL terms, rec + kl = -elbo.  In nats per measure; comparable
+        between models whatever beta, floor or MMD term they were trained with.  eps / generator / max_rows: MeasureVAE.log_weights."""
+        score = to_cuda_variable_long(score_tensor)
+        logw, nll = self.model.log_weights(score, num_samples, eps=eps, generator=generator, max_rows=max_rows)
+        return ops.iw_finish(logw, nll)
+
+    def log_likelihood(self, data_loader, num_samples=64, generator=None, max_rows=4096):
+        """The means over all measures of the loader of measure_log_likelihood's columns: {iwae, elbo, ess, rec, kl, measures,
+        nats_per_tick}, nats_per_tick = -iwae / 24.  Accumulated in float64 on the device, read once at the end."""
+        total, count = None, 0
+        n_bars = getattr(self.dataset, "n_bars", None)
+        for score_tensor, _ in data_loader:
+            if n_bars is not None and score_tensor.dim() == 3:
+                score_tensor = score_tensor.reshape(score_tensor.size(0) * n_bars, -1)
+            cols = self.measure_log_likelihood(score_tensor, num_samples, generator=generator, max_rows=max_rows).sum(0)
+            total = cols if total is None else total + cols
+            count += int(score_tensor.shape[0])
+        if total is None:
+            raise ValueError("log_likelihood: the loader is empty")
+        means = (total / count).tolist()
+        out = dict(zip(self.LL_COLUMNS, means))
+        out["measures"] = count
+        out["nats_per_tick"] = -out["iwae"] / self.measure_seq_len
+        return out
+
     def loss_and_acc_test(self, data_loader):
         """vae_tester.py:113-160: mean reconstruction CE / accuracy over a loader (eval mode, no teacher forcing)."""
         tot = torch.zeros(3)
