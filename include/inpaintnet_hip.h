@@ -263,6 +263,35 @@ int64_t inet_mmd_ws_bytes(int64_t B, int Z);
 int inet_mmd(const float* x, const float* y, int64_t B, int Z, int kind, float var, double a, double c, double diag, double coeff,
              float* out4, float* grad, void* ws, int64_t ws_bytes, void* stream);
 
+/* Attribute-regularised latent dimensions (AR-VAE, Pati & Lerch 2020).
+ *
+ * inet_measure_attrs: tokens [B, T] int64 -> out [B, 4] float32, the columns (num_notes, note_range, rhy_entropy, beat_strength) of the
+ * reference's dataset (folk_dataset.py:607-708), each ONE float operation on ONE exact integer, so that equal attributes are equal bits:
+ *   num_notes     = (T - #slur - #rest) / T
+ *   note_range    = (max midi - min midi) / (midi_hi - midi_lo) over the row's pitched tokens (not slur, rest or None, midi[token] >= 0);
+ *                   0 for a row with none -- per ROW (the reference never resets its has_note flag between rows)
+ *   rhy_entropy   = logf(n), n = the number of non-slur ticks; 0 for n = 0 (the reference: NaN)
+ *   beat_strength = (1000 n0 + 150 n3 + 8 nrest) / 1000, the non-slur ticks at t % 6 == 0, at t % 6 == 3 and elsewhere
+ * V: the vocabulary; slur_index, rest_index, none_index: the three symbols, -1 = the vocabulary has none; midi: V device int32, -1 for
+ * a token without a pitch.  A token outside [0, V) makes its row's four values NaN and never indexes the table.  One coalesced read of
+ * the tokens, no atomics.  -1: a null pointer, B < 1, B > 2^24, V < 1, T not a positive multiple of 6 or > 96, an index outside
+ * [-1, V), midi_hi <= midi_lo -- before any launch.
+ *
+ * inet_attr_reg: z [B, Z] float32; dims: A distinct latent dimensions (HOST ints), 1 <= A <= 8; attrs [B, A] float32, any attributes.
+ * With x = z[:, dims[a]], t_ij = tanhf(delta (x_i - x_j)), s_ij = sgn(attrs[i, a] - attrs[j, a]), sgn(0) = 0:
+ *   L_a = (1 / B^2) sum_ij |t_ij - s_ij|;   out[1 + A] = {coeff sum_a L_a, L_0, .., L_{A-1}}
+ *   counts [A][3] int64 over ordered pairs i != j: concordant (s != 0 and sgn(x_i - x_j) == s), discordant (== -s), attribute-tied (s == 0)
+ *   grad (nullable: the value only) [B, A] = d out[0] / d z[:, dims[a]] = (2 coeff delta / B^2) sum_j sgn(t_ij - s_ij) (1 - t_ij^2)
+ * A NaN in z or attrs reaches the value.  No atomics, every float sum in an order that depends on (B, A) alone: the same inputs give
+ * the same bits, and the value's bits do not depend on grad.  Two launches (pair, finish) through `ws`: inet_attr_reg_ws_bytes(B, A)
+ * bytes of device memory, nothing to zero.  -1: a null z, dims, attrs, out or counts, B < 1, B > 2^24, Z < 1, A outside [1, 8], a
+ * dimension outside [0, Z) or named twice, delta or coeff not finite, ws null or ws_bytes too small -- before any launch. */
+int inet_measure_attrs(const int64_t* tokens, int64_t B, int T, int V, int slur_index, int rest_index, int none_index, const int32_t* midi,
+                       int midi_lo, int midi_hi, float* out, void* stream);
+int64_t inet_attr_reg_ws_bytes(int64_t B, int A);
+int inet_attr_reg(const float* z, int64_t B, int Z, const int32_t* dims, int A, const float* attrs, float delta, double coeff, float* out,
+                  int64_t* counts, float* grad, void* ws, int64_t ws_bytes, void* stream);
+
 /* The importance-weighted log-likelihood of a measure: the IWAE bound of Burda et al. 2016.  For a measure x_b
  * (T = 24 tokens) the encoder gives mu_b, ls_b (log sigma), both [Z].  For k = 0..K-1 and eps[b,k,:] standard normal:
  *   z[b,k,d]   = mu[b,d] + eps[b,k,d] * exp(ls[b,d])

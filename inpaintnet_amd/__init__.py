@@ -17,4 +17,11 @@ import os as _os
 # GPU is enough; a value the user has set is respected.  
 _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
-__all__ = ["synthetic"]
+__all__ = ["synthetic", "attributes", "ATTRIBUTES", "AttributeSpec"]
+
+
+def __getattr__(name):
+    if name in ("ATTRIBUTES", "AttributeSpec"):          # (inpaintnet_amd.attributes: data only, no HIP library needed)
+        from . import attributes
+        return getattr(attributes, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,7 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INET_LIB_PATH") or os.path.join(_HERE, "libinpaintnet_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["preload.hip", "arnn_gen.hip", "decode_b1.hip", "gemm.hip", "gru.hip", "pointwise.hip", "seq.hip", "vae.hip", "api.hip", "prof.hip", "side.hip", "lstm.hip", "gru_chain.hip", "decode_chain.hip", "gru_chain2.hip", "gemm_bf3.hip", "gru_step_bf3.hip", "mmd.hip", "iw.hip"]
+SOURCES = ["preload.hip", "arnn_gen.hip", "decode_b1.hip", "gemm.hip", "gru.hip", "pointwise.hip", "seq.hip", "vae.hip", "api.hip", "prof.hip", "side.hip", "lstm.hip", "gru_chain.hip", "decode_chain.hip", "gru_chain2.hip", "gemm_bf3.hip", "gru_step_bf3.hip", "mmd.hip", "iw.hip", "attr.hip"]
 
 _lib = None
 
@@ -114,6 +114,9 @@ _SIGNATURES = {
     "inet_latent_bwd_fb": (C.c_int, [_P, _P, _P, _P, _F, _P, _P, _I, _P, _P, _L, _I, _P]),
     "inet_mmd_ws_bytes": (_L, [_L, _I]),
     "inet_mmd": (C.c_int, [_P, _P, _L, _I, _I, _F] + [C.c_double] * 4 + [_P, _P, _P, _L, _P]),
+    "inet_measure_attrs": (C.c_int, [_P, _L] + [_I] * 5 + [_P, _I, _I, _P, _P]),
+    "inet_attr_reg_ws_bytes": (_L, [_L, _I]),
+    "inet_attr_reg": (C.c_int, [_P, _L, _I, _P, _I, _P, _F, C.c_double, _P, _P, _P, _P, _L, _P]),
     "inet_iw_draw": (C.c_int, [_P, _P, _P, _L, _P, _P, _L, _I, _I, _P]),
     "inet_nll_rows": (C.c_int, [_P, _L, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P]),
     "inet_iw_finish": (C.c_int, [_P, _P, _L, _L, _I, _P, _P]),

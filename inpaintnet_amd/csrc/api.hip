@@ -14,6 +14,7 @@
 #include "side.h"
 #include "mmd.h"
 #include "iw.h"
+#include "attr.h"
 
 namespace {
 
@@ -259,6 +260,26 @@ int inet_mmd(const float* x, const float* y, int64_t B, int Z, int kind, float v
     if (!x || !y || !out4 || B < 1 || B > (1 << 24) || Z < 1 || (kind != MMD_GAUSSIAN && kind != MMD_IMQ)) return -1;
     if (!(var > 0.f) || !std::isfinite(var) || !std::isfinite(a) || !std::isfinite(c) || !std::isfinite(diag) || !std::isfinite(coeff)) return -1;
     return mmd_launch(x, y, B, Z, kind, var, a, c, diag, coeff, out4, grad, ws, ws_bytes, (hipStream_t)stream);
+}
+// attribute-regularised latent dimensions (attr.hip)
+int inet_measure_attrs(const int64_t* tokens, int64_t B, int T, int V, int slur_index, int rest_index, int none_index, const int32_t* midi,
+                       int midi_lo, int midi_hi, float* out, void* stream) {
+    return attr_measure_launch((const long long*)tokens, B, T, V, slur_index, rest_index, none_index, midi, midi_lo, midi_hi, out,
+                               (hipStream_t)stream);
+}
+int64_t inet_attr_reg_ws_bytes(int64_t B, int A) { return B > (1 << 24) ? -1 : attr_reg_ws_bytes(B, A); }
+int inet_attr_reg(const float* z, int64_t B, int Z, const int32_t* dims, int A, const float* attrs, float delta, double coeff, float* out,
+                  int64_t* counts, float* grad, void* ws, int64_t ws_bytes, void* stream) {
+    if (!z || !dims || !attrs || !out || !counts || B < 1 || B > (1 << 24) || Z < 1 || A < 1 || A > kAttrMaxA) return -1;
+    if (!std::isfinite(delta) || !std::isfinite(coeff)) return -1;
+    AttrDims d{};
+    for (int a = 0; a < A; ++a) {
+        if (dims[a] < 0 || dims[a] >= Z) return -1;
+        for (int b = 0; b < a; ++b)
+            if (dims[b] == dims[a]) return -1;
+        d.d[a] = dims[a];
+    }
+    return attr_reg_launch(z, B, Z, d, A, attrs, delta, coeff, out, (long long*)counts, grad, ws, ws_bytes, (hipStream_t)stream);
 }
 // the importance-weighted log-likelihood (iw.hip): the launchers refuse a bad argument themselves, before anything is launched
 int inet_iw_draw(const float* mu, const float* logsigma, const float* eps, int64_t eps_stride_b, float* z, float* logr, int64_t B, int Kc,

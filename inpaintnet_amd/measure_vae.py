@@ -8,6 +8,7 @@ torch.autograd.Function whose forward/backward are single calls into the C-ABI
 the model's flat gradient arena (`model.grad`) by the backward kernels.
 """
 import contextlib
+import functools
 import os
 import random
 
@@ -151,6 +152,39 @@ class _MmdFn(torch.autograd.Function):
         if gloss is None or G is None:
             return None, None, None, None, None, None
         return G * gloss, None, None, None, None, None
+
+
+@functools.lru_cache(maxsize=None)
+def _attr_columns(dims, device):
+    """The regularised columns as a device index, made once per (dims, device): no host-to-device copy inside a step."""
+    return torch.tensor(dims, dtype=torch.int64, device=device)
+
+
+class _AttrRegFn(torch.autograd.Function):
+    """The attribute regularisation of z_tilde's dimensions `dims` towards the columns of `attrs` (ops.attr_reg)
+    as a loss term: where z_tilde takes a gradient the pair launch of the forward also leaves G = d value / d z_tilde[:, dims], and
+    the backward scatters G * gloss into a [B, Z] gradient that is zero outside those columns.  attrs is a constant.
+    -> value, per_attr [A], counts [A, 3]."""
+
+    @staticmethod
+    def forward(ctx, z_tilde, dims, attrs, delta, coeff):
+        out, counts, G = ops.attr_reg(z_tilde.contiguous(), dims, attrs.detach().contiguous(), delta, coeff,
+                                      want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(G)
+        ctx.dims, ctx.z_shape = list(dims), tuple(z_tilde.shape)
+        value, per_attr = out[0], out[1:]
+        ctx.mark_non_differentiable(per_attr, counts)
+        ctx.set_materialize_grads(False)
+        return value, per_attr, counts
+
+    @staticmethod
+    def backward(ctx, gloss, _gper, _gcounts):
+        G, = ctx.saved_tensors
+        if gloss is None or G is None:
+            return None, None, None, None, None
+        dz = torch.zeros(ctx.z_shape, dtype=G.dtype, device=G.device)
+        dz.index_copy_(1, _attr_columns(tuple(ctx.dims), G.device), G * gloss)
+        return dz, None, None, None, None
 
 
 class _ReparamFbFn(torch.autograd.Function):

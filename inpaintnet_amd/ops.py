@@ -582,6 +582,79 @@ def mmd(z, z_prior, kernel="gaussian", bandwidth=None, estimator="unbiased", coe
     return out4, grad
 
 
+ATTR_MAX_DIMS = 8
+
+
+def measure_attributes(tokens, spec):
+    """tokens [B, T] int64 on the device, T a multiple of 6 (at most 96) -> [B, 4] float32, the columns attributes.ATTRIBUTES of every
+    measure (include/inpaintnet_hip.h inet_measure_attrs).  spec: an attributes.AttributeSpec.  A token outside
+    [0, spec.num_tokens) makes its row NaN."""
+    from .attributes import ATTRIBUTES, AttributeSpec
+    if not isinstance(spec, AttributeSpec):
+        raise ValueError(f"measure_attributes: spec must be an AttributeSpec, got {type(spec).__name__}")
+    if not (isinstance(tokens, torch.Tensor) and tokens.is_cuda and tokens.dtype == torch.int64 and tokens.dim() == 2
+            and tokens.is_contiguous()):
+        raise ValueError("measure_attributes: tokens must be a contiguous [B, T] int64 device tensor")
+    B, T = tokens.shape
+    if B < 1 or T < 6 or T % 6 != 0 or T > 96:
+        raise ValueError(f"measure_attributes: tokens must be [B >= 1, T] with T a positive multiple of 6, at most 96; got {(B, T)}")
+    out = torch.empty(B, len(ATTRIBUTES), dtype=torch.float32, device=tokens.device)
+    midi = spec.midi_table(tokens.device)
+    _hold(tokens, midi)
+    check(_lib.lib().inet_measure_attrs(ptr(tokens), B, T, spec.num_tokens, spec.slur_index, spec.rest_index, spec.none_index, ptr(midi),
+                                        spec.pitch_range[0], spec.pitch_range[1], ptr(out), stream_ptr()), "inet_measure_attrs")
+    return out
+
+
+def attr_dims(dims, Z):
+    """dims as a list of 1 .. 8 distinct ints inside [0, Z), or a ValueError."""
+    try:
+        dims = list(dims)
+    except TypeError:
+        raise ValueError(f"attr_reg: dims must be a sequence of latent dimensions, got {dims!r}")
+    if not 1 <= len(dims) <= ATTR_MAX_DIMS:
+        raise ValueError(f"attr_reg: between 1 and {ATTR_MAX_DIMS} dimensions a call, got {len(dims)}")
+    for d in dims:
+        if isinstance(d, bool) or not isinstance(d, int) or not 0 <= d < Z:
+            raise ValueError(f"attr_reg: every dimension must be an int in [0, {Z}), got {d!r}")
+    if len(set(dims)) != len(dims):
+        raise ValueError(f"attr_reg: the dimensions must be distinct, got {dims}")
+    return dims
+
+
+def attr_reg(z, dims, attrs, delta=10.0, coeff=1.0, want_grad=False):
+    """The attribute regularisation of AR-VAE (include/inpaintnet_hip.h inet_attr_reg): z [B, Z], dims: A distinct
+    latent dimensions (1 <= A <= 8, host ints), attrs [B, A] float32 -- any attributes.  -> (out, counts, G): out [1 + A] = {coeff sum_a
+    L_a, L_0, ..}, L_a = mean_ij |tanh(delta (z_i - z_j)) - sgn(a_i - a_j)| on dimension dims[a]; counts [A, 3] int64 = {concordant,
+    discordant, attribute-tied} ordered pairs i != j; G = d out[0] / d z[:, dims] [B, A] with want_grad, else None (the value launches
+    only).  Two calls on the same inputs give the same bits, and the value's bits do not depend on want_grad."""
+    for name, t in (("z", z), ("attrs", attrs)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()):
+            raise ValueError(f"attr_reg: {name} must be a contiguous 2-d float32 device tensor")
+    B, Z = z.shape
+    if B < 1 or Z < 1:
+        raise ValueError(f"attr_reg: z must be [B >= 1, Z >= 1], got {tuple(z.shape)}")
+    dims = attr_dims(dims, Z)
+    A = len(dims)
+    if tuple(attrs.shape) != (B, A):
+        raise ValueError(f"attr_reg: attrs must be [{B}, {A}] (one column per dimension), got {tuple(attrs.shape)}")
+    delta, coeff = float(delta), float(coeff)
+    if not (abs(delta) <= 3.4028234663852886e38):                               # NaN, inf, or past the largest float32
+        raise ValueError(f"attr_reg delta must be finite, got {delta}")
+    if not math.isfinite(coeff):
+        raise ValueError(f"attr_reg coeff must be finite, got {coeff}")
+    dev = z.device
+    out = torch.empty(1 + A, dtype=torch.float32, device=dev)
+    counts = torch.empty(A, 3, dtype=torch.int64, device=dev)
+    grad = torch.empty(B, A, dtype=torch.float32, device=dev) if want_grad else None
+    L = _lib.lib()
+    ws = _ws(L.inet_attr_reg_ws_bytes(B, A), dev)
+    _hold(z, attrs, ws)
+    check(L.inet_attr_reg(ptr(z), B, Z, (C.c_int32 * A)(*dims), A, ptr(attrs), delta, coeff, ptr(out), ptr(counts), ptr(grad), ptr(ws),
+                          ws.numel() * 4, stream_ptr()), "inet_attr_reg")
+    return out, counts, grad
+
+
 def _iw_f32(name, t, what):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
         raise ValueError(f"{name}: {what} must be a float32 device tensor")

@@ -9,6 +9,7 @@ import os
 import torch
 
 from . import ops
+from .attributes import ATTRIBUTES, AttributeSpec
 from .helpers import to_cuda_variable_long
 from .trainer import Trainer
 
@@ -131,6 +132,80 @@ class VAETester(object):
         out["measures"] = count
         out["nats_per_tick"] = -out["iwae"] / self.measure_seq_len
         return out
+
+    ATTRIBUTES = ATTRIBUTES                          # ('num_notes', 'note_range', 'rhy_entropy', 'beat_strength')
+
+    def _spec(self, spec):
+        if spec is None:
+            if getattr(self, "_attr_spec", None) is None:
+                self._attr_spec = AttributeSpec.from_dataset(self.dataset)
+            spec = self._attr_spec
+        return spec
+
+    def measure_attributes(self, score_tensor, spec=None):
+        """score_tensor (B, 24) -> float32 (B, 4) on the device, the columns ATTRIBUTES of every measure (ops.measure_attributes,
+        DESIGN.md section 27).  spec None: AttributeSpec.from_dataset(self.dataset)."""
+        return ops.measure_attributes(to_cuda_variable_long(score_tensor).contiguous(), self._spec(spec))
+
+    def attribute_concordance(self, data_loader, dims=None, spec=None):
+        """float64 (Z or len(dims), 4) on the device: for latent dimension d (dims None: all of them) and attribute k, (concordant -
+        discordant) / (concordant + discordant) over the ordered pairs i != j of measures WITHIN each batch of the loader whose
+        attributes differ -- concordant where the posterior mean's dimension d orders the pair as the attribute does.  +1: the
+        dimension sorts the measures by the attribute; 0: it knows nothing of it; NaN where no pair differs.  The number that says
+        whether the regularisation took.  The counts come from ops.attr_reg's value launches, 8 dimensions a
+        call, and are accumulated over the batches as integers."""
+        spec = self._spec(spec)
+        Z = self.z_dim
+        dims = list(range(Z)) if dims is None else list(dims)
+        if not dims:
+            raise ValueError("attribute_concordance: no dimensions")
+        for i0 in range(0, len(dims), ops.ATTR_MAX_DIMS):
+            ops.attr_dims(dims[i0:i0 + ops.ATTR_MAX_DIMS], Z)
+        total = None
+        n_bars = getattr(self.dataset, "n_bars", None)
+        for score_tensor, _ in data_loader:
+            if n_bars is not None and score_tensor.dim() == 3:
+                score_tensor = score_tensor.reshape(score_tensor.size(0) * n_bars, -1)
+            score = to_cuda_variable_long(score_tensor).contiguous()
+            with torch.no_grad():
+                loc = self.model.encoder(score).loc.contiguous()
+                attrs = ops.measure_attributes(score, spec)
+                counts = torch.empty(len(dims), len(ATTRIBUTES), 3, dtype=torch.int64, device=loc.device)
+                for k in range(len(ATTRIBUTES)):
+                    for i0 in range(0, len(dims), ops.ATTR_MAX_DIMS):
+                        chunk = dims[i0:i0 + ops.ATTR_MAX_DIMS]
+                        counts[i0:i0 + len(chunk), k] = ops.attr_reg(loc, chunk, attrs[:, k:k + 1].expand(-1, len(chunk)).contiguous())[1]
+            total = counts if total is None else total + counts
+            ops.check_chains("VAETester.attribute_concordance")
+        if total is None:
+            raise ValueError("attribute_concordance: the loader is empty")
+        c, d = total[..., 0].double(), total[..., 1].double()
+        return (c - d) / (c + d)
+
+    def attribute_sweep(self, score_tensor, dim, values, spec=None):
+        """Encodes score_tensor (B, 24), sets the posterior mean's dimension `dim` to each of `values` in turn and decodes by argmax
+        (eval mode, the free-running decoder: ONE decoder call of batch len(values) * B) -> (attrs, tokens): the decoded measures'
+        attributes float32 (len(values), B, 4) and their tokens int64 (len(values), B, 24).  On a model trained with attr_reg the
+        attribute tied to `dim` rises along `values`."""
+        spec = self._spec(spec)
+        values = [float(v) for v in values]
+        if isinstance(dim, bool) or not isinstance(dim, int) or not 0 <= dim < self.z_dim:
+            raise ValueError(f"attribute_sweep: dim must be an int in [0, {self.z_dim}), got {dim!r}")
+        if not values:
+            raise ValueError("attribute_sweep: no values")
+        score = to_cuda_variable_long(score_tensor).contiguous()
+        B, T = score.shape
+        with torch.no_grad():
+            loc = self.model.encoder(score).loc
+            z = loc.unsqueeze(0).repeat(len(values), 1, 1)
+            z[:, :, dim] = torch.tensor(values, dtype=z.dtype, device=z.device).view(-1, 1)
+            dummy = torch.zeros(len(values) * B, T, device=z.device)
+            _, samples = self.decoder(z.reshape(len(values) * B, -1).contiguous(), dummy, self.train)
+        torch.cuda.synchronize()
+        ops.check_chains("VAETester.attribute_sweep")               # never hand back tokens of a failed persistent launch
+        tokens = samples.reshape(len(values) * B, T).long().contiguous()
+        attrs = ops.measure_attributes(tokens, spec)
+        return attrs.view(len(values), B, len(ATTRIBUTES)), tokens.view(len(values), B, T)
 
     def loss_and_acc_test(self, data_loader):
         """vae_tester.py:113-160: mean reconstruction CE / accuracy over a loader (eval mode, no teacher forcing)."""

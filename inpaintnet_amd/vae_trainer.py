@@ -6,7 +6,8 @@ import torch
 
 from . import ops
 from .helpers import to_cuda_variable_long
-from .measure_vae import _MmdFn
+from .attributes import ATTRIBUTES, AttributeSpec
+from .measure_vae import _AttrRegFn, _MmdFn, _attr_columns
 from .trainer import Trainer, _ElboFn, _KLFn
 
 
@@ -15,11 +16,14 @@ class VAETrainer(Trainer):
 
     KL_SETTINGS = ("kl_beta", "kl_warmup_steps", "kl_cycle_steps", "kl_ramp", "free_nats", "free_nats_per")
     MMD_SETTINGS = ("mmd_coeff", "mmd_kernel", "mmd_bandwidth", "mmd_estimator")
+    ATTR_SETTINGS = ("attr_reg", "attr_gamma", "attr_delta", "attr_spec")
 
     def __init__(self, dataset, model, lr=1e-4, max_grad_norm=None, weight_decay=0.0, decay_all=False, ema_decay=None,
                  ema_warmup=False, kl_beta=0.001, kl_warmup_steps=0, kl_cycle_steps=0, kl_ramp=0.5, free_nats=0.0,
-                 free_nats_per='measure', mmd_coeff=0.0, mmd_kernel='gaussian', mmd_bandwidth=None, mmd_estimator='unbiased'):
-        """The loss of a training step is CE + beta_t / B * kl_sum [+ mmd_coeff * MMD(z_tilde, z_prior)].
+                 free_nats_per='measure', mmd_coeff=0.0, mmd_kernel='gaussian', mmd_bandwidth=None, mmd_estimator='unbiased',
+                 attr_reg=None, attr_gamma=10.0, attr_delta=10.0, attr_spec=None):
+        """The loss of a training step is CE + beta_t / B * kl_sum [+ mmd_coeff * MMD(z_tilde, z_prior)]
+        [+ attr_gamma * sum_a L_a(z_tilde, attributes of the step's tokens)].
 
         kl_beta (finite, >= 0): the KL weight; the reference's 0.001.  kl_warmup_steps (an int >= 0): beta rises linearly from 0 to
         kl_beta over that many optimizer steps, then holds.  kl_cycle_steps = M > 0: cyclical annealing (Fu et al. 2019) -- within
@@ -47,7 +51,18 @@ class VAETrainer(Trainer):
         so validation (train=False) adds its value too, without the gradient phase.  Under data parallelism it is the MMD of the
         rank's own shard, as for free_nats_per='dim': no collective.  After a step `last_mmd` holds the device tensors {'value' (the
         term as added), 'S_xx', 'S_yy', 'S_xy' (the kernel sums, diagonals included)}.  With mmd_coeff == 0 nothing is launched
-        and last_mmd stays None."""
+        and last_mmd stays None.
+
+        attr_reg, a mapping from attribute name (attributes.ATTRIBUTES) to latent dimension such as {'num_notes': 0, 'note_range': 1},
+        adds the attribute regularisation of AR-VAE (Pati & Lerch 2020): for every entry attr_gamma (finite,
+        >= 0) times mean_ij |tanh(attr_delta (z_i - z_j)) - sgn(a_i - a_j)| over the batch's pairs, z the named dimension of the
+        step's z_tilde and a the attribute of the step's own tokens (ops.measure_attributes with attr_spec, an AttributeSpec; None:
+        AttributeSpec.from_dataset(dataset)).  After training, moving along that dimension moves the attribute.  The dimensions must
+        be distinct ints inside z_dim, at most 8; attr_delta finite and > 0.  The term is added after the MMD term and combines with
+        it and with the KL settings; a training pass takes its gradient, validation the value alone; under data parallelism it is
+        computed on the rank's own shard.  After a step `last_attr_reg` holds the device tensors {'value' (the term as added),
+        'per_attr' (A,), 'counts' (A, 3) int64: concordant, discordant, attribute-tied ordered pairs, 'attrs' (B, A)}, in the order
+        of attr_reg's entries.  With attr_reg=None nothing is launched and last_attr_reg stays None."""
         kl_beta, kl_ramp, free_nats = float(kl_beta), float(kl_ramp), float(free_nats)
         if not (kl_beta >= 0.0 and math.isfinite(kl_beta)):                     # (NaN fails the comparison)
             raise ValueError(f"kl_beta must be finite and >= 0, got {kl_beta}")
@@ -74,6 +89,7 @@ class VAETrainer(Trainer):
             mmd_bandwidth = float(mmd_bandwidth)
         if not isinstance(mmd_estimator, str) or mmd_estimator not in ops.MMD_ESTIMATORS:
             raise ValueError(f"mmd_estimator must be one of {ops.MMD_ESTIMATORS}, got {mmd_estimator!r}")
+        attr_reg, attr_gamma, attr_delta, attr_spec = self._attr_settings(attr_reg, attr_gamma, attr_delta, attr_spec)
         super().__init__(dataset, model, lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay, decay_all=decay_all,
                          ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.kl_beta, self.kl_warmup_steps, self.kl_cycle_steps, self.kl_ramp = kl_beta, kl_warmup_steps, kl_cycle_steps, kl_ramp
@@ -81,8 +97,37 @@ class VAETrainer(Trainer):
         self.last_kl = None
         self.mmd_coeff, self.mmd_kernel, self.mmd_bandwidth, self.mmd_estimator = mmd_coeff, mmd_kernel, mmd_bandwidth, mmd_estimator
         self.last_mmd = None
+        self.attr_reg, self.attr_gamma, self.attr_delta, self.attr_spec = attr_reg, attr_gamma, attr_delta, attr_spec
+        self.last_attr_reg = None
+        if attr_reg is not None:
+            z_dim = model.latent_space_dim
+            if max(attr_reg.values()) >= z_dim:
+                raise ValueError(f"attr_reg: every latent dimension must lie inside z_dim = {z_dim}, got {attr_reg}")
+            if attr_spec is None:
+                self.attr_spec = AttributeSpec.from_dataset(dataset)
         if free_nats > 0.0:
             model.free_bits = (free_nats, free_nats_per)
+
+    @staticmethod
+    def _attr_settings(attr_reg, attr_gamma, attr_delta, attr_spec):
+        """The four attribute settings checked and in their stored form (attr_reg: a dict in the caller's order, or None)."""
+        if attr_reg is not None:
+            if not hasattr(attr_reg, "items") or len(attr_reg) == 0:
+                raise ValueError(f"attr_reg must be None or a non-empty mapping from attribute name to latent dimension, got {attr_reg!r}")
+            attr_reg = dict(attr_reg.items())
+            for name, d in attr_reg.items():
+                if name not in ATTRIBUTES:
+                    raise ValueError(f"attr_reg: attribute names must come from {ATTRIBUTES}, got {name!r}")
+                if isinstance(d, bool) or not isinstance(d, int) or d < 0:
+                    raise ValueError(f"attr_reg: the latent dimension of {name!r} must be an int >= 0, got {d!r}")
+            if len(set(attr_reg.values())) != len(attr_reg):
+                raise ValueError(f"attr_reg: the latent dimensions must be distinct, got {attr_reg}")
+        for name, v, strict in (("attr_gamma", attr_gamma, False), ("attr_delta", attr_delta, True)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0.0 or (strict and v == 0.0):
+                raise ValueError(f"{name} must be finite and {'> 0' if strict else '>= 0'}, got {v!r}")
+        if attr_spec is not None and not isinstance(attr_spec, AttributeSpec):
+            raise ValueError(f"attr_spec must be None or an AttributeSpec, got {type(attr_spec).__name__}")
+        return attr_reg, float(attr_gamma), float(attr_delta), attr_spec
 
     def beta_at(self, t):
         """The KL weight of the step whose loss is built while adam_t == t (a pure function of the settings)."""
@@ -111,12 +156,12 @@ class VAETrainer(Trainer):
                 t1 = t1.long()
             loss, accuracy = _ElboFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, beta / z_dist.loc.shape[0],
                                            self.model.take_stats(2))
-            return self._add_mmd(loss, z_tilde, z_prior, train), accuracy
+            return self._add_attr_reg(self._add_mmd(loss, z_tilde, z_prior, train), z_tilde, score, train), accuracy
         recons_loss, accuracy = self.mean_crossentropy_loss_and_accuracy(weights, score)
         # (an override written against the reference's two-argument call keeps working while beta is the reference's)
         dist_loss = self.compute_kld_loss(z_dist, prior_dist, **({} if beta == 0.001 else {"beta": beta}))
         loss = recons_loss + dist_loss
-        return self._add_mmd(loss, z_tilde, z_prior, train), accuracy
+        return self._add_attr_reg(self._add_mmd(loss, z_tilde, z_prior, train), z_tilde, score, train), accuracy
 
     def _add_mmd(self, loss, z_tilde, z_prior, train):
         """loss + mmd_coeff * MMD(z_tilde, z_prior); a training pass takes the gradient phase along, validation the value alone."""
@@ -128,6 +173,26 @@ class VAETrainer(Trainer):
         else:
             value, sxx, syy, sxy = ops.mmd(z_tilde.detach().contiguous(), z_prior.detach().contiguous(), *args)[0].unbind(0)
         self.last_mmd = {"value": value.detach(), "S_xx": sxx, "S_yy": syy, "S_xy": sxy}
+        return loss + value
+
+    def _add_attr_reg(self, loss, z_tilde, score, train):
+        """loss + attr_gamma * sum_a L_a; a training pass takes the gradient phase along, validation the value alone."""
+        if self.attr_reg is None:
+            return loss
+        tokens = score.contiguous()
+        if tokens.dtype != torch.int64:
+            tokens = tokens.long()
+        cols = [ATTRIBUTES.index(name) for name in self.attr_reg]
+        attrs = ops.measure_attributes(tokens, self.attr_spec)
+        if cols != list(range(len(ATTRIBUTES))):
+            attrs = attrs.index_select(1, _attr_columns(tuple(cols), attrs.device))
+        dims = list(self.attr_reg.values())
+        if train and torch.is_grad_enabled() and z_tilde.requires_grad:
+            value, per_attr, counts = _AttrRegFn.apply(z_tilde, dims, attrs, self.attr_delta, self.attr_gamma)
+        else:
+            out, counts, _ = ops.attr_reg(z_tilde.detach().contiguous(), dims, attrs, self.attr_delta, self.attr_gamma)
+            value, per_attr = out[0], out[1:]
+        self.last_attr_reg = {"value": value.detach(), "per_attr": per_attr, "counts": counts, "attrs": attrs}
         return loss + value
 
     def process_batch_data(self, batch):
@@ -146,10 +211,12 @@ class VAETrainer(Trainer):
     def training_state(self, next_epoch=0):
         st = super().training_state(next_epoch)
         st.update({k: getattr(self, k) for k in self.KL_SETTINGS + self.MMD_SETTINGS})
+        st.update(attr_reg=None if self.attr_reg is None else dict(self.attr_reg), attr_gamma=self.attr_gamma,
+                  attr_delta=self.attr_delta, attr_spec=None if self.attr_spec is None else self.attr_spec.state())
         return st
 
     def load_training_state(self, path_or_state):
-        """... and the six KL and four MMD settings; a state written before they existed leaves this trainer's own."""
+        """... and the six KL, four MMD and four attribute settings; a state written before they existed leaves this trainer's own."""
         st = torch.load(path_or_state, map_location="cpu") if isinstance(path_or_state, (str, bytes, os.PathLike)) \
             else path_or_state
         out = super().load_training_state(st)
@@ -160,6 +227,10 @@ class VAETrainer(Trainer):
         if "mmd_coeff" in st:
             for k in self.MMD_SETTINGS:
                 setattr(self, k, st[k])
+        if "attr_reg" in st:
+            spec = st["attr_spec"]
+            self.attr_reg, self.attr_gamma, self.attr_delta, self.attr_spec = self._attr_settings(
+                st["attr_reg"], st["attr_gamma"], st["attr_delta"], None if spec is None else AttributeSpec(**spec))
         return out
 
     @staticmethod
