@@ -292,6 +292,46 @@ int64_t inet_attr_reg_ws_bytes(int64_t B, int A);
 int inet_attr_reg(const float* z, int64_t B, int Z, const int32_t* dims, int A, const float* attrs, float delta, double coeff, float* out,
                   int64_t* counts, float* grad, void* ws, int64_t ws_bytes, void* stream);
 
+/* Class-weighted, label-smoothed cross-entropy with an ignore index, and per-class statistics.  The definition
+ * is torch.nn.functional.cross_entropy(x, t, weight=w, label_smoothing=e, ignore_index=i, reduction='mean'):
+ *   valid_r = t_r != i and 0 <= t_r < V;  p = softmax(x_r);  W = sum_c w_c;  denom = sum_valid w[t_r]
+ *   loss = [(1 - e) sum_valid w[t_r] (lse_r - x_r[t_r]) + (e / V) sum_valid sum_c w_c (lse_r - x_r[c])] / denom
+ *   dloss / dx_r[c] = valid_r [(1 - e) w[t_r] (p_c - 1{c = t_r}) + (e / V) (W p_c - w_c)] / denom
+ * class_weight: V device floats (finite, >= 0; 0 is legal), null = all ones.  ignore_index: a HOST pointer, null = nothing is ignored.
+ * ONE divergence from torch: with denom == 0 (every row ignored, or every present target has weight 0) the loss is NaN as torch's is,
+ * but dW is ALL ZEROS (torch: zeros in the first case, NaN in the second).
+ *
+ * inet_class_counts: targets, n int64 on the device -> out, 8 + V + extra_words int64 words on the device, ALL zeroed
+ * by the call (extra_words >= 0: room the caller wants zeroed along, such as the class_stats of the loss launch that follows):
+ *   out[0] the bits of the double denom = sum_c w_c counts_c, added in class order: a pure function of the counts; out[1] n_valid;
+ *   out[2] n_bad; out[5] the bits of the double W; out[3], out[4] tickets of the launches, 0 between calls; out[8 + c] counts[c].
+ * Integer atomics only: the same bits on every call.  A target outside [0, V) that is not ignore_index is never used as an index: it
+ * is treated as ignored, counted in n_bad, and the launch sets the token status word (inet_token_status), as a bad embedding index does.
+ * -1: a null targets or out, n < 1, n > 2^40, V < 1, extra_words < 0.
+ *
+ * inet_cross_entropy_w: one wavefront per row of `weights` (row stride ld_w >= V; the padding is never read), the row read once.
+ * meta: the block inet_class_counts left for the SAME targets, weights and ignore_index (denom, n_valid and W are read from it; the
+ * backward reuses the forward's).  Outputs, each nullable, at least one given:
+ *   dW [rows, ld_dw >= V] = dloss / dx [* scale_dev[0]], the padding never written; an ignored row is exactly 0
+ *   loss[0] = the loss [+ add_scale * add_term[0]];  accuracy[0] = hits / n_valid over the valid rows, unweighted, argmax_first
+ *     (inet_argmax's rule); both WRITTEN, not accumulated
+ *   fwd_out[0] = fwd_scale * scale_dev[0] (needs scale_dev)
+ *   class_stats [V, 3] int64 += {rows with this target, of those the hits, rows with this argmax}; confusion [V, V] int64 += 1 at
+ *     [target, argmax]: the caller zeroes them, a loop over batches accumulates
+ * With dW alone (the backward) there is no sum and no finishing pass.  Float sums go through one double partial per workgroup and the
+ * workgroup that finishes last, which adds them in a fixed order that depends on rows alone: no float atomics, loss, accuracy and dW
+ * have the same bits from call to call, the loss the same bits with or without dW.  Without class_weight, smoothing and ignored rows,
+ * dW and the hit count are inet_cross_entropy_ex's bits (scale = 1 / rows).  ws: inet_cross_entropy_w_ws_bytes(rows) bytes, needed
+ * for loss or accuracy, nothing to zero.  -1: a null weights, targets or meta, rows < 1, V < 1, no output, ld_w < V, ld_dw < V,
+ * label_smoothing outside [0, 1], fwd_out without scale_dev, add_term without loss, ws missing or too small -- before any launch. */
+int inet_class_counts(const int64_t* targets, int64_t n, int V, const float* class_weight, const int64_t* ignore_index, int64_t* out,
+                      int64_t extra_words, void* stream);
+int64_t inet_cross_entropy_w_ws_bytes(int rows);
+int inet_cross_entropy_w(const float* weights, int64_t ld_w, int rows, int V, const int64_t* targets, const float* class_weight,
+                         double label_smoothing, const int64_t* ignore_index, int64_t* meta, float* dW, int64_t ld_dw,
+                         const float* scale_dev, float* loss, float* accuracy, const float* add_term, float add_scale, float* fwd_out,
+                         float fwd_scale, int64_t* class_stats, int64_t* confusion, void* ws, int64_t ws_bytes, void* stream);
+
 /* The importance-weighted log-likelihood of a measure: the IWAE bound of Burda et al. 2016.  For a measure x_b
  * (T = 24 tokens) the encoder gives mu_b, ls_b (log sigma), both [Z].  For k = 0..K-1 and eps[b,k,:] standard normal:
  *   z[b,k,d]   = mu[b,d] + eps[b,k,d] * exp(ls[b,d])

@@ -11,7 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INET_LIB_PATH") or os.path.join(_HERE, "libinpaintnet_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["preload.hip", "arnn_gen.hip", "decode_b1.hip", "gemm.hip", "gru.hip", "pointwise.hip", "seq.hip", "vae.hip", "api.hip", "prof.hip", "side.hip", "lstm.hip", "gru_chain.hip", "decode_chain.hip", "gru_chain2.hip", "gemm_bf3.hip", "gru_step_bf3.hip", "mmd.hip", "iw.hip", "attr.hip"]
+SOURCES = ["preload.hip", "arnn_gen.hip", "decode_b1.hip", "gemm.hip", "gru.hip", "pointwise.hip", "seq.hip", "vae.hip", "api.hip", "prof.hip", "side.hip", "lstm.hip", "gru_chain.hip", "decode_chain.hip", "gru_chain2.hip", "gemm_bf3.hip", "gru_step_bf3.hip", "mmd.hip", "iw.hip", "attr.hip", "ce.hip"]
 
 _lib = None
 
@@ -117,6 +117,9 @@ _SIGNATURES = {
     "inet_measure_attrs": (C.c_int, [_P, _L] + [_I] * 5 + [_P, _I, _I, _P, _P]),
     "inet_attr_reg_ws_bytes": (_L, [_L, _I]),
     "inet_attr_reg": (C.c_int, [_P, _L, _I, _P, _I, _P, _F, C.c_double, _P, _P, _P, _P, _L, _P]),
+    "inet_class_counts": (C.c_int, [_P, _L, _I, _P, _P, _P, _L, _P]),
+    "inet_cross_entropy_w_ws_bytes": (_L, [_I]),
+    "inet_cross_entropy_w": (C.c_int, [_P, _L, _I, _I, _P, _P, C.c_double, _P, _P, _P, _L, _P, _P, _P, _P, _F, _P, _F, _P, _P, _P, _L, _P]),
     "inet_iw_draw": (C.c_int, [_P, _P, _P, _L, _P, _P, _L, _I, _I, _P]),
     "inet_nll_rows": (C.c_int, [_P, _L, _P, _P, _P, _P, _L, _L, _I, _I, _I, _P]),
     "inet_iw_finish": (C.c_int, [_P, _P, _L, _L, _I, _P, _P]),

@@ -23,7 +23,7 @@ from .helpers import to_cuda_variable_long
 from .latent_rnn_trainer import LatentRNNTrainer
 from .measure_vae import _DropState, _next_mask_offset
 from .model import Model, default_device
-from .trainer import Trainer
+from .trainer import Trainer, _ce_w_apply
 
 
 class _EmbeddingFn(torch.autograd.Function):
@@ -546,9 +546,10 @@ class AnticipationRNNGaussianRegTrainer(Trainer):
     """AnticipationRNN/anticipation_rnn_trainer.py:8-182"""
 
     def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, ce_weight=None, label_smoothing=0.0, ignore_index=None):
         super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
-                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup, ce_weight=ce_weight,
+                         label_smoothing=label_smoothing, ignore_index=ignore_index)
         self.min_num_measures_target = 2
         self.max_num_measure_target = 6
         self.measure_seq_len = self.dataset.subdivision * self.dataset.num_beats_per_bar
@@ -559,14 +560,28 @@ class AnticipationRNNGaussianRegTrainer(Trainer):
                                 constraints_loc=constraints_loc, start_tick=start_tick, end_tick=end_tick, train=train, trim=True)
         free = free_positions(constraints_loc)
         targets = score_tensor[:, :, free].transpose(0, 1)                     # (voice, batch, n_free)
-        return self.mean_crossentropy_loss_and_accuracy_voices(weights, targets)
+        if self._ce_plain():
+            self.last_ce = None
+            return self.mean_crossentropy_loss_and_accuracy_voices(weights, targets)
+        w, e, i = self._ce_args(weights[0].device)
+        self.last_ce = {}
+        return self.mean_crossentropy_loss_and_accuracy_voices(weights, targets, weight=w, label_smoothing=e, ignore_index=i,
+                                                               sink=self.last_ce)
 
     @staticmethod
-    def mean_crossentropy_loss_and_accuracy_voices(weights, targets):
-        """mean over voices of the per-voice mean CE / accuracy (:154-182)"""
+    def mean_crossentropy_loss_and_accuracy_voices(weights, targets, weight=None, label_smoothing=0.0, ignore_index=None, sink=None):
+        """mean over voices of the per-voice mean CE / accuracy (:154-182); weight, label_smoothing and ignore_index as
+        Trainer.mean_crossentropy_loss_and_accuracy takes them, each voice with its own denominator.  sink: a dict that receives
+        the device tensors of Trainer.last_ce, summed over the voices."""
         loss = acc = 0
         for i, w in enumerate(weights):
-            l, a = Trainer.mean_crossentropy_loss_and_accuracy(w, targets[i])
+            if weight is None and label_smoothing == 0.0 and ignore_index is None:
+                l, a = Trainer.mean_crossentropy_loss_and_accuracy(w, targets[i])
+            else:
+                one = {}
+                l, a = _ce_w_apply(w, targets[i], weight, label_smoothing, ignore_index, one)
+                if sink is not None:
+                    sink.update(one if i == 0 else {k: sink[k] + v for k, v in one.items()})
             loss, acc = loss + l, acc + a
         return loss / len(weights), acc / len(weights)
 
@@ -606,9 +621,10 @@ class AnticipationRNNBaselineTrainer(AnticipationRNNGaussianRegTrainer):
     Python's `random` (p) and torch's CPU generator (the mask), in the reference's order."""
 
     def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, ce_weight=None, label_smoothing=0.0, ignore_index=None):
         super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
-                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup, ce_weight=ce_weight,
+                         label_smoothing=label_smoothing, ignore_index=ignore_index)
         self.constraint_prod = 0.5
 
     def process_batch_data(self, batch):

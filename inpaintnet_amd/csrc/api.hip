@@ -15,6 +15,7 @@
 #include "mmd.h"
 #include "iw.h"
 #include "attr.h"
+#include "ce.h"
 
 namespace {
 
@@ -280,6 +281,23 @@ int inet_attr_reg(const float* z, int64_t B, int Z, const int32_t* dims, int A, 
         d.d[a] = dims[a];
     }
     return attr_reg_launch(z, B, Z, d, A, attrs, delta, coeff, out, (long long*)counts, grad, ws, ws_bytes, (hipStream_t)stream);
+}
+// class-weighted, label-smoothed cross-entropy and the per-class statistics (ce.hip); ignore_index: a HOST pointer, null = none
+int inet_class_counts(const int64_t* targets, int64_t n, int V, const float* class_weight, const int64_t* ignore_index, int64_t* out,
+                      int64_t extra_words, void* stream) {
+    return ce_count_launch((const long long*)targets, n, V, class_weight, ignore_index != nullptr, ignore_index ? *ignore_index : 0,
+                           (long long*)out, extra_words, (hipStream_t)stream);
+}
+int64_t inet_cross_entropy_w_ws_bytes(int rows) { return ce_w_ws_bytes(rows); }
+int inet_cross_entropy_w(const float* weights, int64_t ld_w, int rows, int V, const int64_t* targets, const float* class_weight,
+                         double label_smoothing, const int64_t* ignore_index, int64_t* meta, float* dW, int64_t ld_dw,
+                         const float* scale_dev, float* loss, float* accuracy, const float* add_term, float add_scale, float* fwd_out,
+                         float fwd_scale, int64_t* class_stats, int64_t* confusion, void* ws, int64_t ws_bytes, void* stream) {
+    if (rows < 1 || ((loss || accuracy) && (!ws || ws_bytes < ce_w_ws_bytes(rows)))) return -1;
+    CeWArgs a{weights, ld_w, rows, V, (const long long*)targets, class_weight, label_smoothing, ignore_index != nullptr,
+              ignore_index ? *ignore_index : 0, (long long*)meta, dW, ld_dw, scale_dev, loss, accuracy, add_term, add_scale, fwd_out,
+              fwd_scale, (long long*)class_stats, (long long*)confusion, ws};
+    return ce_w_launch(a, (hipStream_t)stream);
 }
 // the importance-weighted log-likelihood (iw.hip): the launchers refuse a bad argument themselves, before anything is launched
 int inet_iw_draw(const float* mu, const float* logsigma, const float* eps, int64_t eps_stride_b, float* z, float* logr, int64_t B, int Kc,

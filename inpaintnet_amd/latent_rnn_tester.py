@@ -14,7 +14,7 @@ import torch
 
 from . import ops
 from .helpers import to_cuda_variable_long
-from .trainer import Trainer
+from .trainer import Trainer, class_report_from_counts, class_stats_add, index_to_note_names
 
 
 class LatentRNNTester(object):
@@ -205,6 +205,28 @@ class LatentRNNTester(object):
         else:
             raise ValueError('Invalid argument "type"')
         return to_cuda_variable_long(torch.full((1, num_measures, self.measure_seq_len), int(symbol), dtype=torch.int32))
+
+    def class_report(self, data_loader, fix_num_target=4):
+        """The per-class report of VAETester.class_report for inpainting: the eval-mode forward and fixed split of
+        loss_and_acc_test, statistics and confusion matrix accumulated on the device over the loader."""
+        from .latent_rnn_trainer import LatentRNNTrainer
+        stats = conf = None
+        for score_tensor, _ in data_loader:
+            n_meas = score_tensor.size(-1) // self.measure_seq_len
+            n_past = (n_meas - fix_num_target) // 2
+            past, future, target = LatentRNNTrainer.split_score(score_tensor, n_past, n_meas - n_past - fix_num_target,
+                                                                fix_num_target, self.measure_seq_len)
+            with torch.no_grad():
+                w, _, _ = self.model(past, future, target, fix_num_target, train=False)
+            if stats is None:
+                V = w.size(-1)
+                stats = torch.zeros(V, 3, dtype=torch.int64, device=w.device)
+                conf = torch.zeros(V, V, dtype=torch.int64, device=w.device)
+            class_stats_add(w, target, stats, conf)
+            ops.check_chains("LatentRNNTester.class_report")
+        if stats is None:
+            raise ValueError("class_report: the loader is empty")
+        return class_report_from_counts(stats, conf, index_to_note_names(self.dataset, stats.shape[0]))
 
     def loss_and_acc_test(self, data_loader, fix_num_target=4):
         """Mean loss / accuracy of inpainting over a loader, fixed split as the reference's test loop (:298-340)."""

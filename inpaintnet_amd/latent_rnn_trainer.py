@@ -17,9 +17,10 @@ class LatentRNNTrainer(Trainer):
     feed_fields = (0,)                     # the metadata tensor of a batch is never read (latent_rnn_trainer.py:31-33)
 
     def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, ce_weight=None, label_smoothing=0.0, ignore_index=None):
         super().__init__(dataset, model, lr, early_stopping, max_grad_norm=max_grad_norm, weight_decay=weight_decay,
-                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         decay_all=decay_all, ema_decay=ema_decay, ema_warmup=ema_warmup, ce_weight=ce_weight,
+                         label_smoothing=label_smoothing, ignore_index=ignore_index)
         # window sizes of the stochastic split (latent_rnn_trainer.py:17-22)
         self.min_num_measures_target, self.max_num_measure_target = 2, 6
         n_bars = self.dataset.n_bars
@@ -37,7 +38,7 @@ class LatentRNNTrainer(Trainer):
         n_gen = self.dataset.n_bars - past.size(1) - future.size(1)
         weights, _samples, _gen_z = self.model(past_context=past, future_context=future, target=target,
                                                measures_to_generate=n_gen, train=train)
-        return self.mean_crossentropy_loss_and_accuracy(weights, target)
+        return self._ce_loss(weights, target)
 
     def update_scheduler(self, epoch_num):
         return

@@ -381,6 +381,85 @@ def cross_entropy_ex(weights2d, targets1d, loss_sum=None, correct=None, dW=None,
                                            ptr(fwd_out), float(fwd_scale), stream_ptr()), "inet_cross_entropy_ex")
 
 
+CE_META_WORDS = 8                    # the words in front of the counts (include/inpaintnet_hip.h): denom, n_valid, n_bad, two tickets, W, two spare
+
+
+class ClassCounts:
+    """What inet_class_counts left on the device: `block` (CE_META_WORDS + V int64) and views of it -- counts (V,) int64, n_valid and
+    n_bad () int64, denom () float64 = sum_c w_c counts_c.  Reading any of them is the caller's synchronisation."""
+    __slots__ = ("block", "V", "counts", "extra", "n_valid", "n_bad", "denom")
+
+    def __init__(self, block, V):
+        self.block, self.V = block, V
+        self.counts = block[CE_META_WORDS:CE_META_WORDS + V]
+        self.extra = block[CE_META_WORDS + V:]                                  # the words the caller asked to have zeroed along
+        self.n_valid, self.n_bad = block[1], block[2]
+        self.denom = block[0:1].view(torch.float64)[0]
+
+
+def _ce_common(name, V, weight, label_smoothing, ignore_index, device):
+    """(class weights or None, smoothing as a float, ignore_index as a ctypes reference or None), checked."""
+    if weight is not None:
+        if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and weight.dim() == 1 and weight.numel() == V
+                and weight.is_contiguous() and weight.device == device):
+            raise ValueError(f"{name}: weight must be None or a contiguous float32 tensor of {V} class weights on the logits' device")
+    e = float(label_smoothing)
+    if not 0.0 <= e <= 1.0:                                                     # (NaN fails both comparisons)
+        raise ValueError(f"{name}: label_smoothing must lie in [0, 1], got {label_smoothing!r}")
+    if ignore_index is not None:
+        if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not -2 ** 63 <= ignore_index < 2 ** 63:
+            raise ValueError(f"{name}: ignore_index must be None or an int, got {ignore_index!r}")
+        ignore_index = C.byref(C.c_int64(ignore_index))
+    return weight, e, ignore_index
+
+
+def class_counts(targets, V, weight=None, ignore_index=None, extra=0):
+    """targets: any shape, int64, contiguous, on the device -> ClassCounts (inet_class_counts): the histogram
+    of the targets over [0, V), how many are valid, how many lie outside [0, V) without being ignore_index (never used as an index;
+    the launch sets the token status word: check_tokens() raises) and denom = sum_c weight_c counts_c in double, in class order.
+    Integer atomics only: the same bits on every call.  extra: int64 words behind the counts that the call zeroes along (`.extra`)."""
+    if not (isinstance(targets, torch.Tensor) and targets.is_cuda and targets.dtype == torch.int64 and targets.is_contiguous()
+            and targets.numel() >= 1):
+        raise ValueError("class_counts: targets must be a non-empty contiguous int64 device tensor")
+    if isinstance(V, bool) or not isinstance(V, int) or V < 1:
+        raise ValueError(f"class_counts: V must be an int >= 1, got {V!r}")
+    weight, _, ign = _ce_common("class_counts", V, weight, 0.0, ignore_index, targets.device)
+    block = torch.empty(CE_META_WORDS + V + int(extra), dtype=torch.int64, device=targets.device)
+    check(_lib.lib().inet_class_counts(ptr(targets), targets.numel(), V, ptr(weight), ign, ptr(block), int(extra), stream_ptr()),
+          "inet_class_counts")
+    return ClassCounts(block, V)
+
+
+def cross_entropy_w(weights2d, targets1d, counted, weight=None, label_smoothing=0.0, ignore_index=None, loss=None, accuracy=None,
+                    dW=None, scale_dev=None, add_term=None, add_scale=0.0, fwd_out=None, fwd_scale=0.0, class_stats=None,
+                    confusion=None):
+    """inet_cross_entropy_w: torch's F.cross_entropy(weights2d, targets1d, weight, label_smoothing=,
+    ignore_index=, reduction='mean') and its gradient, one wavefront per row, the row read once.  counted: the ClassCounts of the SAME
+    targets, weight and ignore_index (the backward passes the forward's).  Outputs, each optional: loss / accuracy (1-element float
+    tensors, written), dW [rows, >= V] (times scale_dev[0] when given; an ignored row is exactly 0), fwd_out = fwd_scale * scale_dev,
+    class_stats (V, 3) int64 += {target count, hits, predicted}, confusion (V, V) int64 += 1 at [target, argmax] (the caller zeroes
+    them).  add_term / add_scale: loss += add_scale * add_term[0].  With denom == 0 the loss is NaN and dW all zeros."""
+    rows, V = weights2d.shape
+    assert weights2d.is_cuda and weights2d.dtype == torch.float32 and weights2d.stride(1) == 1
+    _i64c(targets1d)
+    if targets1d.numel() != rows:
+        raise ValueError(f"cross_entropy_w: {rows} rows of logits but {targets1d.numel()} targets")
+    if not isinstance(counted, ClassCounts) or counted.V != V:
+        raise ValueError("cross_entropy_w: counted must be the ClassCounts of these targets at this V")
+    weight, e, ign = _ce_common("cross_entropy_w", V, weight, label_smoothing, ignore_index, weights2d.device)
+    for name, t, shape in (("class_stats", class_stats, (V, 3)), ("confusion", confusion, (V, V))):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"cross_entropy_w: {name} must be a contiguous int64 device tensor of shape {shape}")
+    if dW is not None:
+        assert dW.is_cuda and dW.dtype == torch.float32 and dW.stride(1) == 1 and dW.shape[0] == rows and dW.shape[1] == V
+    L = _lib.lib()
+    ws = _ws(L.inet_cross_entropy_w_ws_bytes(rows), weights2d.device) if loss is not None or accuracy is not None else None
+    check(L.inet_cross_entropy_w(ptr(weights2d), weights2d.stride(0), rows, V, ptr(targets1d), ptr(weight), e, ign, ptr(counted.block),
+                                 ptr(dW), dW.stride(0) if dW is not None else 0, ptr(scale_dev), ptr(loss), ptr(accuracy),
+                                 ptr(add_term), float(add_scale), ptr(fwd_out), float(fwd_scale), ptr(class_stats), ptr(confusion),
+                                 ptr(ws), ws.numel() * 4 if ws is not None else 0, stream_ptr()), "inet_cross_entropy_w")
+
+
 def sample_multinomial(weights2d, seed, offset=0):
     """One draw per row from softmax(weights2d[row]) (decoder.py:506-509), counter-based generator (seed, offset + row)."""
     rows, V = weights2d.shape

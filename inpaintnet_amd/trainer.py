@@ -120,6 +120,133 @@ class _ElboFn(torch.autograd.Function):
         return dW, None, gkl, None, None
 
 
+def _ce_w_forward(ctx, weights2d, targets1d, ce, sink, **glue):
+    """The forward both weighted functions share: ONE counting launch (it also zeroes the statistics' words) and ONE loss launch.
+    ce = (class weights on the device or None, label_smoothing, ignore_index); sink: a dict that receives the step's device
+    tensors, or None."""
+    rows, V = weights2d.shape
+    counted = ops.class_counts(targets1d, V, ce[0], ce[2], extra=3 * V)
+    out = torch.empty(2, dtype=torch.float32, device=weights2d.device)
+    stats = counted.extra.view(V, 3)
+    ops.cross_entropy_w(weights2d, targets1d, counted, *ce, loss=out[0:1], accuracy=out[1:2], class_stats=stats, **glue)
+    ctx.save_for_backward(weights2d, targets1d)
+    ctx.counted, ctx.ce = counted, ce            # the backward takes denom from the forward's count: it does not recount
+    if sink is not None:
+        sink.update(denom=counted.denom, n_valid=counted.n_valid, class_stats=stats)
+    loss, acc = out[0], out[1]
+    ctx.mark_non_differentiable(acc)
+    ctx.set_materialize_grads(False)             # (no fill launch for the accuracy's gradient)
+    return loss, acc
+
+
+class _CrossEntropyWFn(torch.autograd.Function):
+    """torch's F.cross_entropy(weights2d, targets1d, weight, label_smoothing=, ignore_index=) + the accuracy over the valid rows
+    (DESIGN.md section 28): one counting launch plus one loss launch forward, one loss launch backward (dW already times the
+    upstream gradient, read on the device)."""
+
+    @staticmethod
+    def forward(ctx, weights2d, targets1d, weight, label_smoothing, ignore_index, sink):
+        return _ce_w_forward(ctx, weights2d, targets1d, (weight, label_smoothing, ignore_index), sink)
+
+    @staticmethod
+    def backward(ctx, gloss, _gacc):
+        if gloss is None:
+            return (None,) * 6
+        w, t = ctx.saved_tensors
+        dW = torch.empty_like(w)
+        ops.cross_entropy_w(w, t, ctx.counted, *ctx.ce, dW=dW, scale_dev=gloss.reshape(1).contiguous())
+        return (dW,) + (None,) * 5
+
+
+class _ElboWFn(torch.autograd.Function):
+    """_ElboFn on the weighted kernel: loss = weighted CE + kscale * kl_sum, accuracy; the same launches as _CrossEntropyWFn, the
+    KL term folded into the loss launch and kscale * gradient handed on to the KL sum's producer by the backward launch."""
+
+    @staticmethod
+    def forward(ctx, weights2d, targets1d, kl_sum, kscale, weight, label_smoothing, ignore_index, sink):
+        ctx.kscale = kscale
+        return _ce_w_forward(ctx, weights2d, targets1d, (weight, label_smoothing, ignore_index), sink,
+                             add_term=kl_sum.reshape(1), add_scale=kscale)
+
+    @staticmethod
+    def backward(ctx, gloss, _gacc):
+        if gloss is None:
+            return (None,) * 8
+        w, t = ctx.saved_tensors
+        dW = torch.empty_like(w)
+        gkl = torch.empty((), dtype=torch.float32, device=w.device)
+        ops.cross_entropy_w(w, t, ctx.counted, *ctx.ce, dW=dW, scale_dev=gloss.reshape(1).contiguous(), fwd_out=gkl.reshape(1),
+                            fwd_scale=ctx.kscale)
+        return (dW, None, gkl) + (None,) * 5
+
+
+def _ce_weight_on(weight, V, device):
+    """Class weights as the kernel takes them: None, or V float32 on `device`."""
+    if weight is None:
+        return None
+    w = torch.as_tensor(weight, dtype=torch.float32).to(device).contiguous()
+    if w.dim() != 1 or w.numel() != V:
+        raise ValueError(f"weight must hold one value for each of the {V} classes, got shape {tuple(w.shape)}")
+    return w
+
+
+def class_stats_add(weights, targets, class_stats, confusion):
+    """class_stats (V, 3) and confusion (V, V), int64 on the device, += the plain argmax statistics of one batch of logits (any
+    leading shape) against its targets: the counting launch and one loss launch without a loss."""
+    V = weights.size(-1)
+    w2 = weights.detach().contiguous().view(-1, V)
+    t1 = targets.contiguous().view(-1)
+    if t1.dtype != torch.int64:
+        t1 = t1.long()
+    ops.cross_entropy_w(w2, t1, ops.class_counts(t1, V), class_stats=class_stats, confusion=confusion)
+
+
+def class_report_from_counts(class_stats, confusion, names=None):
+    """The per-class report of the testers from the integers the loss kernel accumulated: class_stats (V, 3) = {target count, hits,
+    predicted}, confusion (V, V) indexed [target, argmax] (tensors or arrays; they are read on the host).  recall = hits / counts,
+    precision = hits / predicted, f1 = 2 hits / (counts + predicted), each NaN where its denominator is 0; accuracy = sum hits /
+    sum counts; balanced_accuracy = the mean recall over the classes present."""
+    import numpy as np
+    stats = np.asarray(class_stats.cpu() if isinstance(class_stats, torch.Tensor) else class_stats, dtype=np.int64)
+    conf = np.asarray(confusion.cpu() if isinstance(confusion, torch.Tensor) else confusion, dtype=np.int64)
+    counts, hits, predicted = stats[:, 0], stats[:, 1], stats[:, 2]
+
+    def ratio(num, den):
+        out = np.full(len(den), np.nan)
+        np.divide(num, den, out=out, where=den > 0)
+        return out
+    recall = ratio(hits.astype(np.float64), counts)
+    total = int(counts.sum())
+    present = counts > 0
+    return {"counts": counts, "predicted": predicted, "hits": hits, "recall": recall,
+            "precision": ratio(hits.astype(np.float64), predicted), "f1": ratio(2.0 * hits, counts + predicted),
+            "accuracy": float(hits.sum()) / total if total else float("nan"),
+            "balanced_accuracy": float(recall[present].mean()) if present.any() else float("nan"),
+            "confusion": conf, "names": names}
+
+
+def index_to_note_names(dataset, V):
+    """The dataset's index-to-note table as a list of V strings, or None where it has none."""
+    dicts = getattr(dataset, "index2note_dicts", None)
+    if not dicts:
+        return None
+    table = dicts[getattr(dataset, "NOTES", 0)] if len(dicts) > 1 else dicts[0]
+    try:
+        return [str(table[i]) for i in range(V)]
+    except (KeyError, IndexError, TypeError):
+        return None
+
+
+def _ce_w_apply(weights, targets, weight, label_smoothing, ignore_index, sink):
+    """_CrossEntropyWFn on logits of any leading shape; sink: a dict for the step's device tensors, or None."""
+    V = weights.size(-1)
+    w2 = weights.contiguous().view(-1, V)
+    t1 = targets.contiguous().view(-1)
+    if t1.dtype != torch.int64:
+        t1 = t1.long()
+    return _CrossEntropyWFn.apply(w2, t1, _ce_weight_on(weight, V, w2.device), float(label_smoothing), ignore_index, sink)
+
+
 class _KLFn(torch.autograd.Function):
     """beta * mean_b sum_d KL(N(mu, sigma) || N(0,1))   (vae_trainer.py:128-139)."""
 
@@ -143,8 +270,10 @@ class Trainer(ABC):
 
     feed_fields = (0, 1)       # which members of a (score, metadata) batch the trainer needs on the device
 
+    CE_SETTINGS = ("ce_weight", "label_smoothing", "ignore_index")
+
     def __init__(self, dataset, model, lr=1e-4, early_stopping=False, max_grad_norm=None, weight_decay=0.0, decay_all=False,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, ce_weight=None, label_smoothing=0.0, ignore_index=None):
         """max_grad_norm (None or 0 < value <= inf): clip the gradient arena by its global norm in front of every optimizer step, as
         torch.nn.utils.clip_grad_norm_(..., error_if_nonfinite=False) around optimizer.step() would, and DROP a step whose gradient
         holds an inf or a NaN instead of folding it into the weights -- both on the device (ops.grad_sqnorm in
@@ -159,7 +288,22 @@ class Trainer(ABC):
         launch: ema = ema_decay * ema + (1 - ema_decay) * p behind every applied step; a skipped or dropped step leaves it alone.
         ema_warmup: step t (t = adam_t of that launch) uses min(ema_decay, (1 + t) / (10 + t)), evaluated on the host per launch
         like lr.  ema_state_dict() and `with trainer.ema_weights():` read it; train_model validates under it.
-        With weight_decay == 0 and ema_decay None the trainer launches what it launched before, under the same labels."""
+        With weight_decay == 0 and ema_decay None the trainer launches what it launched before, under the same labels.
+
+        ce_weight, label_smoothing, ignore_index: the reconstruction loss becomes torch's CrossEntropyLoss(weight=ce_weight,
+        label_smoothing=label_smoothing, ignore_index=ignore_index).  ce_weight: None or one finite value
+        >= 0 for each of the V tokens (a sequence or a tensor; 0 is legal: that class contributes nothing as a target and is still
+        counted in the statistics); label_smoothing: finite, in [0, 1]; ignore_index: None (nothing is ignored) or an int outside
+        [0, V).  The mean is over the weights of the valid targets the process sees: under data parallelism the denominator is the
+        rank's own shard, with no collective -- the convention of free_nats_per='dim'.  The settings are part of the objective, so
+        validation (train=False) uses them too; the accuracy stays the plain token accuracy over the valid rows.  After a step on
+        this path `last_ce` holds the device tensors {'denom' () float64, 'n_valid' () int64, 'class_stats' (V, 3)
+        int64: per class its count as a target, of those the hits, its count as the argmax} -- reading them is the caller's
+        synchronisation.  With the defaults the trainer launches what it launched before and last_ce stays None."""
+        self.ce_weight, self.label_smoothing, self.ignore_index = self._ce_settings(ce_weight, label_smoothing, ignore_index,
+                                                                                    self._num_classes(dataset))
+        self._ce_weight_dev = None                   # ce_weight on the logits' device, made at the first step that needs it
+        self.last_ce = None
         weight_decay = float(weight_decay)
         if not (weight_decay >= 0.0 and math.isfinite(weight_decay)):          # (NaN fails the comparison)
             raise ValueError(f"weight_decay must be finite and >= 0, got {weight_decay}")
@@ -229,6 +373,101 @@ class Trainer(ABC):
             self._report_slot(0)
             for e in self._report_events:
                 e.record()
+
+    # ---- the weighted reconstruction loss --------------------
+    @staticmethod
+    def _num_classes(dataset):
+        """V as the trainers' keyword checks see it: the size of every voice's vocabulary where they agree, else None."""
+        dicts = getattr(dataset, "note2index_dicts", None)
+        sizes = {len(d) for d in dicts} if dicts else set()
+        return sizes.pop() if len(sizes) == 1 else None
+
+    @staticmethod
+    def _ce_settings(ce_weight, label_smoothing, ignore_index, V):
+        """The three settings checked and in their stored form (ce_weight: a float32 host tensor or None)."""
+        if ce_weight is not None:
+            try:
+                w = torch.as_tensor(ce_weight, dtype=torch.float32).detach().cpu().contiguous().clone()
+            except (TypeError, ValueError, RuntimeError):
+                raise ValueError(f"ce_weight must be None or a sequence of class weights, got {type(ce_weight).__name__}")
+            if w.dim() != 1 or w.numel() == 0 or (V is not None and w.numel() != V):
+                raise ValueError(f"ce_weight must hold one weight for each of the {V} tokens, got shape {tuple(w.shape)}")
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise ValueError("ce_weight must be finite and >= 0")
+            ce_weight = w
+        if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)) or \
+                not 0.0 <= label_smoothing <= 1.0:                              # (NaN fails both comparisons)
+            raise ValueError(f"label_smoothing must be finite and in [0, 1], got {label_smoothing!r}")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or not isinstance(ignore_index, int) or not -2 ** 63 <= ignore_index < 2 ** 63 or \
+                    (V is not None and 0 <= ignore_index < V):
+                raise ValueError(f"ignore_index must be None or an int outside [0, {V}), got {ignore_index!r}")
+        return ce_weight, float(label_smoothing), ignore_index
+
+    def _ce_plain(self):
+        return self.ce_weight is None and self.label_smoothing == 0.0 and self.ignore_index is None
+
+    def _ce_args(self, device):
+        """(class weights on `device` or None, label_smoothing, ignore_index): what the weighted functions take."""
+        if self.ce_weight is not None and (self._ce_weight_dev is None or self._ce_weight_dev.device != device):
+            self._ce_weight_dev = self.ce_weight.to(device)
+        return (self._ce_weight_dev if self.ce_weight is not None else None), self.label_smoothing, self.ignore_index
+
+    def _ce_loss(self, weights, targets):
+        """mean_crossentropy_loss_and_accuracy under the trainer's settings; leaves last_ce."""
+        if self._ce_plain():
+            self.last_ce = None
+            return self.mean_crossentropy_loss_and_accuracy(weights, targets)
+        if type(self).mean_crossentropy_loss_and_accuracy is not Trainer.mean_crossentropy_loss_and_accuracy:
+            self.last_ce = None                      # an override: it is handed the settings and keeps its own counsel
+            w, e, i = self._ce_args(weights.device)
+            return self.mean_crossentropy_loss_and_accuracy(weights, targets, weight=w, label_smoothing=e, ignore_index=i)
+        self.last_ce = {}
+        return _ce_w_apply(weights, targets, *self._ce_args(weights.device), self.last_ce)
+
+    def class_counts(self, data_loader):
+        """The int64 histogram (V,) of a loader's target tokens -- every token of every score a batch holds -- counted on the
+        device (ops.class_counts), returned on the host: what class_weights() takes."""
+        V = self._num_classes(self.dataset)
+        if V is None:
+            raise ValueError("class_counts: the dataset's voices do not share one vocabulary")
+        total = None
+        for batch in data_loader:
+            score = batch[0] if isinstance(batch, (tuple, list)) else batch
+            t = score.to(self.model.flat.device).reshape(-1)
+            c = ops.class_counts((t if t.dtype == torch.int64 else t.long()).contiguous(), V).counts
+            total = c.clone() if total is None else total + c
+        if total is None:
+            raise ValueError("class_counts: the loader is empty")
+        ops.check_tokens("Trainer.class_counts")
+        return total.cpu()
+
+    @staticmethod
+    def class_weights(counts, scheme='inverse', beta=0.999, normalize=True):
+        """Class weights from a histogram, on the host, in float64 -> a float32 tensor (V,).  scheme 'inverse': 1 / n_c;
+        'inverse_sqrt': 1 / sqrt(n_c); 'effective': (1 - beta) / (1 - beta^n_c), the effective number of samples of Cui et al. 2019
+        (0 <= beta < 1).  A class with count 0 gets the weight of the rarest present class.  normalize: scaled so that sum_c w_c n_c
+        = sum_c n_c -- the weighted loss then stays on the plain loss's scale on the counted data."""
+        n = torch.as_tensor(counts).detach().cpu().to(torch.float64).reshape(-1)
+        if n.numel() == 0 or bool((n < 0).any()) or not bool(torch.isfinite(n).all()) or not bool((n > 0).any()):
+            raise ValueError("class_weights: counts must be non-negative with at least one class present")
+        present = n > 0
+        safe = torch.where(present, n, torch.ones_like(n))
+        if scheme == 'inverse':
+            w = 1.0 / safe
+        elif scheme == 'inverse_sqrt':
+            w = 1.0 / safe.sqrt()
+        elif scheme == 'effective':
+            beta = float(beta)
+            if not 0.0 <= beta < 1.0:
+                raise ValueError(f"class_weights: beta must lie in [0, 1), got {beta}")
+            w = (1.0 - beta) / (1.0 - torch.pow(torch.full_like(safe, beta), safe))
+        else:
+            raise ValueError(f"class_weights: scheme must be 'inverse', 'inverse_sqrt' or 'effective', got {scheme!r}")
+        w = torch.where(present, w, w[present].max())                           # (the rarest present class has the largest weight)
+        if normalize:
+            w = w * (n.sum() / (w * n).sum())
+        return w.to(torch.float32)
 
     # ---- utils/trainer.py:41-124 (plot/log plumbing omitted) -----------------------
     def train_model(self, batch_size, num_epochs, plot=False, log=False, seed=0):
@@ -624,7 +863,9 @@ class Trainer(ABC):
                 "betas": self.betas, "eps": self.eps, "next_epoch": int(next_epoch),
                 "num_parameters": int(self.model.flat.numel()),
                 "weight_decay": self.weight_decay, "decay_all": self.decay_all, "ema_decay": self.ema_decay,
-                "ema_warmup": self.ema_warmup, "ema": None if self.ema is None else self.ema.cpu()}
+                "ema_warmup": self.ema_warmup, "ema": None if self.ema is None else self.ema.cpu(),
+                "ce_weight": None if self.ce_weight is None else self.ce_weight.clone(), "label_smoothing": self.label_smoothing,
+                "ignore_index": self.ignore_index}
 
     def save_training_state(self, path, next_epoch=0):
         torch.save(self.training_state(next_epoch), path)
@@ -658,6 +899,10 @@ class Trainer(ABC):
             # a state written before weight decay and EMA existed: the settings stay this trainer's, the EMA starts at the weights
             self.ema.copy_(self.model.flat)
             print("[inpaintnet_amd] training state without an EMA: the EMA arena was seeded from the model's weights as loaded")
+        if "label_smoothing" in st:                  # (a state written before the three settings existed leaves the trainer's own)
+            self.ce_weight, self.label_smoothing, self.ignore_index = self._ce_settings(
+                st["ce_weight"], st["label_smoothing"], st["ignore_index"], self._num_classes(self.dataset))
+            self._ce_weight_dev = None
         return self.start_epoch
 
     @abstractmethod
@@ -681,13 +926,18 @@ class Trainer(ABC):
 
     # ---- static losses, utils/trainer.py:271-376 -------------------------------------
     @staticmethod
-    def mean_crossentropy_loss_and_accuracy(weights, targets):
-        V = weights.size(-1)
-        w2 = weights.contiguous().view(-1, V)
-        t1 = targets.contiguous().view(-1)
-        if t1.dtype != torch.int64:
-            t1 = t1.long()
-        return _CrossEntropyFn.apply(w2, t1)
+    def mean_crossentropy_loss_and_accuracy(weights, targets, weight=None, label_smoothing=0.0, ignore_index=None):
+        """With two arguments the plain mean cross-entropy and token accuracy (utils/trainer.py:271-306).  weight (V class weights),
+        label_smoothing (in [0, 1]) and ignore_index (None: nothing is ignored) are torch.nn.CrossEntropyLoss's; any non-default
+        one takes the weighted kernel, whose accuracy is over the valid rows."""
+        if weight is None and label_smoothing == 0.0 and ignore_index is None:
+            V = weights.size(-1)
+            w2 = weights.contiguous().view(-1, V)
+            t1 = targets.contiguous().view(-1)
+            if t1.dtype != torch.int64:
+                t1 = t1.long()
+            return _CrossEntropyFn.apply(w2, t1)
+        return _ce_w_apply(weights, targets, weight, label_smoothing, ignore_index, None)
 
     @staticmethod
     def mean_crossentropy_loss(weights, targets):

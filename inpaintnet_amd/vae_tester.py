@@ -11,7 +11,7 @@ import torch
 from . import ops
 from .attributes import ATTRIBUTES, AttributeSpec
 from .helpers import to_cuda_variable_long
-from .trainer import Trainer
+from .trainer import Trainer, class_report_from_counts, class_stats_add, index_to_note_names
 
 
 class VAETester(object):
@@ -206,6 +206,26 @@ class VAETester(object):
         tokens = samples.reshape(len(values) * B, T).long().contiguous()
         attrs = ops.measure_attributes(tokens, spec)
         return attrs.view(len(values), B, len(ATTRIBUTES)), tokens.view(len(values), B, T)
+
+    def class_report(self, data_loader):
+        """How well the model reconstructs each token, as opposed to the hold that fills most ticks: the eval-mode forward of
+        loss_and_acc_test over a loader, its per-class statistics and confusion matrix accumulated on the device (DESIGN.md
+        section 28), read once at the end.  -> dict: counts, predicted, hits (V,) int64; recall, precision, f1 (V,) float64, NaN
+        where undefined; accuracy; balanced_accuracy, the mean recall over the classes present; confusion (V, V) int64 indexed
+        [target, argmax]; names, the dataset's index-to-note table or None."""
+        V = self.model.num_notes
+        dev = self.model.flat.device
+        stats = torch.zeros(V, 3, dtype=torch.int64, device=dev)
+        conf = torch.zeros(V, V, dtype=torch.int64, device=dev)
+        n_bars = getattr(self.dataset, "n_bars", None)
+        for score_tensor, _ in data_loader:
+            if n_bars is not None and score_tensor.dim() == 3:
+                score_tensor = score_tensor.reshape(score_tensor.size(0) * n_bars, -1)
+            score = to_cuda_variable_long(score_tensor)
+            with torch.no_grad():
+                class_stats_add(self.model(measure_score_tensor=score, train=False)[0], score, stats, conf)
+            ops.check_chains("VAETester.class_report")
+        return class_report_from_counts(stats, conf, index_to_note_names(self.dataset, V))
 
     def loss_and_acc_test(self, data_loader):
         """vae_tester.py:113-160: mean reconstruction CE / accuracy over a loader (eval mode, no teacher forcing)."""

@@ -8,7 +8,7 @@ from . import ops
 from .helpers import to_cuda_variable_long
 from .attributes import ATTRIBUTES, AttributeSpec
 from .measure_vae import _AttrRegFn, _MmdFn, _attr_columns
-from .trainer import Trainer, _ElboFn, _KLFn
+from .trainer import Trainer, _ElboFn, _ElboWFn, _KLFn
 
 
 class VAETrainer(Trainer):
@@ -21,9 +21,12 @@ class VAETrainer(Trainer):
     def __init__(self, dataset, model, lr=1e-4, max_grad_norm=None, weight_decay=0.0, decay_all=False, ema_decay=None,
                  ema_warmup=False, kl_beta=0.001, kl_warmup_steps=0, kl_cycle_steps=0, kl_ramp=0.5, free_nats=0.0,
                  free_nats_per='measure', mmd_coeff=0.0, mmd_kernel='gaussian', mmd_bandwidth=None, mmd_estimator='unbiased',
-                 attr_reg=None, attr_gamma=10.0, attr_delta=10.0, attr_spec=None):
+                 ce_weight=None, label_smoothing=0.0, ignore_index=None, attr_reg=None, attr_gamma=10.0, attr_delta=10.0,
+                 attr_spec=None):
         """The loss of a training step is CE + beta_t / B * kl_sum [+ mmd_coeff * MMD(z_tilde, z_prior)]
-        [+ attr_gamma * sum_a L_a(z_tilde, attributes of the step's tokens)].
+        [+ attr_gamma * sum_a L_a(z_tilde, attributes of the step's tokens)].  ce_weight, label_smoothing, ignore_index: Trainer's
+        (CE becomes the class-weighted, label-smoothed cross-entropy of DESIGN.md section 28, still one launch each way next to
+        the counting launch).
 
         kl_beta (finite, >= 0): the KL weight; the reference's 0.001.  kl_warmup_steps (an int >= 0): beta rises linearly from 0 to
         kl_beta over that many optimizer steps, then holds.  kl_cycle_steps = M > 0: cyclical annealing (Fu et al. 2019) -- within
@@ -91,7 +94,8 @@ class VAETrainer(Trainer):
             raise ValueError(f"mmd_estimator must be one of {ops.MMD_ESTIMATORS}, got {mmd_estimator!r}")
         attr_reg, attr_gamma, attr_delta, attr_spec = self._attr_settings(attr_reg, attr_gamma, attr_delta, attr_spec)
         super().__init__(dataset, model, lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay, decay_all=decay_all,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, ce_weight=ce_weight, label_smoothing=label_smoothing,
+                         ignore_index=ignore_index)
         self.kl_beta, self.kl_warmup_steps, self.kl_cycle_steps, self.kl_ramp = kl_beta, kl_warmup_steps, kl_cycle_steps, kl_ramp
         self.free_nats, self.free_nats_per = free_nats, free_nats_per
         self.last_kl = None
@@ -154,10 +158,16 @@ class VAETrainer(Trainer):
             t1 = score.contiguous().view(-1)
             if t1.dtype != torch.int64:
                 t1 = t1.long()
-            loss, accuracy = _ElboFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, beta / z_dist.loc.shape[0],
-                                           self.model.take_stats(2))
+            if self._ce_plain():
+                self.last_ce = None
+                loss, accuracy = _ElboFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, beta / z_dist.loc.shape[0],
+                                               self.model.take_stats(2))
+            else:
+                self.last_ce = {}
+                loss, accuracy = _ElboWFn.apply(weights.contiguous().view(-1, V), t1, kl_sum, beta / z_dist.loc.shape[0],
+                                                *self._ce_args(weights.device), self.last_ce)
             return self._add_attr_reg(self._add_mmd(loss, z_tilde, z_prior, train), z_tilde, score, train), accuracy
-        recons_loss, accuracy = self.mean_crossentropy_loss_and_accuracy(weights, score)
+        recons_loss, accuracy = self._ce_loss(weights, score)
         # (an override written against the reference's two-argument call keeps working while beta is the reference's)
         dist_loss = self.compute_kld_loss(z_dist, prior_dist, **({} if beta == 0.001 else {"beta": beta}))
         loss = recons_loss + dist_loss
@@ -216,7 +226,8 @@ class VAETrainer(Trainer):
         return st
 
     def load_training_state(self, path_or_state):
-        """... and the six KL, four MMD and four attribute settings; a state written before they existed leaves this trainer's own."""
+        """... and the six KL, four MMD and four attribute settings (the three of the reconstruction loss are the base class's); a
+        state written before they existed leaves this trainer's own."""
         st = torch.load(path_or_state, map_location="cpu") if isinstance(path_or_state, (str, bytes, os.PathLike)) \
             else path_or_state
         out = super().load_training_state(st)
