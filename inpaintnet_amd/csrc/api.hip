@@ -16,6 +16,9 @@
 #include "iw.h"
 #include "attr.h"
 #include "ce.h"
+#include "latent.h"
+#include "optim.h"
+#include "sample_rows.h"
 
 namespace {
 

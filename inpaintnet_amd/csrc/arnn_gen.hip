@@ -52,6 +52,7 @@
 #include "prof.h"
 #include "arnn_gen.h"
 #include "pointwise.h"
+#include "reduce.h"
 #include "sample.h"
 
 namespace {
@@ -671,12 +672,6 @@ void arnn_gen_set_mode(int m) { g_mode = (m < 0 || m > 4) ? 3 : m; }
 // stays on the device).  (The free-running pass needs batch element 0 alone, see the head of this file; with its tokens the caller
 // runs the whole batch through the batched, teacher-forced-shaped kernels: 195 -> 14 ms per training step.)
 namespace {
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // dot products of ONE row against weight rows, lanes striding over k: every load of a wave is issued before the first multiply (NI =
 // ceil(K / 64) is a template bound: a runtime k loop waits for each 64-wide slice in turn -- 7 us per launch instead of 2)
 template <int NI>

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "attr.h"
 #include "prof.h"
+#include "reduce.h"
 
 namespace {
 
@@ -25,22 +26,6 @@ constexpr int kAttrTile = 256;                   // columns of a tile: one per t
 constexpr int kAttrFinishBlock = 256;
 
 struct AttrShare { float s; int conc, disc, tied; };
-
-__device__ __forceinline__ float attr_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int attr_wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long attr_wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(256)
 attr_measure_kernel(const long long* __restrict__ tokens, long B, int T, int V, int slur, int rest, int none,
@@ -139,13 +124,13 @@ attr_pair_kernel(const float* __restrict__ z, const float* __restrict__ attrs, l
              (((v[8] + v[9]) + (v[10] + v[11])) + ((v[12] + v[13]) + (v[14] + v[15])));
     }
     // the workgroup's share: the xor tree over a wave's lanes, the four waves in order
-    S = attr_wave_sum(S);
-    conc = attr_wave_sum(conc);
-    disc = attr_wave_sum(disc);
-    tied = attr_wave_sum(tied);
+    S = wave_sum(S);
+    conc = wave_sum(conc);
+    disc = wave_sum(disc);
+    tied = wave_sum(tied);
     if (GRAD) {
 #pragma unroll
-        for (int r = 0; r < kAttrRows; ++r) g[r] = attr_wave_sum(g[r]);
+        for (int r = 0; r < kAttrRows; ++r) g[r] = wave_sum(g[r]);
     }
     if ((t & 63) == 0) {
         red[t >> 6] = S;
@@ -158,13 +143,13 @@ attr_pair_kernel(const float* __restrict__ z, const float* __restrict__ attrs, l
     __syncthreads();
     if (t == 0) {
         AttrShare sh;
-        sh.s = ((red[0] + red[1]) + red[2]) + red[3];
-        sh.conc = cred[0][0] + cred[0][1] + cred[0][2] + cred[0][3];
-        sh.disc = cred[1][0] + cred[1][1] + cred[1][2] + cred[1][3];
-        sh.tied = cred[2][0] + cred[2][1] + cred[2][2] + cred[2][3];
+        sh.s = sum4(red);
+        sh.conc = sum4(cred[0]);
+        sh.disc = sum4(cred[1]);
+        sh.tied = sum4(cred[2]);
         ws[(long)a * nb + blockIdx.x] = sh;
     }
-    if (GRAD && t < nrows) grad[(i0 + t) * A + a] = gcoef * (((gred[t][0] + gred[t][1]) + gred[t][2]) + gred[t][3]);
+    if (GRAD && t < nrows) grad[(i0 + t) * A + a] = gcoef * sum4(gred[t]);
 }
 
 // ONE workgroup, attribute after attribute: thread t adds the shares of row blocks t, t + 256, ... in ascending order, the xor tree
@@ -184,18 +169,18 @@ attr_finish_kernel(const AttrShare* __restrict__ ws, int nb, int A, double inv_b
             s += sh.s;
             c += sh.conc; d += sh.disc; e += sh.tied;
         }
-        s = attr_wave_sum(s);
-        c = attr_wave_sum(c);
-        d = attr_wave_sum(d);
-        e = attr_wave_sum(e);
+        s = wave_sum(s);
+        c = wave_sum(c);
+        d = wave_sum(d);
+        e = wave_sum(e);
         __syncthreads();                         // the previous attribute's totals have been read
         if ((t & 63) == 0) { tot[t >> 6] = s; ctot[0][t >> 6] = c; ctot[1][t >> 6] = d; ctot[2][t >> 6] = e; }
         __syncthreads();
         if (t == 0) {
-            const float Sa = ((tot[0] + tot[1]) + tot[2]) + tot[3];
+            const float Sa = sum4(tot);
             total += (double)Sa;
             out[1 + a] = (float)((double)Sa * inv_b2);
-            for (int k = 0; k < 3; ++k) counts[3 * a + k] = ctot[k][0] + ctot[k][1] + ctot[k][2] + ctot[k][3];
+            for (int k = 0; k < 3; ++k) counts[3 * a + k] = sum4(ctot[k]);
         }
     }
     if (t == 0) out[0] = (float)(coeff * (total * inv_b2));

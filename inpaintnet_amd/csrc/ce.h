@@ -9,6 +9,13 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+// The plain cross-entropy (ce_kernel): loss_sum += out_scale * sum (lse - w[target]), correct += out_scale * hits, both through one
+// float atomic pair per workgroup; dW = (softmax - onehot) * scale.  ce_w below is defined against its bits.
+int pw_cross_entropy(const float* W, long ld_w, int rows, int V, const long long* tgt, float* dW, long ld_dw,
+                     float scale, float out_scale, float* loss_sum, float* correct, hipStream_t s,
+                     const float* scale_dev = nullptr, const float* add_term = nullptr, float add_scale = 0.f,
+                     float* fwd_out = nullptr, float fwd_scale = 0.f);
+
 // The block ce_count_launch leaves behind and ce_w_launch reads: kCeMetaWords int64 words, then counts[V].
 constexpr int kCeMetaWords = 8;
 constexpr int kCeMetaDenom = 0;                  // double: sum_c w_c counts_c, added in class order

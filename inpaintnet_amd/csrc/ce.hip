@@ -1,4 +1,6 @@
-// Class-weighted, label-smoothed cross-entropy with an ignore index (the definition is in ce.h).
+// The cross-entropy kernels.  ce_kernel: the plain one of the training step -- one wavefront per row, the loss and hit sums through one
+// float atomic pair per workgroup.  Behind it the class-weighted, label-smoothed cross-entropy with an ignore index (DESIGN.md
+// section 28; the definition is in ce.h), whose bits are pinned to ce_kernel's.  The wave and workgroup sums are reduce.h's.
 // ce_count: a flat int64 target array -> counts[V], n_valid, n_bad in integer atomics (a workgroup's histogram in LDS while V fits,
 //   one global add per class it met), then the workgroup whose ticket came last forms denom = sum_c w_c counts_c and W = sum_c w_c in
 //   double, one thread, in class order: pure functions of the counts.  A target outside [0, V) that is not ignore_index never indexes
@@ -16,38 +18,68 @@
 #include "ce.h"
 #include "chain.h"
 #include "prof.h"
+#include "pw_launch.h"
+#include "reduce.h"
 
 namespace {
 
 typedef unsigned long long ull;
-constexpr int kAmEq = 0x40000000, kAmNone = 0x7fffffff;      // pointwise.hip's argmax_first key: a NaN at v -> v, the maximum -> kAmEq + v
 
-__device__ __forceinline__ float ce_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+// One wavefront per row of V logits.  loss_sum += out_scale * (lse - w[target]);
+// correct += out_scale * (argmax_first(w) == target); dW = (softmax - onehot) * scale.
+__global__ void ce_kernel(const float* __restrict__ W, long ld_w, int rows, int V,
+                          const long long* __restrict__ tgt, float* __restrict__ dW, long ld_dw, float scale,
+                          float out_scale, float* __restrict__ loss_sum, float* __restrict__ correct,
+                          const float* __restrict__ scale_dev, const float* __restrict__ add_term, float add_scale,
+                          float* __restrict__ fwd_out, float fwd_scale) {
+    // scale_dev: dW is also multiplied by this device scalar (the upstream gradient of the mean loss, read on the device:
+    // no elementwise pass over dW afterwards); add_term: *loss_sum also receives add_scale * add_term[0], once (the KL
+    // term of the ELBO: loss = CE + beta/B * KL leaves this kernel complete)
+    // fwd_out: receives fwd_scale * scale_dev[0] (the gradient handed on to the producer of add_term, e.g. the KL sum)
+    if (scale_dev) {
+        if (fwd_out && blockIdx.x == 0 && threadIdx.x == 0) *fwd_out = fwd_scale * *scale_dev;
+        scale *= *scale_dev;
+    }
+    if (add_term && loss_sum && blockIdx.x == 0 && threadIdx.x == 0) unsafeAtomicAdd(loss_sum, add_scale * *add_term);
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    float lsum = 0.f, csum = 0.f;
+    for (int row = wave; row < rows; row += nwaves) {
+        const float* w = W + (long)row * ld_w;
+        float m = -INFINITY;
+        for (int v = lane; v < V; v += 64) m = fmaxf(m, w[v]);
+        m = wave_max(m);
+        float se = 0.f;
+        int am = kAmNone;
+        for (int v = lane; v < V; v += 64) {
+            const float x = w[v];
+            se += expf(x - m);
+            am = min(am, am_key(x, m, v));
+        }
+        se = wave_sum(se);
+        am = am_index(wave_min(am));
+        const int tg = (int)tgt[row];
+        const float lse = m + logf(se);
+        if (lane == 0) {
+            lsum += lse - w[tg];
+            csum += (am == tg) ? 1.f : 0.f;
+        }
+        if (dW) {
+            float* d = dW + (long)row * ld_dw;
+            const float inv = 1.f / se;
+            for (int v = lane; v < V; v += 64) d[v] = (expf(w[v] - m) * inv - (v == tg ? 1.f : 0.f)) * scale;
+        }
+    }
+    // lane 0 of every wave holds that wave's partials: combine the 4 waves of the block, one atomic pair per block
+    __shared__ float part[2][4];
+    if (lane == 0) { part[0][threadIdx.x >> 6] = lsum; part[1][threadIdx.x >> 6] = csum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (loss_sum) unsafeAtomicAdd(loss_sum, sum4(part[0]) * out_scale);
+        if (correct) unsafeAtomicAdd(correct, sum4(part[1]) * out_scale);
+    }
 }
-__device__ __forceinline__ double ce_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ long long ce_wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float ce_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int ce_wave_min(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int ce_am_key(float x, float m, int v) { return x != x ? v : (x == m ? kAmEq + v : kAmNone); }
 
 // Words another workgroup reads in the same launch: written through and read past this CU's L1 (agent scope).
 __device__ __forceinline__ void ce_put(ull* p, ull v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -90,8 +122,8 @@ ce_count_kernel(const long long* __restrict__ tgt, long n, int V, const float* _
         if (lds) atomicAdd(&s_cnt[(int)k], 1);
         else atomicAdd(counts + k, 1ull);
     }
-    nvalid = ce_wave_sum(nvalid);
-    nbad = ce_wave_sum(nbad);
+    nvalid = wave_sum(nvalid);
+    nbad = wave_sum(nbad);
     if ((t & 63) == 0) { s_part[0][t >> 6] = nvalid; s_part[1][t >> 6] = nbad; }
     __syncthreads();
     if (lds) {
@@ -101,8 +133,8 @@ ce_count_kernel(const long long* __restrict__ tgt, long n, int V, const float* _
         }
     }
     if (t == 0) {
-        const long long a = s_part[0][0] + s_part[0][1] + s_part[0][2] + s_part[0][3];
-        const long long b = s_part[1][0] + s_part[1][1] + s_part[1][2] + s_part[1][3];
+        const long long a = sum4(s_part[0]);
+        const long long b = sum4(s_part[1]);
         if (a) atomicAdd(meta + kCeMetaValid, (ull)a);
         if (b) atomicAdd(meta + kCeMetaBad, (ull)b);
     }
@@ -206,18 +238,18 @@ __global__ void __launch_bounds__(256) ce_w_kernel(CeWArgs a) {
         }
         float m = -INFINITY;
         ce_each<NV>(x, w, V, lane, [&](int, float xv, int) { m = fmaxf(m, xv); });
-        m = ce_wave_max(m);
+        m = wave_max(m);
         float se = 0.f, xt = 0.f;
         int am = kAmNone;
         ce_each<NV>(x, w, V, lane, [&](int v, float xv, int k) {
             const float e = expf(xv - m);
             if constexpr (NV > 0) ex[k] = e;
             se += e;
-            am = min(am, ce_am_key(xv, m, v));
+            am = min(am, am_key(xv, m, v));
             xt = v == tg ? xv : xt;
         });
-        se = ce_wave_sum(se);
-        am = ce_wave_min(am) & (kAmEq - 1);
+        se = wave_sum(se);
+        am = am_index(wave_min(am));
         xt = __shfl(xt, tg & 63, 64);
         const float lse = m + logf(se);
         const float wt = cwv(tg);
@@ -226,7 +258,7 @@ __global__ void __launch_bounds__(256) ce_w_kernel(CeWArgs a) {
             if (smoothing) {
                 float sm = 0.f;
                 ce_each<NV>(x, w, V, lane, [&](int v, float xv, int) { sm += cwv(v) * (lse - xv); });
-                accB += (double)ce_wave_sum(sm);
+                accB += (double)wave_sum(sm);
             }
             hits += am == tg;
             if (lane == 0) {
@@ -281,9 +313,9 @@ __global__ void __launch_bounds__(256) ce_w_kernel(CeWArgs a) {
     ull* ticket = reinterpret_cast<ull*>(a.meta) + kCeMetaLossTicket;
     if (t == 0) {
         CePartial* mine = part + blockIdx.x;
-        ce_put(&mine->a, (ull)__double_as_longlong(((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3]));
-        ce_put(&mine->b, (ull)__double_as_longlong(((s_red[1][0] + s_red[1][1]) + s_red[1][2]) + s_red[1][3]));
-        ce_put(&mine->hits, (ull)(s_hits[0] + s_hits[1] + s_hits[2] + s_hits[3]));
+        ce_put(&mine->a, (ull)__double_as_longlong(sum4(s_red[0])));
+        ce_put(&mine->b, (ull)__double_as_longlong(sum4(s_red[1])));
+        ce_put(&mine->hits, (ull)sum4(s_hits));
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         s_last = ce_last_ticket(ticket, gridDim.x) ? 1 : 0;
     }
@@ -297,16 +329,16 @@ __global__ void __launch_bounds__(256) ce_w_kernel(CeWArgs a) {
         B = __longlong_as_double((long long)ce_get(&part[t].b));
         H = (long long)ce_get(&part[t].hits);
     }
-    A = ce_wave_sum(A);
-    B = ce_wave_sum(B);
-    H = ce_wave_sum(H);
+    A = wave_sum(A);
+    B = wave_sum(B);
+    H = wave_sum(H);
     __syncthreads();                             // (s_red and s_hits have been read by thread 0)
     if ((t & 63) == 0) { s_red[0][t >> 6] = A; s_red[1][t >> 6] = B; s_hits[t >> 6] = H; }
     __syncthreads();
     if (t == 0) {
-        A = ((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3];
-        B = ((s_red[1][0] + s_red[1][1]) + s_red[1][2]) + s_red[1][3];
-        H = s_hits[0] + s_hits[1] + s_hits[2] + s_hits[3];
+        A = sum4(s_red[0]);
+        B = sum4(s_red[1]);
+        H = sum4(s_hits);
         if (a.loss) {
             double l = denom == 0.0 ? (double)NAN : ((1.0 - a.smooth) * A + (a.smooth / (double)V) * B) / denom;
             if (a.add_term) l += (double)a.add_scale * (double)*a.add_term;
@@ -326,6 +358,19 @@ void ce_w_dispatch(const CeWArgs& a, int grid, bool full, hipStream_t s) {
 }
 
 }  // namespace
+
+int pw_cross_entropy(const float* W, long ld_w, int rows, int V, const long long* tgt, float* dW, long ld_dw,
+                     float scale, float out_scale, float* loss_sum, float* correct, hipStream_t s, const float* scale_dev,
+                     const float* add_term, float add_scale, float* fwd_out, float fwd_scale) {
+    // blocks: every block ends with one atomic pair on the same two words, and those serialise (~20 ns each): 2048 blocks (one row
+    // per wave) measured 77 us for the loss glue of the B = 256 step, 512 blocks 54 us with the forward launch at 18.7 us against
+    // 6.2 for the backward launch that has no sums (profiles/r06_p_timeline_full_step.txt).  With sums: 128 blocks (12 rows per
+    // wave at 6144 rows); without (the backward launch): as many as there are rows to go round
+    const int g = grid_for((long)rows * 64, 256, (loss_sum || correct) ? 128 : 512);
+    hipLaunchKernelGGL(ce_kernel, dim3(g), dim3(256), 0, s, W, ld_w, rows, V, tgt, dW, ld_dw, scale, out_scale, loss_sum,
+                       correct, scale_dev, add_term, add_scale, fwd_out, fwd_scale);
+    return ok();
+}
 
 int ce_count_launch(const long long* tgt, long n, int V, const float* cw, int has_ignore, long long ignore, long long* out, long extra,
                     hipStream_t s) {

@@ -37,17 +37,6 @@ __device__ __forceinline__ void kernarg_touch1(T v) { asm volatile("" ::"s"(v));
 template <class... T>
 __device__ __forceinline__ void kernarg_touch(T... v) { (kernarg_touch1(v), ...); }
 
-// maximum over the 64 lanes of the wave without LDS (exact, wave-uniform): two quad permutes, the two mirrors of a 16-lane row, then the four rows through SGPRs
-__device__ __forceinline__ float wave_max_dpp(float v) {
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0xB1, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x4E, 0xF, 0xF, false)));
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x141, 0xF, 0xF, false)));  // row_half_mirror
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), 0x140, 0xF, 0xF, false)));  // row_mirror
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
-
 #define SELU_ALPHA 1.6732632423543772f
 #define SELU_SCALE 1.0507009873554805f
 

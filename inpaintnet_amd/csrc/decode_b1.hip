@@ -61,6 +61,7 @@
 #define INET_GRANULE_KID chain::K_DECODE_B1
 #include "granule.h"
 #include "prof.h"
+#include "reduce.h"
 #include "sample.h"
 #include "decode_chain.h"
 

@@ -8,33 +8,13 @@
 #include "common.h"
 #include "iw.h"
 #include "prof.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int kIwBlock = 256;                    // four waves: four rows of iw_draw, one row of nll_rows, four measures of iw_finish
 constexpr int kIwWaves = kIwBlock / 64;
 constexpr long kIwMaxRows = 1L << 24;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {           // xor butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {           // fmax: a NaN is skipped (the caller looks for NaNs itself)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // One element of a row: z = mu + eps * exp(ls), reparam_kl_kernel's expression with the same expf; the element's term of logr.
 __device__ __forceinline__ float iw_elem(float m, float l, float e, float& zo) {
@@ -134,7 +114,7 @@ iw_finish_kernel(const float* __restrict__ logw, const float* __restrict__ nll, 
         nan |= x != x;
         m = fmax(m, x);
     }
-    m = wave_max_d(m);
+    m = wave_max(m);
     nan = __any(nan);
     double s1 = 0.0, s2 = 0.0, sw = 0.0, sn = 0.0;
     for (int k = lane; k < K; k += 64) {
@@ -144,10 +124,10 @@ iw_finish_kernel(const float* __restrict__ logw, const float* __restrict__ nll, 
         sw += x;
         sn += (double)nl[k];
     }
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    sw = wave_sum_d(sw);
-    sn = wave_sum_d(sn);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    sw = wave_sum(sw);
+    sn = wave_sum(sn);
     if (lane == 0) {
         const double kd = (double)K;
         double iwae = m + log(s1 / kd), elbo = sw / kd, ess = (s1 * s1) / s2;

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "mmd.h"
 #include "prof.h"
+#include "reduce.h"
 
 namespace {
 
@@ -20,12 +21,6 @@ constexpr int kMmdTile = 256;                    // columns of a tile: one per t
 constexpr int kMmdZc = 32;                       // the chunk of Z staged in LDS at a time: any Z >= 1 fits
 constexpr int kMmdSpan = 256;                    // latent dimensions whose gradient a workgroup holds in registers at a time (8 per thread)
 constexpr int kMmdFinishBlock = 256;
-
-__device__ __forceinline__ float mmd_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // kernel value and k'(d) of one distance; expf is the device library's (not the hardware approximation __expf)
 template <int KIND>
@@ -157,11 +152,11 @@ mmd_pair_kernel(const float* __restrict__ x, const float* __restrict__ y, long B
                 }
             }
             if (sp == 0) {                           // the workgroup's share: the xor tree over a wave's lanes, the four waves in order
-                S = mmd_wave_sum(S);
+                S = wave_sum(S);
                 if ((t & 63) == 0) red[t >> 6] = S;
                 __syncthreads();
                 if (t == 0) {
-                    ws[2 * (long)blockIdx.x + phase] = ((red[0] + red[1]) + red[2]) + red[3];
+                    ws[2 * (long)blockIdx.x + phase] = sum4(red);
                     if (!own_x) ws[2 * (long)blockIdx.x + 1] = 0.f;
                 }
             }
@@ -188,15 +183,15 @@ mmd_finish_kernel(const float* __restrict__ ws, int nb, long B, double a, double
         sxy += ws[2 * (long)g + 1];
         syy += ws[2 * ((long)nb + g)];
     }
-    sxx = mmd_wave_sum(sxx);
-    syy = mmd_wave_sum(syy);
-    sxy = mmd_wave_sum(sxy);
+    sxx = wave_sum(sxx);
+    syy = wave_sum(syy);
+    sxy = wave_sum(sxy);
     if ((t & 63) == 0) { tot[0][t >> 6] = sxx; tot[1][t >> 6] = syy; tot[2][t >> 6] = sxy; }
     __syncthreads();
     if (t == 0) {
-        const float Sxx = ((tot[0][0] + tot[0][1]) + tot[0][2]) + tot[0][3];
-        const float Syy = ((tot[1][0] + tot[1][1]) + tot[1][2]) + tot[1][3];
-        const float Sxy = ((tot[2][0] + tot[2][1]) + tot[2][2]) + tot[2][3];
+        const float Sxx = sum4(tot[0]);
+        const float Syy = sum4(tot[1]);
+        const float Sxy = sum4(tot[2]);
         const double off = diag * (double)B;
         out[0] = (float)(coeff * (a * ((double)Sxx - off) + a * ((double)Syy - off) - c * (double)Sxy));
         out[1] = Sxx;

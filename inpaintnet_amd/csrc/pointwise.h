@@ -1,4 +1,5 @@
-// Host-side launchers of the HBM-bound helper kernels (pointwise.hip).
+// Host-side launchers of the HBM-bound layout, gather and small helper kernels (pointwise.hip).  The cross-entropy's are in ce.h,
+// the latent kernels' in latent.h, the optimizer step's in optim.h, the sampling row kernels' and the dropout mask's in sample_rows.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,50 +11,6 @@ int pw_pack_frag(const float* in, long ld, int R, int K, float* out, int transpo
 // the same for up to 8 equally shaped matrices in one launch
 int pw_pack_frag_multi(const float* const* ins, float* const* outs, int n, long ld, int R, int K, int transposed,
                        hipStream_t s);
-int pw_cross_entropy(const float* W, long ld_w, int rows, int V, const long long* tgt, float* dW, long ld_dw,
-                     float scale, float out_scale, float* loss_sum, float* correct, hipStream_t s,
-                     const float* scale_dev = nullptr, const float* add_term = nullptr, float add_scale = 0.f,
-                     float* fwd_out = nullptr, float fwd_scale = 0.f);
-int pw_reparam_kl(const float* mu, const float* ls, const float* eps, float* z, float* sigma, long n, float* kl_sum,
-                  hipStream_t s);
-int pw_latent_bwd(const float* dz, const float* mu, const float* ls, const float* eps, float kscale, const float* kdev,
-                  float* dmu, float* dls, long n, hipStream_t s);
-int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long* out, long stride, uint64_t seed,
-                          uint64_t offset, hipStream_t s);
-// out[row*stride] = sample.h's token of the row W[row,:] for the request r: a row here is what r calls a row, so r's strides step from
-// row to row (uniforms required, logits not written).  ONE of the four row kernels runs -- temperature, truncated, constrained, forced --:
-// the one of level max(floor_level, r.level(V)).  floor_level is 1 or 2: an entry that promises the truncating kernel passes 2, so that
-// inet_sample_truncated with truncation off and no logp still runs it under its trunc_ label; vae.hip's tick loop passes the call's level.
-// Levels 3 and 4 come from r's mask and forced array alone (level 4 without a mask: words of all ones).  A row outside the rule takes
-// argmax_first over its allowed tokens, logp NaN.  -1: what r.ok(V) refuses.
-namespace sample { struct Request; }
-int pw_sample(const float* W, long ld_w, int rows, int V, long long* out, long stride, const sample::Request& r, int floor_level,
-              hipStream_t s);
-// The KL term with a floor (free bits; the rule: pointwise.hip).  per 0 = 'measure' (a part per row, threshold
-// free_nats), 1 = 'dim' (a part per column, threshold rows * free_nats; through a workspace of pw_reparam_kl_fb_ws_bytes).  Two launches.
-// parts / keep: rows or Z floats; kl_sum (floored) and kl_raw (plain) are added onto.  z and eps nullable.
-long pw_reparam_kl_fb_ws_bytes(long rows, int Z, int per);
-int pw_reparam_kl_fb(const float* mu, const float* ls, const float* eps, float* z, long rows, int Z, float free_nats, int per,
-                     float* parts, float* keep, float* kl_sum, float* kl_raw, void* ws, long ws_bytes, hipStream_t s);
-int pw_latent_bwd_fb(const float* dz, const float* mu, const float* ls, const float* eps, float kscale, const float* kdev,
-                     const float* keep, int per, float* dmu, float* dls, long rows, int Z, hipStream_t s);
-// The norm of the gradient arena: partials[pw_sqnorm_parts()] = the f64 sums of squares of the fixed grid's shares of g (every entry
-// written: nothing to zero in front), what the optimizer step takes as `partials`.
-int pw_sqnorm_parts();
-int pw_grad_sqnorm(const float* g, long n, double* partials, hipStream_t s);
-// The optimizer step, one launch (the rule: pointwise.hip).  Nullable members switch a part off.
-struct PwAdamStep {
-    float* p; const float* g; float* m; float* v; long n;
-    float lr, b1, b2, eps; int step; float gscale;
-    float max_norm; const double* partials;      // global-norm clipping and the non-finite drop; null: neither, max_norm is ignored
-    float weight_decay; const unsigned* mask;    // p *= (float)(1 - lr * weight_decay) where the mask says so; null: everywhere
-    float* ema; float ema_decay;                 // ema = fmaf(ema_decay, ema, (float)(1 - ema_decay) * p_new); null: none
-    const float* step_flag;                      // device float, non-zero = skip (the ranks' summed chain status); null: this process's word
-    unsigned* report;                            // host-mapped words zeroed by the caller: four, eight with partials; null: none
-};
-int pw_adam_step(const PwAdamStep& a, hipStream_t s);
-int pw_step_flag_export(float* dst, hipStream_t s);
-int pw_epoch_stats_add(float* sums, const float* loss, const float* acc, hipStream_t s, const float* step_flag = nullptr);
 int pw_colsum(const float* X, long ld, int M, int N, float* out, hipStream_t s);
 // up to 8 column sums (bias gradients of one module) in one launch: out_i[n] += sum_m X_i[m*ld_i + n]
 struct PwColsumJob { const float* X; long ld; int M, N; float* out; };
@@ -87,7 +44,6 @@ int pw_axpb(const float* a, const float* x, long incx, const float* b, float* y,
 // (`partial`: 64 floats of scratch): deterministic from run to run
 int pw_beat_input_grad(const float* sv, const float* w, long incw, const float* b0, float* dw, float* db0, int n,
                        const float* X, long ld, int M, float* partial, hipStream_t s);
-int pw_dropout_mask(float* out, long n, float p, uint64_t seed, uint64_t offset, hipStream_t s);
 int pw_scale(float* x, long n, float a, hipStream_t s);
 int pw_embedding_fwd(const float* table, const long long* idx, long rows, int E, float* out, const float* row_scale,
                      hipStream_t s);

@@ -1,42 +1,17 @@
-// HBM-bound helpers of the hot path: wavefront-reduced softmax / cross-entropy /
-// accuracy, KL + reparameterisation, argmax with the lowest-index tie rule,
-// fused Adam over the flat arena, column sums (bias gradients), one-hot
-// expansion (embedding gradients as MFMA contractions instead of contended
-// atomics), transposes, dropout-mask generation.  All are grid-stride,
-// coalesced along the contiguous dimension, 64-lane wave reductions via DPP
-// shuffles.
+// HBM-bound layout, gather and small helper kernels of the hot path: transposes and the fragment-major packing, column sums
+// (bias gradients), one-hot expansion / token segment sums / table gradients (embedding gradients without contended atomics),
+// the prologue launch, fills, copies and scales, argmax with the lowest-index tie rule, embedding, the measure split.  All are
+// grid-stride and coalesced along the contiguous dimension; the 64-lane wave reductions are reduce.h's xor butterflies.
+// The cross-entropy lives in ce.hip, KL / reparameterisation / free bits in latent.hip, the optimizer step in optim.hip, the
+// sampling row kernels and the dropout mask in sample_rows.hip.
 #include <algorithm>
-#include <cstdio>
 #include "common.h"
 #include "pointwise.h"
-#include "prof.h"
 #include "chain.h"
-#include "sample.h"
+#include "pw_launch.h"
+#include "reduce.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-// argmax_first, np.argmax's rule (the one arnn_gen.hip follows): a NaN is the maximum, the lowest index wins among equals.  `m` is
-// the row's maximum as fmaxf leaves it (NaN skipped).  A lane folds the candidates of its elements into ONE key, so that one wave
-// minimum decides: a NaN at v -> v, an element equal to m -> kAmEq + v (V < 2^30), anything else -> kAmNone; am_index() of the
-// minimum is the row's argmax (every row has a candidate: its maximum, or a NaN).
-constexpr int kAmEq = 0x40000000, kAmNone = 0x7fffffff;
-__device__ __forceinline__ int am_key(float x, float m, int v) { return x != x ? v : (x == m ? kAmEq + v : kAmNone); }
-__device__ __forceinline__ int am_index(int key) { return key & (kAmEq - 1); }
 
 // out[c*ld_out + r] = in[r*ld_in + c]
 __global__ void transpose_kernel(const float* __restrict__ in, long ld_in, float* __restrict__ out, long ld_out,
@@ -109,453 +84,6 @@ __global__ void pack_frag_multi_kernel(PackList pl, long ld, int R, int K, int t
     }
 }
 
-// One wavefront per row of V logits.  loss_sum += out_scale * (lse - w[target]);
-// correct += out_scale * (argmax_first(w) == target); dW = (softmax - onehot) * scale.
-__global__ void ce_kernel(const float* __restrict__ W, long ld_w, int rows, int V,
-                          const long long* __restrict__ tgt, float* __restrict__ dW, long ld_dw, float scale,
-                          float out_scale, float* __restrict__ loss_sum, float* __restrict__ correct,
-                          const float* __restrict__ scale_dev, const float* __restrict__ add_term, float add_scale,
-                          float* __restrict__ fwd_out, float fwd_scale) {
-    // scale_dev: dW is also multiplied by this device scalar (the upstream gradient of the mean loss, read on the device:
-    // no elementwise pass over dW afterwards); add_term: *loss_sum also receives add_scale * add_term[0], once (the KL
-    // term of the ELBO: loss = CE + beta/B * KL leaves this kernel complete)
-    // fwd_out: receives fwd_scale * scale_dev[0] (the gradient handed on to the producer of add_term, e.g. the KL sum)
-    if (scale_dev) {
-        if (fwd_out && blockIdx.x == 0 && threadIdx.x == 0) *fwd_out = fwd_scale * *scale_dev;
-        scale *= *scale_dev;
-    }
-    if (add_term && loss_sum && blockIdx.x == 0 && threadIdx.x == 0) unsafeAtomicAdd(loss_sum, add_scale * *add_term);
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    float lsum = 0.f, csum = 0.f;
-    for (int row = wave; row < rows; row += nwaves) {
-        const float* w = W + (long)row * ld_w;
-        float m = -INFINITY;
-        for (int v = lane; v < V; v += 64) m = fmaxf(m, w[v]);
-        m = wave_max(m);
-        float se = 0.f;
-        int am = kAmNone;
-        for (int v = lane; v < V; v += 64) {
-            const float x = w[v];
-            se += expf(x - m);
-            am = min(am, am_key(x, m, v));
-        }
-        se = wave_sum(se);
-        am = am_index(wave_min_i(am));
-        const int tg = (int)tgt[row];
-        const float lse = m + logf(se);
-        if (lane == 0) {
-            lsum += lse - w[tg];
-            csum += (am == tg) ? 1.f : 0.f;
-        }
-        if (dW) {
-            float* d = dW + (long)row * ld_dw;
-            const float inv = 1.f / se;
-            for (int v = lane; v < V; v += 64) d[v] = (expf(w[v] - m) * inv - (v == tg ? 1.f : 0.f)) * scale;
-        }
-    }
-    // lane 0 of every wave holds that wave's partials: combine the 4 waves of the block, one atomic pair per block
-    __shared__ float part[2][4];
-    if (lane == 0) { part[0][threadIdx.x >> 6] = lsum; part[1][threadIdx.x >> 6] = csum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (loss_sum) unsafeAtomicAdd(loss_sum, (part[0][0] + part[0][1] + part[0][2] + part[0][3]) * out_scale);
-        if (correct) unsafeAtomicAdd(correct, (part[1][0] + part[1][1] + part[1][2] + part[1][3]) * out_scale);
-    }
-}
-
-// z = mu + eps * exp(ls);  kl_sum += sum 0.5(sigma^2 + mu^2 - 1) - ls
-__global__ void reparam_kl_kernel(const float* __restrict__ mu, const float* __restrict__ ls,
-                                  const float* __restrict__ eps, float* __restrict__ z, float* __restrict__ sigma,
-                                  long n, float* __restrict__ kl_sum) {
-    float acc = 0.f;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float l = ls[i], m = mu[i];
-        const float s = expf(l);
-        if (z) z[i] = m + (eps ? eps[i] : 0.f) * s;
-        if (sigma) sigma[i] = s;
-        acc += 0.5f * (s * s + m * m - 1.f) - l;
-    }
-    if (kl_sum) {                                   // one atomic per block: a thousand of them on one address cost ~10 us
-        __shared__ float part[4];
-        acc = wave_sum(acc);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) unsafeAtomicAdd(kl_sum, (part[0] + part[1]) + (part[2] + part[3]));
-    }
-}
-
-// dmu = dz + k*mu ;  dls = dz*eps*sigma + k*(sigma^2 - 1)      (k = kscale [* *kdev]: beta / B times the upstream gradient
-// of the KL term, which autograd hands over as a device scalar)
-__global__ void latent_bwd_kernel(const float* __restrict__ dz, const float* __restrict__ mu,
-                                  const float* __restrict__ ls, const float* __restrict__ eps, float kscale,
-                                  const float* __restrict__ kdev, float* __restrict__ dmu, float* __restrict__ dls, long n) {
-    if (kdev) kscale *= *kdev;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float s = expf(ls[i]);
-        const float g = dz ? dz[i] : 0.f;
-        dmu[i] = g + kscale * mu[i];
-        dls[i] = g * (eps ? eps[i] : 0.f) * s + kscale * (s * s - 1.f);
-    }
-}
-
-// ---- the KL term with a floor ("free bits").  KL[b,d] = 0.5(sigma^2 + mu^2 - 1) - ls over [rows, Z] is summed
-// into PARTS -- 'measure': part[b] = sum_d, one per row; 'dim': part[d] = sum_b, one per column -- and a part counts with
-// max(part, thr): kept = !(part <= thr) (a tie is floored, a NaN part is kept and reaches both sums); kl_sum += sum kept ? part : thr,
-// kl_raw += sum part.  Every part is a pure function of (mu, ls, rows, Z, whether the 16-byte path runs): its additions happen in one
-// fixed order, no float atomic anywhere -- a part next to the threshold keeps its keep bit from run to run, and so do the two scalars
-// their bits.  Two launches per mode: the elementwise pass, then one finishing workgroup.  VEC = 4: Z % 4 == 0 and every pointer
-// 16-byte aligned; VEC = 1 otherwise.
-constexpr int kFbMeasureGrid = 256;              // workgroups of the 'measure' forward: a wave per row, 1024 rows per pass of the grid
-constexpr int kFbDimGrid = 128;                  // workgroups of the 'dim' forward (4 rows each per pass) = rows of its workspace
-
-template <int VEC>
-__device__ __forceinline__ void fb_load(const float* p, float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = x[k];
-    } else {
-        v[0] = *p;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void fb_store(float* p, const float (&v)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-    else *p = v[0];
-}
-// z (nullable) = m + e * exp(l) for the VEC elements at p; returns their KL terms added onto acc, in element order
-template <int VEC>
-__device__ __forceinline__ void fb_elements(const float* __restrict__ mu, const float* __restrict__ ls, const float* __restrict__ eps,
-                                            float* __restrict__ z, long at, float (&acc)[VEC]) {
-    float m[VEC], l[VEC], e[VEC], zz[VEC];
-    fb_load<VEC>(mu + at, m);
-    fb_load<VEC>(ls + at, l);
-    if (eps) fb_load<VEC>(eps + at, e);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) {
-        const float s = expf(l[k]);
-        zz[k] = m[k] + (eps ? e[k] : 0.f) * s;
-        acc[k] += 0.5f * (s * s + m[k] * m[k] - 1.f) - l[k];
-    }
-    if (z) fb_store<VEC>(z + at, zz);
-}
-
-// 'measure', launch 1 of 2: z and parts[row], one wavefront per row.  Lane L adds its elements L*VEC + k + 64*VEC*j in ascending j (one
-// chain per k, then (a0 + a1) + (a2 + a3)), wave_sum's xor tree adds the lanes.  The floor and the two scalars are the finishing launch's.
-template <int VEC>
-__global__ void __launch_bounds__(256)
-reparam_kl_fb_measure_kernel(const float* __restrict__ mu, const float* __restrict__ ls, const float* __restrict__ eps,
-                             float* __restrict__ z, long rows, int Z, float* __restrict__ parts) {
-    const int lane = threadIdx.x & 63;
-    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const long nwaves = ((long)gridDim.x * blockDim.x) >> 6;
-    for (long row = wave; row < rows; row += nwaves) {
-        float acc[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-        for (int c = lane * VEC; c < Z; c += 64 * VEC) fb_elements<VEC>(mu, ls, eps, z, row * Z + c, acc);
-        float a = acc[0];
-        if constexpr (VEC == 4) a = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-        a = wave_sum(a);
-        if (lane == 0) parts[row] = a;
-    }
-}
-
-// 'dim', launch 1 of 2: z, and ws[g*Z + c] = workgroup g's share of column c's sum.  A workgroup is 4 row-lanes (its waves) x 64*VEC
-// columns; row-lane r of workgroup g adds rows 4g + r + 4*gridDim.x*j in ascending j, the four row-lanes are added in order.  EVERY
-// workgroup stores all Z of its entries with plain stores (one without rows: zeros): nothing to zero in front, no atomics -- the
-// consumer is the next launch (grad_sqnorm_kernel's pattern).
-template <int VEC>
-__global__ void __launch_bounds__(256)
-reparam_kl_fb_dim_kernel(const float* __restrict__ mu, const float* __restrict__ ls, const float* __restrict__ eps,
-                         float* __restrict__ z, long rows, int Z, float* __restrict__ ws) {
-    __shared__ float part[4][64 * VEC];
-    const int lane = threadIdx.x & 63, rl = threadIdx.x >> 6;
-    for (int c0 = 0; c0 < Z; c0 += 64 * VEC) {
-        const int c = c0 + lane * VEC;
-        float acc[VEC];
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
-        if (c < Z)                                           // (VEC = 4: Z % 4 == 0, so c < Z covers c + 3)
-            for (long r = (long)blockIdx.x * 4 + rl; r < rows; r += (long)gridDim.x * 4) fb_elements<VEC>(mu, ls, eps, z, r * Z + c, acc);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) part[rl][lane * VEC + k] = acc[k];
-        __syncthreads();
-        if (rl == 0 && c < Z) {
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) {
-                const int j = lane * VEC + k;
-                ws[(long)blockIdx.x * Z + c + k] = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// The finishing launch of both modes: ONE workgroup of kFbFinishBlock threads, so that the two scalars are sums in a fixed order too
-// (two chains of atomics meet their addends in two different orders: with every part kept kl_sum and kl_raw would differ in the last
-// bit from run to run).  ws given ('dim'): part[c] = the G workspace rows of column c -- thread (q, c) adds rows q, q + 4, ... in
-// ascending order, the four q are added in order -- and parts[c] is written here; ws null ('measure'): parts[c] is read.  Then the
-// floor: keep[c], and per thread the floored and the plain sum of its parts c = t, t + 256, ...; wave_sum, the four waves in order,
-// one thread adds onto *kl_sum and *kl_raw.
-constexpr int kFbFinishBlock = 1024;
-__global__ void __launch_bounds__(kFbFinishBlock)
-reparam_kl_fb_finish_kernel(const float* __restrict__ ws, int G, long nparts, float thr, float* __restrict__ parts,
-                            float* __restrict__ keep, float* __restrict__ kl_sum, float* __restrict__ kl_raw) {
-    __shared__ float part[4][256];
-    __shared__ float tot[2][4];
-    const int cl = threadIdx.x & 255, q = threadIdx.x >> 8;
-    float f = 0.f, r = 0.f;
-    for (long c0 = 0; c0 < nparts; c0 += 256) {
-        const long c = c0 + cl;
-        if (ws) {
-            float acc = 0.f;
-            if (c < nparts)
-                for (int g = q; g < G; g += 4) acc += ws[(long)g * nparts + c];
-            part[q][cl] = acc;
-            __syncthreads();
-        }
-        if (q == 0 && c < nparts) {
-            float p;
-            if (ws) { p = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl]; parts[c] = p; }
-            else p = parts[c];
-            const bool kept = !(p <= thr);
-            keep[c] = kept ? 1.f : 0.f;
-            f += kept ? p : thr;
-            r += p;
-        }
-        if (ws) __syncthreads();
-    }
-    if (q == 0) {                                       // threads 0..255: four whole waves
-        f = wave_sum(f);
-        r = wave_sum(r);
-        if ((cl & 63) == 0) { tot[0][cl >> 6] = f; tot[1][cl >> 6] = r; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        *kl_sum += ((tot[0][0] + tot[0][1]) + tot[0][2]) + tot[0][3];
-        *kl_raw += ((tot[1][0] + tot[1][1]) + tot[1][2]) + tot[1][3];
-    }
-}
-
-// latent_bwd_kernel with the keep vector: dmu = dz + kk*mu ; dls = dz*eps*sigma + kk*(sigma^2 - 1), kk = the element's part is kept ?
-// k : 0 -- a SELECTION, never a product with the float keep, so that a floored part hands dz on bit for bit and, with every part kept,
-// the expressions are latent_bwd_kernel's.  Element i belongs to part i / Z ('measure') or i % Z ('dim'); the pair is carried along
-// the grid-stride loop, one division per thread.
-__global__ void latent_bwd_fb_kernel(const float* __restrict__ dz, const float* __restrict__ mu, const float* __restrict__ ls,
-                                     const float* __restrict__ eps, float kscale, const float* __restrict__ kdev,
-                                     const float* __restrict__ keep, int per_dim, float* __restrict__ dmu, float* __restrict__ dls,
-                                     long rows, int Z) {
-    if (kdev) kscale *= *kdev;
-    const long n = rows * Z, stride = (long)gridDim.x * blockDim.x;
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    long row = i / Z;
-    int col = (int)(i - row * Z);
-    const long qs = stride / Z;
-    const int rs = (int)(stride - qs * Z);
-    for (; i < n; i += stride) {
-        const float kk = keep[per_dim ? (long)col : row] != 0.f ? kscale : 0.f;
-        const float s = expf(ls[i]);
-        const float g = dz ? dz[i] : 0.f;
-        dmu[i] = g + kk * mu[i];
-        dls[i] = g * (eps ? eps[i] : 0.f) * s + kk * (s * s - 1.f);
-        col += rs;
-        row += qs;
-        if (col >= Z) { col -= Z; ++row; }
-    }
-}
-
-// ---- the optimizer step and, in front of it, the norm of the gradient arena.  grad_sqnorm_kernel leaves kSqnormParts f64 partial sums
-// of squares; adamw_kernel, the ONE step kernel behind every inet_adam_step* entry point, adds them up itself (clip rule, below).
-constexpr int kSqnormParts = 1024;               // workgroups of grad_sqnorm_kernel = doubles of its output
-constexpr int kSqnormBlock = 256;
-
-__device__ __forceinline__ double wave_sum_d(double v) {           // xor butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// the sum of the workgroup's 256 values on every thread: the wave tree, then the four waves in wave order
-__device__ __forceinline__ double block_sum_d(double v, double* part) {
-    v = wave_sum_d(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((part[0] + part[1]) + part[2]) + part[3];
-}
-
-// partials[b] = the squares of workgroup b's grid-stride share of g, in f64.  EVERY workgroup stores (one without elements: 0.0), with a
-// plain store: nothing to zero in front, no atomics, no hand-off between workgroups -- the consumer is the next launch.
-__global__ void __launch_bounds__(kSqnormBlock) grad_sqnorm_kernel(const float* __restrict__ g, long n, double* __restrict__ partials) {
-    __shared__ double part[4];
-    const long n4 = n >> 2;
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
-    const long stride = (long)gridDim.x * blockDim.x;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;                   // one chain per element slot of the 16-byte load
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    // four loads in flight per lane: the grid holds 4 MB per pass, the HBM pipe wants more than that outstanding
-    for (; i + 3 * stride < n4; i += 4 * stride) {
-        const f32x4 x0 = g4[i], x1 = g4[i + stride], x2 = g4[i + 2 * stride], x3 = g4[i + 3 * stride];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const f32x4 x = k == 0 ? x0 : k == 1 ? x1 : k == 2 ? x2 : x3;
-            a0 = fma((double)x[0], (double)x[0], a0);
-            a1 = fma((double)x[1], (double)x[1], a1);
-            a2 = fma((double)x[2], (double)x[2], a2);
-            a3 = fma((double)x[3], (double)x[3], a3);
-        }
-    }
-    for (; i < n4; i += stride) {
-        const f32x4 x = g4[i];
-        a0 = fma((double)x[0], (double)x[0], a0);
-        a1 = fma((double)x[1], (double)x[1], a1);
-        a2 = fma((double)x[2], (double)x[2], a2);
-        a3 = fma((double)x[3], (double)x[3], a3);
-    }
-    // tail, as the step kernel's
-    for (long t = (n4 << 2) + (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride) a0 = fma((double)g[t], (double)g[t], a0);
-    const double s = block_sum_d((a0 + a1) + (a2 + a3), part);
-    if (threadIdx.x == 0) partials[blockIdx.x] = s;
-}
-
-// ---- the optimizer step: torch.optim.Adam / AdamW (2.x single-tensor form) over the flat arena, optionally
-// behind global-norm clipping, with decoupled weight decay and with EMA shadow weights.  One kernel; the rule, stated once.
-//
-// Skip and report.  A chain kernel gave up waiting for its group (chain.h): the gradients of the step are not valid, so the step leaves
-// every arena as it is.  Which word decides: `step_flag` when the caller passes one -- the flags of ALL ranks summed with the gradients
-// (inet_step_flag_export + the all-reduce), so that every rank of a data-parallel job takes the same decision --, else this process's own
-// device word.  `report` (nullable; host-mapped words the caller owns and zeroed) tells the host what was decided (encoder.py:111-116,
-// decoder.py:424-429): [0] = 1 the kernel ran, [1] = 1 the flag skipped the step, [2] = 1 a parameter left the finite range, [3] = 1
-// SOME rank's prologue kernels met a token outside the vocabulary (step_flag[1] = the ranks' exported token words: every rank raises the
-// reference's check_index ValueError at the same step).  WITHOUT partials only these four words are ever stored to: a record of four
-// words is enough.  With partials the record has eight: [4] = 1 clipped, [5] = 1 dropped for a non-finite gradient, [6] = the bits of
-// (float)norm (also on a skip), [7] stays 0.
-//
-// Clipping (partials given: what grad_sqnorm_kernel left for the gradient arena g[0..n); 0 < max_norm <= +inf; section 18):
-//   1. S = sum (double)g_i * (double)g_i: every square exact in f64, the sum in f64 in a FIXED order that depends on n only.  Every
-//      workgroup sums the kSqnormParts partials itself, in the SAME order (lane-strided reads, the same tree), so that all of them derive
-//      norm, c, scale and the decision bit for bit alike.  norm = |gscale| * sqrt(S) in f64.
-//   2. nonfinite = !isfinite(norm)  (a finite f32 arena cannot overflow the f64 sum: true iff some element is inf or NaN).
-//   3. c = max_norm / (norm + 1e-6) in f64 (torch's clip_grad_norm_ coefficient); scale = c < 1 ? (float)c : 1.0f;
-//      clipped = c < 1.  max_norm = +inf never clips.
-//   4. the chain / step flag says skip: the step is skipped, nonfinite and clipped are reported as 0.
-//   5. else nonfinite: every arena stays untouched, report[5] = 1, report[1] and report[2] stay 0 (not a chain failure).
-//   6. else the step below with gs = the ONE f32 product gscale * scale.
-// Without partials gs = gscale, max_norm is ignored and only the flag skips.
-//
-// Decay and EMA (section 19).  weight_decay >= 0; a nullable decay mask (bit i & 31 of word i >> 5 set: element i decays; null: every
-// element decays); a nullable arena ema[0..n) and ema_decay in [0, 1).  The launcher rounds the factors ONCE, on the host:
-// lr_over_bc1 = (float)(lr / (1 - b1^step)), inv_sqrt_bc2 = (float)(1 / sqrt(1 - b2^step)), decay = (float)(1.0 - (double)lr *
-// (double)weight_decay) -- exactly 1.0f for weight_decay == 0 --, omd = (float)(1.0 - (double)ema_decay).  A skipped or dropped step
-// leaves p, m, v AND ema bit for bit untouched.
-//
-// The applied step, per element, every operation in f32 and every rounding spelled out -- contraction is OFF in the kernel and each fused
-// operation is written as an fmaf, so the bits do not depend on what a compiler would contract (tests/test_gpu_adam_bits.py holds them to
-// a recording):
-//   gr    = g * gs
-//   m     = fmaf(1 - b1, gr, b1 * m)
-//   v     = fmaf(b2, v, gr * ((1 - b2) * gr))        in the 16-byte body;
-//           b2 * v + gr * ((1 - b2) * gr)            in the scalar tail: BOTH products rounded, then the sum.  An oddity, and part of the
-//                                                    recorded bits: the last n & 3 elements round v once more than the rest
-//   denom = fmaf(sqrtf(v), inv_sqrt_bc2, eps)        (torch: sqrt(v) / sqrt(bc2) + eps)
-//   p1    = decays(i) ? p * decay : p                (torch's _single_tensor_adamw order, param.mul_(1 - lr * wd) first; the product is
-//                                                    rounded on its own, never fused into what follows: p * 1.0f is p)
-//   p     = fmaf(-lr_over_bc1, m / denom, p1);       report[2] tests this p
-//   ema   = fmaf(ema_decay, ema, omd * p)            (ema given; the product rounded on its own: ema_decay == 0 gives ema == p)
-//
-// The grid is grid_for(n / 4 + 1, 256, 4096) workgroups of kSqnormBlock threads, grid-stride over 16-byte groups, then the n & 3 elements
-// of the tail.  EMA / MASK: whether `ema` / `mask` are given -- compile-time, so that the plain form carries neither loads nor
-// registers of the other three.  Four consecutive elements never straddle a mask word: the body reads ONE word per 16 bytes.
-template <bool EMA, bool MASK>
-__global__ void __launch_bounds__(kSqnormBlock)
-adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, long n,
-             float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2, float eps, float gscale, float max_norm,
-             const double* __restrict__ partials, float decay, const unsigned* __restrict__ mask, float* __restrict__ ema,
-             float ema_decay, float omd, const unsigned* __restrict__ abort_word, const float* __restrict__ step_flag,
-             unsigned* __restrict__ report) {
-#pragma clang fp contract(off)
-    __shared__ double part[4];
-    const bool skip = step_flag ? (*step_flag != 0.f)
-                                : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
-    bool nonfinite = false, clipped = false;
-    double norm = 0.0, c = 1.0;
-    if (partials) {                                  // uniform over the grid: steps 1-3 of the clip rule
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < kSqnormParts / kSqnormBlock; ++k) acc += partials[threadIdx.x + k * kSqnormBlock];
-        const double S = block_sum_d(acc, part);
-        norm = fabs((double)gscale) * sqrt(S);
-        nonfinite = !skip && !(fabs(norm) <= 1.7976931348623157e308);          // NaN or +inf
-        c = (double)max_norm / (norm + 1e-6);
-        clipped = !skip && !nonfinite && c < 1.0;
-    }
-    if (report && blockIdx.x == 0 && threadIdx.x == 0) {
-        __hip_atomic_store(report + 0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (skip) __hip_atomic_store(report + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (step_flag && step_flag[1] != 0.f) __hip_atomic_store(report + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (partials) {
-            if (clipped) __hip_atomic_store(report + 4, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (nonfinite) __hip_atomic_store(report + 5, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(report + 6, __float_as_uint((float)norm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    if (skip || nonfinite) return;
-    const float gs = partials ? gscale * (clipped ? (float)c : 1.0f) : gscale;
-    const float omb1 = 1.f - b1, omb2 = 1.f - b2;
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-    bool bad = false;
-    const long n4 = n >> 2;
-    f32x4* p4 = reinterpret_cast<f32x4*>(p);
-    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
-    f32x4* m4 = reinterpret_cast<f32x4*>(m);
-    f32x4* v4 = reinterpret_cast<f32x4*>(v);
-    f32x4* e4 = reinterpret_cast<f32x4*>(ema);
-    for (long i = tid; i < n4; i += stride) {
-        f32x4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ee;
-        if (EMA) ee = e4[i];
-        unsigned bits = 0xfu;
-        if (MASK) bits = mask[i >> 3] >> (((unsigned)i & 7u) << 2);            // elements 4i .. 4i+3: word (4i) >> 5, bit (4i) & 31
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gr = gg[e] * gs;
-            mm[e] = fmaf(omb1, gr, b1 * mm[e]);
-            vv[e] = fmaf(b2, vv[e], gr * (omb2 * gr));
-            const float denom = fmaf(sqrtf(vv[e]), inv_sqrt_bc2, eps);
-            const float p1 = (!MASK || ((bits >> e) & 1u)) ? pp[e] * decay : pp[e];
-            pp[e] = fmaf(-lr_over_bc1, mm[e] / denom, p1);
-            bad |= !(fabsf(pp[e]) <= 3.402823466e38f);          // NaN or +-inf
-            if (EMA) ee[e] = fmaf(ema_decay, ee[e], omd * pp[e]);
-        }
-        p4[i] = pp; m4[i] = mm; v4[i] = vv;
-        if (EMA) e4[i] = ee;
-    }
-    for (long i = (n4 << 2) + tid; i < n; i += stride) {          // tail: the mask per element; v's sum rounds both products
-        const float gr = g[i] * gs;
-        const float mm = fmaf(omb1, gr, b1 * m[i]);
-        const float vv = b2 * v[i] + gr * (omb2 * gr);
-        m[i] = mm; v[i] = vv;
-        const float p1 = (!MASK || ((mask[i >> 5] >> ((unsigned)i & 31u)) & 1u)) ? p[i] * decay : p[i];
-        const float pn = fmaf(-lr_over_bc1, mm / fmaf(sqrtf(vv), inv_sqrt_bc2, eps), p1);
-        p[i] = pn;
-        bad |= !(fabsf(pn) <= 3.402823466e38f);
-        if (EMA) ema[i] = fmaf(ema_decay, ema[i], omd * pn);
-    }
-    if (bad && report) __hip_atomic_store(report + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// dst[0] = 1 if a chain launch of this process has timed out since the last reset, else 0: the word a data-parallel caller sums
-// over ranks together with the gradients (inet_step_flag_export)
-// dst[1] = 1 if a prologue kernel of this process has met a token outside the vocabulary since the last reset (the host-mapped
-// word behind inet_token_status): decoder.py:36-45's ValueError, raised by all ranks together
-__global__ void step_flag_export_kernel(const unsigned* abort_word, const unsigned* tok_word, float* dst) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        dst[0] = (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ? 1.f : 0.f;
-        dst[1] = (tok_word && __hip_atomic_load(tok_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) ? 1.f : 0.f;
-    }
-}
-
 // out[n] (+)= sum_m X[m*ld + n].  Block = 64 columns x 4 row-lanes; grid.y splits rows; atomics combine.
 __global__ void colsum_kernel(const float* __restrict__ X, long ld, int M, int N, float* __restrict__ out) {
     __shared__ float part[4][64];
@@ -569,7 +97,7 @@ __global__ void colsum_kernel(const float* __restrict__ X, long ld, int M, int N
     part[rl][threadIdx.x & 63] = s;
     __syncthreads();
     if (rl == 0 && c < N) {
-        s = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+        s = sum4(part, threadIdx.x);
         unsafeAtomicAdd(out + c, s);
     }
 }
@@ -592,7 +120,7 @@ __global__ void colsum_multi_kernel(ColsumList L) {
     part[rl][threadIdx.x & 63] = s;
     __syncthreads();
     if (rl == 0 && c < N) {
-        s = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+        s = sum4(part, threadIdx.x);
         unsafeAtomicAdd(J.out + c, s);
     }
 }
@@ -780,7 +308,7 @@ __global__ void argmax_kernel(const float* __restrict__ W, long ld_w, int rows, 
         m = wave_max(m);
         int am = kAmNone;
         for (int v = lane; v < V; v += 64) am = min(am, am_key(w[v], m, v));
-        am = am_index(wave_min_i(am));
+        am = am_index(wave_min(am));
         if (lane == 0) out[(long)row * stride] = am;
     }
 }
@@ -882,269 +410,6 @@ __global__ void beat_input_grad_kernel(const float* __restrict__ s, const float*
     }
 }
 
-// Counter-based dropout mask: out = keep ? 1/(1-p) : 0, keep ~ Bernoulli(1-p).
-// splitmix64-style hash of (seed, stream offset + element index): reproducible,
-// rank-offsettable, no state.
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__global__ void dropout_mask_kernel(float* __restrict__ out, long n, float p, uint64_t seed, uint64_t offset) {
-    const float scale = 1.f / (1.f - p);
-    const uint32_t thr = (uint32_t)((double)p * 4294967296.0);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const uint64_t h = mix64(mix64(seed) ^ (offset + (uint64_t)i));
-        out[i] = ((uint32_t)(h >> 32) >= thr) ? scale : 0.f;
-    }
-}
-
-// samples[row*stride] ~ Multinomial(softmax(W[row,:]))  (decoder.py:506-509, sampling = 'multinomial'): one wavefront per
-// row, inverse-CDF draw with one counter-based uniform per row (seed, offset + row): reproducible, rank-offsettable.
-__global__ void sample_multinomial_kernel(const float* __restrict__ W, long ld_w, int rows, int V,
-                                          long long* __restrict__ out, long stride, uint64_t seed, uint64_t offset) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    for (int row = wave; row < rows; row += nwaves) {
-        const float* w = W + (long)row * ld_w;
-        float m = -INFINITY;
-        for (int v = lane; v < V; v += 64) m = fmaxf(m, w[v]);
-        m = wave_max(m);
-        float tot = 0.f;
-        for (int v = lane; v < V; v += 64) tot += expf(w[v] - m);
-        tot = wave_sum(tot);
-        const uint64_t h = mix64(mix64(seed) ^ (offset + (uint64_t)row));
-        const float target = (float)((uint32_t)(h >> 40)) * (1.f / 16777216.f) * tot;     // u in [0, 1) times the total mass
-        // `tot` was summed lane-strided and across the wave, the prefix below runs in index order: the two can differ in the last
-        // bits, so for u close to 1 no prefix need exceed the target.  The draw then is the LAST TOKEN WITH MASS (the inverse CDF at
-        // u -> 1), not index V - 1, whose mass may be zero.  (The maximum has e = 1, so there is one; a row of NaN keeps V - 1.)
-        float base = 0.f;
-        int pick, last = V - 1;
-        bool found = false;
-        for (int v0 = 0; v0 < V && !found; v0 += 64) {
-            const int v = v0 + lane;
-            const float e = v < V ? expf(w[v] - m) : 0.f;
-            const unsigned long long mass = __ballot(e > 0.f);
-            if (mass) last = v0 + 63 - __builtin_clzll(mass);
-            float incl = e;                                     // inclusive prefix sum over the 64 lanes
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const float up = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += up;
-            }
-            // e > 0: the lanes' prefixes are summed in different tree orders, so behind the last token with mass a lane's prefix can
-            // come out an ulp ABOVE its neighbour's and cross the target where no lane with mass did
-            const unsigned long long hit = __ballot(v < V && e > 0.f && base + incl > target);
-            if (hit) { pick = v0 + __ffsll((long long)hit) - 1; found = true; }
-            base += __shfl(incl, 63, 64);
-        }
-        if (!found) pick = last;
-        if (lane == 0) out[(long)row * stride] = pick;
-    }
-}
-
-// samples[row*stride] = the token sample.h's rule draws from softmax(temp * W[row,:]) with the uniform uniforms[row*u_stride] (the
-// decoder's temperature sampling outside decode_b1.hip's launch; the same rule): one wavefront per row, V <= 64 NV.  Where the rule
-// does not apply (a NaN among temp * W, a non-finite maximum or total, a uniform outside [0, 1)) the row takes argmax_first.
-template <int NV>
-__global__ void sample_temperature_kernel(const float* __restrict__ W, long ld_w, int rows, int V, float temp,
-                                          const double* __restrict__ uniforms, long u_stride, long long* __restrict__ out, long stride) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    for (int row = wave; row < rows; row += nwaves) {
-        const float* w = W + (long)row * ld_w;
-        const double u = uniforms[(long)row * u_stride];
-        float x[NV], sv[NV], m = -INFINITY, ms = -INFINITY;
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int v = lane + 64 * j;
-            x[j] = v < V ? w[v] : -INFINITY;
-            sv[j] = v < V ? x[j] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-            m = fmaxf(m, x[j]);
-            ms = fmaxf(ms, sv[j]);
-        }
-        double S;                                              // (not read: the temperature draw has no logp)
-        int tok = __ballot(nan) ? -1 : sample::pick<NV>(sv, wave_max(ms), u, V, lane, S);
-        if (tok < 0) {
-            m = wave_max(m);
-            int am = kAmNone;
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                if (lane + 64 * j < V) am = min(am, am_key(x[j], m, lane + 64 * j));
-            tok = am_index(wave_min_i(am));
-        }
-        if (lane == 0) out[(long)row * stride] = tok;
-    }
-}
-
-// The same draw behind sample.h's top-k / nucleus truncation (sample::truncate in front of sample::pick: the decoder's truncated
-// sampling outside decode_b1.hip's launch; the same rule), and logp[row*lp_stride] (nullable) = the drawn token's log-probability
-// under the truncated distribution, NaN for a row that took argmax_first.  One wavefront per row, V <= 64 NV.
-template <int NV>
-__global__ void sample_truncated_kernel(const float* __restrict__ W, long ld_w, int rows, int V, float temp,
-                                        const double* __restrict__ uniforms, long u_stride, int top_k, double top_p,
-                                        long long* __restrict__ out, long stride, float* __restrict__ logp, long lp_stride) {
-    const int lane = threadIdx.x & 63;
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    for (int row = wave; row < rows; row += nwaves) {
-        const float* w = W + (long)row * ld_w;
-        const double u = uniforms[(long)row * u_stride];
-        float x[NV], sv[NV], m = -INFINITY, ms = -INFINITY;
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int v = lane + 64 * j;
-            x[j] = v < V ? w[v] : -INFINITY;
-            sv[j] = v < V ? x[j] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-            m = fmaxf(m, x[j]);
-            ms = fmaxf(ms, sv[j]);
-        }
-        int tok = -1;
-        float lp = __builtin_nanf("");
-        if (!__ballot(nan)) {
-            ms = wave_max(ms);
-            double S;
-            sample::truncate<NV>(sv, ms, top_k, top_p, V, lane);
-            tok = sample::pick<NV>(sv, ms, u, V, lane, S);
-            if (tok >= 0) lp = sample::logp_of(sample::logp_gap<NV>(sv, ms, tok), S);
-        }
-        if (tok < 0) {
-            m = wave_max(m);
-            int am = kAmNone;
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                if (lane + 64 * j < V) am = min(am, am_key(x[j], m, lane + 64 * j));
-            tok = am_index(wave_min_i(am));
-        }
-        if (lane == 0) {
-            out[(long)row * stride] = tok;
-            if (logp) logp[(long)row * lp_stride] = lp;
-        }
-    }
-}
-
-// The truncated draw behind sample.h's per-tick token constraints (the tick-by-tick path of a constrained decoder call; the same rule):
-// allow + row * allow_stride = the row's ceil(V / 64) mask words (<= 8), read by every lane through a wave-uniform address.  An empty mask
-// counts as all ones (sample::mask_words).  A row outside the rule takes argmax_first over its ALLOWED tokens -- the banned entries count
-// as -inf and are no candidates, so the token is an allowed one whatever the logits hold -- with logp NaN.  One wavefront per row, V <= 64 NV.
-template <int NV>
-__global__ void sample_constrained_kernel(const float* __restrict__ W, long ld_w, int rows, int V, float temp,
-                                          const double* __restrict__ uniforms, long u_stride, int top_k, double top_p,
-                                          long long* __restrict__ out, long stride, float* __restrict__ logp, long lp_stride,
-                                          const unsigned long long* __restrict__ allow, long allow_stride) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    const int nw = (V + 63) / 64;
-    for (int row = wave; row < rows; row += nwaves) {
-        const float* w = W + (long)row * ld_w;
-        const double u = uniforms[(long)row * u_stride];
-        unsigned long long aw[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) aw[j] = j < nw ? allow[(long)row * allow_stride + j] : 0ull;
-        sample::mask_words<NV>(aw, V);
-        float x[NV], sv[NV], m = -INFINITY;
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int v = lane + 64 * j;
-            x[j] = v < V ? w[v] : -INFINITY;
-            sv[j] = v < V ? x[j] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-            if (!sample::allowed(aw[j], lane)) x[j] = -INFINITY;
-            m = fmaxf(m, x[j]);
-        }
-        int tok = -1;
-        float lp = __builtin_nanf("");
-        if (!__ballot(nan)) {
-            const float ms = wave_max(sample::mask_scores<NV>(sv, aw, lane));
-            double S;
-            sample::truncate<NV>(sv, ms, top_k, top_p, V, lane);
-            tok = sample::pick<NV>(sv, ms, u, V, lane, S);
-            if (tok >= 0) lp = sample::logp_of(sample::logp_gap<NV>(sv, ms, tok), S);
-        }
-        if (tok < 0) {
-            m = wave_max(m);
-            int am = kAmNone;
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                if (sample::allowed(aw[j], lane)) am = min(am, am_key(x[j], m, lane + 64 * j));
-            tok = am_index(wave_min_i(am));
-        }
-        if (lane == 0) {
-            out[(long)row * stride] = tok;
-            if (logp) logp[(long)row * lp_stride] = lp;
-        }
-    }
-}
-
-// The constrained draw behind sample.h's forced tokens (the tick-by-tick path of a forced decoder call; the same rule): forced[row *
-// forced_stride] = the row's forced token, a value outside [0, V) = a free row, which is sample_constrained_kernel's row.  A forced row runs
-// the same mask, truncation and pick (u = 0.0, for the kept total S alone), returns f whatever the mask, the truncation or the logits hold,
-// and reports logp = (s_f - m) - log S: -inf where f is banned or truncated away, NaN where the rule does not apply.  A null `allow` counts
-// as all ones.  One wavefront per row, V <= 64 NV.
-template <int NV>
-__global__ void sample_forced_kernel(const float* __restrict__ W, long ld_w, int rows, int V, float temp,
-                                     const double* __restrict__ uniforms, long u_stride, int top_k, double top_p,
-                                     long long* __restrict__ out, long stride, float* __restrict__ logp, long lp_stride,
-                                     const unsigned long long* __restrict__ allow, long allow_stride,
-                                     const int* __restrict__ forced, long forced_stride) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    const int nw = (V + 63) / 64;
-    for (int row = wave; row < rows; row += nwaves) {
-        const float* w = W + (long)row * ld_w;
-        const int f = forced[(long)row * forced_stride];
-        const bool isf = sample::is_forced(f, V);
-        const double u = isf ? 0.0 : uniforms[(long)row * u_stride];
-        unsigned long long aw[NV];
-#pragma unroll
-        for (int j = 0; j < NV; ++j) aw[j] = j < nw ? (allow ? allow[(long)row * allow_stride + j] : ~0ull) : 0ull;
-        sample::mask_words<NV>(aw, V);
-        float x[NV], sv[NV], m = -INFINITY;
-        bool nan = false;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int v = lane + 64 * j;
-            x[j] = v < V ? w[v] : -INFINITY;
-            sv[j] = v < V ? x[j] * temp : -INFINITY;
-            nan |= sv[j] != sv[j];
-            if (!sample::allowed(aw[j], lane)) x[j] = -INFINITY;
-            m = fmaxf(m, x[j]);
-        }
-        int tok = -1;
-        float lp = __builtin_nanf("");
-        if (!__ballot(nan)) {
-            const float ms = wave_max(sample::mask_scores<NV>(sv, aw, lane));
-            double S;
-            sample::truncate<NV>(sv, ms, top_k, top_p, V, lane);
-            tok = sample::pick<NV>(sv, ms, u, V, lane, S);
-            if (tok >= 0) lp = sample::logp_of(sample::logp_gap<NV>(sv, ms, isf ? f : tok), S);
-        }
-        if (isf) tok = f;
-        if (tok < 0) {
-            m = wave_max(m);
-            int am = kAmNone;
-#pragma unroll
-            for (int j = 0; j < NV; ++j)
-                if (sample::allowed(aw[j], lane)) am = min(am, am_key(x[j], m, lane + 64 * j));
-            tok = am_index(wave_min_i(am));
-        }
-        if (lane == 0) {
-            out[(long)row * stride] = tok;
-            if (logp) logp[(long)row * lp_stride] = lp;
-        }
-    }
-}
-
 __global__ void scale_kernel(float* __restrict__ x, long n, float a) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] *= a;
 }
@@ -1192,14 +457,6 @@ __global__ void split_measures_kernel(const int* __restrict__ score, int B, int 
     }
 }
 
-inline int grid_for(long n, int block = 256, int cap = 2048) {
-    long g = (n + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (int)g;
-}
-inline int ok() { return hipGetLastError() == hipSuccess ? 0 : -2; }
-
 }  // namespace
 
 int pw_transpose(const float* in, long ld_in, float* out, long ld_out, int rows, int cols, hipStream_t s) {
@@ -1224,123 +481,6 @@ int pw_pack_frag_multi(const float* const* ins, float* const* outs, int n, long 
     dim3 grid(grid_for(slots, 256, 1024), n);
     hipLaunchKernelGGL(pack_frag_multi_kernel, grid, dim3(256), 0, s, pl, ld, R, K, transposed);
     return ok();
-}
-int pw_cross_entropy(const float* W, long ld_w, int rows, int V, const long long* tgt, float* dW, long ld_dw,
-                     float scale, float out_scale, float* loss_sum, float* correct, hipStream_t s, const float* scale_dev,
-                     const float* add_term, float add_scale, float* fwd_out, float fwd_scale) {
-    // blocks: every block ends with one atomic pair on the same two words, and those serialise (~20 ns each): 2048 blocks (one row
-    // per wave) measured 77 us for the loss glue of the B = 256 step, 512 blocks 54 us with the forward launch at 18.7 us against
-    // 6.2 for the backward launch that has no sums (profiles/r06_p_timeline_full_step.txt).  With sums: 128 blocks (12 rows per
-    // wave at 6144 rows); without (the backward launch): as many as there are rows to go round
-    const int g = grid_for((long)rows * 64, 256, (loss_sum || correct) ? 128 : 512);
-    hipLaunchKernelGGL(ce_kernel, dim3(g), dim3(256), 0, s, W, ld_w, rows, V, tgt, dW, ld_dw, scale, out_scale, loss_sum,
-                       correct, scale_dev, add_term, add_scale, fwd_out, fwd_scale);
-    return ok();
-}
-int pw_reparam_kl(const float* mu, const float* ls, const float* eps, float* z, float* sigma, long n, float* kl_sum,
-                  hipStream_t s) {
-    hipLaunchKernelGGL(reparam_kl_kernel, dim3(grid_for(n, 256, kl_sum ? 64 : 512)), dim3(256), 0, s, mu, ls, eps, z, sigma, n, kl_sum);
-    return ok();
-}
-int pw_latent_bwd(const float* dz, const float* mu, const float* ls, const float* eps, float kscale, const float* kdev,
-                  float* dmu, float* dls, long n, hipStream_t s) {
-    hipLaunchKernelGGL(latent_bwd_kernel, dim3(grid_for(n, 256, 512)), dim3(256), 0, s, dz, mu, ls, eps, kscale, kdev, dmu,
-                       dls, n);
-    return ok();
-}
-// the 'dim' forward's grid, a function of rows alone: the order of a column's sum depends on nothing else
-static int fb_dim_grid(long rows) { return (int)std::min<long>((rows + 3) / 4, kFbDimGrid); }
-static bool fb_vec4(int Z, std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = (uintptr_t)(Z & 3);
-    for (const void* p : ptrs) bits |= (uintptr_t)p & 15;          // (a null pointer is aligned)
-    return bits == 0;
-}
-long pw_reparam_kl_fb_ws_bytes(long rows, int Z, int per) {
-    if (rows <= 0 || Z <= 0 || (per != 0 && per != 1)) return -1;
-    return per == 1 ? (long)fb_dim_grid(rows) * Z * (long)sizeof(float) : 0;
-}
-int pw_reparam_kl_fb(const float* mu, const float* ls, const float* eps, float* z, long rows, int Z, float free_nats, int per,
-                     float* parts, float* keep, float* kl_sum, float* kl_raw, void* ws, long ws_bytes, hipStream_t s) {
-    const long need = pw_reparam_kl_fb_ws_bytes(rows, Z, per);
-    if (need < 0 || ws_bytes < need || (need > 0 && !ws)) return -1;
-    const bool v4 = fb_vec4(Z, {mu, ls, eps, z});
-    const double bytes = 4.0 * (double)rows * Z * (2 + (eps ? 1 : 0) + (z ? 1 : 0));
-    const float thr = per == 0 ? free_nats : (float)((double)rows * (double)free_nats);       // 'dim': B * lambda, rounded once
-    const int G = fb_dim_grid(rows);
-    if (per == 0) {
-        ProfScope prof(PROF_HBM, 0.0, s, "reparam_kl_fb_measure", bytes + 4.0 * (double)rows);
-        const dim3 grid(grid_for(rows * 64, 256, kFbMeasureGrid));
-        if (v4) hipLaunchKernelGGL(reparam_kl_fb_measure_kernel<4>, grid, dim3(256), 0, s, mu, ls, eps, z, rows, Z, parts);
-        else    hipLaunchKernelGGL(reparam_kl_fb_measure_kernel<1>, grid, dim3(256), 0, s, mu, ls, eps, z, rows, Z, parts);
-    } else {
-        ProfScope prof(PROF_HBM, 0.0, s, "reparam_kl_fb_dim", bytes + 4.0 * (double)G * Z);
-        if (v4) hipLaunchKernelGGL(reparam_kl_fb_dim_kernel<4>, dim3(G), dim3(256), 0, s, mu, ls, eps, z, rows, Z, (float*)ws);
-        else    hipLaunchKernelGGL(reparam_kl_fb_dim_kernel<1>, dim3(G), dim3(256), 0, s, mu, ls, eps, z, rows, Z, (float*)ws);
-    }
-    if (ok() != 0) return -2;
-    const long nparts = per == 0 ? rows : (long)Z;
-    ProfScope prof(PROF_HBM, 0.0, s, "reparam_kl_fb_finish", (per == 0 ? 4.0 : 4.0 * G + 4.0) * (double)nparts + 4.0 * (double)nparts);
-    hipLaunchKernelGGL(reparam_kl_fb_finish_kernel, dim3(1), dim3(kFbFinishBlock), 0, s, per == 0 ? (const float*)nullptr : (const float*)ws, G,
-                       nparts, thr, parts, keep, kl_sum, kl_raw);
-    return ok();
-}
-int pw_latent_bwd_fb(const float* dz, const float* mu, const float* ls, const float* eps, float kscale, const float* kdev,
-                     const float* keep, int per, float* dmu, float* dls, long rows, int Z, hipStream_t s) {
-    const long n = rows * Z;
-    ProfScope prof(PROF_HBM, 0.0, s, "latent_bwd_fb", 4.0 * (double)n * (4 + (dz ? 1 : 0) + (eps ? 1 : 0)));
-    hipLaunchKernelGGL(latent_bwd_fb_kernel, dim3(grid_for(n, 256, 512)), dim3(256), 0, s, dz, mu, ls, eps, kscale, kdev, keep, per,
-                       dmu, dls, rows, Z);
-    return ok();
-}
-int pw_sqnorm_parts() { return kSqnormParts; }
-int pw_grad_sqnorm(const float* g, long n, double* partials, hipStream_t s) {
-    ProfScope prof(PROF_HBM, 0.0, s, "grad_sqnorm", 4.0 * (double)n);         // one read of the arena
-    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(kSqnormParts), dim3(kSqnormBlock), 0, s, g, n, partials);
-    return ok();
-}
-template <bool EMA, bool MASK>
-static void launch_adam_step(const PwAdamStep& a, float lr_over_bc1, float inv_sqrt_bc2, float decay, float omd, hipStream_t s) {
-    hipLaunchKernelGGL((adamw_kernel<EMA, MASK>), dim3(grid_for(a.n / 4 + 1, 256, 4096)), dim3(kSqnormBlock), 0, s, a.p, a.g, a.m, a.v,
-                       a.n, lr_over_bc1, inv_sqrt_bc2, a.b1, a.b2, a.eps, a.gscale, a.max_norm, a.partials, decay, a.mask, a.ema,
-                       a.ema_decay, omd, (const unsigned*)chain_dev_status(), a.step_flag, a.report);
-}
-int pw_adam_step(const PwAdamStep& a, hipStream_t s) {
-    const double bc1 = 1.0 - pow((double)a.b1, a.step), bc2 = 1.0 - pow((double)a.b2, a.step);
-    // the factors of the rule, rounded ONCE here: what the kernel multiplies by does not depend on how it was compiled
-    const float l1 = (float)(a.lr / bc1), is2 = (float)(1.0 / sqrt(bc2));
-    const float decay = (float)(1.0 - (double)a.lr * (double)a.weight_decay), omd = (float)(1.0 - (double)a.ema_decay);
-    // the label says what the launch does: "w" with decay or an EMA, "_clip" behind the partials
-    const bool w = a.weight_decay > 0.f || a.ema;
-    // read p,g,m,v; write p,m,v + a bit per element of the mask + one read and one write of the EMA arena + the partials
-    ProfScope prof(PROF_HBM, 0.0, s, w ? (a.partials ? "adamw_clip" : "adamw") : (a.partials ? "adam_clip" : "adam"),
-                   28.0 * (double)a.n + (a.mask ? (double)a.n / 8.0 : 0.0) + (a.ema ? 8.0 * (double)a.n : 0.0) +
-                       (a.partials ? 8.0 * kSqnormParts : 0.0));
-    if (a.ema) { if (a.mask) launch_adam_step<true, true>(a, l1, is2, decay, omd, s); else launch_adam_step<true, false>(a, l1, is2, decay, omd, s); }
-    else       { if (a.mask) launch_adam_step<false, true>(a, l1, is2, decay, omd, s); else launch_adam_step<false, false>(a, l1, is2, decay, omd, s); }
-    return ok();
-}
-int pw_step_flag_export(float* dst, hipStream_t s) {
-    hipLaunchKernelGGL(step_flag_export_kernel, dim3(1), dim3(64), 0, s, (const unsigned*)chain_dev_status(),
-                       (const unsigned*)token_host_status(), dst);
-    return ok();
-}
-
-// sums[0..2] += (loss, accuracy, 1) unless a chain launch of this process has timed out since the last reset: the statistics of
-// steps whose results are not valid (and that the optimizer kernel skipped) stay out of the epoch means
-__global__ void epoch_stats_add_kernel(float* sums, const float* loss, const float* acc, const unsigned* abort_word,
-                                       const float* step_flag) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    // the same decision as the optimizer kernel of the step (adamw_kernel): the ranks' summed flag if the caller has one
-    if (step_flag ? (*step_flag != 0.f)
-                  : (abort_word && __hip_atomic_load(abort_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) return;
-    sums[0] += loss[0];
-    if (acc) sums[1] += acc[0];
-    sums[2] += 1.f;
-}
-int pw_epoch_stats_add(float* sums, const float* loss, const float* acc, hipStream_t s, const float* step_flag) {
-    hipLaunchKernelGGL(epoch_stats_add_kernel, dim3(1), dim3(64), 0, s, sums, loss, acc, (const unsigned*)chain_dev_status(),
-                       step_flag);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 int pw_colsum(const float* X, long ld, int M, int N, float* out, hipStream_t s) {
     int gy = (M + 255) / 256;
@@ -1466,43 +606,6 @@ int pw_beat_input_grad(const float* sv, const float* w, long incw, const float* 
     hipLaunchKernelGGL(rowdot_partials_kernel, dim3(kB0Parts), dim3(256), 0, s, X, ld, M, n, w, incw, partial);
     hipLaunchKernelGGL(beat_input_grad_kernel, dim3(grid_for(n)), dim3(256), 0, s, sv, w, incw, b0, dw, db0, n,
                        (const float*)partial);
-    return ok();
-}
-int pw_dropout_mask(float* out, long n, float p, uint64_t seed, uint64_t offset, hipStream_t s) {
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3(grid_for(n)), dim3(256), 0, s, out, n, p, seed, offset);
-    return ok();
-}
-int pw_sample_multinomial(const float* W, long ld_w, int rows, int V, long long* out, long stride, uint64_t seed,
-                          uint64_t offset, hipStream_t s) {
-    hipLaunchKernelGGL(sample_multinomial_kernel, dim3(grid_for((long)rows * 64, 256, 1024)), dim3(256), 0, s, W, ld_w, rows, V,
-                       out, stride, seed, offset);
-    return ok();
-}
-int pw_sample(const float* W, long ld_w, int rows, int V, long long* out, long stride, const sample::Request& r, int floor_level,
-              hipStream_t s) {
-    if (!r.uniforms || r.logits || !r.ok(V)) return -1;
-    const int level = std::max(std::min(floor_level, 2), r.level(V));      // (a floor above 2 would read a null mask or forced array)
-    char label[48];
-    if (level == 1) std::snprintf(label, sizeof label, "sample_temperature B%d V%d", rows, V);
-    else std::snprintf(label, sizeof label, "%ssample B%d V%d", sample::prefix(level), rows, V);
-    // per row: the logits, the uniform and the token; from level 2 the log-probability, the mask words where given, at level 4 the forced word
-    ProfScope prof(PROF_HBM, 0.0, s, label, (double)rows * (4.0 * V + 16.0 + (level >= 2 ? 4.0 : 0.0) + (level >= 4 ? 4.0 : 0.0) +
-                                                            (r.allow ? 8.0 * sample::Request::words(V) : 0.0)));
-    const dim3 grid(grid_for((long)rows * 64, 256, 1024));
-    const float temp = r.temperature;
-#define PW_ST(NV)                                                                                                                         \
-    do { switch (level) {                                                                                                                 \
-        case 1: hipLaunchKernelGGL(sample_temperature_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u, out,   \
-                                   stride); break;                                                                                        \
-        case 2: hipLaunchKernelGGL(sample_truncated_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u, r.top_k, \
-                                   r.top_p, out, stride, r.logp, r.ld_logp); break;                                                       \
-        case 3: hipLaunchKernelGGL(sample_constrained_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u,       \
-                                   r.top_k, r.top_p, out, stride, r.logp, r.ld_logp, r.allow, r.ld_allow); break;                         \
-        default: hipLaunchKernelGGL(sample_forced_kernel<NV>, grid, dim3(256), 0, s, W, ld_w, rows, V, temp, r.uniforms, r.ld_u, r.top_k,  \
-                                    r.top_p, out, stride, r.logp, r.ld_logp, r.allow, r.ld_allow, r.forced, r.ld_forced);                 \
-    } } while (0)
-    if (V <= 64) PW_ST(1); else if (V <= 128) PW_ST(2); else if (V <= 256) PW_ST(4); else PW_ST(8);
-#undef PW_ST
     return ok();
 }
 int pw_scale(float* x, long n, float a, hipStream_t s) {

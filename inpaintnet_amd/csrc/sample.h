@@ -6,11 +6,12 @@
 // token = the first v with prefix_v > u * S, S = the total, by ballot and ctz.  The result is wave-uniform.
 // Below, in this order: pick(), truncate(), the mask and forced-token helpers, draw() -- the device rule of one (row, tick), one build per
 // level -- and, host side, Request: what a CALL asks of the draw, carried as one value from the C-ABI entries to the launch sites of
-// vae.hip, decode_b1.hip, arnn_gen.hip and pointwise.hip.
+// vae.hip, decode_b1.hip, arnn_gen.hip and sample_rows.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "common.h"
+#include "reduce.h"
 
 namespace sample {
 
@@ -242,7 +243,7 @@ __device__ __forceinline__ float logp_of(float gap, double S) { return (float)((
 //  (level 3 up; below it any array), f = the tick's forced word (level 4).
 //  -> the token; gap = s_tok - m (logp_gap()); S = the kept total.  Where the rule does not apply: -1, gap NaN and S = 1 -- the caller
 //  then takes ITS argmax rule (they differ: the decode kernel's padding -1, AnticipationRNN's NaN-aware order over the allowed entries,
-//  pointwise.hip's am_key).  A forced tick returns f, never -1, with gap NaN and S = 1 where the rule does not apply.
+//  reduce.h's am_key in sample_rows.hip).  A forced tick returns f, never -1, with gap NaN and S = 1 where the rule does not apply.
 // s_v = T x_v is ONE rounded f32 product that the NaN test and expf(s_v - m) both read.
 template <int NV, int LEVEL, int NA>
 __device__ __forceinline__ int draw(const float (&x)[NV], float temp, double u, int V, int lane, int top_k, double top_p,

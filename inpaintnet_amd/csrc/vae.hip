@@ -18,6 +18,7 @@
 #include "vae.h"
 #include "decode_chain.h"
 #include "sample.h"
+#include "sample_rows.h"
 #include <cstdlib>
 #include <string>
 

@@ -42,7 +42,7 @@ EXP_U = 4                      # expf: 2 ulp allowed = 4 u
 ELEM_U = 12
 PER = ("measure", "dim")
 
-# the launchers' constants (csrc/pointwise.hip): the 'measure' forward caps its grid at MEASURE_GRID workgroups of 4 waves, one wave per
+# the launchers' constants (csrc/latent.hip): the 'measure' forward caps its grid at MEASURE_GRID workgroups of 4 waves, one wave per
 # row: MEASURE_PASS rows per pass of the grid; the 'dim' forward at DIM_GRID workgroups of 4 row-lanes: DIM_PASS rows per pass
 MEASURE_GRID, DIM_GRID = 256, 128
 MEASURE_PASS, DIM_PASS = 4 * MEASURE_GRID, 4 * DIM_GRID

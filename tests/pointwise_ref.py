@@ -1,4 +1,4 @@
-"""Plain references for the helper kernels of csrc/pointwise.hip, shared by tests/test_pointwise_host.py (CPU) and
+"""Plain references for the helper kernels of csrc/pointwise.hip, ce.hip, latent.hip, optim.hip and sample_rows.hip, shared by tests/test_pointwise_host.py (CPU) and
 tests/test_gpu_pointwise.py (GPU): the counter-based generator mirrored in numpy uint64, everything else in float64.
 
 Nothing here imports the library: a reference that called the code under test would prove nothing."""
@@ -17,7 +17,7 @@ def _u64(x):
 
 
 def mix64(x):
-    """csrc/pointwise.hip mix64 (the splitmix64 finaliser) on uint64 scalars or arrays; wraps modulo 2^64."""
+    """csrc/sample_rows.hip mix64 (the splitmix64 finaliser) on uint64 scalars or arrays; wraps modulo 2^64."""
     with np.errstate(over="ignore"):
         x = _u64(x) + _U64(0x9E3779B97F4A7C15)
         x = (x ^ (x >> _U64(30))) * _U64(0xBF58476D1CE4E5B9)

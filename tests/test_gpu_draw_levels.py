@@ -1,5 +1,5 @@
 """The levels of csrc/sample.h's draw against one another, through inet_sample_temperature / _truncated / _constrained / _forced
-(csrc/pointwise.hip: sample_temperature_kernel, sample_truncated_kernel, sample_constrained_kernel and sample_forced_kernel, one kernel
+(csrc/sample_rows.hip: sample_temperature_kernel, sample_truncated_kernel, sample_constrained_kernel and sample_forced_kernel, one kernel
 per level): a level whose own step is switched off by its arguments returns the level below
 bit for bit --
     level 4 with `forced` all -1                      = level 3,

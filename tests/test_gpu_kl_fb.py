@@ -1,4 +1,4 @@
-"""The free-bits kernels alone (csrc/pointwise.hip: reparam_kl_fb_measure / _dim / _finish, latent_bwd_fb) through
+"""The free-bits kernels alone (csrc/latent.hip: reparam_kl_fb_measure / _dim / _finish, latent_bwd_fb) through
 ops.reparam_kl_fb / ops.latent_bwd_fb, both modes, against the float64 restatement and the bounds derived in tests/kl_fb_ref.py.
 
 Shapes: the ones the kernels can go wrong at -- one element, one row, widths around the 64-lane wave and off the 16-byte path, more

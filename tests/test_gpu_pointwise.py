@@ -1,4 +1,4 @@
-"""The helper kernels of csrc/pointwise.hip and the small entry points in front of them, each alone through the C-ABI and at its
+"""The helper kernels of csrc/pointwise.hip, ce.hip (ce_kernel), latent.hip, optim.hip and sample_rows.hip and the small entry points in front of them, each alone through the C-ABI and at its
 edges: vocabulary widths around the 64-lane wave, one row more than the resident waves, strided operands with poisoned padding,
 ties, NaN and infinities, null optional outputs, the tail of the float4 loops, both paths of the embedding gradient.
 

@@ -87,8 +87,8 @@ def test_gpu_cases_keep_every_part_off_its_threshold(shape, per):
 
 def test_depth_restates_the_launch_constants():
     """kl_fb_ref.depth() and SHAPES' last row count are derived from the launchers' grid caps: the constants here and in
-    csrc/pointwise.hip must be the same numbers."""
-    src = open(os.path.join(ROOT, "inpaintnet_amd", "csrc", "pointwise.hip")).read()
+    csrc/latent.hip must be the same numbers."""
+    src = open(os.path.join(ROOT, "inpaintnet_amd", "csrc", "latent.hip")).read()
     assert int(re.search(r"constexpr int kFbMeasureGrid = (\d+);", src).group(1)) == K.MEASURE_GRID
     assert int(re.search(r"constexpr int kFbDimGrid = (\d+);", src).group(1)) == K.DIM_GRID
     rows = K.SHAPES[-1][0]

@@ -42,6 +42,32 @@ def test_kernel_handles_are_collected_without_a_gpu(L):
         assert L.inet_preload() == -2
 
 
+# Files under csrc/ other than reduce.h that may still spell a 64-lane xor butterfly of their own, and why (reduce.h's head comment and
+# DESIGN.md section 29 name them too).  Nothing but reduce.h may define am_key.
+BUTTERFLY_EXCEPTIONS = [
+    ("arnn_gen.hip", "argmax_wave: a value and its index travel through the butterfly together, compared by argmax_better"),
+    ("gemm.hip", "gemv_rows_kernel: the same order, but calling wave_sum there changes the kernel's assembly; the call site kept its form"),
+]
+
+
+def test_reduction_orders_are_stated_once():
+    """The 'same bits from call to call' promises of the helper kernels rest on ONE order -- the xor butterfly over a wave's 64 lanes,
+    then the four waves in wave order -- and on one argmax_first key.  Both are written in csrc/reduce.h and nowhere else: a second
+    copy is a second order that nothing but eyesight would hold to the first."""
+    csrc = os.path.join(REPO, "inpaintnet_amd", "csrc")
+    butterfly = re.compile(r"for \(int (\w+) = 32; \1 > 0; \1 >>= 1\)[^;]*?__shfl_xor\([^;]*, 64\)")
+    am_key = re.compile(r"\bint\s+\w*am_key\s*\(")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert "reduce.h" in files
+    found = {f: (len(butterfly.findall(open(os.path.join(csrc, f)).read())), len(am_key.findall(open(os.path.join(csrc, f)).read())))
+             for f in files}
+    assert found["reduce.h"] == (4, 1)           # wave_sum<T>, wave_max(float), wave_max(double), wave_min(int); am_key
+    allowed = {f for f, _ in BUTTERFLY_EXCEPTIONS}
+    assert allowed <= set(files) and all(found[f][0] == 1 for f in allowed)         # an exception that has gone leaves the list
+    assert {f for f, (b, k) in found.items() if b and f != "reduce.h"} == allowed
+    assert [f for f, (b, k) in found.items() if k] == ["reduce.h"]
+
+
 def _entries(cfg, count_fn, info_fn):
     n = count_fn(C.byref(cfg))
     out = []

@@ -4,7 +4,8 @@
 --ref REV compiles the same files as of that revision next to the working tree and prints only the kernels whose numbers moved.
 --ref REV --asm compares the gfx950 assembly of the two instead: a host-only change must leave it identical.  Per file the whole-file
 verdict, then per kernel (matched by symbol across ALL the files given, so a kernel may change files): identical | identical, moved
-a.hip -> b.hip | DIFFERS | only in REV | only in tree."""
+a.hip -> b.hip | DIFFERS | only in REV | only in tree.  A file that exists on one side only counts as an empty kernel set there; the last
+line counts the symbols of both sides."""
 import os
 import re
 import subprocess
@@ -42,12 +43,12 @@ def device_asm(src, incdir):
 
 
 def functions(lines):
-    """{symbol: its lines from `.globl SYM` to `.Lfunc_endN:`} without the function's index in its file (block labels, func_begin / end) and the file's count of long branches (post_getpc)"""
+    """{symbol: its lines from `.globl SYM` / `.protected SYM` to `.Lfunc_endN:`} without the function's index in its file (block labels, func_begin / end) and the file's count of long branches (post_getpc)"""
     out, sym = {}, None
     for l in lines:
-        m = re.match(r"\s*\.globl\s+(\S+).*-- Begin function", l)
+        m = re.match(r"\s*\.(globl|protected)\s+(\S+).*-- Begin function", l)      # (.protected leads where the kernel has external linkage)
         if m:
-            sym = m.group(1)
+            sym = m.group(2)
             out[sym] = []
         if sym is not None:
             l = re.sub(r"\.L(func_begin|func_end|post_getpc)\d+", r".L\1", re.sub(r"BB\d+_", "BB_", l))
@@ -66,8 +67,10 @@ def compare_asm(srcs, ref):
     with tempfile.TemporaryDirectory() as tmp:
         subprocess.check_call(f"git -C {REPO} archive {ref} inpaintnet_amd/csrc include | tar -x -C {tmp}", shell=True)
         old_dir = os.path.join(tmp, "inpaintnet_amd", "csrc")
-        old = {os.path.basename(src): device_asm(os.path.join(old_dir, os.path.basename(src)), old_dir) for src in srcs}
-    new = {os.path.basename(src): device_asm(src, CSRC) for src in srcs}
+        # a file that exists on one side only (a kernel's new or former home) is an empty kernel set on the other
+        old = {os.path.basename(src): device_asm(os.path.join(old_dir, os.path.basename(src)), old_dir)
+               if os.path.exists(os.path.join(old_dir, os.path.basename(src))) else [] for src in srcs}
+    new = {os.path.basename(src): device_asm(src, CSRC) if os.path.exists(src) else [] for src in srcs}
     where = [{}, {}]                                            # symbol -> (file, lines), in REV and in the tree
     for side, files in zip(where, (old, new)):
         for f, lines in files.items():
@@ -75,13 +78,15 @@ def compare_asm(srcs, ref):
     for f in new:
         o, n = old[f], new[f]
         first = next((i + 1 for i, (a, b) in enumerate(zip(o, n)) if a != b), None if len(o) == len(n) else min(len(o), len(n)) + 1)
-        print(f"{f}: device code " + (f"identical to {ref} ({len(n)} lines)" if first is None else
+        print(f"{f}: device code " + (f"only in the tree ({len(n)} lines)" if not o else f"only in {ref} ({len(o)} lines)" if not n else
+                                      f"identical to {ref} ({len(n)} lines)" if first is None else
                                       f"DIFFERS from {ref} (first at line {first}; {len(o)} -> {len(n)} lines)"))
         for sym in sorted(s for side in where for s, (g, _) in side.items() if g == f and (side is where[1] or s not in where[1])):
             (fo, bo), (fn, bn) = where[0].get(sym, (None, None)), where[1].get(sym, (None, None))
             verdict = ("only in tree" if fo is None else f"only in {ref}" if fn is None else "DIFFERS" if bo != bn else
                        "identical" if fo == fn else f"identical, moved {fo} -> {fn}")
             print(f"    {pretty(sym)}: {verdict}")
+    print(f"{len(where[0])} kernels in {ref}, {len(where[1])} in the tree")
 
 
 def fmt(r):
